@@ -12,13 +12,20 @@ touched the GPU, and exits with the child's code (a process that has initialised
 `--dry-run` replaces the engine by a stub and RCCL by gloo: the launcher / barrier / gather / JSON plumbing runs on a
 CPU-only box (tests/test_bench_launcher.py); its line carries "dry_run": true and is not a measurement.
 
-The timed region is repeated `--windows` times (default 5), each window = EXACTLY K steps bracketed by barrier +
-synchronize on both sides, max over ranks; `value` / `ms_per_step` are the MEDIAN window, `windows` lists them all.
+The timed region is repeated `--windows` times (default 1; 5 with --full), each window = EXACTLY K steps bracketed by
+barrier + synchronize on both sides, max over ranks; `value` / `ms_per_step` are the MEDIAN window, `windows` lists them all.
+So a plain `--steps K --warmup W` run times exactly K steps after W untimed ones.
 
-Prints ONE JSON line on rank 0 (contract in the task statement). `value` / `ms_per_step` / `roofline` are the
+Prints ONE JSON line on rank 0. `value` / `ms_per_step` / `roofline` are the
 REFERENCE GRAPH: the joint model runs as its three steps (avgpool kernel, dense 6032 x 6032, head; layers.py:233-238,
 257-263), 280.3 MFLOP/site of which 244.0 are executed (layer 0's embedding product is a table lookup).
-Extra objects:
+
+`--dump-outputs DIR` writes what the timed path handed back in its last step (act f32[512, 2], pred as float32[512]) to
+DIR/act.npy and DIR/pred.npy (ranks r > 0 of a multi-GPU run: act_rank<r>.npy, pred_rank<r>.npy). Weights and inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+
+A plain run does only what the headline needs: set up, warm up, time, dump, print. The extra objects below are computed
+with `--full` only (the `--no-*` options leave single ones out of a --full run):
   roofline            the dominant kernel's achieved TFLOP/s (algorithmic 2*M*N*K per launch / HIP-event duration per
                       launch) against the fp32 MFMA peak; fc_path = MFMA utilisation of the dense 6032 x 6032 GEMM,
                       conv_path = HBM GB/s of the signal model's kernels (the two figures the north star names)
@@ -455,6 +462,14 @@ def bf16x3_leg(Engine, w, torch, make_step, timed_windows, local_rank, slots, ls
     return out
 
 
+def dump_outputs(out_dir, act, pred, suffix=""):
+    """--dump-outputs: the last timed step's results as the caller receives them (sigmoid outputs, labels), float32 .npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "act%s.npy" % suffix), np.ascontiguousarray(act, dtype=np.float32))
+    np.save(os.path.join(out_dir, "pred%s.npy" % suffix), np.ascontiguousarray(pred, dtype=np.float32))
+
+
 def np_tile(a, n, off):
     """n rows of `a` starting at row `off`, wrapping around (contiguous copy)."""
     import numpy as np
@@ -590,7 +605,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=5, help="repetitions of the timed K-step window (median reported)")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="repetitions of the timed K-step window (median reported); default 1, 5 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel / roofline passes, host-path, folded-engine, "
+                         "bf16x3, configs[2] and CPU-baseline legs, and for N > 1 the sharded TSV route (the --no-* options "
+                         "below leave single legs out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/act.npy and DIR/pred.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile-pass", action="store_true")
     ap.add_argument("--no-standalone-pass", action="store_true",
@@ -615,6 +637,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / collective / JSON plumbing only (stub engine, gloo, CPU): NOT a measurement")
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))            # fresh child ranks; this parent never touched the GPU
@@ -737,6 +761,10 @@ def main():
     windows = timed_windows(eng, args.windows)
     assert bool(torch.isfinite(out_act).all())
     elapsed = sorted(windows)[len(windows) // 2]          # median window
+    if args.dump_outputs:
+        last = max(K, 1) - 1                              # step i writes slot i: the last timed step's results
+        dump_outputs(args.dump_outputs, out_act[last].cpu().numpy(), out_pred[last].cpu().numpy(),
+                     "" if rank == 0 else "_rank%d" % rank)
 
     result = {
         "metric": "CpG sites/sec (batch=512, k=17, sig=360)",
@@ -757,8 +785,8 @@ def main():
                     "boundary": "inputs resident in HBM: ds_forward_device, K forwards issued back to back over the engine's slots (up to 8 in "
                                 "flight), barrier + synchronize on both sides; a window carries ONE pipeline fill and drain (about one step): "
                                 "~4 % of a 20-step window, 0.2 % of a 400-step one -- the same library reads 406 - 409 k sites/s with --steps 20 "
-                                "and 415 - 418 k with the default 400 on one box (profiles/r06_item3_r04_vs_head.json). The host-inclusive "
-                                "rates ride along in pcie_inclusive / ds_forward_blocking / e2e_tsv"},
+                                "and 415 - 418 k with the default 400 on one box (profiles/r06_item3_r04_vs_head.json). With --full the "
+                                "host-inclusive rates ride along in pcie_inclusive / ds_forward_blocking / e2e_tsv"},
     }
     if not args.dry_run and _engine_mod.LIBRARY_OVERRIDE:
         result["library_override"] = _engine_mod.LIBRARY_OVERRIDE       # DS_HIP_LIBRARY was set: NOT the in-tree product library
@@ -778,7 +806,7 @@ def main():
         return
 
     step = make_step(eng)
-    if rank == 0 and not args.no_profile_pass:
+    if rank == 0 and args.full and not args.no_profile_pass:
         # HIP events on the engine's own streams, eager replay of the same K steps.
         # pass A (mode 2, one pair per launch): per-stage breakdown
         KP = min(K, 50)                   # replayed steps per event pass
@@ -873,7 +901,7 @@ def main():
                                           if k["name"] in alone else None}
                              for k in ks}
         result["stages_us_per_step"] = stages
-    solo = rank == 0 and world == 1 and not launched
+    solo = args.full and rank == 0 and world == 1 and not launched      # the one-GPU legs beside the headline: --full only
     if solo and not args.no_host_path:
         result["pcie_inclusive"] = pcie_inclusive(eng, feats, max(K, 64), BATCH)
         result["ds_forward_blocking"] = forward_blocking(eng, feats, BATCH)
@@ -904,7 +932,7 @@ def main():
         result["fast_mode_folded"] = fm
         engf.close()
     eng.close()
-    if dist is not None and not args.no_host_path:
+    if dist is not None and args.full and not args.no_host_path:
         # the product's multi-GPU route: every rank takes part (collectives inside), rank 0 reports. Also with ONE rank under the
         # launcher, so that the leg's RCCL calls have run on a GPU box before a multi-GPU node ever sees them (tests/test_gpu_rccl.py).
         # A failure here must not take the headline down with it: it is caught on the rank it happens on and reported as text (a

@@ -113,7 +113,7 @@ def test_bench_timed_windows_across_two_ranks_on_one_gpu(tmp_path):
     inside every window), both engines on GPU 0, collectives on gloo (--backend gloo --share-gpu): one JSON line, both
     ranks' window times in it, 2 x K x 512 sites gathered per window."""
     res, dt = _launch(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--windows", "3",
-                          "--no-profile-pass", "--backend", "gloo", "--share-gpu", "--collective-timeout", "120",
+                          "--full", "--no-profile-pass", "--backend", "gloo", "--share-gpu", "--collective-timeout", "120",
                           "--sharded-rows-per-rank", "3000"], timeout=900)
     assert res.returncode == 0, res.stderr.decode()[-3000:]
     lines = [l for l in res.stdout.decode().splitlines() if l.startswith("{")]
