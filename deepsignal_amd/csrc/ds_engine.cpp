@@ -1413,6 +1413,9 @@ static int ds_create_impl(const ds_config* cfg, ds_handle** out)
         return fail(nullptr, DS_ERR_INVALID, "kmer_len must be odd and in [1,255]");
     if (cfg->signal_len < 16 || cfg->class_num < 1 || cfg->class_num > 16)
         return fail(nullptr, DS_ERR_INVALID, "bad signal_len/class_num");
+    if (cfg->signal_len > DS_MAX_SIGNAL_LEN)      // stem1_kernel's window in dynamic LDS (launch_stem1)
+        return fail(nullptr, DS_ERR_UNSUPPORTED, "signal_len " + std::to_string(cfg->signal_len) + " > DS_MAX_SIGNAL_LEN (" +
+                    std::to_string(DS_MAX_SIGNAL_LEN) + "): the stem's window does not fit the 64 KB of dynamic LDS it may use");
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0)

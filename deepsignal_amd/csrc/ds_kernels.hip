@@ -2265,6 +2265,7 @@ hipError_t launch_stem1(const float* signals, const float* w7x64, const float* b
 {
     if (n <= 0) return hipSuccess;
     const size_t lds = (signal_len + 2 * STEM_HALO + 8) * sizeof(float);
+    if (lds > 64 * 1024) return hipErrorInvalidValue;      // no opt-in to more: ds_create refuses signal_len > DS_MAX_SIGNAL_LEN
     if (out_bf16)
         hipLaunchKernelGGL(stem1_kernel<true>, dim3(n), dim3(256), lds, s, signals, w7x64, bias64, out,
                            signal_len, w1, pad_l_conv, wa, pad_l_pool);

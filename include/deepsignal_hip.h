@@ -48,10 +48,14 @@ extern "C" {
 
 typedef struct ds_handle ds_handle;
 
+/* Longest signal window ds_create accepts (longer ones: DS_ERR_UNSUPPORTED). The stem's first conv keeps a site's whole window
+ * plus a 24-float halo in dynamic LDS, (signal_len + 24) x 4 bytes, within the 64 KB a kernel may ask for without opting in to more. */
+#define DS_MAX_SIGNAL_LEN 16360
+
 /* Mirrors Model.__init__'s arguments (model.py:26-27) plus placement. */
 typedef struct ds_config {
     int32_t kmer_len;     /* base_num,   default 17  (deepsignal.py:258-259) */
-    int32_t signal_len;   /* signal_num, default 360 (deepsignal.py:260-262) */
+    int32_t signal_len;   /* signal_num, default 360 (deepsignal.py:260-262); 16 .. DS_MAX_SIGNAL_LEN */
     int32_t class_num;    /* default 2 */
     int32_t is_cnn;       /* model.py:28-29,59-75,89-95 switches (at least one of is_cnn / is_rnn) */
     int32_t is_rnn;
@@ -74,8 +78,11 @@ typedef struct ds_config {
                              process-global tuning state, so two handles in one process never influence each other. */
 } ds_config;
 
-/* ds_config.reserved[2] bits — bits 1, 2, 4 are diagnostics: results are unchanged (same bits out) */
-#define DS_TUNE_NO_FUSED 1       /* layer-granular GEMM launches for the inception modules instead of the fused kernel */
+/* ds_config.reserved[2] bits — bits 2, 4 are diagnostics: results are unchanged (same bits out). Bit 1 is a diagnostic that
+   changes the rounding only: the layer-granular GEMMs sum K in another order than the fused kernels, so results differ within
+   the parity bars (measured at the default shape: fp32 3e-7 on act; bf16 modes 7e-4 on act, a flipped bf16 rounding downstream;
+   tests/test_gpu_long_windows.py). Windows whose widths exceed 96 rows run that path whatever the bit says. */
+#define DS_TUNE_NO_FUSED 1       /* layer-granular GEMM launches for the stem conv2/3 and the inception modules, stand-alone pools */
 #define DS_TUNE_SERIAL 2         /* every launch of a forward on ONE stream (stand-alone kernel durations)            */
 #define DS_TUNE_DEBUG_STAMPS 4   /* attach the s_memtime stamp buffer of the fused kernels (tools/stamps.py)          */
 /* not a diagnostic: changes the arithmetic (within rounding). By default the fp32 engine FOLDS the joint model: the two

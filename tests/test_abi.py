@@ -89,3 +89,20 @@ def test_header_is_plain_c99_and_client_links(tmp_path):
     subprocess.run([gcc, "-std=c99", "-Wall", "-O1", os.path.join(root, "tests", "abi_client.c"), "-o", str(out),
                     "-L" + os.path.dirname(lib), "-ldeepsignal_hip", "-Wl,-rpath," + os.path.dirname(lib)], check=True)
     assert out.exists()
+
+
+def test_signal_len_beyond_the_stem_window_is_refused_in_ds_create(lib):
+    """stem1_kernel keeps a site's window in dynamic LDS, (signal_len + 24) x 4 bytes, and opts in to no more than the 64 KB
+    default: ds_create refuses longer windows (DS_ERR_UNSUPPORTED, before any device work) instead of the first forward
+    failing at launch."""
+    from deepsignal_amd.engine import DsConfig, Engine
+    text = open(os.path.join(ROOT, "include", "deepsignal_hip.h")).read()
+    limit = int(re.search(r"#define DS_MAX_SIGNAL_LEN (\d+)", text).group(1))
+    assert (limit + 24) * 4 <= 64 * 1024 < (limit + 1 + 24) * 4
+    for s in (limit + 1, 100000):
+        cfg = DsConfig(17, s, 2, 1, 1, 1, 0, 0, 8)
+        h = ctypes.c_void_p()
+        assert lib.ds_create(ctypes.byref(cfg), ctypes.byref(h)) == -4 and not h.value
+        assert b"DS_MAX_SIGNAL_LEN" in lib.ds_last_error(None)
+    with pytest.raises(RuntimeError, match="ds_create failed \\(-4\\).*DS_MAX_SIGNAL_LEN"):
+        Engine(signal_len=limit + 1, max_batch=8)

@@ -226,7 +226,9 @@ def test_extreme_logits_do_not_break_sigmoid_or_argmax(stress_weights):
 
 
 @pytest.mark.parametrize("variant", [dict(kmer_len=9, signal_len=100), dict(kmer_len=21, signal_len=128), dict(is_cnn=False),
-                                     dict(is_rnn=False), dict(is_base=False)])
+                                     dict(is_rnn=False), dict(is_base=False),
+                                     # long windows: widths above the fused kernels' 96 rows run the layer-granular path
+                                     dict(signal_len=385), dict(kmer_len=13, signal_len=800)])
 def test_trained_regime_on_other_geometries_and_model_variants(variant):
     """The stress scale (LSTM kernels x 3.5, bias std 0.6, hot BN channels) on the CLI's other shapes (--kmer_len /
     --cent_signals_len, deepsignal.py:258-263) and on the Model(is_cnn, is_rnn, is_base) switches (model.py:28-29,59-75,89-95):

@@ -221,3 +221,49 @@ def test_split_operand_statement_is_exact_in_its_terms_and_fp32_class():
     assert d3 <= max(2.0 * d32, 4e-5) and d3 <= 1e-4, (d3, d32)
     decided = np.abs(a64[:, 1] - a64[:, 0]) > 1e-3
     assert (p3[decided] == p64[decided]).all()
+
+
+# Long windows (--cent_signals_len, deepsignal.py:260): widths on both sides of the fused kernels' 96-row limit, odd widths with
+# a left pool pad of 1 (385, 1537), even ones (800), and a joint width of 23,792 at 1537. tests/test_gpu_long_windows.py holds the
+# HIP engine to the C oracle at these shapes, so the oracle is pinned to both independent statements here first.
+LONG_GEOMETRIES = [(dict(signal_len=385), 4), (dict(kmer_len=13, signal_len=800), 3), (dict(signal_len=1537), 2)]
+
+
+@pytest.fixture(scope="module")
+def long_window_weights():
+    """One weight set per geometry, built once (dense/kernel alone is 2.3 GB of fp32 at signal_len 1537)."""
+    cache = {}
+
+    def get(geom):
+        key = tuple(sorted(geom.items()))
+        if key not in cache:
+            cache[key] = weights.random_weights(seed=41, lstm_bias_std=0.1, **geom)
+        return cache[key]
+    yield get
+    cache.clear()
+
+
+@pytest.mark.parametrize("geom,n", LONG_GEOMETRIES, ids=lambda v: "-".join("%s%d" % kv for kv in v.items()) if isinstance(v, dict) else str(v))
+def test_statements_agree_on_long_signal_windows(long_window_weights, geom, n):
+    """The C oracle (float64) against torch_statement and nn_statement (float64) on every tap, with the bars of
+    test_independent_torch_statement_agrees / test_third_statement_in_nn_modules_agrees. Both statements take the geometry
+    from the feature shapes; nn_statement's ceil-mode pools meet odd widths (97 / 49 / 25, 385 / 193 / 97) here."""
+    from oracle import nn_statement
+    w = long_window_weights(geom)
+    feats = synth.synthetic_features(n, seed=43, **geom)
+    feats["signals"][0, -7:] = 0.0          # a right-padded short window reaches the last rows of every width
+    d = spec.net_dims(geom.get("kmer_len", 17), geom["signal_len"])
+    o_act, o_pred, o_taps = oracle.forward(w, feats, "f64", taps=True, **geom)
+    assert o_taps["module11"].shape == (n, d.w_c, 240) and o_taps["joint"].shape == (n, d.joint)
+    t_act, t_pred, t_taps = torch_statement.forward(w, feats, torch.float64, True)
+    assert set(o_taps) == set(t_taps)
+    assert np.abs(o_act - t_act).max() < 1e-7 and np.array_equal(o_pred, t_pred)
+    for k, v in o_taps.items():
+        assert np.abs(v - t_taps[k]).max() <= 1e-6 * max(1.0, np.abs(v).max()), k
+    del t_taps
+    n_act, n_pred, n_taps = nn_statement.forward(w, feats, torch.float64, True)
+    assert np.abs(o_act - n_act).max() < 1e-7 and np.array_equal(o_pred, n_pred)
+    assert set(n_taps) >= {"lstm_fw_l2", "lstm_bw_l2", "stem_pool", "stem_conv3", "module3", "module4", "module8", "module9",
+                           "module11", "signal_feat", "fc1", "logits"}
+    for k, v in n_taps.items():
+        assert np.abs(v - o_taps[k]).max() <= 1e-6 * max(1.0, np.abs(o_taps[k]).max()), k
