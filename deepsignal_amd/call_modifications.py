@@ -76,6 +76,11 @@ def _read_features_from_fast5s(fast5s, corrected_group, basecall_subgroup, norma
     from .extract_features import _extract_features
     features_list, error = _extract_features(fast5s, corrected_group, basecall_subgroup, normalize_method, motif_seqs,
                                              methyloc, chrom2len, kmer_len, raw_signals_len, methy_label, positions)
+    return [_features_item(features_list)], error
+
+
+def _features_item(features_list):
+    """extract_read_features tuples -> one queue item (reference call_modifications.py:104-121)."""
     sampleinfo, kmers, base_means, base_stds, base_signal_lens, cent_signals, labels = [], [], [], [], [], [], []
     for (chrom, pos, alignstrand, loc_in_ref, readname, strand, k_mer, signal_means, signal_stds, signal_lens,
          kmer_cent_signals, f_methy_label) in features_list:
@@ -86,7 +91,7 @@ def _read_features_from_fast5s(fast5s, corrected_group, basecall_subgroup, norma
         base_signal_lens.append(signal_lens)
         cent_signals.append(kmer_cent_signals)
         labels.append(f_methy_label)
-    return [(sampleinfo, kmers, base_means, base_stds, base_signal_lens, cent_signals, labels)], error
+    return (sampleinfo, kmers, base_means, base_stds, base_signal_lens, cent_signals, labels)
 
 
 def _call_mods(features_batch: FeaturesBatch, engine, batch_size: int):
@@ -512,7 +517,7 @@ def _call_mods_sharded(input_path, engine, batch_size, result_file, kmer_len, ce
 def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
               batch_size, learning_rate, class_num, nproc, is_gpu, is_rnn, is_base, is_cnn,
               f5_args, engine=None, f5_batch_num=None, native_io=True, precision="fp32", dist=None, force_sharded=False,
-              engine_batch=0):
+              engine_batch=0, extract_on="cpu"):
     """The reference's call_mods (call_modifications.py:417-495), same signature and argument meaning.
 
     learning_rate / is_gpu are accepted for signature compatibility: inference ignores the learning rate
@@ -524,7 +529,10 @@ def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
     (submit / wait, several batches in flight) and, when launched by torch.distributed.run with WORLD_SIZE > 1, one
     process per GPU takes its share of the reads. force_sharded=True takes that multi-process route (byte ranges, row
     gather through the process group's collectives) even in a world of one: one rank under the launcher runs the same
-    RCCL calls as eight."""
+    RCCL calls as eight. extract_on="gpu" (directory input only) computes the features of the fast5 route on the GPU
+    (ds_submit_reads) instead of on the host."""
+    if extract_on not in ("cpu", "gpu"):
+        raise ValueError("extract_on must be 'cpu' or 'gpu'")
     start = time.time()
     f5 = _unpack_f5_args(f5_args, f5_batch_num)
     dist, rank, world, local = _distributed_context(dist)
@@ -546,7 +554,7 @@ def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
     try:
         if os.path.isdir(input_path):
             nsites = _call_mods_from_fast5s(input_path, result_file, kmer_len, cent_signals_len, batch_size, f5, engine,
-                                            nproc=nproc, dist=dist, rank=rank, world=world, device=device)
+                                            nproc=nproc, dist=dist, rank=rank, world=world, device=device, extract_on=extract_on)
         elif world > 1 or (force_sharded and dist is not None):
             # launched as `python -m torch.distributed.run --nproc-per-node N -m deepsignal_amd.deepsignal call_mods ...`
             if not native_io:
@@ -627,8 +635,125 @@ def _fast5_task(task):
     return _read_features_from_fast5s(*task)
 
 
+def _device_read_record(raw, starts, lengths, bases, scaling, offset, info, motif_seqs, methyloc, chrom2len, kmer_len,
+                        positions=None):
+    """One read's arrays (as _read_fast5 returns them) -> ("gpu", read tuple of ReadBatch, site locs, sampleinfo rows, k-mer
+    codes) for the device extractor; () when the read has no site; None when the device route cannot take the read (a
+    signal that is not int16, bases outside ACGTN, events outside the signal, a non-float64 offset)."""
+    import zlib
+    from . import extract_features as ef
+    from .engine import base_codes
+    readname, strand, alignstrand, chrom, chrom_start = info
+    chromlen = chrom2len.get(chrom) if chrom2len is not None else None
+    if chrom2len is not None and chromlen is None:
+        print("warning - chrom_name in fast5 not in provided reference genome!")
+    raw = np.asarray(raw)
+    codes = base_codes(bases)
+    starts, lengths = np.asarray(starts, np.int64), np.asarray(lengths, np.int64)
+    if raw.dtype != np.int16 or (codes < 0).any() or (starts < 0).any() or (lengths < 1).any() or \
+            (starts + lengths > len(raw)).any() or np.asarray(offset).dtype != np.float64:
+        return None
+    sites = ef.read_sites(bases, motif_seqs, methyloc, kmer_len, alignstrand, chrom, chrom_start, chromlen, positions)
+    if not sites:
+        return ()
+    nb = (kmer_len - 1) // 2
+    locs = np.array([loc for loc, _, _ in sites], np.int32)
+    text = "".join("\t".join([chrom, str(pos), alignstrand, str(pis), readname, strand]) + "\n" for _, pos, pis in sites)
+    kmers = codes[locs[:, None] + np.arange(-nb, nb + 1)].astype(np.int32)
+    return ("gpu", (raw, starts, lengths, codes, float(scaling), float(offset), zlib.crc32(readname.encode())), locs,
+            text.encode(), kmers)
+
+
+def _fast5_reads_task(task):
+    """Worker of the fast5 route with extract_on="gpu": one batch of files -> per read, either ("gpu", read arrays, sites) for
+    the device extractor or ("cpu", queue item) -- the host route for a read the device route cannot take (a signal that is
+    not int16, bases outside ACGTN, events outside the signal) -- and the number of failed files."""
+    from . import extract_features as ef
+    (fast5s, corrected_group, basecall_subgroup, normalize_method, motif_seqs, methyloc, chrom2len, kmer_len,
+     raw_signals_len, methy_label, positions) = task
+    out, error = [], 0
+    for fp in fast5s:
+        try:
+            raw, starts, lengths, bases, scaling, offset, info = ef._read_fast5(fp, corrected_group, basecall_subgroup)
+        except Exception:
+            out.append(("cpu", _read_features_from_fast5s([fp], *task[1:])))   # counts and reports the failure as the host route
+            continue
+        rec = _device_read_record(raw, starts, lengths, bases, scaling, offset, info, motif_seqs, methyloc, chrom2len, kmer_len,
+                                  positions)
+        if rec is None:
+            print("note: %s: read taken by the host extractor (not an int16 signal with ACGTN bases and events inside it)" % fp,
+                  file=sys.stderr)
+            out.append(("cpu", _read_features_from_fast5s([fp], *task[1:])))
+        elif rec:
+            out.append(rec)
+    return out, error
+
+
+def _rows_from_device(records, engine, batch_size, normalize_method):
+    """Rows of one file batch, in file order: the GPU-route reads go through ds_submit_reads in batches of up to
+    engine.max_batch sites (a read whose sites straddle two batches is carried by both), several batches in flight, rows
+    formatted by the native formatter; host-route reads run as the default route does."""
+    import collections
+    from . import fastio
+    from .engine import ReadBatch
+    cap = int(engine.max_batch)
+    out = []
+    inflight = collections.deque()
+    cur = []                               # (record, first site, end site) of the batch being filled
+    ncur = [0]
+
+    def drain(limit):
+        while len(inflight) > limit:
+            ticket, segs = inflight.popleft()
+            act, pred = engine.wait(ticket)
+            o = 0
+            for rec, s, e in segs:
+                info = rec[3]
+                lines = info.split(b"\n")[s:e]
+                blob = b"".join(lines)
+                off = np.zeros(e - s + 1, np.int64)
+                off[1:] = np.cumsum([len(l) for l in lines])
+                out.append(fastio.format_rows(np.frombuffer(blob, np.uint8), off, act[o:o + e - s], pred[o:o + e - s],
+                                              rec[4][s:e]).decode())
+                o += e - s
+
+    def submit():
+        if not cur:
+            return
+        drain(engine.slots - 1)
+        reads = [rec[1] for rec, _, _ in cur]
+        sr = np.concatenate([np.full(e - s, i, np.int32) for i, (rec, s, e) in enumerate(cur)])
+        sl = np.concatenate([rec[2][s:e] for rec, s, e in cur])
+        batch = ReadBatch(reads, sr, sl, norm=normalize_method)
+        inflight.append((engine.submit_reads(batch), list(cur)))
+        keep.append(batch)
+        del cur[:]
+        ncur[0] = 0
+
+    keep = collections.deque(maxlen=2 * max(1, engine.slots))     # descriptors stay alive while their copies may run
+    for rec in records:
+        if rec[0] == "cpu":
+            submit()
+            drain(0)
+            for fb in rec[1][0]:
+                pred_str, _, _ = _call_mods(fb, engine, batch_size)
+                out.extend(r + "\n" for r in pred_str)
+            continue
+        n, s = len(rec[2]), 0
+        while s < n:
+            take = min(n - s, cap - ncur[0])
+            cur.append((rec, s, s + take))
+            ncur[0] += take
+            s += take
+            if ncur[0] == cap:
+                submit()
+    submit()
+    drain(0)
+    return out
+
+
 def _call_mods_from_fast5s(fast5_dir, result_file, kmer_len, cent_signals_len, batch_size, f5, engine, nproc=1,
-                           dist=None, rank=0, world=1, device=None):
+                           dist=None, rank=0, world=1, device=None, extract_on="cpu"):
     """fast5-directory mode (reference call_modifications.py:431-448 + :300-414): batches of f5_batch_num files ->
     features on the host -> engine -> rows. Needs h5py for the HDF5 files. With world > 1 (one process per GPU) file
     batch k belongs to rank k % world -- extraction, the forward and row formatting all happen on the owning rank -- and
@@ -646,14 +771,15 @@ def _call_mods_from_fast5s(fast5_dir, result_file, kmer_len, cent_signals_len, b
              for i in range(0, len(fast5s), f5.f5_batch_num)]
     mine = tasks[rank::world]
     pool = None
+    task_fn = _fast5_reads_task if extract_on == "gpu" else _fast5_task
     if nproc > 2 and len(mine) > 1:
         # the reference runs nproc - 1 extraction processes next to the GPU process (call_modifications.py:431-448);
         # here nproc - 1 workers extract file batches (in order) while this process drives the engine
         import multiprocessing as mp
         pool = mp.get_context("spawn").Pool(min(nproc - 1, len(mine)))
-        results = pool.imap(_fast5_task, mine)
+        results = pool.imap(task_fn, mine)
     else:
-        results = (_fast5_task(t) for t in mine)
+        results = (task_fn(t) for t in mine)
     gather = None
     failed = False
     if world > 1:
@@ -664,12 +790,18 @@ def _call_mods_from_fast5s(fast5_dir, result_file, kmer_len, cent_signals_len, b
     try:
         for batches, err in results:
             errors += err
-            rows = []
-            for fb in batches:
-                pred_str, _, _ = _call_mods(fb, engine, batch_size)
-                rows.extend(pred_str)
-            nsites += len(rows)
-            text = "".join(r + "\n" for r in rows)
+            if extract_on == "gpu":
+                errors += sum(rec[1][1] for rec in batches if rec[0] == "cpu")
+                chunks = _rows_from_device(batches, engine, batch_size, f5.normalize_method)
+                text = "".join(chunks)
+                nsites += text.count("\n")
+            else:
+                rows = []
+                for fb in batches:
+                    pred_str, _, _ = _call_mods(fb, engine, batch_size)
+                    rows.extend(pred_str)
+                nsites += len(rows)
+                text = "".join(r + "\n" for r in rows)
             if gather is None:
                 wf.write(text)
                 wf.flush()

@@ -4,6 +4,7 @@
 // and layers.py (cited per stage below); nothing here falls back to a CPU path.
 #include "../../include/deepsignal_hip.h"
 #include "ds_internal.h"
+#include "ds_extract.h"
 
 #include <algorithm>
 #include <cmath>
@@ -73,7 +74,7 @@ struct Op {
 
 // per-kernel accumulators (one entry per __global__ function / template instantiation)
 enum KernelClass { K_GEMM_CONV = 0, K_GEMM_FC, K_GEMM_LSTM, K_GEMM_CONV_WIDE, K_GEMM_CONV_POOL, K_GEMM_FC_DENSE, K_GEMM_LSTM_DENSE, K_FUSED1, K_FUSED2, K_FUSED3, K_STEM1, K_MAXPOOL, K_AVGPOOL, K_HEAD,
-                   K_GEMM_BCONV, K_GEMM_BCONV_POOL, K_GEMM_BFC, K_GEMM_BFC_DENSE, K_PACKEV, K_GEMM_BLSTM, K_GEMM_BLSTM_DENSE, K_FUSEDB1, K_FUSEDB2, K_FUSEDB3, K_GEMM_LSTM_T, K_GEMM_LSTM_T_DENSE, K_GEMM_BLSTM_T, K_GEMM_BLSTM_T_DENSE, K_LSTM_CELL1, K_LSTM_CELL2, K_LSTM_CELL4, K_LSTM_LDS1, K_LSTM_LDS2, K_STEM23, K_HEADF, K_LSTM_B11, K_LSTM_B12, K_LSTM_B22, K_STEM23B, K_FUSEDS1, K_FUSEDS2, K_FUSEDS3, K_LSTM_S11, K_LSTM_S12, K_LSTM_S22, K_DENSE_SPLIT, K_STEM23S, K_LSTM_XPROJ, K_LSTM_S28, K_COUNT };
+                   K_GEMM_BCONV, K_GEMM_BCONV_POOL, K_GEMM_BFC, K_GEMM_BFC_DENSE, K_PACKEV, K_GEMM_BLSTM, K_GEMM_BLSTM_DENSE, K_FUSEDB1, K_FUSEDB2, K_FUSEDB3, K_GEMM_LSTM_T, K_GEMM_LSTM_T_DENSE, K_GEMM_BLSTM_T, K_GEMM_BLSTM_T_DENSE, K_LSTM_CELL1, K_LSTM_CELL2, K_LSTM_CELL4, K_LSTM_LDS1, K_LSTM_LDS2, K_STEM23, K_HEADF, K_LSTM_B11, K_LSTM_B12, K_LSTM_B22, K_STEM23B, K_FUSEDS1, K_FUSEDS2, K_FUSEDS3, K_LSTM_S11, K_LSTM_S12, K_LSTM_S22, K_DENSE_SPLIT, K_STEM23S, K_LSTM_XPROJ, K_LSTM_S28, K_EXTRACT_STATS, K_EXTRACT_SITES, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"gemm_kernel<1,2,4,1,0,0,1,1>", "gemm_kernel<1,3,4,1,0,0,2,1>", "gemm_kernel<1,4,4,1,1,0,1,1>",
                                            "gemm_kernel<2,2,2,2,0,0,1,1>", "gemm_kernel<1,2,4,1,0,1,1,1>", "gemm_kernel<1,3,4,1,0,2,2,1>",
                                            "gemm_kernel<1,4,4,1,1,2,1,1>", "inception_fused_kernel<1>",
@@ -91,7 +92,8 @@ const char* const kKernelNames[K_COUNT] = {"gemm_kernel<1,2,4,1,0,0,1,1>", "gemm
                                            "lstm_cell_bf16_kernel<1,1>", "lstm_cell_bf16_kernel<1,2>", "lstm_cell_bf16_kernel<2,2>", "stem23_bf16_kernel",
                                            "inception_fused_split_kernel<1>", "inception_fused_split_kernel<2>", "inception_fused_split_kernel<3>",
                                            "lstm_cell_split_kernel<1,1>", "lstm_cell_split_kernel<1,2>", "lstm_cell_split_kernel<2,2>",
-                                           "dense_split_kernel (+ pack_joint_split_kernel)", "stem23_split_kernel", "lstm_xproj_kernel", "lstm_cell_split_kernel<1,2,4,2>"};
+                                           "dense_split_kernel (+ pack_joint_split_kernel)", "stem23_split_kernel", "lstm_xproj_kernel", "lstm_cell_split_kernel<1,2,4,2>",
+                                           "extract_stats_kernel", "extract_sites_kernel"};
 struct KernelStat {
     int64_t launches = 0;
     double total_ms = 0;
@@ -151,6 +153,11 @@ struct Slot {
     float* pin_act = nullptr;
     int* pin_pred = nullptr;
     int submitted_n = -1;                 // sites of the forward in flight on this slot (-1: none)
+    // ds_submit_reads / ds_extract: the packed reads (pinned image and its device copy + histograms), grown while the slot is idle
+    char* pin_reads = nullptr;
+    size_t pin_reads_cap = 0;
+    char* d_reads = nullptr;
+    size_t d_reads_cap = 0;
 
     std::map<int, Plan> plans;
     int last_n = 0;
@@ -1510,6 +1517,8 @@ void ds_destroy(ds_handle* h)
             for (Op& op : kv.second.ops) { if (op.ev0) hipEventDestroy(op.ev0); if (op.ev1) hipEventDestroy(op.ev1); }
         }
         if (sl.pin_in) hipHostFree(sl.pin_in);
+        if (sl.pin_reads) hipHostFree(sl.pin_reads);
+        if (sl.d_reads) hipFree(sl.d_reads);
         if (sl.pin_act) hipHostFree(sl.pin_act);       // pin_pred points into it
         if (sl.ev_fork) hipEventDestroy(sl.ev_fork);
         if (sl.ev_join) hipEventDestroy(sl.ev_join);
@@ -1713,8 +1722,8 @@ static int ds_submit_parts_impl(ds_handle* h, int32_t nparts, const int32_t* cou
     if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_submit: every slot is in flight; ds_wait the oldest ticket first");
     const size_t B = h->B, T = h->T, S = h->S;
     const size_t in_bytes = B * (4 * T * 4 + S * 4);
-    if (!sl.pin_in) {
-        HIPCHK(h, hipHostMalloc((void**)&sl.pin_in, in_bytes, hipHostMallocDefault));
+    if (!sl.pin_in) HIPCHK(h, hipHostMalloc((void**)&sl.pin_in, in_bytes, hipHostMallocDefault));
+    if (!sl.pin_act) {       // ds_submit_reads may have allocated it already
         HIPCHK(h, hipHostMalloc((void**)&sl.pin_act, (B * h->C + B) * 4, hipHostMallocDefault));      // [act | pred]
         sl.pin_pred = reinterpret_cast<int*>(sl.pin_act + B * h->C);
     }
@@ -1769,6 +1778,113 @@ static int ds_wait_impl(ds_handle* h, int32_t ticket, float* act, int32_t* pred)
     memcpy(pred, sl.pin_pred, (size_t)sl.submitted_n * 4);
     sl.submitted_n = -1;
     return DS_OK;
+}
+
+
+// Scope row f2 on the device: the reads of `r` are validated, packed into the slot's pinned block, copied to its device block
+// and the extraction kernels write the features into the slot's forward inputs (d_kmer .. d_signals), all on sl.s0. Captured
+// forward graphs are untouched: they are launched behind these kernels on the same stream.
+static int stage_reads(ds_handle* h, Slot& sl, const ds_reads* r, dsx::ExtractPlan* p, hipEvent_t* ev)
+{
+    std::string err;
+    int rc = dsx::plan(r, h->T, h->S, h->B, p, &err);
+    if (rc) return fail(h, rc, err);
+    if (p->image_bytes > sl.pin_reads_cap || p->device_bytes > sl.d_reads_cap) {
+        HIPCHK(h, hipStreamSynchronize(sl.s0));        // idle slot: nothing may still read the old blocks
+        if (p->image_bytes > sl.pin_reads_cap) {
+            if (sl.pin_reads) HIPCHK(h, hipHostFree(sl.pin_reads));
+            sl.pin_reads = nullptr; sl.pin_reads_cap = 0;
+            const size_t cap = p->image_bytes + p->image_bytes / 4;
+            HIPCHK(h, hipHostMalloc((void**)&sl.pin_reads, cap, hipHostMallocDefault));
+            sl.pin_reads_cap = cap;
+        }
+        if (p->device_bytes > sl.d_reads_cap) {
+            if (sl.d_reads) HIPCHK(h, hipFree(sl.d_reads));
+            sl.d_reads = nullptr; sl.d_reads_cap = 0;
+            const size_t cap = p->device_bytes + p->device_bytes / 4;
+            hipError_t e = hipMalloc((void**)&sl.d_reads, cap);
+            if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, DS_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+            sl.d_reads_cap = cap;
+        }
+    }
+    dsx::stage(r, *p, sl.pin_reads);
+    HIPCHK(h, hipMemcpyAsync(sl.d_reads, sl.pin_reads, p->image_bytes, hipMemcpyHostToDevice, sl.s0));
+    const dsx::ExtractArgs a = dsx::device_args(r, *p, sl.d_reads);
+    HIPCHK(h, dsx::launch(*p, a, sl.d_reads, sl.d_kmer, sl.d_means, sl.d_stds, sl.d_sanums, sl.d_signals, sl.s0, ev));
+    return DS_OK;
+}
+
+static int ds_extract_impl(ds_handle* h, const ds_reads* r, int32_t* kmer, float* means, float* stds, float* sanums, float* signals)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (!kmer || !means || !stds || !sanums || !signals) return fail(h, DS_ERR_INVALID, "null buffer");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int si = (int)(h->next_slot % h->slots.size());       // the slot the next ds_submit takes; not advanced
+    Slot& sl = h->slots[si];
+    if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_extract: every slot is in flight; ds_wait the oldest ticket first");
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    const bool timed = h->profiling != 0;
+    if (timed)
+        for (auto& e : ev) HIPCHK(h, hipEventCreate(&e));
+    dsx::ExtractPlan p;
+    int rc = stage_reads(h, sl, r, &p, timed ? ev : nullptr);
+    if (!rc) {
+        const size_t T = h->T, n = p.nsites;
+        auto d2h = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sl.s0); };
+        hipError_t e = d2h(kmer, sl.d_kmer, n * T * 4);
+        if (e == hipSuccess) e = d2h(means, sl.d_means, n * T * 4);
+        if (e == hipSuccess) e = d2h(stds, sl.d_stds, n * T * 4);
+        if (e == hipSuccess) e = d2h(sanums, sl.d_sanums, n * T * 4);
+        if (e == hipSuccess) e = d2h(signals, sl.d_signals, n * (size_t)h->S * 4);
+        if (e == hipSuccess) e = hipStreamSynchronize(sl.s0);
+        if (e != hipSuccess) { (void)hipGetLastError(); rc = fail(h, DS_ERR_HIP, std::string("ds_extract: ") + hipGetErrorString(e)); }
+        if (!rc && timed) {
+            float ms0 = 0, ms1 = 0;
+            hipEventElapsedTime(&ms0, ev[0], ev[1]);
+            hipEventElapsedTime(&ms1, ev[1], ev[2]);
+            h->kstat[K_EXTRACT_STATS].launches += 1; h->kstat[K_EXTRACT_STATS].total_ms += ms0;
+            h->kstat[K_EXTRACT_SITES].launches += 1; h->kstat[K_EXTRACT_SITES].total_ms += ms1;
+        }
+    }
+    if (timed)
+        for (auto& e : ev) hipEventDestroy(e);
+    return rc;
+}
+
+static int ds_submit_reads_impl(ds_handle* h, const ds_reads* r, int32_t* ticket)
+{
+    if (!h || !ticket) return DS_ERR_INVALID;
+    if (!h->finalized) return fail(h, DS_ERR_INVALID, "weights not loaded");
+    if (h->profiling) return fail(h, DS_ERR_INVALID, "ds_submit_reads is not available while profiling is on");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int si = (int)(h->next_slot % h->slots.size());
+    Slot& sl = h->slots[si];
+    if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_submit_reads: every slot is in flight; ds_wait the oldest ticket first");
+    if (!sl.pin_act) {       // ds_wait copies act / pred out of the pinned result block (the input staging block is not needed here)
+        HIPCHK(h, hipHostMalloc((void**)&sl.pin_act, ((size_t)h->B * h->C + h->B) * 4, hipHostMallocDefault));
+        sl.pin_pred = reinterpret_cast<int*>(sl.pin_act + (size_t)h->B * h->C);
+    }
+    dsx::ExtractPlan p;
+    int rc = stage_reads(h, sl, r, &p, nullptr);
+    if (rc) return rc;
+    h->next_slot++;
+    h->cur = &sl;
+    const int n = p.nsites;
+    rc = run_resident(h, n);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(sl.pin_act, sl.act, ((size_t)h->B * h->C + (size_t)n) * 4, hipMemcpyDeviceToHost, sl.s0));
+    sl.submitted_n = n;
+    *ticket = si;
+    return DS_OK;
+}
+
+int ds_extract_reference(const ds_reads* r, int32_t kmer_len, int32_t signal_len, int32_t* kmer, float* means, float* stds,
+                         float* sanums, float* signals)
+{
+    std::string err;
+    int rc = dsx::reference(r, kmer_len, signal_len, kmer, means, stds, sanums, signals, &err);
+    if (rc) fail(nullptr, rc, err);
+    return rc;
 }
 
 int ds_num_slots(ds_handle* h) { return h ? (int)h->slots.size() : DS_ERR_INVALID; }
@@ -2061,4 +2177,6 @@ int ds_forward(ds_handle* h, int32_t n, const int32_t* kmer, const float* means,
 int ds_submit(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums, const float* signals, int32_t* ticket) { return guarded(h, [&] { return ds_submit_impl(h, n, kmer, means, stds, sanums, signals, ticket); }); }
 int ds_submit_parts(ds_handle* h, int32_t nparts, const int32_t* counts, const int32_t* const* kmer, const float* const* means, const float* const* stds, const float* const* sanums, const float* const* signals, int32_t* ticket) { return guarded(h, [&] { return ds_submit_parts_impl(h, nparts, counts, kmer, means, stds, sanums, signals, ticket); }); }
 int ds_wait(ds_handle* h, int32_t ticket, float* act, int32_t* pred) { return guarded(h, [&] { return ds_wait_impl(h, ticket, act, pred); }); }
+int ds_extract(ds_handle* h, const ds_reads* reads, int32_t* kmer, float* means, float* stds, float* sanums, float* signals) { return guarded(h, [&] { return ds_extract_impl(h, reads, kmer, means, stds, sanums, signals); }); }
+int ds_submit_reads(ds_handle* h, const ds_reads* reads, int32_t* ticket) { return guarded(h, [&] { return ds_submit_reads_impl(h, reads, ticket); }); }
 }  // extern "C"

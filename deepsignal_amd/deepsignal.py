@@ -24,7 +24,7 @@ def main_call_mods(args):
     call_mods(args.input_path, args.model_path, args.result_file, args.kmer_len, args.cent_signals_len,
               args.batch_size, args.learning_rate, args.class_num, args.nproc, str2bool(args.is_gpu),
               str2bool(args.is_rnn), str2bool(args.is_base), str2bool(args.is_cnn), f5_args,
-              precision=args.precision, engine_batch=args.engine_batch)
+              precision=args.precision, engine_batch=args.engine_batch, extract_on=args.extract_on)
 
 
 def main_extraction(args):
@@ -76,6 +76,10 @@ def build_parser():
                    help="fp32 (reference numerics, native fp32 matrix instructions); bf16x3 (fp32-class results: fp32 operands carried "
                         "as three bf16 terms on the bf16 matrix pipe, held to the fp32 parity bars); bf16 / bf16_all (bf16 conv+FC "
                         "operands with fp32 accumulate: fast, probabilities good to ~1e-2 only)")
+    g.add_argument("--extract_on", default="cpu", choices=["cpu", "gpu"],
+                   help="fast5-directory input only: compute the per-site features on the host (cpu, default) or on the GPU next "
+                        "to the forward (gpu; same features bit for bit, except that a middle base of >= cent_signals_len samples "
+                        "is subsampled by a seeded hash instead of Python's unseeded random)")
     g.add_argument("--engine_batch", type=int, default=0,
                    help="sites per GPU forward the engine is created for (default 0: the larger of --batch_size and 4096; results do "
                         "not depend on it, device and pinned memory grow with it -- lower it on a small or shared GPU; the "

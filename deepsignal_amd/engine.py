@@ -35,6 +35,8 @@ EXPORTED_SYMBOLS = (
     "ds_tsv_size", "ds_tsv_align", "ds_tsv_set_range", "ds_tsv_locate", "ds_tsv_parse_into",
     # scope row f3 (TF checkpoint import)
     "ds_crc32c",
+    # scope row f2 on the device (fast5 feature extraction)
+    "ds_extract", "ds_submit_reads", "ds_extract_reference",
 )
 
 
@@ -45,6 +47,78 @@ class DsConfig(ctypes.Structure):
         ("device", ctypes.c_int32), ("precision", ctypes.c_int32), ("max_batch", ctypes.c_int32),
         ("reserved", ctypes.c_int32 * 7),
     ]
+
+
+class DsReads(ctypes.Structure):
+    """include/deepsignal_hip.h ds_reads"""
+    _fields_ = [
+        ("nreads", ctypes.c_int32), ("raw", ctypes.c_void_p), ("raw_off", ctypes.c_void_p), ("start", ctypes.c_void_p),
+        ("length", ctypes.c_void_p), ("base", ctypes.c_void_p), ("base_off", ctypes.c_void_p), ("scaling", ctypes.c_void_p),
+        ("offset", ctypes.c_void_p), ("key", ctypes.c_void_p), ("nsites", ctypes.c_int32), ("site_read", ctypes.c_void_p),
+        ("site_loc", ctypes.c_void_p), ("norm", ctypes.c_int32), ("seed", ctypes.c_uint64),
+    ]
+
+
+NORMS = {"mad": 0, "zscore": 1}       # DS_NORM_MAD, DS_NORM_ZSCORE
+_BASE_CODES = np.full(256, -1, np.int8)
+for _i, _b in enumerate(b"ACGTN"):
+    _BASE_CODES[_b] = _i
+
+
+def base_codes(bases: str) -> np.ndarray:
+    """'ACGTN' text -> int8 codes 0 .. 4 (base2code_dna); any other letter -> -1, which ds_reads validation refuses."""
+    return _BASE_CODES[np.frombuffer(bases.encode("latin-1"), np.uint8)]
+
+
+class ReadBatch:
+    """Packed reads and the sites to extract from them: the ds_reads of ds_extract / ds_submit_reads / ds_extract_reference.
+
+    `reads`: sequence of (raw int16[n], starts[nbases] (read_start_rel_to_raw applied), lengths[nbases], base codes int8[nbases]
+    (base_codes), scaling, offset) tuples, optionally with a 7th entry, the read's subsample key (default: its index here).
+    `site_read[i]` / `site_loc[i]`: the read and the index of the targeted base of site i. The arrays stay referenced here."""
+
+    def __init__(self, reads, site_read, site_loc, norm: str = "mad", seed: int = 0):
+        if norm not in NORMS:
+            raise ValueError("norm must be one of %s" % (sorted(NORMS),))
+        raws = [np.asarray(r[0]) for r in reads]
+        if any(x.dtype != np.int16 for x in raws):
+            raise ValueError("raw signals must be int16")
+        self.raw = np.ascontiguousarray(np.concatenate(raws) if raws else np.zeros(0, np.int16))
+        self.raw_off = np.zeros(len(raws) + 1, np.int64)
+        self.raw_off[1:] = np.cumsum([len(x) for x in raws])
+        self.start = np.ascontiguousarray(np.concatenate([np.asarray(r[1], np.int64) for r in reads]), np.int64)
+        self.length = np.ascontiguousarray(np.concatenate([np.asarray(r[2], np.int64) for r in reads]).astype(np.int32))
+        self.base = np.ascontiguousarray(np.concatenate([np.asarray(r[3], np.int8) for r in reads]), np.int8)
+        self.base_off = np.zeros(len(raws) + 1, np.int64)
+        self.base_off[1:] = np.cumsum([len(r[3]) for r in reads])
+        self.scaling = np.array([r[4] for r in reads], np.float64)
+        self.offset = np.array([r[5] for r in reads], np.float64)
+        self.key = np.array([r[6] if len(r) > 6 else i for i, r in enumerate(reads)], np.uint64)
+        self.site_read = np.ascontiguousarray(site_read, np.int32)
+        self.site_loc = np.ascontiguousarray(site_loc, np.int32)
+        self.nsites = int(self.site_read.shape[0])
+        self.desc = DsReads(len(raws), self.raw.ctypes.data, self.raw_off.ctypes.data, self.start.ctypes.data,
+                            self.length.ctypes.data, self.base.ctypes.data, self.base_off.ctypes.data, self.scaling.ctypes.data,
+                            self.offset.ctypes.data, self.key.ctypes.data, self.nsites, self.site_read.ctypes.data,
+                            self.site_loc.ctypes.data, NORMS[norm], seed)
+
+
+def _feature_arrays(n: int, kmer_len: int, signal_len: int):
+    return {"kmer": np.empty((n, kmer_len), np.int32), "means": np.empty((n, kmer_len), np.float32),
+            "stds": np.empty((n, kmer_len), np.float32), "sanums": np.empty((n, kmer_len), np.float32),
+            "signals": np.empty((n, signal_len), np.float32)}
+
+
+def extract_reference(batch: ReadBatch, kmer_len: int = 17, signal_len: int = 360) -> Dict[str, np.ndarray]:
+    """ds_extract_reference: the device route's features computed on the CPU from the same arithmetic. A checker for the
+    tests (no GPU needed), not a fall-back: inference has no CPU path."""
+    lib = load_library()
+    out = _feature_arrays(batch.nsites, kmer_len, signal_len)
+    rc = lib.ds_extract_reference(ctypes.byref(batch.desc), kmer_len, signal_len,
+                                  *(out[k].ctypes.data for k in ("kmer", "means", "stds", "sanums", "signals")))
+    if rc != 0:
+        raise RuntimeError("ds_extract_reference failed (%d): %s" % (rc, lib.ds_last_error(None).decode()))
+    return out
 
 
 # ds_config.precision (include/deepsignal_hip.h): "bf16" = bf16 conv + FC operands with fp32 accumulation, fp32 BiLSTM;
@@ -122,6 +196,9 @@ def load_library() -> ctypes.CDLL:
     lib.ds_reset_stage_times.argtypes = [vp]
     lib.ds_set_graph.argtypes = [vp, i32]
     lib.ds_num_kernels.argtypes = [vp]
+    lib.ds_extract.argtypes = [vp, ctypes.POINTER(DsReads), vp, vp, vp, vp, vp]
+    lib.ds_submit_reads.argtypes = [vp, ctypes.POINTER(DsReads), ctypes.POINTER(i32)]
+    lib.ds_extract_reference.argtypes = [ctypes.POINTER(DsReads), i32, i32, vp, vp, vp, vp, vp]
     lib.ds_get_kernel_stat.argtypes = [vp, i32, ctypes.c_char_p, i32, ctypes.POINTER(i64),
                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
     _lib = lib
@@ -256,6 +333,21 @@ class Engine:
         pred = np.empty((n,), np.int32)
         self._check(self._lib.ds_wait(self._h, slot, act.ctypes.data, pred.ctypes.data), "ds_wait")
         return act, pred
+
+    def extract(self, batch: ReadBatch) -> Dict[str, np.ndarray]:
+        """ds_extract: the features of every site of `batch` (nsites <= max_batch), computed on the GPU, as host arrays
+        kmer / means / stds / sanums / signals (the inputs of run())."""
+        out = _feature_arrays(batch.nsites, self.kmer_len, self.signal_len)
+        self._check(self._lib.ds_extract(self._h, ctypes.byref(batch.desc),
+                                         *(out[k].ctypes.data for k in ("kmer", "means", "stds", "sanums", "signals"))),
+                    "ds_extract")
+        return out
+
+    def submit_reads(self, batch: ReadBatch) -> Tuple[int, int]:
+        """ds_submit_reads: features extracted on the GPU straight into the forward's inputs; a ticket for wait(), as submit()."""
+        t = ctypes.c_int32()
+        self._check(self._lib.ds_submit_reads(self._h, ctypes.byref(batch.desc), ctypes.byref(t)), "ds_submit_reads")
+        return (int(t.value), batch.nsites)
 
     @property
     def slots(self) -> int:

@@ -94,6 +94,27 @@ def _get_central_signals(signals_list: Sequence[np.ndarray], rawsignal_num: int 
     return np.append(left[-left_len:], right[:right_len])
 
 
+def read_sites(bases: str, motif_seqs: Iterable[str], methyloc: int, kmer_len: int, alignstrand: str, chrom: str,
+               chrom_start: int, chromlen: Optional[int], positions: Optional[Set[str]] = None) -> List[Tuple[int, int, int]]:
+    """The sites of one read, without their features: (loc = index of the targeted base, pos, pos_in_strand) for every motif hit
+    with (kmer_len - 1) / 2 bases on either side that passes the `positions` filter (reference extract_features.py:238-256)."""
+    num_bases = (kmer_len - 1) // 2
+    out = []
+    for loc in get_refloc_of_methysite_in_motif(bases, set(motif_seqs), methyloc):
+        if not (num_bases <= loc < len(bases) - num_bases):
+            continue
+        if alignstrand == "-":
+            pos = chrom_start + len(bases) - 1 - loc
+            pos_in_strand = chromlen - 1 - pos if chromlen is not None else -1
+        else:
+            pos = chrom_start + loc
+            pos_in_strand = pos if chromlen is not None else -1
+        if positions is not None and key_sep.join([chrom, str(pos), alignstrand]) not in positions:
+            continue
+        out.append((loc, pos, pos_in_strand))
+    return out
+
+
 def extract_read_features(raw_signal, starts, lengths, bases: str, scaling: float, offset: float, readname: str,
                           strand: str, alignstrand: str, chrom: str, chrom_start: int, chromlen: Optional[int],
                           motif_seqs: Iterable[str], methyloc: int, kmer_len: int, raw_signals_len: int,
@@ -106,17 +127,8 @@ def extract_read_features(raw_signal, starts, lengths, bases: str, scaling: floa
     signal_list = [norm[int(s):int(s) + int(l)] for s, l in zip(starts, lengths)]
     genomeseq = bases
     out = []
-    for loc in get_refloc_of_methysite_in_motif(genomeseq, set(motif_seqs), methyloc):
-        if not (num_bases <= loc < len(genomeseq) - num_bases):
-            continue
-        if alignstrand == "-":
-            pos = chrom_start + len(genomeseq) - 1 - loc
-            pos_in_strand = chromlen - 1 - pos if chromlen is not None else -1
-        else:
-            pos = chrom_start + loc
-            pos_in_strand = pos if chromlen is not None else -1
-        if positions is not None and key_sep.join([chrom, str(pos), alignstrand]) not in positions:
-            continue
+    for loc, pos, pos_in_strand in read_sites(bases, motif_seqs, methyloc, kmer_len, alignstrand, chrom, chrom_start, chromlen,
+                                              positions):
         k_mer = genomeseq[loc - num_bases:loc + num_bases + 1]
         k_signals = signal_list[loc - num_bases:loc + num_bases + 1]
         signal_lens = [len(x) for x in k_signals]

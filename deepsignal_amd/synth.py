@@ -34,3 +34,18 @@ def synthetic_features(n: int, seed: int = FEATURE_SEED, kmer_len: int = 17,
     labels = rng.integers(0, 2, size=n, dtype=np.int32)
     return {"kmer": kmer, "means": means, "stds": stds, "sanums": sanums,
             "signals": signals, "labels": labels}
+
+
+def synthetic_read(nbases: int, seed: int, min_per_base: int = 4, max_per_base: int = 15, long_bases: int = 0):
+    """One seeded tombo-like read: (raw int16, starts, lengths, bases str, scaling, offset). Events tile the signal after a
+    random leading stretch; `long_bases` bases get 400 .. 900 samples (the subsample branch of the central window)."""
+    rng = np.random.default_rng(seed)
+    lengths = rng.integers(min_per_base, max_per_base + 1, nbases).astype(np.int64)
+    if long_bases:
+        lengths[rng.choice(nbases, long_bases, replace=False)] = rng.integers(400, 900, long_bases)
+    lead = int(rng.integers(0, 50))
+    starts = lead + np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64)
+    n = lead + int(lengths.sum()) + int(rng.integers(0, 50))
+    raw = np.clip(rng.normal(500, 80, n), -32768, 32767).astype(np.int16)
+    bases = "".join(rng.choice(list("ACGT"), nbases))
+    return raw, starts, lengths, bases, 1400.0 / 8192.0 * (1 + 0.01 * rng.random()), float(rng.integers(-10, 30))

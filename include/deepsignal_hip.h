@@ -256,6 +256,51 @@ int64_t ds_format_rows(int64_t n, const char *info, const int64_t *info_off, con
  * tf.train.Saver().restore (call_modifications.py:210-211). Host code only. */
 uint32_t ds_crc32c(const void *data, size_t n, uint32_t crc);
 
+/* ---- scope row f2 on the device: fast5 feature extraction (ds_extract.hip) ----------------------------------------------
+ * A packed batch of reads and the sites to extract from them. Read r owns raw[raw_off[r] .. raw_off[r + 1]) and the bases
+ * base_off[r] .. base_off[r + 1] of start / length / base; start is the base's first sample relative to the read's raw signal
+ * (read_start_rel_to_raw already applied). A site is (site_read[i], site_loc[i]): the read and the index of the targeted base
+ * within it. kmer_len and signal_len come from the handle's ds_config (ds_extract_reference takes them as arguments).
+ * Features are those of the host extractor (extract_features.extract_read_features, reference extract_features.py:143-190,
+ * 225-280) after the float32 narrowing the engine's inputs get, bit for bit -- except when a site's middle base alone has
+ * >= signal_len samples: the reference then draws an unseeded random.sample; here an ordered sample without replacement of
+ * that base's samples (selection sampling driven by a hash of (seed, key, loc): deterministic for a seed). */
+#define DS_NORM_MAD 0       /* median / MAD (statsmodels.robust.mad scale), the default of the reference */
+#define DS_NORM_ZSCORE 1    /* mean / population std */
+typedef struct ds_reads {
+    int32_t nreads;
+    const int16_t *raw;        /* all reads' raw samples, concatenated */
+    const int64_t *raw_off;    /* [nreads + 1], raw_off[0] == 0, non-decreasing */
+    const int64_t *start;      /* per base (all reads concatenated): first sample of the base's event, 0 <= start */
+    const int32_t *length;     /* per base: samples of the event, >= 1, start + length <= the read's sample count */
+    const int8_t *base;        /* per base: A, C, G, T, N -> 0 .. 4 */
+    const int64_t *base_off;   /* [nreads + 1], base_off[0] == 0, non-decreasing */
+    const double *scaling;     /* per read: pA = scaling * (raw + offset) (range / digitisation, offset of channel_id) */
+    const double *offset;
+    const uint64_t *key;       /* per read: key of the subsample hash (NULL: the read's index in this descriptor) */
+    int32_t nsites;
+    const int32_t *site_read;  /* [nsites] in [0, nreads) */
+    const int32_t *site_loc;   /* [nsites]: (kmer_len - 1) / 2 <= loc < bases of the read - (kmer_len - 1) / 2 */
+    int32_t norm;              /* DS_NORM_MAD | DS_NORM_ZSCORE */
+    uint64_t seed;             /* seed of the subsample hash */
+} ds_reads;
+
+/* Features of every site of `reads` (1 <= nsites <= max_batch) into host rows: kmer int32[nsites, kmer_len],
+ * means / stds / sanums float[nsites, kmer_len], signals float[nsites, signal_len] -- the inputs of ds_forward. Blocking;
+ * runs on an idle pipeline slot (DS_ERR_INVALID while every slot is in flight). With profiling on (ds_set_profiling) the
+ * two extraction kernels are timed into ds_get_kernel_stat. Invalid descriptors return DS_ERR_INVALID with a message. */
+int ds_extract(ds_handle *h, const ds_reads *reads, int32_t *kmer, float *means, float *stds, float *sanums, float *signals);
+/* Asynchronous sibling of ds_submit: the reads are staged in the next slot's pinned block, copied to its device block, and the
+ * extraction kernels write the features straight into the slot's forward inputs on the slot's stream, ahead of the forward;
+ * act / pred come back with ds_wait(ticket) (nsites rows, site order). Same ticket rules as ds_submit. A read whose sites
+ * span two batches is given in both descriptors. */
+int ds_submit_reads(ds_handle *h, const ds_reads *reads, int32_t *ticket);
+/* The same features computed on the CPU from the same arithmetic (csrc/ds_extract.h): a CHECKER for the tests, needs no
+ * handle and no GPU. It is not a fall-back -- the library has no CPU inference path. Rows as ds_extract; errors
+ * (DS_ERR_INVALID) leave their message in ds_last_error(NULL). */
+int ds_extract_reference(const ds_reads *reads, int32_t kmer_len, int32_t signal_len, int32_t *kmer, float *means,
+                         float *stds, float *sanums, float *signals);
+
 /* Use a captured hipGraph for the forward (default on). */
 int ds_set_graph(ds_handle *h, int32_t enable);
 
