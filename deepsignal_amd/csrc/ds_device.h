@@ -38,6 +38,13 @@ __device__ __forceinline__ float4 gload4_nt(const float* p)      // global_load_
     return make_float4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ void gstore(float* p, float v) { *(gptr1w)(p) = v; }
+// (wave-uniform base) + (32-bit byte offset of the lane): hipcc then keeps the base in SGPRs (global_load ... v, s[n:n+1])
+__device__ __forceinline__ float4 gload4_at(const float* base, unsigned byte_off)
+{
+    const v4f v = *(gptr4)(reinterpret_cast<const char*>(base) + byte_off);
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ float gload_at(const float* base, unsigned byte_off) { return *(gptr1)(reinterpret_cast<const char*>(base) + byte_off); }
 
 // ---- bf16 helpers (mixed-precision mode: bf16 operands, fp32 accumulate) ----
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -123,38 +130,61 @@ template <int I> struct LdsSlot { static constexpr int value = I; };
 // row plus the (mean, std, len) rank-1 terms. Every load of a group is issued before anything waits: one L2 round
 // trip for the biases, two (code -> table row) for layer 0 -- written with per-gate branches this was four to eight
 // SERIALIZED round trips in front of every tile.
+// The layer-0 terms come in TWO groups of 32 load registers, not one of 64: group 1 (the features, the code and the
+// first two rank-1 rows) is folded into 16 partial sums while the code is on its way, group 2 (third rank-1 row and the
+// table row, which has to wait for the code anyway) and the biases follow -- still two round trips, and the whole
+// prologue stays inside the 72 VGPRs that let two cell waves sit beside two fused-module waves on a SIMD (DESIGN.md 4,
+// "Sharing a CU"). The fma chain of every element is the one it always was.
 __device__ __forceinline__ void lstm_acc_init(const LstmCell& C, int p8, int rowc, int T, floatx16& acc)
 {
+    // every address is (wave-uniform base in SGPRs) + (32-bit byte offset of the lane): no 64-bit VGPR pairs
+    const unsigned po = (unsigned)p8 * 4u;
     float4 z[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) z[g] = gload4(C.bias + g * 256 + p8);
     if (C.use_feat) {                                    // wave-uniform: the two layer-0 cells of a diagonal
         const float* wf = C.wfeat;
         const float* tab = C.table;
-        const unsigned it = (unsigned)rowc * T + C.t;
-        const float f0 = gload(C.means + it), f1 = gload(C.stds + it), f2 = gload(C.lens + it);
-        // codes index the folded [vocab = 1024][1024] table; a non-Python client may pass anything: clamp
-        const int code = tab ? min(max(*(const __attribute__((address_space(1))) int*)(C.codes + it), 0), 1023) : 0;
-        float4 w0[4], w1[4], w2[4], tb[4];
+        const unsigned it4 = ((unsigned)rowc * T + C.t) * 4u;
+        const float f0 = gload_at(C.means, it4), f1 = gload_at(C.stds, it4), f2 = gload_at(C.lens, it4);
+        // codes index the folded [vocab = 1024][1024] table; a non-Python client may pass anything: clamp. Without a
+        // table (is_base = no) the word read is any valid one and the row is the bias row: no branch in front of group 1
+        const unsigned raw = __float_as_uint(gload_at(tab ? reinterpret_cast<const float*>(C.codes) : C.means, it4));
+        float4 x[4];
+        {
+            float4 w0[4], w1[4];
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            w0[g] = gload4(wf + g * 256 + p8);
-            w1[g] = gload4(wf + 1024 + g * 256 + p8);
-            w2[g] = gload4(wf + 2048 + g * 256 + p8);
-        }
-        const float* trow = tab ? tab + (size_t)code * 1024 : C.bias;      // no table (is_base = no): any valid address
-#pragma unroll
-        for (int g = 0; g < 4; ++g) tb[g] = gload4(trow + g * 256 + p8);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
+            for (int g = 0; g < 4; ++g) {
+                w0[g] = gload4_at(wf, po + g * 1024);
+                w1[g] = gload4_at(wf + 1024, po + g * 1024);
+            }
             // explicit fma chains: every instantiation / tiling must round identically
-            float4 x = make_float4(fmaf(f2, w2[g].x, fmaf(f1, w1[g].x, f0 * w0[g].x)), fmaf(f2, w2[g].y, fmaf(f1, w1[g].y, f0 * w0[g].y)),
-                                   fmaf(f2, w2[g].z, fmaf(f1, w1[g].z, f0 * w0[g].z)), fmaf(f2, w2[g].w, fmaf(f1, w1[g].w, f0 * w0[g].w)));
-            if (tab) { x.x += tb[g].x; x.y += tb[g].y; x.z += tb[g].z; x.w += tb[g].w; }
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                x[g] = make_float4(fmaf(f1, w1[g].x, f0 * w0[g].x), fmaf(f1, w1[g].y, f0 * w0[g].y),
+                                   fmaf(f1, w1[g].z, f0 * w0[g].z), fmaf(f1, w1[g].w, f0 * w0[g].w));
+        }
+        // group 2 is requested only once group 1 has been folded: its registers are the ones group 1 has just freed
+#pragma unroll
+        for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(x[g].x), "+v"(x[g].y), "+v"(x[g].z), "+v"(x[g].w) : : "memory");
+        const unsigned to = po + (tab ? (unsigned)min(max((int)raw, 0), 1023) * 4096u : 0u);
+        const float* trow = tab ? tab : C.bias;
+        float4 w2[4], tb[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            w2[g] = gload4_at(wf + 2048, po + g * 1024);
+            tb[g] = gload4_at(trow, to + g * 1024);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) z[g] = gload4_at(C.bias, po + g * 1024);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            x[g] = make_float4(fmaf(f2, w2[g].x, x[g].x), fmaf(f2, w2[g].y, x[g].y), fmaf(f2, w2[g].z, x[g].z), fmaf(f2, w2[g].w, x[g].w));
+            if (tab) { x[g].x += tb[g].x; x[g].y += tb[g].y; x[g].z += tb[g].z; x[g].w += tb[g].w; }
             if (g == 2) { z[g].x += 1.0f; z[g].y += 1.0f; z[g].z += 1.0f; z[g].w += 1.0f; }
-            z[g].x += x.x; z[g].y += x.y; z[g].z += x.z; z[g].w += x.w;
+            z[g].x += x[g].x; z[g].y += x[g].y; z[g].z += x[g].z; z[g].w += x[g].w;
         }
     } else {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) z[g] = gload4_at(C.bias, po + g * 1024);
         z[2].x += 1.0f; z[2].y += 1.0f; z[2].z += 1.0f; z[2].w += 1.0f;
     }
 #pragma unroll

@@ -611,7 +611,7 @@ __device__ __forceinline__ floatx16 mfma_bf_early(float4 a, float4 b, floatx16 c
 }
 
 template <int NT>
-__global__ __launch_bounds__(256, NT == 1 ? 5 : 2) void lstm_cell_lds_kernel(const LstmLaunch L_)
+__global__ __launch_bounds__(256, NT == 1 ? 7 : 2) void lstm_cell_lds_kernel(const LstmLaunch L_)
 {
     const LstmLaunch* const Lp = &L_;      // by-value kernel argument (see lstm_cell_kernel)
     constexpr int FR = 2 + 2 * NT;            // fragments per k-group: 2 m-tiles of h, 2 * NT n-tiles of weights
@@ -619,10 +619,12 @@ __global__ __launch_bounds__(256, NT == 1 ? 5 : 2) void lstm_cell_lds_kernel(con
     constexpr int LPS = KGS * FR / 4;         // DMA requests per wave and stage
     constexpr int STAGE = KGS * FR * 256;     // floats
     // Dynamic on purpose: with a static array hipcc derives the register budget from the LDS-limited occupancy and ignores
-    // __launch_bounds__. Footprint per workgroup (NT = 1): 12 KB of LDS and 88 VGPRs per wave -- up to five workgroups per
-    // CU, and one of them fits next to a fused-module workgroup (2 x 184 + 88 VGPRs per SIMD, 105 + 12 KB). Measured at 512
-    // sites per forward (ring = 3 stages of KGS k-groups): KGS 4 / 136 VGPRs 545 k sites/s, KGS 2 / 88 VGPRs 554 k,
-    // KGS 1 / 88 VGPRs 561 k (one barrier per four MFMAs of a wave, but more waves per SIMD to hide it).
+    // __launch_bounds__. Footprint per workgroup (NT = 1): 12 KB of LDS and 70 VGPRs per wave (72 granted) -- up to seven
+    // workgroups per CU, and TWO of them fit next to a fused-module workgroup (2 x 184 + 2 x 72 = 512 VGPRs per SIMD, 111 +
+    // 2 x 12 KB; tests/test_cell_cotenancy_budget.py). The K loop needs ~30 registers; the budget is set by the prologue, which
+    // is why lstm_acc_init loads the layer-0 terms in two groups and addresses everything as scalar base + 32-bit lane offset.
+    // Measured at 512 sites per forward (ring = 3 stages of KGS k-groups): KGS 4 / 136 VGPRs 545 k sites/s, KGS 2 / 88 VGPRs
+    // 554 k, KGS 1 / 88 VGPRs 561 k (one barrier per four MFMAs of a wave, but more waves per SIMD to hide it).
     extern __shared__ __attribute__((aligned(16))) float ring[];      // [3 * STAGE]
 
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);

@@ -1,8 +1,9 @@
 """VGPRs, scratch and static LDS of every kernel in deepsignal_amd/csrc/*.hip (hipcc -S, device only, ~40 s; DS_KERNEL_SOURCES="ds_split.hip" restricts the files).
 
 Two of the numbers carry a property the 512-site throughput depends on ("Sharing a CU"): the fused inception
-module must stay at <= 184 VGPRs and the BiLSTM cell kernel at <= 96 (88 today), so that two module waves and one cell
-wave fit a SIMD's 512 registers; tests/test_kernel_resources.py asserts them.
+module must stay at <= 184 VGPRs and the BiLSTM cell kernel at <= 72 (70 today), so that two module waves and TWO cell
+waves fit a SIMD's 512 registers (2 x 184 + 2 x 72, registers are granted in blocks of 8); tests/test_cell_cotenancy_budget.py
+asserts the sum, tests/test_kernel_resources.py the older one-cell-wave budgets (<= 184, <= 96) and the other kernels' caps.
 
 usage: python tools/kernel_resources.py [name filter]"""
 import os, re, subprocess, sys, tempfile
