@@ -46,25 +46,37 @@ struct PackedGemm {      // device-resident packed weights of one GEMM
 };
 
 enum OpKind { OP_GEMM, OP_STEM1, OP_MAXPOOL, OP_AVGPOOL, OP_HEAD, OP_FUSED, OP_PACKEV, OP_LSTM, OP_STEM23, OP_HEADF, OP_DENSES, OP_XPROJ };
+// operand form of the kernels that exist in several: native fp32, bf16 rows (DS_PRECISION_BF16*), fp32 rows as three bf16 terms (DS_PRECISION_BF16X3)
+enum Operands { OPS_FP32, OPS_BF16, OPS_SPLIT };
+constexpr KernelClass kFusedKernels[3][3] = {{K_FUSED1, K_FUSED2, K_FUSED3}, {K_FUSEDB1, K_FUSEDB2, K_FUSEDB3}, {K_FUSEDS1, K_FUSEDS2, K_FUSEDS3}};   // [Operands][tm - 1]
+constexpr KernelClass kStem23Kernels[3] = {K_STEM23, K_STEM23B, K_STEM23S};
 
+struct GemmOp { GemmCfg cfg; int launch_index, total_tiles; };      // launch_index: into the plan's GemmLaunch array
+struct Stem1Op { const float* signals; float* out; };
+// OP_MAXPOOL: maxpool(3, stride 2, SAME) of win -> wout rows per site, pad rows on the left, ch = channel pitch of both sides;
+// OP_AVGPOOL: avgpool(7) + flatten of win rows x ch channels per site
+struct PoolOp { const float* in; float* out; int win, wout, pad, ch; };
+struct LstmDiagOp { int launch_index; LstmTile tile; };              // launch_index: into the plan's LstmLaunch array
+
+// One launch of a forward. The planner fills `kernel` where it chooses the variant: issue_op launches what the op says and the
+// profiling counters are booked under it. Of the per-kind parameter blocks only the one of `kind` is filled.
 struct Op {
     OpKind kind;
+    KernelClass kernel;
+    Operands operands = OPS_FP32;         // OP_STEM1 / OP_MAXPOOL / OP_AVGPOOL (bf16 rows or fp32), OP_STEM23, OP_FUSED
     int stream;          // 0 = signal/joint stream, 1 = event (BiLSTM) stream
     int stage;
-    GemmCfg cfg;
-    int launch_index;    // index into the plan's GemmLaunch array
-    int total_tiles;
-    // elementwise params
-    const float* in = nullptr;
-    float* out = nullptr;
-    int a = 0, b = 0, c = 0, d = 0;
-    FusedArgs fa{};                       // OP_FUSED (bf16 modes: the first module of the chain)
-    FusedChain fc{};                      // OP_FUSED, bf16 modes: consecutive modules of one width class in ONE launch
+    bool after_join = false;              // joint model: runs on stream 0 once the event stream has joined it
+    GemmOp gemm{};                        // OP_GEMM
+    Stem1Op stem1{};                      // OP_STEM1
+    PoolOp pool{};                        // OP_MAXPOOL, OP_AVGPOOL
+    LstmDiagOp lstm{};                    // OP_LSTM
+    FusedChain fc{};                      // OP_FUSED: consecutive modules of one width class in ONE launch
+    int tm = 0;                           // OP_FUSED: 32-row m-tiles per workgroup tile
     Stem23Args sa{};                      // OP_STEM23
     HeadFoldedArgs ha{};                  // OP_HEADF
     SplitDense sd{};                      // OP_DENSES
     LstmXproj xp{};                       // OP_XPROJ
-    int tm = 0;
     double flops = 0;                     // algorithmic FLOPs of this launch
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // profiling mode only
     bool pending = false;
@@ -72,28 +84,10 @@ struct Op {
     double run_flops = 0;
 };
 
-// per-kernel accumulators (one entry per __global__ function / template instantiation)
-enum KernelClass { K_GEMM_CONV = 0, K_GEMM_FC, K_GEMM_LSTM, K_GEMM_CONV_WIDE, K_GEMM_CONV_POOL, K_GEMM_FC_DENSE, K_GEMM_LSTM_DENSE, K_FUSED1, K_FUSED2, K_FUSED3, K_STEM1, K_MAXPOOL, K_AVGPOOL, K_HEAD,
-                   K_GEMM_BCONV, K_GEMM_BCONV_POOL, K_GEMM_BFC, K_GEMM_BFC_DENSE, K_PACKEV, K_GEMM_BLSTM, K_GEMM_BLSTM_DENSE, K_FUSEDB1, K_FUSEDB2, K_FUSEDB3, K_GEMM_LSTM_T, K_GEMM_LSTM_T_DENSE, K_GEMM_BLSTM_T, K_GEMM_BLSTM_T_DENSE, K_LSTM_CELL1, K_LSTM_CELL2, K_LSTM_CELL4, K_LSTM_LDS1, K_LSTM_LDS2, K_STEM23, K_HEADF, K_LSTM_B11, K_LSTM_B12, K_LSTM_B22, K_STEM23B, K_FUSEDS1, K_FUSEDS2, K_FUSEDS3, K_LSTM_S11, K_LSTM_S12, K_LSTM_S22, K_DENSE_SPLIT, K_STEM23S, K_LSTM_XPROJ, K_LSTM_S28, K_EXTRACT_STATS, K_EXTRACT_SITES, K_COUNT };
-const char* const kKernelNames[K_COUNT] = {"gemm_kernel<1,2,4,1,0,0,1,1>", "gemm_kernel<1,3,4,1,0,0,2,1>", "gemm_kernel<1,4,4,1,1,0,1,1>",
-                                           "gemm_kernel<2,2,2,2,0,0,1,1>", "gemm_kernel<1,2,4,1,0,1,1,1>", "gemm_kernel<1,3,4,1,0,2,2,1>",
-                                           "gemm_kernel<1,4,4,1,1,2,1,1>", "inception_fused_kernel<1>",
-                                           "inception_fused_kernel<2>", "inception_fused_kernel<3>", "stem1_kernel",
-                                           "maxpool_s2_kernel", "avgpool7_kernel", "head_kernel",
-                                           "gemm_kernel<1,2,4,1,0,0,1,1,bf16>", "gemm_kernel<1,2,4,1,0,1,1,1,bf16>",
-                                           "gemm_kernel<4,2,1,4,0,0,2,1,bf16>", "gemm_kernel<4,2,1,4,0,2,2,1,bf16>",
-                                           "pack_event_feat_bf16_kernel", "gemm_kernel<1,4,4,1,1,0,3,1,bf16>",
-                                           "gemm_kernel<1,4,4,1,1,2,3,1,bf16>", "inception_fused_bf16_kernel<1>",
-                                           "inception_fused_bf16_kernel<2>", "inception_fused_bf16_kernel<3>",
-                                           "gemm_kernel<1,1,4,1,2,0,1,1>", "gemm_kernel<1,1,4,1,2,2,1,1>",
-                                           "gemm_kernel<1,1,4,1,2,0,3,1,bf16>", "gemm_kernel<1,1,4,1,2,2,3,1,bf16>",
-                                           "lstm_cell_kernel<1>", "lstm_cell_kernel<2>", "lstm_cell_kernel<4>",
-                                           "lstm_cell_lds_kernel<1>", "lstm_cell_lds_kernel<2>", "stem23_kernel", "head_folded_kernel",
-                                           "lstm_cell_bf16_kernel<1,1>", "lstm_cell_bf16_kernel<1,2>", "lstm_cell_bf16_kernel<2,2>", "stem23_bf16_kernel",
-                                           "inception_fused_split_kernel<1>", "inception_fused_split_kernel<2>", "inception_fused_split_kernel<3>",
-                                           "lstm_cell_split_kernel<1,1>", "lstm_cell_split_kernel<1,2>", "lstm_cell_split_kernel<2,2>",
-                                           "dense_split_kernel (+ pack_joint_split_kernel)", "stem23_split_kernel", "lstm_xproj_kernel", "lstm_cell_split_kernel<1,2,4,2>",
-                                           "extract_stats_kernel", "extract_sites_kernel"};
+// names of the kernel table, by position (what ds_get_kernel_stat reports)
+#define DS_KERNEL_NAME(id, name) name,
+const char* const kKernelNames[K_COUNT] = {DS_KERNEL_TABLE(DS_KERNEL_NAME)};
+#undef DS_KERNEL_NAME
 struct KernelStat {
     int64_t launches = 0;
     double total_ms = 0;
@@ -196,7 +190,6 @@ struct ds_handle {
     int fuse_min_tiles = 128; // fused-module grids keep at least this many workgroups when the batch allows it
     bool lstm_bf16 = false;   // DS_PRECISION_BF16_ALL: additionally bf16 h / weight operands in the LSTM matmuls (fp32 accumulate,
                               // gates and cell state; the layer-0 input projection stays an fp32 table lookup)
-    bool lstm_frag = false;   // fp32 BiLSTM cells: lstm_cell_kernel on fragment-major h / c (every mode but DS_PRECISION_BF16_ALL)
     int Bp32 = 0;             // max_batch rounded up to whole 32-site m-tiles (rows of the fragment-major buffers)
     int JP = 0;           // J rounded up to a whole K chunk (32 bf16)
     bool finalized = false;
@@ -219,7 +212,6 @@ struct ds_handle {
     float* fc2 = nullptr;
     float* w12f = nullptr;    // fold_fc: [J][C] = (avgpool^T on the signal rows) (W1 W2), float64 product rounded once
 
-    bool debug_keep_pool = false;   // keep the stand-alone maxpool kernels (diagnostic)
     const float* zero_seg = nullptr;
     unsigned long long* dbg_stamps = nullptr;   // [NMOD][1024 wgs][2 waves][8] when DS_TUNE_DEBUG_STAMPS is set
     unsigned long long* dbg_lstm = nullptr;     // [32 diagonals][1024 wgs][8] stamps of the fp32 BiLSTM cell launches
@@ -640,8 +632,40 @@ int alloc_workspace(ds_handle* h)
 // bytes per MFMA win: 647 k against 623 k sites/s (three-step), 849 k against 802 k (folded) at 512 sites, 8 slots. Tiny forwards keep
 // the small tile (too few 128 x 128 workgroups to fill anything).
 #ifndef DS_SPLIT_LSTM_TILE
-#define DS_SPLIT_LSTM_TILE(n) ((n) >= 256 ? 322 : 311)
+#define DS_SPLIT_LSTM_TILE(n) ((n) >= 256 ? LT_S22 : LT_S11)
 #endif
+
+// The BiLSTM tile of a forward of n sites: ds_config.reserved[3] (DS_LSTM_TILING_*) names a shape, `cells` the kernel family that
+// runs it; a shape the family does not have (and DS_LSTM_TILING_AUTO) is the automatic choice by n.
+//   fp32 cells: n-tiles per wave 1 fills the GPU at <= 768 sites per forward (768 workgroups per full diagonal at 512), wider tiles
+//   re-read the activation fragments less at bigger batches; bf16-operand and split cells: workgroup tile 64 x 64 .. 128 x 128.
+LstmTile choose_lstm_tile(int tiling, Operands cells, int n)
+{
+    switch (cells) {
+    case OPS_FP32:
+        return tiling == DS_LSTM_TILING_NARROW ? LT_F1 : tiling == DS_LSTM_TILING_WIDE ? LT_F4 : tiling == DS_LSTM_TILING_LDS1 ? LT_LDS1
+               : tiling == DS_LSTM_TILING_LDS2 ? LT_LDS2 : n <= 1024 ? LT_LDS1 : LT_LDS2;
+    case OPS_BF16:
+        return tiling == DS_LSTM_TILING_NARROW ? LT_B11 : tiling == DS_LSTM_TILING_LDS1 ? LT_B12 : tiling == DS_LSTM_TILING_WIDE ? LT_B22
+               : n >= 2048 ? LT_B22 : n > 768 ? LT_B12 : LT_B11;
+    case OPS_SPLIT:
+        return tiling == DS_LSTM_TILING_NARROW ? LT_S11 : tiling == DS_LSTM_TILING_LDS1 ? LT_S12 : tiling == DS_LSTM_TILING_WIDE ? LT_S22
+               : tiling == DS_LSTM_TILING_WIDE8 ? LT_S28 : DS_SPLIT_LSTM_TILE(n);
+    }
+    return LT_COUNT;
+}
+
+KernelClass gemm_kernel_class(GemmCfg cfg)
+{
+    switch (cfg) {
+    case CFG_CONV: return K_GEMM_CONV;             case CFG_BCONV: return K_GEMM_BCONV;
+    case CFG_CONV_POOL: return K_GEMM_CONV_POOL;   case CFG_BCONV_POOL: return K_GEMM_BCONV_POOL;
+    case CFG_FC: return K_GEMM_FC;                 case CFG_BFC: return K_GEMM_BFC;
+    case CFG_FC_DENSE: return K_GEMM_FC_DENSE;     case CFG_BFC_DENSE: return K_GEMM_BFC_DENSE;
+    case CFG_CONV_WIDE: return K_GEMM_CONV_WIDE;
+    }
+    return K_COUNT;
+}
 
 int module_width(const ds_handle* h, int m) { return m < 3 ? h->wa : (m < 8 ? h->wb : h->wc); }
 
@@ -699,240 +723,263 @@ int stage_id(ds_handle* h, const std::string& name, int stream)
     return (int)h->stages.size() - 1;
 }
 
-int build_plan(ds_handle* h, int n, Plan* plan)
+Op make_op(OpKind kind, KernelClass kernel, int stream, int stage)
 {
-    plan->n = n;
-    std::vector<Op> cnn, rnn;
-    auto& LS = plan->launches;
-    const bool first_plan = !h->stages_done;
-    const bool bf = h->bf16;
-    auto U = [&](int elems) { return bf ? elems / 2 : elems; };                // elements -> 4-byte units of the A operand
-    auto eoff = [&](float* p, size_t elems) { return bf ? reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(p) + elems) : p + elems; };
-    const int CL = bf ? 256 : INC_OUT;                                         // channel pitch of module outputs
-    auto add_gemm_op = [&](std::vector<Op>& list, int stream, int stage, GemmCfg cfg, const GemmLaunch& L, double kscale = 1.0) {
-        Op op{};
-        op.kind = OP_GEMM; op.stream = stream; op.stage = stage; op.cfg = cfg;
-        op.launch_index = (int)LS.size(); op.total_tiles = L.total_tiles;
+    Op op{};
+    op.kind = kind; op.kernel = kernel; op.stream = stream; op.stage = stage;
+    return op;
+}
+
+// What the parts of build_plan share: the ops of the two independent branches and of the joint model in issue order, and the
+// bookkeeping every op goes through (add_op).
+struct Planner {
+    ds_handle* h;
+    Plan* plan;
+    int n;
+    bool first_plan;                      // the handle's first plan fills the stage table (launches and FLOPs per site)
+    bool bf;                              // DS_PRECISION_BF16*: activations are bf16 rows
+    std::vector<Op> cnn, rnn, tail;
+    const float* sig_rows = nullptr;      // module 11's output rows (what the folded head reads)
+
+    Operands rows() const { return bf ? OPS_BF16 : OPS_FP32; }
+    int U(int elems) const { return bf ? elems / 2 : elems; }      // elements -> 4-byte units of the A operand
+    float* eoff(float* p, size_t elems) const { return bf ? reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(p) + elems) : p + elems; }
+    int CL() const { return bf ? 256 : INC_OUT; }                  // channel pitch of module outputs
+
+    // The one way into the plan. On the handle's first plan the op's stage gets a launch and the op's FLOPs per site: every formula
+    // is n times an integer far below 2^53, so flops / n is that integer exactly (the GEMMs' zero-pad scale aside, which always was
+    // flops / n). An op without FLOPs (pools, packing, lstm_xproj's image) counts as a launch only.
+    void add_op(std::vector<Op>& list, const Op& op)
+    {
+        list.push_back(op);
+        if (!first_plan) return;
+        h->stages[op.stage].launches += 1;
+        h->stages[op.stage].flops_per_site += op.flops / n;
+    }
+    void add_gemm_op(std::vector<Op>& list, int stage, GemmCfg cfg, const GemmLaunch& L, double kscale = 1.0)
+    {
+        Op op = make_op(OP_GEMM, gemm_kernel_class(cfg), 0, stage);
+        op.gemm = {cfg, (int)plan->launches.size(), L.total_tiles};
         const bool bf_cfg = cfg >= CFG_BCONV && cfg <= CFG_BFC_DENSE;
         const double kelems = (bf_cfg ? 2.0 : 1.0) * kscale;   // bf16 problems count K in units; kscale removes zero pad
         for (int i = 0; i < L.nprob; ++i) op.flops += 2.0 * L.prob[i].M * (double)L.prob[i].N * L.prob[i].K * kelems;
-        LS.push_back(L);
-        list.push_back(op);
-        if (first_plan) {
-            h->stages[stage].launches += 1;
-            h->stages[stage].flops_per_site += op.flops / n;
-        }
-    };
-    auto add_ew_op = [&](std::vector<Op>& list, Op op) {
-        list.push_back(op);
-        if (first_plan) h->stages[op.stage].launches += 1;
-    };
-
-    // ================= signal model (stream 0) — layers.py:181-239 =================
-    int st = 0;
-    const float* sig_rows = nullptr;      // module 11's output rows (what the folded head reads)
-    if (h->is_cnn) {
-    st = stage_id(h, "stem", 0);
-    {
-        Op op{};
-        op.kind = OP_STEM1; op.stream = 0; op.stage = st; op.in = h->cur->d_signals; op.out = h->cur->stem_pool; op.a = bf;
-        op.flops = 2.0 * h->w1 * 7 * 64 * n;
-        add_ew_op(cnn, op);
-        if (first_plan) h->stages[st].flops_per_site += 2.0 * h->w1 * 7 * 64;
-        const int M = n * h->wa;
-        if (!h->no_fused && h->wa <= 96 && (bf ? stem23_bf16_lds_bytes(h->wa, 1) : stem23_lds_bytes(h->wa, 1)) <= STEM23_MAX_LDS) {
-            // conv_layer2 + conv_layer3 in one kernel (stem23_kernel): tiles of whole sites, conv2's rows never leave LDS
-            Op o2{};
-            o2.kind = OP_STEM23; o2.stream = 0; o2.stage = st; o2.a = bf;
-            o2.sa.X = h->cur->stem_pool; o2.sa.Y = h->cur->conv3o; o2.sa.C2 = h->debug ? h->cur->conv2o : nullptr;
-            o2.sa.Bp2 = h->conv2.Bp; o2.sa.bias2 = h->conv2.bias; o2.sa.Bp3 = h->conv3.Bp; o2.sa.bias3 = h->conv3.bias;
-            o2.sa.n_sites = n; o2.sa.W = h->wa;
-            // sites per tile: as full as 96 rows allow, as long as every CU still gets a tile
-            int spt = std::max(1, 96 / h->wa);
-            while (spt > 1 && (n + spt - 1) / spt < 256) --spt;
-            // the T tile carries two halo rows per site: short sites (signal_len <= 128) at the full 96 rows pass the 80 KB the
-            // kernel may ask for at two workgroups per CU (configure_fused_kernels)
-            while (spt > 1 && (bf ? stem23_bf16_lds_bytes(h->wa, spt) : stem23_lds_bytes(h->wa, spt)) > STEM23_MAX_LDS) --spt;
-            o2.sa.spt = spt;
-            if (h->split && stem23_split_lds_bytes(h->wa, spt) <= 160 * 1024) {      // DS_PRECISION_BF16X3: split operands (ds_split.hip)
-                o2.a = 2;
-                o2.sa.Bp2 = h->conv2.Bps; o2.sa.Bp3 = h->conv3.Bps;
-            }
-            o2.flops = 2.0 * M * (64.0 * 128 + 384.0 * 256);
-            add_ew_op(cnn, o2);
-            if (first_plan) h->stages[st].flops_per_site += 2.0 * h->wa * (64.0 * 128 + 384.0 * 256);
-        } else {
-        GemmLaunch L{};
-        const GemmCfg ccfg = bf ? CFG_BCONV : CFG_CONV;
-        GemmProblem P = base_problem(M, 128, h->wa, h->conv2);                 // conv_layer2 1x1 (layers.py:192-197)
-        add_seg(P, h->cur->stem_pool, U(64), 0, U(64));
-        add_out(P, h->cur->conv2o, 128, 0, 128, 1, nullptr, 0, bf);
-        add_tiles(L, P, ccfg, h->zero_seg);
-        add_gemm_op(cnn, 0, st, ccfg, L);
-        GemmLaunch L3{};
-        GemmProblem P3 = base_problem(M, 256, h->wa, h->conv3);                // conv_layer3 1x3 (layers.py:198-203)
-        for (int t = 0; t < 3; ++t) add_seg(P3, h->cur->conv2o, U(128), t - 1, U(128));
-        add_out(P3, h->cur->conv3o, 256, 0, 256, 1, nullptr, 0, bf);
-        add_tiles(L3, P3, ccfg, h->zero_seg);
-        add_gemm_op(cnn, 0, st, ccfg, L3);
-        }
+        plan->launches.push_back(L);
+        add_op(list, op);
     }
+};
+
+// stem: conv1 + pool (stem1_kernel), then conv_layer2 + conv_layer3                                  layers.py:183-203
+void plan_stem(Planner& P)
+{
+    ds_handle* h = P.h;
+    const int n = P.n, st = stage_id(h, "stem", 0), M = n * h->wa;
+    const bool bf = P.bf;
+    Op op = make_op(OP_STEM1, K_STEM1, 0, st);
+    op.operands = P.rows();
+    op.stem1 = {h->cur->d_signals, h->cur->stem_pool};
+    op.flops = 2.0 * h->w1 * 7 * 64 * n;
+    P.add_op(P.cnn, op);
+    if (!h->no_fused && h->wa <= 96 && (bf ? stem23_bf16_lds_bytes(h->wa, 1) : stem23_lds_bytes(h->wa, 1)) <= STEM23_MAX_LDS) {
+        // conv_layer2 + conv_layer3 in one kernel (stem23_kernel): tiles of whole sites, conv2's rows never leave LDS
+        // sites per tile: as full as 96 rows allow, as long as every CU still gets a tile
+        int spt = std::max(1, 96 / h->wa);
+        while (spt > 1 && (n + spt - 1) / spt < 256) --spt;
+        // the T tile carries two halo rows per site: short sites (signal_len <= 128) at the full 96 rows pass the 80 KB the
+        // kernel may ask for at two workgroups per CU (configure_fused_kernels)
+        while (spt > 1 && (bf ? stem23_bf16_lds_bytes(h->wa, spt) : stem23_lds_bytes(h->wa, spt)) > STEM23_MAX_LDS) --spt;
+        // DS_PRECISION_BF16X3: split operands (ds_split.hip)
+        const Operands ops = (h->split && stem23_split_lds_bytes(h->wa, spt) <= 160 * 1024) ? OPS_SPLIT : P.rows();
+        Op o2 = make_op(OP_STEM23, kStem23Kernels[ops], 0, st);
+        o2.operands = ops;
+        o2.sa.X = h->cur->stem_pool; o2.sa.Y = h->cur->conv3o; o2.sa.C2 = h->debug ? h->cur->conv2o : nullptr;
+        o2.sa.Bp2 = ops == OPS_SPLIT ? h->conv2.Bps : h->conv2.Bp; o2.sa.bias2 = h->conv2.bias;
+        o2.sa.Bp3 = ops == OPS_SPLIT ? h->conv3.Bps : h->conv3.Bp; o2.sa.bias3 = h->conv3.bias;
+        o2.sa.n_sites = n; o2.sa.W = h->wa; o2.sa.spt = spt;
+        o2.flops = 2.0 * M * (64.0 * 128 + 384.0 * 256);
+        P.add_op(P.cnn, o2);
+        return;
+    }
+    const GemmCfg ccfg = bf ? CFG_BCONV : CFG_CONV;
+    GemmLaunch L{};
+    GemmProblem G = base_problem(M, 128, h->wa, h->conv2);                 // conv_layer2 1x1 (layers.py:192-197)
+    add_seg(G, h->cur->stem_pool, P.U(64), 0, P.U(64));
+    add_out(G, h->cur->conv2o, 128, 0, 128, 1, nullptr, 0, bf);
+    add_tiles(L, G, ccfg, h->zero_seg);
+    P.add_gemm_op(P.cnn, st, ccfg, L);
+    GemmLaunch L3{};
+    GemmProblem G3 = base_problem(M, 256, h->wa, h->conv3);                // conv_layer3 1x3 (layers.py:198-203)
+    for (int t = 0; t < 3; ++t) add_seg(G3, h->cur->conv2o, P.U(128), t - 1, P.U(128));
+    add_out(G3, h->cur->conv3o, 256, 0, 256, 1, nullptr, 0, bf);
+    add_tiles(L3, G3, ccfg, h->zero_seg);
+    P.add_gemm_op(P.cnn, st, ccfg, L3);
+}
+
+// Inception module m as ONE fused launch, or as one more module of the previous launch's chain. pool_win > 0: the stride-2 maxpool
+// in front of the module is taken while staging its input.
+void plan_module_fused(Planner& P, int m, int st, const float* x, float* y, int cin, int pool_win, int pool_pad)
+{
+    ds_handle* h = P.h;
+    const int n = P.n, W = module_width(h, m), M = n * W;
+    // tile = spt whole sites (<= 96 rows). Pick the spt that minimises padded rows (= matrix-pipe time) while keeping >= 128
+    // workgroups when the batch allows it: with several forwards in flight the CUs a short grid leaves idle are taken by other
+    // kernels, so fewer, fuller tiles win (W = 23 at 512 sites: 128 tiles of 92/96 rows instead of 512 tiles of 23/32 rows, +2 %).
+    int best_spt = 1; long best_rows = -1;
+    for (int spt = 1; spt * W <= 96 && spt <= h->fuse_max_spt; ++spt) {
+        const int tiles = (n + spt - 1) / spt;
+        if (spt > 1 && tiles < std::min(h->fuse_min_tiles, n)) break;
+        const long rows = (long)tiles * ((spt * W + 31) / 32) * 32;
+        if (best_rows < 0 || rows < best_rows) { best_rows = rows; best_spt = spt; }
+    }
+    const int tm = (best_spt * W + 31) / 32;
+    // DS_PRECISION_BF16X3: the split-operand kernel (ds_split.hip) on the three-term panels; a module whose input is
+    // not a whole number of 16-channel chunks of 240 / 256 channels does not exist in this network
+    const bool sp = h->split && (cin == 240 || cin == 256) && inception_fused_split_lds_bytes(tm, W, best_spt) <= 160 * 1024;
+    const Operands ops = sp ? OPS_SPLIT : P.rows();
+    Op op = make_op(OP_FUSED, kFusedKernels[ops][tm - 1], 0, st);
+    op.operands = ops; op.tm = tm;
+    FusedArgs& fa = op.fc.m[0];
+    op.fc.nmod = 1;
+    fa.X = x; fa.Y = y; fa.n_sites = n; fa.W = W; fa.cin = P.bf ? 128 : cin; fa.spt = best_spt;   // bf16: row pitch in units
+    fa.pool_win = pool_win; fa.pool_pad = pool_pad;
+    fa.Bp1 = sp ? h->m_f1[m].Bps : h->m_f1[m].Bp; fa.bias1 = h->m_f1[m].bias;
+    fa.Bp3b = sp ? h->m_b3b[m].Bps : h->m_b3b[m].Bp; fa.bias3b = h->m_b3b[m].bias;
+    fa.Bp4b = sp ? h->m_b4b[m].Bps : h->m_b4b[m].Bp; fa.bias4b = h->m_b4b[m].bias;
+    fa.Bp5b = sp ? h->m_b5b[m].Bps : h->m_b5b[m].Bp; fa.bias5b = h->m_b5b[m].bias;
+    fa.Bp5c = sp ? h->m_b5c[m].Bps : h->m_b5c[m].Bp; fa.bias5c = h->m_b5c[m].bias;
+    fa.dbg = h->dbg_stamps ? h->dbg_stamps + (size_t)m * 1024 * 16 : nullptr;
+    fa.write_rows = 1;
+    op.flops = 2.0 * M * ((double)cin * 240 + 96 * 48 + 160 * 48 + 96 * 64 + 64 * 48);
+    // a module joins the launch of the module before it when both run the same kernel on the same tiling of the batch and it reads
+    // that module's rows as they are (no stride-2 pool in between): every workgroup then takes its sites through the whole
+    // chain (ds_internal.h FusedChain)
+    Op* prev = (!P.cnn.empty() && P.cnn.back().kind == OP_FUSED) ? &P.cnn.back() : nullptr;
+    if (prev && prev->fc.nmod < FUSED_CHAIN_MAX && pool_win == 0 && prev->fc.m[0].W == W && prev->fc.m[0].spt == best_spt &&
+        prev->kernel == op.kernel && prev->fc.m[prev->fc.nmod - 1].Y == fa.X && fa.Y != prev->fc.m[0].X && !h->serial_modules) {
+        // bf16: rows of a chain's inner modules never leave the CU (unless the taps of debug mode want them)
+        if (P.bf && !h->debug) prev->fc.m[prev->fc.nmod - 1].write_rows = 0;
+        prev->fc.m[prev->fc.nmod++] = fa;
+        prev->flops += op.flops;
+        // no op of its own: the launch (and, in the profiles, the time) is booked on the chain's first module, but the FLOPs a
+        // site costs in THIS module stay on this module's stage
+        if (P.first_plan) h->stages[st].flops_per_site += op.flops / n;
+    } else {
+        P.add_op(P.cnn, op);
+    }
+}
+
+// Inception module m layer by layer: four grouped-GEMM launches (DS_TUNE_NO_FUSED, and windows too long for the fused tile)
+void plan_module_layers(Planner& P, int m, int st, const float* x, float* y, int cin)
+{
+    ds_handle* h = P.h;
+    const bool bf = P.bf;
+    const int W = module_width(h, m), M = P.n * W, CL = P.CL();
+    const GemmCfg ccfg = bf ? CFG_BCONV : CFG_CONV, pcfg = bf ? CFG_BCONV_POOL : CFG_CONV_POOL;
+    {   // five 1x1 convs on the module input + branch1 (maxpool on load)   layers.py:90-101,103,112,121-126
+        // bf16 mode: rows have a 256-channel pitch (cin = 240 inputs carry 16 zero channels, matched by zero weight rows)
+        const int xld = bf ? 256 : cin;
+        const double ks = (double)cin / xld;
+        GemmLaunch L{};
+        GemmProblem G = base_problem(M, 192, W, h->m_s1[m]);
+        add_seg(G, x, P.U(xld), 0, P.U(xld));
+        add_out(G, P.eoff(y, 48), CL, 0, 48, 1, nullptr, 0, bf);        // branch2
+        add_out(G, h->cur->tmpS, 48, 48, 48, 0);                        // branch5 stem (BN, no ReLU), kept fp32
+        add_out(G, h->cur->tmpA, 96, 96, 96, 1, nullptr, 0, bf);        // b3a | b4a | b5a
+        add_tiles(L, G, ccfg, h->zero_seg);
+        P.add_gemm_op(P.cnn, st, ccfg, L, ks);
+        GemmLaunch L1{};
+        GemmProblem Q = base_problem(M, 48, W, h->m_b1[m]);
+        Q.a_mode = 1;                                   // maxpool(3, s1) fused into the A load (layers.py:90-91)
+        add_seg(Q, x, P.U(xld), 0, P.U(xld));
+        add_out(Q, y, CL, 0, 48, 1, nullptr, 0, bf);    // branch1
+        add_tiles(L1, Q, pcfg, h->zero_seg);
+        P.add_gemm_op(P.cnn, st, pcfg, L1, ks);
+    }
+    {   // second-stage convs from the 32-channel intermediates             layers.py:106-110,115-119,127-131
+        GemmLaunch L{};
+        GemmProblem G = base_problem(M, 48, W, h->m_b3b[m]);
+        for (int t = 0; t < 3; ++t) add_seg(G, P.eoff(h->cur->tmpA, 0), P.U(96), t - 1, P.U(32));
+        add_out(G, P.eoff(y, 96), CL, 0, 48, 1, nullptr, 0, bf);
+        add_tiles(L, G, ccfg, h->zero_seg);
+        GemmProblem Q = base_problem(M, 48, W, h->m_b4b[m]);
+        for (int t = 0; t < 5; ++t) add_seg(Q, P.eoff(h->cur->tmpA, 32), P.U(96), t - 2, P.U(32));
+        add_out(Q, P.eoff(y, 144), CL, 0, 48, 1, nullptr, 0, bf);
+        add_tiles(L, Q, ccfg, h->zero_seg);
+        GemmProblem R = base_problem(M, 64, W, h->m_b5b[m]);
+        for (int t = 0; t < 3; ++t) add_seg(R, P.eoff(h->cur->tmpA, 64), P.U(96), t - 1, P.U(32));
+        add_out(R, h->cur->tmpB, 64, 0, 64, 1, nullptr, 0, bf);
+        add_tiles(L, R, ccfg, h->zero_seg);
+        P.add_gemm_op(P.cnn, st, ccfg, L);
+    }
+    {   // residual tail: relu(stem + BN(1x1 48 of tmpB))                    layers.py:132-138
+        GemmLaunch L{};
+        GemmProblem G = base_problem(M, 48, W, h->m_b5c[m]);
+        add_seg(G, h->cur->tmpB, P.U(64), 0, P.U(64));
+        add_out(G, P.eoff(y, 192), CL, 0, 48, 1, h->cur->tmpS, 48, bf);
+        add_tiles(L, G, ccfg, h->zero_seg);
+        P.add_gemm_op(P.cnn, st, ccfg, L);
+    }
+}
+
+// ================= signal model (stream 0) — layers.py:181-239 =================
+void plan_signal_model(Planner& P)
+{
+    ds_handle* h = P.h;
+    plan_stem(P);
     const float* x = h->cur->conv3o;
     int cin = 256;
     int pend_pool_win = 0, pend_pool_pad = 0;      // a stride-2 maxpool waiting to be folded into the next fused module
     for (int m = 0; m < NMOD; ++m) {
         char nm[32];
         snprintf(nm, sizeof nm, "module%d", m + 1);
-        st = stage_id(h, nm, 0);
-        const int W = module_width(h, m), M = n * W;
+        const int st = stage_id(h, nm, 0);
+        const int W = module_width(h, m);
         float* y = h->cur->modout[m];
-        if (!h->no_fused && W <= 96) {
-            // one fused launch per module; tile = spt whole sites (<= 96 rows). Pick the spt that minimises padded
-            // rows (= matrix-pipe time) while keeping >= 128 workgroups when the batch allows it: with several
-            // forwards in flight the CUs a short grid leaves idle are taken by other kernels, so fewer, fuller
-            // tiles win (W = 23 at 512 sites: 128 tiles of 92/96 rows instead of 512 tiles of 23/32 rows, +2 %).
-            int best_spt = 1; long best_rows = -1;
-            for (int spt = 1; spt * W <= 96 && spt <= h->fuse_max_spt; ++spt) {
-                const int tiles = (n + spt - 1) / spt;
-                if (spt > 1 && tiles < std::min(h->fuse_min_tiles, n)) break;
-                const long rows = (long)tiles * ((spt * W + 31) / 32) * 32;
-                if (best_rows < 0 || rows < best_rows) { best_rows = rows; best_spt = spt; }
-            }
-            Op op{};
-            op.kind = OP_FUSED; op.stream = 0; op.stage = st;
-            op.tm = (best_spt * W + 31) / 32;
-            op.fa.X = x; op.fa.Y = y; op.fa.n_sites = n; op.fa.W = W; op.fa.cin = bf ? 128 : cin; op.fa.spt = best_spt;   // bf16: row pitch in units
-            op.fa.pool_win = pend_pool_win; op.fa.pool_pad = pend_pool_pad;
-            pend_pool_win = 0;
-            // DS_PRECISION_BF16X3: the split-operand kernel (ds_split.hip) on the three-term panels; a module whose input is
-            // not a whole number of 16-channel chunks of 240 / 256 channels does not exist in this network
-            const bool sp = h->split && (cin == 240 || cin == 256) && inception_fused_split_lds_bytes(op.tm, W, best_spt) <= 160 * 1024;
-            op.d = sp ? 3 : 0;
-            op.fa.Bp1 = sp ? h->m_f1[m].Bps : h->m_f1[m].Bp; op.fa.bias1 = h->m_f1[m].bias;
-            op.fa.Bp3b = sp ? h->m_b3b[m].Bps : h->m_b3b[m].Bp; op.fa.bias3b = h->m_b3b[m].bias;
-            op.fa.Bp4b = sp ? h->m_b4b[m].Bps : h->m_b4b[m].Bp; op.fa.bias4b = h->m_b4b[m].bias;
-            op.fa.Bp5b = sp ? h->m_b5b[m].Bps : h->m_b5b[m].Bp; op.fa.bias5b = h->m_b5b[m].bias;
-            op.fa.Bp5c = sp ? h->m_b5c[m].Bps : h->m_b5c[m].Bp; op.fa.bias5c = h->m_b5c[m].bias;
-            op.fa.dbg = h->dbg_stamps ? h->dbg_stamps + (size_t)m * 1024 * 16 : nullptr;
-            op.fa.write_rows = 1;
-            op.flops = 2.0 * M * ((double)cin * 240 + 96 * 48 + 160 * 48 + 96 * 64 + 64 * 48);
-            if (first_plan) h->stages[st].flops_per_site += op.flops / n;
-            // a module joins the launch of the module before it when both tile the batch alike and it reads that
-            // module's rows as they are (no stride-2 pool in between): every workgroup then takes its sites through the whole
-            // chain (ds_internal.h FusedChain). Stage times of a chain are booked on its first module.
-            Op* prev = (!cnn.empty() && cnn.back().kind == OP_FUSED) ? &cnn.back() : nullptr;
-            if (prev && prev->fc.nmod < FUSED_CHAIN_MAX && op.fa.pool_win == 0 && prev->fa.W == W && prev->fa.spt == best_spt &&
-                prev->tm == op.tm && prev->d == op.d && prev->fc.m[prev->fc.nmod - 1].Y == op.fa.X && op.fa.Y != prev->fc.m[0].X && !h->serial_modules) {
-                // bf16: rows of a chain's inner modules never leave the CU (unless the taps of debug mode want them)
-                if (bf && !h->debug) prev->fc.m[prev->fc.nmod - 1].write_rows = 0;
-                prev->fc.m[prev->fc.nmod++] = op.fa;
-                prev->flops += op.flops;
-            } else {
-                op.fc.m[0] = op.fa; op.fc.nmod = 1;
-                add_ew_op(cnn, op);
-            }
-        } else {
-        {   // five 1x1 convs on the module input + branch1 (maxpool on load)   layers.py:90-101,103,112,121-126
-            // bf16 mode: rows have a 256-channel pitch (cin = 240 inputs carry 16 zero channels, matched by zero weight rows)
-            const int xld = bf ? 256 : cin;
-            const double ks = (double)cin / xld;
-            const GemmCfg ccfg = bf ? CFG_BCONV : CFG_CONV, pcfg = bf ? CFG_BCONV_POOL : CFG_CONV_POOL;
-            GemmLaunch L{};
-            GemmProblem P = base_problem(M, 192, W, h->m_s1[m]);
-            add_seg(P, x, U(xld), 0, U(xld));
-            add_out(P, eoff(y, 48), CL, 0, 48, 1, nullptr, 0, bf);          // branch2
-            add_out(P, h->cur->tmpS, 48, 48, 48, 0);                        // branch5 stem (BN, no ReLU), kept fp32
-            add_out(P, h->cur->tmpA, 96, 96, 96, 1, nullptr, 0, bf);        // b3a | b4a | b5a
-            add_tiles(L, P, ccfg, h->zero_seg);
-            add_gemm_op(cnn, 0, st, ccfg, L, ks);
-            GemmLaunch L1{};
-            GemmProblem Q = base_problem(M, 48, W, h->m_b1[m]);
-            Q.a_mode = 1;                                   // maxpool(3, s1) fused into the A load (layers.py:90-91)
-            add_seg(Q, x, U(xld), 0, U(xld));
-            add_out(Q, y, CL, 0, 48, 1, nullptr, 0, bf);    // branch1
-            add_tiles(L1, Q, pcfg, h->zero_seg);
-            add_gemm_op(cnn, 0, st, pcfg, L1, ks);
-        }
-        {   // second-stage convs from the 32-channel intermediates             layers.py:106-110,115-119,127-131
-            const GemmCfg ccfg = bf ? CFG_BCONV : CFG_CONV;
-            GemmLaunch L{};
-            GemmProblem P = base_problem(M, 48, W, h->m_b3b[m]);
-            for (int t = 0; t < 3; ++t) add_seg(P, eoff(h->cur->tmpA, 0), U(96), t - 1, U(32));
-            add_out(P, eoff(y, 96), CL, 0, 48, 1, nullptr, 0, bf);
-            add_tiles(L, P, ccfg, h->zero_seg);
-            GemmProblem Q = base_problem(M, 48, W, h->m_b4b[m]);
-            for (int t = 0; t < 5; ++t) add_seg(Q, eoff(h->cur->tmpA, 32), U(96), t - 2, U(32));
-            add_out(Q, eoff(y, 144), CL, 0, 48, 1, nullptr, 0, bf);
-            add_tiles(L, Q, ccfg, h->zero_seg);
-            GemmProblem R = base_problem(M, 64, W, h->m_b5b[m]);
-            for (int t = 0; t < 3; ++t) add_seg(R, eoff(h->cur->tmpA, 64), U(96), t - 1, U(32));
-            add_out(R, h->cur->tmpB, 64, 0, 64, 1, nullptr, 0, bf);
-            add_tiles(L, R, ccfg, h->zero_seg);
-            add_gemm_op(cnn, 0, st, ccfg, L);
-        }
-        {   // residual tail: relu(stem + BN(1x1 48 of tmpB))                    layers.py:132-138
-            const GemmCfg ccfg = bf ? CFG_BCONV : CFG_CONV;
-            GemmLaunch L{};
-            GemmProblem P = base_problem(M, 48, W, h->m_b5c[m]);
-            add_seg(P, h->cur->tmpB, U(64), 0, U(64));
-            add_out(P, eoff(y, 192), CL, 0, 48, 1, h->cur->tmpS, 48, bf);
-            add_tiles(L, P, ccfg, h->zero_seg);
-            add_gemm_op(cnn, 0, st, ccfg, L);
-        }
-        }
+        if (!h->no_fused && W <= 96) plan_module_fused(P, m, st, x, y, cin, pend_pool_win, pend_pool_pad);
+        else plan_module_layers(P, m, st, x, y, cin);
+        pend_pool_win = 0;
         x = y; cin = INC_OUT;
         if (m == 2 || m == 7) {   // maxpool_layer2/3                            layers.py:211-213,224-226
             const int wout = m == 2 ? h->wb : h->wc, pad = m == 2 ? h->pl_pool2 : h->pl_pool3;
-            if (!h->no_fused && wout <= 96 && !h->debug_keep_pool) {
+            if (!h->no_fused && wout <= 96) {
                 pend_pool_win = W; pend_pool_pad = pad;      // folded into module m+2's staging: no launch, no buffer
             } else {
-                Op op{};
-                op.kind = OP_MAXPOOL; op.stream = 0; op.stage = stage_id(h, "pools", 0);
-                op.in = y; op.out = m == 2 ? h->cur->pool2 : h->cur->pool3;
-                op.a = W; op.b = wout; op.c = pad; op.d = CL;
-                add_ew_op(cnn, op);
-                x = op.out;
+                Op op = make_op(OP_MAXPOOL, K_MAXPOOL, 0, stage_id(h, "pools", 0));
+                op.operands = P.rows();
+                op.pool = {y, m == 2 ? h->cur->pool2 : h->cur->pool3, W, wout, pad, P.CL()};
+                P.add_op(P.cnn, op);
+                x = op.pool.out;
             }
         }
     }
-    sig_rows = x;
+    P.sig_rows = x;
     if (!h->fold_fc) {   // avgpool_layer1 + flatten (the folded head's matrix carries the pool: it reads module 11's rows)   layers.py:233-238
-        Op op{};
-        op.kind = OP_AVGPOOL; op.stream = 0; op.stage = stage_id(h, "pools", 0);
-        op.in = x; op.out = bf ? h->cur->joint : h->cur->sigfeat; op.a = h->wc; op.d = INC_OUT;
-        add_ew_op(cnn, op);
+        Op op = make_op(OP_AVGPOOL, K_AVGPOOL, 0, stage_id(h, "pools", 0));
+        op.operands = P.rows();
+        op.pool = {x, P.bf ? h->cur->joint : h->cur->sigfeat, h->wc, 0, 0, INC_OUT};
+        P.add_op(P.cnn, op);
     }
-    }   // is_cnn
+}
 
-    // ================= event model (stream 1) — layers.py:20-72,161-173 =================
-    // Anti-diagonal wavefront: diagonal d runs cells (layer l, step d-l) of both directions in ONE
-    // grouped launch; cell (l,s) depends only on (l-1,s) and (l,s-1), both on diagonal d-1.
-    st = stage_id(h, "bilstm", 1);
-    const int T = h->T;
-    const bool lbf = h->lstm_bf16;
-    const int HU = lbf ? HID / 2 : HID;                 // floats per site of one h vector (bf16 h: two units per float)
-    const GemmCfg fc_cfg = bf ? (n % 128 == 0 ? CFG_BFC_DENSE : CFG_BFC) : (n % 128 == 0 ? CFG_FC_DENSE : CFG_FC);
+// ================= event model (stream 1) — layers.py:20-72,161-173 =================
+// Anti-diagonal wavefront: diagonal d runs cells (layer l, step d-l) of both directions in ONE
+// grouped launch; cell (l,s) depends only on (l-1,s) and (l,s-1), both on diagonal d-1.
+// Dedicated cell kernels, h / c in MFMA-fragment-major buffers (ds_internal.h LstmCell).
+void plan_event_model(Planner& P)
+{
+    ds_handle* h = P.h;
+    const int n = P.n, T = h->T, st = stage_id(h, "bilstm", 1);
     if (h->is_rnn) {
-        // dedicated cell kernels, h / c in MFMA-fragment-major buffers (ds_internal.h LstmCell). fp32 cells: n-tiles per wave
-        // 1 fills the GPU at <= 768 sites per forward (768 workgroups per full diagonal at 512), wider tiles re-read the
-        // activation fragments less at bigger batches; every width gives the same bits (same K order per element).
-        // bf16-operand cells (DS_PRECISION_BF16_ALL): lstm_cell_bf16_kernel, workgroup tile 64 x 64 .. 128 x 128 by batch.
-        const int mtiles = (n + 31) / 32;
-        const int nt = lbf ? (h->lstm_variant == DS_LSTM_TILING_NARROW ? 211 : h->lstm_variant == DS_LSTM_TILING_LDS1 ? 212
-                              : h->lstm_variant == DS_LSTM_TILING_WIDE ? 222
-                              : n >= 2048 ? 222 : n > 768 ? 212 : 211)
-                       : h->lstm_variant == DS_LSTM_TILING_NARROW ? 1 : h->lstm_variant == DS_LSTM_TILING_WIDE ? 4
-                       : h->lstm_variant == DS_LSTM_TILING_LDS1 ? 101 : h->lstm_variant == DS_LSTM_TILING_LDS2 ? 102
-                       : (n <= 1024 ? 101 : 102);
-        const bool lsp = h->split;                                         // split cells (ds_split.hip): tile code 311 | 312 | 322
-        const int nt_split = h->lstm_variant == DS_LSTM_TILING_NARROW ? 311 : h->lstm_variant == DS_LSTM_TILING_LDS1 ? 312
-                             : h->lstm_variant == DS_LSTM_TILING_WIDE ? 322 : h->lstm_variant == DS_LSTM_TILING_WIDE8 ? 328 : DS_SPLIT_LSTM_TILE(n);
-        const size_t step = lsp ? (size_t)h->Bp32 * HID * 3 / 2 : (size_t)h->Bp32 * HU;      // floats of one time step in H (bf16 h: half; split h: 3/2)
+        const Operands cells = h->split ? OPS_SPLIT : h->lstm_bf16 ? OPS_BF16 : OPS_FP32;
+        const LstmTile tile = choose_lstm_tile(h->lstm_variant, cells, n);
+        const int mtiles = (n + 31) / 32, per_cell = lstm_tiles_per_cell(tile, mtiles);
+        const bool lsp = cells == OPS_SPLIT, lbf = cells == OPS_BF16;
+        // floats of one time step in H (bf16 h: two units per float; split h: 3/2)
+        const size_t step = lsp ? (size_t)h->Bp32 * HID * 3 / 2 : (size_t)h->Bp32 * (lbf ? HID / 2 : HID);
         const bool xpj = h->lstm_xproj && lsp;
         const size_t xstep = (size_t)h->Bp32 * 4 * HID;
         if (xpj) {
-            Op op{};
-            op.kind = OP_XPROJ; op.stream = 1; op.stage = st;
+            // (no FLOPs booked: the launch finishes the two first-step cells, which have no matrix product, and writes the image)
+            Op op = make_op(OP_XPROJ, K_LSTM_XPROJ, 1, st);
             LstmXproj& X = op.xp;
             for (int dir = 0; dir < 2; ++dir) {
                 LstmCell& C = X.cell[dir];
@@ -942,15 +989,14 @@ int build_plan(ds_handle* h, int n, Plan* plan)
                 X.xinit[dir] = h->cur->xproj[dir];
             }
             X.h_step = step; X.x_step = xstep; X.n = n; X.mtiles = mtiles; X.T = T; X.nsteps = h->lstm_xproj_all ? T : 1;
-            rnn.push_back(op);
-            if (first_plan) h->stages[st].launches += 1;
+            P.add_op(P.rnn, op);
         }
         for (int d = xpj ? 1 : 0; d < T + NLAYER - 1; ++d) {      // (diagonal 0 = the two first-step cells of layer 0: done by lstm_xproj_kernel)
             LstmLaunch L;
             memset(&L, 0, sizeof L);
             L.n = n; L.mtiles = mtiles; L.T = T;
             L.dbg = (h->dbg_lstm && d < 32) ? h->dbg_lstm + (size_t)d * 1024 * 8 : nullptr;
-            double flops = 0;
+            Op op = make_op(OP_LSTM, kLstmTiles[tile].kernel, 1, st);
             for (int dir = 0; dir < 2; ++dir)
                 for (int l = 0; l < NLAYER; ++l) {
                     const int sidx = d - l;
@@ -974,69 +1020,55 @@ int build_plan(ds_handle* h, int n, Plan* plan)
                     // the joint FC reads the top layer's final h (fw: t = T-1, bw: t = 0) row-major   layers.py:171-172
                     C.h_row = (l == NLAYER - 1 && sidx == T - 1) ? h->cur->hlast[dir] : nullptr;
                     C.t = t; C.use_feat = l == 0; C.c_zero = sidx == 0;
-                    flops += 2.0 * n * 4 * HID * ((l > 0 ? HID : 0) + (sidx > 0 ? HID : 0));
+                    op.flops += 2.0 * n * 4 * HID * ((l > 0 ? HID : 0) + (sidx > 0 ? HID : 0));
                 }
-            // heaviest cells first (K = 512, then 256, then 0): lstm_logical_tile deals tiles to the CUs in that order
+            // heaviest cells first (K = 512, then 256, then 0): lstm_logical_tile deals tiles to the CUs in that order,
+            // from the workgroup tiles of the two heaviest work classes
             std::stable_sort(L.cell, L.cell + L.ncell, [](const LstmCell& a, const LstmCell& b) {
                 return (a.ax != nullptr) + (a.ah != nullptr) > (b.ax != nullptr) + (b.ah != nullptr);
             });
-            {   // workgroup tiles per work class, for lstm_logical_tile
-                const int ntc = lsp ? nt_split - 100 : nt;      // the split tiles deal workgroups like the bf16 tiles of the same shape
-                const int per_cell = (ntc == 222 || ntc == 228) ? ((mtiles + 3) / 4) * 8 : ntc == 212 ? ((mtiles + 1) / 2) * 8 : ntc == 211 ? ((mtiles + 1) / 2) * 16
-                                     : nt > 100 ? ((mtiles + 1) / 2) * (16 / (nt - 100)) : ((mtiles + 3) / 4) * (32 / nt);
-                L.cls_tiles[0] = L.cls_tiles[1] = 0;
-                for (int i = 0; i < L.ncell; ++i) {
-                    const int k = (L.cell[i].ax != nullptr) + (L.cell[i].ah != nullptr);
-                    if (k == 2) L.cls_tiles[0] += per_cell; else if (k == 1) L.cls_tiles[1] += per_cell;
-                }
+            for (int i = 0; i < L.ncell; ++i) {
+                const int k = (L.cell[i].ax != nullptr) + (L.cell[i].ah != nullptr);
+                if (k == 2) L.cls_tiles[0] += per_cell; else if (k == 1) L.cls_tiles[1] += per_cell;
             }
-            Op op{};
-            op.kind = OP_LSTM; op.stream = 1; op.stage = st;
-            op.launch_index = (int)plan->lstm_launches.size();
-            op.a = L.ncell; op.b = mtiles; op.c = lsp ? nt_split : nt;
-            op.flops = flops;
-            plan->lstm_launches.push_back(L);
-            rnn.push_back(op);
-            if (first_plan) {
-                h->stages[st].launches += 1;
-                h->stages[st].flops_per_site += flops / n;
-            }
+            op.lstm = {(int)P.plan->lstm_launches.size(), tile};
+            P.plan->lstm_launches.push_back(L);
+            P.add_op(P.rnn, op);
         }
     }
-    if (bf && h->is_rnn) {     // the bf16 FC reads [bf16(h_fw(T-1)) | bf16(h_bw(0)) | signal features] from one buffer
-        Op op{};
-        op.kind = OP_PACKEV; op.stream = 1; op.stage = st;
-        add_ew_op(rnn, op);
-    }
+    if (P.bf && h->is_rnn)     // the bf16 FC reads [bf16(h_fw(T-1)) | bf16(h_bw(0)) | signal features] from one buffer
+        P.add_op(P.rnn, make_op(OP_PACKEV, K_PACKEV, 1, st));
+}
 
-    // ================= joint model (stream 0 after join) — layers.py:247-264 =================
-    std::vector<Op> tail;
+// ================= joint model (stream 0 after join) — layers.py:247-264 =================
+void plan_joint_model(Planner& P)
+{
+    ds_handle* h = P.h;
+    const int n = P.n;
+    const bool bf = P.bf;
     if (h->fold_fc) {
-        st = stage_id(h, "head", 0);
-        Op op{};
-        op.kind = OP_HEADF; op.stream = 0; op.stage = st;
+        Op op = make_op(OP_HEADF, K_HEADF, 0, stage_id(h, "head", 0));
         HeadFoldedArgs& a = op.ha;
         if (bf) {
             a.bf16 = 1;
             if (h->is_rnn) { a.seg[a.nseg] = h->cur->joint; a.len[a.nseg] = 2 * HID; a.pitch[a.nseg++] = h->JP; }     // [bf16 h_fw | h_bw] (pack_event_feat_bf16_kernel)
-            if (h->is_cnn) { a.seg[a.nseg] = sig_rows; a.len[a.nseg] = h->wc * 256; a.pitch[a.nseg++] = h->wc * 256; }
+            if (h->is_cnn) { a.seg[a.nseg] = P.sig_rows; a.len[a.nseg] = h->wc * 256; a.pitch[a.nseg++] = h->wc * 256; }
         } else {
-        if (h->is_rnn) {
-            a.seg[a.nseg] = h->cur->hlast[0]; a.len[a.nseg++] = HID;
-            a.seg[a.nseg] = h->cur->hlast[1]; a.len[a.nseg++] = HID;
-        }
-        if (h->is_cnn) { a.seg[a.nseg] = sig_rows; a.len[a.nseg++] = h->SF; }
+            if (h->is_rnn) {
+                a.seg[a.nseg] = h->cur->hlast[0]; a.len[a.nseg++] = HID;
+                a.seg[a.nseg] = h->cur->hlast[1]; a.len[a.nseg++] = HID;
+            }
+            if (h->is_cnn) { a.seg[a.nseg] = P.sig_rows; a.len[a.nseg++] = h->SF; }
         }
         a.w = h->w12f; a.logits = h->cur->logits; a.act = h->cur->act; a.pred = h->cur->pred; a.n = n; a.C = h->C;
         op.flops = 2.0 * h->J * h->C * n;
-        add_ew_op(tail, op);
-        if (first_plan) h->stages[st].flops_per_site += 2.0 * h->J * h->C;
-    } else {
-    st = stage_id(h, "fc1", 0);
+        P.add_op(P.tail, op);
+        return;
+    }
+    const int st = stage_id(h, "fc1", 0);
     if (h->split && h->fc1.Bps && h->cur->jsplit && n >= h->split_dense_min_n) {
         // dense(J, J) with split operands (ds_split.hip): the joint row's segments -> term image -> LDS-DMA ring GEMM
-        Op op{};
-        op.kind = OP_DENSES; op.stream = 0; op.stage = st;
+        Op op = make_op(OP_DENSES, K_DENSE_SPLIT, 0, st);
         SplitDense& d = op.sd;
         int ns = 0;
         if (h->is_rnn) { d.seg[ns] = h->cur->hlast[0]; d.len[ns++] = HID; d.seg[ns] = h->cur->hlast[1]; d.len[ns++] = HID; }
@@ -1054,46 +1086,50 @@ int build_plan(ds_handle* h, int n, Plan* plan)
         // forward -- ragged tails run with few workgroups instead; always 4 ranges cost 8 - 12 % from 1,024 sites)
         if (d.wide) d.splits = std::max(1, std::min(DS_SPLIT_DENSE_PARTS, 256 / ((((h->B + 31) / 32 + 7) / 8) * ((d.ntiles + 5) / 6))));
         d.part_stride = (size_t)h->B * h->J;
-        plan->fc1_parts = d.splits;
+        P.plan->fc1_parts = d.splits;
         op.flops = 2.0 * n * (double)h->J * h->J;
-        add_ew_op(tail, op);
-        if (first_plan) h->stages[st].flops_per_site += 2.0 * (double)h->J * h->J;
+        P.add_op(P.tail, op);
     } else {
+        const GemmCfg fc_cfg = bf ? (n % 128 == 0 ? CFG_BFC_DENSE : CFG_BFC) : (n % 128 == 0 ? CFG_FC_DENSE : CFG_FC);
         GemmLaunch L{};
-        GemmProblem P = base_problem(n, h->J, n, h->fc1);
+        GemmProblem G = base_problem(n, h->J, n, h->fc1);
         // joint = [fw h(T-1) | bw h(0) | signal features]: three A segments, no concat buffer (layers.py:171-172,250-252)
         if (bf) {
-            add_seg(P, h->cur->joint, h->JP / 2, 0, h->JP / 2);
+            add_seg(G, h->cur->joint, h->JP / 2, 0, h->JP / 2);
         } else {
-        if (h->is_rnn) {       // fp32 mode always runs the fp32 cells: their row-major copy of the two final h vectors
-            add_seg(P, h->cur->hlast[0], HID, 0, HID);
-            add_seg(P, h->cur->hlast[1], HID, 0, HID);
+            if (h->is_rnn) {       // fp32 mode always runs the fp32 cells: their row-major copy of the two final h vectors
+                add_seg(G, h->cur->hlast[0], HID, 0, HID);
+                add_seg(G, h->cur->hlast[1], HID, 0, HID);
+            }
+            if (h->is_cnn) add_seg(G, h->cur->sigfeat, h->SF, 0, h->SF);
         }
-        if (h->is_cnn) add_seg(P, h->cur->sigfeat, h->SF, 0, h->SF);
-        }
-        add_out(P, h->cur->fc1o, h->J, 0, h->J, 0);
-        add_tiles(L, P, fc_cfg, h->zero_seg);
-        add_gemm_op(tail, 0, st, fc_cfg, L, bf ? (double)h->J / h->JP : 1.0);
+        add_out(G, h->cur->fc1o, h->J, 0, h->J, 0);
+        add_tiles(L, G, fc_cfg, h->zero_seg);
+        P.add_gemm_op(P.tail, st, fc_cfg, L, bf ? (double)h->J / h->JP : 1.0);
     }
-    st = stage_id(h, "head", 0);
-    {
-        Op op{};
-        op.kind = OP_HEAD; op.stream = 0; op.stage = st;
-        op.flops = 2.0 * h->J * h->C * n;
-        add_ew_op(tail, op);
-        if (first_plan) h->stages[st].flops_per_site += 2.0 * h->J * h->C;
-    }
-    }
+    Op op = make_op(OP_HEAD, K_HEAD, 0, stage_id(h, "head", 0));
+    op.flops = 2.0 * h->J * h->C * n;
+    P.add_op(P.tail, op);
+}
 
-    // merged issue order: alternate the two independent branches, then the tail
+int build_plan(ds_handle* h, int n, Plan* plan)
+{
+    plan->n = n;
+    Planner P{h, plan, n, !h->stages_done, h->bf16};
+    if (h->is_cnn) plan_signal_model(P);
+    plan_event_model(P);
+    plan_joint_model(P);
+
+    // merged issue order: alternate the two independent branches, then the joint model after the join
     size_t i = 0, j = 0;
-    while (i < cnn.size() || j < rnn.size()) {
-        if (i < cnn.size()) plan->ops.push_back(cnn[i++]);
-        if (j < rnn.size()) plan->ops.push_back(rnn[j++]);
+    while (i < P.cnn.size() || j < P.rnn.size()) {
+        if (i < P.cnn.size()) plan->ops.push_back(P.cnn[i++]);
+        if (j < P.rnn.size()) plan->ops.push_back(P.rnn[j++]);
     }
-    for (auto& op : tail) plan->ops.push_back(op);
+    for (Op& op : P.tail) { op.after_join = true; plan->ops.push_back(op); }
 
     void* p = nullptr;
+    const auto& LS = plan->launches;
     HIPCHK(h, hipMalloc(&p, LS.size() * sizeof(GemmLaunch)));
     h->allocs.push_back(p);
     plan->d_launches = static_cast<GemmLaunch*>(p);
@@ -1104,46 +1140,39 @@ int build_plan(ds_handle* h, int n, Plan* plan)
 int issue_op(ds_handle* h, Plan& plan, const Op& op, hipStream_t s)
 {
     const int n = plan.n;
+    const bool bf_rows = op.operands == OPS_BF16;
     switch (op.kind) {
-    case OP_GEMM:
-        HIPCHK(h, launch_gemm(op.cfg, plan.d_launches + op.launch_index, op.total_tiles, s));
-        break;
-    case OP_STEM1:
-        HIPCHK(h, launch_stem1(op.in, h->stem1_w, h->stem1_b, op.out, n, h->S, h->w1, h->pl_conv1, h->wa, h->pl_pool1, op.a, s));
-        break;
+    case OP_GEMM: HIPCHK(h, launch_gemm(op.gemm.cfg, plan.d_launches + op.gemm.launch_index, op.gemm.total_tiles, s)); break;
+    case OP_STEM1: HIPCHK(h, launch_stem1(op.stem1.signals, h->stem1_w, h->stem1_b, op.stem1.out, n, h->S, h->w1, h->pl_conv1, h->wa, h->pl_pool1, bf_rows, s)); break;
     case OP_MAXPOOL:
-        if (h->bf16) HIPCHK(h, launch_maxpool_s2_bf16(op.in, op.out, n, op.a, op.b, op.c, op.d, s));
-        else HIPCHK(h, launch_maxpool_s2(op.in, op.out, n, op.a, op.b, op.c, op.d, s));
+        if (bf_rows) HIPCHK(h, launch_maxpool_s2_bf16(op.pool.in, op.pool.out, n, op.pool.win, op.pool.wout, op.pool.pad, op.pool.ch, s));
+        else HIPCHK(h, launch_maxpool_s2(op.pool.in, op.pool.out, n, op.pool.win, op.pool.wout, op.pool.pad, op.pool.ch, s));
         break;
     case OP_AVGPOOL:
-        if (h->bf16) HIPCHK(h, launch_avgpool7_bf16(op.in, op.out, n, op.a, op.d, 256, h->JP, h->is_rnn ? 2 * HID : 0, s));
-        else HIPCHK(h, launch_avgpool7(op.in, op.out, n, op.a, op.d, s));
+        if (bf_rows) HIPCHK(h, launch_avgpool7_bf16(op.pool.in, op.pool.out, n, op.pool.win, op.pool.ch, 256, h->JP, h->is_rnn ? 2 * HID : 0, s));
+        else HIPCHK(h, launch_avgpool7(op.pool.in, op.pool.out, n, op.pool.win, op.pool.ch, s));
         break;
-    case OP_PACKEV:
-        HIPCHK(h, launch_pack_event_feat_bf16(h->cur->hlast[0], h->cur->hlast[1], h->cur->joint, n, h->JP, 0, s));
-        break;
+    case OP_PACKEV: HIPCHK(h, launch_pack_event_feat_bf16(h->cur->hlast[0], h->cur->hlast[1], h->cur->joint, n, h->JP, 0, s)); break;
     case OP_LSTM:
-        if (op.c >= 300) HIPCHK(h, launch_lstm_cells_split(op.c - 300, plan.lstm_launches[op.launch_index], s));
-        else HIPCHK(h, launch_lstm_cells(op.c, plan.lstm_launches[op.launch_index], s));
+        if (lstm_tile_is_split(op.lstm.tile)) HIPCHK(h, launch_lstm_cells_split(op.lstm.tile, plan.lstm_launches[op.lstm.launch_index], s));
+        else HIPCHK(h, launch_lstm_cells(op.lstm.tile, plan.lstm_launches[op.lstm.launch_index], s));
         break;
-    case OP_DENSES:
-        HIPCHK(h, launch_dense_split(op.sd, s));
-        break;
-    case OP_XPROJ:
-        HIPCHK(h, launch_lstm_xproj(op.xp, s));
-        break;
+    case OP_DENSES: HIPCHK(h, launch_dense_split(op.sd, s)); break;
+    case OP_XPROJ: HIPCHK(h, launch_lstm_xproj(op.xp, s)); break;
     case OP_STEM23:
-        if (op.a == 2) HIPCHK(h, launch_stem23_split(op.sa, s));
-        else if (op.a) HIPCHK(h, launch_stem23_bf16(op.sa, s));
-        else HIPCHK(h, launch_stem23(op.sa, s));
+        switch (op.operands) {
+        case OPS_FP32: HIPCHK(h, launch_stem23(op.sa, s)); break;
+        case OPS_BF16: HIPCHK(h, launch_stem23_bf16(op.sa, s)); break;
+        case OPS_SPLIT: HIPCHK(h, launch_stem23_split(op.sa, s)); break;
+        }
         break;
-    case OP_HEADF:
-        HIPCHK(h, launch_head_folded(op.ha, s));
-        break;
+    case OP_HEADF: HIPCHK(h, launch_head_folded(op.ha, s)); break;
     case OP_FUSED:
-        if (h->bf16) HIPCHK(h, launch_inception_fused_bf16(op.tm, op.fc, s));
-        else if (op.d == 3) HIPCHK(h, launch_inception_fused_split(op.tm, op.fc, s));
-        else HIPCHK(h, launch_inception_fused(op.tm, op.fc, s));
+        switch (op.operands) {
+        case OPS_FP32: HIPCHK(h, launch_inception_fused(op.tm, op.fc, s)); break;
+        case OPS_BF16: HIPCHK(h, launch_inception_fused_bf16(op.tm, op.fc, s)); break;
+        case OPS_SPLIT: HIPCHK(h, launch_inception_fused_split(op.tm, op.fc, s)); break;
+        }
         break;
     case OP_HEAD:
         HIPCHK(h, launch_head(h->cur->fc1o, h->fc2, h->cur->logits, h->cur->act, h->cur->pred, n, h->J, h->C, s, plan.fc1_parts, (size_t)h->B * h->J));
@@ -1154,8 +1183,6 @@ int issue_op(ds_handle* h, Plan& plan, const Op& op, hipStream_t s)
 
 // Enqueue the whole forward on (s0, s1): fork after the inputs are in place, join before fc1.
 // timed: bracket every launch with its own HIP event pair on the stream it is launched on.
-int kernel_class(const Op& op);
-
 int enqueue_forward(ds_handle* h, Plan& plan, int timed)
 {
     HIPCHK(h, hipEventRecord(h->cur->ev_fork, h->cur->s0));
@@ -1175,8 +1202,7 @@ int enqueue_forward(ds_handle* h, Plan& plan, int timed)
     for (Op& op : plan.ops) {
         const int si = (op.stream == 0 || serial) ? 0 : 1;
         hipStream_t s = si == 0 ? h->cur->s0 : h->cur->s1;
-        const bool is_tail = h->stages[op.stage].name == "fc1" || h->stages[op.stage].name == "head";
-        if (is_tail && !joined) {
+        if (op.after_join && !joined) {
             int rc = close_run(0); if (rc) return rc;
             rc = close_run(1); if (rc) return rc;
             HIPCHK(h, hipEventRecord(h->cur->ev_join, h->cur->s1));
@@ -1191,7 +1217,7 @@ int enqueue_forward(ds_handle* h, Plan& plan, int timed)
             HIPCHK(h, hipEventRecord(op.ev0, s));
             op.run_launches = 1; op.run_flops = op.flops;
         } else if (timed == 1) {
-            if (head[si] && kernel_class(*head[si]) != kernel_class(op)) { int rc = close_run(si); if (rc) return rc; }
+            if (head[si] && head[si]->kernel != op.kernel) { int rc = close_run(si); if (rc) return rc; }
             if (!head[si]) {
                 head[si] = &op;
                 op.run_launches = 0; op.run_flops = 0;
@@ -1215,34 +1241,6 @@ int enqueue_forward(ds_handle* h, Plan& plan, int timed)
     return DS_OK;
 }
 
-int kernel_class(const Op& op)
-{
-    switch (op.kind) {
-    case OP_GEMM:
-        return op.cfg == CFG_CONV ? K_GEMM_CONV : op.cfg == CFG_FC ? K_GEMM_FC
-               : op.cfg == CFG_CONV_POOL ? K_GEMM_CONV_POOL : op.cfg == CFG_FC_DENSE ? K_GEMM_FC_DENSE
-               : op.cfg == CFG_BCONV ? K_GEMM_BCONV : op.cfg == CFG_BCONV_POOL ? K_GEMM_BCONV_POOL : op.cfg == CFG_BFC ? K_GEMM_BFC
-               : op.cfg == CFG_BFC_DENSE ? K_GEMM_BFC_DENSE : K_GEMM_CONV_WIDE;
-    case OP_FUSED:
-        if (op.fa.cin == 128) return op.tm == 1 ? K_FUSEDB1 : op.tm == 2 ? K_FUSEDB2 : K_FUSEDB3;   // bf16 rows: pitch in units
-        if (op.d == 3) return op.tm == 1 ? K_FUSEDS1 : op.tm == 2 ? K_FUSEDS2 : K_FUSEDS3;          // split operands (three terms)
-        return op.tm == 1 ? K_FUSED1 : op.tm == 2 ? K_FUSED2 : K_FUSED3;
-    case OP_STEM1: return K_STEM1;
-    case OP_STEM23: return op.a == 2 ? K_STEM23S : op.a ? K_STEM23B : K_STEM23;
-    case OP_HEADF: return K_HEADF;
-    case OP_MAXPOOL: return K_MAXPOOL;
-    case OP_AVGPOOL: return K_AVGPOOL;
-    case OP_HEAD: return K_HEAD;
-    case OP_PACKEV: return K_PACKEV;
-    case OP_DENSES: return K_DENSE_SPLIT;
-    case OP_XPROJ: return K_LSTM_XPROJ;
-    case OP_LSTM: if (op.c >= 300) return op.c == 311 ? K_LSTM_S11 : op.c == 312 ? K_LSTM_S12 : op.c == 328 ? K_LSTM_S28 : K_LSTM_S22;
-        return op.c == 1 ? K_LSTM_CELL1 : op.c == 2 ? K_LSTM_CELL2 : op.c == 4 ? K_LSTM_CELL4 : op.c == 101 ? K_LSTM_LDS1
-               : op.c == 211 ? K_LSTM_B11 : op.c == 212 ? K_LSTM_B12 : op.c == 222 ? K_LSTM_B22 : K_LSTM_LDS2;
-    }
-    return K_HEAD;
-}
-
 int collect_stage_times(ds_handle* h)
 {
     for (Slot& sl : h->slots)
@@ -1253,7 +1251,7 @@ int collect_stage_times(ds_handle* h)
             float ms = 0;
             HIPCHK(h, hipEventElapsedTime(&ms, op.ev0, op.ev1));
             h->stages[op.stage].total_ms += ms;     // per-stage times are only meaningful in mode 2
-            KernelStat& K = h->kstat[kernel_class(op)];
+            KernelStat& K = h->kstat[op.kernel];
             K.launches += op.run_launches; K.total_ms += ms; K.flops += op.run_flops;
             op.pending = false;
         }
@@ -1460,7 +1458,6 @@ static int ds_create_impl(const ds_config* cfg, ds_handle** out)
     h->split_dense_narrow = (flags & DS_TUNE_SPLIT_DENSE_NARROW) != 0;
     h->lstm_xproj = h->split && h->is_rnn && !(flags & DS_TUNE_NO_LSTM_XPROJ);
     h->lstm_xproj_all = h->lstm_xproj && (flags & DS_TUNE_LSTM_XPROJ_ALL);
-    h->lstm_frag = h->is_rnn && !h->lstm_bf16;
     h->Bp32 = (h->B + 31) / 32 * 32;
     h->JP = (h->J + 31) / 32 * 32;
     h->debug = cfg->reserved[0] != 0;

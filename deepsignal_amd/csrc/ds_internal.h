@@ -60,6 +60,42 @@ enum GemmCfg { CFG_CONV = 0, CFG_FC = 1, CFG_CONV_WIDE = 3, CFG_CONV_POOL = 4, C
                // bf16-operand variants (mixed-precision mode)
                CFG_BCONV = 7, CFG_BCONV_POOL = 8, CFG_BFC = 9, CFG_BFC_DENSE = 10 };
 
+// ---- the kernel table: one entry per __global__ function / template instantiation the engine books launches under. The planner
+// names an op's entry when it chooses the variant (Op::kernel); ds_num_kernels / ds_get_kernel_stat expose the table by POSITION and
+// recorded profiles are keyed by the name strings, so order, count and names are ABI: append, never reorder, rename or remove (the
+// grouped-GEMM BiLSTM configurations, the wide conv tile and lstm_cell_kernel<2> are launched by no plan any more and stay).
+#define DS_KERNEL_TABLE(X)                                                                                                             \
+    X(K_GEMM_CONV, "gemm_kernel<1,2,4,1,0,0,1,1>")             X(K_GEMM_FC, "gemm_kernel<1,3,4,1,0,0,2,1>")                             \
+    X(K_GEMM_LSTM, "gemm_kernel<1,4,4,1,1,0,1,1>")             X(K_GEMM_CONV_WIDE, "gemm_kernel<2,2,2,2,0,0,1,1>")                      \
+    X(K_GEMM_CONV_POOL, "gemm_kernel<1,2,4,1,0,1,1,1>")        X(K_GEMM_FC_DENSE, "gemm_kernel<1,3,4,1,0,2,2,1>")                       \
+    X(K_GEMM_LSTM_DENSE, "gemm_kernel<1,4,4,1,1,2,1,1>")       X(K_FUSED1, "inception_fused_kernel<1>")                                 \
+    X(K_FUSED2, "inception_fused_kernel<2>")                   X(K_FUSED3, "inception_fused_kernel<3>")                                 \
+    X(K_STEM1, "stem1_kernel")                                 X(K_MAXPOOL, "maxpool_s2_kernel")                                        \
+    X(K_AVGPOOL, "avgpool7_kernel")                            X(K_HEAD, "head_kernel")                                                 \
+    X(K_GEMM_BCONV, "gemm_kernel<1,2,4,1,0,0,1,1,bf16>")       X(K_GEMM_BCONV_POOL, "gemm_kernel<1,2,4,1,0,1,1,1,bf16>")                \
+    X(K_GEMM_BFC, "gemm_kernel<4,2,1,4,0,0,2,1,bf16>")         X(K_GEMM_BFC_DENSE, "gemm_kernel<4,2,1,4,0,2,2,1,bf16>")                 \
+    X(K_PACKEV, "pack_event_feat_bf16_kernel")                 X(K_GEMM_BLSTM, "gemm_kernel<1,4,4,1,1,0,3,1,bf16>")                     \
+    X(K_GEMM_BLSTM_DENSE, "gemm_kernel<1,4,4,1,1,2,3,1,bf16>") X(K_FUSEDB1, "inception_fused_bf16_kernel<1>")                           \
+    X(K_FUSEDB2, "inception_fused_bf16_kernel<2>")             X(K_FUSEDB3, "inception_fused_bf16_kernel<3>")                           \
+    X(K_GEMM_LSTM_T, "gemm_kernel<1,1,4,1,2,0,1,1>")           X(K_GEMM_LSTM_T_DENSE, "gemm_kernel<1,1,4,1,2,2,1,1>")                   \
+    X(K_GEMM_BLSTM_T, "gemm_kernel<1,1,4,1,2,0,3,1,bf16>")     X(K_GEMM_BLSTM_T_DENSE, "gemm_kernel<1,1,4,1,2,2,3,1,bf16>")             \
+    X(K_LSTM_CELL1, "lstm_cell_kernel<1>")                     X(K_LSTM_CELL2, "lstm_cell_kernel<2>")                                   \
+    X(K_LSTM_CELL4, "lstm_cell_kernel<4>")                     X(K_LSTM_LDS1, "lstm_cell_lds_kernel<1>")                                \
+    X(K_LSTM_LDS2, "lstm_cell_lds_kernel<2>")                  X(K_STEM23, "stem23_kernel")                                             \
+    X(K_HEADF, "head_folded_kernel")                           X(K_LSTM_B11, "lstm_cell_bf16_kernel<1,1>")                              \
+    X(K_LSTM_B12, "lstm_cell_bf16_kernel<1,2>")                X(K_LSTM_B22, "lstm_cell_bf16_kernel<2,2>")                              \
+    X(K_STEM23B, "stem23_bf16_kernel")                         X(K_FUSEDS1, "inception_fused_split_kernel<1>")                          \
+    X(K_FUSEDS2, "inception_fused_split_kernel<2>")            X(K_FUSEDS3, "inception_fused_split_kernel<3>")                          \
+    X(K_LSTM_S11, "lstm_cell_split_kernel<1,1>")               X(K_LSTM_S12, "lstm_cell_split_kernel<1,2>")                             \
+    X(K_LSTM_S22, "lstm_cell_split_kernel<2,2>")               X(K_DENSE_SPLIT, "dense_split_kernel (+ pack_joint_split_kernel)")       \
+    X(K_STEM23S, "stem23_split_kernel")                        X(K_LSTM_XPROJ, "lstm_xproj_kernel")                                     \
+    X(K_LSTM_S28, "lstm_cell_split_kernel<1,2,4,2>")           X(K_EXTRACT_STATS, "extract_stats_kernel")                               \
+    X(K_EXTRACT_SITES, "extract_sites_kernel")
+#define DS_KERNEL_ID(id, name) id,
+enum KernelClass { DS_KERNEL_TABLE(DS_KERNEL_ID) K_COUNT };
+#undef DS_KERNEL_ID
+static_assert(K_GEMM_CONV == 0 && K_EXTRACT_SITES == 50 && K_COUNT == 51, "the kernel table is ABI: append only");
+
 // ---- fp32 BiLSTM cell launch (lstm_cell_kernel) ---------------------------------------------------------------
 // h and c of the fp32 BiLSTM live in MFMA-FRAGMENT-MAJOR buffers: [m-tile of 32 sites][k-group of 8 units][64 lanes][4]
 // where lane (site r = lane & 31, half = lane >> 5) holds units 8g + 4*half .. + 3 of site 32*mtile + r. That is
@@ -111,8 +147,31 @@ struct LstmXproj {
                                // values), T = all of them
 };
 hipError_t launch_lstm_xproj(const LstmXproj& X, hipStream_t s);
-// nt = 32-column n-tiles per wave (1, 2 or 4): the same bits for every nt (same K order per output element)
-hipError_t launch_lstm_cells(int nt, const LstmLaunch& L, hipStream_t s);      // L travels as a by-value kernel argument
+// Workgroup tile of a BiLSTM cell launch = the kernel instantiation that runs it. One cell's [mtiles x 32 sites] x [1024 gate columns]
+// product is cut into blocks of mtiles_per_wg m-tiles, each shared by wgs_per_mblock workgroups along the columns. Every tile of a
+// family gives the same bits (same K order per output element).
+enum LstmTile {
+    LT_F1, LT_F2, LT_F4,          // fp32 cells, operands from global memory: 128 sites x 1, 2 or 4 n-tiles of 32 columns per wave
+    LT_LDS1, LT_LDS2,             // fp32 cells, operands through an LDS ring: 64 sites x 64 / 128 columns
+    LT_B11, LT_B12, LT_B22,       // bf16-operand cells (DS_PRECISION_BF16_ALL): 64 x 64, 64 x 128, 128 x 128
+    LT_S11, LT_S12, LT_S22,       // split-operand cells (DS_PRECISION_BF16X3, ds_split.hip): the same three shapes ...
+    LT_S28,                       // ... and 128 x 128 by eight waves (4 x 2, each 32 x 64) instead of four
+    LT_COUNT
+};
+struct LstmTileInfo { KernelClass kernel; int mtiles_per_wg; int wgs_per_mblock; };
+constexpr LstmTileInfo kLstmTiles[LT_COUNT] = {
+    {K_LSTM_CELL1, 4, 32}, {K_LSTM_CELL2, 4, 16}, {K_LSTM_CELL4, 4, 8}, {K_LSTM_LDS1, 2, 16}, {K_LSTM_LDS2, 2, 8},
+    {K_LSTM_B11, 2, 16},   {K_LSTM_B12, 2, 8},    {K_LSTM_B22, 4, 8},
+    {K_LSTM_S11, 2, 16},   {K_LSTM_S12, 2, 8},    {K_LSTM_S22, 4, 8},   {K_LSTM_S28, 4, 8}};
+// workgroups one cell adds to a launch: the launchers' grid is ncell times this, and LstmLaunch::cls_tiles sums it per work class
+// (lstm_logical_tile maps workgroups to tiles from both, so both come from here)
+inline int lstm_tiles_per_cell(LstmTile t, int mtiles)
+{
+    return (mtiles + kLstmTiles[t].mtiles_per_wg - 1) / kLstmTiles[t].mtiles_per_wg * kLstmTiles[t].wgs_per_mblock;
+}
+inline bool lstm_tile_is_split(LstmTile t) { return t >= LT_S11; }
+// the fp32 and bf16-operand tiles (ds_kernels.hip); L travels as a by-value kernel argument
+hipError_t launch_lstm_cells(LstmTile tile, const LstmLaunch& L, hipStream_t s);
 
 // tile geometry per config (host needs it for grid sizing)
 struct TileGeom { int bm, bn, threads, ksplit; };
@@ -160,8 +219,8 @@ size_t inception_fused_split_lds_bytes(int tm, int W, int spt);
 hipError_t configure_split_kernels();
 // BiLSTM cells of one diagonal with split operands (ds_split.hip): h buffers are fragment-major term images
 // [m-tile][k-step of 16 units][term][64 lanes][8 bf16] (48 KiB per m-tile), C.Bp points at pack_b_split panels, kg_stride = k-steps per
-// n-tile panel; c, bias, table, the gates and h_row as in the fp32 cells. tile = 11 | 12 | 22: workgroup tile of 64 x 64 .. 128 x 128.
-hipError_t launch_lstm_cells_split(int tile, const LstmLaunch& L, hipStream_t s);
+// n-tile panel; c, bias, table, the gates and h_row as in the fp32 cells. tile = one of LT_S11 .. LT_S28.
+hipError_t launch_lstm_cells_split(LstmTile tile, const LstmLaunch& L, hipStream_t s);
 // dense(J, J) of the three-step joint model with split operands: pack_joint_split_kernel writes the joint rows (three fp32 row
 // segments per site) as a fragment-major term image A, dense_split_kernel multiplies it with W1's pack_b_split panels into C [n][N]
 struct SplitDense {

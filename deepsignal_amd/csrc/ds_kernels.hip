@@ -956,24 +956,23 @@ __global__ __launch_bounds__(256, MTW * NTW >= 4 ? 2 : 3) void lstm_cell_bf16_ke
 #undef DS_LSTAMP
 }
 
-hipError_t launch_lstm_cells(int nt, const LstmLaunch& L, hipStream_t s)
+hipError_t launch_lstm_cells(LstmTile tile, const LstmLaunch& L, hipStream_t s)
 {
-    const int ncell = L.ncell, mtiles = L.mtiles;
-    if (ncell <= 0 || mtiles <= 0) return hipSuccess;
-    const int mblocks = (mtiles + 3) / 4, mblocks2 = (mtiles + 1) / 2;
-    switch (nt) {
-    case 101: hipLaunchKernelGGL(lstm_cell_lds_kernel<1>, dim3(ncell * mblocks2 * 16), dim3(256), 3 * 1 * 4 * 1024, s, L); break;      // 3 stages x KGS x FR KiB
-    case 102: hipLaunchKernelGGL(lstm_cell_lds_kernel<2>, dim3(ncell * mblocks2 * 8), dim3(256), 3 * 2 * 6 * 1024, s, L); break;
-    // bf16-operand cells (DS_PRECISION_BF16_ALL): 2MN = workgroup tile of 64 M sites x 64 N columns
-    case 211: hipLaunchKernelGGL((lstm_cell_bf16_kernel<1, 1>), dim3(ncell * ((mtiles + 1) / 2) * 16), dim3(256), 3 * 2 * 4 * 1024, s, L); break;
-    case 212: hipLaunchKernelGGL((lstm_cell_bf16_kernel<1, 2>), dim3(ncell * ((mtiles + 1) / 2) * 8), dim3(256), 3 * 2 * 6 * 1024, s, L); break;
-    case 222: hipLaunchKernelGGL((lstm_cell_bf16_kernel<2, 2>), dim3(ncell * ((mtiles + 3) / 4) * 8), dim3(256), 3 * 2 * 8 * 1024, s, L); break;
+    if (L.ncell <= 0 || L.mtiles <= 0) return hipSuccess;
+    const dim3 grid(L.ncell * lstm_tiles_per_cell(tile, L.mtiles));
+    switch (tile) {
+    case LT_LDS1: hipLaunchKernelGGL(lstm_cell_lds_kernel<1>, grid, dim3(256), 3 * 1 * 4 * 1024, s, L); break;      // 3 stages x KGS x FR KiB
+    case LT_LDS2: hipLaunchKernelGGL(lstm_cell_lds_kernel<2>, grid, dim3(256), 3 * 2 * 6 * 1024, s, L); break;
+    // bf16-operand cells (DS_PRECISION_BF16_ALL): LT_Bmn = workgroup tile of 64 m sites x 64 n columns
+    case LT_B11: hipLaunchKernelGGL((lstm_cell_bf16_kernel<1, 1>), grid, dim3(256), 3 * 2 * 4 * 1024, s, L); break;
+    case LT_B12: hipLaunchKernelGGL((lstm_cell_bf16_kernel<1, 2>), grid, dim3(256), 3 * 2 * 6 * 1024, s, L); break;
+    case LT_B22: hipLaunchKernelGGL((lstm_cell_bf16_kernel<2, 2>), grid, dim3(256), 3 * 2 * 8 * 1024, s, L); break;
     // (a 128 x 256 tile -- a wave owning 64 sites x 128 columns, 0.09 KiB of operand fragments per MFMA against 0.125 -- was measured in
     // round 5: 756 against 673 us per 4096-site step; 768 workgroups of 72 KB rings fill the GPU in 1.5 rounds)
-    case 1: hipLaunchKernelGGL(lstm_cell_kernel<1>, dim3(ncell * mblocks * 32), dim3(256), 0, s, L); break;
-    case 2: hipLaunchKernelGGL(lstm_cell_kernel<2>, dim3(ncell * mblocks * 16), dim3(256), 0, s, L); break;
-    case 4: hipLaunchKernelGGL(lstm_cell_kernel<4>, dim3(ncell * mblocks * 8), dim3(256), 0, s, L); break;
-    default: return hipErrorInvalidValue;
+    case LT_F1: hipLaunchKernelGGL(lstm_cell_kernel<1>, grid, dim3(256), 0, s, L); break;
+    case LT_F2: hipLaunchKernelGGL(lstm_cell_kernel<2>, grid, dim3(256), 0, s, L); break;
+    case LT_F4: hipLaunchKernelGGL(lstm_cell_kernel<4>, grid, dim3(256), 0, s, L); break;
+    case LT_S11: case LT_S12: case LT_S22: case LT_S28: case LT_COUNT: return hipErrorInvalidValue;      // launch_lstm_cells_split's
     }
     return hipGetLastError();
 }

@@ -1299,17 +1299,18 @@ hipError_t launch_lstm_xproj(const LstmXproj& X, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_lstm_cells_split(int tile, const LstmLaunch& L, hipStream_t s)
+hipError_t launch_lstm_cells_split(LstmTile tile, const LstmLaunch& L, hipStream_t s)
 {
-    const int ncell = L.ncell, mtiles = L.mtiles;
-    if (ncell <= 0 || mtiles <= 0) return hipSuccess;
+    if (L.ncell <= 0 || L.mtiles <= 0) return hipSuccess;
+    const dim3 grid(L.ncell * lstm_tiles_per_cell(tile, L.mtiles));
     switch (tile) {
-    case 11: hipLaunchKernelGGL((lstm_cell_split_kernel<1, 1>), dim3(ncell * ((mtiles + 1) / 2) * 16), dim3(256), (SplitRing<1, 1, 2, 2, DS_SPLIT_LSTM_SLOTS>::LDS_BYTES), s, L); break;
-    case 12: hipLaunchKernelGGL((lstm_cell_split_kernel<1, 2>), dim3(ncell * ((mtiles + 1) / 2) * 8), dim3(256), (SplitRing<1, 2, 2, 2, DS_SPLIT_LSTM_SLOTS>::LDS_BYTES), s, L); break;
-    case 22: hipLaunchKernelGGL((lstm_cell_split_kernel<2, 2>), dim3(ncell * ((mtiles + 3) / 4) * 8), dim3(256), (SplitRing<2, 2, 2, 2, DS_SPLIT_LSTM_SLOTS>::LDS_BYTES), s, L); break;
+    case LT_S11: hipLaunchKernelGGL((lstm_cell_split_kernel<1, 1>), grid, dim3(256), (SplitRing<1, 1, 2, 2, DS_SPLIT_LSTM_SLOTS>::LDS_BYTES), s, L); break;
+    case LT_S12: hipLaunchKernelGGL((lstm_cell_split_kernel<1, 2>), grid, dim3(256), (SplitRing<1, 2, 2, 2, DS_SPLIT_LSTM_SLOTS>::LDS_BYTES), s, L); break;
+    case LT_S22: hipLaunchKernelGGL((lstm_cell_split_kernel<2, 2>), grid, dim3(256), (SplitRing<2, 2, 2, 2, DS_SPLIT_LSTM_SLOTS>::LDS_BYTES), s, L); break;
     // the same 128 x 128 workgroup tile by EIGHT waves (4 x 2, each 32 x 64): two waves per SIMD of the one workgroup a CU holds
-    case 28: hipLaunchKernelGGL((lstm_cell_split_kernel<1, 2, 4, 2>), dim3(ncell * ((mtiles + 3) / 4) * 8), dim3(512), (SplitRing<1, 2, 4, 2, DS_SPLIT_LSTM_SLOTS>::LDS_BYTES), s, L); break;
-    default: return hipErrorInvalidValue;
+    case LT_S28: hipLaunchKernelGGL((lstm_cell_split_kernel<1, 2, 4, 2>), grid, dim3(512), (SplitRing<1, 2, 4, 2, DS_SPLIT_LSTM_SLOTS>::LDS_BYTES), s, L); break;
+    case LT_F1: case LT_F2: case LT_F4: case LT_LDS1: case LT_LDS2: case LT_B11: case LT_B12: case LT_B22: case LT_COUNT:
+        return hipErrorInvalidValue;      // launch_lstm_cells' (ds_kernels.hip)
     }
     return hipGetLastError();
 }
