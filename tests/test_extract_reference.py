@@ -11,6 +11,8 @@ from deepsignal_amd import extract_features as ef
 from deepsignal_amd import synth
 from deepsignal_amd.engine import ReadBatch, base_codes, extract_reference
 
+import extract_cases as xc
+
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "extract_golden.json")
 
 
@@ -208,3 +210,61 @@ def test_invalid_inputs_rejected(what):
         batch.raw_off[0] = 1
     with pytest.raises(RuntimeError, match="ds_reads"):
         extract_reference(batch)
+
+
+# ---- the shared case table (tests/extract_cases.py): the inputs tests/test_gpu_extract.py runs the kernels on ------------
+def test_case_table_covers_every_code_path():
+    """Every case takes the paths it is listed for, and the table as a whole takes every path of ds_extract.hip that
+    extract_cases.derive_paths distinguishes: the table may not shrink to cases that miss a branch."""
+    union = set()
+    for c in xc.CASES:
+        got = c.derived()
+        assert c.paths <= got, (c.name, sorted(c.paths - got))
+        union |= got
+    assert union == xc.ALL_PATHS, (sorted(xc.ALL_PATHS - union), sorted(union - xc.ALL_PATHS))
+
+
+def _host_step(step):
+    """The host extractor's features of a step's sites, in the step's site order, and the mask of SUB windows."""
+    reads, site_read, site_loc, norm, T, S, _ = step
+    per_read = {}
+    for i, r in enumerate(reads):
+        locs = sorted(int(loc) for rd, loc in zip(site_read, site_loc) if rd == i)
+        if not locs:
+            continue
+        bases = "".join("ACGTN"[c] for c in r[3])
+        assert _sites(bases, ["CG"], T) == locs
+        with np.errstate(all="ignore"):
+            per_read[i] = (locs, _host_features(r[0], r[1], r[2], bases, r[4], r[5], ["CG"], T, S, norm))
+    rows = [(per_read[int(rd)][1], per_read[int(rd)][0].index(int(loc))) for rd, loc in zip(site_read, site_loc)]
+    host = {k: np.stack([h[k][j] for h, j in rows]) for k in xc.KEYS}
+    sub = np.array([reads[rd][2][loc] >= S for rd, loc in zip(site_read, site_loc)])
+    return host, sub
+
+
+@pytest.mark.parametrize("name,norm", xc.case_norm_params())
+def test_case_table_bit_identical_to_host(name, norm):
+    """ds_extract_reference == the numpy host extractor on every step of every case. Degenerate cases (scale == 0): NaNs at
+    the same positions, everything else (+-inf included) bit for bit."""
+    case = xc.BY_NAME[name]
+    for step in case.steps(norm):
+        reads, site_read, site_loc, _, T, S, seed = step
+        host, sub = _host_step(step)
+        dev = extract_reference(ReadBatch(reads, site_read, site_loc, norm=norm, seed=seed), T, S)
+        for k in ("kmer", "means", "stds", "sanums"):
+            assert xc.same_bits(dev[k], host[k], nan_positions=case.degenerate), k
+        assert xc.same_bits(dev["signals"][~sub], host["signals"][~sub], nan_positions=case.degenerate)
+        if case.degenerate and norm == "mad":      # what the host extractor yields for MAD == 0: NaN and +-inf, nothing finite
+            assert not np.isfinite(host["means"]).any() and not np.isfinite(host["stds"]).any()
+        elif not case.degenerate:
+            assert all(np.isfinite(host[k]).all() for k in xc.KEYS)
+
+
+@pytest.mark.parametrize("norm", ["mad", "zscore"])
+def test_empty_read_does_not_change_its_neighbours(norm):
+    (with_empty,), (without,) = xc.BY_NAME["mixed_batch"].steps(norm), xc.BY_NAME["mixed_batch_no_empty"].steps(norm)
+    assert len(with_empty[0]) == len(without[0]) + 1 and len(with_empty[0][1][0]) == 0
+    a = extract_reference(ReadBatch(*with_empty[:3], norm=norm, seed=with_empty[6]))
+    b = extract_reference(ReadBatch(*without[:3], norm=norm, seed=without[6]))
+    for k in xc.KEYS:
+        assert xc.same_bits(a[k], b[k]), k

@@ -10,6 +10,8 @@ from deepsignal_amd import extract_features as ef
 from deepsignal_amd import synth, weights
 from deepsignal_amd.engine import Engine, ReadBatch, base_codes, extract_reference
 
+import extract_cases as xc
+
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "extract_golden.json")
@@ -207,3 +209,136 @@ def test_call_mods_extract_on_gpu_rows_match_cpu(tmp_path, style, norm):
             assert ca[:6] == cb[:6] and ca[9] == cb[9]
         else:
             assert ra == rb
+
+
+# ---- the shared case table (tests/extract_cases.py; tests/test_extract_reference.py holds the checker to numpy on it) -------
+@pytest.fixture(scope="module")
+def geometry_engines():
+    """One engine per (kmer_len, signal_len), kept for the module: ds_extract does not advance the slot, so consecutive cases
+    of a geometry share slot 0, its pinned and device blocks and whatever the batch before left in them."""
+    engines = {}
+    yield lambda T, S: engines.setdefault((T, S), Engine(kmer_len=T, signal_len=S, device=0, max_batch=512))
+    for e in engines.values():
+        e.close()
+
+
+def _batch(step):
+    reads, site_read, site_loc, norm, _, _, seed = step
+    return ReadBatch(reads, site_read, site_loc, norm=norm, seed=seed)
+
+
+@pytest.mark.parametrize("name,norm", xc.case_norm_params())
+def test_case_table_matches_reference(geometry_engines, name, norm):
+    """The kernels == ds_extract_reference on every step of every case, in the case's order, on one slot. Degenerate cases
+    (scale == 0): NaNs at the same positions (sign and payload not compared), everything else, +-inf included, bit for bit;
+    that is the only relaxation of bit equality in this file."""
+    case = xc.BY_NAME[name]
+    e = geometry_engines(*case.geometry)
+    for i, step in enumerate(case.steps(norm)):
+        b = _batch(step)
+        got, want = e.extract(b), extract_reference(b, *case.geometry)
+        for k in KEYS:
+            assert xc.same_bits(got[k], want[k], nan_positions=case.degenerate), (i, k)
+
+
+@pytest.mark.parametrize("norm", ["mad", "zscore"])
+def test_empty_read_does_not_change_its_neighbours(geometry_engines, norm):
+    e = geometry_engines(17, 360)
+    (with_empty,), (without,) = xc.BY_NAME["mixed_batch"].steps(norm), xc.BY_NAME["mixed_batch_no_empty"].steps(norm)
+    _assert_same(e.extract(_batch(with_empty)), e.extract(_batch(without)))
+
+
+def test_blocks_grow_and_are_reused_on_one_slot():
+    """A fresh engine's slot allocates its blocks for a small batch, re-allocates them for one fifty times the size, and the
+    small batch then runs in the large blocks."""
+    case = xc.BY_NAME["block_growth"]
+    e = Engine(device=0, max_batch=512)
+    try:
+        steps = case.steps("zscore")
+        sizes = [len(s[0][0][0]) + sum(len(r[0]) for r in s[0][1:]) for s in steps]
+        assert sizes[1] > 40 * sizes[0] and sizes[2] == sizes[0]
+        for norm in case.norms:
+            for step in case.steps(norm):
+                b = _batch(step)
+                _assert_same(e.extract(b), extract_reference(b))
+    finally:
+        e.close()
+
+
+def _independence_reads():
+    """Four reads with ~50 sites each: one of more than 16 numpy blocks, one with a wide raw range, one with long middle
+    bases (SUB windows), one ordinary; explicit subsample keys, so a SUB window does not depend on the read's index."""
+    rng = np.random.default_rng(2024)
+    out = []
+    for i, (nbases, long_bases) in enumerate([(15000, 0), (2500, 0), (1500, 12), (900, 0)]):
+        raw, starts, lengths, _, scaling, offset = synth.synthetic_read(nbases, 600 + i, long_bases=long_bases)
+        if i == 1:
+            raw = raw.copy()
+            raw[rng.choice(len(raw), 50, replace=False)] = rng.integers(-15000, 15000, 50).astype(np.int16)
+        locs = np.sort(rng.choice(np.arange(8, nbases - 9, 2), 50, replace=False))
+        if long_bases:
+            sub = [int(v) for v in np.flatnonzero(lengths >= 360) if 8 <= v < nbases - 9][:6]
+            locs = np.array(sorted(set(locs.tolist()) | set(sub) - {v + 1 for v in sub} - {v - 1 for v in sub}))
+            locs = locs[np.concatenate([[True], np.diff(locs) >= 2])]
+        out.append(((raw, starts, lengths, xc._codes(nbases, locs, rng), scaling, offset, 9000 + i), [int(v) for v in locs]))
+    assert len(out[0][0][0]) > 16 * 8192 and int(out[1][0][0].max()) - int(out[1][0][0].min()) >= 8192
+    assert any(out[2][0][2][loc] >= 360 for loc in out[2][1])
+    return out
+
+
+@pytest.mark.parametrize("norm", ["mad", "zscore"])
+def test_site_bits_do_not_depend_on_the_batch(geometry_engines, norm):
+    """The five feature rows of a site carry the same bits whatever batch the site travels in: (a) all reads in one batch,
+    (b) reads in reversed order, (c) sites shuffled, (d) one read per batch, (e) an unrelated 1 M-sample read added."""
+    e = geometry_engines(17, 360)
+    rl = _independence_reads()
+    rng = np.random.default_rng(5)
+
+    def run(read_locs, order=None):
+        reads, sr, sl = xc._one(read_locs)
+        if order is not None:
+            sr, sl = [sr[i] for i in order], [sl[i] for i in order]
+        f = e.extract(ReadBatch(reads, sr, sl, norm=norm, seed=3))
+        return {(reads[r][6], loc): tuple(f[k][i].view(np.uint32).tobytes() if f[k].dtype == np.float32 else f[k][i].tobytes()
+                                          for k in KEYS) for i, (r, loc) in enumerate(zip(sr, sl))}
+
+    a = run(rl)
+    assert 180 <= len(a) <= 512
+    b = run(rl[::-1])
+    c = run(rl, order=rng.permutation(len(a)).tolist())
+    d = {}
+    for one in rl:
+        d.update(run([one]))
+    big = xc._spread_read(xc._signal(1000003, rng), 17, rng, 777)
+    f = run([big] + rl)
+    for other in (b, c, d, f):
+        assert all(other[site] == rows for site, rows in a.items())
+    assert len(f) == len(a) + len(big[1]) and len(b) == len(c) == len(d) == len(a)
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
+def test_submit_reads_long_reads_growing_blocks(precision):
+    """ds_submit_reads on long reads == ds_submit of the checker's features. The batches ascend in size (20 k samples to
+    1 M) and fill every slot, so each slot allocates its blocks while its neighbours' extraction and forward are in flight;
+    a second round re-allocates every slot's blocks for a larger batch than it held. Tickets are waited newest first."""
+    e = Engine(device=0, max_batch=512, precision=precision, slots=4)
+    try:
+        e.load_weights(weights.random_weights(seed=3, lstm_bias_std=0.1))
+        assert e.slots == 4
+        rng = np.random.default_rng(31)
+        sizes = [20011, 8192 * 17 + 4000, 300007, 600001, 8192 * 33 + 129, 1050001, 8192 * 16 + 127, 700001]
+        batches = []
+        for i, n in enumerate(sorted(sizes)):
+            reads, sr, sl = xc._one([xc._spread_read(xc._signal(n, rng), 17, rng, 50 + i, nsites=24),
+                                     xc._synthetic(1200, 800 + i, 70 + i, 17, 100, long_bases=2)])
+            batches.append(ReadBatch(reads, sr, sl, norm=("zscore", "mad")[i % 2], seed=1))
+        for s in range(0, len(batches), e.slots):
+            group = batches[s:s + e.slots]
+            tickets = [e.submit_reads(b) for b in group]
+            got = [e.wait(t) for t in tickets[::-1]][::-1]
+            for b, (act, pred) in zip(group, got):
+                f = extract_reference(b)
+                act2, pred2 = e.wait(e.submit(f["kmer"], f["means"], f["stds"], f["sanums"], f["signals"]))
+                assert np.array_equal(_bits(act), _bits(act2)) and np.array_equal(pred, pred2)
+    finally:
+        e.close()
