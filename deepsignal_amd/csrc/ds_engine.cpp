@@ -212,7 +212,6 @@ struct ds_handle {
     float* fc2 = nullptr;
     float* w12f = nullptr;    // fold_fc: [J][C] = (avgpool^T on the signal rows) (W1 W2), float64 product rounded once
 
-    const float* zero_seg = nullptr;
     unsigned long long* dbg_stamps = nullptr;   // [NMOD][1024 wgs][2 waves][8] when DS_TUNE_DEBUG_STAMPS is set
     unsigned long long* dbg_lstm = nullptr;     // [32 diagonals][1024 wgs][8] stamps of the fp32 BiLSTM cell launches
     std::vector<Stage> stages;
@@ -273,7 +272,7 @@ int upload(ds_handle* h, float** dst, const std::vector<float>& v)
 // lane (j = lane&31, half = lane>>5) element s holds W[kgroup*8 + 4*half + s][ntile*32 + j].
 std::vector<float> pack_b(int K, int N, const std::function<float(int, int)>& w_in)
 {
-    // K is padded to a multiple of 32 with zero rows so K-split kernels may run one extra (zero) chunk
+    // K is padded to a multiple of 32 with zero rows (the panel stride every reader uses: base_problem's kgroups_stride)
     const int Kp = (K + 31) / 32 * 32;
     auto w = [&](int k, int col) { return k < K ? w_in(k, col) : 0.0f; };
     const int ntiles = (N + 31) / 32, kg = Kp / 8;
@@ -662,24 +661,15 @@ KernelClass gemm_kernel_class(GemmCfg cfg)
     case CFG_CONV_POOL: return K_GEMM_CONV_POOL;   case CFG_BCONV_POOL: return K_GEMM_BCONV_POOL;
     case CFG_FC: return K_GEMM_FC;                 case CFG_BFC: return K_GEMM_BFC;
     case CFG_FC_DENSE: return K_GEMM_FC_DENSE;     case CFG_BFC_DENSE: return K_GEMM_BFC_DENSE;
-    case CFG_CONV_WIDE: return K_GEMM_CONV_WIDE;
     }
     return K_COUNT;
 }
 
 int module_width(const ds_handle* h, int m) { return m < 3 ? h->wa : (m < 8 ? h->wb : h->wc); }
 
-// zero16: 16 zero floats on the handle's device (the A operand of the zero-padding segment K-split kernels append)
-void add_tiles(GemmLaunch& L, GemmProblem& P, GemmCfg cfg, const float* zero16)
+void add_tiles(GemmLaunch& L, GemmProblem& P, GemmCfg cfg)
 {
     const TileGeom g = gemm_geom(cfg);
-    // K-split kernels need a chunk count divisible by the split: append a zero A segment (ld = 0, so
-    // every row reads the same 16 zeros); the packed weights are zero-padded past K as well.
-    while ((P.K / KC) % g.ksplit != 0) {
-        ASeg& z = P.seg[P.nseg++];
-        z.base = zero16; z.ld = 0; z.row_shift = 0; z.klen = KC;
-        P.K += KC;
-    }
     P.tiles_m = (P.M + g.bm - 1) / g.bm;
     P.tiles_n = (P.N + g.bn - 1) / g.bn;
     P.ntiles32 = (P.N + 31) / 32;
@@ -804,13 +794,13 @@ void plan_stem(Planner& P)
     GemmProblem G = base_problem(M, 128, h->wa, h->conv2);                 // conv_layer2 1x1 (layers.py:192-197)
     add_seg(G, h->cur->stem_pool, P.U(64), 0, P.U(64));
     add_out(G, h->cur->conv2o, 128, 0, 128, 1, nullptr, 0, bf);
-    add_tiles(L, G, ccfg, h->zero_seg);
+    add_tiles(L, G, ccfg);
     P.add_gemm_op(P.cnn, st, ccfg, L);
     GemmLaunch L3{};
     GemmProblem G3 = base_problem(M, 256, h->wa, h->conv3);                // conv_layer3 1x3 (layers.py:198-203)
     for (int t = 0; t < 3; ++t) add_seg(G3, h->cur->conv2o, P.U(128), t - 1, P.U(128));
     add_out(G3, h->cur->conv3o, 256, 0, 256, 1, nullptr, 0, bf);
-    add_tiles(L3, G3, ccfg, h->zero_seg);
+    add_tiles(L3, G3, ccfg);
     P.add_gemm_op(P.cnn, st, ccfg, L3);
 }
 
@@ -884,14 +874,14 @@ void plan_module_layers(Planner& P, int m, int st, const float* x, float* y, int
         add_out(G, P.eoff(y, 48), CL, 0, 48, 1, nullptr, 0, bf);        // branch2
         add_out(G, h->cur->tmpS, 48, 48, 48, 0);                        // branch5 stem (BN, no ReLU), kept fp32
         add_out(G, h->cur->tmpA, 96, 96, 96, 1, nullptr, 0, bf);        // b3a | b4a | b5a
-        add_tiles(L, G, ccfg, h->zero_seg);
+        add_tiles(L, G, ccfg);
         P.add_gemm_op(P.cnn, st, ccfg, L, ks);
         GemmLaunch L1{};
         GemmProblem Q = base_problem(M, 48, W, h->m_b1[m]);
         Q.a_mode = 1;                                   // maxpool(3, s1) fused into the A load (layers.py:90-91)
         add_seg(Q, x, P.U(xld), 0, P.U(xld));
         add_out(Q, y, CL, 0, 48, 1, nullptr, 0, bf);    // branch1
-        add_tiles(L1, Q, pcfg, h->zero_seg);
+        add_tiles(L1, Q, pcfg);
         P.add_gemm_op(P.cnn, st, pcfg, L1, ks);
     }
     {   // second-stage convs from the 32-channel intermediates             layers.py:106-110,115-119,127-131
@@ -899,15 +889,15 @@ void plan_module_layers(Planner& P, int m, int st, const float* x, float* y, int
         GemmProblem G = base_problem(M, 48, W, h->m_b3b[m]);
         for (int t = 0; t < 3; ++t) add_seg(G, P.eoff(h->cur->tmpA, 0), P.U(96), t - 1, P.U(32));
         add_out(G, P.eoff(y, 96), CL, 0, 48, 1, nullptr, 0, bf);
-        add_tiles(L, G, ccfg, h->zero_seg);
+        add_tiles(L, G, ccfg);
         GemmProblem Q = base_problem(M, 48, W, h->m_b4b[m]);
         for (int t = 0; t < 5; ++t) add_seg(Q, P.eoff(h->cur->tmpA, 32), P.U(96), t - 2, P.U(32));
         add_out(Q, P.eoff(y, 144), CL, 0, 48, 1, nullptr, 0, bf);
-        add_tiles(L, Q, ccfg, h->zero_seg);
+        add_tiles(L, Q, ccfg);
         GemmProblem R = base_problem(M, 64, W, h->m_b5b[m]);
         for (int t = 0; t < 3; ++t) add_seg(R, P.eoff(h->cur->tmpA, 64), P.U(96), t - 1, P.U(32));
         add_out(R, h->cur->tmpB, 64, 0, 64, 1, nullptr, 0, bf);
-        add_tiles(L, R, ccfg, h->zero_seg);
+        add_tiles(L, R, ccfg);
         P.add_gemm_op(P.cnn, st, ccfg, L);
     }
     {   // residual tail: relu(stem + BN(1x1 48 of tmpB))                    layers.py:132-138
@@ -915,7 +905,7 @@ void plan_module_layers(Planner& P, int m, int st, const float* x, float* y, int
         GemmProblem G = base_problem(M, 48, W, h->m_b5c[m]);
         add_seg(G, h->cur->tmpB, P.U(64), 0, P.U(64));
         add_out(G, P.eoff(y, 192), CL, 0, 48, 1, h->cur->tmpS, 48, bf);
-        add_tiles(L, G, ccfg, h->zero_seg);
+        add_tiles(L, G, ccfg);
         P.add_gemm_op(P.cnn, st, ccfg, L);
     }
 }
@@ -1104,7 +1094,7 @@ void plan_joint_model(Planner& P)
             if (h->is_cnn) add_seg(G, h->cur->sigfeat, h->SF, 0, h->SF);
         }
         add_out(G, h->cur->fc1o, h->J, 0, h->J, 0);
-        add_tiles(L, G, fc_cfg, h->zero_seg);
+        add_tiles(L, G, fc_cfg);
         P.add_gemm_op(P.tail, st, fc_cfg, L, bf ? (double)h->J / h->JP : 1.0);
     }
     Op op = make_op(OP_HEAD, K_HEAD, 0, stage_id(h, "head", 0));
@@ -1483,10 +1473,6 @@ static int ds_create_impl(const ds_config* cfg, ds_handle** out)
     h->cur = &h->slots[0];
 #undef CK
     if (!rc) {
-        float* z = nullptr;
-        rc = dalloc(h, &z, 64);
-        if (!rc && hipMemset(z, 0, 256) != hipSuccess) rc = fail(h, DS_ERR_HIP, "hipMemset");
-        h->zero_seg = z;
         if (!rc && (flags & DS_TUNE_DEBUG_STAMPS)) {
             rc = dalloc(h, &h->dbg_stamps, (size_t)NMOD * 1024 * 16);
             if (!rc) hipMemset(h->dbg_stamps, 0, (size_t)NMOD * 1024 * 16 * 8);

@@ -55,15 +55,17 @@ struct GemmLaunch {
     int pad_[2];
 };
 
-// (the numbering keeps the gaps the BiLSTM configurations of rounds 1 - 2 left: the cells have their own kernels now)
-enum GemmCfg { CFG_CONV = 0, CFG_FC = 1, CFG_CONV_WIDE = 3, CFG_CONV_POOL = 4, CFG_FC_DENSE = 5,
+// (the numbering keeps the gaps the BiLSTM configurations of rounds 1 - 2 left: the cells have their own kernels now; 3 was
+// CFG_CONV_WIDE, the 128 x 128 conv tile no plan chose)
+enum GemmCfg { CFG_CONV = 0, CFG_FC = 1, CFG_CONV_POOL = 4, CFG_FC_DENSE = 5,
                // bf16-operand variants (mixed-precision mode)
                CFG_BCONV = 7, CFG_BCONV_POOL = 8, CFG_BFC = 9, CFG_BFC_DENSE = 10 };
 
 // ---- the kernel table: one entry per __global__ function / template instantiation the engine books launches under. The planner
 // names an op's entry when it chooses the variant (Op::kernel); ds_num_kernels / ds_get_kernel_stat expose the table by POSITION and
 // recorded profiles are keyed by the name strings, so order, count and names are ABI: append, never reorder, rename or remove (the
-// grouped-GEMM BiLSTM configurations, the wide conv tile and lstm_cell_kernel<2> are launched by no plan any more and stay).
+// grouped-GEMM BiLSTM configurations, the wide conv tile gemm_kernel<2,2,2,2,0,0,1,1> and lstm_cell_kernel<2> are no longer built or
+// launched; their entries stay).
 #define DS_KERNEL_TABLE(X)                                                                                                             \
     X(K_GEMM_CONV, "gemm_kernel<1,2,4,1,0,0,1,1>")             X(K_GEMM_FC, "gemm_kernel<1,3,4,1,0,0,2,1>")                             \
     X(K_GEMM_LSTM, "gemm_kernel<1,4,4,1,1,0,1,1>")             X(K_GEMM_CONV_WIDE, "gemm_kernel<2,2,2,2,0,0,1,1>")                      \
@@ -151,7 +153,7 @@ hipError_t launch_lstm_xproj(const LstmXproj& X, hipStream_t s);
 // product is cut into blocks of mtiles_per_wg m-tiles, each shared by wgs_per_mblock workgroups along the columns. Every tile of a
 // family gives the same bits (same K order per output element).
 enum LstmTile {
-    LT_F1, LT_F2, LT_F4,          // fp32 cells, operands from global memory: 128 sites x 1, 2 or 4 n-tiles of 32 columns per wave
+    LT_F1, LT_F4,                 // fp32 cells, operands from global memory: 128 sites x 1 or 4 n-tiles of 32 columns per wave
     LT_LDS1, LT_LDS2,             // fp32 cells, operands through an LDS ring: 64 sites x 64 / 128 columns
     LT_B11, LT_B12, LT_B22,       // bf16-operand cells (DS_PRECISION_BF16_ALL): 64 x 64, 64 x 128, 128 x 128
     LT_S11, LT_S12, LT_S22,       // split-operand cells (DS_PRECISION_BF16X3, ds_split.hip): the same three shapes ...
@@ -160,7 +162,7 @@ enum LstmTile {
 };
 struct LstmTileInfo { KernelClass kernel; int mtiles_per_wg; int wgs_per_mblock; };
 constexpr LstmTileInfo kLstmTiles[LT_COUNT] = {
-    {K_LSTM_CELL1, 4, 32}, {K_LSTM_CELL2, 4, 16}, {K_LSTM_CELL4, 4, 8}, {K_LSTM_LDS1, 2, 16}, {K_LSTM_LDS2, 2, 8},
+    {K_LSTM_CELL1, 4, 32}, {K_LSTM_CELL4, 4, 8},  {K_LSTM_LDS1, 2, 16}, {K_LSTM_LDS2, 2, 8},
     {K_LSTM_B11, 2, 16},   {K_LSTM_B12, 2, 8},    {K_LSTM_B22, 4, 8},
     {K_LSTM_S11, 2, 16},   {K_LSTM_S12, 2, 8},    {K_LSTM_S22, 4, 8},   {K_LSTM_S28, 4, 8}};
 // workgroups one cell adds to a launch: the launchers' grid is ncell times this, and LstmLaunch::cls_tiles sums it per work class
@@ -174,7 +176,7 @@ inline bool lstm_tile_is_split(LstmTile t) { return t >= LT_S11; }
 hipError_t launch_lstm_cells(LstmTile tile, const LstmLaunch& L, hipStream_t s);
 
 // tile geometry per config (host needs it for grid sizing)
-struct TileGeom { int bm, bn, threads, ksplit; };
+struct TileGeom { int bm, bn, threads; };
 TileGeom gemm_geom(GemmCfg cfg);
 
 hipError_t launch_gemm(GemmCfg cfg, const GemmLaunch* d_launch, int total_tiles, hipStream_t s);

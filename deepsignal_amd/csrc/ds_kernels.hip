@@ -24,29 +24,28 @@ namespace ds {
 // K chunk is 16 units = 64 B per row (16 floats / 32 bf16), one 16-B fragment per lane feeds four
 // v_mfma_f32_32x32x2_f32 (fp32) or ONE v_mfma_f32_32x32x16_bf16 (lane half h owns k = 8h..8h+7 of the 16).
 // The host passes ld / klen / K of bf16 operands in units, so the staging code is shared.
-// KS = in-workgroup K split: KS wave groups ("K-lanes") own the same output tile and take alternate
-// 16-wide K chunks (lane g: chunks g, g+KS, ...), each with its own LDS staging area, and the partial
-// accumulators are exchanged through LDS at the end. It doubles the waves per SIMD for grids that
-// only have ~one workgroup per CU and halves the serial chunk chain of short-K problems.
+// KS is 1 in every instantiation (it was an in-workgroup K split that no plan selected, retired to
+// profiles/experiments/); the parameter stays because the kernel names in the kernel table and the committed profiles carry it.
 template <int MT, int NT, int WM, int WN, int EPI, int AMODE, int BD, int KS, bool BF = false>
-__global__ __launch_bounds__(64 * WM * WN * KS, 1) void gemm_kernel(const GemmLaunch* __restrict__ L)
+__global__ __launch_bounds__(64 * WM * WN, 1) void gemm_kernel(const GemmLaunch* __restrict__ L)
 {
+    static_assert(KS == 1, "the in-workgroup K split is retired (profiles/EXPERIMENTS.md)");
     constexpr int BM = WM * MT * 32;
     constexpr int LDA = KC + 4;
-    constexpr int NTHR = 64 * WM * WN;          // threads per K-lane
+    constexpr int NTHR = 64 * WM * WN;
     constexpr int SLOTS = (BM * 4 + NTHR - 1) / NTHR;
-    constexpr int AS_FLOATS = 2 * KS * BM * LDA;
-    constexpr int RED_FLOATS = KS > 1 ? WM * WN * MT * NT * 16 * 64 : 0;
-    __shared__ __attribute__((aligned(16))) float smem_[AS_FLOATS > RED_FLOATS ? AS_FLOATS : RED_FLOATS];
+    __shared__ __attribute__((aligned(16))) float smem_[2 * BM * LDA];
 
     // the wave index is wave-uniform, but hipcc cannot prove it from threadIdx: readfirstlane keeps the
-    // K-lane / segment-cursor logic on the scalar unit (otherwise it becomes exec-masked vector code)
+    // segment-cursor logic on the scalar unit (otherwise it becomes exec-masked vector code)
     const int lane = threadIdx.x & 63, wave_all = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int kl = wave_all / (WM * WN);        // K-lane of this wave
+    // kl is 0 (a workgroup is NTHR threads) and hipcc folds it, but late: with the literal in its place the same instructions come
+    // out on other scalar registers in every instantiation. It stays in these five lines so that the device code is the measured one.
+    const int kl = wave_all / (WM * WN);
     const int wave = wave_all % (WM * WN);
-    const int tid = threadIdx.x - kl * NTHR;    // thread index inside the K-lane
-    float* const As0 = smem_ + (0 * KS + kl) * BM * LDA;
-    float* const As1 = smem_ + (1 * KS + kl) * BM * LDA;
+    const int tid = threadIdx.x - kl * NTHR;
+    float* const As0 = smem_ + kl * BM * LDA;
+    float* const As1 = smem_ + (1 + kl) * BM * LDA;
     const int wm = wave % WM, wn = wave / WM;
     // XCD-aware tile order: hardware deals workgroup b to XCD b % 8, each with a private L2. Give every XCD a
     // contiguous run of logical tiles (m-tiles of one weight panel are neighbours), so a weight panel is pulled
@@ -68,7 +67,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS, 1) void gemm_kernel(const GemmLa
     const int tn = P.n_fast ? local % P.tiles_n : local / P.tiles_m;
     const int m0 = tm * BM;
     const int M = P.M, W = P.W;
-    const int nchunks = P.K / KC / KS;          // chunks per K-lane (planner pads K to a multiple of KC*KS)
+    const int nchunks = P.K / KC;               // (the planner pads K to a multiple of KC)
     const int nseg = P.nseg;
 
     // per-slot row bookkeeping (a slot = one float4 of the staged A chunk)
@@ -129,14 +128,6 @@ __global__ __launch_bounds__(64 * WM * WN * KS, 1) void gemm_kernel(const GemmLa
     auto advance = [&]() {
         if (--seg_left == 0 && ++seg_i < nseg) seg_begin(seg_i);
     };
-    auto skip_chunk = [&]() {     // step the cursor over a chunk that belongs to another K-lane
-#pragma unroll
-        for (int i = 0; i < SLOTS; ++i) {
-            ap[i] += KC;
-            if (AMODE == 1) { apm[i] += KC; app[i] += KC; }
-        }
-        advance();
-    };
     // Software pipeline (per chunk c, parity X = c&1; chunk k lives in R[k&1] / b[k&1] / As[k&1] / a[k&1]):
     //   (1) issue global loads: A rows of chunk c+2 -> R[X], weights of chunk c+BD -> b[(c+BD) % (BD+1)]
     //       (BD = weight prefetch distance in chunks: 1 for L2-resident weights, 2 when they stream from HBM)
@@ -169,8 +160,6 @@ __global__ __launch_bounds__(64 * WM * WN * KS, 1) void gemm_kernel(const GemmLa
             if (AMODE != 2) lok[X][i] = aok[i];
         }
         advance();
-#pragma unroll
-        for (int j = 1; j < KS; ++j) skip_chunk();
     };
     auto store_a = [&](int X, int P = -1) {      // ring slot X -> LDS buffer P (default: the slot's own parity)
         float* dst = (P < 0 ? X : P) ? As1 : As0;
@@ -195,7 +184,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS, 1) void gemm_kernel(const GemmLa
         for (int nt = 0; nt < NT; ++nt) {
             bq[X][nt][0] = gload4(bp[nt]);
             bq[X][nt][1] = gload4(bp[nt] + 256);
-            bp[nt] += 512 * KS;
+            bp[nt] += 512;
         }
     };
     auto read_frags = [&](int X) {
@@ -298,9 +287,6 @@ __global__ __launch_bounds__(64 * WM * WN * KS, 1) void gemm_kernel(const GemmLa
 
     if (nchunks > 0) {
         seg_begin(0);
-#pragma unroll
-        for (int j = 0; j < KS - 1; ++j)
-            if (j < kl) skip_chunk();
         load_a(0);
         load_b(0);
         store_a(0);
@@ -380,37 +366,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS, 1) void gemm_kernel(const GemmLa
 #undef DS_STEP
 #undef DS_STEPD
 
-    // ---------------- K-lane exchange: each lane ends up owning half of the accumulator rows ----------------
-    constexpr int R0 = 0;
-    int r_lo = 0, r_hi = 16;
-    if (KS == 2) {
-        __syncthreads();                       // staging buffers are dead; reuse them for the exchange
-        float* red = smem_ + (size_t)wave * MT * NT * 16 * 64;
-        const int give_lo = kl == 0 ? 8 : 0;   // registers this lane hands to the other lane
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const float v = kl == 0 ? acc[mt][nt][8 + r] : acc[mt][nt][r];
-                    red[((mt * NT + nt) * 16 + give_lo + r) * 64 + lane] = v;
-                }
-        __syncthreads();
-        const int take_lo = kl == 0 ? 0 : 8;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const float v = red[((mt * NT + nt) * 16 + take_lo + r) * 64 + lane];
-                    if (kl == 0) acc[mt][nt][r] += v; else acc[mt][nt][8 + r] += v;
-                }
-        r_lo = take_lo; r_hi = take_lo + 8;
-    }
-    (void)R0;
-    // ---------------- epilogue (rows r_lo..r_hi-1 of every 16-register accumulator) ----------------
+    // ---------------- epilogue ----------------
     const int rbase = m0 + wm * MT * 32 + 4 * (lane >> 5);
     if (EPI == 0) {
 #pragma unroll
@@ -428,7 +384,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS, 1) void gemm_kernel(const GemmLa
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = rbase + mt * 32 + (r & 3) + 8 * (r >> 2);
-                    if (row < M && r >= r_lo && r < r_hi) {
+                    if (row < M) {
                         float v = acc[mt][nt][r] + bias;
                         if (os.add) v += gload(os.add + (size_t)row * os.add_ld + cc);
                         if (os.relu) v = relu_f(v);
@@ -446,17 +402,16 @@ __global__ __launch_bounds__(64 * WM * WN * KS, 1) void gemm_kernel(const GemmLa
 TileGeom gemm_geom(GemmCfg cfg)
 {
     switch (cfg) {
-    case CFG_CONV: return {128, 64, 256, 1};        // MT1 NT2 WM4 WN1
-    case CFG_FC: return {128, 96, 256, 1};          // MT1 NT3 WM4 WN1, weights prefetched 2 chunks ahead
-    case CFG_CONV_WIDE: return {128, 128, 256, 1};  // MT2 NT2 WM2 WN2
-    case CFG_CONV_POOL: return {128, 64, 256, 1};   // CFG_CONV with maxpool(3,s1) fused into the A load
-    case CFG_FC_DENSE: return {128, 96, 256, 1};    // CFG_FC for M % 128 == 0 (no row masks)
-    case CFG_BCONV: return {128, 64, 256, 1};       // bf16 operands, same staging as CFG_CONV
-    case CFG_BCONV_POOL: return {128, 64, 256, 1};
-    case CFG_BFC: return {128, 256, 256, 1};        // MT4 NT2 WM1 WN4: every wave owns all 128 rows x 64 columns, so a
-    case CFG_BFC_DENSE: return {128, 256, 256, 1};  // weight fragment is loaded by exactly one wave of the workgroup
+    case CFG_CONV: return {128, 64, 256};        // MT1 NT2 WM4 WN1
+    case CFG_FC: return {128, 96, 256};          // MT1 NT3 WM4 WN1, weights prefetched 2 chunks ahead
+    case CFG_CONV_POOL: return {128, 64, 256};   // CFG_CONV with maxpool(3,s1) fused into the A load
+    case CFG_FC_DENSE: return {128, 96, 256};    // CFG_FC for M % 128 == 0 (no row masks)
+    case CFG_BCONV: return {128, 64, 256};       // bf16 operands, same staging as CFG_CONV
+    case CFG_BCONV_POOL: return {128, 64, 256};
+    case CFG_BFC: return {128, 256, 256};        // MT4 NT2 WM1 WN4: every wave owns all 128 rows x 64 columns, so a
+    case CFG_BFC_DENSE: return {128, 256, 256};  // weight fragment is loaded by exactly one wave of the workgroup
     }
-    return {0, 0, 0, 1};
+    return {0, 0, 0};
 }
 
 hipError_t launch_gemm(GemmCfg cfg, const GemmLaunch* d_launch, int total_tiles, hipStream_t s)
@@ -465,7 +420,6 @@ hipError_t launch_gemm(GemmCfg cfg, const GemmLaunch* d_launch, int total_tiles,
     switch (cfg) {
     case CFG_CONV: hipLaunchKernelGGL((gemm_kernel<1, 2, 4, 1, 0, 0, 1, 1>), dim3(total_tiles), dim3(256), 0, s, d_launch); break;
     case CFG_FC: hipLaunchKernelGGL((gemm_kernel<1, 3, 4, 1, 0, 0, 2, 1>), dim3(total_tiles), dim3(256), 0, s, d_launch); break;
-    case CFG_CONV_WIDE: hipLaunchKernelGGL((gemm_kernel<2, 2, 2, 2, 0, 0, 1, 1>), dim3(total_tiles), dim3(256), 0, s, d_launch); break;
     case CFG_CONV_POOL: hipLaunchKernelGGL((gemm_kernel<1, 2, 4, 1, 0, 1, 1, 1>), dim3(total_tiles), dim3(256), 0, s, d_launch); break;
     case CFG_FC_DENSE: hipLaunchKernelGGL((gemm_kernel<1, 3, 4, 1, 0, 2, 2, 1>), dim3(total_tiles), dim3(256), 0, s, d_launch); break;
     case CFG_BCONV: hipLaunchKernelGGL((gemm_kernel<1, 2, 4, 1, 0, 0, 1, 1, true>), dim3(total_tiles), dim3(256), 0, s, d_launch); break;
@@ -899,7 +853,7 @@ __global__ __launch_bounds__(256, MTW * NTW >= 4 ? 2 : 3) void lstm_cell_bf16_ke
 
     const float* const fa0 = ring + (mi * MTW) * 256 + lane4;
     const float* const fb0 = ring + (FRA + nj * NTW) * 256 + lane4;
-    // (SplitRing::run_piped's register-piped, pinned K loop -- ds_split.hip -- was built into this kernel in round 6, git 5dac46d: bit-identical,
+    // (SplitRing::run's register-piped, pinned K loop -- ds_split.hip -- was built into this kernel in round 6, git 5dac46d: bit-identical,
     // 715 - 722 against 689 - 693 us per 4,096-site step, 159 against 163 us at 512; at 2 - 3 workgroups per CU the other waves already fill the
     // gaps that order closes for the one-wave-per-SIMD split kernels: profiles/r06_bf16_lstm_piped.json)
     auto stage = [&](int st, auto slot_c) __attribute__((always_inline)) {
@@ -970,7 +924,6 @@ hipError_t launch_lstm_cells(LstmTile tile, const LstmLaunch& L, hipStream_t s)
     // (a 128 x 256 tile -- a wave owning 64 sites x 128 columns, 0.09 KiB of operand fragments per MFMA against 0.125 -- was measured in
     // round 5: 756 against 673 us per 4096-site step; 768 workgroups of 72 KB rings fill the GPU in 1.5 rounds)
     case LT_F1: hipLaunchKernelGGL(lstm_cell_kernel<1>, grid, dim3(256), 0, s, L); break;
-    case LT_F2: hipLaunchKernelGGL(lstm_cell_kernel<2>, grid, dim3(256), 0, s, L); break;
     case LT_F4: hipLaunchKernelGGL(lstm_cell_kernel<4>, grid, dim3(256), 0, s, L); break;
     case LT_S11: case LT_S12: case LT_S22: case LT_S28: case LT_COUNT: return hipErrorInvalidValue;      // launch_lstm_cells_split's
     }
@@ -1454,16 +1407,6 @@ hipError_t launch_inception_fused(int tm, const FusedChain& c, hipStream_t s)
 #ifndef DS_FUSEDB_WPS
 #define DS_FUSEDB_WPS 4
 #endif
-// input rows are read exactly once: a non-temporal load does not keep them in the XCD's L2, which then holds the rows the
-// workgroups have just WRITTEN (the next module of the chain reads those)
-#ifndef DS_FUSEDB_NT
-#define DS_FUSEDB_NT 1
-#endif
-#if DS_FUSEDB_NT
-#define DS_FUSEDB_TILE_LOAD(p) gload4_nt(p)
-#else
-#define DS_FUSEDB_TILE_LOAD(p) gload4(p)
-#endif
 #ifndef DS_FUSEDB_POOLPRIO
 #define DS_FUSEDB_POOLPRIO 2
 #endif
@@ -1611,7 +1554,9 @@ __global__ __launch_bounds__(512, TM >= 2 ? DS_FUSEDB_WPS : 2) void inception_fu
             for (int i = 0; i < NSLOT; ++i) {
                 const int id = tid + i * 512, row = id >> 5, q = id & 31;
                 const int rr = row < TRv ? row : TRv - 1;
-                st[i] = DS_FUSEDB_TILE_LOAD(a.X + (grow0 + rr) * cinu + q * 4);      // read once: see DS_FUSEDB_NT
+                // read exactly once: a non-temporal load does not keep the input rows in the XCD's L2, which then holds the rows the
+                // workgroups have just WRITTEN (the next module of the chain reads those)
+                st[i] = gload4_nt(a.X + (grow0 + rr) * cinu + q * 4);
             }
         } else {
             // module right after maxpool_layer2/3: staged row (site s, w) = max of the input rows 2w - pad + {0,1,2} that exist

@@ -143,23 +143,6 @@ __device__ __forceinline__ void fuseds_conv_units(const char* T1, const int (&rm
 #define DS_SPLIT_SW0 0          // the two waves whose phase stamps a debug build records (tools/stamps.py prints them as "wave 0" / "wave 7")
 #define DS_SPLIT_SW1 7
 #endif
-#ifndef DS_SPLIT_BISECT
-#define DS_SPLIT_BISECT 0       // timing-only bisect builds of P1 (results WRONG): 1 no transform / LDS writes, 2 no row loads, 4 no barrier in the
-#endif                          // chunk loop, 8 no weight loads, 16 no fragment reads, 32 no transform arithmetic, 64 no staged writes, 128 no raw reads
-#ifndef DS_SPLIT_WNT
-#define DS_SPLIT_WNT 0          // 1: P1 weight fragments by non-temporal loads
-#endif
-#if DS_SPLIT_WNT
-#define DS_SPLIT_WLOAD(p) gload4_nt(p)
-#else
-#define DS_SPLIT_WLOAD(p) gload4(p)
-#endif
-#ifndef DS_SPLIT_READS_FIRST
-#define DS_SPLIT_READS_FIRST 1
-#endif
-#ifndef DS_P1_CLOCK
-#define DS_P1_CLOCK 0           // 1: s_memtime inside every P1 step (lo half | LDS drain | barrier | hi half), printed by two workgroups for the chain's
-#endif                          // second module (diagnostic build: tools/attic/r06_p1clk.sh)
 template <int R> struct SplitRole { static constexpr int value = R; };
 
 template <int TM>
@@ -277,68 +260,39 @@ __global__ __launch_bounds__(512, 2) void inception_fused_split_kernel(const Fus
         float4 vo[VD];                      // the stager's 16 B of its row, chunks in flight
         float4 bq[BD][3];
         float4 af[2][3][TM];
-#if DS_SPLIT_BISECT
-        {
-            const float4 z = make_float4(__uint_as_float(tid), 1.f, 2.f, 3.f);
-            for (int i = 0; i < VD; ++i) vo[i] = z;
-            for (int i = 0; i < BD; ++i) bq[i][0] = bq[i][1] = bq[i][2] = z;
-            for (int i = 0; i < 2; ++i) for (int p = 0; p < 3; ++p) for (int mt = 0; mt < TM; ++mt) af[i][p][mt] = z;
-        }
-#endif
         // waves 6, 7 (branch 1) read the pooled half of a staged row
         const char* const fsrc = Pst + rlane * S_LDP + (lane >> 5) * 16 + (wave >= 6 ? 96 : 0);
         char* const sdst = Pst + sr * S_LDP + sq * 8;
         char* const rdst = Raw + sr * S_LDR + sq * 16;
         auto load_a = [&](int V) __attribute__((always_inline)) {
-            if (STG && !(DS_SPLIT_BISECT & 2)) {
+            if (STG) {
                 vo[V] = gload4(pc);
                 if (pooled_in) vo[V] = f4max(f4max(vo[V], gload4(pc + oq)), gload4(pc + orr));      // wave-uniform branch
                 pc += KC;
             }
         };
         auto raw_a = [&](int X, int V) __attribute__((always_inline)) {
-            if (STG && !(DS_SPLIT_BISECT & 1)) *reinterpret_cast<float4*>(rdst + X * TR32 * S_LDR) = vo[V];
-        };
-        float4 rv[3];                                   // (DS_P1_CLOCK 2 only: the raw rows read apart from the transform)
-        auto raw_read = [&](int slot) __attribute__((always_inline)) {
-            if (STG && !(DS_SPLIT_BISECT & 1)) {
-                const char* r = rdst + slot * TR32 * S_LDR;
-                rv[0] = *reinterpret_cast<const float4*>(r);
-                rv[1] = *reinterpret_cast<const float4*>(r + om);
-                rv[2] = *reinterpret_cast<const float4*>(r + op);
-            }
+            if (STG) *reinterpret_cast<float4*>(rdst + X * TR32 * S_LDR) = vo[V];
         };
         auto store_a = [&](int X) __attribute__((always_inline)) {
-            if (STG && !(DS_SPLIT_BISECT & 1)) {
+            if (STG) {
                 const char* r = rdst + X * TR32 * S_LDR;
-                float4 o, m, n;
-                if (DS_SPLIT_BISECT & 128) { o = vo[0]; m = vo[1 % VD]; n = vo[2 % VD]; }      // (timing only: no raw reads)
-                else if (DS_P1_CLOCK == 2) { o = rv[0]; m = rv[1]; n = rv[2]; }
-                else {
-                    o = *reinterpret_cast<const float4*>(r);
-                    m = *reinterpret_cast<const float4*>(r + om);
-                    n = *reinterpret_cast<const float4*>(r + op);
-                }
+                const float4 o = *reinterpret_cast<const float4*>(r);
+                const float4 m = *reinterpret_cast<const float4*>(r + om);
+                const float4 n = *reinterpret_cast<const float4*>(r + op);
                 char* d = sdst + X * TR32 * S_LDP;
                 uint2 t0, t1, t2;
-                constexpr bool NOARITH = (DS_SPLIT_BISECT & 32) != 0, NOWRITE = (DS_SPLIT_BISECT & 64) != 0;      // (timing-only builds)
-                if (NOARITH) { t0 = make_uint2(__float_as_uint(o.x), __float_as_uint(o.y)); t1 = make_uint2(__float_as_uint(o.z), __float_as_uint(o.w)); t2 = make_uint2(__float_as_uint(m.x), __float_as_uint(m.y)); }
-                else split3x4(o.x, o.y, o.z, o.w, t0, t1, t2);
-                if (NOWRITE) asm volatile("" ::"v"(t0.x), "v"(t0.y), "v"(t1.x), "v"(t1.y), "v"(t2.x), "v"(t2.y));
-                else { *reinterpret_cast<uint2*>(d) = t0; *reinterpret_cast<uint2*>(d + 32) = t1; *reinterpret_cast<uint2*>(d + 64) = t2; }
-                if (NOARITH) { t0 = make_uint2(__float_as_uint(m.z), __float_as_uint(m.w)); t1 = make_uint2(__float_as_uint(n.x), __float_as_uint(n.y)); t2 = make_uint2(__float_as_uint(n.z), __float_as_uint(n.w)); }
-                else split3x4(fmaxf(fmaxf(o.x, m.x), n.x), fmaxf(fmaxf(o.y, m.y), n.y), fmaxf(fmaxf(o.z, m.z), n.z), fmaxf(fmaxf(o.w, m.w), n.w), t0, t1, t2);
-                if (NOWRITE) asm volatile("" ::"v"(t0.x), "v"(t0.y), "v"(t1.x), "v"(t1.y), "v"(t2.x), "v"(t2.y));
-                else { *reinterpret_cast<uint2*>(d + 96) = t0; *reinterpret_cast<uint2*>(d + 128) = t1; *reinterpret_cast<uint2*>(d + 160) = t2; }
+                split3x4(o.x, o.y, o.z, o.w, t0, t1, t2);
+                *reinterpret_cast<uint2*>(d) = t0; *reinterpret_cast<uint2*>(d + 32) = t1; *reinterpret_cast<uint2*>(d + 64) = t2;
+                split3x4(fmaxf(fmaxf(o.x, m.x), n.x), fmaxf(fmaxf(o.y, m.y), n.y), fmaxf(fmaxf(o.z, m.z), n.z), fmaxf(fmaxf(o.w, m.w), n.w), t0, t1, t2);
+                *reinterpret_cast<uint2*>(d + 96) = t0; *reinterpret_cast<uint2*>(d + 128) = t1; *reinterpret_cast<uint2*>(d + 160) = t2;
             }
         };
         auto load_b = [&](int Bi) __attribute__((always_inline)) {
-            if (DS_SPLIT_BISECT & 8) return;
-            bq[Bi][0] = DS_SPLIT_WLOAD(bp); bq[Bi][1] = DS_SPLIT_WLOAD(bp + 256); bq[Bi][2] = DS_SPLIT_WLOAD(bp + 512);
+            bq[Bi][0] = gload4(bp); bq[Bi][1] = gload4(bp + 256); bq[Bi][2] = gload4(bp + 512);
             bp += 768;
         };
         auto read_frags = [&](int X) __attribute__((always_inline)) {
-            if (DS_SPLIT_BISECT & 16) return;
 #pragma unroll
             for (int mt = 0; mt < TM; ++mt) {
                 const char* q = fsrc + X * TR32 * S_LDP + mt * 32 * S_LDP;
@@ -353,15 +307,9 @@ __global__ __launch_bounds__(512, 2) void inception_fused_split_kernel(const Fus
         raw_a(0, 0);
         raw_a(1, 1 % VD);
         lds_barrier();
-        if (DS_P1_CLOCK == 2) raw_read(0);
         store_a(0);
         lds_barrier();
         read_frags(0);
-#if DS_P1_CLOCK
-        unsigned long long pk[4] = {0, 0, 0, 0}, pl[4] = {0, 0, 0, 0}, plast = 0, pm = 0;
-        unsigned long long ptop = __builtin_amdgcn_s_memtime();
-        const unsigned long long pbeg = ptop;
-#endif
 #pragma unroll
         for (int cc = 0; cc < 16; ++cc) {
             if (cc < nchunks) {                                   // wave-uniform; only cc = 15 is really conditional
@@ -370,57 +318,18 @@ __global__ __launch_bounds__(512, 2) void inception_fused_split_kernel(const Fus
                 if (has2) raw_a(X, (cc + 2) % VD);                // the raw copy chunk cc lived in was last read at step cc - 1
                 if (cc + VD < nchunks) load_a(cc % VD);           // chunk cc + VD into the register stage chunk cc left two steps ago
                 if (cc + BD - 1 < nchunks) load_b((cc + BD - 1) % BD);
-#if DS_P1_CLOCK == 2
-                // (diagnostic: the lo half taken apart -- loads / raw write | raw reads until they have landed | arithmetic + staged writes issued | MFMAs)
-                __builtin_amdgcn_sched_barrier(0);
-                const unsigned long long l0 = __builtin_amdgcn_s_memtime();
-                if (has1 && STG) { raw_read((cc + 1) & 1); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-                __builtin_amdgcn_sched_barrier(0);
-                const unsigned long long l1 = __builtin_amdgcn_s_memtime();
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
                 if (has1) store_a(X ^ 1);
-                __builtin_amdgcn_sched_barrier(0);
-                const unsigned long long l2 = __builtin_amdgcn_s_memtime();
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                const unsigned long long l3 = __builtin_amdgcn_s_memtime();
-                __builtin_amdgcn_sched_barrier(0);
-                pl[0] += l0 - ptop; pl[1] += l1 - l0; pl[2] += l2 - l1; pl[3] += l3 - l2; plast = l3;
-#else
-                if (has1) store_a(X ^ 1);
-#endif
 #pragma unroll
                 for (int mt = 0; mt < TM; ++mt) acc[mt] = mfma3_lo(bq[cc % BD], af[X][0][mt], af[X][1][mt], af[X][2][mt], acc[mt]);
                 __builtin_amdgcn_sched_barrier(0);
-#if DS_P1_CLOCK
-                const unsigned long long q1 = __builtin_amdgcn_s_memtime();
-                pm += q1 - plast;
-                asm volatile("s_waitcnt lgkmcnt(1)" ::: "memory");      // (everything but the stamp just requested)
-                const unsigned long long q2 = __builtin_amdgcn_s_memtime();
-                asm volatile("s_barrier" ::: "memory");
-                const unsigned long long q3 = __builtin_amdgcn_s_memtime();
-#else
-                if (!(DS_SPLIT_BISECT & 4)) lds_barrier();
-#endif
+                lds_barrier();
                 if (has1) read_frags(X ^ 1);
 #pragma unroll
                 for (int mt = 0; mt < TM; ++mt) acc[mt] = mfma3_hi(bq[cc % BD], af[X][0][mt], af[X][1][mt], acc[mt]);
-#if DS_SPLIT_READS_FIRST
                 if (has1) __builtin_amdgcn_sched_group_barrier(0x100, 3 * TM, 0);      // the next chunk's fragment reads lead the half-step
-#endif
                 __builtin_amdgcn_sched_barrier(0);
-#if DS_P1_CLOCK
-                const unsigned long long q4 = __builtin_amdgcn_s_memtime();
-                pk[0] += q1 - ptop; pk[1] += q2 - q1; pk[2] += q3 - q2; pk[3] += q4 - q3; ptop = q4;
-#endif
             }
         }
-#if DS_P1_CLOCK
-        if (mi == 1 && (blockIdx.x == 0 || blockIdx.x == 37) && lane == 0)
-            printf("P1CLK block %d wave %d role %d W %d: cycles per step lo %d drain %d barrier %d hi %d | P1 total %d | lo: top %d rawread %d transform %d writes-land %d mfma %d\n", (int)blockIdx.x, wave, ROLE, W,
-                   (int)(pk[0] / nchunks), (int)(pk[1] / nchunks), (int)(pk[2] / nchunks), (int)(pk[3] / nchunks), (int)(ptop - pbeg),
-                   (int)(pl[0] / nchunks), (int)(pl[1] / nchunks), (int)(pl[2] / nchunks), (int)(pl[3] / nchunks), (int)(pm / nchunks));
-#endif
     };
     if (wave < 2 * TM) run_p1(SplitRole<1>{}); else run_p1(SplitRole<0>{});      // wave-uniform
     DS_STAMP(1);
@@ -785,7 +694,7 @@ hipError_t launch_stem23_split(const Stem23Args& a, hipStream_t s)
 // which is what a cell's epilogue writes for h (split once, where it is produced) and what pack_joint_split_kernel writes for the
 // joint row; the weights are pack_b_split's panels [n-tile][k-step][term][64][8].
 // One workgroup per CU means one wave per SIMD: hipcc's read -> wait -> MFMA schedule and the requests' issue time in front of the
-// MFMAs cost these kernels 12 - 25 % until SplitRing::run_piped pinned the order (round 5). What bounds them since is what a CU takes in
+// MFMAs cost these kernels 12 - 25 % until SplitRing::run pinned the order (round 5). What bounds them since is what a CU takes in
 // from the L2 (round 6): at full matrix rate a tile asks for 2048 (M + N) / (M N) B/clk -- 32 at 128 x 128, where
 // the cells move 23; 18.7 at 256 x 192, where the dense is bound by the matrix pipe -- and the same 128 x 128 tile by EIGHT waves (two per
 // SIMD, WM x WN = 4 x 2) takes the same time. The split cells use the 128 x 128 tile: slower alone than 64 x 64, faster in the pipelined step;
@@ -793,55 +702,30 @@ hipError_t launch_stem23_split(const Stem23Args& a, hipStream_t s)
 constexpr int SPLIT_KSTEP_BYTES = 3 * 1024;               // the three term fragments of one k-step
 constexpr int SPLIT_MT_BYTES = 16 * SPLIT_KSTEP_BYTES;    // one m-tile of a split h buffer (256 units = 16 k-steps)
 
-#ifndef DS_SPLIT_PIPED
-#define DS_SPLIT_PIPED 1        // SplitRing::run: 1 = the register-piped K loop with the pinned instruction order (shipped), 0 = one stage at a
-#endif                          // time (run_simple: the loop of mid-round 5, kept for same-box A/Bs through tools/build_variant.sh)
-#ifndef DS_SPLIT_KGS11
-#define DS_SPLIT_KGS11 1
-#endif
-#ifndef DS_SPLIT_KGS22
-#define DS_SPLIT_KGS22 1
-#endif
-#ifndef DS_RING_SCHED
-#define DS_RING_SCHED 1
-#endif
-#ifndef DS_RING_BISECT
-#define DS_RING_BISECT 0      // timing experiments only (results WRONG): 4 = no K loop at all; with DS_SPLIT_PIPED=0 also 1 = no MFMAs, 2 = no LDS-DMA requests, 3 = no barrier
-#endif
 #ifndef DS_SPLIT_LSTM_SLOTS
 #define DS_SPLIT_LSTM_SLOTS 3
 #endif
 #ifndef DS_SPLIT_DENSE_SLOTS
 #define DS_SPLIT_DENSE_SLOTS 4
 #endif
-// WM x WN waves (= 4), each MTW x NTW tiles of 32 x 32; NSLOT ring slots: stage st + NSLOT - 1 is requested while stage st is consumed
+// WM x WN waves (= 4), each MTW x NTW tiles of 32 x 32; NSLOT ring slots: stage st + NSLOT is requested into the slot of
+// stage st once every wave has read it
 template <int MTW, int NTW, int WM = 2, int WN = 2, int NSLOT = 3>
 struct SplitRing {
     static constexpr int NW = WM * WN;                       // waves per workgroup: 4, or 8 (two per SIMD: one wave's waits and requests under the other's MFMAs)
     static_assert(NW == 4 || NW == 8, "four or eight waves per workgroup");
-    static_assert(NSLOT >= 3 && (NSLOT - 2) * ((3 * (WM * MTW + WN * NTW) + NW - 1) / NW) <= 63, "vmcnt holds six bits");
     static constexpr int FRA = WM * MTW, FRB = WN * NTW;
     static constexpr int NF1 = 3 * (FRA + FRB);              // 1 KiB fragments per k-step
-    // k-steps per ring stage: one barrier per KGS k-steps. DS_SPLIT_KGS11 / DS_SPLIT_KGS22: measured choices for the 64 x 64 and the
-    // 128 x 128 tile. The fragments of a stage are dealt to the four waves round robin; where NF is not a multiple of 4 (the 64 x 128
-    // tile: 18) waves 0 .. NF % NW - 1 request one more than the others and wait with a count of their own.
-    static constexpr int KGS = (MTW == 1 && NTW == 1) ? DS_SPLIT_KGS11 : (MTW == 2 && NTW == 2) ? DS_SPLIT_KGS22 : 1;
-    static constexpr int NF = KGS * NF1;
-    static constexpr int LPS = (NF + NW - 1) / NW;                 // LDS-DMA requests per wave and stage (waves >= NF % NW: one fewer if NF % NW)
-    static constexpr int STAGE = NF * 256;                   // floats
-    // (piped loop: waves with one fragment fewer send a filler request into a pad, so that every wave counts the same vmcnt)
-    static constexpr int PAD_BYTES = (DS_SPLIT_PIPED && NF % NW != 0) ? NW * 1024 : 0;
+    // one k-step per ring stage. The fragments of a stage are dealt to the waves round robin; where NF1 is not a multiple of NW (the
+    // 64 x 128 tile: 18 over 4) waves >= NF1 % NW have one fragment fewer: they send a filler request into a pad, so that every wave
+    // counts the same vmcnt
+    static constexpr int LPS = (NF1 + NW - 1) / NW;           // LDS-DMA requests per wave and stage
+    static constexpr int STAGE = NF1 * 256;                  // floats
+    static constexpr int PAD_BYTES = NF1 % NW != 0 ? NW * 1024 : 0;
+    static_assert(NSLOT >= 3 && (NSLOT - 1) * LPS <= 63, "vmcnt holds six bits");
     static constexpr size_t LDS_BYTES = (size_t)NSLOT * STAGE * 4 + PAD_BYTES;
-#ifndef DS_RING_CLOCK
-#define DS_RING_CLOCK 0       // 1: s_memtime around the piped loop's wait / barrier / requests / rest, printed by two workgroups of the dense kernel
-#endif
-#if DS_RING_CLOCK
-    mutable unsigned long long clk[5] = {0, 0, 0, 0, 0};
-#endif
-    const char* src[LPS];
-    mutable const char* rs[LPS];          // piped loop: request sources of stage 0, moved to the second A segment when the stages reach it
+    mutable const char* rs[LPS];          // request sources of stage 0, moved to the second A segment when the stages reach it
     mutable bool in_seg1 = false;
-    int kgi_[LPS];
     bool is_a[LPS];
     long dseg;
     int s0;
@@ -860,31 +744,21 @@ struct SplitRing {
         dseg = (a1 - a0) - (long)s0_ * SPLIT_KSTEP_BYTES;
 #pragma unroll
         for (int j = 0; j < LPS; ++j) {
-            const int q = min(wave_ + NW * j, NF - 1), kgi = q / NF1, f = q - kgi * NF1;       // (q >= NF: never requested)
-            kgi_[j] = kgi;
+            // fragment wave_ + NW j of the stage (past the last one: this wave's filler request repeats it). k0, the k-step inside the stage, is
+            // 0; written as a quotient hipcc folds it late and keeps the shipped scalar address arithmetic (as a literal it reassociates
+            // the panel offset into a 64-bit multiply chain)
+            const int q = min(wave_ + NW * j, NF1 - 1), k0 = q / NF1, f = q - k0 * NF1;
             is_a[j] = f < 3 * FRA;
             if (f < 3 * FRA) {
                 const int m = min(mt0 + f / 3, mtiles - 1);
-                src[j] = a0 + (size_t)m * a_mt + (size_t)kgi * SPLIT_KSTEP_BYTES + (f % 3) * 1024;
+                rs[j] = a0 + (size_t)m * a_mt + (f % 3) * 1024;
             } else {
                 const int g = f - 3 * FRA;
-                src[j] = B + ((size_t)(nt0 + g / 3) * kg_stride + kgi) * SPLIT_KSTEP_BYTES + (g % 3) * 1024;
+                rs[j] = B + ((size_t)(nt0 + g / 3) * kg_stride + k0) * SPLIT_KSTEP_BYTES + (g % 3) * 1024;
             }
-            rs[j] = src[j];
         }
     }
-    __device__ __forceinline__ void request(int st, int slot) const
-    {
-        const unsigned dst = __builtin_amdgcn_readfirstlane(ring_lds + (slot * STAGE + wave * 256) * 4);
-#pragma unroll
-        for (int j = 0; j < LPS; ++j) {
-            if (NF % NW != 0 && j == LPS - 1 && wave >= NF % NW) break;      // wave-uniform: this wave has no fragment 4 j + wave
-            const int ks = st * KGS + kgi_[j];
-            const long off = (long)st * (KGS * SPLIT_KSTEP_BYTES) + ((is_a[j] && ks >= s0) ? dseg : 0);
-            glds16s(src[j] + off, lane16, dst + j * (NW * 1024));      // fragment q = wave + 4 j of the stage
-        }
-    }
-    // ---- piped loop, requests: the source of request J is (wave-uniform base rs[J]) + (lane offset + stage offset, ONE vector add per
+    // ---- requests: the source of request J is (wave-uniform base rs[J]) + (lane offset + stage offset, ONE vector add per
     // stage): no scalar address arithmetic per request; no branch either -- past the last stage the requests repeat it into the slot
     // that has just been freed, and a wave without a fragment 4 J + wave refetches its last one into a pad
     __device__ __forceinline__ unsigned stage_voff(int sreq) const
@@ -901,7 +775,7 @@ struct SplitRing {
     __device__ __forceinline__ void request3(unsigned voff, unsigned rdst) const
     {
         unsigned dst = rdst + J * (NW * 1024);
-        if (NF % NW != 0 && J == LPS - 1 && wave >= NF % NW) dst = ring_lds + NSLOT * STAGE * 4 + wave * 1024;
+        if (NF1 % NW != 0 && J == LPS - 1 && wave >= NF1 % NW) dst = ring_lds + NSLOT * STAGE * 4 + wave * 1024;
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(rs[J]), "s"(dst) : "memory");      // (m0: saved and restored around the run of requests by the caller; hipcc rejects m0 as a clobber -- "reserved register" -- so tests/test_kernel_resources.py holds what the save/restore relies on: no SGPR spill, hence no compiler use of m0, in these kernels)
     }
     template <int J>
@@ -911,9 +785,7 @@ struct SplitRing {
     }
     __device__ __forceinline__ void prologue(int nstages) const
     {
-#if DS_SPLIT_PIPED
-        static_assert(KGS == 1 && (NSLOT - 1) * LPS <= 63, "one k-step per stage; vmcnt holds six bits");
-        if (nstages <= 0 || DS_RING_BISECT == 4) return;
+        if (nstages <= 0) return;
         unsigned keep_m0;
         asm volatile("s_mov_b32 %0, m0" : "=s"(keep_m0));
 #pragma unroll
@@ -922,79 +794,17 @@ struct SplitRing {
             request3_all<0>(voff, __builtin_amdgcn_readfirstlane(ring_lds + (s * STAGE + wave * 256) * 4));
         }
         asm volatile("s_mov_b32 m0, %0" ::"s"(keep_m0));
-        return;
-#endif
-#pragma unroll
-        for (int s = 0; s < NSLOT - 1; ++s)
-            if (DS_RING_BISECT != 2 && DS_RING_BISECT != 4 && s < nstages) request(s, s);
-    }
-    // wait until all but the last K stages requested have landed (this wave's share; waves >= NF % NW request one fragment fewer)
-    template <int K>
-    __device__ __forceinline__ void wait_but(int later) const
-    {
-        if (later >= K) {
-            if (NF % NW == 0 || wave < NF % NW) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K * LPS) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K * (LPS - 1)) : "memory");
-        } else if constexpr (K > 0) wait_but<K - 1>(later);
-    }
-    // stage st has landed once every wave's requests for it are done: counted wait (stages st + 1 .. st + NSLOT - 2 stay in flight),
-    // barrier -- which also frees ring slot (st - 1) % NSLOT, read during stage st - 1 --, request stage st + NSLOT - 1 into it, then
-    // this stage's MFMAs
-    template <int SLOT>
-    __device__ __forceinline__ void stage(int st, int nstages, const float* fa0, const float* fb0, floatx16 (&acc)[MTW][NTW]) const
-    {
-        wait_but<NSLOT - 2>(nstages - 1 - st);
-        if (DS_RING_BISECT != 3) __builtin_amdgcn_s_barrier();
-        if (DS_RING_BISECT != 2 && st + NSLOT - 1 < nstages) request(st + NSLOT - 1, (SLOT + NSLOT - 1) % NSLOT);
-#pragma unroll
-        for (int kgi = 0; kgi < KGS; ++kgi) {
-            float4 a[MTW][3], b[NTW][3];
-#pragma unroll
-            for (int i = 0; i < MTW; ++i)
-#pragma unroll
-                for (int p = 0; p < 3; ++p) a[i][p] = *reinterpret_cast<const float4*>(fa0 + SLOT * STAGE + (kgi * NF1 + i * 3 + p) * 256);
-#pragma unroll
-            for (int j = 0; j < NTW; ++j)
-#pragma unroll
-                for (int p = 0; p < 3; ++p) b[j][p] = *reinterpret_cast<const float4*>(fb0 + SLOT * STAGE + (kgi * NF1 + j * 3 + p) * 256);
-#pragma unroll
-            for (int i = 0; i < MTW; ++i)
-#pragma unroll
-                for (int j = 0; j < NTW; ++j) {
-                    if (DS_RING_BISECT == 1) { acc[i][j][0] += b[j][0].x + b[j][1].y + b[j][2].z + a[i][0].x + a[i][1].y + a[i][2].z; continue; }
-                    acc[i][j] = mfma3_lo(b[j], a[i][0], a[i][1], a[i][2], acc[i][j]);      // transposed: (A B)^T
-                    acc[i][j] = mfma3_hi(b[j], a[i][0], a[i][1], acc[i][j]);
-                }
-#if DS_RING_SCHED == 1
-            // hipcc's own schedule reads a fragment, waits for it and issues its MFMA, one after the other, in 20 registers: every LDS
-            // latency is exposed (one wave per SIMD). All of a k-step's reads first, then its MFMAs behind counted waits.
-            __builtin_amdgcn_sched_group_barrier(0x100, 3 * (MTW + NTW), 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 6 * MTW * NTW, 0);
-#endif
-        }
-    }
-    template <int SLOT>
-    __device__ __forceinline__ void run_from(int& st, int nstages, const float* fa0, const float* fb0, floatx16 (&acc)[MTW][NTW]) const
-    {
-        stage<SLOT>(st, nstages, fa0, fb0, acc);
-        if (++st >= nstages) return;
-        if constexpr (SLOT + 1 < NSLOT) run_from<SLOT + 1>(st, nstages, fa0, fb0, acc);
-    }
-    __device__ __forceinline__ void run_simple(int nstages, const float* fa0, const float* fb0, floatx16 (&acc)[MTW][NTW]) const
-    {
-        if (DS_RING_BISECT == 4) return;
-        for (int st = 0; st < nstages;) run_from<0>(st, nstages, fa0, fb0, acc);
     }
 
-    // The same ring with a stage's fragments DOUBLE-BUFFERED IN REGISTERS. With one wave per SIMD (one workgroup per CU: the 128 x 96 dense
-    // tile, the 128 x 128 cell tile) nothing else issues while a wave waits, so run_simple pays per k-step, one after the other: the
-    // barrier, the requests, the LDS latency of the first fragments, then the MFMAs (dense(6032, 6032), 512 sites: 1,080 cycles per
-    // k-step WITHOUT any operand traffic, for 576 of MFMA). Here iteration st holds stage st in registers; it waits until stage st + 1
-    // has landed, passes the barrier (everybody's share of st + 1 has landed, everybody has READ stage st: its slot is free), requests
-    // stage st + NSLOT into that slot and then issues the LDS reads of stage st + 1 BETWEEN the MFMAs of stage st -- the interleave is
-    // pinned instruction by instruction (sched_barrier), hipcc's own schedule serialises read -> wait -> MFMA. NSLOT stages are requested ahead.
-    // The MFMAs of one accumulator keep their order: bit-identical to run_simple.
-    static_assert(!DS_SPLIT_PIPED || KGS == 1, "the piped loop takes one k-step per stage");
+    // The K loop holds a stage's fragments DOUBLE-BUFFERED IN REGISTERS. With one wave per SIMD (one workgroup per CU: the 128 x 96 dense
+    // tile, the 128 x 128 cell tile) nothing else issues while a wave waits, so a loop that takes one stage at a time pays per k-step, one
+    // after the other: the barrier, the requests, the LDS latency of the first fragments, then the MFMAs (dense(6032, 6032), 512 sites:
+    // 1,080 cycles per k-step WITHOUT any operand traffic, for 576 of MFMA). Here iteration st holds stage st in registers; it waits until
+    // stage st + 1 has landed, passes the barrier (everybody's share of st + 1 has landed, everybody has READ stage st: its slot is free),
+    // requests stage st + NSLOT into that slot and then issues the LDS reads of stage st + 1 BETWEEN the MFMAs of stage st -- the interleave
+    // is pinned instruction by instruction (sched_barrier); hipcc's own schedule reads a fragment, waits for it and issues its MFMA, one
+    // after the other, in 20 registers: every LDS latency is exposed. NSLOT stages are requested ahead.
+    // The MFMAs of one accumulator are issued in mfma3_lo / mfma3_hi order: bit-identical to a plain loop over the k-steps.
     typedef float4 Frag[MTW + NTW][3];
     __device__ __forceinline__ void read_frags(const float* fa0, const float* fb0, int slot, Frag& f) const
     {
@@ -1065,18 +875,8 @@ struct SplitRing {
     // one iteration: registers `cur` hold stage st (slot = its ring slot), `nxt` take stage st + 1
     __device__ __forceinline__ void piped(int st, int slot, int nstages, const float* fa0, const float* fb0, const Frag& cur, Frag& nxt, floatx16 (&acc)[MTW][NTW]) const
     {
-#if DS_RING_CLOCK
-        const unsigned long long c0 = __builtin_amdgcn_s_memtime();
-        if (clk[4]) clk[3] += c0 - clk[4];
-#endif
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((NSLOT - 2) * LPS) : "memory");
-#if DS_RING_CLOCK
-        const unsigned long long c1 = __builtin_amdgcn_s_memtime();
-#endif
         __builtin_amdgcn_s_barrier();
-#if DS_RING_CLOCK
-        const unsigned long long c2 = __builtin_amdgcn_s_memtime();
-#endif
         // the order is pinned instruction by instruction: MFMA m (round robin over the accumulators, the six products of one accumulator
         // in mfma3_lo / mfma3_hi order), behind it LDS read m of the next stage, and every NM / LPS MFMAs one LDS-DMA request. In one
         // burst behind the barrier the four waves' 21 requests held every wave for 350 cycles per k-step in front of its MFMAs
@@ -1086,10 +886,6 @@ struct SplitRing {
         const int nslot = slot + 1 == NSLOT ? 0 : slot + 1;
         const float* fa = fa0 + nslot * STAGE;
         const float* fb = fb0 + nslot * STAGE;
-#if DS_RING_CLOCK
-        const unsigned long long c3 = __builtin_amdgcn_s_memtime();
-        clk[0] += c1 - c0; clk[1] += c2 - c1; clk[2] += c3 - c2; clk[4] = c3;
-#endif
         unsigned keep_m0;
         asm volatile("s_mov_b32 %0, m0" : "=s"(keep_m0));
         __builtin_amdgcn_sched_barrier(0);
@@ -1097,7 +893,7 @@ struct SplitRing {
         asm volatile("s_mov_b32 m0, %0" ::"s"(keep_m0));
         __builtin_amdgcn_sched_barrier(0);      // (the next iteration's lgkmcnt(0) stays behind this iteration's last MFMAs)
     }
-    __device__ __forceinline__ void run_piped(int nstages, const float* fa0, const float* fb0, floatx16 (&acc)[MTW][NTW]) const
+    __device__ __forceinline__ void run(int nstages, const float* fa0, const float* fb0, floatx16 (&acc)[MTW][NTW]) const
     {
         if (nstages <= 0) return;
         // (prologue() has requested stages 0 .. NSLOT - 1)
@@ -1116,15 +912,6 @@ struct SplitRing {
         }
         if (nstages & 1) piped(st, slot, nstages, fa0, fb0, f0, f1, acc);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // (the filler requests and reads of the last iterations)
-    }
-    __device__ __forceinline__ void run(int nstages, const float* fa0, const float* fb0, floatx16 (&acc)[MTW][NTW]) const
-    {
-#if DS_SPLIT_PIPED
-        if (DS_RING_BISECT == 4) return;
-        run_piped(nstages, fa0, fb0, acc);
-#else
-        run_simple(nstages, fa0, fb0, acc);
-#endif
     }
 };
 
@@ -1152,14 +939,10 @@ __global__ __launch_bounds__(64 * WM * WN, (SplitRing<MTW, NTW, WM, WN, DS_SPLIT
     const unsigned lane4 = (unsigned)lane * 4;
     const bool has_x = C.ax != nullptr, has_h = C.ah != nullptr;
     const int KS = (has_x ? 16 : 0) + (has_h ? 16 : 0);       // k-steps: x rows first, then h rows (TF kernel order)
-    const int nstages = KS / R::KGS;
-#if DS_RING_CLOCK
-    const unsigned long long k0 = __builtin_amdgcn_s_memtime();
-#endif
     R rg;
     rg.init(ring, wave, lane, reinterpret_cast<const char*>(has_x ? C.ax : C.ah), reinterpret_cast<const char*>(has_h ? C.ah : C.ax),
             has_x ? 16 : 0, SPLIT_MT_BYTES, mb * R::FRA, mtiles, reinterpret_cast<const char*>(C.Bp), C.kg_stride, ng * R::FRB);
-    rg.prologue(nstages);
+    rg.prologue(KS);
 
     int mt[MTW];
     bool valid[MTW];
@@ -1207,13 +990,7 @@ __global__ __launch_bounds__(64 * WM * WN, (SplitRing<MTW, NTW, WM, WN, DS_SPLIT
             asm volatile("" : "+v"(cp[i][j].x), "+v"(cp[i][j].y), "+v"(cp[i][j].z), "+v"(cp[i][j].w));
             asm volatile("" : "+v"(acc[i][j]));
         }
-#if DS_RING_CLOCK
-    const unsigned long long k1 = __builtin_amdgcn_s_memtime();
-#endif
-    rg.run(nstages, ring + (mi * MTW * 3) * 256 + lane4, ring + (3 * R::FRA + nj * NTW * 3) * 256 + lane4, acc);
-#if DS_RING_CLOCK
-    const unsigned long long k2 = __builtin_amdgcn_s_memtime();
-#endif
+    rg.run(KS, ring + (mi * MTW * 3) * 256 + lane4, ring + (3 * R::FRA + nj * NTW * 3) * 256 + lane4, acc);
 
     // ---- gates (fp32), new state; c fragment-major fp32, h fragment-major in three terms (8 bytes per lane and term), optional
     // row-major fp32 h for the joint model
@@ -1242,14 +1019,6 @@ __global__ __launch_bounds__(64 * WM * WN, (SplitRing<MTW, NTW, WM, WN, DS_SPLIT
             }
         }
     }
-#if DS_RING_CLOCK
-    const unsigned long long k3 = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long k4 = __builtin_amdgcn_s_memtime();
-    if ((blockIdx.x == 0 || blockIdx.x == gridDim.x - 1 || blockIdx.x == 77) && threadIdx.x == 0 && C.t == 8)
-        printf("CELL block %d of %d cell %d ksteps %d: cycles init %d loop %d gates+stores issued %d stores done %d\n", (int)blockIdx.x, (int)gridDim.x, ci, KS,
-               (int)(k1 - k0), (int)(k2 - k1), (int)(k3 - k2), (int)(k4 - k3));
-#endif
 }
 
 // ---- layer 0's accumulator-initial values for every step of both directions, and the first step's cells (ds_internal.h LstmXproj).
@@ -1309,7 +1078,7 @@ hipError_t launch_lstm_cells_split(LstmTile tile, const LstmLaunch& L, hipStream
     case LT_S22: hipLaunchKernelGGL((lstm_cell_split_kernel<2, 2>), grid, dim3(256), (SplitRing<2, 2, 2, 2, DS_SPLIT_LSTM_SLOTS>::LDS_BYTES), s, L); break;
     // the same 128 x 128 workgroup tile by EIGHT waves (4 x 2, each 32 x 64): two waves per SIMD of the one workgroup a CU holds
     case LT_S28: hipLaunchKernelGGL((lstm_cell_split_kernel<1, 2, 4, 2>), grid, dim3(512), (SplitRing<1, 2, 4, 2, DS_SPLIT_LSTM_SLOTS>::LDS_BYTES), s, L); break;
-    case LT_F1: case LT_F2: case LT_F4: case LT_LDS1: case LT_LDS2: case LT_B11: case LT_B12: case LT_B22: case LT_COUNT:
+    case LT_F1: case LT_F4: case LT_LDS1: case LT_LDS2: case LT_B11: case LT_B12: case LT_B22: case LT_COUNT:
         return hipErrorInvalidValue;      // launch_lstm_cells' (ds_kernels.hip)
     }
     return hipGetLastError();
@@ -1379,7 +1148,7 @@ __global__ __launch_bounds__(256, (DenseRing<MTW, NTW, WM, WN>::R::LDS_BYTES > 8
     const int k0 = (int)((long)ks * d.ksteps / d.splits), k1 = (int)((long)(ks + 1) * d.ksteps / d.splits);
     const int half = lane >> 5, r31 = lane & 31;
     const unsigned lane4 = (unsigned)lane * 4;
-    const int nstages = (k1 - k0) / R::KGS;         // (ksteps is even wherever KGS = 2 is instantiated: checked by the launcher)
+    const int nstages = k1 - k0;
     R rg;
     rg.init(ring, wave, lane, d.A + (size_t)k0 * SPLIT_KSTEP_BYTES, d.A + (size_t)k0 * SPLIT_KSTEP_BYTES, nstages, (long)d.ksteps * SPLIT_KSTEP_BYTES, mb * R::FRA,
             d.mtiles, d.Bp + (size_t)k0 * SPLIT_KSTEP_BYTES, d.kg_stride, min(nb * R::FRB, d.ntiles_alloc - R::FRB));
@@ -1393,11 +1162,6 @@ __global__ __launch_bounds__(256, (DenseRing<MTW, NTW, WM, WN>::R::LDS_BYTES > 8
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
     rg.run(nstages, ring + (mi * MTW * 3) * 256 + lane4, ring + (3 * R::FRA + nj * NTW * 3) * 256 + lane4, acc);
-#if DS_RING_CLOCK
-    if ((blockIdx.x == 0 || blockIdx.x == 101) && lane == 0 && (wave == 0 || wave == 3))
-        printf("RING block %d wave %d: per k-step (100 MHz ticks x 1000) wait %d barrier %d request %d rest %d\n", (int)blockIdx.x, wave,
-               (int)(rg.clk[0] * 1000 / nstages), (int)(rg.clk[1] * 1000 / nstages), (int)(rg.clk[2] * 1000 / nstages), (int)(rg.clk[3] * 1000 / nstages));
-#endif
     const int nt_base = min(nb * R::FRB, d.ntiles_alloc - R::FRB);
 #pragma unroll
     for (int i = 0; i < MTW; ++i) {
