@@ -635,58 +635,13 @@ def _fast5_task(task):
     return _read_features_from_fast5s(*task)
 
 
-def _device_read_record(raw, starts, lengths, bases, scaling, offset, info, motif_seqs, methyloc, chrom2len, kmer_len,
-                        positions=None):
-    """One read's arrays (as _read_fast5 returns them) -> ("gpu", read tuple of ReadBatch, site locs, sampleinfo rows, k-mer
-    codes) for the device extractor; () when the read has no site; None when the device route cannot take the read (a
-    signal that is not int16, bases outside ACGTN, events outside the signal, a non-float64 offset)."""
-    import zlib
-    from . import extract_features as ef
-    from .engine import base_codes
-    readname, strand, alignstrand, chrom, chrom_start = info
-    chromlen = chrom2len.get(chrom) if chrom2len is not None else None
-    if chrom2len is not None and chromlen is None:
-        print("warning - chrom_name in fast5 not in provided reference genome!")
-    raw = np.asarray(raw)
-    codes = base_codes(bases)
-    starts, lengths = np.asarray(starts, np.int64), np.asarray(lengths, np.int64)
-    if raw.dtype != np.int16 or (codes < 0).any() or (starts < 0).any() or (lengths < 1).any() or \
-            (starts + lengths > len(raw)).any() or np.asarray(offset).dtype != np.float64:
-        return None
-    sites = ef.read_sites(bases, motif_seqs, methyloc, kmer_len, alignstrand, chrom, chrom_start, chromlen, positions)
-    if not sites:
-        return ()
-    nb = (kmer_len - 1) // 2
-    locs = np.array([loc for loc, _, _ in sites], np.int32)
-    text = "".join("\t".join([chrom, str(pos), alignstrand, str(pis), readname, strand]) + "\n" for _, pos, pis in sites)
-    kmers = codes[locs[:, None] + np.arange(-nb, nb + 1)].astype(np.int32)
-    return ("gpu", (raw, starts, lengths, codes, float(scaling), float(offset), zlib.crc32(readname.encode())), locs,
-            text.encode(), kmers)
-
-
 def _fast5_reads_task(task):
     """Worker of the fast5 route with extract_on="gpu": one batch of files -> per read, either ("gpu", read arrays, sites) for
     the device extractor or ("cpu", queue item) -- the host route for a read the device route cannot take (a signal that is
-    not int16, bases outside ACGTN, events outside the signal) -- and the number of failed files."""
+    not int16, bases outside ACGTN, events outside the signal) -- and the number of failed files
+    (extract_features._device_read_records, shared with `extract --extract_on gpu`)."""
     from . import extract_features as ef
-    (fast5s, corrected_group, basecall_subgroup, normalize_method, motif_seqs, methyloc, chrom2len, kmer_len,
-     raw_signals_len, methy_label, positions) = task
-    out, error = [], 0
-    for fp in fast5s:
-        try:
-            raw, starts, lengths, bases, scaling, offset, info = ef._read_fast5(fp, corrected_group, basecall_subgroup)
-        except Exception:
-            out.append(("cpu", _read_features_from_fast5s([fp], *task[1:])))   # counts and reports the failure as the host route
-            continue
-        rec = _device_read_record(raw, starts, lengths, bases, scaling, offset, info, motif_seqs, methyloc, chrom2len, kmer_len,
-                                  positions)
-        if rec is None:
-            print("note: %s: read taken by the host extractor (not an int16 signal with ACGTN bases and events inside it)" % fp,
-                  file=sys.stderr)
-            out.append(("cpu", _read_features_from_fast5s([fp], *task[1:])))
-        elif rec:
-            out.append(rec)
-    return out, error
+    return ef._device_read_records(task, lambda fp: _read_features_from_fast5s([fp], *task[1:]))
 
 
 def _rows_from_device(records, engine, batch_size, normalize_method):

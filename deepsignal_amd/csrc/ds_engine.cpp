@@ -152,6 +152,14 @@ struct Slot {
     size_t pin_reads_cap = 0;
     char* d_reads = nullptr;
     size_t d_reads_cap = 0;
+    // ds_submit_rows / ds_extract_rows: allocated at the slot's first rows call. d_rows = [float64 values | row offsets | row
+    // lengths | text sized for the longest rows max_batch sites can have]; pin_rows grows to the largest text a ticket returned
+    bool rows_ticket = false;             // the ticket in flight is a rows ticket (ds_wait_rows), not a forward (ds_wait)
+    char* d_rows = nullptr;
+    size_t d_rows_cap = 0, d_rows_info = 0;
+    int64_t* pin_rowoff = nullptr;
+    char* pin_rows = nullptr;
+    size_t pin_rows_cap = 0;
 
     std::map<int, Plan> plans;
     int last_n = 0;
@@ -216,6 +224,8 @@ struct ds_handle {
     unsigned long long* dbg_lstm = nullptr;     // [32 diagonals][1024 wgs][8] stamps of the fp32 BiLSTM cell launches
     std::vector<Stage> stages;
     KernelStat kstat[K_COUNT];
+    int64_t rows_batches = 0;             // ds_extract_rows calls timed while profiling is on, and their summed device milliseconds:
+    double rows_ms[5] = {0, 0, 0, 0, 0};  // statistics, values, lengths + scan, format kernels; text device-to-host copy
     // pipelining: consecutive forwards rotate over independent slots (own workspace, streams, graphs), so the
     // dependency chain of one 512-site forward overlaps the next ones'; weights are shared
     std::vector<Slot> slots;
@@ -1367,7 +1377,7 @@ void prepare_slots(ds_handle* h)
 // from a corrupt header, ...): every allocating entry point runs behind this guard and reports a DS_ERR_* code instead.
 namespace {
 template <class F>
-int guarded(ds_handle* h, F&& body)
+auto guarded(ds_handle* h, F&& body) -> decltype(body())      // int, or the int64_t of the entry points that return byte counts
 {
     try {
         return body();
@@ -1502,6 +1512,9 @@ void ds_destroy(ds_handle* h)
         if (sl.pin_in) hipHostFree(sl.pin_in);
         if (sl.pin_reads) hipHostFree(sl.pin_reads);
         if (sl.d_reads) hipFree(sl.d_reads);
+        if (sl.d_rows) hipFree(sl.d_rows);
+        if (sl.pin_rowoff) hipHostFree(sl.pin_rowoff);
+        if (sl.pin_rows) hipHostFree(sl.pin_rows);
         if (sl.pin_act) hipHostFree(sl.pin_act);       // pin_pred points into it
         if (sl.ev_fork) hipEventDestroy(sl.ev_fork);
         if (sl.ev_join) hipEventDestroy(sl.ev_join);
@@ -1655,6 +1668,7 @@ static int ds_forward_impl(ds_handle* h, int32_t n, const int32_t* kmer, const f
                 if (sl.s0) hipStreamSynchronize(sl.s0);
                 if (sl.s1) hipStreamSynchronize(sl.s1);
                 sl.submitted_n = -1;
+                sl.rows_ticket = false;
             }
             h->err = msg;
         }
@@ -1753,7 +1767,7 @@ static int ds_submit_impl(ds_handle* h, int32_t n, const int32_t* kmer, const fl
 static int ds_wait_impl(ds_handle* h, int32_t ticket, float* act, int32_t* pred)
 {
     if (!h || !act || !pred) return DS_ERR_INVALID;
-    if (ticket < 0 || ticket >= (int)h->slots.size() || h->slots[ticket].submitted_n < 0)
+    if (ticket < 0 || ticket >= (int)h->slots.size() || h->slots[ticket].submitted_n < 0 || h->slots[ticket].rows_ticket)
         return fail(h, DS_ERR_INVALID, "ds_wait: no forward in flight for this ticket");
     Slot& sl = h->slots[ticket];
     HIPCHK(h, hipStreamSynchronize(sl.s0));
@@ -1767,24 +1781,26 @@ static int ds_wait_impl(ds_handle* h, int32_t ticket, float* act, int32_t* pred)
 // Scope row f2 on the device: the reads of `r` are validated, packed into the slot's pinned block, copied to its device block
 // and the extraction kernels write the features into the slot's forward inputs (d_kmer .. d_signals), all on sl.s0. Captured
 // forward graphs are untouched: they are launched behind these kernels on the same stream.
-static int stage_reads(ds_handle* h, Slot& sl, const ds_reads* r, dsx::ExtractPlan* p, hipEvent_t* ev)
+// the slot's pinned and device blocks hold the packed reads of *p plus `extra` bytes behind them; the image is staged and copied
+static int stage_reads_block(ds_handle* h, Slot& sl, const ds_reads* r, dsx::ExtractPlan* p, size_t extra)
 {
     std::string err;
     int rc = dsx::plan(r, h->T, h->S, h->B, p, &err);
     if (rc) return fail(h, rc, err);
-    if (p->image_bytes > sl.pin_reads_cap || p->device_bytes > sl.d_reads_cap) {
+    const size_t pin_need = p->image_bytes + extra, dev_need = p->device_bytes + extra;
+    if (pin_need > sl.pin_reads_cap || dev_need > sl.d_reads_cap) {
         HIPCHK(h, hipStreamSynchronize(sl.s0));        // idle slot: nothing may still read the old blocks
-        if (p->image_bytes > sl.pin_reads_cap) {
+        if (pin_need > sl.pin_reads_cap) {
             if (sl.pin_reads) HIPCHK(h, hipHostFree(sl.pin_reads));
             sl.pin_reads = nullptr; sl.pin_reads_cap = 0;
-            const size_t cap = p->image_bytes + p->image_bytes / 4;
+            const size_t cap = pin_need + pin_need / 4;
             HIPCHK(h, hipHostMalloc((void**)&sl.pin_reads, cap, hipHostMallocDefault));
             sl.pin_reads_cap = cap;
         }
-        if (p->device_bytes > sl.d_reads_cap) {
+        if (dev_need > sl.d_reads_cap) {
             if (sl.d_reads) HIPCHK(h, hipFree(sl.d_reads));
             sl.d_reads = nullptr; sl.d_reads_cap = 0;
-            const size_t cap = p->device_bytes + p->device_bytes / 4;
+            const size_t cap = dev_need + dev_need / 4;
             hipError_t e = hipMalloc((void**)&sl.d_reads, cap);
             if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, DS_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
             sl.d_reads_cap = cap;
@@ -1792,6 +1808,13 @@ static int stage_reads(ds_handle* h, Slot& sl, const ds_reads* r, dsx::ExtractPl
     }
     dsx::stage(r, *p, sl.pin_reads);
     HIPCHK(h, hipMemcpyAsync(sl.d_reads, sl.pin_reads, p->image_bytes, hipMemcpyHostToDevice, sl.s0));
+    return DS_OK;
+}
+
+static int stage_reads(ds_handle* h, Slot& sl, const ds_reads* r, dsx::ExtractPlan* p, hipEvent_t* ev)
+{
+    int rc = stage_reads_block(h, sl, r, p, 0);
+    if (rc) return rc;
     const dsx::ExtractArgs a = dsx::device_args(r, *p, sl.d_reads);
     HIPCHK(h, dsx::launch(*p, a, sl.d_reads, sl.d_kmer, sl.d_means, sl.d_stds, sl.d_sanums, sl.d_signals, sl.s0, ev));
     return DS_OK;
@@ -1858,6 +1881,189 @@ static int ds_submit_reads_impl(ds_handle* h, const ds_reads* r, int32_t* ticket
     HIPCHK(h, hipMemcpyAsync(sl.pin_act, sl.act, ((size_t)h->B * h->C + (size_t)n) * 4, hipMemcpyDeviceToHost, sl.s0));
     sl.submitted_n = n;
     *ticket = si;
+    return DS_OK;
+}
+
+// ---- feature rows: float64 values and their text on the device (ds_extract.hip rows_*_kernel) ---------------------------------
+// Needs no weights: the slot's streams and the blocks below are all it uses. The rows path enqueues, on sl.s0: H2D of the packed
+// reads and of info / info_off, the statistics, values, length, scan and format kernels, D2H of the row offsets.
+static int enqueue_rows(ds_handle* h, Slot& sl, const ds_reads* r, const char* info, const int64_t* info_off, int32_t label,
+                        dsx::ExtractPlan* p, hipEvent_t* ev)
+{
+    if (!r || r->nsites < 1) return fail(h, DS_ERR_INVALID, "ds_reads: nsites must be in [1, " + std::to_string(h->B) + "]");
+    std::string err;
+    const int64_t info_bytes = dsx::check_info(info, info_off, r->nsites, &err);
+    if (info_bytes < 0) return fail(h, DS_ERR_INVALID, err);
+    const size_t off_bytes = ((size_t)r->nsites + 1) * 8;
+    const size_t extra = 16 + off_bytes + (size_t)info_bytes;      // behind the reads: [info_off | info], 16-byte aligned
+    int rc = stage_reads_block(h, sl, r, p, extra);
+    if (rc) return rc;
+    const size_t B = h->B, V = 2 * (size_t)h->T + h->S;
+    const size_t o_off = B * V * 8, o_len = o_off + (B + 1) * 8, o_text = (o_len + B * 4 + 15) & ~(size_t)15;
+    const size_t need = o_text + B * (size_t)dsx::row_text_max(h->T, h->S) + (size_t)info_bytes;
+    if (need > sl.d_rows_cap) {
+        HIPCHK(h, hipStreamSynchronize(sl.s0));
+        if (sl.d_rows) HIPCHK(h, hipFree(sl.d_rows));
+        sl.d_rows = nullptr; sl.d_rows_cap = 0;
+        const size_t cap = need + std::max<size_t>((size_t)info_bytes, B * 64);      // room for longer leading columns
+        hipError_t e = hipMalloc((void**)&sl.d_rows, cap);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, DS_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+        sl.d_rows_cap = cap;
+    }
+    if (!sl.pin_rowoff) HIPCHK(h, hipHostMalloc((void**)&sl.pin_rowoff, (B + 1) * 8, hipHostMallocDefault));
+    const size_t pin_at = (p->image_bytes + 15) & ~(size_t)15, dev_at = (p->device_bytes + 15) & ~(size_t)15;
+    memcpy(sl.pin_reads + pin_at, info_off, off_bytes);
+    if (info_bytes) memcpy(sl.pin_reads + pin_at + off_bytes, info, (size_t)info_bytes);
+    HIPCHK(h, hipMemcpyAsync(sl.d_reads + dev_at, sl.pin_reads + pin_at, off_bytes + (size_t)info_bytes, hipMemcpyHostToDevice, sl.s0));
+    const dsx::ExtractArgs a = dsx::device_args(r, *p, sl.d_reads);
+    dsx::RowsArgs ra{};
+    ra.info_off = reinterpret_cast<const int64_t*>(sl.d_reads + dev_at);
+    ra.info = sl.d_reads + dev_at + off_bytes;
+    ra.vals = reinterpret_cast<double*>(sl.d_rows);
+    ra.row_off = reinterpret_cast<int64_t*>(sl.d_rows + o_off);
+    ra.row_len = reinterpret_cast<int32_t*>(sl.d_rows + o_len);
+    ra.text = sl.d_rows + o_text;
+    ra.text_cap = (int64_t)(sl.d_rows_cap - o_text);
+    ra.label = label;
+    HIPCHK(h, dsx::launch_rows(*p, a, ra, sl.d_reads, sl.s0, ev));
+    HIPCHK(h, hipMemcpyAsync(sl.pin_rowoff, ra.row_off, off_bytes, hipMemcpyDeviceToHost, sl.s0));
+    return DS_OK;
+}
+
+// the text of the rows ticket on sl: bytes written, or -(bytes needed) with the ticket kept
+static int64_t collect_rows(ds_handle* h, Slot& sl, char* out, int64_t cap, int64_t* row_off, hipEvent_t* ev)
+{
+    HIPCHK(h, hipStreamSynchronize(sl.s0));
+    const int n = sl.submitted_n;
+    const int64_t total = sl.pin_rowoff[n];
+    if (total > cap) return -total;
+    if ((size_t)total > sl.pin_rows_cap) {
+        if (sl.pin_rows) HIPCHK(h, hipHostFree(sl.pin_rows));
+        sl.pin_rows = nullptr; sl.pin_rows_cap = 0;
+        const size_t want = (size_t)total + (size_t)total / 4;
+        HIPCHK(h, hipHostMalloc((void**)&sl.pin_rows, want, hipHostMallocDefault));
+        sl.pin_rows_cap = want;
+    }
+    const size_t B = h->B, V = 2 * (size_t)h->T + h->S;
+    const size_t o_text = (B * V * 8 + (B + 1) * 8 + B * 4 + 15) & ~(size_t)15;
+    if (ev) HIPCHK(h, hipEventRecord(ev[0], sl.s0));
+    HIPCHK(h, hipMemcpyAsync(sl.pin_rows, sl.d_rows + o_text, (size_t)total, hipMemcpyDeviceToHost, sl.s0));      // only the bytes used
+    if (ev) HIPCHK(h, hipEventRecord(ev[1], sl.s0));
+    HIPCHK(h, hipStreamSynchronize(sl.s0));
+    memcpy(out, sl.pin_rows, (size_t)total);
+    if (row_off) memcpy(row_off, sl.pin_rowoff, ((size_t)n + 1) * 8);
+    sl.submitted_n = -1;
+    sl.rows_ticket = false;
+    return total;
+}
+
+static int ds_submit_rows_impl(ds_handle* h, const ds_reads* r, const char* info, const int64_t* info_off, int32_t label, int32_t* ticket)
+{
+    if (!h || !ticket) return DS_ERR_INVALID;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int si = (int)(h->next_slot % h->slots.size());
+    Slot& sl = h->slots[si];
+    if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_submit_rows: every slot is in flight; wait the oldest ticket first");
+    dsx::ExtractPlan p;
+    int rc = enqueue_rows(h, sl, r, info, info_off, label, &p, nullptr);
+    if (rc) return rc;
+    h->next_slot++;
+    sl.submitted_n = p.nsites;
+    sl.rows_ticket = true;
+    *ticket = si;
+    return DS_OK;
+}
+
+static int64_t ds_wait_rows_impl(ds_handle* h, int32_t ticket, char* out, int64_t cap, int64_t* row_off)
+{
+    if (!h || !out) return DS_ERR_INVALID;
+    if (ticket < 0 || ticket >= (int)h->slots.size() || h->slots[ticket].submitted_n < 0 || !h->slots[ticket].rows_ticket)
+        return fail(h, DS_ERR_INVALID, "ds_wait_rows: no rows in flight for this ticket");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    return collect_rows(h, h->slots[ticket], out, cap, row_off, nullptr);
+}
+
+// Blocking form on an idle slot (not advanced, as ds_extract). With profiling on, the kernels and the text copy are timed.
+static int64_t ds_extract_rows_impl(ds_handle* h, const ds_reads* r, const char* info, const int64_t* info_off, int32_t label,
+                                    char* out, int64_t cap, int64_t* row_off)
+{
+    if (!h || !out) return DS_ERR_INVALID;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    Slot& sl = h->slots[h->next_slot % h->slots.size()];
+    if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_extract_rows: every slot is in flight; wait the oldest ticket first");
+    hipEvent_t ev[7] = {nullptr};
+    const bool timed = h->profiling != 0;
+    if (timed)
+        for (auto& e : ev) HIPCHK(h, hipEventCreate(&e));
+    dsx::ExtractPlan p;
+    int64_t got = enqueue_rows(h, sl, r, info, info_off, label, &p, timed ? ev : nullptr);
+    if (!got) {
+        sl.submitted_n = p.nsites;
+        sl.rows_ticket = true;
+        got = collect_rows(h, sl, out, cap, row_off, timed ? ev + 5 : nullptr);
+        sl.submitted_n = -1;          // a short buffer consumes nothing the caller could come back for: the call is repeated
+        sl.rows_ticket = false;
+        if (got >= 0 && timed) {
+            h->rows_batches += 1;
+            for (int i = 0; i < 4; ++i) { float ms = 0; hipEventElapsedTime(&ms, ev[i], ev[i + 1]); h->rows_ms[i] += ms; }
+            float ms = 0;
+            hipEventElapsedTime(&ms, ev[5], ev[6]);
+            h->rows_ms[4] += ms;
+        }
+    }
+    if (timed)
+        for (auto& e : ev) hipEventDestroy(e);
+    return got;
+}
+
+static int64_t ds_format_values_impl(ds_handle* h, int64_t n, const double* values, char* out, int64_t cap)
+{
+    if (n < 0 || (n > 0 && !values) || !out) return h ? fail(h, DS_ERR_INVALID, "ds_format_values: bad argument") : DS_ERR_INVALID;
+    if (n == 0) return 0;
+    if (!h) {
+        const std::string text = dsx::format_values_host(values, n);
+        if ((int64_t)text.size() > cap) return -(int64_t)text.size();
+        memcpy(out, text.data(), text.size());
+        return (int64_t)text.size();
+    }
+    // a diagnostic: its device buffers live for the call
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    Slot& sl = h->slots[h->next_slot % h->slots.size()];
+    if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_format_values: every slot is in flight");
+    const size_t vbytes = ((size_t)n * 8 + 15) & ~(size_t)15, tbytes = (size_t)n * (dsx::VALUE_TEXT_MAX + 1);
+    char* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, vbytes + 16 + tbytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, DS_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+    int64_t total = 0;
+    e = hipMemcpyAsync(d, values, (size_t)n * 8, hipMemcpyHostToDevice, sl.s0);
+    if (e == hipSuccess) e = dsx::launch_format_values(reinterpret_cast<double*>(d), n, d + vbytes + 16, reinterpret_cast<int64_t*>(d + vbytes), sl.s0);
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, d + vbytes, 8, hipMemcpyDeviceToHost, sl.s0);
+    if (e == hipSuccess) e = hipStreamSynchronize(sl.s0);
+    if (e == hipSuccess && total <= cap) e = hipMemcpy(out, d + vbytes + 16, (size_t)total, hipMemcpyDeviceToHost);
+    hipFree(d);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, DS_ERR_HIP, std::string("ds_format_values: ") + hipGetErrorString(e)); }
+    return total <= cap ? total : -total;
+}
+
+int64_t ds_extract_rows_reference(const ds_reads* r, int32_t kmer_len, int32_t signal_len, const char* info, const int64_t* info_off,
+                                  int32_t label, char* out, int64_t cap, int64_t* row_off)
+{
+    std::string err, text;
+    std::vector<int64_t> off;
+    int rc = out ? dsx::rows_reference(r, kmer_len, signal_len, info, info_off, label, &text, &off, &err) : DS_ERR_INVALID;
+    if (rc) { fail(nullptr, rc, err.empty() ? "ds_extract_rows_reference: null output" : err); return rc; }
+    if ((int64_t)text.size() > cap) return -(int64_t)text.size();
+    memcpy(out, text.data(), text.size());
+    if (row_off) memcpy(row_off, off.data(), off.size() * 8);
+    return (int64_t)text.size();
+}
+
+int ds_get_rows_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms)
+{
+    if (!h || !batches || !ms) return DS_ERR_INVALID;
+    *batches = h->rows_batches;
+    for (int i = 0; i < 5; ++i) ms[i] = h->rows_ms[i];
+    if (reset) { h->rows_batches = 0; for (double& v : h->rows_ms) v = 0; }
     return DS_OK;
 }
 
@@ -2162,4 +2368,8 @@ int ds_submit_parts(ds_handle* h, int32_t nparts, const int32_t* counts, const i
 int ds_wait(ds_handle* h, int32_t ticket, float* act, int32_t* pred) { return guarded(h, [&] { return ds_wait_impl(h, ticket, act, pred); }); }
 int ds_extract(ds_handle* h, const ds_reads* reads, int32_t* kmer, float* means, float* stds, float* sanums, float* signals) { return guarded(h, [&] { return ds_extract_impl(h, reads, kmer, means, stds, sanums, signals); }); }
 int ds_submit_reads(ds_handle* h, const ds_reads* reads, int32_t* ticket) { return guarded(h, [&] { return ds_submit_reads_impl(h, reads, ticket); }); }
+int ds_submit_rows(ds_handle* h, const ds_reads* reads, const char* info, const int64_t* info_off, int32_t label, int32_t* ticket) { return guarded(h, [&] { return ds_submit_rows_impl(h, reads, info, info_off, label, ticket); }); }
+int64_t ds_wait_rows(ds_handle* h, int32_t ticket, char* out, int64_t cap, int64_t* row_off) { return guarded(h, [&] { return ds_wait_rows_impl(h, ticket, out, cap, row_off); }); }
+int64_t ds_extract_rows(ds_handle* h, const ds_reads* reads, const char* info, const int64_t* info_off, int32_t label, char* out, int64_t cap, int64_t* row_off) { return guarded(h, [&] { return ds_extract_rows_impl(h, reads, info, info_off, label, out, cap, row_off); }); }
+int64_t ds_format_values(ds_handle* h, int64_t n, const double* values, char* out, int64_t cap) { return guarded(h, [&] { return ds_format_values_impl(h, n, values, out, cap); }); }
 }  // extern "C"

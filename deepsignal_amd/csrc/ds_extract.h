@@ -240,6 +240,111 @@ DSX_HD void subsample(uint64_t seed, uint64_t key, int64_t loc, int64_t L, int S
         if ((double)(L - i) * uniform(seed, key, loc, i) < (double)(S - k)) emit(k++, i);
 }
 
+// ---- the text of a feature row (extract_features._features_to_str) ------------------------------------------------------------
+// Every float of a row is np.around(v, 6) == rint(v * 1e6) / 1e6, and str() of such a float64 is a function of the integer
+// K = rint(v * 1e6) and its sign bit alone (for |K| < 1e15; checked against numpy on 600 k values): K == +-0 prints 0.0 / -0.0;
+// 1 <= |K| < 100 prints the exponent form 1e-06, 1.2e-05, 9.9e-05; above, <K div 1e6>.<the six fraction digits without their
+// trailing zeros, at least one kept>. NaN prints nan whatever its sign, +-inf inf / -inf. So a value is integer-to-decimal work.
+// |K| from 2^63 on prints as +-inf: far outside what a normalised sample can be, and it bounds a value's text (VALUE_TEXT_MAX).
+constexpr int VALUE_TEXT_MAX = 27;       // sign, 19 integer digits, point, six fraction digits
+constexpr int INT_TEXT_MAX = 20;         // sign and the 19 digits of an int64
+
+struct ValueText { int kind; bool neg; uint64_t a; };      // kind 0: the number +-a / 1e6, 1: nan, 2: +-inf
+
+DSX_HD ValueText value_text(double v)
+{
+    ValueText t{0, false, 0};
+    if (v != v) { t.kind = 1; return t; }
+    const double k = rint(v * 1e6);
+    t.neg = __builtin_signbit(k) != 0;
+    const double ak = fabs(k);
+    if (!(ak < 9.2e18)) { t.kind = 2; return t; }
+    t.a = (uint64_t)ak;
+    return t;
+}
+
+DSX_HD int dec_digits(uint64_t x) { int n = 1; while (x >= 10) { x /= 10; ++n; } return n; }
+DSX_HD void put_dec(uint64_t x, int nd, char* dst) { for (int i = nd - 1; i >= 0; --i) { dst[i] = (char)('0' + x % 10); x /= 10; } }
+
+DSX_HD int value_len(const ValueText& t)
+{
+    if (t.kind == 1) return 3;
+    if (t.kind == 2) return 3 + (t.neg ? 1 : 0);
+    const int n = t.neg ? 1 : 0;
+    if (t.a == 0) return n + 3;
+    if (t.a < 100) return n + (t.a < 10 || t.a % 10 == 0 ? 5 : 7);
+    uint32_t f = (uint32_t)(t.a % 1000000);
+    int fd = 6;
+    if (f == 0) fd = 1; else while (f % 10 == 0) { f /= 10; --fd; }
+    return n + dec_digits(t.a / 1000000) + 1 + fd;
+}
+
+// writes value_len(t) characters at dst
+DSX_HD void value_put(const ValueText& t, char* dst)
+{
+    if (t.kind == 1) { dst[0] = 'n'; dst[1] = 'a'; dst[2] = 'n'; return; }
+    if (t.neg) *dst++ = '-';
+    if (t.kind == 2) { dst[0] = 'i'; dst[1] = 'n'; dst[2] = 'f'; return; }
+    if (t.a == 0) { dst[0] = '0'; dst[1] = '.'; dst[2] = '0'; return; }
+    if (t.a < 100) {
+        const bool tens = t.a >= 10;
+        const int lead = tens ? (int)(t.a / 10) : (int)t.a, frac = tens ? (int)(t.a % 10) : 0;
+        *dst++ = (char)('0' + lead);
+        if (frac) { *dst++ = '.'; *dst++ = (char)('0' + frac); }
+        dst[0] = 'e'; dst[1] = '-'; dst[2] = '0'; dst[3] = tens ? '5' : '6';
+        return;
+    }
+    const uint64_t ip = t.a / 1000000;
+    uint32_t f = (uint32_t)(t.a % 1000000);
+    const int nd = dec_digits(ip);
+    put_dec(ip, nd, dst);
+    dst += nd;
+    *dst++ = '.';
+    int fd = 6;
+    if (f == 0) fd = 1; else while (f % 10 == 0) { f /= 10; --fd; }
+    put_dec(f, fd, dst);
+}
+
+DSX_HD int int_len(int64_t v) { return (v < 0 ? 1 : 0) + dec_digits(v < 0 ? 0 - (uint64_t)v : (uint64_t)v); }
+DSX_HD void int_put(int64_t v, char* dst)
+{
+    const uint64_t a = v < 0 ? 0 - (uint64_t)v : (uint64_t)v;
+    if (v < 0) *dst++ = '-';
+    put_dec(a, dec_digits(a), dst);
+}
+
+// One element of a row's lists, in row order: e in [0, T) means, [T, 2T) stds, [2T, 3T) lens, [3T, 3T + S) signals, 3T + S the
+// label; each is followed by sep (',' inside a list, '\t' behind it, '\n' behind the label; 0: nothing follows).
+struct RowElem { bool is_int; ValueText v; int64_t i; char sep; };
+
+DSX_HD int row_elems(int T, int S) { return 3 * T + S + 1; }
+
+// vals: the site's float64 values [means T | stds T | signals S]; lens: the k-mer's event lengths
+DSX_HD RowElem row_elem(const double* vals, const int32_t* lens, int T, int S, int64_t label, int e)
+{
+    RowElem el{false, ValueText{0, false, 0}, 0, ','};
+    if (e < 2 * T) el.v = value_text(vals[e]);
+    else if (e < 3 * T) { el.is_int = true; el.i = lens[e - 2 * T]; }
+    else if (e < 3 * T + S) el.v = value_text(vals[e - T]);
+    else { el.is_int = true; el.i = label; el.sep = '\n'; }
+    if (e == T - 1 || e == 2 * T - 1 || e == 3 * T - 1 || e == 3 * T + S - 1) el.sep = '\t';
+    return el;
+}
+
+DSX_HD int elem_len(const RowElem& el) { return (el.is_int ? int_len(el.i) : value_len(el.v)) + (el.sep ? 1 : 0); }
+DSX_HD void elem_put(const RowElem& el, char* dst)
+{
+    const int n = el.is_int ? int_len(el.i) : value_len(el.v);
+    if (el.is_int) int_put(el.i, dst); else value_put(el.v, dst);
+    if (el.sep) dst[n] = el.sep;
+}
+
+// most bytes a row can take beside its leading columns: k-mer letters, lists, label, separators
+DSX_HD int64_t row_text_max(int T, int S)
+{
+    return (int64_t)(VALUE_TEXT_MAX + 1) * (2 * T + S) + (int64_t)(INT_TEXT_MAX + 1) * (T + 1) + T + 2;
+}
+
 }  // namespace dsx
 
 // ---- host <-> device plumbing (ds_extract.hip; used by ds_engine.cpp) -------------------------------------------------
@@ -285,5 +390,28 @@ hipError_t launch(const ExtractPlan& p, const ExtractArgs& a, char* d_block, int
 // ds_extract_reference: the same features on the CPU (rows of pitch T / S)
 int reference(const ds_reads* r, int T, int S, int32_t* kmer, float* means, float* stds, float* sanums, float* signals,
               std::string* err);
+
+// ---- feature rows (ds_submit_rows / ds_extract_rows): device pointers of the rows path of one batch
+struct RowsArgs {
+    const char* info; const int64_t* info_off;   // the rows' six leading columns: row i is info[info_off[i] .. info_off[i + 1])
+    double* vals;                                // [nsites][2T + S]: means | stds | signals in float64
+    int32_t* row_len;                            // [nsites]
+    int64_t* row_off;                            // [nsites + 1]
+    char* text; int64_t text_cap;                // the rows, back to back in site order
+    int64_t label;
+};
+// the validated info / info_off of a rows call: total bytes, or DS_ERR_INVALID
+int64_t check_info(const char* info, const int64_t* info_off, int nsites, std::string* err);
+// on `stream`: clear the histograms, per-read statistics, per-site float64 values, row lengths, their scan, the rows' text.
+// ev (optional, 5 events): recorded around the four kernels
+hipError_t launch_rows(const ExtractPlan& p, const ExtractArgs& a, const RowsArgs& ra, char* d_block, hipStream_t stream,
+                       hipEvent_t* ev);
+// ds_extract_rows_reference: the same rows on the CPU
+int rows_reference(const ds_reads* r, int T, int S, const char* info, const int64_t* info_off, int64_t label, std::string* text,
+                   std::vector<int64_t>* off, std::string* err);
+// ds_format_values: n values comma-joined; the device form needs (VALUE_TEXT_MAX + 1) * n bytes at d_text and writes the
+// byte count to *d_total
+std::string format_values_host(const double* v, int64_t n);
+hipError_t launch_format_values(const double* d_vals, int64_t n, char* d_text, int64_t* d_total, hipStream_t stream);
 
 }  // namespace dsx

@@ -129,9 +129,10 @@ __global__ __launch_bounds__(STATS_THREADS) void extract_stats_kernel(ExtractArg
     }
 }
 
-// the features of site s; lanes [lane, lane + nlanes, ...] of the work (the host checker runs it with one lane)
-__host__ __device__ inline void site_features(const ExtractArgs& a, int s, int lane, int nlanes, int32_t* kmer, float* means,
-                                              float* stds, float* sanums, float* signals)
+// the features of site s in float64; lanes [lane, lane + nlanes, ...] of the work (the host checkers run it with one lane).
+// out.base(j, code, mean, std, len) receives base j of the k-mer, out.signal(q, v) position q of the window.
+template <class Sink>
+__host__ __device__ inline void site_values(const ExtractArgs& a, int s, int lane, int nlanes, const Sink& out)
 {
     const int T = a.T, S = a.S, nb = (T - 1) / 2, mid = (T - 1) / 2;
     const int r = a.site_read[s];
@@ -146,27 +147,43 @@ __host__ __device__ inline void site_features(const ExtractArgs& a, int s, int l
         const int64_t s0 = st[j];
         double m, sd;
         np_mean_std([&](int64_t i) { return nv(s0 + i); }, ln[j], &m, &sd);
-        kmer[(size_t)s * T + j] = a.code[b0 + j];
-        means[(size_t)s * T + j] = (float)m;
-        stds[(size_t)s * T + j] = (float)sd;
-        sanums[(size_t)s * T + j] = (float)ln[j];
+        out.base(j, a.code[b0 + j], m, sd, ln[j]);
     }
     auto lens = [&](int j) -> int64_t { return ln[j]; };
     auto starts = [&](int j) -> int64_t { return st[j]; };
     const Window w = window_plan(lens, T, S);
-    float* out = signals + (size_t)s * S;
     if (w.mode == WIN_SUB) {
         if (lane == 0) {
             const uint64_t key = a.key ? a.key[r] : (uint64_t)r;
             const int64_t s0 = st[mid];
-            subsample(a.seed, key, loc, ln[mid], S, [&](int k, int64_t i) { out[k] = (float)nv(s0 + i); });
+            subsample(a.seed, key, loc, ln[mid], S, [&](int k, int64_t i) { out.signal(k, nv(s0 + i)); });
         }
         return;
     }
     for (int q = lane; q < S; q += nlanes) {
         const int64_t src = window_source(w, lens, starts, T, q);
-        out[q] = src < 0 ? 0.0f : (float)nv(src);
+        out.signal(q, src < 0 ? 0.0 : nv(src));
     }
+}
+
+// the forward's inputs: the values narrowed to float32, rows of pitch T / S
+struct FloatRows {
+    int32_t* kmer; float *means, *stds, *sanums, *signals;
+    int T, S, s;
+    __host__ __device__ void base(int j, int code, double m, double sd, int len) const
+    {
+        kmer[(size_t)s * T + j] = code;
+        means[(size_t)s * T + j] = (float)m;
+        stds[(size_t)s * T + j] = (float)sd;
+        sanums[(size_t)s * T + j] = (float)len;
+    }
+    __host__ __device__ void signal(int q, double v) const { signals[(size_t)s * S + q] = (float)v; }
+};
+
+__host__ __device__ inline void site_features(const ExtractArgs& a, int s, int lane, int nlanes, int32_t* kmer, float* means,
+                                              float* stds, float* sanums, float* signals)
+{
+    site_values(a, s, lane, nlanes, FloatRows{kmer, means, stds, sanums, signals, a.T, a.S, s});
 }
 
 __global__ __launch_bounds__(64 * SITES_PER_WG) void extract_sites_kernel(ExtractArgs a, int32_t* kmer, float* means, float* stds,
@@ -175,6 +192,131 @@ __global__ __launch_bounds__(64 * SITES_PER_WG) void extract_sites_kernel(Extrac
     const int s = blockIdx.x * SITES_PER_WG + threadIdx.x / 64;
     if (s >= a.nsites) return;
     site_features(a, s, threadIdx.x % 64, 64, kmer, means, stds, sanums, signals);
+}
+
+// ---- feature rows: the float64 values of a site, and their text (ds_extract.h: value_text .. elem_put) ------------------------
+// the row's values as the text needs them: [means T | stds T | signals S] in float64 (k-mer codes and lengths are read from the
+// staged reads)
+struct DoubleRow {
+    double* row;
+    int T;
+    __host__ __device__ void base(int j, int, double m, double sd, int) const { row[j] = m; row[T + j] = sd; }
+    __host__ __device__ void signal(int q, double v) const { row[2 * T + q] = v; }
+};
+
+__global__ __launch_bounds__(64 * SITES_PER_WG) void rows_values_kernel(ExtractArgs a, double* vals)
+{
+    const int s = blockIdx.x * SITES_PER_WG + threadIdx.x / 64;
+    if (s >= a.nsites) return;
+    site_values(a, s, threadIdx.x % 64, 64, DoubleRow{vals + (size_t)s * (2 * a.T + a.S), a.T});
+}
+
+__host__ __device__ inline const int32_t* site_lens(const ExtractArgs& a, int s)
+{
+    return a.len + a.base_off[a.site_read[s]] + a.site_loc[s] - (a.T - 1) / 2;
+}
+
+// one wave per site: the row's byte length = leading columns, tab, k-mer letters, tab, every list element with its separator
+__global__ __launch_bounds__(64 * SITES_PER_WG) void rows_len_kernel(ExtractArgs a, RowsArgs ra)
+{
+    const int s = blockIdx.x * SITES_PER_WG + threadIdx.x / 64, lane = threadIdx.x % 64;
+    if (s >= a.nsites) return;
+    const double* vals = ra.vals + (size_t)s * (2 * a.T + a.S);
+    const int32_t* lens = site_lens(a, s);
+    int n = 0;
+    for (int e = lane; e < row_elems(a.T, a.S); e += 64) n += elem_len(row_elem(vals, lens, a.T, a.S, ra.label, e));
+    for (int d = 32; d; d >>= 1) n += __shfl_down(n, d, 64);
+    if (lane == 0) ra.row_len[s] = n + (int)(ra.info_off[s + 1] - ra.info_off[s]) + a.T + 2;
+}
+
+// exclusive scan of the n <= max_batch row lengths into off[0 .. n] by one workgroup: a run of consecutive rows per thread
+constexpr int SCAN_THREADS = 1024;
+__global__ __launch_bounds__(SCAN_THREADS) void rows_scan_kernel(const int32_t* len, int64_t* off, int n)
+{
+    __shared__ int64_t part[SCAN_THREADS];
+    const int tid = threadIdx.x, per = (n + SCAN_THREADS - 1) / SCAN_THREADS;
+    const int b = min(n, tid * per), e = min(n, b + per);
+    int64_t sum = 0;
+    for (int i = b; i < e; ++i) sum += len[i];
+    part[tid] = sum;
+    __syncthreads();
+    for (int d = 1; d < SCAN_THREADS; d <<= 1) {
+        const int64_t t = tid >= d ? part[tid - d] : 0;
+        __syncthreads();
+        part[tid] += t;
+        __syncthreads();
+    }
+    int64_t run = part[tid] - sum;
+    for (int i = b; i < e; ++i) { off[i] = run; run += len[i]; }
+    if (tid == SCAN_THREADS - 1) off[n] = part[tid];
+}
+
+constexpr int CHUNK_TEXT = 64 * (VALUE_TEXT_MAX + 1);      // most bytes 64 elements take (a value is the longest element)
+static_assert(VALUE_TEXT_MAX >= INT_TEXT_MAX, "an LDS chunk is sized by the longest element");
+
+// One wave writes elements elem(0) .. elem(ne - 1) back to back at dst, 64 at a time: every lane takes one element, a wave scan of
+// their lengths places them in the wave's LDS chunk, and the chunk leaves with consecutive lanes storing consecutive bytes.
+// Every wave of the workgroup calls it with the same ne (idle waves with active == false): the chunk is handed over at
+// workgroup barriers. Returns the bytes written.
+template <class ElemFn>
+__device__ inline int64_t wave_format(int lane, int ne, bool active, const ElemFn& elem, char* lds, char* dst)
+{
+    int64_t run = 0;
+    for (int e0 = 0; e0 < ne; e0 += 64) {
+        const int e = e0 + lane;
+        RowElem el{};
+        int len = 0;
+        if (active && e < ne) { el = elem(e); len = elem_len(el); }
+        int inc = len;
+        for (int d = 1; d < 64; d <<= 1) {
+            const int t = __shfl_up(inc, d, 64);
+            if (lane >= d) inc += t;
+        }
+        const int total = __shfl(inc, 63, 64);
+        if (len) elem_put(el, lds + (inc - len));
+        __syncthreads();
+        for (int b = lane; b < total; b += 64) dst[run + b] = lds[b];
+        __syncthreads();
+        run += total;
+    }
+    return run;
+}
+
+__global__ __launch_bounds__(64 * SITES_PER_WG) void rows_format_kernel(ExtractArgs a, RowsArgs ra)
+{
+    __shared__ char chunk[SITES_PER_WG][CHUNK_TEXT];
+    const int w = threadIdx.x / 64, lane = threadIdx.x % 64;
+    const int s = blockIdx.x * SITES_PER_WG + w;
+    // a row that would end past the buffer is not written (the buffer is sized for the longest rows there can be)
+    const bool active = s < a.nsites && ra.row_off[s + 1] <= ra.text_cap;
+    const int sc = active ? s : 0;
+    const int T = a.T, S = a.S;
+    char* dst = ra.text + ra.row_off[sc];
+    const int64_t i0 = ra.info_off[sc], ni = ra.info_off[sc + 1] - i0;
+    if (active) {
+        for (int64_t b = lane; b < ni; b += 64) dst[b] = ra.info[i0 + b];
+        const int8_t* code = a.code + a.base_off[a.site_read[sc]] + a.site_loc[sc] - (T - 1) / 2;
+        for (int j = lane; j < T; j += 64) dst[ni + 1 + j] = "ACGTN"[code[j]];
+        if (lane == 0) { dst[ni] = '\t'; dst[ni + 1 + T] = '\t'; }
+    }
+    const double* vals = ra.vals + (size_t)sc * (2 * T + S);
+    const int32_t* lens = site_lens(a, sc);
+    wave_format(lane, row_elems(T, S), active, [&](int e) { return row_elem(vals, lens, T, S, ra.label, e); }, chunk[w],
+                dst + ni + T + 2);
+}
+
+// ds_format_values on the device: one wave, the values comma-joined
+__global__ __launch_bounds__(64) void format_values_kernel(const double* v, int64_t n, char* text, int64_t* total)
+{
+    __shared__ char chunk[CHUNK_TEXT];
+    const int lane = threadIdx.x;
+    int64_t run = 0;
+    for (int64_t e0 = 0; e0 < n; e0 += 1 << 20) {      // wave_format counts elements in an int
+        const int ne = (int)(n - e0 < (1 << 20) ? n - e0 : 1 << 20);
+        run += wave_format(lane, ne, true, [&](int e) {
+            return RowElem{false, value_text(v[e0 + e]), 0, e0 + e + 1 < n ? ',' : (char)0}; }, chunk, text + run);
+    }
+    if (lane == 0) *total = run;
 }
 
 size_t align_up(size_t v) { return (v + 15) & ~(size_t)15; }
@@ -309,6 +451,36 @@ hipError_t launch(const ExtractPlan& p, const ExtractArgs& a, char* d_block, int
     return hipGetLastError();
 }
 
+namespace {
+
+// the per-read statistics on the CPU and the checker's view of r (host pointers)
+ExtractArgs host_args(const ds_reads* r, const ExtractPlan& p, int T, int S, std::vector<double>* stats)
+{
+    stats->assign((size_t)p.nreads * 2, 0.0);
+    for (int i = 0; i < p.nreads; ++i) {
+        const int16_t* x = r->raw + r->raw_off[i];
+        const int64_t n = r->raw_off[i + 1] - r->raw_off[i];
+        const double sc = r->scaling[i], of = r->offset[i];
+        double* st = stats->data() + 2 * i;
+        if (r->norm == DS_NORM_MAD) {
+            const int span = (int)(p.hist_off[i + 1] - p.hist_off[i]), vmin = p.vmin[i];
+            std::vector<int64_t> cdf(std::max(span, 1), 0);
+            for (int64_t k = 0; k < n; ++k) cdf[x[k] - vmin] += 1;
+            for (int k = 1; k < span; ++k) cdf[k] += cdf[k - 1];
+            mad_stats([&](int k) { return cdf[k]; }, span, vmin, n, sc, of, &st[0], &st[1]);
+        } else {
+            np_mean_std([&](int64_t k) { return rescale(x[k], sc, of); }, n, &st[0], &st[1]);
+        }
+    }
+    ExtractArgs a{};
+    a.raw = r->raw; a.raw_off = r->raw_off; a.start = r->start; a.len = r->length; a.code = r->base; a.base_off = r->base_off;
+    a.scaling = r->scaling; a.offset = r->offset; a.key = r->key; a.site_read = r->site_read; a.site_loc = r->site_loc;
+    a.stats = stats->data(); a.T = T; a.S = S; a.norm = r->norm; a.nsites = r->nsites; a.seed = r->seed;
+    return a;
+}
+
+}  // namespace
+
 // host checker: the same functions on the CPU, one read / site at a time
 int reference(const ds_reads* r, int T, int S, int32_t* kmer, float* means, float* stds, float* sanums, float* signals,
               std::string* err)
@@ -317,27 +489,87 @@ int reference(const ds_reads* r, int T, int S, int32_t* kmer, float* means, floa
     ExtractPlan p;
     int rc = plan(r, T, S, INT32_MAX, &p, err);
     if (rc) return rc;
-    std::vector<double> stats((size_t)p.nreads * 2);
-    for (int i = 0; i < p.nreads; ++i) {
-        const int16_t* x = r->raw + r->raw_off[i];
-        const int64_t n = r->raw_off[i + 1] - r->raw_off[i];
-        const double sc = r->scaling[i], of = r->offset[i];
-        if (r->norm == DS_NORM_MAD) {
-            const int span = (int)(p.hist_off[i + 1] - p.hist_off[i]), vmin = p.vmin[i];
-            std::vector<int64_t> cdf(std::max(span, 1), 0);
-            for (int64_t k = 0; k < n; ++k) cdf[x[k] - vmin] += 1;
-            for (int k = 1; k < span; ++k) cdf[k] += cdf[k - 1];
-            mad_stats([&](int k) { return cdf[k]; }, span, vmin, n, sc, of, &stats[2 * i], &stats[2 * i + 1]);
-        } else {
-            np_mean_std([&](int64_t k) { return rescale(x[k], sc, of); }, n, &stats[2 * i], &stats[2 * i + 1]);
-        }
-    }
-    ExtractArgs a{};
-    a.raw = r->raw; a.raw_off = r->raw_off; a.start = r->start; a.len = r->length; a.code = r->base; a.base_off = r->base_off;
-    a.scaling = r->scaling; a.offset = r->offset; a.key = r->key; a.site_read = r->site_read; a.site_loc = r->site_loc;
-    a.stats = stats.data(); a.T = T; a.S = S; a.norm = r->norm; a.nsites = r->nsites; a.seed = r->seed;
+    std::vector<double> stats;
+    const ExtractArgs a = host_args(r, p, T, S, &stats);
     for (int s = 0; s < r->nsites; ++s) site_features(a, s, 0, 1, kmer, means, stds, sanums, signals);
     return DS_OK;
+}
+
+int64_t check_info(const char* info, const int64_t* info_off, int nsites, std::string* err)
+{
+    if (!info_off || info_off[0] != 0) { *err = "rows: info_off must start at 0"; return DS_ERR_INVALID; }
+    for (int i = 0; i < nsites; ++i)
+        if (info_off[i + 1] < info_off[i]) { *err = "rows: info_off must be non-decreasing"; return DS_ERR_INVALID; }
+    if (info_off[nsites] > 0 && !info) { *err = "rows: null info"; return DS_ERR_INVALID; }
+    return info_off[nsites];
+}
+
+hipError_t launch_rows(const ExtractPlan& p, const ExtractArgs& a, const RowsArgs& ra, char* d_block, hipStream_t stream,
+                       hipEvent_t* ev)
+{
+    hipError_t e = hipSuccess;
+    if (p.hist_off[p.nreads] > 0 && (e = hipMemsetAsync(d_block + p.o_hist, 0, (size_t)p.hist_off[p.nreads] * 4, stream)) != hipSuccess)
+        return e;
+    const dim3 site_grid((p.nsites + SITES_PER_WG - 1) / SITES_PER_WG), site_block(64 * SITES_PER_WG);
+    if (ev && (e = hipEventRecord(ev[0], stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(extract_stats_kernel, dim3(p.nreads), dim3(STATS_THREADS), 0, stream, a);
+    if (ev && (e = hipEventRecord(ev[1], stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(rows_values_kernel, site_grid, site_block, 0, stream, a, ra.vals);
+    if (ev && (e = hipEventRecord(ev[2], stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(rows_len_kernel, site_grid, site_block, 0, stream, a, ra);
+    hipLaunchKernelGGL(rows_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, ra.row_len, ra.row_off, p.nsites);
+    if (ev && (e = hipEventRecord(ev[3], stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(rows_format_kernel, site_grid, site_block, 0, stream, a, ra);
+    if (ev && (e = hipEventRecord(ev[4], stream)) != hipSuccess) return e;
+    return hipGetLastError();
+}
+
+int rows_reference(const ds_reads* r, int T, int S, const char* info, const int64_t* info_off, int64_t label, std::string* text,
+                   std::vector<int64_t>* off, std::string* err)
+{
+    ExtractPlan p;
+    int rc = plan(r, T, S, INT32_MAX, &p, err);
+    if (rc) return rc;
+    if (check_info(info, info_off, p.nsites, err) < 0) return DS_ERR_INVALID;
+    std::vector<double> stats, vals((size_t)2 * T + S);
+    const ExtractArgs a = host_args(r, p, T, S, &stats);
+    text->clear();
+    off->assign(1, 0);
+    char buf[VALUE_TEXT_MAX + 1];
+    for (int s = 0; s < p.nsites; ++s) {
+        site_values(a, s, 0, 1, DoubleRow{vals.data(), T});
+        text->append(info + info_off[s], (size_t)(info_off[s + 1] - info_off[s]));
+        text->push_back('\t');
+        const int8_t* code = a.code + a.base_off[a.site_read[s]] + a.site_loc[s] - (T - 1) / 2;
+        for (int j = 0; j < T; ++j) text->push_back("ACGTN"[code[j]]);
+        text->push_back('\t');
+        const int32_t* lens = site_lens(a, s);
+        for (int e = 0; e < row_elems(T, S); ++e) {
+            const RowElem el = row_elem(vals.data(), lens, T, S, label, e);
+            elem_put(el, buf);
+            text->append(buf, (size_t)elem_len(el));
+        }
+        off->push_back((int64_t)text->size());
+    }
+    return DS_OK;
+}
+
+std::string format_values_host(const double* v, int64_t n)
+{
+    std::string out;
+    char buf[VALUE_TEXT_MAX + 1];
+    for (int64_t i = 0; i < n; ++i) {
+        const RowElem el{false, value_text(v[i]), 0, i + 1 < n ? ',' : (char)0};
+        elem_put(el, buf);
+        out.append(buf, (size_t)elem_len(el));
+    }
+    return out;
+}
+
+hipError_t launch_format_values(const double* d_vals, int64_t n, char* d_text, int64_t* d_total, hipStream_t stream)
+{
+    hipLaunchKernelGGL(format_values_kernel, dim3(1), dim3(64), 0, stream, d_vals, n, d_text, d_total);
+    return hipGetLastError();
 }
 
 }  // namespace dsx

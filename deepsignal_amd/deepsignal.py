@@ -33,14 +33,15 @@ def main_extraction(args):
     extract_features(args.fast5_dir, str2bool(args.recursively), args.reference_path, str2bool(args.is_dna),
                      args.f5_batch_num, args.write_path, args.nproc, args.corrected_group, args.basecall_subgroup,
                      args.normalize_method, args.motifs, args.mod_loc, args.kmer_len, args.cent_signals_len,
-                     args.methy_label, args.positions, str2bool(args.w_is_dir), args.w_batch_num)
+                     args.methy_label, args.positions, str2bool(args.w_is_dir), args.w_batch_num,
+                     extract_on=args.extract_on, device=args.device, engine_batch=args.engine_batch)
 
 
 def build_parser():
     parser = argparse.ArgumentParser(prog="deepsignal", description="call_mods on MI355X (gfx950)")
     sub = parser.add_subparsers(title="modules", dest="module")
     # `extract`: the step before the path -- fast5 -> feature TSV (reference deepsignal/deepsignal.py:155-234, same flags)
-    e = sub.add_parser("extract", description="extract features from fast5 files (host side; HDF5 through h5py, or deepsignal_amd.minihdf5 where h5py is absent)")
+    e = sub.add_parser("extract", description="extract features from fast5 files (on the host, or with --extract_on gpu the numeric part and the row text on the GPU; HDF5 through h5py, or deepsignal_amd.minihdf5 where h5py is absent)")
     g = e.add_argument_group("INPUT")
     g.add_argument("--fast5_dir", "-i", required=True)
     g.add_argument("--recursively", "-r", default="yes")
@@ -62,6 +63,13 @@ def build_parser():
     g.add_argument("--w_batch_num", type=int, default=200)
     e.add_argument("--nproc", "-p", type=int, default=1)
     e.add_argument("--f5_batch_num", type=int, default=50)
+    g = e.add_argument_group("ENGINE")
+    g.add_argument("--extract_on", default="cpu", choices=["cpu", "gpu"],
+                   help="gpu: normalisation, per-site features and the rows' text are computed on the GPU (no model needed); the "
+                        "workers only read the fast5 files. Rows equal the cpu route's, except the signals of a site whose middle "
+                        "base alone has >= cent_signals_len samples (an ordered subsample on both routes)")
+    g.add_argument("--device", type=int, default=0, help="GPU ordinal of --extract_on gpu")
+    g.add_argument("--engine_batch", type=int, default=4096, help="most sites per device pass of --extract_on gpu")
     e.set_defaults(func=main_extraction)
     p = sub.add_parser("call_mods", description="call modifications")
     g = p.add_argument_group("INPUT")

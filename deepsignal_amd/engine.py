@@ -37,6 +37,8 @@ EXPORTED_SYMBOLS = (
     "ds_crc32c",
     # scope row f2 on the device (fast5 feature extraction)
     "ds_extract", "ds_submit_reads", "ds_extract_reference",
+    # feature rows on the device (the text half of `extract`)
+    "ds_submit_rows", "ds_wait_rows", "ds_extract_rows", "ds_extract_rows_reference", "ds_format_values", "ds_get_rows_times",
 )
 
 
@@ -121,6 +123,53 @@ def extract_reference(batch: ReadBatch, kmer_len: int = 17, signal_len: int = 36
     return out
 
 
+def pack_info(info_rows):
+    """The six leading columns of each row (bytes, tab-joined, no newline) -> (uint8 blob, int64 offsets[n + 1]): the info /
+    info_off layout of ds_format_rows and the rows entry points."""
+    off = np.zeros(len(info_rows) + 1, np.int64)
+    off[1:] = np.cumsum([len(r) for r in info_rows])
+    return np.frombuffer(b"".join(info_rows), np.uint8), off
+
+
+def _rows_call(call, nsites: int, buf: Optional[np.ndarray] = None):
+    """Run call(out pointer, capacity, row_off pointer) -> bytes written or -(bytes needed), growing the buffer when asked."""
+    if buf is None:
+        buf = np.empty(max(4096, nsites * 4096), np.uint8)
+    row_off = np.empty(nsites + 1, np.int64)
+    got = int(call(buf.ctypes.data, buf.size, row_off.ctypes.data))
+    if got < -5:                    # -(bytes needed): a row is longer than that; the error codes are -1 .. -5
+        buf = np.empty(-got, np.uint8)
+        got = int(call(buf.ctypes.data, buf.size, row_off.ctypes.data))
+    return got, buf, row_off
+
+
+def extract_rows_reference(batch: ReadBatch, info, info_off, label: int, kmer_len: int = 17, signal_len: int = 360):
+    """ds_extract_rows_reference: the feature rows of `batch` on the CPU -> (bytes, int64 row offsets[nsites + 1]). A checker
+    for the tests, as extract_reference."""
+    lib = load_library()
+    info = np.ascontiguousarray(info, np.uint8)
+    info_off = np.ascontiguousarray(info_off, np.int64)
+    got, buf, row_off = _rows_call(lambda o, c, ro: lib.ds_extract_rows_reference(
+        ctypes.byref(batch.desc), kmer_len, signal_len, info.ctypes.data, info_off.ctypes.data, label, o, c, ro), batch.nsites)
+    if got < 0:
+        raise RuntimeError("ds_extract_rows_reference failed (%d): %s" % (got, lib.ds_last_error(None).decode()))
+    return buf[:got].tobytes(), row_off
+
+
+def format_values(values, engine: Optional["Engine"] = None, cap: Optional[int] = None) -> bytes:
+    """ds_format_values: the comma-joined row text of float64 values, by the host code (engine None) or the device routine.
+    cap: the output capacity to offer (default: enough); a short one raises with the bytes needed in the message."""
+    lib = load_library()
+    v = np.ascontiguousarray(values, np.float64)
+    buf = np.empty(28 * max(1, v.size) if cap is None else cap, np.uint8)
+    h = engine._h if engine is not None else None
+    got = int(lib.ds_format_values(h, v.size, v.ctypes.data, buf.ctypes.data, buf.size))
+    if got < 0:
+        raise RuntimeError("ds_format_values failed (%d)%s" % (got, ": " + lib.ds_last_error(h).decode() if got >= -5 else
+                                                               ": %d bytes needed" % -got))
+    return buf[:got].tobytes()
+
+
 # ds_config.precision (include/deepsignal_hip.h): "bf16" = bf16 conv + FC operands with fp32 accumulation, fp32 BiLSTM;
 # "bf16_all" = also bf16 h / weight operands in the LSTM matmuls (fp32 accumulate, gates, cell state)
 PRECISIONS = {"fp32": 0, "bf16": 1, "bf16_all": 2, "bf16x3": 3}
@@ -199,6 +248,16 @@ def load_library() -> ctypes.CDLL:
     lib.ds_extract.argtypes = [vp, ctypes.POINTER(DsReads), vp, vp, vp, vp, vp]
     lib.ds_submit_reads.argtypes = [vp, ctypes.POINTER(DsReads), ctypes.POINTER(i32)]
     lib.ds_extract_reference.argtypes = [ctypes.POINTER(DsReads), i32, i32, vp, vp, vp, vp, vp]
+    lib.ds_submit_rows.argtypes = [vp, ctypes.POINTER(DsReads), vp, vp, i32, ctypes.POINTER(i32)]
+    lib.ds_wait_rows.argtypes = [vp, i32, vp, i64, vp]
+    lib.ds_wait_rows.restype = i64
+    lib.ds_extract_rows.argtypes = [vp, ctypes.POINTER(DsReads), vp, vp, i32, vp, i64, vp]
+    lib.ds_extract_rows.restype = i64
+    lib.ds_extract_rows_reference.argtypes = [ctypes.POINTER(DsReads), i32, i32, vp, vp, i32, vp, i64, vp]
+    lib.ds_extract_rows_reference.restype = i64
+    lib.ds_format_values.argtypes = [vp, i64, vp, vp, i64]
+    lib.ds_format_values.restype = i64
+    lib.ds_get_rows_times.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_double)]
     lib.ds_get_kernel_stat.argtypes = [vp, i32, ctypes.c_char_p, i32, ctypes.POINTER(i64),
                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
     _lib = lib
@@ -348,6 +407,45 @@ class Engine:
         t = ctypes.c_int32()
         self._check(self._lib.ds_submit_reads(self._h, ctypes.byref(batch.desc), ctypes.byref(t)), "ds_submit_reads")
         return (int(t.value), batch.nsites)
+
+    def submit_rows(self, batch: ReadBatch, info, info_off, label: int) -> Tuple[int, int]:
+        """ds_submit_rows: the feature rows of `batch` (nsites <= max_batch) formatted on the GPU; a ticket for wait_rows().
+        info / info_off: the rows' six leading columns (pack_info). Needs no weights."""
+        info = np.ascontiguousarray(info, np.uint8)
+        info_off = np.ascontiguousarray(info_off, np.int64)
+        if info_off.shape[0] != batch.nsites + 1:
+            raise ValueError("info_off must have nsites + 1 entries")
+        t = ctypes.c_int32()
+        self._check(self._lib.ds_submit_rows(self._h, ctypes.byref(batch.desc), info.ctypes.data, info_off.ctypes.data, label,
+                                             ctypes.byref(t)), "ds_submit_rows")
+        return (int(t.value), batch.nsites)
+
+    def wait_rows(self, ticket: Tuple[int, int]):
+        """ds_wait_rows -> (the rows' bytes, int64 row offsets[nsites + 1])."""
+        slot, n = ticket
+        got, self._rows_buf, row_off = _rows_call(lambda o, c, ro: self._lib.ds_wait_rows(self._h, slot, o, c, ro), n,
+                                                  getattr(self, "_rows_buf", None))
+        self._check(got, "ds_wait_rows")
+        return self._rows_buf[:got].tobytes(), row_off
+
+    def extract_rows(self, batch: ReadBatch, info, info_off, label: int):
+        """ds_extract_rows: the blocking form of submit_rows() + wait_rows()."""
+        info = np.ascontiguousarray(info, np.uint8)
+        info_off = np.ascontiguousarray(info_off, np.int64)
+        if info_off.shape[0] != batch.nsites + 1:
+            raise ValueError("info_off must have nsites + 1 entries")
+        got, self._rows_buf, row_off = _rows_call(lambda o, c, ro: self._lib.ds_extract_rows(
+            self._h, ctypes.byref(batch.desc), info.ctypes.data, info_off.ctypes.data, label, o, c, ro), batch.nsites,
+            getattr(self, "_rows_buf", None))
+        self._check(got, "ds_extract_rows")
+        return self._rows_buf[:got].tobytes(), row_off
+
+    def rows_times(self, reset: bool = False) -> dict:
+        """ds_get_rows_times: device milliseconds of the extract_rows() calls made while profiling was on."""
+        n = ctypes.c_int64()
+        ms = (ctypes.c_double * 5)()
+        self._check(self._lib.ds_get_rows_times(self._h, int(reset), ctypes.byref(n), ms), "ds_get_rows_times")
+        return dict(zip(("stats_ms", "values_ms", "length_ms", "format_ms", "d2h_ms"), ms), batches=int(n.value))
 
     @property
     def slots(self) -> int:

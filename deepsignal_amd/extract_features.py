@@ -1,4 +1,5 @@
-"""fast5 -> per-site features (scope row f2; stays host Python as the north star asks).
+"""fast5 -> per-site features (scope row f2): the host extractor, and the `extract --extract_on gpu` route that leaves the
+numeric part and the row text to the engine (ds_submit_rows).
 
 From-scratch statement of the reference extractor
 (/root/reference/deepsignal/extract_features.py:35-72,121-286,289-303 and
@@ -258,6 +259,119 @@ def _extract_batch(task):
     return [_features_to_str(f) for f in feats], err
 
 
+# ------------------------------------------------------------------ the device route (shared with call_mods --extract_on gpu)
+def _device_read_record(raw, starts, lengths, bases, scaling, offset, info, motif_seqs, methyloc, chrom2len, kmer_len,
+                        positions=None):
+    """One read's arrays (as _read_fast5 returns them) -> ("gpu", read tuple of ReadBatch, site locs, sampleinfo rows, k-mer
+    codes) for the device extractor; () when the read has no site; None when the device route cannot take the read (a
+    signal that is not int16, bases outside ACGTN, events outside the signal, a non-float64 offset)."""
+    import zlib
+    from .engine import base_codes
+    readname, strand, alignstrand, chrom, chrom_start = info
+    chromlen = chrom2len.get(chrom) if chrom2len is not None else None
+    if chrom2len is not None and chromlen is None:
+        print("warning - chrom_name in fast5 not in provided reference genome!")
+    raw = np.asarray(raw)
+    codes = base_codes(bases)
+    starts, lengths = np.asarray(starts, np.int64), np.asarray(lengths, np.int64)
+    if raw.dtype != np.int16 or (codes < 0).any() or (starts < 0).any() or (lengths < 1).any() or \
+            (starts + lengths > len(raw)).any() or np.asarray(offset).dtype != np.float64:
+        return None
+    sites = read_sites(bases, motif_seqs, methyloc, kmer_len, alignstrand, chrom, chrom_start, chromlen, positions)
+    if not sites:
+        return ()
+    nb = (kmer_len - 1) // 2
+    locs = np.array([loc for loc, _, _ in sites], np.int32)
+    text = "".join("\t".join([chrom, str(pos), alignstrand, str(pis), readname, strand]) + "\n" for _, pos, pis in sites)
+    kmers = codes[locs[:, None] + np.arange(-nb, nb + 1)].astype(np.int32)
+    return ("gpu", (raw, starts, lengths, codes, float(scaling), float(offset), zlib.crc32(readname.encode())), locs,
+            text.encode(), kmers)
+
+
+def _device_read_records(task, host_route):
+    """One batch of files -> per read, in file order, either a _device_read_record or ("cpu", host_route(fast5 path)) -- a
+    read the device route cannot take (a note on stderr) or a file that fails to open; and 0 (failures are counted by the host
+    route's payload)."""
+    (fast5s, corrected_group, basecall_subgroup, _, motif_seqs, methyloc, chrom2len, kmer_len, _, _, positions) = task
+    out = []
+    for fp in fast5s:
+        try:
+            raw, starts, lengths, bases, scaling, offset, info = _read_fast5(fp, corrected_group, basecall_subgroup)
+        except Exception:
+            out.append(("cpu", host_route(fp)))      # counts and reports the failure as the host route does
+            continue
+        rec = _device_read_record(raw, starts, lengths, bases, scaling, offset, info, motif_seqs, methyloc, chrom2len, kmer_len,
+                                  positions)
+        if rec is None:
+            print("note: %s: read taken by the host extractor (not an int16 signal with ACGTN bases and events inside it)" % fp,
+                  file=sys.stderr)
+            out.append(("cpu", host_route(fp)))
+        elif rec:
+            out.append(rec)
+    return out, 0
+
+
+def _device_site_batches(records, cap):
+    """Pack the device-route records of one file batch into batches of up to `cap` sites, in order: yields ("gpu", [(record,
+    first site, end site), ...]) -- a read whose sites straddle two batches is carried by both -- and ("cpu", record) for a
+    host-route record, behind the batch that was being filled."""
+    cur, ncur = [], 0
+    for rec in records:
+        if rec[0] == "cpu":
+            if cur:
+                yield "gpu", cur
+                cur, ncur = [], 0
+            yield "cpu", rec
+            continue
+        n, s = len(rec[2]), 0
+        while s < n:
+            take = min(n - s, cap - ncur)
+            cur.append((rec, s, s + take))
+            ncur += take
+            s += take
+            if ncur == cap:
+                yield "gpu", cur
+                cur, ncur = [], 0
+    if cur:
+        yield "gpu", cur
+
+
+def _fast5_rows_task(task):
+    """Worker of `extract --extract_on gpu`: the host-route payload of a read is its finished rows and failure count."""
+    return _device_read_records(task, lambda fp: _extract_batch(((fp,),) + tuple(task[1:])))
+
+
+def _rows_from_device(records, engine, normalize_method, methy_label):
+    """The feature rows of one file batch as chunks of newline-terminated bytes, in the order the host route writes them: the
+    device-route reads go through ds_submit_rows in batches of up to engine.max_batch sites, several in flight."""
+    import collections
+    from .engine import ReadBatch, pack_info
+    out, errors = [], 0
+    inflight = collections.deque()
+    keep = collections.deque(maxlen=2 * max(1, engine.slots))     # descriptors stay alive while their copies may run
+
+    def drain(limit):
+        while len(inflight) > limit:
+            out.append(engine.wait_rows(inflight.popleft())[0])
+
+    for kind, item in _device_site_batches(records, int(engine.max_batch)):
+        if kind == "cpu":
+            drain(0)
+            rows, err = item[1]
+            errors += err
+            out.append("".join(r + "\n" for r in rows).encode())
+            continue
+        drain(engine.slots - 1)
+        sr = np.concatenate([np.full(e - s, i, np.int32) for i, (_, s, e) in enumerate(item)])
+        sl = np.concatenate([rec[2][s:e] for rec, s, e in item])
+        info, info_off = pack_info([line for rec, s, e in item for line in rec[3].split(b"\n")[s:e]])
+        batch = ReadBatch([rec[1] for rec, _, _ in item], sr, sl, norm=normalize_method)
+        inflight.append(engine.submit_rows(batch, info, info_off, methy_label))
+        keep.append(batch)
+    drain(0)
+    return out, errors
+
+
 class _FeatureWriter:
     """One file, or a directory of <n>.tsv files holding w_batch_num batches each (extract_features.py:336-385 role)."""
 
@@ -283,17 +397,31 @@ class _FeatureWriter:
         self.wf.flush()
         self.batch_count += 1
 
+    def write_chunks(self, chunks):
+        """write_batch for rows that arrive as newline-terminated bytes (the device route)"""
+        self.write_batch(())
+        for chunk in chunks:
+            self.wf.write(chunk.decode())
+        self.wf.flush()
+
     def close(self):
         self.wf.close()
 
 
 def extract_features(fast5_dir, is_recursive, reference_path, is_dna, batch_size, write_fp, nproc,
                      corrected_group, basecall_subgroup, normalize_method, motifs, methyloc, kmer_len, raw_signals_len,
-                     methy_label, position_file, w_is_dir, w_batch_num):
+                     methy_label, position_file, w_is_dir, w_batch_num, extract_on="cpu", device=0, engine_batch=4096):
     """`deepsignal extract`: fast5 directory -> feature TSV (same arguments as the reference's
     extract_features.py:424-428). Files are taken in batches of `batch_size`; `nproc` > 1 spreads the batches over a
-    process pool (rows of a batch stay together; batches are written in completion order, as in the reference)."""
+    process pool (rows of a batch stay together; batches are written in completion order, as in the reference).
+    extract_on="gpu": the workers only read the files and list the sites; the numeric part and the row text run on GPU
+    `device` in batches of up to `engine_batch` sites (ds_submit_rows; no model is loaded), nproc - 1 workers beside this
+    process, file batches written in order. Rows are the host route's byte for byte, except the signals of a site whose middle
+    base alone has >= raw_signals_len samples (an ordered subsample either way; the host draws random.sample, the device a
+    hash of the read name and the site)."""
     import time
+    if extract_on not in ("cpu", "gpu"):
+        raise ValueError("extract_on must be 'cpu' or 'gpu'")
     start = time.time()
     fast5s = get_fast5s(fast5_dir, is_recursive)
     print("{} fast5 files in total..".format(len(fast5s)))
@@ -304,8 +432,23 @@ def extract_features(fast5_dir, is_recursive, reference_path, is_dna, batch_size
               chrom2len, kmer_len, raw_signals_len, methy_label, positions) for i in range(0, len(fast5s), batch_size)]
     writer = _FeatureWriter(write_fp, w_is_dir, w_batch_num)
     errors = nrows = 0
+    engine = pool = None
     try:
-        if nproc > 1 and len(tasks) > 1:
+        if extract_on == "gpu":
+            from .engine import Engine
+            engine = Engine(kmer_len=kmer_len, signal_len=raw_signals_len, device=device, max_batch=engine_batch)
+            if nproc > 2 and len(tasks) > 1:
+                import multiprocessing as mp
+                pool = mp.get_context("spawn").Pool(min(nproc - 1, len(tasks)))
+                results = pool.imap(_fast5_rows_task, tasks)
+            else:
+                results = (_fast5_rows_task(t) for t in tasks)
+            for records, err in results:
+                chunks, failed = _rows_from_device(records, engine, normalize_method, methy_label)
+                writer.write_chunks(chunks)
+                errors += err + failed
+                nrows += sum(c.count(b"\n") for c in chunks)
+        elif nproc > 1 and len(tasks) > 1:
             import multiprocessing as mp
             with mp.get_context("spawn").Pool(min(nproc, len(tasks))) as pool:
                 for rows, err in pool.imap_unordered(_extract_batch, tasks):
@@ -319,6 +462,11 @@ def extract_features(fast5_dir, is_recursive, reference_path, is_dna, batch_size
                 errors += err
                 nrows += len(rows)
     finally:
+        if pool is not None:
+            pool.close()
+            pool.join()
+        if engine is not None:
+            engine.close()
         writer.close()
     print("%d of %d fast5 files failed.." % (errors, len(fast5s)))
     print("[extract] finished, cost {:.1f}s ({} feature rows)".format(time.time() - start, nrows))

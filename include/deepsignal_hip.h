@@ -301,6 +301,42 @@ int ds_submit_reads(ds_handle *h, const ds_reads *reads, int32_t *ticket);
 int ds_extract_reference(const ds_reads *reads, int32_t kmer_len, int32_t signal_len, int32_t *kmer, float *means,
                          float *stds, float *sanums, float *signals);
 
+/* ---- feature rows on the device: the second half of `extract` (extract_features._features_to_str, reference
+ * extract_features.py:289-303). The sites of `reads` become the 12-column rows of the feature TSV:
+ *   info[i] \t k-mer letters \t means \t stds \t lens \t signals \t label \n      (lists comma-joined)
+ * info[info_off[i] .. info_off[i + 1]) holds row i's six leading columns (tab-separated, no trailing tab or newline; info_off[0]
+ * == 0), as ds_format_rows takes them. The float64 values of the host extractor are kept on the device (no float32 narrowing)
+ * and printed as str(np.around(v, 6)) prints them (csrc/ds_extract.h value_text). Rows come back packed back to back in site
+ * order: `out` receives the text, row_off (optional) int64[nsites + 1] with row i at out[row_off[i] .. row_off[i + 1]). The same
+ * one difference from the host as ds_extract: the ordered subsample of a middle base of >= signal_len samples.
+ * None of these needs weights: they work on a handle straight from ds_create. 1 <= nsites <= max_batch.
+ *
+ * ds_submit_rows: the asynchronous producer, on the pipeline slots ds_submit / ds_submit_reads rotate over; the descriptor's
+ * arrays, info and info_off are staged before it returns. ds_wait_rows blocks on that ticket and returns the bytes written, or
+ * -(bytes needed) when cap is too small -- nothing is consumed then and the ticket stays valid. Only the bytes used travel
+ * device-to-host. Same ticket rules as ds_submit / ds_wait; a rows ticket is waited with ds_wait_rows only. The slot's row
+ * buffers are allocated at its first rows call. */
+int ds_submit_rows(ds_handle *h, const ds_reads *reads, const char *info, const int64_t *info_off, int32_t label,
+                   int32_t *ticket);
+int64_t ds_wait_rows(ds_handle *h, int32_t ticket, char *out, int64_t cap, int64_t *row_off);
+/* The blocking form of the pair above, on an idle slot (DS_ERR_INVALID while every slot is in flight). Returns the bytes
+ * written or -(bytes needed). With profiling on (ds_set_profiling) the call is timed into ds_get_rows_times. */
+int64_t ds_extract_rows(ds_handle *h, const ds_reads *reads, const char *info, const int64_t *info_off, int32_t label,
+                        char *out, int64_t cap, int64_t *row_off);
+/* The same rows on the CPU from the same code (csrc/ds_extract.h): a CHECKER like ds_extract_reference, no handle, no GPU;
+ * errors leave their message in ds_last_error(NULL). */
+int64_t ds_extract_rows_reference(const ds_reads *reads, int32_t kmer_len, int32_t signal_len, const char *info,
+                                  const int64_t *info_off, int32_t label, char *out, int64_t cap, int64_t *row_off);
+/* Diagnostic: the comma-joined text of n float64 values by the rows' number rule. h == NULL runs the host code, otherwise the
+ * device routine the rows kernels use runs on h's GPU (an idle slot; its buffers live for the call). Read values rarely reach
+ * the exponent form or the specials, so the tests feed directed values here. Returns bytes written or -(bytes needed). */
+int64_t ds_format_values(ds_handle *h, int64_t n, const double *values, char *out, int64_t cap);
+/* Device milliseconds of the ds_extract_rows calls made while profiling was on, summed over *batches calls: ms[0] the
+ * statistics kernel, ms[1] rows_values_kernel, ms[2] rows_len_kernel + rows_scan_kernel, ms[3] rows_format_kernel, ms[4] the
+ * text's device-to-host copy. reset != 0 clears the sums afterwards. (The ds_get_kernel_stat table is positional ABI and holds
+ * the forward's kernels; the rows kernels are reported here.) */
+int ds_get_rows_times(ds_handle *h, int32_t reset, int64_t *batches, double *ms);
+
 /* Use a captured hipGraph for the forward (default on). */
 int ds_set_graph(ds_handle *h, int32_t enable);
 

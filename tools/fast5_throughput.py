@@ -6,13 +6,21 @@
 HDF5 reading is bypassed: each worker synthesises the reads (deepsignal_amd.synth.synthetic_read: 10 - 50 k bases, 4 - 15
 samples per base, random ACGT, CG sites) before the clock starts, then runs the route's own per-read code on them --
 extract_features.extract_read_features + call_modifications._features_item for the host route,
-call_modifications._device_read_record (motif scan, site list, packing) for the device route -- and the main process drives the
+extract_features._device_read_record (motif scan, site list, packing) for the device route -- and the main process drives the
 engine exactly as _call_mods_from_fast5s does (_call_mods / _rows_from_device). As there, --nproc > 2 runs nproc - 1 worker
 processes next to the engine process; otherwise the workers' part runs inline.
 
 Printed (one JSON line): sites/s of both routes; the device route's worker-side rate (sites per worker-second times workers:
 what the motif scan + packing can feed); the forward alone on resident-size batches (submit / wait of host features); and the
 extraction kernels' device time per batch of max_batch sites (Engine.kernel_stats() with profiling on, ds_extract).
+
+    python tools/fast5_throughput.py --mode extract [--reads 24] [--nproc 8] [--norm mad] [--out result.json]
+
+`extract` (fast5-like reads -> the feature TSV's row bytes, no forward, no model): the host route as extract_features runs it --
+nproc workers, each extract_read_features + _features_to_str, the parent writing the rows to a file -- against
+`extract --extract_on gpu` -- nproc - 1 workers running _device_read_record, the parent driving ds_submit_rows / ds_wait_rows
+through extract_features._rows_from_device and writing the returned bytes to a file. Also printed: device microseconds per
+batch of the statistics, values, length + scan and format kernels and of the text's device-to-host copy (Engine.rows_times()).
 """
 import argparse
 import json
@@ -60,8 +68,20 @@ def _host_task(idx):
     return cm._features_item(feats), time.perf_counter() - t0
 
 
+def _host_rows_task(idx):
+    from deepsignal_amd import extract_features as ef
+    t0 = time.perf_counter()
+    rows = []
+    for i in idx:
+        raw, starts, lengths, bases, scaling, offset, (name, strand, astrand, chrom, cstart) = _READS[i]
+        rows += [ef._features_to_str(f) for f in
+                 ef.extract_read_features(raw, starts, lengths, bases, scaling, offset, name, strand, astrand, chrom, cstart,
+                                          None, ["CG"], 0, KMER, SIGNAL, 1, _CFG["norm"])]
+    return "".join(r + "\n" for r in rows).encode(), time.perf_counter() - t0
+
+
 def _device_task(idx):
-    from deepsignal_amd import call_modifications as cm
+    from deepsignal_amd import extract_features as cm
     t0 = time.perf_counter()
     recs = []
     for i in idx:
@@ -102,6 +122,99 @@ def _run_route(route, eng, tasks, nproc, args):
             pool.join()
     return {"sites": nsites, "seconds": round(wall, 4), "sites_per_s": round(nsites / wall, 1),
             "worker_seconds": round(worker_s, 4), "worker_sites_per_s": round(nsites / worker_s * workers, 1), "workers": workers}
+
+
+def _run_extract_route(route, eng, tasks, nproc, args, out_path):
+    """One route of `extract`: rows to out_path; the host route uses all nproc processes as workers (extract_features does),
+    the device route nproc - 1 beside the process that drives the engine."""
+    from deepsignal_amd import extract_features as ef
+    fn = _host_rows_task if route == "cpu" else _device_task
+    workers = min(nproc if route == "cpu" else nproc - 1, len(tasks))
+    pool = None
+    if workers > 1 or (route == "gpu" and nproc > 2):
+        import multiprocessing as mp
+        workers = max(1, workers)
+        pool = mp.get_context("spawn").Pool(workers, initializer=_init, initargs=(args.reads, args.seed, args.norm))
+        pool.map(_ready, range(4 * workers))
+    else:
+        workers = 1
+        _init(args.reads, args.seed, args.norm)
+    try:
+        nsites = nbytes = 0
+        worker_s = 0.0
+        with open(out_path, "wb") as wf:
+            t0 = time.perf_counter()
+            results = (pool.imap_unordered if route == "cpu" else pool.imap)(fn, tasks) if pool is not None else (fn(t) for t in tasks)
+            for payload, dt in results:
+                worker_s += dt
+                chunks = [payload] if route == "cpu" else ef._rows_from_device(payload, eng, args.norm, 1)[0]
+                for c in chunks:
+                    wf.write(c)
+                    nsites += c.count(b"\n")
+                    nbytes += len(c)
+            wf.flush()
+            os.fsync(wf.fileno())
+            wall = time.perf_counter() - t0
+    finally:
+        if pool is not None:
+            pool.close()
+            pool.join()
+    return {"sites": nsites, "bytes": nbytes, "seconds": round(wall, 4), "sites_per_s": round(nsites / wall, 1),
+            "MB_per_s": round(nbytes / wall / 1e6, 1), "worker_seconds": round(worker_s, 4), "workers": workers}
+
+
+def _rows_kernel_times(eng, args, repeats=3):
+    """extract_rows of the reads in full batches with profiling on: device µs per batch of each step (first pass is warm-up)."""
+    from deepsignal_amd.engine import ReadBatch, pack_info
+    _init(args.reads, args.seed, args.norm)
+    recs = _device_task(list(range(args.reads)))[0]
+    B = eng.max_batch
+    sr = np.concatenate([np.full(len(r[2]), i, np.int32) for i, r in enumerate(recs)])
+    sl = np.concatenate([r[2] for r in recs])
+    lines = [line for r in recs for line in r[3].split(b"\n")[:-1]]
+    batches = []
+    for k in range(len(sr) // B):
+        used = np.unique(sr[k * B:(k + 1) * B])
+        remap = np.full(len(recs), -1, np.int32)
+        remap[used] = np.arange(len(used), dtype=np.int32)
+        batches.append((ReadBatch([recs[i][1] for i in used], remap[sr[k * B:(k + 1) * B]], sl[k * B:(k + 1) * B], norm=args.norm),)
+                       + pack_info(lines[k * B:(k + 1) * B]))
+    nbytes = [len(eng.extract_rows(b, info, off, 1)[0]) for b, info, off in batches]
+    eng.set_profiling(1)
+    eng.rows_times(reset=True)
+    for _ in range(repeats):
+        for b, info, off in batches:
+            eng.extract_rows(b, info, off, 1)
+    t = eng.rows_times(reset=True)
+    eng.set_profiling(0)
+    n = max(1, t["batches"])
+    out = {"batches": len(batches), "repeats": repeats, "sites_per_batch": B, "text_bytes_per_batch": round(float(np.mean(nbytes)), 1)}
+    for k in ("stats_ms", "values_ms", "length_ms", "format_ms", "d2h_ms"):
+        out[k[:-3] + "_us_per_batch"] = round(t[k] * 1e3 / n, 1)
+    return out
+
+
+def _main_extract(args):
+    import tempfile
+    from deepsignal_amd.engine import Engine
+    eng = Engine(device=0, max_batch=args.engine_batch)          # no weights: extraction has no model
+    tmp = tempfile.mkdtemp(prefix="fast5_throughput_")
+    try:
+        tasks = [list(range(i, min(args.reads, i + args.reads_per_task))) for i in range(0, args.reads, args.reads_per_task)]
+        res = {"tool": "fast5_throughput", "mode": "extract", "reads": args.reads, "nproc": args.nproc, "norm": args.norm,
+               "engine_batch": args.engine_batch, "hdf5": "bypassed (reads synthesised in memory)"}
+        for route in args.routes.split(","):
+            res[route] = _run_extract_route(route, eng, tasks, args.nproc, args, os.path.join(tmp, route + ".tsv"))
+            print("# %s route: %s" % (route, res[route]), file=sys.stderr, flush=True)
+        if "cpu" in res and "gpu" in res:
+            res["gpu_over_cpu"] = round(res["gpu"]["sites_per_s"] / res["cpu"]["sites_per_s"], 2)
+            res["same_sites"] = res["gpu"]["sites"] == res["cpu"]["sites"]
+        res["rows_kernels"] = _rows_kernel_times(eng, args)
+    finally:
+        eng.close()
+        import shutil
+        shutil.rmtree(tmp, ignore_errors=True)
+    return res
 
 
 def _kernel_times(eng, args):
@@ -169,7 +282,15 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--routes", default="cpu,gpu")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--mode", default="call_mods", choices=["call_mods", "extract"])
     args = ap.parse_args(argv)
+    if args.mode == "extract":
+        line = json.dumps(_main_extract(args))
+        print(line)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
     from deepsignal_amd import weights
     from deepsignal_amd.engine import Engine
     eng = Engine(device=0, max_batch=args.engine_batch, precision=args.precision)
