@@ -195,9 +195,12 @@ def engine_batch_for(batch_size: int, precision: str, engine_batch: int = 0) -> 
 
 def make_engine(model_path: str, kmer_len: int, cent_signals_len: int, class_num: int, batch_size: int,
                 is_cnn: bool = True, is_rnn: bool = True, is_base: bool = True, device: int = 0,
-                precision: str = "fp32", engine_batch: int = 0):
-    """Model(...) + Session + Saver.restore (reference call_modifications.py:203-212)."""
+                precision: str = "fp32", engine_batch: int = 0, recheck_margin: float = 0.0, recheck_precision: str = "fp32"):
+    """Model(...) + Session + Saver.restore (reference call_modifications.py:203-212). recheck_margin > 0: a second engine of
+    `recheck_precision` with the same geometry, device and weights is built and attached (Engine.set_recheck): the sites
+    whose |prob_1 - prob_0| comes out below the margin are run again on it; the returned engine owns it."""
     from .engine import Engine
+    check_recheck_args(precision, recheck_margin, recheck_precision)
     weights = load_model_weights(model_path, kmer_len, cent_signals_len, class_num, is_cnn, is_rnn, is_base)
     # `batch_size` is the reference's rows-per-sess.run (call_modifications.py:157-166); a site's result does not depend on
     # its batch mates (tests: the same bits alone, in a sub-batch, in a full batch), so the engine is sized for the batch the
@@ -215,11 +218,40 @@ def make_engine(model_path: str, kmer_len: int, cent_signals_len: int, class_num
         print("note: no device memory for an engine of %d sites per forward (%s); falling back to --batch_size %d"
               % (want, exc, batch_size), file=sys.stderr)
         eng = Engine(max_batch=batch_size, **kw)
-    if weights is None:
-        eng.load_weights_file(model_path)
-    else:
-        eng.load_weights(weights)
+    def load(e):
+        if weights is None:
+            e.load_weights_file(model_path)
+        else:
+            e.load_weights(weights)
+
+    load(eng)
+    if recheck_margin > 0:
+        try:
+            fine = Engine(max_batch=engine_batch_for(batch_size, recheck_precision, engine_batch), **dict(kw, precision=recheck_precision))
+            try:
+                load(fine)
+                eng.set_recheck(fine, recheck_margin, own=True)
+            except BaseException:
+                fine.close()
+                raise
+        except BaseException:
+            eng.close()
+            raise
     return eng
+
+
+FINE_PRECISIONS = ("fp32", "bf16x3")      # the fp32-class modes: held to the fp32 parity bars
+
+
+def check_recheck_args(precision: str, recheck_margin: float, recheck_precision: str) -> None:
+    """Usage errors of --recheck_margin / --recheck_precision (raised before any GPU work)."""
+    if recheck_margin != recheck_margin or recheck_margin < 0:
+        raise ValueError("--recheck_margin must be >= 0 (0 = off)")
+    if recheck_precision not in FINE_PRECISIONS:
+        raise ValueError("--recheck_precision must be one of %s" % (FINE_PRECISIONS,))
+    if recheck_margin > 0 and precision in FINE_PRECISIONS:
+        raise ValueError("--recheck_margin %g with --precision %s: there is nothing to recheck, every site already runs in an "
+                         "fp32-class mode (use --precision bf16 or bf16_all)" % (recheck_margin, precision))
 
 
 def _distributed_context(dist):
@@ -517,7 +549,7 @@ def _call_mods_sharded(input_path, engine, batch_size, result_file, kmer_len, ce
 def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
               batch_size, learning_rate, class_num, nproc, is_gpu, is_rnn, is_base, is_cnn,
               f5_args, engine=None, f5_batch_num=None, native_io=True, precision="fp32", dist=None, force_sharded=False,
-              engine_batch=0, extract_on="cpu"):
+              engine_batch=0, extract_on="cpu", recheck_margin=0.0, recheck_precision="fp32"):
     """The reference's call_mods (call_modifications.py:417-495), same signature and argument meaning.
 
     learning_rate / is_gpu are accepted for signature compatibility: inference ignores the learning rate
@@ -530,9 +562,13 @@ def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
     process per GPU takes its share of the reads. force_sharded=True takes that multi-process route (byte ranges, row
     gather through the process group's collectives) even in a world of one: one rank under the launcher runs the same
     RCCL calls as eight. extract_on="gpu" (directory input only) computes the features of the fast5 route on the GPU
-    (ds_submit_reads) instead of on the host."""
+    (ds_submit_reads) instead of on the host. recheck_margin > 0 (with a bf16 `precision`): the sites whose |prob_1 - prob_0|
+    comes out below it are run again in `recheck_precision` and take that result (make_engine); every rank of a multi-GPU run
+    builds its own pair."""
     if extract_on not in ("cpu", "gpu"):
         raise ValueError("extract_on must be 'cpu' or 'gpu'")
+    if engine is None:
+        check_recheck_args(precision, recheck_margin, recheck_precision)
     start = time.time()
     f5 = _unpack_f5_args(f5_args, f5_batch_num)
     dist, rank, world, local = _distributed_context(dist)
@@ -550,7 +586,8 @@ def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
     if own:
         engine = make_engine(model_path, kmer_len, cent_signals_len, class_num, batch_size,
                              is_cnn=is_cnn, is_rnn=is_rnn, is_base=is_base, device=local, precision=precision,
-                             engine_batch=engine_batch)
+                             engine_batch=engine_batch, recheck_margin=recheck_margin, recheck_precision=recheck_precision)
+    recheck = None
     try:
         if os.path.isdir(input_path):
             nsites = _call_mods_from_fast5s(input_path, result_file, kmer_len, cent_signals_len, batch_size, f5, engine,
@@ -590,9 +627,15 @@ def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
                         wf.write(row + "\n")
                     wf.flush()
                     nsites += len(pred_str)
+        if own and recheck_margin > 0:
+            recheck = engine.recheck_stats()
     finally:
         if own:
             engine.close()
+    if recheck is not None:
+        print("recheck%s: %d sites, %d rechecked in %s (margin %g), share %.4f"
+              % (" (rank %d)" % rank if world > 1 else "", recheck["sites"], recheck["rechecked"], recheck_precision, recheck_margin,
+                 recheck["rechecked"] / max(1, recheck["sites"])))
     if rank == 0:
         print("call_mods costs %.2f seconds.. (%d sites)" % (time.time() - start, nsites))
     return nsites

@@ -160,6 +160,13 @@ struct Slot {
     int64_t* pin_rowoff = nullptr;
     char* pin_rows = nullptr;
     size_t pin_rows_cap = 0;
+    // ds_set_recheck: allocated at the handle's first attachment. d_rc = [count, 3 pad | index[B] | the selected sites' inputs,
+    // an image of d_in | the fine handle's act[B][C] | pred[B]]; pin_rc = [count, 3 pad | index[B] | fine act | fine pred]
+    char* d_rc = nullptr;
+    int* pin_rc = nullptr;
+    hipEvent_t rc_ev[2] = {nullptr, nullptr};   // around recheck_select_kernel of a profiled forward (ds_get_recheck_times)
+    bool rc_selected = false;             // the forward in flight carries a selection (a recheck was attached when it was submitted)
+    bool rc_timed = false;
 
     std::map<int, Plan> plans;
     int last_n = 0;
@@ -226,6 +233,13 @@ struct ds_handle {
     KernelStat kstat[K_COUNT];
     int64_t rows_batches = 0;             // ds_extract_rows calls timed while profiling is on, and their summed device milliseconds:
     double rows_ms[5] = {0, 0, 0, 0, 0};  // statistics, values, lengths + scan, format kernels; text device-to-host copy
+    // cascaded precision (ds_set_recheck): sites of this handle's forwards within rc_margin of the threshold are run again on
+    // rc_fine (caller-owned) and its results replace this handle's for them
+    ds_handle* rc_fine = nullptr;
+    float rc_margin = 0.f;
+    int64_t rc_sites = 0, rc_rechecked = 0, rc_forwards = 0;      // since the attachment
+    int64_t rc_launches = 0;              // recheck_select_kernel launches timed while profiling was on, and their summed device ms
+    double rc_ms = 0;
     // pipelining: consecutive forwards rotate over independent slots (own workspace, streams, graphs), so the
     // dependency chain of one 512-site forward overlaps the next ones'; weights are shared
     std::vector<Slot> slots;
@@ -1516,6 +1530,9 @@ void ds_destroy(ds_handle* h)
         if (sl.pin_rowoff) hipHostFree(sl.pin_rowoff);
         if (sl.pin_rows) hipHostFree(sl.pin_rows);
         if (sl.pin_act) hipHostFree(sl.pin_act);       // pin_pred points into it
+        if (sl.d_rc) hipFree(sl.d_rc);
+        if (sl.pin_rc) hipHostFree(sl.pin_rc);
+        for (hipEvent_t e : sl.rc_ev) if (e) hipEventDestroy(e);
         if (sl.ev_fork) hipEventDestroy(sl.ev_fork);
         if (sl.ev_join) hipEventDestroy(sl.ev_join);
         if (sl.s0) hipStreamDestroy(sl.s0);
@@ -1600,6 +1617,8 @@ static int ds_forward_device_impl(ds_handle* h, int32_t n, const int32_t* d_kmer
     if (!h) return DS_ERR_INVALID;
     if (!h->finalized) return fail(h, DS_ERR_INVALID, "weights not loaded");
     if (n < 0 || n > h->B) return fail(h, DS_ERR_INVALID, "n exceeds max_batch");
+    if (h->rc_fine)       // the outputs are the caller's device memory: there is no host-side place to merge the fine results
+        return fail(h, DS_ERR_UNSUPPORTED, "ds_forward_device is not available on a handle with a recheck attached (ds_set_recheck)");
     if (n == 0) return DS_OK;
     if (!d_kmer || !d_means || !d_stds || !d_sanums || !d_signals || !d_act || !d_pred)
         return fail(h, DS_ERR_INVALID, "null buffer");
@@ -1624,6 +1643,10 @@ int ds_sync(ds_handle* h)
     if (h->profiling) return collect_stage_times(h);
     return DS_OK;
 }
+
+// cascaded precision (ds_set_recheck, below): the selection behind a forward, and the merge of the fine handle's results
+static int enqueue_recheck(ds_handle* h, Slot& sl, int n);
+static int finish_recheck(ds_handle* h, Slot& sl, int n, float* act, int32_t* pred);
 
 static int ds_forward_impl(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums,
                const float* signals, float* act, int32_t* pred)
@@ -1669,6 +1692,7 @@ static int ds_forward_impl(ds_handle* h, int32_t n, const int32_t* kmer, const f
                 if (sl.s1) hipStreamSynchronize(sl.s1);
                 sl.submitted_n = -1;
                 sl.rows_ticket = false;
+                sl.rc_selected = false;
             }
             h->err = msg;
         }
@@ -1686,11 +1710,198 @@ static int ds_forward_impl(ds_handle* h, int32_t n, const int32_t* kmer, const f
         HIPCHK(h, hipMemcpyAsync(h->cur->d_signals, signals + (size_t)off * h->S, (size_t)m * h->S * 4, hipMemcpyHostToDevice, h->cur->s0));
         int rc = run_resident(h, m);
         if (rc) return rc;
+        rc = enqueue_recheck(h, *h->cur, m);
+        if (rc) return rc;
         HIPCHK(h, hipMemcpyAsync(act + (size_t)off * h->C, h->cur->act, (size_t)m * h->C * 4, hipMemcpyDeviceToHost, h->cur->s0));
         HIPCHK(h, hipMemcpyAsync(pred + off, h->cur->pred, (size_t)m * 4, hipMemcpyDeviceToHost, h->cur->s0));
         rc = ds_sync(h);
         if (rc) return rc;
+        rc = finish_recheck(h, *h->cur, m, act + (size_t)off * h->C, pred + off);
+        if (rc) return rc;
     }
+    return DS_OK;
+}
+
+// ---- cascaded precision (ds_set_recheck) ----------------------------------------------------------------------------------
+// A forward of a handle with a fine handle attached is followed, on the slot's stream, by recheck_select_kernel (ds_recheck.hip):
+// count, index and the selected sites' inputs land in the slot's recheck block, count and index travel to the host behind the
+// forward's own results. The wait then runs the fine handle on the compacted inputs (device to device, chunks of the fine
+// handle's max_batch) and replaces the selected sites' act / pred in the caller's arrays: a host loop over index, m x 12 bytes.
+struct RcLayout { size_t index, in, act, pred, total, pin_act, pin_pred, pin_total; };
+static RcLayout rc_layout(const ds_handle* h)
+{
+    const size_t B = h->B, T = h->T, S = h->S, C = h->C;
+    RcLayout L;
+    L.index = 16;
+    L.in = L.index + 4 * B;
+    L.act = L.in + 4 * B * (4 * T + S);
+    L.pred = L.act + 4 * B * C;              // [act | pred] contiguous: one copy back, as the forward's own results
+    L.total = L.pred + 4 * B;
+    L.pin_act = L.index + 4 * B;
+    L.pin_pred = L.pin_act + 4 * B * C;
+    L.pin_total = L.pin_pred + 4 * B;
+    return L;
+}
+
+static int alloc_recheck(ds_handle* h)
+{
+    const RcLayout L = rc_layout(h);
+    for (Slot& sl : h->slots) {
+        if (!sl.d_rc) {
+            hipError_t e = hipMalloc((void**)&sl.d_rc, L.total);
+            if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, DS_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+        }
+        if (!sl.pin_rc) HIPCHK(h, hipHostMalloc((void**)&sl.pin_rc, L.pin_total, hipHostMallocDefault));
+        for (hipEvent_t& e : sl.rc_ev)
+            if (!e) HIPCHK(h, hipEventCreate(&e));
+    }
+    return DS_OK;
+}
+
+static RecheckArgs recheck_args(const ds_handle* h, Slot& sl, int n, float margin)
+{
+    const RcLayout L = rc_layout(h);
+    RecheckArgs a;
+    a.act = sl.act; a.in = sl.d_in; a.out = reinterpret_cast<float*>(sl.d_rc + L.in);
+    a.count = reinterpret_cast<int*>(sl.d_rc); a.index = reinterpret_cast<int*>(sl.d_rc + L.index);
+    a.margin = margin; a.n = n; a.C = h->C; a.T = h->T; a.S = h->S; a.B = h->B;
+    return a;
+}
+
+// behind the forward of n sites on sl.s0
+static int enqueue_recheck(ds_handle* h, Slot& sl, int n)
+{
+    sl.rc_selected = false;
+    if (!h->rc_fine) return DS_OK;
+    sl.rc_timed = h->profiling != 0;
+    if (sl.rc_timed) HIPCHK(h, hipEventRecord(sl.rc_ev[0], sl.s0));
+    HIPCHK(h, launch_recheck_select(recheck_args(h, sl, n, h->rc_margin), sl.s0));
+    if (sl.rc_timed) HIPCHK(h, hipEventRecord(sl.rc_ev[1], sl.s0));
+    HIPCHK(h, hipMemcpyAsync(sl.pin_rc, sl.d_rc, rc_layout(h).index + 4 * (size_t)n, hipMemcpyDeviceToHost, sl.s0));
+    sl.rc_selected = true;
+    return DS_OK;
+}
+
+// sl.s0 is drained and act / pred hold the coarse results of the slot's n sites: the selected ones get the fine handle's
+static int finish_recheck(ds_handle* h, Slot& sl, int n, float* act, int32_t* pred)
+{
+    if (!sl.rc_selected) return DS_OK;
+    sl.rc_selected = false;
+    ds_handle* f = h->rc_fine;
+    if (!f) return fail(h, DS_ERR_INVALID, "recheck: the fine handle was detached while a forward was in flight");
+    if (sl.rc_timed) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, sl.rc_ev[0], sl.rc_ev[1]) == hipSuccess) { h->rc_launches += 1; h->rc_ms += ms; }
+        else (void)hipGetLastError();
+    }
+    const RcLayout L = rc_layout(h);
+    const int m = sl.pin_rc[0];
+    const int* index = sl.pin_rc + L.index / 4;
+    if (m < 0 || m > n) return fail(h, DS_ERR_INVALID, "recheck: selection count out of range");
+    h->rc_sites += n;
+    if (m == 0) return DS_OK;
+    const size_t T = h->T, S = h->S, C = h->C, B = h->B;
+    const float* in = reinterpret_cast<const float*>(sl.d_rc + L.in);
+    float* d_act = reinterpret_cast<float*>(sl.d_rc + L.act);
+    int32_t* d_pred = reinterpret_cast<int32_t*>(sl.d_rc + L.pred);
+    for (int off = 0; off < m; off += f->B) {
+        const int mc = std::min(f->B, m - off);
+        const size_t o = (size_t)off;
+        int rc = ds_forward_device(f, mc, reinterpret_cast<const int32_t*>(in) + o * T, in + B * T + o * T, in + 2 * B * T + o * T,
+                                   in + 3 * B * T + o * T, in + 4 * B * T + o * S, d_act + o * C, d_pred + off);
+        if (rc) { ds_sync(f); return fail(h, rc, "recheck: the fine handle's forward failed: " + f->err); }
+        h->rc_forwards += 1;
+    }
+    int rc = ds_sync(f);
+    if (rc) return fail(h, rc, "recheck: the fine handle's forward failed: " + f->err);
+    char* pin = reinterpret_cast<char*>(sl.pin_rc);
+    HIPCHK(h, hipMemcpyAsync(pin + L.pin_act, d_act, (B * C + (size_t)m) * 4, hipMemcpyDeviceToHost, sl.s0));
+    HIPCHK(h, hipStreamSynchronize(sl.s0));
+    const float* f_act = reinterpret_cast<const float*>(pin + L.pin_act);
+    const int32_t* f_pred = reinterpret_cast<const int32_t*>(pin + L.pin_pred);
+    for (int k = 0; k < m; ++k) {
+        const int i = index[k];
+        if (i < 0 || i >= n) return fail(h, DS_ERR_INVALID, "recheck: selected site out of range");
+        memcpy(act + (size_t)i * C, f_act + (size_t)k * C, C * 4);
+        pred[i] = f_pred[k];
+    }
+    h->rc_rechecked += m;
+    return DS_OK;
+}
+
+static int ds_set_recheck_impl(ds_handle* c, ds_handle* f, float margin)
+{
+    if (!c) return DS_ERR_INVALID;
+    if (margin != margin) return fail(c, DS_ERR_INVALID, "ds_set_recheck: margin is NaN");
+    for (Slot& sl : c->slots)
+        if (sl.submitted_n >= 0) return fail(c, DS_ERR_INVALID, "ds_set_recheck: tickets are still in flight");
+    if (!f || margin <= 0) {
+        c->rc_fine = nullptr;
+        c->rc_margin = 0.f;
+        return DS_OK;
+    }
+    if (f == c) return fail(c, DS_ERR_INVALID, "ds_set_recheck: fine is the coarse handle itself");
+    if (f->rc_fine) return fail(c, DS_ERR_INVALID, "ds_set_recheck: the fine handle has a recheck attached itself (no chains)");
+    auto differs = [&](const char* what, int a, int b) {
+        return fail(c, DS_ERR_INVALID, std::string("ds_set_recheck: ") + what + " differs (coarse " + std::to_string(a) + ", fine " + std::to_string(b) + ")");
+    };
+    if (c->T != f->T) return differs("kmer_len", c->T, f->T);
+    if (c->S != f->S) return differs("signal_len", c->S, f->S);
+    if (c->C != f->C) return differs("class_num", c->C, f->C);
+    if (c->is_cnn != f->is_cnn) return differs("is_cnn", c->is_cnn, f->is_cnn);
+    if (c->is_rnn != f->is_rnn) return differs("is_rnn", c->is_rnn, f->is_rnn);
+    if (c->is_base != f->is_base) return differs("is_base", c->is_base, f->is_base);
+    if (c->cfg.device != f->cfg.device) return differs("device", c->cfg.device, f->cfg.device);
+    if (c->C != 2)
+        return fail(c, DS_ERR_UNSUPPORTED, "ds_set_recheck: class_num " + std::to_string(c->C) + ": the selection rule is defined for two classes");
+    if (!c->finalized || !f->finalized) return fail(c, DS_ERR_INVALID, "ds_set_recheck: weights not loaded");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    int rc = alloc_recheck(c);
+    if (rc) return rc;
+    c->rc_fine = f;
+    c->rc_margin = margin;
+    c->rc_sites = c->rc_rechecked = c->rc_forwards = 0;
+    return DS_OK;
+}
+
+int ds_get_recheck_stats(ds_handle* h, int64_t* sites, int64_t* rechecked, int64_t* fine_forwards)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (sites) *sites = h->rc_sites;
+    if (rechecked) *rechecked = h->rc_rechecked;
+    if (fine_forwards) *fine_forwards = h->rc_forwards;
+    return DS_OK;
+}
+
+int ds_get_recheck_times(ds_handle* h, int32_t reset, int64_t* launches, double* ms)
+{
+    if (!h || !launches || !ms) return DS_ERR_INVALID;
+    *launches = h->rc_launches;
+    *ms = h->rc_ms;
+    if (reset) { h->rc_launches = 0; h->rc_ms = 0; }
+    return DS_OK;
+}
+
+// Diagnostic: the selection of recheck_select_kernel for n rows of act given by the caller (directed values: the specials, every
+// lane / wave / workgroup pattern), on an idle slot. The rows it compacts are whatever the slot's inputs hold.
+static int ds_recheck_select_impl(ds_handle* h, int32_t n, const float* act, float margin, int32_t* count, int32_t* index)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (!act || !count || !index || n < 1 || n > h->B) return fail(h, DS_ERR_INVALID, "ds_recheck_select: bad argument");
+    if (h->C != 2) return fail(h, DS_ERR_UNSUPPORTED, "ds_recheck_select: the selection rule is defined for two classes");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    Slot& sl = h->slots[h->next_slot % h->slots.size()];
+    if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_recheck_select: every slot is in flight");
+    int rc = alloc_recheck(h);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(sl.act, act, (size_t)n * h->C * 4, hipMemcpyHostToDevice, sl.s0));
+    HIPCHK(h, launch_recheck_select(recheck_args(h, sl, n, margin), sl.s0));
+    HIPCHK(h, hipMemcpyAsync(sl.pin_rc, sl.d_rc, rc_layout(h).index + 4 * (size_t)n, hipMemcpyDeviceToHost, sl.s0));
+    HIPCHK(h, hipStreamSynchronize(sl.s0));
+    const int m = sl.pin_rc[0];
+    if (m < 0 || m > n) return fail(h, DS_ERR_INVALID, "ds_recheck_select: selection count out of range");
+    *count = m;
+    memcpy(index, sl.pin_rc + rc_layout(h).index / 4, (size_t)m * 4);
     return DS_OK;
 }
 
@@ -1750,6 +1961,8 @@ static int ds_submit_parts_impl(ds_handle* h, int32_t nparts, const int32_t* cou
     }
     int rc = run_resident(h, n);
     if (rc) return rc;
+    rc = enqueue_recheck(h, sl, n);
+    if (rc) return rc;
     // [act (max_batch rows) | pred]: one copy back
     HIPCHK(h, hipMemcpyAsync(sl.pin_act, sl.act, (B * h->C + (size_t)n) * 4, hipMemcpyDeviceToHost, sl.s0));
     sl.submitted_n = n;
@@ -1773,8 +1986,9 @@ static int ds_wait_impl(ds_handle* h, int32_t ticket, float* act, int32_t* pred)
     HIPCHK(h, hipStreamSynchronize(sl.s0));
     memcpy(act, sl.pin_act, (size_t)sl.submitted_n * h->C * 4);
     memcpy(pred, sl.pin_pred, (size_t)sl.submitted_n * 4);
+    const int n = sl.submitted_n;
     sl.submitted_n = -1;
-    return DS_OK;
+    return finish_recheck(h, sl, n, act, pred);      // the ticket is complete once its rechecks are merged
 }
 
 
@@ -1877,6 +2091,8 @@ static int ds_submit_reads_impl(ds_handle* h, const ds_reads* r, int32_t* ticket
     h->cur = &sl;
     const int n = p.nsites;
     rc = run_resident(h, n);
+    if (rc) return rc;
+    rc = enqueue_recheck(h, sl, n);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(sl.pin_act, sl.act, ((size_t)h->B * h->C + (size_t)n) * 4, hipMemcpyDeviceToHost, sl.s0));
     sl.submitted_n = n;
@@ -2371,5 +2587,7 @@ int ds_submit_reads(ds_handle* h, const ds_reads* reads, int32_t* ticket) { retu
 int ds_submit_rows(ds_handle* h, const ds_reads* reads, const char* info, const int64_t* info_off, int32_t label, int32_t* ticket) { return guarded(h, [&] { return ds_submit_rows_impl(h, reads, info, info_off, label, ticket); }); }
 int64_t ds_wait_rows(ds_handle* h, int32_t ticket, char* out, int64_t cap, int64_t* row_off) { return guarded(h, [&] { return ds_wait_rows_impl(h, ticket, out, cap, row_off); }); }
 int64_t ds_extract_rows(ds_handle* h, const ds_reads* reads, const char* info, const int64_t* info_off, int32_t label, char* out, int64_t cap, int64_t* row_off) { return guarded(h, [&] { return ds_extract_rows_impl(h, reads, info, info_off, label, out, cap, row_off); }); }
+int ds_set_recheck(ds_handle* coarse, ds_handle* fine, float margin) { return guarded(coarse, [&] { return ds_set_recheck_impl(coarse, fine, margin); }); }
+int ds_recheck_select(ds_handle* h, int32_t n, const float* act, float margin, int32_t* count, int32_t* index) { return guarded(h, [&] { return ds_recheck_select_impl(h, n, act, margin, count, index); }); }
 int64_t ds_format_values(ds_handle* h, int64_t n, const double* values, char* out, int64_t cap) { return guarded(h, [&] { return ds_format_values_impl(h, n, values, out, cap); }); }
 }  // extern "C"

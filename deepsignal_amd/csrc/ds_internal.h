@@ -292,6 +292,20 @@ hipError_t launch_head_folded(const HeadFoldedArgs& a, hipStream_t s);
 hipError_t launch_gather_inputs(const int* kmer, const float* means, const float* stds, const float* lens, const float* signals,
                                 float* block, int n, int T, int S, int B, hipStream_t s);
 hipError_t launch_scatter_outputs(const float* act, const int* pred, float* act_out, int* pred_out, int n, int C, hipStream_t s);
+// Cascaded precision (ds_recheck.hip, ds_set_recheck): the sites of a finished forward whose act falls within `margin` of the
+// threshold, in ascending site order: count[0] = how many, index[k] = the k-th one, and its five input rows copied to row k of
+// `out`. in / out are input blocks [kmer | means | stds | sanums | signals] with regions sized for B sites (Slot::d_in's layout).
+// Not in DS_KERNEL_TABLE (positional ABI of the forward's kernels): timed into ds_get_recheck_times.
+struct RecheckArgs {
+    const float* act;      // [n][C]
+    const float* in;
+    float* out;
+    int* count;
+    int* index;            // [B]
+    float margin;
+    int n, C, T, S, B;
+};
+hipError_t launch_recheck_select(const RecheckArgs& a, hipStream_t s);
 // table[v][c] = sum_e emb[v][e] * kernel[e][c]  (embedding folded into layer-0 W_x; model.py:61-69)
 hipError_t launch_embed_table(const float* emb, const float* kernel, float* table, int vocab, int esize, int ncol, hipStream_t s);
 

@@ -24,7 +24,8 @@ def main_call_mods(args):
     call_mods(args.input_path, args.model_path, args.result_file, args.kmer_len, args.cent_signals_len,
               args.batch_size, args.learning_rate, args.class_num, args.nproc, str2bool(args.is_gpu),
               str2bool(args.is_rnn), str2bool(args.is_base), str2bool(args.is_cnn), f5_args,
-              precision=args.precision, engine_batch=args.engine_batch, extract_on=args.extract_on)
+              precision=args.precision, engine_batch=args.engine_batch, extract_on=args.extract_on,
+              recheck_margin=args.recheck_margin, recheck_precision=args.recheck_precision)
 
 
 def main_extraction(args):
@@ -84,6 +85,12 @@ def build_parser():
                    help="fp32 (reference numerics, native fp32 matrix instructions); bf16x3 (fp32-class results: fp32 operands carried "
                         "as three bf16 terms on the bf16 matrix pipe, held to the fp32 parity bars); bf16 / bf16_all (bf16 conv+FC "
                         "operands with fp32 accumulate: fast, probabilities good to ~1e-2 only)")
+    g.add_argument("--recheck_margin", type=float, default=0.0,
+                   help="cascaded precision, with --precision bf16 / bf16_all: sites whose |prob_1 - prob_0| comes out below this "
+                        "margin are run again in --recheck_precision and take that result (default 0 = off; an fp32-class "
+                        "--precision has nothing to recheck and is refused)")
+    g.add_argument("--recheck_precision", default="fp32", choices=["fp32", "bf16x3"],
+                   help="the mode of the second forward of --recheck_margin")
     g.add_argument("--extract_on", default="cpu", choices=["cpu", "gpu"],
                    help="fast5-directory input only: compute the per-site features on the host (cpu, default) or on the GPU next "
                         "to the forward (gpu; same features bit for bit, except that a middle base of >= cent_signals_len samples "
@@ -126,6 +133,12 @@ def main(argv=None):
     if not getattr(args, "func", None):
         parser.print_help()
         return 1
+    if args.module == "call_mods":
+        from .call_modifications import check_recheck_args
+        try:
+            check_recheck_args(args.precision, args.recheck_margin, args.recheck_precision)
+        except ValueError as exc:
+            parser.error(str(exc))
     args.func(args)
     return 0
 

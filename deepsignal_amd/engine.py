@@ -39,6 +39,8 @@ EXPORTED_SYMBOLS = (
     "ds_extract", "ds_submit_reads", "ds_extract_reference",
     # feature rows on the device (the text half of `extract`)
     "ds_submit_rows", "ds_wait_rows", "ds_extract_rows", "ds_extract_rows_reference", "ds_format_values", "ds_get_rows_times",
+    # cascaded precision (a fine handle rechecks the near-threshold sites of a coarse one)
+    "ds_set_recheck", "ds_get_recheck_stats", "ds_get_recheck_times", "ds_recheck_select",
 )
 
 
@@ -258,6 +260,12 @@ def load_library() -> ctypes.CDLL:
     lib.ds_format_values.argtypes = [vp, i64, vp, vp, i64]
     lib.ds_format_values.restype = i64
     lib.ds_get_rows_times.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_double)]
+    lib.ds_set_recheck.argtypes = [vp, vp, ctypes.c_float]
+    lib.ds_set_recheck.restype = ctypes.c_int
+    lib.ds_get_recheck_stats.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    lib.ds_get_recheck_stats.restype = ctypes.c_int
+    lib.ds_get_recheck_times.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_double)]
+    lib.ds_recheck_select.argtypes = [vp, i32, vp, ctypes.c_float, ctypes.POINTER(i32), vp]
     lib.ds_get_kernel_stat.argtypes = [vp, i32, ctypes.c_char_p, i32, ctypes.POINTER(i64),
                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
     _lib = lib
@@ -304,12 +312,20 @@ class Engine:
         self._lib.ds_num_slots.argtypes = [ctypes.c_void_p]
         self._slots = int(self._lib.ds_num_slots(self._h))
         self.device, self.max_batch = device, max_batch
+        self._fine: Optional["Engine"] = None      # set_recheck: the attached engine stays referenced here
+        self._owns_fine = False
 
     # -- lifecycle -----------------------------------------------------------------------------
     def close(self) -> None:
         if getattr(self, "_h", None) and self._h.value:
+            fine, owned = getattr(self, "_fine", None), getattr(self, "_owns_fine", False)
+            if fine is not None:                   # detach first: the library must not keep a handle that may go away
+                self._lib.ds_set_recheck(self._h, None, 0.0)
+                self._fine, self._owns_fine = None, False
             self._lib.ds_destroy(self._h)
             self._h = ctypes.c_void_p()
+            if fine is not None and owned:
+                fine.close()
 
     def __del__(self):
         try:
@@ -446,6 +462,43 @@ class Engine:
         ms = (ctypes.c_double * 5)()
         self._check(self._lib.ds_get_rows_times(self._h, int(reset), ctypes.byref(n), ms), "ds_get_rows_times")
         return dict(zip(("stats_ms", "values_ms", "length_ms", "format_ms", "d2h_ms"), ms), batches=int(n.value))
+
+    # -- cascaded precision (ds_set_recheck) ---------------------------------------------------
+    def set_recheck(self, fine: Optional["Engine"], margin: float, own: bool = False) -> None:
+        """Attach `fine` (same geometry and device, weights loaded): every site whose result here falls within `margin` of the
+        threshold -- |p1 - p0| < margin on the normalised probabilities, or a non-finite result -- is run again on `fine`,
+        whose act / pred replace this engine's for that site. run(), submit() / submit_parts() / wait() and submit_reads()
+        honour it; run_device() raises while it is attached. `fine` must not be used directly while attached. fine None or
+        margin <= 0 detaches. own=True: close() of this engine closes `fine` too."""
+        if fine is not None and not isinstance(fine, Engine):
+            raise TypeError("fine must be an Engine or None")
+        h = fine._h if fine is not None else None
+        self._check(self._lib.ds_set_recheck(self._h, h, float(margin)), "ds_set_recheck")
+        attached = fine is not None and margin > 0
+        self._fine, self._owns_fine = (fine, bool(own)) if attached else (None, False)
+
+    def recheck_stats(self) -> dict:
+        """ds_get_recheck_stats since the attachment: sites through this engine, sites rechecked, forwards of the fine engine."""
+        a, b, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._lib.ds_get_recheck_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
+                    "ds_get_recheck_stats")
+        return {"sites": int(a.value), "rechecked": int(b.value), "fine_forwards": int(c.value)}
+
+    def recheck_times(self, reset: bool = False) -> dict:
+        """ds_get_recheck_times: device milliseconds of the selection kernel over the run() calls made while profiling was on."""
+        n, ms = ctypes.c_int64(), ctypes.c_double()
+        self._check(self._lib.ds_get_recheck_times(self._h, int(reset), ctypes.byref(n), ctypes.byref(ms)), "ds_get_recheck_times")
+        return {"launches": int(n.value), "select_ms": float(ms.value)}
+
+    def recheck_select(self, act, margin: float) -> np.ndarray:
+        """ds_recheck_select (diagnostic): the ascending indices the selection kernel picks for the given act rows."""
+        act = np.ascontiguousarray(act, np.float32)
+        n = int(act.shape[0])
+        count = ctypes.c_int32()
+        index = np.empty(n, np.int32)
+        self._check(self._lib.ds_recheck_select(self._h, n, act.ctypes.data, float(margin), ctypes.byref(count), index.ctypes.data),
+                    "ds_recheck_select")
+        return index[:count.value].copy()
 
     @property
     def slots(self) -> int:

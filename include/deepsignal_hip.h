@@ -337,6 +337,39 @@ int64_t ds_format_values(ds_handle *h, int64_t n, const double *values, char *ou
  * the forward's kernels; the rows kernels are reported here.) */
 int ds_get_rows_times(ds_handle *h, int32_t reset, int64_t *batches, double *ms);
 
+/* ---- cascaded precision: a fast forward on every site, a second forward on the sites it leaves near the threshold ------------
+ * ds_set_recheck(coarse, fine, margin) attaches `fine` -- another handle with weights loaded, on the same device, with the same
+ * kmer_len, signal_len, class_num and is_cnn / is_rnn / is_base -- to `coarse`. From then on every forward of `coarse` through
+ * ds_forward, ds_submit / ds_submit_parts / ds_wait and ds_submit_reads is followed by a selection on its act, in float32 with
+ * exactly these operations (no fused multiply-add):
+ *     d = fabsf(act[i][1] - act[i][0]);  s = act[i][0] + act[i][1];
+ *     site i is selected iff d < margin * s, or d or s is not finite
+ * which is |prob_1 - prob_0| < margin on the normalised probabilities call_mods prints, without the division. The selected
+ * sites' inputs are compacted on the device in ascending site order and forwarded through `fine` in chunks of at most fine's
+ * max_batch (the last one may be partial); for a selected site act[i] / pred[i] are fine's outputs for that site's inputs, for
+ * every other site coarse's, untouched; row order is unchanged. A ticket is complete when its rechecks are merged (inside
+ * ds_wait); tickets complete in submission order and up to `slots` coarse forwards stay in flight as without a recheck.
+ * fine == NULL or margin <= 0 detaches. DS_ERR_INVALID (ds_last_error(coarse) names the reason): mismatched geometry or device,
+ * fine == coarse, a fine handle that has a recheck attached itself, a NaN margin, tickets in flight on coarse.
+ * DS_ERR_UNSUPPORTED: class_num != 2. Any precision pair is accepted; a bf16 coarse handle with an fp32-class fine one is
+ * the useful one.
+ * OWNERSHIP: the caller keeps `fine`, must keep it alive while it is attached (detach before ds_destroy(fine)) and must not
+ * call anything on `fine` directly in the meantime: its pipeline slots are driven by coarse's waits.
+ * ds_forward_device on a handle with a recheck attached returns DS_ERR_UNSUPPORTED: its outputs are caller-owned device
+ * memory, and the merge happens where the results reach the host. The slots' recheck buffers (inputs of max_batch sites, index,
+ * fine results) are allocated at a handle's first attachment. */
+int ds_set_recheck(ds_handle *coarse, ds_handle *fine, float margin);
+/* Since the attachment: sites that went through the coarse handle, sites rechecked, forwards issued on the fine handle. */
+int ds_get_recheck_stats(ds_handle *coarse, int64_t *sites, int64_t *rechecked, int64_t *fine_forwards);
+/* Device milliseconds of recheck_select_kernel (selection + compaction) summed over the *launches forwards made through
+ * ds_forward while profiling was on (ds_set_profiling); reset != 0 clears the sums. Like the rows kernels, the kernel is
+ * not part of the positional ds_get_kernel_stat table. */
+int ds_get_recheck_times(ds_handle *coarse, int32_t reset, int64_t *launches, double *ms);
+/* Diagnostic: the selection alone, for n rows of act given by the caller (1 <= n <= max_batch, class_num == 2) on an idle slot
+ * of h's GPU: *count selected sites, index[0 .. *count) ascending. For directed values -- NaN, +-inf, every lane pattern --
+ * that no forward produces on demand. Needs no weights and no attachment. */
+int ds_recheck_select(ds_handle *h, int32_t n, const float *act, float margin, int32_t *count, int32_t *index);
+
 /* Use a captured hipGraph for the forward (default on). */
 int ds_set_graph(ds_handle *h, int32_t enable);
 
