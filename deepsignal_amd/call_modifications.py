@@ -417,6 +417,80 @@ class _RowPipeline:
             self._worker = None
 
 
+class _TicketRows(NamedTuple):
+    """What wait_text returns for one ticket, in the shape _RowPipeline._emit reads from an item."""
+    info: np.ndarray
+    info_off: np.ndarray
+    kmer: np.ndarray
+
+
+class _TextPipeline(_RowPipeline):
+    """_RowPipeline fed with located-but-unparsed items (fastio.SpanItem): a batch is handed to the engine as row spans of the
+    mapped file (submit_text), the GPU parses them straight into the forward's inputs, and wait_text brings back what the
+    formatter needs (k-mer codes, the six leading columns). Batches are still filled across items to engine.max_batch and rows
+    leave in feed order."""
+
+    def __init__(self, engine, batch_size, sink, reader):
+        _RowPipeline.__init__(self, engine, batch_size, sink)
+        if not self.pipelined:
+            raise ValueError("parse_on='gpu' needs batch_size <= engine.max_batch")
+        self.reader = reader
+
+    def feed(self, item, tag=None):
+        n = len(item.begin)
+        self.nsites += n
+        s = 0
+        while s < n:
+            take = min(n - s, self.batch_size - self.count)
+            self.segs.append((tag, item, s, s + take))
+            self.count += take
+            s += take
+            if self.count == self.batch_size:
+                self._submit()
+
+    def _submit(self):
+        segs, self.segs, self.count = self.segs, [], 0
+        self._drain(self.engine.slots - 1)
+        begin = np.concatenate([it.begin[s:e] for _, it, s, e in segs])
+        end = np.concatenate([it.end[s:e] for _, it, s, e in segs])
+        self.inflight.append((self.engine.submit_text(self.reader.data, begin, end), segs))
+
+    def _drain(self, limit):
+        while len(self.inflight) > limit:
+            ticket, segs = self.inflight.popleft()
+            try:
+                act, pred, kmer, _, info, info_off = self.engine.wait_text(ticket)
+            except ValueError as exc:
+                row = getattr(exc, "row", -1)
+                for _, it, s, e in segs:       # the message the host route gives for this row (ds_io.cpp ds_tsv_parse_into)
+                    if 0 <= row < e - s:
+                        raise ValueError("feature file: %s: malformed feature row" % it.where(s + row))
+                    row -= e - s
+                raise
+            self._check_worker()
+            rows, out, o = _TicketRows(info, info_off, kmer), [], 0
+            for tag, _, s, e in segs:
+                out.append((tag, rows, o, o + e - s))
+                o += e - s
+            with self._qlock:
+                for seg in out:
+                    self._queued[seg[0]] = self._queued.get(seg[0], 0) + 1
+            self._outq.put((out, act, pred))
+
+
+def _check_parse_on(parse_on, input_path, native_io, engine):
+    """Usage errors of parse_on (raised before any GPU work when the engine is not built yet)."""
+    if parse_on not in ("cpu", "gpu"):
+        raise ValueError("parse_on must be 'cpu' or 'gpu'")
+    if parse_on == "gpu":
+        if os.path.isdir(input_path):
+            raise ValueError("parse_on='gpu' reads a feature file; %s is a directory (fast5 input: see extract_on)" % input_path)
+        if not native_io:
+            raise ValueError("parse_on='gpu' uses the native feature reader (native_io=True)")
+        if engine is not None and not (hasattr(engine, "submit_text") and hasattr(engine, "wait_text")):
+            raise ValueError("parse_on='gpu' needs an engine with submit_text / wait_text")
+
+
 def _prefetch(iterable, depth=3):
     """Run `iterable` on a helper thread (the native parser releases the GIL), a bounded queue ahead of the consumer.
     The producer has always EXITED when this generator is finished or closed -- also when the consumer stops early
@@ -477,7 +551,7 @@ def _local_world(world):
 
 
 def _call_mods_sharded(input_path, engine, batch_size, result_file, kmer_len, cent_signals_len, f5_batch_num,
-                       dist, rank, world, device=None):
+                       dist, rank, world, device=None, parse_on="cpu"):
     """One process per GPU. Each rank parses ONLY its own byte ranges of the feature file (cut at read
     boundaries by ds_tsv_align, which every rank computes alike -- per-rank parsing cost is 1/world of the file),
     runs them on its own weight replica and formats its own rows; the rows go to rank 0 through
@@ -498,7 +572,7 @@ def _call_mods_sharded(input_path, engine, batch_size, result_file, kmer_len, ce
     def sink(tag, data):
         bufs[tag].append(data)
 
-    pipe = _RowPipeline(engine, batch_size, sink)
+    pipe = _TextPipeline(engine, batch_size, sink, reader) if parse_on == "gpu" else _RowPipeline(engine, batch_size, sink)
     # rows of chunk c are complete once everything fed up to the chunk's end has drained; with batches filled across
     # chunk borders that is known when a LATER batch drains, so hand chunks over lazily and flush at the very end
 
@@ -512,7 +586,7 @@ def _call_mods_sharded(input_path, engine, batch_size, result_file, kmer_len, ce
     def rows():
         for c in mine:
             reader.set_range(cuts[c], cuts[c + 1])
-            for item in reader.items(f5_batch_num):
+            for item in (reader.spans(f5_batch_num) if parse_on == "gpu" else reader.items(f5_batch_num)):
                 yield c, item
             yield c, None
 
@@ -549,7 +623,7 @@ def _call_mods_sharded(input_path, engine, batch_size, result_file, kmer_len, ce
 def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
               batch_size, learning_rate, class_num, nproc, is_gpu, is_rnn, is_base, is_cnn,
               f5_args, engine=None, f5_batch_num=None, native_io=True, precision="fp32", dist=None, force_sharded=False,
-              engine_batch=0, extract_on="cpu", recheck_margin=0.0, recheck_precision="fp32"):
+              engine_batch=0, extract_on="cpu", recheck_margin=0.0, recheck_precision="fp32", parse_on="cpu"):
     """The reference's call_mods (call_modifications.py:417-495), same signature and argument meaning.
 
     learning_rate / is_gpu are accepted for signature compatibility: inference ignores the learning rate
@@ -564,9 +638,12 @@ def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
     RCCL calls as eight. extract_on="gpu" (directory input only) computes the features of the fast5 route on the GPU
     (ds_submit_reads) instead of on the host. recheck_margin > 0 (with a bf16 `precision`): the sites whose |prob_1 - prob_0|
     comes out below it are run again in `recheck_precision` and take that result (make_engine); every rank of a multi-GPU run
-    builds its own pair."""
+    builds its own pair. parse_on="gpu" (feature-file input with the native reader only): the host only finds the rows; their
+    ~411 decimal tokens each are parsed on the GPU straight into the forward's inputs (ds_submit_text). Same output bytes: a
+    row in a form the device does not parse goes through the host parser, and a malformed row raises the same ValueError."""
     if extract_on not in ("cpu", "gpu"):
         raise ValueError("extract_on must be 'cpu' or 'gpu'")
+    _check_parse_on(parse_on, input_path, native_io, engine)
     if engine is None:
         check_recheck_args(precision, recheck_margin, recheck_precision)
     start = time.time()
@@ -588,6 +665,7 @@ def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
                              is_cnn=is_cnn, is_rnn=is_rnn, is_base=is_base, device=local, precision=precision,
                              engine_batch=engine_batch, recheck_margin=recheck_margin, recheck_precision=recheck_precision)
     recheck = None
+    text0 = engine.text_stats() if parse_on == "gpu" else None
     try:
         if os.path.isdir(input_path):
             nsites = _call_mods_from_fast5s(input_path, result_file, kmer_len, cent_signals_len, batch_size, f5, engine,
@@ -597,7 +675,7 @@ def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
             if not native_io:
                 raise ValueError("multi-GPU call_mods uses the native feature reader (native_io=True)")
             nsites = _call_mods_sharded(input_path, engine, batch_size, result_file, kmer_len, cent_signals_len,
-                                        f5.f5_batch_num, dist, rank, world, device)
+                                        f5.f5_batch_num, dist, rank, world, device, parse_on=parse_on)
         elif native_io:
             # row f1: native reader (host threads, one item ahead on a helper thread) + native row formatter;
             # same items, same row text
@@ -605,8 +683,12 @@ def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
             reader = fastio.FeatureReader(input_path, kmer_len, cent_signals_len)
             try:
                 with open(result_file, "wb") as wf:
-                    pipe = _RowPipeline(engine, batch_size, lambda tag, data: wf.write(data))
-                    items = _prefetch(reader.items(f5.f5_batch_num))
+                    if parse_on == "gpu":
+                        pipe = _TextPipeline(engine, batch_size, lambda tag, data: wf.write(data), reader)
+                        items = _prefetch(reader.spans(f5.f5_batch_num))
+                    else:
+                        pipe = _RowPipeline(engine, batch_size, lambda tag, data: wf.write(data))
+                        items = _prefetch(reader.items(f5.f5_batch_num))
                     try:
                         for item in items:
                             pipe.feed(item)
@@ -629,6 +711,12 @@ def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
                     nsites += len(pred_str)
         if own and recheck_margin > 0:
             recheck = engine.recheck_stats()
+        if text0 is not None:
+            text1 = engine.text_stats()
+            text0 = {k: text1[k] - text0[k] for k in text1}
+    except BaseException:
+        text0 = None
+        raise
     finally:
         if own:
             engine.close()
@@ -636,6 +724,8 @@ def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
         print("recheck%s: %d sites, %d rechecked in %s (margin %g), share %.4f"
               % (" (rank %d)" % rank if world > 1 else "", recheck["sites"], recheck["rechecked"], recheck_precision, recheck_margin,
                  recheck["rechecked"] / max(1, recheck["sites"])))
+    if text0 is not None:
+        print("parse_on gpu%s: %d rows, %d taken by the host parser" % (" (rank %d)" % rank if world > 1 else "", text0["rows"], text0["host_rows"]))
     if rank == 0:
         print("call_mods costs %.2f seconds.. (%d sites)" % (time.time() - start, nsites))
     return nsites

@@ -5,6 +5,7 @@
 #include "../../include/deepsignal_hip.h"
 #include "ds_internal.h"
 #include "ds_extract.h"
+#include "ds_tsv_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -167,6 +168,16 @@ struct Slot {
     hipEvent_t rc_ev[2] = {nullptr, nullptr};   // around recheck_select_kernel of a profiled forward (ds_get_recheck_times)
     bool rc_selected = false;             // the forward in flight carries a selection (a recheck was attached when it was submitted)
     bool rc_timed = false;
+    // ds_submit_text / ds_parse_text: allocated at the slot's first text call. pin_text / d_text = [int64 off[B] | int32 len[B] |
+    // the rows' text, DS_TEXT_BYTES_PER_ROW x B bytes and one parse step of pad]; d_tres / pin_tres = [status[B] | label[B] |
+    // info_len[B]], the pinned one followed by the k-mer codes [B][T]
+    bool text_ticket = false;             // the ticket in flight is a text ticket (ds_wait_text)
+    char* pin_text = nullptr;
+    char* d_text = nullptr;
+    int32_t* d_tres = nullptr;
+    int32_t* pin_tres = nullptr;
+    hipEvent_t tx_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // around the text's H2D, the parse kernel, the results' D2H
+    std::vector<std::pair<const char*, const char*>> text_rows;  // the caller's rows of the ticket in flight (info columns, host route)
 
     std::map<int, Plan> plans;
     int last_n = 0;
@@ -238,6 +249,9 @@ struct ds_handle {
     ds_handle* rc_fine = nullptr;
     float rc_margin = 0.f;
     int64_t rc_sites = 0, rc_rechecked = 0, rc_forwards = 0;      // since the attachment
+    int64_t tx_rows = 0, tx_host_rows = 0;   // rows through ds_submit_text / ds_parse_text, and those the host parser took
+    int64_t tx_batches = 0;               // text batches timed (every one: three event pairs per batch), and their summed device ms:
+    double tx_ms[3] = {0, 0, 0};          // H2D of the text, tsv_parse_kernel, D2H of status / label / info length / k-mer
     int64_t rc_launches = 0;              // recheck_select_kernel launches timed while profiling was on, and their summed device ms
     double rc_ms = 0;
     // pipelining: consecutive forwards rotate over independent slots (own workspace, streams, graphs), so the
@@ -1532,6 +1546,11 @@ void ds_destroy(ds_handle* h)
         if (sl.pin_act) hipHostFree(sl.pin_act);       // pin_pred points into it
         if (sl.d_rc) hipFree(sl.d_rc);
         if (sl.pin_rc) hipHostFree(sl.pin_rc);
+        if (sl.pin_text) hipHostFree(sl.pin_text);
+        if (sl.d_text) hipFree(sl.d_text);
+        if (sl.d_tres) hipFree(sl.d_tres);
+        if (sl.pin_tres) hipHostFree(sl.pin_tres);
+        for (hipEvent_t e : sl.tx_ev) if (e) hipEventDestroy(e);
         for (hipEvent_t e : sl.rc_ev) if (e) hipEventDestroy(e);
         if (sl.ev_fork) hipEventDestroy(sl.ev_fork);
         if (sl.ev_join) hipEventDestroy(sl.ev_join);
@@ -1692,6 +1711,7 @@ static int ds_forward_impl(ds_handle* h, int32_t n, const int32_t* kmer, const f
                 if (sl.s1) hipStreamSynchronize(sl.s1);
                 sl.submitted_n = -1;
                 sl.rows_ticket = false;
+                sl.text_ticket = false;
                 sl.rc_selected = false;
             }
             h->err = msg;
@@ -1980,7 +2000,8 @@ static int ds_submit_impl(ds_handle* h, int32_t n, const int32_t* kmer, const fl
 static int ds_wait_impl(ds_handle* h, int32_t ticket, float* act, int32_t* pred)
 {
     if (!h || !act || !pred) return DS_ERR_INVALID;
-    if (ticket < 0 || ticket >= (int)h->slots.size() || h->slots[ticket].submitted_n < 0 || h->slots[ticket].rows_ticket)
+    if (ticket < 0 || ticket >= (int)h->slots.size() || h->slots[ticket].submitted_n < 0 || h->slots[ticket].rows_ticket ||
+        h->slots[ticket].text_ticket)
         return fail(h, DS_ERR_INVALID, "ds_wait: no forward in flight for this ticket");
     Slot& sl = h->slots[ticket];
     HIPCHK(h, hipStreamSynchronize(sl.s0));
@@ -2097,6 +2118,301 @@ static int ds_submit_reads_impl(ds_handle* h, const ds_reads* r, int32_t* ticket
     HIPCHK(h, hipMemcpyAsync(sl.pin_act, sl.act, ((size_t)h->B * h->C + (size_t)n) * 4, hipMemcpyDeviceToHost, sl.s0));
     sl.submitted_n = n;
     *ticket = si;
+    return DS_OK;
+}
+
+// ---- feature-TSV rows parsed on the device (ds_tsv_parse.hip tsv_parse_kernel; call_mods --parse_on gpu) ----------------------------
+// The producer beside ds_submit_reads: the rows' text is packed into the slot's pinned block (16-byte aligned starts, an offset
+// and a length per row), copied to the device and parsed on sl.s0 into the slot's forward inputs; the forward, the recheck
+// selection and the copies back follow on the same stream. The host keeps only the rows' spans: ds_wait_text takes the six
+// leading columns from them, and parses the rows the device left to it (status ROW_HOST) with the reader's own parse_row.
+struct TxLayout { size_t len, text, text_cap, total; };      // byte offsets in Slot::pin_text / d_text
+static TxLayout tx_layout(const ds_handle* h)
+{
+    const size_t B = h->B;
+    TxLayout L;
+    L.len = B * 8;
+    L.text = (L.len + B * 4 + 15) & ~(size_t)15;
+    L.text_cap = B * (size_t)DS_TEXT_BYTES_PER_ROW;
+    L.total = L.text + L.text_cap + dst::STEP;               // the kernel looks at a row one step at a time: one step of pad
+    return L;
+}
+
+static int alloc_text(ds_handle* h, Slot& sl)
+{
+    if (!dst::parse_lds_bytes(h->T, h->S, nullptr))
+        return fail(h, DS_ERR_UNSUPPORTED, "text rows: the token table of kmer_len " + std::to_string(h->T) + " / signal_len " + std::to_string(h->S) +
+                    " does not fit the parse kernel's LDS");
+    const TxLayout L = tx_layout(h);
+    const size_t B = h->B;
+    auto dev = [&](void** p, size_t bytes) {
+        if (*p) return DS_OK;
+        hipError_t e = hipMalloc(p, bytes);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, DS_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+        return DS_OK;
+    };
+    if (!sl.pin_text) HIPCHK(h, hipHostMalloc((void**)&sl.pin_text, L.total, hipHostMallocDefault));
+    if (!sl.pin_tres) HIPCHK(h, hipHostMalloc((void**)&sl.pin_tres, (3 * B + B * (size_t)h->T) * 4, hipHostMallocDefault));
+    int rc = dev((void**)&sl.d_text, L.total);
+    if (!rc) rc = dev((void**)&sl.d_tres, 3 * B * 4);
+    if (rc) return rc;
+    for (hipEvent_t& e : sl.tx_ev)
+        if (!e) HIPCHK(h, hipEventCreate(&e));
+    if (!sl.pin_act) {       // ds_wait_text copies act / pred out of the pinned result block, as ds_wait
+        HIPCHK(h, hipHostMalloc((void**)&sl.pin_act, (B * h->C + B) * 4, hipHostMallocDefault));
+        sl.pin_pred = reinterpret_cast<int*>(sl.pin_act + B * h->C);
+    }
+    return DS_OK;
+}
+
+// rows -> the slot's pinned block, then on sl.s0: H2D of [offsets | lengths | text used] and the parse kernel (tx_ev[0 .. 2] around them)
+static int enqueue_parse(ds_handle* h, Slot& sl, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end)
+{
+    const TxLayout L = tx_layout(h);
+    int64_t* off = reinterpret_cast<int64_t*>(sl.pin_text);
+    int32_t* len = reinterpret_cast<int32_t*>(sl.pin_text + L.len);
+    char* dst_text = sl.pin_text + L.text;
+    sl.text_rows.resize((size_t)nrows);
+    size_t cur = 0;
+    for (int i = 0; i < nrows; ++i) {
+        if (begin[i] < 0 || end[i] < begin[i]) return fail(h, DS_ERR_INVALID, "text rows: row " + std::to_string(i) + " has a bad span");
+        const size_t n = (size_t)(end[i] - begin[i]);
+        sl.text_rows[(size_t)i] = {text + begin[i], text + end[i]};
+        if (n > L.text_cap - cur) {      // does not fit what is left of the block: the host parser takes it, nothing is copied
+            off[i] = 0; len[i] = -1;
+            continue;
+        }
+        memcpy(dst_text + cur, text + begin[i], n);
+        off[i] = (int64_t)cur; len[i] = (int32_t)n;
+        cur = std::min(L.text_cap, (cur + n + 15) & ~(size_t)15);
+    }
+    dst::ParseArgs a{};
+    a.text = sl.d_text + L.text;
+    a.off = reinterpret_cast<const int64_t*>(sl.d_text);
+    a.len = reinterpret_cast<const int32_t*>(sl.d_text + L.len);
+    a.kmer = sl.d_kmer; a.means = sl.d_means; a.stds = sl.d_stds; a.lens = sl.d_sanums; a.signals = sl.d_signals;
+    a.status = sl.d_tres; a.label = sl.d_tres + h->B; a.info_len = sl.d_tres + 2 * (size_t)h->B;
+    a.n = nrows; a.K = h->T; a.S = h->S;
+    HIPCHK(h, hipEventRecord(sl.tx_ev[0], sl.s0));
+    HIPCHK(h, hipMemcpyAsync(sl.d_text, sl.pin_text, L.text + cur, hipMemcpyHostToDevice, sl.s0));
+    HIPCHK(h, hipEventRecord(sl.tx_ev[1], sl.s0));
+    HIPCHK(h, dst::launch_parse(a, sl.s0));
+    HIPCHK(h, hipEventRecord(sl.tx_ev[2], sl.s0));
+    return DS_OK;
+}
+
+// sl.s0 is drained: the three event pairs of the slot's text batch into the handle's sums
+static void book_text_times(ds_handle* h, Slot& sl)
+{
+    float ms[3] = {0, 0, 0};
+    if (hipEventElapsedTime(&ms[0], sl.tx_ev[0], sl.tx_ev[1]) != hipSuccess || hipEventElapsedTime(&ms[1], sl.tx_ev[1], sl.tx_ev[2]) != hipSuccess ||
+        hipEventElapsedTime(&ms[2], sl.tx_ev[3], sl.tx_ev[4]) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+    }
+    h->tx_batches += 1;
+    for (int i = 0; i < 3; ++i) h->tx_ms[i] += ms[i];
+}
+
+static int check_text_args(ds_handle* h, const char* what, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end)
+{
+    if (!text || !begin || !end) return fail(h, DS_ERR_INVALID, std::string(what) + ": null argument");
+    if (nrows < 1 || nrows > h->B) return fail(h, DS_ERR_INVALID, std::string(what) + ": nrows must be in [1, max_batch]");
+    return DS_OK;
+}
+
+static int ds_submit_text_impl(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, int32_t* ticket)
+{
+    if (!h || !ticket) return DS_ERR_INVALID;
+    if (!h->finalized) return fail(h, DS_ERR_INVALID, "weights not loaded");
+    if (h->profiling) return fail(h, DS_ERR_INVALID, "ds_submit_text is not available while profiling is on");
+    int rc = check_text_args(h, "ds_submit_text", text, nrows, begin, end);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int si = (int)(h->next_slot % h->slots.size());
+    Slot& sl = h->slots[si];
+    if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_submit_text: every slot is in flight; wait the oldest ticket first");
+    rc = alloc_text(h, sl);
+    if (rc) return rc;
+    rc = enqueue_parse(h, sl, text, nrows, begin, end);
+    if (rc) return rc;
+    h->next_slot++;
+    h->cur = &sl;
+    const int n = nrows;
+    const size_t B = h->B;
+    rc = run_resident(h, n);
+    if (rc) return rc;
+    rc = enqueue_recheck(h, sl, n);
+    if (rc) return rc;
+    HIPCHK(h, hipEventRecord(sl.tx_ev[3], sl.s0));
+    HIPCHK(h, hipMemcpyAsync(sl.pin_tres, sl.d_tres, 3 * B * 4, hipMemcpyDeviceToHost, sl.s0));
+    HIPCHK(h, hipMemcpyAsync(sl.pin_tres + 3 * B, sl.d_kmer, (size_t)n * h->T * 4, hipMemcpyDeviceToHost, sl.s0));
+    HIPCHK(h, hipEventRecord(sl.tx_ev[4], sl.s0));
+    HIPCHK(h, hipMemcpyAsync(sl.pin_act, sl.act, (B * h->C + (size_t)n) * 4, hipMemcpyDeviceToHost, sl.s0));
+    sl.submitted_n = n;
+    sl.text_ticket = true;
+    *ticket = si;
+    return DS_OK;
+}
+
+// m host arrays through the forward on the idle slot sl, by the steps ds_forward's passes take (pinned staging, H2D, forward,
+// recheck selection, one copy back, merge of the rechecks)
+static int forward_on_slot(ds_handle* h, Slot& sl, int m, const int32_t* kmer, const float* means, const float* stds, const float* sanums,
+                           const float* signals, float* act, int32_t* pred)
+{
+    const size_t B = h->B, T = h->T, S = h->S;
+    if (!sl.pin_in) HIPCHK(h, hipHostMalloc((void**)&sl.pin_in, B * (4 * T * 4 + S * 4), hipHostMallocDefault));
+    const size_t nt = (size_t)m * T * 4, ns = (size_t)m * S * 4;
+    char* p = sl.pin_in;
+    memcpy(p, kmer, nt);
+    memcpy(p + B * T * 4, means, nt);
+    memcpy(p + 2 * B * T * 4, stds, nt);
+    memcpy(p + 3 * B * T * 4, sanums, nt);
+    memcpy(p + 4 * B * T * 4, signals, ns);
+    HIPCHK(h, hipMemcpyAsync(sl.d_kmer, p, nt, hipMemcpyHostToDevice, sl.s0));
+    HIPCHK(h, hipMemcpyAsync(sl.d_means, p + B * T * 4, nt, hipMemcpyHostToDevice, sl.s0));
+    HIPCHK(h, hipMemcpyAsync(sl.d_stds, p + 2 * B * T * 4, nt, hipMemcpyHostToDevice, sl.s0));
+    HIPCHK(h, hipMemcpyAsync(sl.d_sanums, p + 3 * B * T * 4, nt, hipMemcpyHostToDevice, sl.s0));
+    HIPCHK(h, hipMemcpyAsync(sl.d_signals, p + 4 * B * T * 4, ns, hipMemcpyHostToDevice, sl.s0));
+    h->cur = &sl;
+    int rc = run_resident(h, m);
+    if (rc) return rc;
+    rc = enqueue_recheck(h, sl, m);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(sl.pin_act, sl.act, (B * h->C + (size_t)m) * 4, hipMemcpyDeviceToHost, sl.s0));
+    HIPCHK(h, hipStreamSynchronize(sl.s0));
+    memcpy(act, sl.pin_act, (size_t)m * h->C * 4);
+    memcpy(pred, sl.pin_pred, (size_t)m * 4);
+    return finish_recheck(h, sl, m, act, pred);
+}
+
+static int ds_wait_text_impl(ds_handle* h, int32_t ticket, float* act, int32_t* pred, int32_t* kmer, int32_t* labels, char* info,
+                             int64_t info_cap, int64_t* info_off)
+{
+    if (!h || !act || !pred || !kmer || !labels || !info || !info_off) return DS_ERR_INVALID;
+    if (ticket < 0 || ticket >= (int)h->slots.size() || h->slots[ticket].submitted_n < 0 || !h->slots[ticket].text_ticket)
+        return fail(h, DS_ERR_INVALID, "ds_wait_text: no text rows in flight for this ticket");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    Slot& sl = h->slots[ticket];
+    HIPCHK(h, hipStreamSynchronize(sl.s0));
+    const int n = sl.submitted_n;
+    const size_t B = h->B, T = h->T, S = h->S, C = h->C;
+    memcpy(act, sl.pin_act, (size_t)n * C * 4);
+    memcpy(pred, sl.pin_pred, (size_t)n * 4);
+    sl.submitted_n = -1;
+    sl.text_ticket = false;
+    int rc = finish_recheck(h, sl, n, act, pred);
+    if (rc) return rc;
+    book_text_times(h, sl);
+    const int32_t* status = sl.pin_tres;
+    memcpy(labels, sl.pin_tres + B, (size_t)n * 4);
+    memcpy(kmer, sl.pin_tres + 3 * B, (size_t)n * T * 4);
+    std::vector<int64_t> ilen((size_t)n);
+    std::vector<int> host_rows;
+    for (int i = 0; i < n; ++i) {
+        ilen[(size_t)i] = sl.pin_tres[2 * B + (size_t)i];
+        if (status[i] != dst::ROW_OK) host_rows.push_back(i);
+    }
+    h->tx_rows += n;
+    h->tx_host_rows += (int64_t)host_rows.size();
+    if (!host_rows.empty()) {
+        // the forms the device does not parse: the reader's own row parser decides, and what it accepts is forwarded once on this
+        // slot (idle now); an attached recheck applies to it as to any forward
+        const size_t m = host_rows.size();
+        std::vector<int32_t> hk(m * T), hlab(m), hpred(m);
+        std::vector<float> hm(m * T), hs(m * T), hl(m * T), hsig(m * S), hact(m * C);
+        for (size_t k = 0; k < m; ++k) {
+            const auto& row = sl.text_rows[(size_t)host_rows[k]];
+            if (!ds_io::parse_row_host(h->T, h->S, row.first, row.second, &hk[k * T], &hm[k * T], &hs[k * T], &hl[k * T], &hsig[k * S], &hlab[k],
+                                       &ilen[(size_t)host_rows[k]]))
+                return fail(h, DS_ERR_IO, "ds_wait_text: row " + std::to_string(host_rows[k]) + " of the ticket: malformed feature row");
+        }
+        rc = forward_on_slot(h, sl, (int)m, hk.data(), hm.data(), hs.data(), hl.data(), hsig.data(), hact.data(), hpred.data());
+        if (rc) return rc;
+        for (size_t k = 0; k < m; ++k) {
+            const size_t i = (size_t)host_rows[k];
+            memcpy(act + i * C, &hact[k * C], C * 4);
+            pred[i] = hpred[k];
+            memcpy(kmer + i * T, &hk[k * T], T * 4);
+            labels[i] = hlab[k];
+        }
+    }
+    int64_t tot = 0;
+    for (int i = 0; i < n; ++i) {
+        const auto& row = sl.text_rows[(size_t)i];
+        if (ilen[(size_t)i] < 0 || ilen[(size_t)i] > row.second - row.first) return fail(h, DS_ERR_INVALID, "ds_wait_text: info length out of range");
+        info_off[i] = tot;
+        tot += ilen[(size_t)i];
+    }
+    info_off[n] = tot;
+    if (tot > info_cap) return fail(h, DS_ERR_INVALID, "ds_wait_text: info buffer too small (" + std::to_string(tot) + " bytes needed)");
+    for (int i = 0; i < n; ++i) memcpy(info + info_off[i], sl.text_rows[(size_t)i].first, (size_t)ilen[(size_t)i]);
+    return DS_OK;
+}
+
+// Blocking diagnostic on an idle slot (not advanced, as ds_extract): the device's arrays and per-row status, no forward
+static int ds_parse_text_impl(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, int32_t* kmer,
+                              float* means, float* stds, float* lens, float* signals, int32_t* labels, int32_t* info_len, int32_t* status)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (!kmer || !means || !stds || !lens || !signals || !labels || !status) return fail(h, DS_ERR_INVALID, "null buffer");
+    int rc = check_text_args(h, "ds_parse_text", text, nrows, begin, end);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    Slot& sl = h->slots[h->next_slot % h->slots.size()];
+    if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_parse_text: every slot is in flight; wait the oldest ticket first");
+    rc = alloc_text(h, sl);
+    if (rc) return rc;
+    rc = enqueue_parse(h, sl, text, nrows, begin, end);
+    if (rc) return rc;
+    const size_t B = h->B, T = h->T, n = (size_t)nrows;
+    auto d2h = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sl.s0); };
+    hipError_t e = hipEventRecord(sl.tx_ev[3], sl.s0);
+    if (e == hipSuccess) e = d2h(sl.pin_tres, sl.d_tres, 3 * B * 4);
+    if (e == hipSuccess) e = d2h(sl.pin_tres + 3 * B, sl.d_kmer, n * T * 4);
+    if (e == hipSuccess) e = hipEventRecord(sl.tx_ev[4], sl.s0);
+    if (e == hipSuccess) e = d2h(means, sl.d_means, n * T * 4);
+    if (e == hipSuccess) e = d2h(stds, sl.d_stds, n * T * 4);
+    if (e == hipSuccess) e = d2h(lens, sl.d_sanums, n * T * 4);
+    if (e == hipSuccess) e = d2h(signals, sl.d_signals, n * (size_t)h->S * 4);
+    if (e == hipSuccess) e = hipStreamSynchronize(sl.s0);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, DS_ERR_HIP, std::string("ds_parse_text: ") + hipGetErrorString(e)); }
+    book_text_times(h, sl);
+    memcpy(status, sl.pin_tres, n * 4);
+    memcpy(labels, sl.pin_tres + B, n * 4);
+    if (info_len) memcpy(info_len, sl.pin_tres + 2 * B, n * 4);
+    memcpy(kmer, sl.pin_tres + 3 * B, n * T * 4);
+    return DS_OK;
+}
+
+int ds_parse_text_reference(int32_t kmer_len, int32_t signal_len, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end,
+                            int32_t* kmer, float* means, float* stds, float* lens, float* signals, int32_t* labels, int32_t* info_len,
+                            int32_t* status)
+{
+    if (nrows == 0) return DS_OK;
+    if (kmer_len < 1 || signal_len < 1 || nrows < 0 || !text || !begin || !end || !kmer || !means || !stds || !lens || !signals || !labels ||
+        !info_len || !status)
+        return fail(nullptr, DS_ERR_INVALID, "ds_parse_text_reference: bad argument");
+    for (int i = 0; i < nrows; ++i)
+        if (begin[i] < 0 || end[i] < begin[i]) return fail(nullptr, DS_ERR_INVALID, "ds_parse_text_reference: row " + std::to_string(i) + " has a bad span");
+    dst::parse_reference(kmer_len, signal_len, text, nrows, begin, end, kmer, means, stds, lens, signals, labels, info_len, status);
+    return DS_OK;
+}
+
+int ds_get_text_stats(ds_handle* h, int64_t* rows, int64_t* host_rows)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (rows) *rows = h->tx_rows;
+    if (host_rows) *host_rows = h->tx_host_rows;
+    return DS_OK;
+}
+
+int ds_get_text_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms)
+{
+    if (!h || !batches || !ms) return DS_ERR_INVALID;
+    *batches = h->tx_batches;
+    for (int i = 0; i < 3; ++i) ms[i] = h->tx_ms[i];
+    if (reset) { h->tx_batches = 0; for (double& v : h->tx_ms) v = 0; }
     return DS_OK;
 }
 
@@ -2590,4 +2906,7 @@ int64_t ds_extract_rows(ds_handle* h, const ds_reads* reads, const char* info, c
 int ds_set_recheck(ds_handle* coarse, ds_handle* fine, float margin) { return guarded(coarse, [&] { return ds_set_recheck_impl(coarse, fine, margin); }); }
 int ds_recheck_select(ds_handle* h, int32_t n, const float* act, float margin, int32_t* count, int32_t* index) { return guarded(h, [&] { return ds_recheck_select_impl(h, n, act, margin, count, index); }); }
 int64_t ds_format_values(ds_handle* h, int64_t n, const double* values, char* out, int64_t cap) { return guarded(h, [&] { return ds_format_values_impl(h, n, values, out, cap); }); }
+int ds_submit_text(ds_handle* h, const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, int32_t* ticket) { return guarded(h, [&] { return ds_submit_text_impl(h, text, nrows, row_begin, row_end, ticket); }); }
+int ds_wait_text(ds_handle* h, int32_t ticket, float* act, int32_t* pred, int32_t* kmer, int32_t* labels, char* info, int64_t info_cap, int64_t* info_off) { return guarded(h, [&] { return ds_wait_text_impl(h, ticket, act, pred, kmer, labels, info, info_cap, info_off); }); }
+int ds_parse_text(ds_handle* h, const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, int32_t* kmer, float* means, float* stds, float* lens, float* signals, int32_t* labels, int32_t* info_len, int32_t* status) { return guarded(h, [&] { return ds_parse_text_impl(h, text, nrows, row_begin, row_end, kmer, means, stds, lens, signals, labels, info_len, status); }); }
 }  // extern "C"

@@ -395,6 +395,18 @@ void scan_lines(ds_tsv* t)
 }
 }  // namespace
 
+// parse_row for a caller without a reader (ds_wait_text: the rows the device left to the host); declared in ds_tsv_device.h
+namespace ds_io {
+bool parse_row_host(int kmer_len, int signal_len, const char* b, const char* e, int32_t* kmer, float* means, float* stds, float* lens,
+                    float* signals, int32_t* label, int64_t* info_len)
+{
+    ds_tsv t;                    // no mapped file: tokens go through the byte loop (no 17-byte look-ahead)
+    t.kmer_len = kmer_len; t.signal_len = signal_len;
+    const RowDest dest{kmer, means, stds, lens, signals, label};
+    return parse_row(&t, dest, 0, b, e, info_len);
+}
+}  // namespace ds_io
+
 extern "C" {
 
 int ds_tsv_open(const char* path, int32_t kmer_len, int32_t signal_len, int32_t nthreads, ds_tsv** out)
@@ -543,6 +555,30 @@ int64_t ds_tsv_next(ds_tsv* t, int32_t max_reads)
     t->signals.resize(m * S); t->labels.resize(m);
     return ds_tsv_parse_into(t, n, t->kmer.data(), t->means.data(), t->stds.data(), t->lens.data(), t->signals.data(), t->labels.data());
 }
+
+// The other consumer of a located item (call_mods --parse_on gpu): hand the rows out as byte spans of the mapped file
+// (ds_tsv_data) instead of parsing them. Like ds_tsv_parse_into it is the one consumer of its ds_tsv_locate() and advances the
+// row count that error messages name.
+int64_t ds_tsv_take_lines(ds_tsv* t, int64_t capacity_rows, int64_t* begin, int64_t* end)
+{
+    if (!t) return DS_ERR_INVALID;
+    const size_t n = t->lines.size();
+    if (n == 0) return 0;
+    if (capacity_rows < (int64_t)n) {
+        t->err = "ds_tsv_take_lines: the caller's arrays hold " + std::to_string(capacity_rows) + " rows, the located item has " + std::to_string(n);
+        return DS_ERR_INVALID;
+    }
+    if (!begin || !end) return DS_ERR_INVALID;
+    for (size_t i = 0; i < n; ++i) {
+        begin[i] = (int64_t)(t->lines[i].first - t->data);
+        end[i] = (int64_t)(t->lines[i].second - t->data);
+    }
+    t->line_no += (int64_t)n;
+    t->lines.clear();
+    return (int64_t)n;
+}
+
+const char* ds_tsv_data(const ds_tsv* t) { return t ? t->data : nullptr; }
 
 int64_t ds_tsv_size(const ds_tsv* t) { return t ? (int64_t)t->size : DS_ERR_INVALID; }
 

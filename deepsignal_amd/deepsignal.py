@@ -25,7 +25,7 @@ def main_call_mods(args):
               args.batch_size, args.learning_rate, args.class_num, args.nproc, str2bool(args.is_gpu),
               str2bool(args.is_rnn), str2bool(args.is_base), str2bool(args.is_cnn), f5_args,
               precision=args.precision, engine_batch=args.engine_batch, extract_on=args.extract_on,
-              recheck_margin=args.recheck_margin, recheck_precision=args.recheck_precision)
+              recheck_margin=args.recheck_margin, recheck_precision=args.recheck_precision, parse_on=args.parse_on)
 
 
 def main_extraction(args):
@@ -95,6 +95,10 @@ def build_parser():
                    help="fast5-directory input only: compute the per-site features on the host (cpu, default) or on the GPU next "
                         "to the forward (gpu; same features bit for bit, except that a middle base of >= cent_signals_len samples "
                         "is subsampled by a seeded hash instead of Python's unseeded random)")
+    g.add_argument("--parse_on", default="cpu", choices=["cpu", "gpu"],
+                   help="feature-file input only: parse the rows' numbers on the host threads (cpu, default) or on the GPU straight "
+                        "into the forward's inputs (gpu; the host only finds the rows). Same output bytes: rows in a form the device "
+                        "does not parse go through the host parser")
     g.add_argument("--engine_batch", type=int, default=0,
                    help="sites per GPU forward the engine is created for (default 0: the larger of --batch_size and 4096; results do "
                         "not depend on it, device and pinned memory grow with it -- lower it on a small or shared GPU; the "

@@ -41,6 +41,9 @@ EXPORTED_SYMBOLS = (
     "ds_submit_rows", "ds_wait_rows", "ds_extract_rows", "ds_extract_rows_reference", "ds_format_values", "ds_get_rows_times",
     # cascaded precision (a fine handle rechecks the near-threshold sites of a coarse one)
     "ds_set_recheck", "ds_get_recheck_stats", "ds_get_recheck_times", "ds_recheck_select",
+    # feature-TSV rows parsed on the device (call_mods --parse_on gpu)
+    "ds_submit_text", "ds_wait_text", "ds_parse_text", "ds_parse_text_reference", "ds_get_text_stats", "ds_get_text_times",
+    "ds_tsv_take_lines", "ds_tsv_data",
 )
 
 
@@ -172,6 +175,57 @@ def format_values(values, engine: Optional["Engine"] = None, cap: Optional[int] 
     return buf[:got].tobytes()
 
 
+TEXT_ROW_OK, TEXT_ROW_HOST = 0, 1      # DS_TEXT_ROW_*: per-row status of the device's TSV parser
+
+
+class TextRowError(ValueError):
+    """wait_text: a row the device left to the host parser is malformed; `row` = its index within the ticket."""
+
+    def __init__(self, row: int, message: str):
+        ValueError.__init__(self, message)
+        self.row = row
+
+
+def _text_args(text, begin, end):
+    """(keep-alive object, address) of a text buffer given as bytes / a uint8 array / a raw address, and the int64 span arrays."""
+    begin = np.ascontiguousarray(begin, np.int64)
+    end = np.ascontiguousarray(end, np.int64)
+    if begin.ndim != 1 or begin.shape != end.shape:
+        raise ValueError("begin / end must be 1-d arrays of one length")
+    if isinstance(text, (int, np.integer)):
+        return None, int(text), begin, end
+    if isinstance(text, (bytes, bytearray)):
+        text = np.frombuffer(text, np.uint8)
+    text = np.ascontiguousarray(text, np.uint8)
+    if begin.size and (int(begin.min()) < 0 or int(end.max()) > text.size or bool((end < begin).any())):
+        raise ValueError("row spans outside the text")
+    return text, text.ctypes.data, begin, end
+
+
+def _text_arrays(n: int, kmer_len: int, signal_len: int):
+    out = _feature_arrays(n, kmer_len, signal_len)
+    out["lens"] = out.pop("sanums")
+    out.update(labels=np.empty(n, np.int32), info_len=np.empty(n, np.int32), status=np.empty(n, np.int32))
+    return out
+
+
+_TEXT_ORDER = ("kmer", "means", "stds", "lens", "signals", "labels", "info_len", "status")
+
+
+def parse_text_reference(text, begin, end, kmer_len: int = 17, signal_len: int = 360) -> Dict[str, np.ndarray]:
+    """ds_parse_text_reference: the device's TSV row parser on the CPU, from the same token routines -> kmer, means, stds, lens,
+    signals, labels, info_len, status (TEXT_ROW_OK / TEXT_ROW_HOST; the values of a HOST row are unspecified). A checker for
+    the tests (no GPU needed), not a fall-back."""
+    lib = load_library()
+    keep, addr, begin, end = _text_args(text, begin, end)
+    out = _text_arrays(begin.size, kmer_len, signal_len)
+    rc = lib.ds_parse_text_reference(kmer_len, signal_len, addr, begin.size, begin.ctypes.data, end.ctypes.data,
+                                     *(out[k].ctypes.data for k in _TEXT_ORDER))
+    if rc != 0:
+        raise RuntimeError("ds_parse_text_reference failed (%d): %s" % (rc, lib.ds_last_error(None).decode()))
+    return out
+
+
 # ds_config.precision (include/deepsignal_hip.h): "bf16" = bf16 conv + FC operands with fp32 accumulation, fp32 BiLSTM;
 # "bf16_all" = also bf16 h / weight operands in the LSTM matmuls (fp32 accumulate, gates, cell state)
 PRECISIONS = {"fp32": 0, "bf16": 1, "bf16_all": 2, "bf16x3": 3}
@@ -268,6 +322,12 @@ def load_library() -> ctypes.CDLL:
     lib.ds_recheck_select.argtypes = [vp, i32, vp, ctypes.c_float, ctypes.POINTER(i32), vp]
     lib.ds_get_kernel_stat.argtypes = [vp, i32, ctypes.c_char_p, i32, ctypes.POINTER(i64),
                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
+    lib.ds_submit_text.argtypes = [vp, vp, i32, vp, vp, ctypes.POINTER(i32)]
+    lib.ds_wait_text.argtypes = [vp, i32, vp, vp, vp, vp, vp, i64, vp]
+    lib.ds_parse_text.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.ds_parse_text_reference.argtypes = [i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.ds_get_text_stats.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    lib.ds_get_text_times.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_double)]
     _lib = lib
     return lib
 
@@ -455,6 +515,58 @@ class Engine:
             getattr(self, "_rows_buf", None))
         self._check(got, "ds_extract_rows")
         return self._rows_buf[:got].tobytes(), row_off
+
+    # -- feature-TSV rows parsed on the device (ds_submit_text / ds_wait_text) -------------------
+    def submit_text(self, text, begin, end):
+        """ds_submit_text: the rows text[begin[i]:end[i]] (bytes, a uint8 array, or the address of a buffer such as
+        FeatureReader.data) parsed on the GPU straight into a forward's inputs; a ticket for wait_text(). The text must stay
+        alive and unchanged until then (an array given here is kept referenced by the ticket)."""
+        keep, addr, begin, end = _text_args(text, begin, end)
+        t = ctypes.c_int32()
+        self._check(self._lib.ds_submit_text(self._h, addr, begin.size, begin.ctypes.data, end.ctypes.data, ctypes.byref(t)),
+                    "ds_submit_text")
+        return (int(t.value), int(begin.size), int((end - begin).sum()), keep)
+
+    def wait_text(self, ticket):
+        """ds_wait_text -> (act, pred, kmer, labels, info uint8 blob, info_off int64[n + 1]): wait()'s results plus what
+        fastio.format_rows needs. Rows outside the device's grammar were parsed by the host parser and forwarded again; a
+        malformed one raises TextRowError (its .row = the index within the ticket)."""
+        slot, n, nbytes = ticket[0], ticket[1], ticket[2]
+        act = np.empty((n, self.class_num), np.float32)
+        pred, labels = np.empty((n,), np.int32), np.empty((n,), np.int32)
+        kmer = np.empty((n, self.kmer_len), np.int32)
+        info = np.empty(max(1, nbytes), np.uint8)
+        info_off = np.empty(n + 1, np.int64)
+        rc = self._lib.ds_wait_text(self._h, slot, act.ctypes.data, pred.ctypes.data, kmer.ctypes.data, labels.ctypes.data,
+                                    info.ctypes.data, info.size, info_off.ctypes.data)
+        if rc == -3:
+            import re
+            msg = self._lib.ds_last_error(self._h).decode()
+            m = re.search(r"row (\d+) of the ticket", msg)
+            raise TextRowError(int(m.group(1)) if m else -1, msg)
+        self._check(rc, "ds_wait_text")
+        return act, pred, kmer, labels, info[:int(info_off[n])], info_off
+
+    def parse_text(self, text, begin, end) -> Dict[str, np.ndarray]:
+        """ds_parse_text (diagnostic, needs no weights): the device parser's arrays and per-row status, as parse_text_reference."""
+        keep, addr, begin, end = _text_args(text, begin, end)
+        out = _text_arrays(begin.size, self.kmer_len, self.signal_len)
+        self._check(self._lib.ds_parse_text(self._h, addr, begin.size, begin.ctypes.data, end.ctypes.data,
+                                            *(out[k].ctypes.data for k in _TEXT_ORDER)), "ds_parse_text")
+        return out
+
+    def text_stats(self) -> dict:
+        """ds_get_text_stats: rows through submit_text / wait_text since construction, and those the host parser took."""
+        a, b = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._lib.ds_get_text_stats(self._h, ctypes.byref(a), ctypes.byref(b)), "ds_get_text_stats")
+        return {"rows": int(a.value), "host_rows": int(b.value)}
+
+    def text_times(self, reset: bool = False) -> dict:
+        """ds_get_text_times: device milliseconds of the text batches so far (H2D of the text, the parse kernel, D2H)."""
+        n = ctypes.c_int64()
+        ms = (ctypes.c_double * 3)()
+        self._check(self._lib.ds_get_text_times(self._h, int(reset), ctypes.byref(n), ms), "ds_get_text_times")
+        return dict(zip(("h2d_ms", "kernel_ms", "d2h_ms"), ms), batches=int(n.value))
 
     def rows_times(self, reset: bool = False) -> dict:
         """ds_get_rows_times: device milliseconds of the extract_rows() calls made while profiling was on."""

@@ -53,6 +53,21 @@ class FeatureItem(NamedTuple):
                 self.lens.astype(np.int64).tolist(), self.signals.tolist(), self.labels.tolist())
 
 
+class SpanItem(NamedTuple):
+    """One queue item located but not parsed (FeatureReader.spans): row i is the bytes [begin[i], end[i]) of the mapped file."""
+    begin: np.ndarray         # int64[n]
+    end: np.ndarray           # int64[n]
+    first_row: int            # rows the reader handed out before this item (since open / set_range): what error messages count from
+    range: tuple              # (range begin, range end, file size) the reader was restricted to when the item was located
+
+    def where(self, i: int) -> str:
+        """Row i as the native reader's error messages name it (ds_io.cpp row_where)."""
+        w = "row %d" % (self.first_row + i + 1)
+        if self.range[0] != 0 or self.range[1] != self.range[2]:
+            w += " of the byte range [%d, %d)" % (self.range[0], self.range[1])
+        return w + " (line at byte offset %d)" % int(self.begin[i])
+
+
 def _bind():
     lib = load_library()
     if getattr(lib, "_io_bound", False):
@@ -73,6 +88,10 @@ def _bind():
         f = getattr(lib, "ds_tsv_" + name)
         f.argtypes = [vp]
         f.restype = vp
+    lib.ds_tsv_take_lines.argtypes = [vp, i64, vp, vp]
+    lib.ds_tsv_take_lines.restype = i64
+    lib.ds_tsv_data.argtypes = [vp]
+    lib.ds_tsv_data.restype = vp
     lib.ds_tsv_size.argtypes = [vp]
     lib.ds_tsv_size.restype = i64
     lib.ds_tsv_align.argtypes = [vp, i64]
@@ -100,6 +119,12 @@ class FeatureReader:
         if rc != 0:
             raise IOError("cannot open feature file %s (%d)" % (path, rc))
         self.kmer_len, self.signal_len = kmer_len, signal_len
+        self._range, self._rows_out = None, 0       # for spans(): the byte range in force and the rows handed out in it
+
+    @property
+    def data(self) -> int:
+        """Address of the mapped file (ds_tsv_data): the text buffer the spans of spans() index; valid until close()."""
+        return int(self._lib.ds_tsv_data(self._h) or 0)
 
     def close(self):
         if self._h.value:
@@ -127,6 +152,7 @@ class FeatureReader:
         """Read rows of the byte range [begin, end) only (both ends from align())."""
         if self._lib.ds_tsv_set_range(self._h, int(begin), int(end)) != 0:
             raise ValueError("bad byte range [%d, %d)" % (begin, end))
+        self._range, self._rows_out = (int(begin), int(end)), 0
 
     def cut_points(self, nchunks: int) -> list:
         """nchunks + 1 byte offsets that tile the file into chunks of whole reads, near-equal in bytes."""
@@ -154,6 +180,25 @@ class FeatureReader:
                 raise ValueError("feature file: %s" % lib.ds_tsv_error(h).decode())
             off = _view(lib.ds_tsv_info_offsets(h), np.int64, (n + 1,))
             yield FeatureItem(_view(lib.ds_tsv_info(h), np.uint8, (int(off[-1]),)), off, kmer, means, stds, lens, signals, labels)
+
+
+    def spans(self, f5_batch_num: int = 50) -> Iterator[SpanItem]:
+        """The items of items(), located but NOT parsed: per item the rows' byte spans in the mapped file (`data`), for
+        Engine.submit_text (call_mods parse_on="gpu"). Same grouping, same order; use either items() or spans() on a range."""
+        lib, h = self._lib, self._h
+        size = self.size
+        while True:
+            n = lib.ds_tsv_locate(h, f5_batch_num)
+            if n < 0:
+                raise ValueError("feature file: %s" % lib.ds_tsv_error(h).decode())
+            if n == 0:
+                return
+            begin, end = np.empty(n, np.int64), np.empty(n, np.int64)
+            if lib.ds_tsv_take_lines(h, n, begin.ctypes.data, end.ctypes.data) != n:
+                raise ValueError("feature file: %s" % lib.ds_tsv_error(h).decode())
+            rng = self._range or (0, size)
+            yield SpanItem(begin, end, self._rows_out, (rng[0], rng[1], size))
+            self._rows_out += int(n)
 
 
 def format_rows(item_info: np.ndarray, info_off: np.ndarray, act: np.ndarray, pred: np.ndarray,

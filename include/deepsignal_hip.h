@@ -226,6 +226,13 @@ int64_t ds_tsv_next(ds_tsv *t, int32_t max_reads);
 int64_t ds_tsv_locate(ds_tsv *t, int32_t max_reads);
 int64_t ds_tsv_parse_into(ds_tsv *t, int64_t capacity_rows, int32_t *kmer, float *means, float *stds, float *lens, float *signals,
                           int32_t *labels);
+/* The other consumer of a located item (call_mods --parse_on gpu): the rows as byte spans [begin[i], end[i]) of the mapped file,
+ * ds_tsv_data(t), in file order ('\r'-trimmed, blank lines skipped), for ds_submit_text. It takes the place of ds_tsv_parse_into
+ * as the ONE consumer of its ds_tsv_locate() and advances the reader's row count the same way, so the row numbers of later error
+ * messages are unchanged. Returns n; DS_ERR_INVALID (nothing consumed) when capacity_rows < n. The spans stay valid until
+ * ds_tsv_close(). */
+int64_t ds_tsv_take_lines(ds_tsv *t, int64_t capacity_rows, int64_t *begin, int64_t *end);
+const char *ds_tsv_data(const ds_tsv *t);
 /* Multi-GPU call_mods (sites sharded BY READ): each rank parses only its own byte ranges of the file.
  * ds_tsv_align(t, pos) = the first read boundary at or after byte pos (start of the first line beginning at or after
  * pos whose read id differs from the line before it; 0 -> 0; file size when none follows), a function of the file
@@ -369,6 +376,52 @@ int ds_get_recheck_times(ds_handle *coarse, int32_t reset, int64_t *launches, do
  * of h's GPU: *count selected sites, index[0 .. *count) ascending. For directed values -- NaN, +-inf, every lane pattern --
  * that no forward produces on demand. Needs no weights and no attachment. */
 int ds_recheck_select(ds_handle *h, int32_t n, const float *act, float margin, int32_t *count, int32_t *index);
+
+/* ---- feature-TSV rows parsed on the device (ds_tsv_parse.hip; call_mods --parse_on gpu) -------------------------------------------
+ * The reader's decimal parsing (about 411 tokens a row) moved to the GPU: the host only finds the rows (ds_tsv_locate /
+ * ds_tsv_take_lines) and keeps their text for the six sampleinfo columns. Rows are spans text[row_begin[i] .. row_end[i]) of a host
+ * buffer, in the order their results are wanted; they need not be contiguous. 1 <= nrows <= max_batch.
+ * The device parses floats of the form [-]digits[.digits][e|E[+-]digits] with at most 15 significant digits and a net decimal
+ * exponent in [-22, 22] (one exact-operand IEEE double multiplication or division, then the float32 narrowing: strtod's bits) and
+ * integers [-]digits of at most 9 digits (event lengths, label; the label tolerates trailing '\r' and spaces). Every other row -- a
+ * leading '+', inf, nan, 1e400, a longer mantissa, any other byte, a wrong column or token count, a bad k-mer letter or length --
+ * is not an error on the device: its status is DS_TEXT_ROW_HOST and the host parser of ds_tsv_parse_into decides. Columns beyond
+ * the 12th are ignored.
+ *
+ * ds_submit_text: the asynchronous producer on the pipeline slots of ds_submit. The rows are packed into the slot's pinned text
+ * block, copied to the device and parsed there into the slot's forward inputs; forward, recheck selection and the copies back
+ * follow as in ds_submit. A slot's text blocks (pinned and device) are allocated at its first text call and hold
+ * max_batch x DS_TEXT_BYTES_PER_ROW bytes of text -- the typical 4 - 6 KB of a row, not the longest possible one; a row that does
+ * not fit what is left of the block is not copied and goes the host way. `text` must stay readable until the ticket is waited.
+ * ds_wait_text: act / pred as ds_wait, plus the rows' k-mer codes int32[n, kmer_len], labels int32[n] and the six leading
+ * columns packed into info (info_cap bytes) with int64 info_off[n + 1] -- the arguments of ds_format_rows. Rows with status
+ * DS_TEXT_ROW_HOST are parsed here by the host parser: a malformed one fails the call with DS_ERR_IO and ds_last_error names its
+ * index within the ticket ("row I of the ticket"); well-formed ones are forwarded once on the now idle slot by the steps of a
+ * ds_forward pass (an attached recheck applies to them too) and merged in, so the results equal the host route's for every row.
+ * A text ticket is waited with ds_wait_text only; a failed wait consumes the ticket. Same ticket order rules as ds_submit. */
+#define DS_TEXT_BYTES_PER_ROW 6144
+#define DS_TEXT_ROW_OK 0
+#define DS_TEXT_ROW_HOST 1
+int ds_submit_text(ds_handle *h, const char *text, int32_t nrows, const int64_t *row_begin, const int64_t *row_end, int32_t *ticket);
+int ds_wait_text(ds_handle *h, int32_t ticket, float *act, int32_t *pred, int32_t *kmer, int32_t *labels, char *info,
+                 int64_t info_cap, int64_t *info_off);
+/* The blocking diagnostic (ds_extract's counterpart) on an idle slot: the device's arrays -- kmer, means / stds / lens
+ * float[nrows, kmer_len], signals float[nrows, signal_len], labels, info_len (bytes of columns 0..5; may be NULL) -- and the
+ * per-row status, on the host. Needs no weights. The values of a DS_TEXT_ROW_HOST row are unspecified. */
+int ds_parse_text(ds_handle *h, const char *text, int32_t nrows, const int64_t *row_begin, const int64_t *row_end, int32_t *kmer,
+                  float *means, float *stds, float *lens, float *signals, int32_t *labels, int32_t *info_len, int32_t *status);
+/* The same call on the CPU from the same token routines (csrc/ds_tsv_device.h): a CHECKER like ds_extract_reference, no handle,
+ * no GPU, any nrows >= 0; not a fall-back. Errors leave their message in ds_last_error(NULL). */
+int ds_parse_text_reference(int32_t kmer_len, int32_t signal_len, const char *text, int32_t nrows, const int64_t *row_begin,
+                            const int64_t *row_end, int32_t *kmer, float *means, float *stds, float *lens, float *signals,
+                            int32_t *labels, int32_t *info_len, int32_t *status);
+/* Rows that went through ds_submit_text / ds_wait_text since ds_create, and how many of them the host parser took. */
+int ds_get_text_stats(ds_handle *h, int64_t *rows, int64_t *host_rows);
+/* Device milliseconds summed over *batches text batches (ds_submit_text tickets waited, ds_parse_text calls): ms[0] the text's
+ * host-to-device copy, ms[1] tsv_parse_kernel, ms[2] the device-to-host copy of status / label / info length / k-mer codes.
+ * Every batch is timed (three event pairs). reset != 0 clears the sums. Like the rows kernels, the kernel is not part of the
+ * positional ds_get_kernel_stat table. */
+int ds_get_text_times(ds_handle *h, int32_t reset, int64_t *batches, double *ms);
 
 /* Use a captured hipGraph for the forward (default on). */
 int ds_set_graph(ds_handle *h, int32_t enable);
