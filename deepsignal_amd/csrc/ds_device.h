@@ -6,9 +6,18 @@ namespace ds {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ float4 f4max(float4 a, float4 b)
+// Max-pool taps. Every pooled tensor of this network is a ReLU output (relu_f below: never negative, never -0.0), and for such
+// values the bit patterns order like UNSIGNED integers with every NaN -- of either sign, any payload -- above +inf: a NaN tap
+// wins the maximum and stays, as in F.max_pool1d, where fmaxf (IEEE maxNum) would drop it and hand the next layer a finite
+// number. One v_max_u32 per value; padded taps are skipped by the callers (an edge row is pooled with itself), 0 is the identity.
+__device__ __forceinline__ float relu_max(float a, float b)
 {
-    return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w));
+    const unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
+    return __uint_as_float(ua > ub ? ua : ub);
+}
+__device__ __forceinline__ float4 f4max_relu(float4 a, float4 b)
+{
+    return make_float4(relu_max(a.x, b.x), relu_max(a.y, b.y), relu_max(a.z, b.z), relu_max(a.w, b.w));
 }
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 // LSTM gate non-linearities on the hardware exp (v_exp_f32, ~1 ulp): abs error < 2e-7, far inside the
@@ -48,42 +57,30 @@ __device__ __forceinline__ float gload_at(const float* base, unsigned byte_off) 
 
 // ---- bf16 helpers (mixed-precision mode: bf16 operands, fp32 accumulate) ----
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-// max of two packed bf16 pairs; widening a bf16 to fp32 is a shift, and max returns one of its inputs, so
-// narrowing back by truncation is exact
-__device__ __forceinline__ float bf2max(float a, float b)
+// Max of packed bf16 ReLU outputs: the same unsigned order on 16-bit halves (0x7f81 .. 0x7fff and 0xff81 .. 0xffff, the NaNs,
+// lie above 0x7f80 = +inf; -0 and negative numbers never reach a pool). One v_pk_max_u16 per pair.
+typedef unsigned short ushort2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float bf2max_relu(float a, float b)
 {
-    const unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
-    const float lo = fmaxf(__uint_as_float(ua << 16), __uint_as_float(ub << 16));
-    const float hi = fmaxf(__uint_as_float(ua & 0xffff0000u), __uint_as_float(ub & 0xffff0000u));
-    return __uint_as_float((__float_as_uint(hi) & 0xffff0000u) | (__float_as_uint(lo) >> 16));
+    return __builtin_bit_cast(float, __builtin_elementwise_max(__builtin_bit_cast(ushort2v, a), __builtin_bit_cast(ushort2v, b)));
 }
-__device__ __forceinline__ float4 bf8max(float4 a, float4 b)
+__device__ __forceinline__ float4 bf8max_relu(float4 a, float4 b)
 {
-    return make_float4(bf2max(a.x, b.x), bf2max(a.y, b.y), bf2max(a.z, b.z), bf2max(a.w, b.w));
-}
-// Max of packed bf16 values that are all >= 0 (or -0): every pooled tensor of this network is a ReLU output, and for
-// non-negative floats the bit patterns order like signed 16-bit integers (-0 = 0x8000 is the smallest, so
-// max(-0, x) = x as it should). One v_pk_max_i16 per pair instead of ~9 VALU ops.
-typedef short short2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float bf2max_nn(float a, float b)
-{
-    return __builtin_bit_cast(float, __builtin_elementwise_max(__builtin_bit_cast(short2v, a), __builtin_bit_cast(short2v, b)));
-}
-__device__ __forceinline__ float4 bf8max_nn(float4 a, float4 b)
-{
-    return make_float4(bf2max_nn(a.x, b.x), bf2max_nn(a.y, b.y), bf2max_nn(a.z, b.z), bf2max_nn(a.w, b.w));
+    return make_float4(bf2max_relu(a.x, b.x), bf2max_relu(a.y, b.y), bf2max_relu(a.z, b.z), bf2max_relu(a.w, b.w));
 }
 __device__ __forceinline__ unsigned short f2bf(float v)     // round to nearest even (v_cvt_pk_bf16_f32)
 {
     return __builtin_bit_cast(unsigned short, (__bf16)v);
 }
 __device__ __forceinline__ float bf2f(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
-// relu on the bits: max(int(x), 0). One v_max_i32; relu_f(x) costs two instructions in IEEE mode (hipcc first quiets
-// a possible signalling NaN with v_max_f32 x, x). Same result for every non-NaN x (-0.0 -> +0.0 either way).
+// relu as the IEEE 754-2019 maximum of x and +0.0: ONE v_maximum3_f32 x, 0, 0 (gfx950). A NaN of either sign comes out a NaN,
+// maximum(-0.0, +0.0) is +0.0, every other x gives the bits max(int(x), 0) gave. That integer maximum is also one instruction
+// but turns a NaN whose sign bit is set into +0.0; v_max_f32 x, 0 (maxNum) drops every NaN; a select on the operand's class
+// (v_cmp_class_f32 + v_cndmask_b32) keeps them at two instructions and measurably slower chains (profiles/hostile_inputs_ab.json).
+// The result is never negative and never -0.0, which is what relu_max / bf2max_relu above rely on.
 __device__ __forceinline__ float relu_f(float x)
 {
-    const int b = __builtin_bit_cast(int, x);
-    return __builtin_bit_cast(float, b > 0 ? b : 0);
+    return __builtin_elementwise_maximum(x, 0.0f);
 }
 // two floats -> one dword of two bf16 (round to nearest even): ONE v_cvt_pk_bf16_f32, low half = a
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));

@@ -167,8 +167,8 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_kernel(const GemmLaunch*
         for (int i = 0; i < SLOTS; ++i) {
             const int idx = tid + i * NTHR;
             float4 v = R[X][i];
-            if (AMODE == 1) v = BF ? bf8max_nn(bf8max_nn(v, Rm[X][i]), Rp[X][i])
-                                   : f4max(f4max(v, Rm[X][i]), Rp[X][i]);   // maxpool(3, s1, SAME): padded taps ignored
+            if (AMODE == 1) v = BF ? bf8max_relu(bf8max_relu(v, Rm[X][i]), Rp[X][i])
+                                   : f4max_relu(f4max_relu(v, Rm[X][i]), Rp[X][i]);   // maxpool(3, s1, SAME): padded taps ignored
             if (AMODE != 2) {     // AMODE 2 = dense: every row of every tile is valid, no taps -> no select
                 v.x = lok[X][i] ? v.x : 0.0f;
                 v.y = lok[X][i] ? v.y : 0.0f;
@@ -417,6 +417,8 @@ TileGeom gemm_geom(GemmCfg cfg)
 hipError_t launch_gemm(GemmCfg cfg, const GemmLaunch* d_launch, int total_tiles, hipStream_t s)
 {
     if (total_tiles <= 0) return hipSuccess;
+    // CFG_CONV_POOL / CFG_BCONV_POOL (AMODE 1) pool with f4max_relu / bf8max_relu: their A operand must come from a relu epilogue
+    // (os.relu set in the producing launch, or stem1 / a fused module); on signed values the unsigned maximum is wrong.
     switch (cfg) {
     case CFG_CONV: hipLaunchKernelGGL((gemm_kernel<1, 2, 4, 1, 0, 0, 1, 1>), dim3(total_tiles), dim3(256), 0, s, d_launch); break;
     case CFG_FC: hipLaunchKernelGGL((gemm_kernel<1, 3, 4, 1, 0, 0, 2, 1>), dim3(total_tiles), dim3(256), 0, s, d_launch); break;
@@ -1126,7 +1128,7 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
             if (!POOL && stager) {
                 vc[V] = gload4(pc); pc += KC;
                 if (pooled_in) {       // wave-uniform per launch
-                    vc[V] = f4max(f4max(vc[V], gload4(pq)), gload4(pr));
+                    vc[V] = f4max_relu(f4max_relu(vc[V], gload4(pq)), gload4(pr));
                     pq += KC; pr += KC;
                 }
             }
@@ -1146,7 +1148,7 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
                 for (int mt = 0; mt < TM; ++mt) {
                     const float* q = Ad + X * TR32 * F_LDA + (mt * 32 + (lane & 31)) * F_LDA + rs * 8 + (lane >> 5) * 4;
                     float4 v = *reinterpret_cast<const float4*>(q);
-                    if (POOL) v = f4max(f4max(v, *reinterpret_cast<const float4*>(q + offm[mt])), *reinterpret_cast<const float4*>(q + offp[mt]));
+                    if (POOL) v = f4max_relu(f4max_relu(v, *reinterpret_cast<const float4*>(q + offm[mt])), *reinterpret_cast<const float4*>(q + offp[mt]));
                     af[X][rs][mt] = v;
                 }
         };
@@ -1397,7 +1399,7 @@ hipError_t launch_inception_fused(int tm, const FusedChain& c, hipStream_t s)
 // what matters is the memory traffic and how much of it a CU keeps in flight. Round 3 form:
 //   * TWO workgroups per CU (<= 128 VGPRs, <= 76 KB of LDS each): one tile's load / store phases run under the other's MFMAs;
 //   * the 3-tap max-pooled copy of the input tile (branch 1's operand, 50 KB) is gone: waves 6, 7 pool their fragments
-//     on the fly (three ds_read_b128 + v_pk_max_i16 per fragment), as the fp32 kernel does;
+//     on the fly (three ds_read_b128 + v_pk_max_u16 per fragment), as the fp32 kernel does;
 //   * the P1 weights stream through a ring of two fragments per wave instead of sixteen resident ones;
 //   * a launch carries the modules of one width class and the tile's rows STAY IN LDS from module to module: every result is
 //     written in place over the (dead) input rows in the layout the next module's P1 reads. Only the chain's first module
@@ -1570,7 +1572,7 @@ __global__ __launch_bounds__(512, TM >= 2 ? DS_FUSEDB_WPS : 2) void inception_fu
                 const int ib = i0 + 1 < a.pool_win ? (i0 + 1 < 0 ? ia : i0 + 1) : ia;
                 const int ic = i0 + 2 < a.pool_win ? i0 + 2 : ib;
                 const float* sb = a.X + ((size_t)(site0 + s_) * a.pool_win) * cinu + q * 4;
-                st[i] = bf8max_nn(bf8max_nn(gload4(sb + (size_t)ia * cinu), gload4(sb + (size_t)ib * cinu)), gload4(sb + (size_t)ic * cinu));
+                st[i] = bf8max_relu(bf8max_relu(gload4(sb + (size_t)ia * cinu), gload4(sb + (size_t)ib * cinu)), gload4(sb + (size_t)ic * cinu));
             }
         }
         request_biases();
@@ -1637,7 +1639,7 @@ __global__ __launch_bounds__(512, TM >= 2 ? DS_FUSEDB_WPS : 2) void inception_fu
             }
         } else {
             // pooled operand: raw[mt] = (own, previous, next) row fragments of k-step g, requested one k-step ahead; per
-            // m-tile: 3-tap max (8 x v_pk_max_i16) -> MFMA -> request the next k-step's three fragments into the registers
+            // m-tile: 3-tap max (8 x v_pk_max_u16) -> MFMA -> request the next k-step's three fragments into the registers
             // just consumed. The max of m-tile mt + 1 issues under the MFMA of m-tile mt.
             int om[TM], op[TM];
 #pragma unroll
@@ -1658,7 +1660,7 @@ __global__ __launch_bounds__(512, TM >= 2 ? DS_FUSEDB_WPS : 2) void inception_fu
             for (int g = 0; g < 16; ++g) {
 #pragma unroll
                 for (int mt = 0; mt < TM; ++mt) {
-                    const float4 af = bf8max_nn(bf8max_nn(raw[mt][0], raw[mt][1]), raw[mt][2]);
+                    const float4 af = bf8max_relu(bf8max_relu(raw[mt][0], raw[mt][1]), raw[mt][2]);
                     if (g + 1 < 16) {
                         const float* q = src + mt * 32 * B_LDA + (g + 1) * 8;
                         raw[mt][0] = *reinterpret_cast<const float4*>(q);
@@ -2198,7 +2200,9 @@ __global__ __launch_bounds__(256) void stem1_kernel(const float* __restrict__ si
 #pragma unroll
             for (int t = 0; t < 7; ++t) a = fmaf(v[2 * pt + t], wk[t], a);
             const int wc = wc0 + pt;
-            best = (wc >= 0 && wc < w1) ? fmaxf(best, a) : best;     // padded pool taps are ignored
+            // padded pool taps are ignored; a NaN tap wins and stays (fmaxf would drop it: a window that is NaN throughout
+            // came out as relu(-inf + b) = 0). These are pre-ReLU values of either sign: no relu_max here, the IEEE maximum.
+            best = (wc >= 0 && wc < w1) ? __builtin_elementwise_maximum(best, a) : best;
         }
         const float y = relu_f(best + b);
         if (OUT_BF) reinterpret_cast<unsigned short*>(out)[((size_t)site * wa + p) * 64 + c] = f2bf(y);
@@ -2229,11 +2233,11 @@ __global__ __launch_bounds__(256) void maxpool_s2_kernel(const float4* __restric
         const long r = i / ch4;
         const int wo = (int)(r % wout);
         const long site = r / wout;
-        float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        float4 m = make_float4(0.0f, 0.0f, 0.0f, 0.0f);      // ReLU outputs: 0 is f4max_relu's identity
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
             const int wi = 2 * wo + t - pad_l;
-            if (wi >= 0 && wi < win) m = f4max(m, in[(site * win + wi) * ch4 + c]);
+            if (wi >= 0 && wi < win) m = f4max_relu(m, in[(site * win + wi) * ch4 + c]);
         }
         out[i] = m;
     }
@@ -2489,12 +2493,11 @@ __global__ __launch_bounds__(256) void maxpool_s2_bf16_kernel(const float4* __re
         const long r = i / ch8;
         const int wo = (int)(r % wout);
         const long site = r / wout;
-        const float ninf2 = __uint_as_float(0xff80ff80u);   // two bf16 -inf
-        float4 m = make_float4(ninf2, ninf2, ninf2, ninf2);
+        float4 m = make_float4(0.0f, 0.0f, 0.0f, 0.0f);      // ReLU outputs: 0 is bf8max_relu's identity
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
             const int wi = 2 * wo + t - pad_l;
-            if (wi >= 0 && wi < win) m = bf8max(m, in[(site * win + wi) * ch8 + c]);
+            if (wi >= 0 && wi < win) m = bf8max_relu(m, in[(site * win + wi) * ch8 + c]);
         }
         out[i] = m;
     }

@@ -267,7 +267,7 @@ __global__ __launch_bounds__(512, 2) void inception_fused_split_kernel(const Fus
         auto load_a = [&](int V) __attribute__((always_inline)) {
             if (STG) {
                 vo[V] = gload4(pc);
-                if (pooled_in) vo[V] = f4max(f4max(vo[V], gload4(pc + oq)), gload4(pc + orr));      // wave-uniform branch
+                if (pooled_in) vo[V] = f4max_relu(f4max_relu(vo[V], gload4(pc + oq)), gload4(pc + orr));      // wave-uniform branch
                 pc += KC;
             }
         };
@@ -284,7 +284,10 @@ __global__ __launch_bounds__(512, 2) void inception_fused_split_kernel(const Fus
                 uint2 t0, t1, t2;
                 split3x4(o.x, o.y, o.z, o.w, t0, t1, t2);
                 *reinterpret_cast<uint2*>(d) = t0; *reinterpret_cast<uint2*>(d + 32) = t1; *reinterpret_cast<uint2*>(d + 64) = t2;
-                split3x4(fmaxf(fmaxf(o.x, m.x), n.x), fmaxf(fmaxf(o.y, m.y), n.y), fmaxf(fmaxf(o.z, m.z), n.z), fmaxf(fmaxf(o.w, m.w), n.w), t0, t1, t2);
+                {
+                    const float4 pm = f4max_relu(f4max_relu(o, m), n);
+                    split3x4(pm.x, pm.y, pm.z, pm.w, t0, t1, t2);
+                }
                 *reinterpret_cast<uint2*>(d + 96) = t0; *reinterpret_cast<uint2*>(d + 128) = t1; *reinterpret_cast<uint2*>(d + 160) = t2;
             }
         };

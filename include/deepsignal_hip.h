@@ -136,7 +136,22 @@ int ds_finalize_weights(ds_handle *h);
  * Host buffers, row-major: kmer int32[n,kmer_len] (base codes, process_utils.py:21);
  * means/stds/sanums float[n,kmer_len]; signals float[n,signal_len]. Outputs: act float[n,class_num]
  * = sigmoid(logits) (NOT normalised — the caller normalises, call_modifications.py:185-187) and
- * pred int32[n] = argmax (ties -> lowest index). Blocking. */
+ * pred int32[n] = argmax (ties -> lowest index). Blocking.
+ *
+ * Inputs are not required to be clean (a feature file may hold nan, -nan, inf and overflowed tokens; a client of this ABI may
+ * pass any int32 as a code). What every forward entry point (ds_forward, ds_forward_device, ds_submit / ds_submit_parts /
+ * ds_wait, and the producers that feed them) guarantees then, on every precision:
+ *  1. ISOLATION. A site's act / pred bits do not depend on the values of any other site: not of the sites that share its call,
+ *     its tile or its m-tile, and not of the sites of the call that used the same pipeline slot before. Non-finite values
+ *     included.
+ *  2. NON-FINITE VISIBILITY. act is NaN exactly where the reference forward (oracle/ds_oracle.c, whose ReLU and max-pools
+ *     propagate NaN as the library ops of TensorFlow / PyTorch do) is NaN: a NaN of either sign and any payload in a site's
+ *     signals or features reaches both of its outputs, and a finite number never stands in for one. Where the reference is
+ *     finite -- an infinite LSTM feature saturates the gates, 1e30 is a number -- the precision's usual bar holds. pred of a
+ *     site whose act is NaN is unspecified.
+ *  3. CODES. kmer values 0 .. 1023 select the embedding row; a value below 0 acts as 0 and one above 1023 as 1023 (no read
+ *     outside the table). With is_base = 0 the codes are not read for their value at all.
+ * tests/test_gpu_hostile_inputs.py holds the engine to this; DESIGN.md section 2 lists the cases. */
 int ds_forward(ds_handle *h, int32_t n, const int32_t *kmer, const float *means, const float *stds,
                const float *sanums, const float *signals, float *act, int32_t *pred);
 

@@ -120,7 +120,9 @@ static int conv_bn(const convbn_t *L, const real *in, int win, real *out)
 }
 
 /* tf.layers.max_pooling2d([1,3], strides=s, SAME): padded taps are ignored.
- * layers.py:90-91 (s=1), :189-191, :211-213, :224-226 (s=2). */
+ * layers.py:90-91 (s=1), :189-191, :211-213, :224-226 (s=2).
+ * NaN-honest like the library pools of the other two statements (F.max_pool1d, nn.MaxPool1d): a NaN tap wins, and once
+ * the maximum is NaN it stays NaN (`v > NaN` is false). A `v > m` alone would keep the NaN only when it is the first tap. */
 static int maxpool3(const real *in, int win, int ch, int stride, real *out)
 {
     int wout, pl;
@@ -132,7 +134,7 @@ static int maxpool3(const real *in, int win, int ch, int stride, real *out)
                 int iw = w * stride + t - pl;
                 if (iw < 0 || iw >= win) continue;
                 real v = in[(size_t)iw * ch + c];
-                if (!have || v > m) { m = v; have = 1; }
+                if (!have || v > m || v != v) { m = v; have = 1; }
             }
             out[(size_t)w * ch + c] = m;
         }
@@ -186,7 +188,7 @@ static void inception(const convbn_t *M, const real *in, int w, int cin, real *o
     for (int i = 0; i < w; ++i)
         for (int c = 0; c < 48; ++c) {
             real v = t48[(size_t)i * 48 + c] + t48b[(size_t)i * 48 + c];
-            out[(size_t)i * INC_OUT + 192 + c] = v > 0 ? v : 0;
+            out[(size_t)i * INC_OUT + 192 + c] = (v > 0 || v != v) ? v : 0;   /* ReLU keeps NaN, as torch.relu does */
         }
 }
 
@@ -407,7 +409,8 @@ int ds_oracle_forward(int kmer_len, int signal_len, int class_num, int is_cnn, i
             if (taps && taps->logits) taps->logits[(size_t)s * class_num + c] = (float)acc;
             real a = sigmoid_r(acc);
             act[(size_t)s * class_num + c] = (float)a;
-            if (c == 0 || a > best) { best = a; bi = c; }
+            /* ties -> first index; a NaN counts as the maximum and the first one wins (torch.argmax, np.argmax) */
+            if (c == 0 || a > best || (a != a && best == best)) { best = a; bi = c; }
         }
         pred[s] = bi;
     }
