@@ -6,6 +6,7 @@
 #include "ds_internal.h"
 #include "ds_extract.h"
 #include "ds_tsv_device.h"
+#include "ds_freq.h"
 
 #include <algorithm>
 #include <cmath>
@@ -254,6 +255,9 @@ struct ds_handle {
     double tx_ms[3] = {0, 0, 0};          // H2D of the text, tsv_parse_kernel, D2H of status / label / info length / k-mer
     int64_t rc_launches = 0;              // recheck_select_kernel launches timed while profiling was on, and their summed device ms
     double rc_ms = 0;
+    dsf::Freq* freq = nullptr;            // call_freq --on gpu: the open run (ds_freq_begin .. ds_freq_end); its table and buffers are its own
+    int64_t fq_batches = 0;               // batches of the runs ended so far, and their device ms (the open run's are added on top)
+    double fq_ms[4] = {0, 0, 0, 0};
     // pipelining: consecutive forwards rotate over independent slots (own workspace, streams, graphs), so the
     // dependency chain of one 512-site forward overlaps the next ones'; weights are shared
     std::vector<Slot> slots;
@@ -1557,6 +1561,7 @@ void ds_destroy(ds_handle* h)
         if (sl.s0) hipStreamDestroy(sl.s0);
         if (sl.s1 && sl.owns_s1) hipStreamDestroy(sl.s1);
     }
+    delete h->freq;
     for (void* p : h->allocs) hipFree(p);
     (void)hipGetLastError();      // nothing a teardown call returned may surface in a later handle's first launch
     delete h;
@@ -2416,6 +2421,90 @@ int ds_get_text_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms)
     return DS_OK;
 }
 
+// ---- per-site modification frequency on the device (ds_freq.hip; call_freq --on gpu) ------------------------------------------------
+// The run's state is a dsf::Freq of its own (table, row buffers, stream): no pipeline slot, no weights.
+static void freq_close(ds_handle* h)
+{
+    if (!h->freq) return;
+    h->fq_batches += h->freq->batches;
+    for (int i = 0; i < 4; ++i) h->fq_ms[i] += h->freq->ms[i];
+    delete h->freq;
+    h->freq = nullptr;
+}
+
+static int ds_freq_begin_impl(ds_handle* h, int64_t total_rows, int32_t batch_rows, double prob_cf)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (h->freq) return fail(h, DS_ERR_INVALID, "ds_freq_begin: a run is open on this handle (ds_freq_end first)");
+    h->freq = new dsf::Freq();
+    std::string err;
+    const int rc = h->freq->begin(h->cfg.device, total_rows, batch_rows, prob_cf, &err);
+    if (rc) { delete h->freq; h->freq = nullptr; return fail(h, rc, err); }
+    return DS_OK;
+}
+
+static int ds_freq_parse_impl(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, const int32_t* chrom,
+                              const uint8_t* flags, int32_t* status)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (!h->freq) return fail(h, DS_ERR_INVALID, "ds_freq_parse: no run is open (ds_freq_begin first)");
+    std::string err;
+    const int rc = h->freq->parse(text, nrows, begin, end, chrom, flags, status, &err);
+    return rc ? fail(h, rc, err) : DS_OK;
+}
+
+static int ds_freq_accumulate_impl(ds_handle* h, int32_t nover, const int32_t* row, const int32_t* chrom, const int64_t* pos, const double* p0,
+                                   const double* p1, const int32_t* met)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (!h->freq) return fail(h, DS_ERR_INVALID, "ds_freq_accumulate: no run is open (ds_freq_begin first)");
+    std::string err;
+    const int rc = h->freq->accumulate(nover, row, chrom, pos, p0, p1, met, &err);
+    return rc ? fail(h, rc, err) : DS_OK;
+}
+
+static int64_t ds_freq_result_impl(ds_handle* h, int64_t cap, int64_t* first_row, int32_t* chrom, int64_t* pos, double* sum0, double* sum1,
+                                   int32_t* met, int32_t* unmet, int64_t* rows, int64_t* used)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (!h->freq) return fail(h, DS_ERR_INVALID, "ds_freq_result: no run is open (ds_freq_begin first)");
+    std::string err;
+    const int64_t rc = h->freq->result(cap, first_row, chrom, pos, sum0, sum1, met, unmet, rows, used, &err);
+    return rc < 0 ? fail(h, (int)rc, err) : rc;
+}
+
+int ds_freq_end(ds_handle* h)
+{
+    if (!h) return DS_ERR_INVALID;
+    freq_close(h);
+    return DS_OK;
+}
+
+int64_t ds_freq_reference(const char* text, int64_t nrows, const int64_t* begin, const int64_t* end, const int32_t* chrom, const uint8_t* flags,
+                          double prob_cf, int32_t* status, int64_t* pos, double* p0, double* p1, int32_t* met, int64_t cap, int64_t* first_row,
+                          int32_t* site_chrom, int64_t* site_pos, double* sum0, double* sum1, int32_t* site_met, int32_t* site_unmet, int64_t* used)
+{
+    return guarded(nullptr, [&]() -> int64_t {
+        std::string err;
+        const int64_t rc = dsf::reference(text, nrows, begin, end, chrom, flags, prob_cf, status, pos, p0, p1, met, cap, first_row, site_chrom,
+                                          site_pos, sum0, sum1, site_met, site_unmet, used, &err);
+        return rc < 0 ? fail(nullptr, DS_ERR_INVALID, err) : rc;
+    });
+}
+
+int ds_get_freq_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms)
+{
+    if (!h || !batches || !ms) return DS_ERR_INVALID;
+    *batches = h->fq_batches + (h->freq ? h->freq->batches : 0);
+    for (int i = 0; i < 4; ++i) ms[i] = h->fq_ms[i] + (h->freq ? h->freq->ms[i] : 0.0);
+    if (reset) {
+        h->fq_batches = 0;
+        for (double& v : h->fq_ms) v = 0;
+        if (h->freq) { h->freq->batches = 0; for (double& v : h->freq->ms) v = 0; }
+    }
+    return DS_OK;
+}
+
 // ---- feature rows: float64 values and their text on the device (ds_extract.hip rows_*_kernel) ---------------------------------
 // Needs no weights: the slot's streams and the blocks below are all it uses. The rows path enqueues, on sl.s0: H2D of the packed
 // reads and of info / info_off, the statistics, values, length, scan and format kernels, D2H of the row offsets.
@@ -2906,6 +2995,10 @@ int64_t ds_extract_rows(ds_handle* h, const ds_reads* reads, const char* info, c
 int ds_set_recheck(ds_handle* coarse, ds_handle* fine, float margin) { return guarded(coarse, [&] { return ds_set_recheck_impl(coarse, fine, margin); }); }
 int ds_recheck_select(ds_handle* h, int32_t n, const float* act, float margin, int32_t* count, int32_t* index) { return guarded(h, [&] { return ds_recheck_select_impl(h, n, act, margin, count, index); }); }
 int64_t ds_format_values(ds_handle* h, int64_t n, const double* values, char* out, int64_t cap) { return guarded(h, [&] { return ds_format_values_impl(h, n, values, out, cap); }); }
+int ds_freq_begin(ds_handle* h, int64_t total_rows, int32_t batch_rows, double prob_cf) { return guarded(h, [&] { return ds_freq_begin_impl(h, total_rows, batch_rows, prob_cf); }); }
+int ds_freq_parse(ds_handle* h, const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, const int32_t* chrom, const uint8_t* flags, int32_t* status) { return guarded(h, [&] { return ds_freq_parse_impl(h, text, nrows, row_begin, row_end, chrom, flags, status); }); }
+int ds_freq_accumulate(ds_handle* h, int32_t nover, const int32_t* row, const int32_t* chrom, const int64_t* pos, const double* p0, const double* p1, const int32_t* met) { return guarded(h, [&] { return ds_freq_accumulate_impl(h, nover, row, chrom, pos, p0, p1, met); }); }
+int64_t ds_freq_result(ds_handle* h, int64_t cap, int64_t* first_row, int32_t* chrom, int64_t* pos, double* sum0, double* sum1, int32_t* met, int32_t* unmet, int64_t* rows, int64_t* used) { return guarded(h, [&] { return ds_freq_result_impl(h, cap, first_row, chrom, pos, sum0, sum1, met, unmet, rows, used); }); }
 int ds_submit_text(ds_handle* h, const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, int32_t* ticket) { return guarded(h, [&] { return ds_submit_text_impl(h, text, nrows, row_begin, row_end, ticket); }); }
 int ds_wait_text(ds_handle* h, int32_t ticket, float* act, int32_t* pred, int32_t* kmer, int32_t* labels, char* info, int64_t info_cap, int64_t* info_off) { return guarded(h, [&] { return ds_wait_text_impl(h, ticket, act, pred, kmer, labels, info, info_cap, info_off); }); }
 int ds_parse_text(ds_handle* h, const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, int32_t* kmer, float* means, float* stds, float* lens, float* signals, int32_t* labels, int32_t* info_len, int32_t* status) { return guarded(h, [&] { return ds_parse_text_impl(h, text, nrows, row_begin, row_end, kmer, means, stds, lens, signals, labels, info_len, status); }); }

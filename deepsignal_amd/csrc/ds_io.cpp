@@ -24,7 +24,9 @@
 #include <functional>
 #include <mutex>
 #include <string>
+#include <string_view>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include <fcntl.h>
@@ -702,6 +704,71 @@ uint32_t ds_crc32c(const void* data, size_t n, uint32_t crc)
     }
     while (n--) crc = T[0][(crc ^ *p++) & 0xFF] ^ (crc >> 8);
     return ~crc;
+}
+
+// The host half of call_freq --on gpu (ds_freq.hip): the rows of a call_mods result buffer and a chromosome id per row. A row is
+// what lies between two '\n' (a last row needs none). Column 0 is compared with the previous row's and otherwise looked up in a
+// table; ids count up in first-appearance order and the names come back '\n'-joined. A row Python would strip or decode differently
+// from its raw bytes -- blank, first or last byte whitespace (str.strip's ASCII set), any byte >= 0x80, any '\r' (universal
+// newlines end a line there) -- gets flag 1 and chromosome -1: the Python parser takes it, and its column 0 names no chromosome here.
+int64_t ds_freq_locate(const char* text, int64_t nbytes, int64_t cap_rows, int64_t* row_begin, int64_t* row_end, int32_t* chrom,
+                       uint8_t* flags, char* names, int64_t names_cap, int64_t* names_bytes, int32_t* n_names)
+{
+    if (nbytes < 0 || (nbytes > 0 && !text) || cap_rows < 0 || names_cap < 0 || !names_bytes || !n_names ||
+        (cap_rows > 0 && (!row_begin || !row_end || !chrom || !flags)) || (names_cap > 0 && !names))
+        return DS_ERR_INVALID;
+    auto is_space = [](unsigned char c) { return c == ' ' || (c >= 9 && c <= 13) || (c >= 0x1c && c <= 0x1f); };
+    std::unordered_map<std::string_view, int32_t> table;
+    const char* prev = nullptr;
+    size_t prev_len = 0;
+    int32_t prev_id = -1;
+    int64_t nrows = 0, nb = 0;
+    const char* p = text;
+    const char* const end = text + nbytes;
+    while (p < end) {
+        const char* nl = static_cast<const char*>(memchr(p, '\n', (size_t)(end - p)));
+        const char* e = nl ? nl : end;
+        bool host = e == p || is_space((unsigned char)p[0]) || is_space((unsigned char)e[-1]) || memchr(p, '\r', (size_t)(e - p)) != nullptr;
+        if (!host) {
+            unsigned char hi = 0;
+            for (const char* q = p; q < e; ++q) hi |= (unsigned char)*q;
+            host = (hi & 0x80) != 0;
+        }
+        int32_t id = -1;
+        if (!host) {
+            const char* tab = static_cast<const char*>(memchr(p, '\t', (size_t)(e - p)));
+            const size_t len = (size_t)((tab ? tab : e) - p);
+            if (prev && len == prev_len && memcmp(p, prev, len) == 0) {
+                id = prev_id;
+            } else {
+                auto it = table.find(std::string_view(p, len));
+                if (it != table.end()) {
+                    id = it->second;
+                } else {
+                    if (table.size() >= 0x7fffffffu) return DS_ERR_UNSUPPORTED;
+                    id = (int32_t)table.size();
+                    table.emplace(std::string_view(p, len), id);
+                    if (nb + (int64_t)len + 1 <= names_cap) {
+                        memcpy(names + nb, p, len);
+                        names[nb + (int64_t)len] = '\n';
+                    }
+                    nb += (int64_t)len + 1;
+                }
+                prev = p; prev_len = len; prev_id = id;
+            }
+        }
+        if (nrows < cap_rows) {
+            row_begin[nrows] = (int64_t)(p - text);
+            row_end[nrows] = (int64_t)(e - text);
+            chrom[nrows] = id;
+            flags[nrows] = host ? 1 : 0;
+        }
+        ++nrows;
+        p = nl ? nl + 1 : end;
+    }
+    *names_bytes = nb;
+    *n_names = (int32_t)table.size();
+    return nrows;
 }
 
 }  // extern "C"

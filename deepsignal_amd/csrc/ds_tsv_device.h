@@ -31,9 +31,10 @@ DST_HD int base_code(char c)
 
 // [-]digits[.digits][e|E[+-]digits], the whole of [p, e): at most 15 significant digits m < 2^53 and a net decimal exponent in
 // [-22, 22], so that m and 10^|x| are exact doubles and one multiplication or division gives the correctly rounded double
-// strtod / float() return (Clinger's fast path); then (float). False: some other form (a leading '+', inf, nan, 1e400, a longer
-// mantissa, an empty token, any other byte).
-DST_HD bool float_token(const char* p, const char* e, float* out)
+// strtod / float() return (Clinger's fast path). False: some other form (a leading '+', inf, nan, 1e400, a longer mantissa, an
+// empty token, any other byte). double_token keeps the double (the probabilities of call_freq --on gpu, ds_freq.h); float_token
+// narrows it to float32 (the feature TSV).
+DST_HD bool double_token(const char* p, const char* e, double* out)
 {
     const double kPow10[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15,
                                1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
@@ -75,7 +76,15 @@ DST_HD bool float_token(const char* p, const char* e, float* out)
     const int net = ex - frac;
     if (net < -22 || net > 22) return false;
     const double v = net < 0 ? (double)m / kPow10[-net] : (double)m * kPow10[net];
-    *out = (float)(neg ? -v : v);
+    *out = neg ? -v : v;
+    return true;
+}
+
+DST_HD bool float_token(const char* p, const char* e, float* out)
+{
+    double v;
+    if (!double_token(p, e, &v)) return false;
+    *out = (float)v;
     return true;
 }
 
@@ -92,6 +101,24 @@ DST_HD bool int_token(const char* p, const char* e, int* out)
         const unsigned c = (unsigned char)*q;
         if (c - '0' > 9u) return false;
         v = v * 10 + (int)(c - '0');
+    }
+    *out = neg ? -v : v;
+    return true;
+}
+
+// [-]digits, the whole of [p, e), at most 18 digits (genome positions)
+DST_HD bool int64_token(const char* p, const char* e, int64_t* out)
+{
+    const char* q = p;
+    const bool neg = q < e && *q == '-';
+    if (neg) ++q;
+    const int nd = (int)(e - q);
+    if (nd < 1 || nd > 18) return false;
+    int64_t v = 0;
+    for (; q < e; ++q) {
+        const unsigned c = (unsigned char)*q;
+        if (c - '0' > 9u) return false;
+        v = v * 10 + (int64_t)(c - '0');
     }
     *out = neg ? -v : v;
     return true;

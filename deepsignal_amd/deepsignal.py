@@ -1,6 +1,7 @@
 """`deepsignal call_mods` command line — the reference's flag surface for this sub-command
 (reference deepsignal/deepsignal.py:236-326, defaults included), driving the MI355X engine — plus `extract`, the
-host-side step that produces call_mods' feature-TSV input (deepsignal.py:155-234).
+host-side step that produces call_mods' feature-TSV input (deepsignal.py:155-234), and `call_freq`, the per-site frequency table
+from call_mods' result files (scripts/call_modification_frequency.py).
 
 Multi-GPU: one process per GPU, e.g.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
@@ -36,6 +37,19 @@ def main_extraction(args):
                      args.normalize_method, args.motifs, args.mod_loc, args.kmer_len, args.cent_signals_len,
                      args.methy_label, args.positions, str2bool(args.w_is_dir), args.w_batch_num,
                      extract_on=args.extract_on, device=args.device, engine_batch=args.engine_batch)
+
+
+def main_call_freq(args):
+    from .call_modification_frequency import main as freq_main
+    argv = []
+    for path in args.input_path:
+        argv += ["-i", path]
+    argv += ["-o", args.result_file, "--prob_cf", repr(args.prob_cf), "--on", args.on]
+    argv += ["--bed"] if args.bed else []
+    argv += ["--sort"] if args.sort else []
+    argv += ["--file_uid", args.file_uid] if args.file_uid is not None else []
+    argv += ["--device", str(args.device)] if args.device is not None else []
+    return freq_main(argv)
 
 
 def build_parser():
@@ -128,6 +142,20 @@ def build_parser():
     p.add_argument("--nproc", "-p", type=int, default=1)
     p.add_argument("--is_gpu", default="no", choices=["yes", "no"])
     p.set_defaults(func=main_call_mods)
+    # `call_freq`: the step after the path -- call_mods result files -> per-site frequency table or bedMethyl (the reference's later
+    # releases expose scripts/call_modification_frequency.py under this name; same flags, plus --on / --device)
+    f = sub.add_parser("call_freq", description="calculate the modification frequency of every site from call_mods result files")
+    f.add_argument("--input_path", "-i", action="append", type=str, required=True,
+                   help="a result file of call_mods (may be .gz) or a directory of them; may be given more than once")
+    f.add_argument("--result_file", "-o", type=str, required=True)
+    f.add_argument("--bed", action="store_true", default=False, help="write bedMethyl instead of the 11-column table")
+    f.add_argument("--sort", action="store_true", default=False, help="sort the sites by (chromosome, position)")
+    f.add_argument("--prob_cf", type=float, default=0.0, help="leave out calls with |prob_0 - prob_1| below this")
+    f.add_argument("--file_uid", type=str, default=None, help="with a directory: only the files whose name holds this")
+    f.add_argument("--on", default="cpu", choices=["cpu", "gpu"],
+                   help="gpu: rows parsed and aggregated on the GPU (the host only finds them); same output bytes")
+    f.add_argument("--device", type=int, default=None, help="GPU ordinal of --on gpu (default 0)")
+    f.set_defaults(func=main_call_freq)
     return parser
 
 
@@ -143,6 +171,8 @@ def main(argv=None):
             check_recheck_args(args.precision, args.recheck_margin, args.recheck_precision)
         except ValueError as exc:
             parser.error(str(exc))
+    if args.module == "call_freq":
+        return args.func(args)       # the script's own main: it validates the forwarded flags and returns the exit status
     args.func(args)
     return 0
 

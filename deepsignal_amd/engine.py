@@ -44,6 +44,9 @@ EXPORTED_SYMBOLS = (
     # feature-TSV rows parsed on the device (call_mods --parse_on gpu)
     "ds_submit_text", "ds_wait_text", "ds_parse_text", "ds_parse_text_reference", "ds_get_text_stats", "ds_get_text_times",
     "ds_tsv_take_lines", "ds_tsv_data",
+    # per-site modification frequency on the device (call_freq --on gpu)
+    "ds_freq_locate", "ds_freq_begin", "ds_freq_parse", "ds_freq_accumulate", "ds_freq_result", "ds_freq_end",
+    "ds_freq_reference", "ds_get_freq_times",
 )
 
 
@@ -226,6 +229,74 @@ def parse_text_reference(text, begin, end, kmer_len: int = 17, signal_len: int =
     return out
 
 
+FREQ_ROW_GIVEN = 2                     # DS_FREQ_ROW_GIVEN: freq_reference takes this row's values from the caller
+FREQ_POS_LIMIT, FREQ_CHROM_LIMIT = 1 << 40, 1 << 23      # a site key is chrom_id << 40 | pos
+FREQ_MAX_BATCH, FREQ_MAX_ROWS = 1 << 24, 1 << 30
+
+
+class FreqNoMemory(RuntimeError):
+    """freq_begin: the site table or the batch buffers do not fit the device."""
+
+
+def freq_locate(text):
+    """ds_freq_locate: the rows of a call_mods result buffer (bytes, or a uint8 array such as a memory map) -> (row_begin int64[n],
+    row_end int64[n], chrom int32[n], flags uint8[n], names): chrom = the row's chromosome id, an index into `names` (bytes, in
+    first-appearance order); flags 1 = a row Python strips or decodes differently from its raw bytes (chrom -1)."""
+    lib = load_library()
+    if isinstance(text, (bytes, bytearray)):
+        text = np.frombuffer(text, np.uint8)
+    text = np.ascontiguousarray(text, np.uint8)
+    if text.ndim != 1:
+        raise ValueError("text must be a flat byte buffer")
+    nb, nn = ctypes.c_int64(), ctypes.c_int32()
+    cap, names_cap = text.size // 32 + 1, 1 << 16      # a result row is ~100 bytes: one pass over the buffer in the common case
+    while True:
+        begin, end = np.empty(cap, np.int64), np.empty(cap, np.int64)
+        chrom, flags = np.empty(cap, np.int32), np.empty(cap, np.uint8)
+        names = np.empty(names_cap, np.uint8)
+        n = int(lib.ds_freq_locate(text.ctypes.data if text.size else None, text.size, cap, begin.ctypes.data, end.ctypes.data,
+                                   chrom.ctypes.data, flags.ctypes.data, names.ctypes.data, names_cap, ctypes.byref(nb),
+                                   ctypes.byref(nn)))
+        if n < 0:
+            raise RuntimeError("ds_freq_locate failed (%d)" % n)
+        if n <= cap and nb.value <= names_cap:
+            blob = names[:nb.value].tobytes()
+            return begin[:n], end[:n], chrom[:n], flags[:n], blob.split(b"\n")[:nn.value]
+        cap, names_cap = max(cap, n), max(names_cap, int(nb.value))
+
+
+_FREQ_SITE_FIELDS = (("first_row", np.int64), ("chrom", np.int32), ("pos", np.int64), ("sum0", np.float64), ("sum1", np.float64),
+                     ("met", np.int32), ("unmet", np.int32))
+
+
+def freq_reference(text, begin, end, chrom, flags, prob_cf: float = 0.0, given=None) -> Dict[str, np.ndarray]:
+    """ds_freq_reference: the device route's aggregation on the CPU from the same row routine, one pass in row order. A checker
+    for the tests (no GPU needed), not a fall-back. `given`: {row index: (chrom id, pos, p0, p1, met)} for rows whose values
+    the caller supplies (what the device route does with the rows it leaves to Python). Returns the per-row status / pos / p0 /
+    p1 / met and the sites in the order of their first used row (first_row, chrom, pos, sum0, sum1, met, unmet), plus `used`."""
+    lib = load_library()
+    keep, addr, begin, end = _text_args(text, begin, end)
+    n = int(begin.size)
+    chrom = np.array(chrom, np.int32)              # a copy: the given rows' ids go in
+    flags = np.ascontiguousarray(flags, np.uint8)
+    if chrom.shape != (n,) or flags.shape != (n,):
+        raise ValueError("chrom / flags must have one entry per row")
+    status = np.zeros(n, np.int32)
+    pos, p0, p1, met = np.zeros(n, np.int64), np.zeros(n, np.float64), np.zeros(n, np.float64), np.zeros(n, np.int32)
+    for i, (c, q, a, b, m) in (given or {}).items():
+        status[i], chrom[i], pos[i], p0[i], p1[i], met[i] = FREQ_ROW_GIVEN, c, q, a, b, m
+    sites = {k: np.empty(n, dt) for k, dt in _FREQ_SITE_FIELDS}
+    used = ctypes.c_int64()
+    got = int(lib.ds_freq_reference(addr, n, begin.ctypes.data, end.ctypes.data, chrom.ctypes.data, flags.ctypes.data, float(prob_cf),
+                                    status.ctypes.data, pos.ctypes.data, p0.ctypes.data, p1.ctypes.data, met.ctypes.data, n,
+                                    *(sites[k].ctypes.data for k, _ in _FREQ_SITE_FIELDS), ctypes.byref(used)))
+    if got < 0:
+        raise RuntimeError("ds_freq_reference failed (%d): %s" % (got, lib.ds_last_error(None).decode()))
+    out = {k: v[:got] for k, v in sites.items()}
+    out.update(status=status, row_pos=pos, row_p0=p0, row_p1=p1, row_met=met, used=int(used.value))
+    return out
+
+
 # ds_config.precision (include/deepsignal_hip.h): "bf16" = bf16 conv + FC operands with fp32 accumulation, fp32 BiLSTM;
 # "bf16_all" = also bf16 h / weight operands in the LSTM matmuls (fp32 accumulate, gates, cell state)
 PRECISIONS = {"fp32": 0, "bf16": 1, "bf16_all": 2, "bf16x3": 3}
@@ -328,6 +399,19 @@ def load_library() -> ctypes.CDLL:
     lib.ds_parse_text_reference.argtypes = [i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.ds_get_text_stats.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]
     lib.ds_get_text_times.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_double)]
+    f64 = ctypes.c_double
+    lib.ds_freq_locate.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i32)]
+    lib.ds_freq_locate.restype = i64
+    lib.ds_freq_begin.argtypes = [vp, i64, i32, f64]
+    lib.ds_freq_parse.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.ds_freq_accumulate.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.ds_freq_result.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    lib.ds_freq_result.restype = i64
+    lib.ds_freq_end.argtypes = [vp]
+    lib.ds_freq_reference.argtypes = [vp, i64, vp, vp, vp, vp, f64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp,
+                                      ctypes.POINTER(i64)]
+    lib.ds_freq_reference.restype = i64
+    lib.ds_get_freq_times.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(f64)]
     _lib = lib
     return lib
 
@@ -567,6 +651,89 @@ class Engine:
         ms = (ctypes.c_double * 3)()
         self._check(self._lib.ds_get_text_times(self._h, int(reset), ctypes.byref(n), ms), "ds_get_text_times")
         return dict(zip(("h2d_ms", "kernel_ms", "d2h_ms"), ms), batches=int(n.value))
+
+    # -- per-site modification frequency on the device (ds_freq_*; call_freq --on gpu) ----------
+    def freq_begin(self, total_rows: int, batch_rows: int, prob_cf: float = 0.0) -> None:
+        """ds_freq_begin: open a run whose batches hold at most batch_rows rows and total_rows rows in all (the site table is
+        sized from it, at most half full). FreqNoMemory when the table or the buffers do not fit the device. Needs no weights."""
+        total_rows, batch_rows, prob_cf = int(total_rows), int(batch_rows), float(prob_cf)
+        if not 1 <= total_rows <= FREQ_MAX_ROWS:
+            raise ValueError("total_rows must be in [1, 2^30]")
+        if not 1 <= batch_rows <= FREQ_MAX_BATCH:
+            raise ValueError("batch_rows must be in [1, 2^24]")
+        if prob_cf != prob_cf:
+            raise ValueError("prob_cf must not be NaN")
+        rc = self._lib.ds_freq_begin(self._h, total_rows, batch_rows, prob_cf)
+        if rc == -5:
+            raise FreqNoMemory(self._lib.ds_last_error(self._h).decode())
+        self._check(rc, "ds_freq_begin")
+        self._freq_batch, self._freq_pending = batch_rows, -1
+
+    def freq_parse(self, text, begin, end, chrom, flags) -> np.ndarray:
+        """ds_freq_parse: one batch of rows (ascending spans of one buffer; chrom / flags per row as freq_locate gives them, the
+        ids mapped to one numbering for the whole run) parsed on the GPU -> the per-row status (TEXT_ROW_OK / TEXT_ROW_HOST)."""
+        keep, addr, begin, end = _text_args(text, begin, end)
+        chrom = np.ascontiguousarray(chrom, np.int32)
+        flags = np.ascontiguousarray(flags, np.uint8)
+        n = int(begin.size)
+        if chrom.shape != (n,) or flags.shape != (n,):
+            raise ValueError("chrom / flags must have one entry per row")
+        if not 1 <= n <= getattr(self, "_freq_batch", 0):
+            raise ValueError("a batch holds 1 .. batch_rows rows of an open run")
+        if n > 1 and bool((begin[1:] < end[:-1]).any()):
+            raise ValueError("the rows of a batch must be ascending and disjoint")
+        status = np.empty(n, np.int32)
+        self._check(self._lib.ds_freq_parse(self._h, addr, n, begin.ctypes.data, end.ctypes.data, chrom.ctypes.data,
+                                            flags.ctypes.data, status.ctypes.data), "ds_freq_parse")
+        self._freq_pending = n
+        return status
+
+    def freq_accumulate(self, rows=(), chrom=(), pos=(), p0=(), p1=(), met=()) -> None:
+        """ds_freq_accumulate: add the batch just parsed to the run. rows .. met: the caller's values for the batch's
+        TEXT_ROW_HOST rows (ascending batch row indices, every such row; 0 <= chrom < 2^23, 0 <= pos < 2^40)."""
+        rows, chrom, met = (np.ascontiguousarray(a, np.int32) for a in (rows, chrom, met))
+        pos = np.ascontiguousarray(pos, np.int64)
+        p0, p1 = np.ascontiguousarray(p0, np.float64), np.ascontiguousarray(p1, np.float64)
+        m = int(rows.size)
+        if any(a.shape != (m,) for a in (chrom, pos, p0, p1, met)):
+            raise ValueError("the override arrays must have one length")
+        n = getattr(self, "_freq_pending", -1)
+        if n < 0:
+            raise ValueError("freq_accumulate needs a batch from freq_parse")
+        if m and (int(rows.min()) < 0 or int(rows.max()) >= n or bool((np.diff(rows) <= 0).any())):
+            raise ValueError("override rows must be ascending indices of the batch")
+        if m and (int(chrom.min()) < 0 or int(chrom.max()) >= FREQ_CHROM_LIMIT or int(pos.min()) < 0 or int(pos.max()) >= FREQ_POS_LIMIT):
+            raise ValueError("override chromosome ids / positions must fit the key (2^23 ids, pos < 2^40)")
+        self._freq_pending = -1
+        self._check(self._lib.ds_freq_accumulate(self._h, m, rows.ctypes.data, chrom.ctypes.data, pos.ctypes.data, p0.ctypes.data,
+                                                 p1.ctypes.data, met.ctypes.data), "ds_freq_accumulate")
+
+    def freq_result(self) -> Dict[str, np.ndarray]:
+        """ds_freq_result: the sites of the run so far, in no particular order -> first_row, chrom, pos, sum0, sum1, met, unmet
+        arrays, and the scalars rows (accumulated) and used (rows that passed the threshold)."""
+        rows, used = ctypes.c_int64(), ctypes.c_int64()
+        n = int(self._lib.ds_freq_result(self._h, 0, None, None, None, None, None, None, None, ctypes.byref(rows), ctypes.byref(used)))
+        self._check(n, "ds_freq_result")
+        out = {k: np.empty(n, dt) for k, dt in _FREQ_SITE_FIELDS}
+        if n:
+            got = int(self._lib.ds_freq_result(self._h, n, *(out[k].ctypes.data for k, _ in _FREQ_SITE_FIELDS), ctypes.byref(rows),
+                                               ctypes.byref(used)))
+            self._check(got, "ds_freq_result")
+            if got != n:
+                raise RuntimeError("ds_freq_result: %d sites announced, %d returned" % (n, got))
+        out.update(rows=int(rows.value), used=int(used.value))
+        return out
+
+    def freq_end(self) -> None:
+        self._freq_batch, self._freq_pending = 0, -1
+        self._check(self._lib.ds_freq_end(self._h), "ds_freq_end")
+
+    def freq_times(self, reset: bool = False) -> dict:
+        """ds_get_freq_times: device milliseconds of the frequency batches so far (copies, parse kernel, sort, insert + accumulate)."""
+        n = ctypes.c_int64()
+        ms = (ctypes.c_double * 4)()
+        self._check(self._lib.ds_get_freq_times(self._h, int(reset), ctypes.byref(n), ms), "ds_get_freq_times")
+        return dict(zip(("copy_ms", "parse_ms", "sort_ms", "accumulate_ms"), ms), batches=int(n.value))
 
     def rows_times(self, reset: bool = False) -> dict:
         """ds_get_rows_times: device milliseconds of the extract_rows() calls made while profiling was on."""

@@ -438,6 +438,59 @@ int ds_get_text_stats(ds_handle *h, int64_t *rows, int64_t *host_rows);
  * positional ds_get_kernel_stat table. */
 int ds_get_text_times(ds_handle *h, int32_t reset, int64_t *batches, double *ms);
 
+/* ---- per-site modification frequency on the device (ds_freq.hip; call_freq --on gpu) ---------------------------------------------
+ * The aggregation of scripts/call_modification_frequency.py over call_mods result rows
+ *   chrom \t pos \t strand \t pos_in_strand \t readname \t read_strand \t prob_0 \t prob_1 \t label \t k-mer
+ * A site is (chrom, pos); a row is used unless |prob_0 - prob_1| < prob_cf in double; per site the two probability sums are
+ * doubles added IN ROW ORDER (no floating-point atomics anywhere), met counts the used rows whose label is 1, unmet the others.
+ * The host only finds the rows and numbers the chromosomes (ds_freq_locate); the device parses pos as [-]digits with
+ * 0 <= pos < 2^40, pos_in_strand as [-]digits (checked, not kept), the label as [-]digits of at most 9 digits and the probabilities
+ * as [-]digits[.digits][e|E[+-]digits] with at most 15 significant digits and a net decimal exponent in [-22, 22] (one
+ * exact-operand IEEE double multiplication or division: strtod's bits, kept as double). Every other row -- nan, inf, 1e-30, a
+ * leading '+', fewer than ten columns, a chromosome id outside [0, 2^23), a row ds_freq_locate flagged -- is not an error: its
+ * status is DS_TEXT_ROW_HOST and the caller supplies its values. Columns beyond the tenth are ignored. None of this needs weights.
+ *
+ * ds_freq_locate (host, no handle): the rows of a buffer -- what lies between two '\n'; a last row needs none -- as spans
+ * row_begin / row_end, a chromosome id per row (column 0; ids count up in first-appearance order, the names come back '\n'-joined
+ * in `names`) and flags: 1 = Python would strip or decode the row differently from its raw bytes (blank, first or last byte
+ * whitespace, a byte >= 0x80, a '\r'); such a row has chromosome -1 and registers no name. Returns the rows found; arrays are
+ * filled up to cap_rows and names up to names_cap bytes, *names_bytes is what the names need: call again with room when short.
+ *
+ * One run on a handle: ds_freq_begin sizes the site table -- open addressing over the exact key chrom << 40 | pos, at most half
+ * full with total_rows rows -- and the buffers of a batch (1 <= nrows <= batch_rows <= 2^24); DS_ERR_NOMEM when they do not fit the
+ * device. Then, strictly in sequence per batch: ds_freq_parse (rows ascending and disjoint inside one buffer; the per-row status
+ * comes back) and ds_freq_accumulate, which first takes the caller's values for the batch's DS_TEXT_ROW_HOST rows (ascending
+ * batch row indices; all of them must be given, 0 <= chrom < 2^23, 0 <= pos < 2^40), then inserts the used rows' keys (the slot is
+ * the site id, the first global row of a site is kept), sorts (site, row) over the batch and adds each site's run in row order
+ * to the site's running sums. Global row numbers count up over the batches of the run. ds_freq_result returns the number of
+ * sites and, when the arrays are given (cap >= that number), per site in no particular order: its first used row, chromosome id,
+ * pos, the two sums, met and unmet; *rows = rows accumulated, *used = rows that passed the threshold. cap == 0 with null arrays
+ * asks for the count alone. ds_freq_end closes the run (ds_destroy does too). Every call blocks. */
+int64_t ds_freq_locate(const char *text, int64_t nbytes, int64_t cap_rows, int64_t *row_begin, int64_t *row_end, int32_t *chrom,
+                       uint8_t *flags, char *names, int64_t names_cap, int64_t *names_bytes, int32_t *n_names);
+int ds_freq_begin(ds_handle *h, int64_t total_rows, int32_t batch_rows, double prob_cf);
+int ds_freq_parse(ds_handle *h, const char *text, int32_t nrows, const int64_t *row_begin, const int64_t *row_end, const int32_t *chrom,
+                  const uint8_t *flags, int32_t *status);
+int ds_freq_accumulate(ds_handle *h, int32_t nover, const int32_t *row, const int32_t *chrom, const int64_t *pos, const double *p0,
+                       const double *p1, const int32_t *met);
+int64_t ds_freq_result(ds_handle *h, int64_t cap, int64_t *first_row, int32_t *chrom, int64_t *pos, double *sum0, double *sum1,
+                       int32_t *met, int32_t *unmet, int64_t *rows, int64_t *used);
+int ds_freq_end(ds_handle *h);
+/* The same aggregation on the CPU from the same row routine (csrc/ds_freq.h), one pass in row order: a CHECKER like
+ * ds_parse_text_reference, no handle, no GPU, not a fall-back. status is in / out: a row whose status is DS_FREQ_ROW_GIVEN on
+ * entry takes chrom / pos / p0 / p1 / met from the caller's arrays; every other row is parsed and its values and status are
+ * written (DS_TEXT_ROW_HOST rows take no part in the sums). Sites come out in the order of their first used row. Returns the
+ * number of sites; errors (DS_ERR_INVALID, cap too small among them) leave their message in ds_last_error(NULL). */
+#define DS_FREQ_ROW_GIVEN 2
+int64_t ds_freq_reference(const char *text, int64_t nrows, const int64_t *row_begin, const int64_t *row_end, const int32_t *chrom,
+                          const uint8_t *flags, double prob_cf, int32_t *status, int64_t *pos, double *p0, double *p1, int32_t *met,
+                          int64_t cap, int64_t *first_row, int32_t *site_chrom, int64_t *site_pos, double *sum0, double *sum1,
+                          int32_t *site_met, int32_t *site_unmet, int64_t *used);
+/* Device milliseconds summed over *batches accumulated batches since ds_create: ms[0] the copies (text, row spans, overrides,
+ * status), ms[1] freq_parse_kernel, ms[2] the bitonic sort, ms[3] freq_insert_kernel + freq_accumulate_kernel. Every batch is
+ * timed. reset != 0 clears the sums. */
+int ds_get_freq_times(ds_handle *h, int32_t reset, int64_t *batches, double *ms);
+
 /* Use a captured hipGraph for the forward (default on). */
 int ds_set_graph(ds_handle *h, int32_t enable);
 

@@ -1,0 +1,89 @@
+"""Shared by the frequency tests (CPU and GPU): synthetic call_mods result files, and the CPU checker ds_freq_reference put
+behind the interface calculate_mods_frequency_gpu drives, so the Python half of `--on gpu` runs without a GPU."""
+import struct
+
+import numpy as np
+
+from deepsignal_amd import engine as eng
+
+KMER = "ACGTACGTCGACGTACG"
+
+
+def bits(x: float) -> bytes:
+    return struct.pack("<d", x)
+
+
+def call_row(chrom, pos, p0, p1, label=None, strand="+", pis=None, read="read0", kmer=KMER) -> str:
+    """One result row; p0 / p1 are written as given when they are text, else as str(np.float32)."""
+    t0 = p0 if isinstance(p0, str) else str(np.float32(p0))
+    t1 = p1 if isinstance(p1, str) else str(np.float32(p1))
+    if pis is None:
+        pis = 1000 - pos if isinstance(pos, int) else 7
+    if label is None and not (isinstance(p0, str) or isinstance(p1, str)):
+        label = int(float(t1) > float(t0))
+    return "\t".join([chrom, str(pos), strand, str(pis), read, "t", t0, t1, str(1 if label is None else label), kmer])
+
+
+def random_rows(seed: int, nrows: int, nsites: int, nchrom: int):
+    """nrows rows over at most nsites sites of nchrom chromosomes, scattered; probabilities as call_mods prints them
+    (str(np.float32) of p and of 1 - p, now and then a tiny one in exponent form)."""
+    rng = np.random.default_rng(seed)
+    sites = [("chr%d" % rng.integers(1, nchrom + 1), int(rng.integers(0, 5000))) for _ in range(nsites)]
+    rows = []
+    for r in range(nrows):
+        chrom, pos = sites[int(rng.integers(0, nsites))]
+        p = np.float32(rng.random()) if rng.random() > 0.05 else np.float32(10.0 ** -rng.uniform(4, 9))
+        rows.append(call_row(chrom, pos, np.float32(1) - p, p, read="read%d" % r))
+    return rows
+
+
+def stats_tuple(stats):
+    """SiteStats dict -> comparable list in dict order: key, text fields, the sums' bits, the counts."""
+    return [(k, s.strand, s.pos_in_strand, s.kmer, bits(s.prob_0), bits(s.prob_1), s.met, s.unmet, s.coverage)
+            for k, s in stats.items()]
+
+
+class ReferenceBackend:
+    """freq_begin .. freq_end of Engine on top of ds_freq_reference: the batches are remembered and the checker makes its one
+    pass in row order over all of them when the result is asked for."""
+
+    def __init__(self):
+        self.batches = []
+        self.cf = 0.0
+
+    def freq_begin(self, total_rows, batch_rows, prob_cf=0.0):
+        self.total, self.batch, self.cf = total_rows, batch_rows, prob_cf
+
+    def freq_parse(self, text, begin, end, chrom, flags):
+        assert 1 <= len(begin) <= self.batch
+        lo, hi = int(begin[0]), int(end[-1])
+        chunk = np.asarray(text[lo:hi]).tobytes()
+        b, e = np.asarray(begin, np.int64) - lo, np.asarray(end, np.int64) - lo
+        status = eng.freq_reference(chunk, b, e, chrom, flags, self.cf)["status"]
+        self.batches.append([chunk, b, e, np.array(chrom, np.int32), np.array(flags, np.uint8), {}])
+        return status
+
+    def freq_accumulate(self, rows=(), chrom=(), pos=(), p0=(), p1=(), met=()):
+        self.batches[-1][5] = {int(r): (int(c), int(q), float(a), float(b), int(m))
+                               for r, c, q, a, b, m in zip(rows, chrom, pos, p0, p1, met)}
+
+    def freq_result(self):
+        text, begin, end, chrom, flags, given, off, row = [], [], [], [], [], {}, 0, 0
+        for chunk, b, e, c, f, g in self.batches:
+            text.append(chunk); begin.append(b + off); end.append(e + off); chrom.append(c); flags.append(f)
+            given.update({row + r: v for r, v in g.items()})
+            off += len(chunk); row += len(b)
+        out = eng.freq_reference(b"".join(text), np.concatenate(begin), np.concatenate(end), np.concatenate(chrom),
+                                 np.concatenate(flags), self.cf, given)
+        assert not (out["status"] != eng.TEXT_ROW_OK).any(), "a host row got no values"
+        return {"first_row": out["first_row"], "chrom": out["chrom"], "pos": out["pos"], "sum0": out["sum0"], "sum1": out["sum1"],
+                "met": out["met"], "unmet": out["unmet"], "rows": row, "used": out["used"]}
+
+    def freq_times(self, reset=False):
+        return {}
+
+    def freq_end(self):
+        pass
+
+    def close(self):
+        pass

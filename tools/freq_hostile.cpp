@@ -1,0 +1,68 @@
+// freq_hostile.cpp — the host half of call_freq --on gpu (ds_freq_locate, and dsf::reference behind ds_freq_reference) over hostile
+// buffers, as a stand-alone program for a host sanitizer build. Every buffer is copied into a heap block of exactly its size, so a
+// read past either end is a report. Build and run (host code only; nothing here touches a GPU):
+//   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
+//         -x hip tools/freq_hostile.cpp deepsignal_amd/csrc/ds_freq.hip deepsignal_amd/csrc/ds_io.cpp -o freq_hostile && ./freq_hostile
+#include "../include/deepsignal_hip.h"
+#include "../deepsignal_amd/csrc/ds_freq.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+static int run(const std::string& data, const char* what)
+{
+    char* buf = static_cast<char*>(malloc(data.size() ? data.size() : 1));
+    memcpy(buf, data.data(), data.size());
+    const char* text = data.size() ? buf : nullptr;
+    int64_t nb = 0;
+    int32_t nn = 0;
+    const int64_t n = ds_freq_locate(text, (int64_t)data.size(), 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &nb, &nn);
+    if (n < 0) { printf("%s: locate failed\n", what); return 1; }
+    std::vector<int64_t> b((size_t)n + 1), e((size_t)n + 1), pos((size_t)n + 1), first((size_t)n + 1), spos((size_t)n + 1);
+    std::vector<int32_t> chrom((size_t)n + 1), status((size_t)n + 1, 0), met((size_t)n + 1), schrom((size_t)n + 1), smet((size_t)n + 1), sunmet((size_t)n + 1);
+    std::vector<uint8_t> flags((size_t)n + 1);
+    std::vector<double> p0((size_t)n + 1), p1((size_t)n + 1), s0((size_t)n + 1), s1((size_t)n + 1);
+    char* names = static_cast<char*>(malloc(nb ? (size_t)nb : 1));
+    const int64_t n2 = ds_freq_locate(text, (int64_t)data.size(), n, b.data(), e.data(), chrom.data(), flags.data(), names, nb, &nb, &nn);
+    int64_t used = 0;
+    std::string err;
+    const int64_t sites = dsf::reference(text ? text : "", n, b.data(), e.data(), chrom.data(), flags.data(), 0.1, status.data(), pos.data(), p0.data(),
+                                         p1.data(), met.data(), n, first.data(), schrom.data(), spos.data(), s0.data(), s1.data(), smet.data(),
+                                         sunmet.data(), &used, &err);
+    int64_t host = 0;
+    for (int64_t i = 0; i < n; ++i) host += status[(size_t)i] != 0;
+    printf("%-28s %6lld bytes %4lld rows %3d names %4lld host rows %4lld sites %4lld used\n", what, (long long)data.size(), (long long)n, nn,
+           (long long)host, (long long)sites, (long long)used);
+    free(names);
+    free(buf);
+    return n2 == n && sites >= 0 ? 0 : 1;
+}
+
+int main()
+{
+    const std::string good = "chr1\t10\t+\t990\tread0\tt\t0.25\t0.75\t1\tACGTACGTCGACGTACG";
+    auto row = [](const std::string& pos, const std::string& p0, const std::string& p1, const std::string& label) {
+        return "chr2\t" + pos + "\t-\t7\tread1\tt\t" + p0 + "\t" + p1 + "\t" + label + "\tACGTACGTCGACGTACG";
+    };
+    std::vector<std::string> rows = {good, good, row("5", "nan", "0.5", "1"), row("5", "inf", "0.5", "1"), row("5", "1e-30", "0.5", "0"),
+                                     row("5", "+0.5", "0.5", "1"), " " + good, good + "\r", "a\rb", "", "\t", "\t\t\t\t\t\t\t\t\t", good + "\t", row("1099511627776", "0.1", "0.9", "1"),
+                                     row("-1", "0.1", "0.9", "1"), row("1099511627775", "0.1", "0.9", "1"), row("999999999999999999999", "0.1", "0.9", "1"),
+                                     row("5", "1234567890123456", "0.9", "1"), row("5", "1e22", "1e-22", "1"), row("5", "1e23", "1e-23", "1"),
+                                     row("5", "1e", ".", "-"), row("5", "0.1", "0.9", "1234567890"), row("5", "0.1", "0.9", ""), "chr\xc3\xa9\t1\t+\t2", good.substr(0, 40),
+                                     row("5", "1e99999999999999999999", "0.9", "1"), row("5", "-", "-", "-"), std::string(5000, '7'), std::string(300, '\t'), good};
+    std::string all;
+    for (const std::string& r : rows) all += r + "\n";
+    int bad = 0;
+    bad += run(all, "hostile rows");
+    bad += run(all.substr(0, all.size() - 1), "no trailing newline");
+    bad += run("", "empty");
+    bad += run("\n", "one blank row");
+    bad += run(good, "one row, no newline");
+    for (size_t cut = 0; cut <= good.size() + 1; ++cut) bad += run((good + "\n" + good).substr(0, good.size() + 1 + cut), "truncated");
+    for (size_t cut = 1; cut < all.size(); cut += 37) bad += run(all.substr(0, cut), "truncated hostile");
+    printf(bad ? "FAILED\n" : "all buffers done\n");
+    return bad ? 1 : 0;
+}
