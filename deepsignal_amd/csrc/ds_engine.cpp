@@ -119,14 +119,31 @@ struct Plan {
                                           // recur, and the per-slot plan cache is bounded (get_plan)
 };
 
+enum class Ticket { Idle, Forward, Text, Rows };      // what a slot carries: nothing, or a ticket for ds_wait | ds_wait_text | ds_wait_rows
+template <int K>
+struct Times {           // what a ds_get_*_times getter reports: batches timed so far and their summed device milliseconds
+    int64_t batches = 0;
+    double ms[K] = {};
+    int get(int32_t reset, int64_t* n, double* out)
+    {
+        if (!n || !out) return DS_ERR_INVALID;
+        *n = batches;
+        std::copy(ms, ms + K, out);
+        if (reset) *this = Times();
+        return DS_OK;
+    }
+};
+struct Block { char* p = nullptr; size_t cap = 0; };   // pinned host or device memory of a slot that grows with its batches (grow())
+
 }  // namespace
 
-// One in-flight forward: private workspace, stream pair, fork/join events and captured graphs.
+// One pipeline slot: private workspace, stream pair, fork/join events and captured graphs, and the staging blocks of every route
+// through it. All work of a slot is enqueued on s0 (the forward forks to s1 and joins back), so a drained s0 is an idle slot.
 struct Slot {
     hipStream_t s0 = nullptr, s1 = nullptr;
     bool owns_s1 = true;                 // false: DS_TUNE_SHARED_EVENT_STREAM -- s1 is slot 0's event-model stream
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    float* d_in = nullptr;               // [kmer | means | stds | sanums | signals] (the five pointers below point into it)
+    float* d_in = nullptr;               // [kmer | means | stds | sanums | signals] (InLayout; the five pointers below point into it)
     int* d_kmer = nullptr;
     float *d_means = nullptr, *d_stds = nullptr, *d_sanums = nullptr, *d_signals = nullptr;
     float *stem_pool = nullptr, *conv2o = nullptr, *conv3o = nullptr;
@@ -144,41 +161,33 @@ struct Slot {
     float* joint = nullptr;              // bf16 mode: [B][JP] bf16 FC operand (event features | signal features | zero pad)
     char* jsplit = nullptr;              // DS_PRECISION_BF16X3, three-step joint model: the joint rows as a fragment-major term image
 
-    // ds_submit / ds_wait: pinned host staging of one batch (inputs in, 12 B/site out), allocated on first use
+    // The ticket in flight and its site count: read and written only by the helpers under "pipeline slots" below. A submit takes
+    // the idle slot next_slot points at, stages its inputs, advances next_slot and holds the slot; the wait of the ticket's kind
+    // releases it. The blocking diagnostics borrow the idle slot and leave it idle.
+    Ticket ticket = Ticket::Idle;
+    int submitted_n = 0;
+    // Staging blocks, each allocated at the first call that needs it.
+    // every forward route: the pinned image of d_in (stage_host_inputs) and of [act | pred] (pin_pred points into pin_act)
     char* pin_in = nullptr;
     float* pin_act = nullptr;
     int* pin_pred = nullptr;
-    int submitted_n = -1;                 // sites of the forward in flight on this slot (-1: none)
-    // ds_submit_reads / ds_extract: the packed reads (pinned image and its device copy + histograms), grown while the slot is idle
-    char* pin_reads = nullptr;
-    size_t pin_reads_cap = 0;
-    char* d_reads = nullptr;
-    size_t d_reads_cap = 0;
-    // ds_submit_rows / ds_extract_rows: allocated at the slot's first rows call. d_rows = [float64 values | row offsets | row
-    // lengths | text sized for the longest rows max_batch sites can have]; pin_rows grows to the largest text a ticket returned
-    bool rows_ticket = false;             // the ticket in flight is a rows ticket (ds_wait_rows), not a forward (ds_wait)
-    char* d_rows = nullptr;
-    size_t d_rows_cap = 0, d_rows_info = 0;
+    // reads (ds_submit_reads / ds_extract and the rows calls): the packed reads, pinned image and device copy + histograms
+    Block pin_reads, d_reads;
+    // rows (ds_submit_rows / ds_extract_rows): d_rows = RowsLayout, pin_rowoff = row offsets [B + 1], pin_rows = the longest text so far
+    Block d_rows, pin_rows;
     int64_t* pin_rowoff = nullptr;
-    char* pin_rows = nullptr;
-    size_t pin_rows_cap = 0;
-    // ds_set_recheck: allocated at the handle's first attachment. d_rc = [count, 3 pad | index[B] | the selected sites' inputs,
-    // an image of d_in | the fine handle's act[B][C] | pred[B]]; pin_rc = [count, 3 pad | index[B] | fine act | fine pred]
+    // recheck (ds_set_recheck), every slot's at the handle's first attachment: d_rc / pin_rc = RcLayout
     char* d_rc = nullptr;
     int* pin_rc = nullptr;
     hipEvent_t rc_ev[2] = {nullptr, nullptr};   // around recheck_select_kernel of a profiled forward (ds_get_recheck_times)
-    bool rc_selected = false;             // the forward in flight carries a selection (a recheck was attached when it was submitted)
+    bool rc_selected = false;             // the forward enqueued last carries a selection (a recheck was attached then)
     bool rc_timed = false;
-    // ds_submit_text / ds_parse_text: allocated at the slot's first text call. pin_text / d_text = [int64 off[B] | int32 len[B] |
-    // the rows' text, DS_TEXT_BYTES_PER_ROW x B bytes and one parse step of pad]; d_tres / pin_tres = [status[B] | label[B] |
+    // text (ds_submit_text / ds_parse_text): pin_text / d_text = TxLayout; d_tres / pin_tres = [status[B] | label[B] |
     // info_len[B]], the pinned one followed by the k-mer codes [B][T]
-    bool text_ticket = false;             // the ticket in flight is a text ticket (ds_wait_text)
-    char* pin_text = nullptr;
-    char* d_text = nullptr;
-    int32_t* d_tres = nullptr;
-    int32_t* pin_tres = nullptr;
+    char *pin_text = nullptr, *d_text = nullptr;
+    int32_t *d_tres = nullptr, *pin_tres = nullptr;
     hipEvent_t tx_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // around the text's H2D, the parse kernel, the results' D2H
-    std::vector<std::pair<const char*, const char*>> text_rows;  // the caller's rows of the ticket in flight (info columns, host route)
+    std::vector<std::pair<const char*, const char*>> text_rows;  // the caller's rows of the text ticket (info columns, host route)
 
     std::map<int, Plan> plans;
     int last_n = 0;
@@ -243,21 +252,17 @@ struct ds_handle {
     unsigned long long* dbg_lstm = nullptr;     // [32 diagonals][1024 wgs][8] stamps of the fp32 BiLSTM cell launches
     std::vector<Stage> stages;
     KernelStat kstat[K_COUNT];
-    int64_t rows_batches = 0;             // ds_extract_rows calls timed while profiling is on, and their summed device milliseconds:
-    double rows_ms[5] = {0, 0, 0, 0, 0};  // statistics, values, lengths + scan, format kernels; text device-to-host copy
+    Times<5> rows_t;      // profiled ds_extract_rows calls: statistics, values, lengths + scan, format kernels; text D2H copy
     // cascaded precision (ds_set_recheck): sites of this handle's forwards within rc_margin of the threshold are run again on
     // rc_fine (caller-owned) and its results replace this handle's for them
     ds_handle* rc_fine = nullptr;
     float rc_margin = 0.f;
     int64_t rc_sites = 0, rc_rechecked = 0, rc_forwards = 0;      // since the attachment
     int64_t tx_rows = 0, tx_host_rows = 0;   // rows through ds_submit_text / ds_parse_text, and those the host parser took
-    int64_t tx_batches = 0;               // text batches timed (every one: three event pairs per batch), and their summed device ms:
-    double tx_ms[3] = {0, 0, 0};          // H2D of the text, tsv_parse_kernel, D2H of status / label / info length / k-mer
-    int64_t rc_launches = 0;              // recheck_select_kernel launches timed while profiling was on, and their summed device ms
-    double rc_ms = 0;
+    Times<3> tx_t;        // text batches, every one: H2D of the text, tsv_parse_kernel, D2H of status / label / info length / k-mer
+    Times<1> rc_t;        // recheck_select_kernel launches timed while profiling was on
     dsf::Freq* freq = nullptr;            // call_freq --on gpu: the open run (ds_freq_begin .. ds_freq_end); its table and buffers are its own
-    int64_t fq_batches = 0;               // batches of the runs ended so far, and their device ms (the open run's are added on top)
-    double fq_ms[4] = {0, 0, 0, 0};
+    Times<4> fq_t;        // batches of the frequency runs ended so far (the open run's are added on top)
     // pipelining: consecutive forwards rotate over independent slots (own workspace, streams, graphs), so the
     // dependency chain of one 512-site forward overlaps the next ones'; weights are shared
     std::vector<Slot> slots;
@@ -284,22 +289,66 @@ int fail(ds_handle* h, int code, const std::string& msg)
         }                                                                                                \
     } while (0)
 
+// Every hipMalloc of the library. hipGetLastError() returns (and clears) the thread's last error; every launcher ends with it.
+// Left in place, a failed hipMalloc would be reported by the first launch of the NEXT handle this thread creates
+// (call_modifications.make_engine's fall-back to the user's batch size after an out-of-memory ds_create)
+int dev_malloc(ds_handle* h, void** p, size_t bytes)
+{
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) return DS_OK;
+    (void)hipGetLastError();
+    return fail(h, DS_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+}
+
 template <class T>
-int dalloc(ds_handle* h, T** p, size_t count)
+int dalloc(ds_handle* h, T** p, size_t count)      // device memory that lives as long as the handle
 {
     void* q = nullptr;
-    size_t bytes = std::max<size_t>(count * sizeof(T), 256);
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) {
-        // hipGetLastError() returns (and clears) the thread's last error; every launcher ends with it. Left in place, a failed
-        // hipMalloc would be reported by the first launch of the NEXT handle this thread creates (call_modifications.make_engine's
-        // fall-back to the user's batch size after an out-of-memory ds_create)
-        (void)hipGetLastError();
-        return fail(h, DS_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    }
+    int rc = dev_malloc(h, &q, std::max<size_t>(count * sizeof(T), 256));
+    if (rc) return rc;
     h->allocs.push_back(q);
     *p = static_cast<T*>(q);
     return DS_OK;
+}
+
+// b holds `need` bytes when this returns DS_OK: a block too small is replaced by one of need + slack bytes, its contents lost.
+// sl.s0 is drained first: nothing enqueued on the slot may still read the old block.
+int grow(ds_handle* h, Slot& sl, Block& b, size_t need, size_t slack, bool pinned)
+{
+    if (need <= b.cap) return DS_OK;
+    HIPCHK(h, hipStreamSynchronize(sl.s0));
+    if (b.p) HIPCHK(h, pinned ? hipHostFree(b.p) : hipFree(b.p));
+    b = Block();
+    if (pinned) HIPCHK(h, hipHostMalloc((void**)&b.p, need + slack, hipHostMallocDefault));
+    else if (int rc = dev_malloc(h, (void**)&b.p, need + slack)) return rc;
+    b.cap = need + slack;
+    return DS_OK;
+}
+
+template <int N>
+struct CallEvents {      // the profiling events of one blocking call: destroyed when it returns, whichever way it does
+    hipEvent_t ev[N] = {};
+    hipError_t create()
+    {
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < N && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+        return e;
+    }
+    ~CallEvents() { for (hipEvent_t e : ev) if (e) hipEventDestroy(e); }
+};
+
+// The inputs of a forward as ONE block pitched for max_batch sites, [kmer | means | stds | sanums | signals]: Slot::d_in, its
+// pinned image Slot::pin_in (a full batch arrives with one H2D copy) and the compacted inputs of the recheck block.
+struct InLayout { size_t at[5], row[5], total; };      // per array: byte offset in the block, bytes per site; bytes of the block
+InLayout in_layout(const ds_handle* h)
+{
+    InLayout L{};
+    for (int k = 0; k < 5; ++k) {
+        L.at[k] = L.total;
+        L.row[k] = 4 * (size_t)(k < 4 ? h->T : h->S);
+        L.total += (size_t)h->B * L.row[k];
+    }
+    return L;
 }
 
 int upload(ds_handle* h, float** dst, const std::vector<float>& v)
@@ -623,11 +672,12 @@ int alloc_workspace(ds_handle* h)
     auto A = [&](auto** p, size_t count) { if (!rc) rc = dalloc(h, p, count); };
     // inputs of a forward: ONE block [kmer | means | stds | sanums | signals], every region sized for max_batch -- the image
     // of the pinned staging buffer of ds_submit, so a full batch arrives with one H2D copy
-    A(&h->cur->d_in, B * (4 * h->T + h->S));
+    const InLayout L = in_layout(h);
+    A(&h->cur->d_in, L.total / 4);
     if (!rc) {
-        h->cur->d_kmer = reinterpret_cast<int*>(h->cur->d_in);
-        h->cur->d_means = h->cur->d_in + B * h->T; h->cur->d_stds = h->cur->d_in + 2 * B * h->T;
-        h->cur->d_sanums = h->cur->d_in + 3 * B * h->T; h->cur->d_signals = h->cur->d_in + 4 * B * h->T;
+        auto at = [&](int k) { return reinterpret_cast<float*>(reinterpret_cast<char*>(h->cur->d_in) + L.at[k]); };
+        h->cur->d_kmer = reinterpret_cast<int*>(at(0));
+        h->cur->d_means = at(1); h->cur->d_stds = at(2); h->cur->d_sanums = at(3); h->cur->d_signals = at(4);
     }
     A(&h->cur->stem_pool, B * h->wa * 64); A(&h->cur->conv2o, B * h->wa * 128); A(&h->cur->conv3o, B * h->wa * 256);
     A(&h->cur->pool2, B * h->wb * INC_OUT); A(&h->cur->pool3, B * h->wc * INC_OUT);
@@ -1541,19 +1591,11 @@ void ds_destroy(ds_handle* h)
             if (kv.second.graph) hipGraphExecDestroy(kv.second.graph);
             for (Op& op : kv.second.ops) { if (op.ev0) hipEventDestroy(op.ev0); if (op.ev1) hipEventDestroy(op.ev1); }
         }
-        if (sl.pin_in) hipHostFree(sl.pin_in);
-        if (sl.pin_reads) hipHostFree(sl.pin_reads);
-        if (sl.d_reads) hipFree(sl.d_reads);
-        if (sl.d_rows) hipFree(sl.d_rows);
-        if (sl.pin_rowoff) hipHostFree(sl.pin_rowoff);
-        if (sl.pin_rows) hipHostFree(sl.pin_rows);
-        if (sl.pin_act) hipHostFree(sl.pin_act);       // pin_pred points into it
-        if (sl.d_rc) hipFree(sl.d_rc);
-        if (sl.pin_rc) hipHostFree(sl.pin_rc);
-        if (sl.pin_text) hipHostFree(sl.pin_text);
-        if (sl.d_text) hipFree(sl.d_text);
-        if (sl.d_tres) hipFree(sl.d_tres);
-        if (sl.pin_tres) hipHostFree(sl.pin_tres);
+        for (void* p : {(void*)sl.pin_in, (void*)sl.pin_act /* pin_pred points into it */, (void*)sl.pin_rowoff, (void*)sl.pin_rc,
+                        (void*)sl.pin_text, (void*)sl.pin_tres, (void*)sl.pin_reads.p, (void*)sl.pin_rows.p})
+            if (p) hipHostFree(p);
+        for (void* p : {(void*)sl.d_rc, (void*)sl.d_text, (void*)sl.d_tres, (void*)sl.d_reads.p, (void*)sl.d_rows.p})
+            if (p) hipFree(p);
         for (hipEvent_t e : sl.tx_ev) if (e) hipEventDestroy(e);
         for (hipEvent_t e : sl.rc_ev) if (e) hipEventDestroy(e);
         if (sl.ev_fork) hipEventDestroy(sl.ev_fork);
@@ -1672,6 +1714,136 @@ int ds_sync(ds_handle* h)
 static int enqueue_recheck(ds_handle* h, Slot& sl, int n);
 static int finish_recheck(ds_handle* h, Slot& sl, int n, float* act, int32_t* pred);
 
+// ---- pipeline slots: the ticket lifecycle and the forward's staging, shared by every route ------------------------------------
+// A forward route is: idle_slot, its inputs staged on sl.s0, submit_forward; its wait: ticket_slot, take_results, its own decoding.
+// Nothing outside this section reads or writes Slot::ticket / submitted_n.
+
+// The slot the next submit takes, with the handle's device selected. next_slot is not advanced: the blocking diagnostics only
+// borrow the slot.
+static int idle_slot(ds_handle* h, const char* who, Slot** sl)
+{
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int si = (int)(h->next_slot % h->slots.size());
+    if (h->slots[si].ticket != Ticket::Idle)
+        return fail(h, DS_ERR_INVALID, std::string(who) + ": every slot is in flight; wait the oldest ticket first");
+    *sl = &h->slots[si];
+    return DS_OK;
+}
+
+// the slot carries a ticket of n sites from here, and the caller gets its number
+static void hold(ds_handle* h, Slot& sl, Ticket kind, int n, int32_t* ticket)
+{
+    sl.ticket = kind;
+    sl.submitted_n = n;
+    *ticket = (int32_t)(&sl - h->slots.data());
+}
+
+static void release(Slot& sl) { sl.ticket = Ticket::Idle; sl.submitted_n = 0; }
+
+static bool tickets_in_flight(const ds_handle* h)
+{
+    return std::any_of(h->slots.begin(), h->slots.end(), [](const Slot& sl) { return sl.ticket != Ticket::Idle; });
+}
+
+// The slot of a ticket of the given kind and its site count, with the handle's device selected. A wait of another kind is
+// refused and the ticket stays collectable.
+static int ticket_slot(ds_handle* h, const char* who, int32_t ticket, Ticket kind, Slot** sl, int* n)
+{
+    static const char* const carries[] = {"nothing", "forward", "text rows", "rows"};
+    if (ticket < 0 || ticket >= (int)h->slots.size() || h->slots[ticket].ticket != kind)
+        return fail(h, DS_ERR_INVALID, std::string(who) + ": no " + carries[(int)kind] + " in flight for this ticket");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    *sl = &h->slots[ticket];
+    *n = (*sl)->submitted_n;
+    return DS_OK;
+}
+
+// Host arrays, given as nparts row segments of counts[i] sites, -> the slot's pinned image -> its device inputs on sl.s0: one
+// copy when the batch is full (the image is the device block's), one per array otherwise.
+static int stage_host_inputs(ds_handle* h, Slot& sl, int nparts, const int32_t* counts, const int32_t* const* kmer, const float* const* means,
+                             const float* const* stds, const float* const* sanums, const float* const* signals)
+{
+    const InLayout L = in_layout(h);
+    if (!sl.pin_in) HIPCHK(h, hipHostMalloc((void**)&sl.pin_in, L.total, hipHostMallocDefault));
+    char* dev = reinterpret_cast<char*>(sl.d_in);
+    size_t n = 0;
+    for (int i = 0; i < nparts; ++i) {
+        const size_t c = (size_t)counts[i];
+        if (!c) continue;
+        const void* src[5] = {kmer[i], means[i], stds[i], sanums[i], signals[i]};
+        for (int k = 0; k < 5; ++k) memcpy(sl.pin_in + L.at[k] + n * L.row[k], src[k], c * L.row[k]);
+        n += c;
+    }
+    if (n == (size_t)h->B) {
+        HIPCHK(h, hipMemcpyAsync(dev, sl.pin_in, L.total, hipMemcpyHostToDevice, sl.s0));
+        return DS_OK;
+    }
+    for (int k = 0; k < 5; ++k)
+        HIPCHK(h, hipMemcpyAsync(dev + L.at[k], sl.pin_in + L.at[k], n * L.row[k], hipMemcpyHostToDevice, sl.s0));
+    return DS_OK;
+}
+
+// behind the slot's inputs on sl.s0: the forward of n sites and, with a recheck attached, the selection
+static int enqueue_forward_on(ds_handle* h, Slot& sl, int n)
+{
+    if (!sl.pin_act) {       // where enqueue_results puts [act | pred]
+        HIPCHK(h, hipHostMalloc((void**)&sl.pin_act, ((size_t)h->B * h->C + h->B) * 4, hipHostMallocDefault));
+        sl.pin_pred = reinterpret_cast<int*>(sl.pin_act + (size_t)h->B * h->C);
+    }
+    h->cur = &sl;
+    int rc = run_resident(h, n);
+    return rc ? rc : enqueue_recheck(h, sl, n);
+}
+
+// behind enqueue_forward_on (and a route's own result copies): [act (max_batch rows) | pred (n)] to the pinned block, one copy
+static int enqueue_results(ds_handle* h, Slot& sl, int n)
+{
+    HIPCHK(h, hipMemcpyAsync(sl.pin_act, sl.act, ((size_t)h->B * h->C + (size_t)n) * 4, hipMemcpyDeviceToHost, sl.s0));
+    return DS_OK;
+}
+
+static int enqueue_forward_and_results(ds_handle* h, Slot& sl, int n)
+{
+    int rc = enqueue_forward_on(h, sl, n);
+    return rc ? rc : enqueue_results(h, sl, n);
+}
+
+// The tail of a submit whose n sites are staged: the slot is taken (only now: a refused batch consumes none), the forward and
+// its results follow the inputs, and the slot holds a forward ticket. A failure leaves the slot idle.
+static int submit_forward(ds_handle* h, Slot& sl, int n, int32_t* ticket)
+{
+    h->next_slot++;
+    int rc = enqueue_forward_and_results(h, sl, n);
+    if (!rc) hold(h, sl, Ticket::Forward, n, ticket);
+    return rc;
+}
+
+// The results of the n sites enqueue_results left in the pinned block. The slot is idle from the copy out of that block on -- the
+// rechecks run on the fine handle, and ds_wait_text forwards its host rows on this very slot -- but the ticket is complete only once
+// its rechecks are merged.
+static int take_results(ds_handle* h, Slot& sl, int n, float* act, int32_t* pred)
+{
+    HIPCHK(h, hipStreamSynchronize(sl.s0));
+    memcpy(act, sl.pin_act, (size_t)n * h->C * 4);
+    memcpy(pred, sl.pin_pred, (size_t)n * 4);
+    release(sl);
+    return finish_recheck(h, sl, n, act, pred);
+}
+
+// the inputs of the slot's n sites -> the caller's arrays (InLayout's order; a null one is skipped), and sl.s0 drained
+static int inputs_to_host(ds_handle* h, Slot& sl, const char* who, size_t n, void* const (&dst)[5])
+{
+    const InLayout L = in_layout(h);
+    const char* in = reinterpret_cast<const char*>(sl.d_in);
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 5 && e == hipSuccess; ++k)
+        if (dst[k]) e = hipMemcpyAsync(dst[k], in + L.at[k], n * L.row[k], hipMemcpyDeviceToHost, sl.s0);
+    if (e == hipSuccess) e = hipStreamSynchronize(sl.s0);
+    if (e == hipSuccess) return DS_OK;
+    (void)hipGetLastError();
+    return fail(h, DS_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+}
+
 static int ds_forward_impl(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums,
                const float* signals, float* act, int32_t* pred)
 {
@@ -1685,8 +1857,7 @@ static int ds_forward_impl(ds_handle* h, int32_t n, const int32_t* kmer, const f
         // every pass goes through the asynchronous boundary: the batch is staged in the slot's pinned block (ONE H2D copy of
         // a full batch, one D2H copy of [act | pred]; five pageable copies in and two out before), and a call of more than
         // max_batch sites keeps up to `slots` passes in flight, results copied out in order
-        for (Slot& sl : h->slots)
-            if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_forward: ds_submit tickets are still in flight");
+        if (tickets_in_flight(h)) return fail(h, DS_ERR_INVALID, "ds_forward: ds_submit tickets are still in flight");
         const int nslots = (int)h->slots.size();
         std::vector<int32_t> tickets;
         size_t tail = 0;
@@ -1714,9 +1885,7 @@ static int ds_forward_impl(ds_handle* h, int32_t n, const int32_t* kmer, const f
             for (Slot& sl : h->slots) {
                 if (sl.s0) hipStreamSynchronize(sl.s0);
                 if (sl.s1) hipStreamSynchronize(sl.s1);
-                sl.submitted_n = -1;
-                sl.rows_ticket = false;
-                sl.text_ticket = false;
+                release(sl);
                 sl.rc_selected = false;
             }
             h->err = msg;
@@ -1724,24 +1893,24 @@ static int ds_forward_impl(ds_handle* h, int32_t n, const int32_t* kmer, const f
         return rc;
     }
     // profiling runs stay on slot 0 with plain copies, so that the event statistics are coherent
+    const InLayout L = in_layout(h);
+    Slot& sl = h->slots[0];
     for (int off = 0; off < n; off += h->B) {
         const int m = std::min(h->B, n - off);
-        h->cur = &h->slots[0];
-        const size_t mt = (size_t)m * h->T, ot = (size_t)off * h->T;
-        HIPCHK(h, hipMemcpyAsync(h->cur->d_kmer, kmer + ot, mt * 4, hipMemcpyHostToDevice, h->cur->s0));
-        HIPCHK(h, hipMemcpyAsync(h->cur->d_means, means + ot, mt * 4, hipMemcpyHostToDevice, h->cur->s0));
-        HIPCHK(h, hipMemcpyAsync(h->cur->d_stds, stds + ot, mt * 4, hipMemcpyHostToDevice, h->cur->s0));
-        HIPCHK(h, hipMemcpyAsync(h->cur->d_sanums, sanums + ot, mt * 4, hipMemcpyHostToDevice, h->cur->s0));
-        HIPCHK(h, hipMemcpyAsync(h->cur->d_signals, signals + (size_t)off * h->S, (size_t)m * h->S * 4, hipMemcpyHostToDevice, h->cur->s0));
+        h->cur = &sl;
+        const char* src[5] = {(const char*)kmer, (const char*)means, (const char*)stds, (const char*)sanums, (const char*)signals};
+        for (int k = 0; k < 5; ++k)
+            HIPCHK(h, hipMemcpyAsync(reinterpret_cast<char*>(sl.d_in) + L.at[k], src[k] + (size_t)off * L.row[k], (size_t)m * L.row[k],
+                                     hipMemcpyHostToDevice, sl.s0));
         int rc = run_resident(h, m);
         if (rc) return rc;
-        rc = enqueue_recheck(h, *h->cur, m);
+        rc = enqueue_recheck(h, sl, m);
         if (rc) return rc;
-        HIPCHK(h, hipMemcpyAsync(act + (size_t)off * h->C, h->cur->act, (size_t)m * h->C * 4, hipMemcpyDeviceToHost, h->cur->s0));
-        HIPCHK(h, hipMemcpyAsync(pred + off, h->cur->pred, (size_t)m * 4, hipMemcpyDeviceToHost, h->cur->s0));
+        HIPCHK(h, hipMemcpyAsync(act + (size_t)off * h->C, sl.act, (size_t)m * h->C * 4, hipMemcpyDeviceToHost, sl.s0));
+        HIPCHK(h, hipMemcpyAsync(pred + off, sl.pred, (size_t)m * 4, hipMemcpyDeviceToHost, sl.s0));
         rc = ds_sync(h);
         if (rc) return rc;
-        rc = finish_recheck(h, *h->cur, m, act + (size_t)off * h->C, pred + off);
+        rc = finish_recheck(h, sl, m, act + (size_t)off * h->C, pred + off);
         if (rc) return rc;
     }
     return DS_OK;
@@ -1755,11 +1924,11 @@ static int ds_forward_impl(ds_handle* h, int32_t n, const int32_t* kmer, const f
 struct RcLayout { size_t index, in, act, pred, total, pin_act, pin_pred, pin_total; };
 static RcLayout rc_layout(const ds_handle* h)
 {
-    const size_t B = h->B, T = h->T, S = h->S, C = h->C;
+    const size_t B = h->B, C = h->C;
     RcLayout L;
     L.index = 16;
     L.in = L.index + 4 * B;
-    L.act = L.in + 4 * B * (4 * T + S);
+    L.act = L.in + in_layout(h).total;
     L.pred = L.act + 4 * B * C;              // [act | pred] contiguous: one copy back, as the forward's own results
     L.total = L.pred + 4 * B;
     L.pin_act = L.index + 4 * B;
@@ -1772,10 +1941,8 @@ static int alloc_recheck(ds_handle* h)
 {
     const RcLayout L = rc_layout(h);
     for (Slot& sl : h->slots) {
-        if (!sl.d_rc) {
-            hipError_t e = hipMalloc((void**)&sl.d_rc, L.total);
-            if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, DS_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
-        }
+        if (!sl.d_rc)
+            if (int rc = dev_malloc(h, (void**)&sl.d_rc, L.total)) return rc;
         if (!sl.pin_rc) HIPCHK(h, hipHostMalloc((void**)&sl.pin_rc, L.pin_total, hipHostMallocDefault));
         for (hipEvent_t& e : sl.rc_ev)
             if (!e) HIPCHK(h, hipEventCreate(&e));
@@ -1816,7 +1983,7 @@ static int finish_recheck(ds_handle* h, Slot& sl, int n, float* act, int32_t* pr
     if (!f) return fail(h, DS_ERR_INVALID, "recheck: the fine handle was detached while a forward was in flight");
     if (sl.rc_timed) {
         float ms = 0;
-        if (hipEventElapsedTime(&ms, sl.rc_ev[0], sl.rc_ev[1]) == hipSuccess) { h->rc_launches += 1; h->rc_ms += ms; }
+        if (hipEventElapsedTime(&ms, sl.rc_ev[0], sl.rc_ev[1]) == hipSuccess) { h->rc_t.batches += 1; h->rc_t.ms[0] += ms; }
         else (void)hipGetLastError();
     }
     const RcLayout L = rc_layout(h);
@@ -1825,15 +1992,16 @@ static int finish_recheck(ds_handle* h, Slot& sl, int n, float* act, int32_t* pr
     if (m < 0 || m > n) return fail(h, DS_ERR_INVALID, "recheck: selection count out of range");
     h->rc_sites += n;
     if (m == 0) return DS_OK;
-    const size_t T = h->T, S = h->S, C = h->C, B = h->B;
-    const float* in = reinterpret_cast<const float*>(sl.d_rc + L.in);
+    const size_t C = h->C, B = h->B;
+    const InLayout I = in_layout(h);
+    auto in = [&](int k, size_t site) { return sl.d_rc + L.in + I.at[k] + site * I.row[k]; };      // array k of the compacted inputs
     float* d_act = reinterpret_cast<float*>(sl.d_rc + L.act);
     int32_t* d_pred = reinterpret_cast<int32_t*>(sl.d_rc + L.pred);
     for (int off = 0; off < m; off += f->B) {
         const int mc = std::min(f->B, m - off);
         const size_t o = (size_t)off;
-        int rc = ds_forward_device(f, mc, reinterpret_cast<const int32_t*>(in) + o * T, in + B * T + o * T, in + 2 * B * T + o * T,
-                                   in + 3 * B * T + o * T, in + 4 * B * T + o * S, d_act + o * C, d_pred + off);
+        int rc = ds_forward_device(f, mc, (const int32_t*)in(0, o), (const float*)in(1, o), (const float*)in(2, o), (const float*)in(3, o),
+                                   (const float*)in(4, o), d_act + o * C, d_pred + off);
         if (rc) { ds_sync(f); return fail(h, rc, "recheck: the fine handle's forward failed: " + f->err); }
         h->rc_forwards += 1;
     }
@@ -1858,8 +2026,7 @@ static int ds_set_recheck_impl(ds_handle* c, ds_handle* f, float margin)
 {
     if (!c) return DS_ERR_INVALID;
     if (margin != margin) return fail(c, DS_ERR_INVALID, "ds_set_recheck: margin is NaN");
-    for (Slot& sl : c->slots)
-        if (sl.submitted_n >= 0) return fail(c, DS_ERR_INVALID, "ds_set_recheck: tickets are still in flight");
+    if (tickets_in_flight(c)) return fail(c, DS_ERR_INVALID, "ds_set_recheck: tickets are still in flight");
     if (!f || margin <= 0) {
         c->rc_fine = nullptr;
         c->rc_margin = 0.f;
@@ -1898,14 +2065,7 @@ int ds_get_recheck_stats(ds_handle* h, int64_t* sites, int64_t* rechecked, int64
     return DS_OK;
 }
 
-int ds_get_recheck_times(ds_handle* h, int32_t reset, int64_t* launches, double* ms)
-{
-    if (!h || !launches || !ms) return DS_ERR_INVALID;
-    *launches = h->rc_launches;
-    *ms = h->rc_ms;
-    if (reset) { h->rc_launches = 0; h->rc_ms = 0; }
-    return DS_OK;
-}
+int ds_get_recheck_times(ds_handle* h, int32_t reset, int64_t* launches, double* ms) { return h ? h->rc_t.get(reset, launches, ms) : DS_ERR_INVALID; }
 
 // Diagnostic: the selection of recheck_select_kernel for n rows of act given by the caller (directed values: the specials, every
 // lane / wave / workgroup pattern), on an idle slot. The rows it compacts are whatever the slot's inputs hold.
@@ -1914,10 +2074,11 @@ static int ds_recheck_select_impl(ds_handle* h, int32_t n, const float* act, flo
     if (!h) return DS_ERR_INVALID;
     if (!act || !count || !index || n < 1 || n > h->B) return fail(h, DS_ERR_INVALID, "ds_recheck_select: bad argument");
     if (h->C != 2) return fail(h, DS_ERR_UNSUPPORTED, "ds_recheck_select: the selection rule is defined for two classes");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    Slot& sl = h->slots[h->next_slot % h->slots.size()];
-    if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_recheck_select: every slot is in flight");
-    int rc = alloc_recheck(h);
+    Slot* idle = nullptr;
+    int rc = idle_slot(h, "ds_recheck_select", &idle);
+    if (rc) return rc;
+    Slot& sl = *idle;
+    rc = alloc_recheck(h);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(sl.act, act, (size_t)n * h->C * 4, hipMemcpyHostToDevice, sl.s0));
     HIPCHK(h, launch_recheck_select(recheck_args(h, sl, n, margin), sl.s0));
@@ -1949,50 +2110,10 @@ static int ds_submit_parts_impl(ds_handle* h, int32_t nparts, const int32_t* cou
     if (n64 <= 0 || n64 > h->B) return fail(h, DS_ERR_INVALID, "ds_submit: n must be in [1, max_batch]");
     const int n = (int)n64;
     if (h->profiling) return fail(h, DS_ERR_INVALID, "ds_submit is not available while profiling is on");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int si = (int)(h->next_slot % h->slots.size());
-    Slot& sl = h->slots[si];
-    if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_submit: every slot is in flight; ds_wait the oldest ticket first");
-    const size_t B = h->B, T = h->T, S = h->S;
-    const size_t in_bytes = B * (4 * T * 4 + S * 4);
-    if (!sl.pin_in) HIPCHK(h, hipHostMalloc((void**)&sl.pin_in, in_bytes, hipHostMallocDefault));
-    if (!sl.pin_act) {       // ds_submit_reads may have allocated it already
-        HIPCHK(h, hipHostMalloc((void**)&sl.pin_act, (B * h->C + B) * 4, hipHostMallocDefault));      // [act | pred]
-        sl.pin_pred = reinterpret_cast<int*>(sl.pin_act + B * h->C);
-    }
-    h->next_slot++;
-    h->cur = &sl;
-    const size_t nt = (size_t)n * T * 4;
-    char* p = sl.pin_in;
-    size_t row = 0;
-    for (int i = 0; i < nparts; ++i) {
-        const size_t c = (size_t)counts[i];
-        if (!c) continue;
-        memcpy(p + row * T * 4, kmer[i], c * T * 4);
-        memcpy(p + B * T * 4 + row * T * 4, means[i], c * T * 4);
-        memcpy(p + 2 * B * T * 4 + row * T * 4, stds[i], c * T * 4);
-        memcpy(p + 3 * B * T * 4 + row * T * 4, sanums[i], c * T * 4);
-        memcpy(p + 4 * B * T * 4 + row * S * 4, signals[i], c * S * 4);
-        row += c;
-    }
-    if ((size_t)n == B) {        // the staging buffer is the image of the device block: one copy
-        HIPCHK(h, hipMemcpyAsync(sl.d_in, p, in_bytes, hipMemcpyHostToDevice, sl.s0));
-    } else {
-        HIPCHK(h, hipMemcpyAsync(sl.d_kmer, p, nt, hipMemcpyHostToDevice, sl.s0));
-        HIPCHK(h, hipMemcpyAsync(sl.d_means, p + B * T * 4, nt, hipMemcpyHostToDevice, sl.s0));
-        HIPCHK(h, hipMemcpyAsync(sl.d_stds, p + 2 * B * T * 4, nt, hipMemcpyHostToDevice, sl.s0));
-        HIPCHK(h, hipMemcpyAsync(sl.d_sanums, p + 3 * B * T * 4, nt, hipMemcpyHostToDevice, sl.s0));
-        HIPCHK(h, hipMemcpyAsync(sl.d_signals, p + 4 * B * T * 4, (size_t)n * S * 4, hipMemcpyHostToDevice, sl.s0));
-    }
-    int rc = run_resident(h, n);
-    if (rc) return rc;
-    rc = enqueue_recheck(h, sl, n);
-    if (rc) return rc;
-    // [act (max_batch rows) | pred]: one copy back
-    HIPCHK(h, hipMemcpyAsync(sl.pin_act, sl.act, (B * h->C + (size_t)n) * 4, hipMemcpyDeviceToHost, sl.s0));
-    sl.submitted_n = n;
-    *ticket = si;
-    return DS_OK;
+    Slot* sl = nullptr;
+    int rc = idle_slot(h, "ds_submit", &sl);
+    if (!rc) rc = stage_host_inputs(h, *sl, nparts, counts, kmer, means, stds, sanums, signals);
+    return rc ? rc : submit_forward(h, *sl, n, ticket);
 }
 
 static int ds_submit_impl(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums,
@@ -2005,18 +2126,11 @@ static int ds_submit_impl(ds_handle* h, int32_t n, const int32_t* kmer, const fl
 static int ds_wait_impl(ds_handle* h, int32_t ticket, float* act, int32_t* pred)
 {
     if (!h || !act || !pred) return DS_ERR_INVALID;
-    if (ticket < 0 || ticket >= (int)h->slots.size() || h->slots[ticket].submitted_n < 0 || h->slots[ticket].rows_ticket ||
-        h->slots[ticket].text_ticket)
-        return fail(h, DS_ERR_INVALID, "ds_wait: no forward in flight for this ticket");
-    Slot& sl = h->slots[ticket];
-    HIPCHK(h, hipStreamSynchronize(sl.s0));
-    memcpy(act, sl.pin_act, (size_t)sl.submitted_n * h->C * 4);
-    memcpy(pred, sl.pin_pred, (size_t)sl.submitted_n * 4);
-    const int n = sl.submitted_n;
-    sl.submitted_n = -1;
-    return finish_recheck(h, sl, n, act, pred);      // the ticket is complete once its rechecks are merged
+    Slot* sl = nullptr;
+    int n = 0;
+    int rc = ticket_slot(h, "ds_wait", ticket, Ticket::Forward, &sl, &n);
+    return rc ? rc : take_results(h, *sl, n, act, pred);
 }
-
 
 // Scope row f2 on the device: the reads of `r` are validated, packed into the slot's pinned block, copied to its device block
 // and the extraction kernels write the features into the slot's forward inputs (d_kmer .. d_signals), all on sl.s0. Captured
@@ -2028,26 +2142,11 @@ static int stage_reads_block(ds_handle* h, Slot& sl, const ds_reads* r, dsx::Ext
     int rc = dsx::plan(r, h->T, h->S, h->B, p, &err);
     if (rc) return fail(h, rc, err);
     const size_t pin_need = p->image_bytes + extra, dev_need = p->device_bytes + extra;
-    if (pin_need > sl.pin_reads_cap || dev_need > sl.d_reads_cap) {
-        HIPCHK(h, hipStreamSynchronize(sl.s0));        // idle slot: nothing may still read the old blocks
-        if (pin_need > sl.pin_reads_cap) {
-            if (sl.pin_reads) HIPCHK(h, hipHostFree(sl.pin_reads));
-            sl.pin_reads = nullptr; sl.pin_reads_cap = 0;
-            const size_t cap = pin_need + pin_need / 4;
-            HIPCHK(h, hipHostMalloc((void**)&sl.pin_reads, cap, hipHostMallocDefault));
-            sl.pin_reads_cap = cap;
-        }
-        if (dev_need > sl.d_reads_cap) {
-            if (sl.d_reads) HIPCHK(h, hipFree(sl.d_reads));
-            sl.d_reads = nullptr; sl.d_reads_cap = 0;
-            const size_t cap = dev_need + dev_need / 4;
-            hipError_t e = hipMalloc((void**)&sl.d_reads, cap);
-            if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, DS_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
-            sl.d_reads_cap = cap;
-        }
-    }
-    dsx::stage(r, *p, sl.pin_reads);
-    HIPCHK(h, hipMemcpyAsync(sl.d_reads, sl.pin_reads, p->image_bytes, hipMemcpyHostToDevice, sl.s0));
+    rc = grow(h, sl, sl.pin_reads, pin_need, pin_need / 4, true);
+    if (!rc) rc = grow(h, sl, sl.d_reads, dev_need, dev_need / 4, false);
+    if (rc) return rc;
+    dsx::stage(r, *p, sl.pin_reads.p);
+    HIPCHK(h, hipMemcpyAsync(sl.d_reads.p, sl.pin_reads.p, p->image_bytes, hipMemcpyHostToDevice, sl.s0));
     return DS_OK;
 }
 
@@ -2055,8 +2154,8 @@ static int stage_reads(ds_handle* h, Slot& sl, const ds_reads* r, dsx::ExtractPl
 {
     int rc = stage_reads_block(h, sl, r, p, 0);
     if (rc) return rc;
-    const dsx::ExtractArgs a = dsx::device_args(r, *p, sl.d_reads);
-    HIPCHK(h, dsx::launch(*p, a, sl.d_reads, sl.d_kmer, sl.d_means, sl.d_stds, sl.d_sanums, sl.d_signals, sl.s0, ev));
+    const dsx::ExtractArgs a = dsx::device_args(r, *p, sl.d_reads.p);
+    HIPCHK(h, dsx::launch(*p, a, sl.d_reads.p, sl.d_kmer, sl.d_means, sl.d_stds, sl.d_sanums, sl.d_signals, sl.s0, ev));
     return DS_OK;
 }
 
@@ -2064,36 +2163,22 @@ static int ds_extract_impl(ds_handle* h, const ds_reads* r, int32_t* kmer, float
 {
     if (!h) return DS_ERR_INVALID;
     if (!kmer || !means || !stds || !sanums || !signals) return fail(h, DS_ERR_INVALID, "null buffer");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int si = (int)(h->next_slot % h->slots.size());       // the slot the next ds_submit takes; not advanced
-    Slot& sl = h->slots[si];
-    if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_extract: every slot is in flight; ds_wait the oldest ticket first");
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    Slot* sl = nullptr;
+    int rc = idle_slot(h, "ds_extract", &sl);
+    if (rc) return rc;
+    CallEvents<3> ev;
     const bool timed = h->profiling != 0;
-    if (timed)
-        for (auto& e : ev) HIPCHK(h, hipEventCreate(&e));
+    if (timed) HIPCHK(h, ev.create());
     dsx::ExtractPlan p;
-    int rc = stage_reads(h, sl, r, &p, timed ? ev : nullptr);
-    if (!rc) {
-        const size_t T = h->T, n = p.nsites;
-        auto d2h = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sl.s0); };
-        hipError_t e = d2h(kmer, sl.d_kmer, n * T * 4);
-        if (e == hipSuccess) e = d2h(means, sl.d_means, n * T * 4);
-        if (e == hipSuccess) e = d2h(stds, sl.d_stds, n * T * 4);
-        if (e == hipSuccess) e = d2h(sanums, sl.d_sanums, n * T * 4);
-        if (e == hipSuccess) e = d2h(signals, sl.d_signals, n * (size_t)h->S * 4);
-        if (e == hipSuccess) e = hipStreamSynchronize(sl.s0);
-        if (e != hipSuccess) { (void)hipGetLastError(); rc = fail(h, DS_ERR_HIP, std::string("ds_extract: ") + hipGetErrorString(e)); }
-        if (!rc && timed) {
-            float ms0 = 0, ms1 = 0;
-            hipEventElapsedTime(&ms0, ev[0], ev[1]);
-            hipEventElapsedTime(&ms1, ev[1], ev[2]);
-            h->kstat[K_EXTRACT_STATS].launches += 1; h->kstat[K_EXTRACT_STATS].total_ms += ms0;
-            h->kstat[K_EXTRACT_SITES].launches += 1; h->kstat[K_EXTRACT_SITES].total_ms += ms1;
-        }
+    rc = stage_reads(h, *sl, r, &p, timed ? ev.ev : nullptr);
+    if (!rc) rc = inputs_to_host(h, *sl, "ds_extract", (size_t)p.nsites, {kmer, means, stds, sanums, signals});
+    if (!rc && timed) {
+        float ms0 = 0, ms1 = 0;
+        hipEventElapsedTime(&ms0, ev.ev[0], ev.ev[1]);
+        hipEventElapsedTime(&ms1, ev.ev[1], ev.ev[2]);
+        h->kstat[K_EXTRACT_STATS].launches += 1; h->kstat[K_EXTRACT_STATS].total_ms += ms0;
+        h->kstat[K_EXTRACT_SITES].launches += 1; h->kstat[K_EXTRACT_SITES].total_ms += ms1;
     }
-    if (timed)
-        for (auto& e : ev) hipEventDestroy(e);
     return rc;
 }
 
@@ -2102,28 +2187,11 @@ static int ds_submit_reads_impl(ds_handle* h, const ds_reads* r, int32_t* ticket
     if (!h || !ticket) return DS_ERR_INVALID;
     if (!h->finalized) return fail(h, DS_ERR_INVALID, "weights not loaded");
     if (h->profiling) return fail(h, DS_ERR_INVALID, "ds_submit_reads is not available while profiling is on");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int si = (int)(h->next_slot % h->slots.size());
-    Slot& sl = h->slots[si];
-    if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_submit_reads: every slot is in flight; ds_wait the oldest ticket first");
-    if (!sl.pin_act) {       // ds_wait copies act / pred out of the pinned result block (the input staging block is not needed here)
-        HIPCHK(h, hipHostMalloc((void**)&sl.pin_act, ((size_t)h->B * h->C + h->B) * 4, hipHostMallocDefault));
-        sl.pin_pred = reinterpret_cast<int*>(sl.pin_act + (size_t)h->B * h->C);
-    }
+    Slot* sl = nullptr;
     dsx::ExtractPlan p;
-    int rc = stage_reads(h, sl, r, &p, nullptr);
-    if (rc) return rc;
-    h->next_slot++;
-    h->cur = &sl;
-    const int n = p.nsites;
-    rc = run_resident(h, n);
-    if (rc) return rc;
-    rc = enqueue_recheck(h, sl, n);
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(sl.pin_act, sl.act, ((size_t)h->B * h->C + (size_t)n) * 4, hipMemcpyDeviceToHost, sl.s0));
-    sl.submitted_n = n;
-    *ticket = si;
-    return DS_OK;
+    int rc = idle_slot(h, "ds_submit_reads", &sl);
+    if (!rc) rc = stage_reads(h, *sl, r, &p, nullptr);
+    return rc ? rc : submit_forward(h, *sl, p.nsites, ticket);
 }
 
 // ---- feature-TSV rows parsed on the device (ds_tsv_parse.hip tsv_parse_kernel; call_mods --parse_on gpu) ----------------------------
@@ -2150,12 +2218,7 @@ static int alloc_text(ds_handle* h, Slot& sl)
                     " does not fit the parse kernel's LDS");
     const TxLayout L = tx_layout(h);
     const size_t B = h->B;
-    auto dev = [&](void** p, size_t bytes) {
-        if (*p) return DS_OK;
-        hipError_t e = hipMalloc(p, bytes);
-        if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, DS_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
-        return DS_OK;
-    };
+    auto dev = [&](void** p, size_t bytes) { return *p ? DS_OK : dev_malloc(h, p, bytes); };
     if (!sl.pin_text) HIPCHK(h, hipHostMalloc((void**)&sl.pin_text, L.total, hipHostMallocDefault));
     if (!sl.pin_tres) HIPCHK(h, hipHostMalloc((void**)&sl.pin_tres, (3 * B + B * (size_t)h->T) * 4, hipHostMallocDefault));
     int rc = dev((void**)&sl.d_text, L.total);
@@ -2163,10 +2226,6 @@ static int alloc_text(ds_handle* h, Slot& sl)
     if (rc) return rc;
     for (hipEvent_t& e : sl.tx_ev)
         if (!e) HIPCHK(h, hipEventCreate(&e));
-    if (!sl.pin_act) {       // ds_wait_text copies act / pred out of the pinned result block, as ds_wait
-        HIPCHK(h, hipHostMalloc((void**)&sl.pin_act, (B * h->C + B) * 4, hipHostMallocDefault));
-        sl.pin_pred = reinterpret_cast<int*>(sl.pin_act + B * h->C);
-    }
     return DS_OK;
 }
 
@@ -2215,8 +2274,8 @@ static void book_text_times(ds_handle* h, Slot& sl)
         (void)hipGetLastError();
         return;
     }
-    h->tx_batches += 1;
-    for (int i = 0; i < 3; ++i) h->tx_ms[i] += ms[i];
+    h->tx_t.batches += 1;
+    for (int i = 0; i < 3; ++i) h->tx_t.ms[i] += ms[i];
 }
 
 static int check_text_args(ds_handle* h, const char* what, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end)
@@ -2226,38 +2285,36 @@ static int check_text_args(ds_handle* h, const char* what, const char* text, int
     return DS_OK;
 }
 
+// behind enqueue_parse (and, for a ticket, the forward): status / label / info length and the k-mer codes of the n rows to the
+// pinned block, tx_ev[3 .. 4] around them
+static hipError_t enqueue_text_results(const ds_handle* h, Slot& sl, int n)
+{
+    const size_t B = h->B;
+    hipError_t e = hipEventRecord(sl.tx_ev[3], sl.s0);
+    if (e == hipSuccess) e = hipMemcpyAsync(sl.pin_tres, sl.d_tres, 3 * B * 4, hipMemcpyDeviceToHost, sl.s0);
+    if (e == hipSuccess) e = hipMemcpyAsync(sl.pin_tres + 3 * B, sl.d_kmer, (size_t)n * h->T * 4, hipMemcpyDeviceToHost, sl.s0);
+    if (e == hipSuccess) e = hipEventRecord(sl.tx_ev[4], sl.s0);
+    return e;
+}
+
 static int ds_submit_text_impl(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, int32_t* ticket)
 {
     if (!h || !ticket) return DS_ERR_INVALID;
     if (!h->finalized) return fail(h, DS_ERR_INVALID, "weights not loaded");
     if (h->profiling) return fail(h, DS_ERR_INVALID, "ds_submit_text is not available while profiling is on");
     int rc = check_text_args(h, "ds_submit_text", text, nrows, begin, end);
-    if (rc) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int si = (int)(h->next_slot % h->slots.size());
-    Slot& sl = h->slots[si];
-    if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_submit_text: every slot is in flight; wait the oldest ticket first");
-    rc = alloc_text(h, sl);
-    if (rc) return rc;
-    rc = enqueue_parse(h, sl, text, nrows, begin, end);
+    Slot* sl = nullptr;
+    if (!rc) rc = idle_slot(h, "ds_submit_text", &sl);
+    if (!rc) rc = alloc_text(h, *sl);
+    if (!rc) rc = enqueue_parse(h, *sl, text, nrows, begin, end);
     if (rc) return rc;
     h->next_slot++;
-    h->cur = &sl;
-    const int n = nrows;
-    const size_t B = h->B;
-    rc = run_resident(h, n);
+    rc = enqueue_forward_on(h, *sl, nrows);
     if (rc) return rc;
-    rc = enqueue_recheck(h, sl, n);
-    if (rc) return rc;
-    HIPCHK(h, hipEventRecord(sl.tx_ev[3], sl.s0));
-    HIPCHK(h, hipMemcpyAsync(sl.pin_tres, sl.d_tres, 3 * B * 4, hipMemcpyDeviceToHost, sl.s0));
-    HIPCHK(h, hipMemcpyAsync(sl.pin_tres + 3 * B, sl.d_kmer, (size_t)n * h->T * 4, hipMemcpyDeviceToHost, sl.s0));
-    HIPCHK(h, hipEventRecord(sl.tx_ev[4], sl.s0));
-    HIPCHK(h, hipMemcpyAsync(sl.pin_act, sl.act, (B * h->C + (size_t)n) * 4, hipMemcpyDeviceToHost, sl.s0));
-    sl.submitted_n = n;
-    sl.text_ticket = true;
-    *ticket = si;
-    return DS_OK;
+    HIPCHK(h, enqueue_text_results(h, *sl, nrows));      // between the selection and [act | pred], as the ticket's wait books them
+    rc = enqueue_results(h, *sl, nrows);
+    if (!rc) hold(h, *sl, Ticket::Text, nrows, ticket);
+    return rc;
 }
 
 // m host arrays through the forward on the idle slot sl, by the steps ds_forward's passes take (pinned staging, H2D, forward,
@@ -2265,48 +2322,22 @@ static int ds_submit_text_impl(ds_handle* h, const char* text, int32_t nrows, co
 static int forward_on_slot(ds_handle* h, Slot& sl, int m, const int32_t* kmer, const float* means, const float* stds, const float* sanums,
                            const float* signals, float* act, int32_t* pred)
 {
-    const size_t B = h->B, T = h->T, S = h->S;
-    if (!sl.pin_in) HIPCHK(h, hipHostMalloc((void**)&sl.pin_in, B * (4 * T * 4 + S * 4), hipHostMallocDefault));
-    const size_t nt = (size_t)m * T * 4, ns = (size_t)m * S * 4;
-    char* p = sl.pin_in;
-    memcpy(p, kmer, nt);
-    memcpy(p + B * T * 4, means, nt);
-    memcpy(p + 2 * B * T * 4, stds, nt);
-    memcpy(p + 3 * B * T * 4, sanums, nt);
-    memcpy(p + 4 * B * T * 4, signals, ns);
-    HIPCHK(h, hipMemcpyAsync(sl.d_kmer, p, nt, hipMemcpyHostToDevice, sl.s0));
-    HIPCHK(h, hipMemcpyAsync(sl.d_means, p + B * T * 4, nt, hipMemcpyHostToDevice, sl.s0));
-    HIPCHK(h, hipMemcpyAsync(sl.d_stds, p + 2 * B * T * 4, nt, hipMemcpyHostToDevice, sl.s0));
-    HIPCHK(h, hipMemcpyAsync(sl.d_sanums, p + 3 * B * T * 4, nt, hipMemcpyHostToDevice, sl.s0));
-    HIPCHK(h, hipMemcpyAsync(sl.d_signals, p + 4 * B * T * 4, ns, hipMemcpyHostToDevice, sl.s0));
-    h->cur = &sl;
-    int rc = run_resident(h, m);
-    if (rc) return rc;
-    rc = enqueue_recheck(h, sl, m);
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(sl.pin_act, sl.act, (B * h->C + (size_t)m) * 4, hipMemcpyDeviceToHost, sl.s0));
-    HIPCHK(h, hipStreamSynchronize(sl.s0));
-    memcpy(act, sl.pin_act, (size_t)m * h->C * 4);
-    memcpy(pred, sl.pin_pred, (size_t)m * 4);
-    return finish_recheck(h, sl, m, act, pred);
+    int rc = stage_host_inputs(h, sl, 1, &m, &kmer, &means, &stds, &sanums, &signals);
+    if (!rc) rc = enqueue_forward_and_results(h, sl, m);
+    return rc ? rc : take_results(h, sl, m, act, pred);
 }
 
 static int ds_wait_text_impl(ds_handle* h, int32_t ticket, float* act, int32_t* pred, int32_t* kmer, int32_t* labels, char* info,
                              int64_t info_cap, int64_t* info_off)
 {
     if (!h || !act || !pred || !kmer || !labels || !info || !info_off) return DS_ERR_INVALID;
-    if (ticket < 0 || ticket >= (int)h->slots.size() || h->slots[ticket].submitted_n < 0 || !h->slots[ticket].text_ticket)
-        return fail(h, DS_ERR_INVALID, "ds_wait_text: no text rows in flight for this ticket");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    Slot& sl = h->slots[ticket];
-    HIPCHK(h, hipStreamSynchronize(sl.s0));
-    const int n = sl.submitted_n;
+    Slot* held = nullptr;
+    int n = 0;
+    int rc = ticket_slot(h, "ds_wait_text", ticket, Ticket::Text, &held, &n);
+    if (rc) return rc;
+    Slot& sl = *held;
     const size_t B = h->B, T = h->T, S = h->S, C = h->C;
-    memcpy(act, sl.pin_act, (size_t)n * C * 4);
-    memcpy(pred, sl.pin_pred, (size_t)n * 4);
-    sl.submitted_n = -1;
-    sl.text_ticket = false;
-    int rc = finish_recheck(h, sl, n, act, pred);
+    rc = take_results(h, sl, n, act, pred);
     if (rc) return rc;
     book_text_times(h, sl);
     const int32_t* status = sl.pin_tres;
@@ -2363,25 +2394,18 @@ static int ds_parse_text_impl(ds_handle* h, const char* text, int32_t nrows, con
     if (!kmer || !means || !stds || !lens || !signals || !labels || !status) return fail(h, DS_ERR_INVALID, "null buffer");
     int rc = check_text_args(h, "ds_parse_text", text, nrows, begin, end);
     if (rc) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    Slot& sl = h->slots[h->next_slot % h->slots.size()];
-    if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_parse_text: every slot is in flight; wait the oldest ticket first");
+    Slot* idle = nullptr;
+    rc = idle_slot(h, "ds_parse_text", &idle);
+    if (rc) return rc;
+    Slot& sl = *idle;
     rc = alloc_text(h, sl);
+    if (!rc) rc = enqueue_parse(h, sl, text, nrows, begin, end);
     if (rc) return rc;
-    rc = enqueue_parse(h, sl, text, nrows, begin, end);
-    if (rc) return rc;
-    const size_t B = h->B, T = h->T, n = (size_t)nrows;
-    auto d2h = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sl.s0); };
-    hipError_t e = hipEventRecord(sl.tx_ev[3], sl.s0);
-    if (e == hipSuccess) e = d2h(sl.pin_tres, sl.d_tres, 3 * B * 4);
-    if (e == hipSuccess) e = d2h(sl.pin_tres + 3 * B, sl.d_kmer, n * T * 4);
-    if (e == hipSuccess) e = hipEventRecord(sl.tx_ev[4], sl.s0);
-    if (e == hipSuccess) e = d2h(means, sl.d_means, n * T * 4);
-    if (e == hipSuccess) e = d2h(stds, sl.d_stds, n * T * 4);
-    if (e == hipSuccess) e = d2h(lens, sl.d_sanums, n * T * 4);
-    if (e == hipSuccess) e = d2h(signals, sl.d_signals, n * (size_t)h->S * 4);
-    if (e == hipSuccess) e = hipStreamSynchronize(sl.s0);
+    const hipError_t e = enqueue_text_results(h, sl, nrows);
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, DS_ERR_HIP, std::string("ds_parse_text: ") + hipGetErrorString(e)); }
+    const size_t B = h->B, T = h->T, n = (size_t)nrows;
+    rc = inputs_to_host(h, sl, "ds_parse_text", n, {nullptr /* the k-mer codes come with the results */, means, stds, lens, signals});
+    if (rc) return rc;
     book_text_times(h, sl);
     memcpy(status, sl.pin_tres, n * 4);
     memcpy(labels, sl.pin_tres + B, n * 4);
@@ -2412,22 +2436,15 @@ int ds_get_text_stats(ds_handle* h, int64_t* rows, int64_t* host_rows)
     return DS_OK;
 }
 
-int ds_get_text_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms)
-{
-    if (!h || !batches || !ms) return DS_ERR_INVALID;
-    *batches = h->tx_batches;
-    for (int i = 0; i < 3; ++i) ms[i] = h->tx_ms[i];
-    if (reset) { h->tx_batches = 0; for (double& v : h->tx_ms) v = 0; }
-    return DS_OK;
-}
+int ds_get_text_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms) { return h ? h->tx_t.get(reset, batches, ms) : DS_ERR_INVALID; }
 
 // ---- per-site modification frequency on the device (ds_freq.hip; call_freq --on gpu) ------------------------------------------------
 // The run's state is a dsf::Freq of its own (table, row buffers, stream): no pipeline slot, no weights.
 static void freq_close(ds_handle* h)
 {
     if (!h->freq) return;
-    h->fq_batches += h->freq->batches;
-    for (int i = 0; i < 4; ++i) h->fq_ms[i] += h->freq->ms[i];
+    h->fq_t.batches += h->freq->batches;
+    for (int i = 0; i < 4; ++i) h->fq_t.ms[i] += h->freq->ms[i];
     delete h->freq;
     h->freq = nullptr;
 }
@@ -2495,11 +2512,10 @@ int64_t ds_freq_reference(const char* text, int64_t nrows, const int64_t* begin,
 int ds_get_freq_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms)
 {
     if (!h || !batches || !ms) return DS_ERR_INVALID;
-    *batches = h->fq_batches + (h->freq ? h->freq->batches : 0);
-    for (int i = 0; i < 4; ++i) ms[i] = h->fq_ms[i] + (h->freq ? h->freq->ms[i] : 0.0);
+    *batches = h->fq_t.batches + (h->freq ? h->freq->batches : 0);
+    for (int i = 0; i < 4; ++i) ms[i] = h->fq_t.ms[i] + (h->freq ? h->freq->ms[i] : 0.0);
     if (reset) {
-        h->fq_batches = 0;
-        for (double& v : h->fq_ms) v = 0;
+        h->fq_t = Times<4>();
         if (h->freq) { h->freq->batches = 0; for (double& v : h->freq->ms) v = 0; }
     }
     return DS_OK;
@@ -2508,6 +2524,18 @@ int ds_get_freq_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms)
 // ---- feature rows: float64 values and their text on the device (ds_extract.hip rows_*_kernel) ---------------------------------
 // Needs no weights: the slot's streams and the blocks below are all it uses. The rows path enqueues, on sl.s0: H2D of the packed
 // reads and of info / info_off, the statistics, values, length, scan and format kernels, D2H of the row offsets.
+struct RowsLayout { size_t off, len, text, fixed; };      // byte offsets in Slot::d_rows: [float64 values | row offsets | lengths | text]
+static RowsLayout rows_layout(const ds_handle* h)
+{
+    const size_t B = h->B, V = 2 * (size_t)h->T + h->S;
+    RowsLayout L;
+    L.off = B * V * 8;
+    L.len = L.off + (B + 1) * 8;
+    L.text = (L.len + B * 4 + 15) & ~(size_t)15;
+    L.fixed = L.text + B * (size_t)dsx::row_text_max(h->T, h->S);      // the block without the rows' leading columns
+    return L;
+}
+
 static int enqueue_rows(ds_handle* h, Slot& sl, const ds_reads* r, const char* info, const int64_t* info_off, int32_t label,
                         dsx::ExtractPlan* p, hipEvent_t* ev)
 {
@@ -2519,121 +2547,96 @@ static int enqueue_rows(ds_handle* h, Slot& sl, const ds_reads* r, const char* i
     const size_t extra = 16 + off_bytes + (size_t)info_bytes;      // behind the reads: [info_off | info], 16-byte aligned
     int rc = stage_reads_block(h, sl, r, p, extra);
     if (rc) return rc;
-    const size_t B = h->B, V = 2 * (size_t)h->T + h->S;
-    const size_t o_off = B * V * 8, o_len = o_off + (B + 1) * 8, o_text = (o_len + B * 4 + 15) & ~(size_t)15;
-    const size_t need = o_text + B * (size_t)dsx::row_text_max(h->T, h->S) + (size_t)info_bytes;
-    if (need > sl.d_rows_cap) {
-        HIPCHK(h, hipStreamSynchronize(sl.s0));
-        if (sl.d_rows) HIPCHK(h, hipFree(sl.d_rows));
-        sl.d_rows = nullptr; sl.d_rows_cap = 0;
-        const size_t cap = need + std::max<size_t>((size_t)info_bytes, B * 64);      // room for longer leading columns
-        hipError_t e = hipMalloc((void**)&sl.d_rows, cap);
-        if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, DS_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
-        sl.d_rows_cap = cap;
-    }
+    const size_t B = h->B;
+    const RowsLayout L = rows_layout(h);
+    // slack: room for longer leading columns
+    rc = grow(h, sl, sl.d_rows, L.fixed + (size_t)info_bytes, std::max<size_t>((size_t)info_bytes, B * 64), false);
+    if (rc) return rc;
     if (!sl.pin_rowoff) HIPCHK(h, hipHostMalloc((void**)&sl.pin_rowoff, (B + 1) * 8, hipHostMallocDefault));
     const size_t pin_at = (p->image_bytes + 15) & ~(size_t)15, dev_at = (p->device_bytes + 15) & ~(size_t)15;
-    memcpy(sl.pin_reads + pin_at, info_off, off_bytes);
-    if (info_bytes) memcpy(sl.pin_reads + pin_at + off_bytes, info, (size_t)info_bytes);
-    HIPCHK(h, hipMemcpyAsync(sl.d_reads + dev_at, sl.pin_reads + pin_at, off_bytes + (size_t)info_bytes, hipMemcpyHostToDevice, sl.s0));
-    const dsx::ExtractArgs a = dsx::device_args(r, *p, sl.d_reads);
+    memcpy(sl.pin_reads.p + pin_at, info_off, off_bytes);
+    if (info_bytes) memcpy(sl.pin_reads.p + pin_at + off_bytes, info, (size_t)info_bytes);
+    HIPCHK(h, hipMemcpyAsync(sl.d_reads.p + dev_at, sl.pin_reads.p + pin_at, off_bytes + (size_t)info_bytes, hipMemcpyHostToDevice, sl.s0));
+    const dsx::ExtractArgs a = dsx::device_args(r, *p, sl.d_reads.p);
     dsx::RowsArgs ra{};
-    ra.info_off = reinterpret_cast<const int64_t*>(sl.d_reads + dev_at);
-    ra.info = sl.d_reads + dev_at + off_bytes;
-    ra.vals = reinterpret_cast<double*>(sl.d_rows);
-    ra.row_off = reinterpret_cast<int64_t*>(sl.d_rows + o_off);
-    ra.row_len = reinterpret_cast<int32_t*>(sl.d_rows + o_len);
-    ra.text = sl.d_rows + o_text;
-    ra.text_cap = (int64_t)(sl.d_rows_cap - o_text);
+    ra.info_off = reinterpret_cast<const int64_t*>(sl.d_reads.p + dev_at);
+    ra.info = sl.d_reads.p + dev_at + off_bytes;
+    ra.vals = reinterpret_cast<double*>(sl.d_rows.p);
+    ra.row_off = reinterpret_cast<int64_t*>(sl.d_rows.p + L.off);
+    ra.row_len = reinterpret_cast<int32_t*>(sl.d_rows.p + L.len);
+    ra.text = sl.d_rows.p + L.text;
+    ra.text_cap = (int64_t)(sl.d_rows.cap - L.text);
     ra.label = label;
-    HIPCHK(h, dsx::launch_rows(*p, a, ra, sl.d_reads, sl.s0, ev));
+    HIPCHK(h, dsx::launch_rows(*p, a, ra, sl.d_reads.p, sl.s0, ev));
     HIPCHK(h, hipMemcpyAsync(sl.pin_rowoff, ra.row_off, off_bytes, hipMemcpyDeviceToHost, sl.s0));
     return DS_OK;
 }
 
-// the text of the rows ticket on sl: bytes written, or -(bytes needed) with the ticket kept
-static int64_t collect_rows(ds_handle* h, Slot& sl, char* out, int64_t cap, int64_t* row_off, hipEvent_t* ev)
+// the text of the n rows enqueue_rows left on sl: bytes written, or -(bytes needed) with nothing consumed
+static int64_t collect_rows(ds_handle* h, Slot& sl, int n, char* out, int64_t cap, int64_t* row_off, hipEvent_t* ev)
 {
     HIPCHK(h, hipStreamSynchronize(sl.s0));
-    const int n = sl.submitted_n;
     const int64_t total = sl.pin_rowoff[n];
     if (total > cap) return -total;
-    if ((size_t)total > sl.pin_rows_cap) {
-        if (sl.pin_rows) HIPCHK(h, hipHostFree(sl.pin_rows));
-        sl.pin_rows = nullptr; sl.pin_rows_cap = 0;
-        const size_t want = (size_t)total + (size_t)total / 4;
-        HIPCHK(h, hipHostMalloc((void**)&sl.pin_rows, want, hipHostMallocDefault));
-        sl.pin_rows_cap = want;
-    }
-    const size_t B = h->B, V = 2 * (size_t)h->T + h->S;
-    const size_t o_text = (B * V * 8 + (B + 1) * 8 + B * 4 + 15) & ~(size_t)15;
+    int rc = grow(h, sl, sl.pin_rows, (size_t)total, (size_t)total / 4, true);
+    if (rc) return rc;
     if (ev) HIPCHK(h, hipEventRecord(ev[0], sl.s0));
-    HIPCHK(h, hipMemcpyAsync(sl.pin_rows, sl.d_rows + o_text, (size_t)total, hipMemcpyDeviceToHost, sl.s0));      // only the bytes used
+    HIPCHK(h, hipMemcpyAsync(sl.pin_rows.p, sl.d_rows.p + rows_layout(h).text, (size_t)total, hipMemcpyDeviceToHost, sl.s0));
     if (ev) HIPCHK(h, hipEventRecord(ev[1], sl.s0));
     HIPCHK(h, hipStreamSynchronize(sl.s0));
-    memcpy(out, sl.pin_rows, (size_t)total);
+    memcpy(out, sl.pin_rows.p, (size_t)total);
     if (row_off) memcpy(row_off, sl.pin_rowoff, ((size_t)n + 1) * 8);
-    sl.submitted_n = -1;
-    sl.rows_ticket = false;
     return total;
 }
 
 static int ds_submit_rows_impl(ds_handle* h, const ds_reads* r, const char* info, const int64_t* info_off, int32_t label, int32_t* ticket)
 {
     if (!h || !ticket) return DS_ERR_INVALID;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int si = (int)(h->next_slot % h->slots.size());
-    Slot& sl = h->slots[si];
-    if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_submit_rows: every slot is in flight; wait the oldest ticket first");
+    Slot* sl = nullptr;
     dsx::ExtractPlan p;
-    int rc = enqueue_rows(h, sl, r, info, info_off, label, &p, nullptr);
+    int rc = idle_slot(h, "ds_submit_rows", &sl);
+    if (!rc) rc = enqueue_rows(h, *sl, r, info, info_off, label, &p, nullptr);
     if (rc) return rc;
     h->next_slot++;
-    sl.submitted_n = p.nsites;
-    sl.rows_ticket = true;
-    *ticket = si;
+    hold(h, *sl, Ticket::Rows, p.nsites, ticket);
     return DS_OK;
 }
 
 static int64_t ds_wait_rows_impl(ds_handle* h, int32_t ticket, char* out, int64_t cap, int64_t* row_off)
 {
     if (!h || !out) return DS_ERR_INVALID;
-    if (ticket < 0 || ticket >= (int)h->slots.size() || h->slots[ticket].submitted_n < 0 || !h->slots[ticket].rows_ticket)
-        return fail(h, DS_ERR_INVALID, "ds_wait_rows: no rows in flight for this ticket");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    return collect_rows(h, h->slots[ticket], out, cap, row_off, nullptr);
+    Slot* sl = nullptr;
+    int n = 0;
+    int rc = ticket_slot(h, "ds_wait_rows", ticket, Ticket::Rows, &sl, &n);
+    if (rc) return rc;
+    const int64_t got = collect_rows(h, *sl, n, out, cap, row_off, nullptr);
+    if (got >= 0) release(*sl);       // a short buffer (or a failed copy) keeps the ticket: the wait is repeated
+    return got;
 }
 
-// Blocking form on an idle slot (not advanced, as ds_extract). With profiling on, the kernels and the text copy are timed.
+// Blocking form on the idle slot, which it leaves idle: a short buffer consumes nothing the caller could come back for, the
+// call is repeated. With profiling on, the kernels and the text copy are timed.
 static int64_t ds_extract_rows_impl(ds_handle* h, const ds_reads* r, const char* info, const int64_t* info_off, int32_t label,
                                     char* out, int64_t cap, int64_t* row_off)
 {
     if (!h || !out) return DS_ERR_INVALID;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    Slot& sl = h->slots[h->next_slot % h->slots.size()];
-    if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_extract_rows: every slot is in flight; wait the oldest ticket first");
-    hipEvent_t ev[7] = {nullptr};
+    Slot* sl = nullptr;
+    int rc = idle_slot(h, "ds_extract_rows", &sl);
+    if (rc) return rc;
+    CallEvents<7> ev;
     const bool timed = h->profiling != 0;
-    if (timed)
-        for (auto& e : ev) HIPCHK(h, hipEventCreate(&e));
+    if (timed) HIPCHK(h, ev.create());
     dsx::ExtractPlan p;
-    int64_t got = enqueue_rows(h, sl, r, info, info_off, label, &p, timed ? ev : nullptr);
-    if (!got) {
-        sl.submitted_n = p.nsites;
-        sl.rows_ticket = true;
-        got = collect_rows(h, sl, out, cap, row_off, timed ? ev + 5 : nullptr);
-        sl.submitted_n = -1;          // a short buffer consumes nothing the caller could come back for: the call is repeated
-        sl.rows_ticket = false;
-        if (got >= 0 && timed) {
-            h->rows_batches += 1;
-            for (int i = 0; i < 4; ++i) { float ms = 0; hipEventElapsedTime(&ms, ev[i], ev[i + 1]); h->rows_ms[i] += ms; }
-            float ms = 0;
-            hipEventElapsedTime(&ms, ev[5], ev[6]);
-            h->rows_ms[4] += ms;
-        }
+    rc = enqueue_rows(h, *sl, r, info, info_off, label, &p, timed ? ev.ev : nullptr);
+    if (rc) return rc;
+    const int64_t got = collect_rows(h, *sl, p.nsites, out, cap, row_off, timed ? ev.ev + 5 : nullptr);
+    if (got >= 0 && timed) {
+        h->rows_t.batches += 1;
+        for (int i = 0; i < 4; ++i) { float ms = 0; hipEventElapsedTime(&ms, ev.ev[i], ev.ev[i + 1]); h->rows_t.ms[i] += ms; }
+        float ms = 0;
+        hipEventElapsedTime(&ms, ev.ev[5], ev.ev[6]);
+        h->rows_t.ms[4] += ms;
     }
-    if (timed)
-        for (auto& e : ev) hipEventDestroy(e);
     return got;
 }
 
@@ -2648,15 +2651,16 @@ static int64_t ds_format_values_impl(ds_handle* h, int64_t n, const double* valu
         return (int64_t)text.size();
     }
     // a diagnostic: its device buffers live for the call
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    Slot& sl = h->slots[h->next_slot % h->slots.size()];
-    if (sl.submitted_n >= 0) return fail(h, DS_ERR_INVALID, "ds_format_values: every slot is in flight");
+    Slot* idle = nullptr;
+    int rc = idle_slot(h, "ds_format_values", &idle);
+    if (rc) return rc;
+    Slot& sl = *idle;
     const size_t vbytes = ((size_t)n * 8 + 15) & ~(size_t)15, tbytes = (size_t)n * (dsx::VALUE_TEXT_MAX + 1);
     char* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, vbytes + 16 + tbytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, DS_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+    rc = dev_malloc(h, (void**)&d, vbytes + 16 + tbytes);
+    if (rc) return rc;
     int64_t total = 0;
-    e = hipMemcpyAsync(d, values, (size_t)n * 8, hipMemcpyHostToDevice, sl.s0);
+    hipError_t e = hipMemcpyAsync(d, values, (size_t)n * 8, hipMemcpyHostToDevice, sl.s0);
     if (e == hipSuccess) e = dsx::launch_format_values(reinterpret_cast<double*>(d), n, d + vbytes + 16, reinterpret_cast<int64_t*>(d + vbytes), sl.s0);
     if (e == hipSuccess) e = hipMemcpyAsync(&total, d + vbytes, 8, hipMemcpyDeviceToHost, sl.s0);
     if (e == hipSuccess) e = hipStreamSynchronize(sl.s0);
@@ -2679,14 +2683,7 @@ int64_t ds_extract_rows_reference(const ds_reads* r, int32_t kmer_len, int32_t s
     return (int64_t)text.size();
 }
 
-int ds_get_rows_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms)
-{
-    if (!h || !batches || !ms) return DS_ERR_INVALID;
-    *batches = h->rows_batches;
-    for (int i = 0; i < 5; ++i) ms[i] = h->rows_ms[i];
-    if (reset) { h->rows_batches = 0; for (double& v : h->rows_ms) v = 0; }
-    return DS_OK;
-}
+int ds_get_rows_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms) { return h ? h->rows_t.get(reset, batches, ms) : DS_ERR_INVALID; }
 
 int ds_extract_reference(const ds_reads* r, int32_t kmer_len, int32_t signal_len, int32_t* kmer, float* means, float* stds,
                          float* sanums, float* signals)
