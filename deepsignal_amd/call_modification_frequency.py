@@ -4,6 +4,9 @@ path; what users actually consume). Same algorithm, flags and output formats as 
 group calls by (chromosome, pos), keep a call if |prob_0 - prob_1| >= prob_cf, accumulate prob sums,
 met / unmet counts and coverage, write the 11-column table or bedMethyl.
 
+`call_mods --freq_file` (FreqStream) computes the table from the forward's results as call_mods has them, with no result text
+written or parsed in between; it shares the device kernels and the host-row expressions with `--on gpu`.
+
 `--on gpu` (calculate_mods_frequency_gpu) computes the same SiteStats on the MI355X: the host only finds the rows and numbers
 the chromosomes (ds_freq_locate), the device parses and aggregates them (csrc/ds_freq.hip), and the rows in a form the device
 does not parse go through the expressions of the cpu route right here. The table is byte-identical to `--on cpu`.
@@ -101,6 +104,187 @@ def _python_row(raw: bytes) -> List[str]:
     return lines[0].strip().split("\t")
 
 
+def _host_row_values(w: List[str], prob_cf: float, chrom_id):
+    """One row `w` the device left to Python, through the expressions of the cpu route -> what ds_freq_accumulate takes for it:
+    (chromosome id, pos, prob_0, prob_1, met, used). `used`: the row passes the threshold (the device makes the same comparison on
+    these doubles) and its key has been looked up -- chrom_id(name), or chrom_id((name, pos)) with pos 0 for a position outside
+    the key: a site under an id of its own. Shared by `call_freq --on gpu` and `call_mods --freq_file`."""
+    from . import engine as eng
+    prob_0, prob_1 = float(w[6]), float(w[7])
+    cid, pos, met, used = 0, 0, 0, False
+    if not abs(prob_0 - prob_1) < prob_cf:
+        name, pos = w[0], int(w[1])
+        if 0 <= pos < eng.FREQ_POS_LIMIT:
+            cid = chrom_id(name)
+        else:
+            cid, pos = chrom_id((name, pos)), 0
+        met = 1 if int(w[8]) == 1 else 0
+        used = True
+    return cid, pos, prob_0, prob_1, met, used
+
+
+def _chrom_table():
+    """names: chromosome id -> its name, or (name, pos) for a site whose position does not fit the key; chrom_id(name) numbers them
+    in first-appearance order."""
+    from . import engine as eng
+    names: list = []
+    ids: dict = {}
+
+    def chrom_id(name):
+        i = ids.get(name)
+        if i is None:
+            i = ids[name] = len(names)
+            names.append(name)
+            if i >= eng.FREQ_CHROM_LIMIT:
+                raise _CpuRoute("more than 2^23 chromosome names")
+        return i
+
+    return names, chrom_id
+
+
+def _print_used(host_rows: int, used: int, total: int) -> None:
+    if host_rows:
+        print("{} row(s) parsed on the host (a form the device does not take)..".format(host_rows))
+    print("{:.2f}% ({} of {}) calls used..".format(used / float(total) * 100 if total else 0.0, used, total))
+
+
+_KMER_BASES = b"ACGTN"
+
+
+class FreqStream:
+    """`call_mods --freq_file`: calculate_mods_frequency over the rows call_mods writes (or would write), fed with what the rows
+    are made from -- sampleinfo, the forward's act rows, pred and the k-mer codes, exactly the arguments of fastio.format_rows --
+    in result-file order. No row text is made or parsed: the keys come from ds_freq_keys, the two doubles float() would read from
+    the printed probabilities from freq_values_kernel, the sums from the kernels of `call_freq --on gpu` on a table that grows. A row
+    the device leaves to Python (a flagged sampleinfo, NaN, a probability below ~1e-14) is formatted on its own and read by the cpu
+    route's expressions. finish() returns the dict calculate_mods_frequency gives on the text, in the same order.
+    _CpuRoute: the stream cannot go on (the message says why); the caller runs the cpu route over the result file or gives up.
+    make_engine: what provides freq_begin_stream .. freq_end (default: an Engine of its own on `device`, never the forward's)."""
+
+    def __init__(self, prob_cf: float = 0.0, device: int = 0, batch_rows: int = 1 << 16, initial_slots: int = 1 << 16, make_engine=None):
+        from . import engine as eng
+        if not 1 <= batch_rows <= eng.FREQ_MAX_BATCH:
+            raise ValueError("batch_rows must be in [1, 2^24]")
+        if prob_cf != prob_cf:
+            raise ValueError("prob_cf must not be NaN")
+        self.prob_cf, self.batch_rows = prob_cf, batch_rows
+        self.names, self.chrom_id = _chrom_table()
+        self.rows = self.host_rows = 0
+        self._buf, self._nbuf = [], 0                        # rows pushed, not yet on the device
+        self.first: Dict[int, Tuple[str, int, str]] = {}     # a site's first used row -> its strand, pos_in_strand, k-mer
+        self.info: dict = {}
+        # a handle of its own, the smallest there is (see calculate_mods_frequency_gpu): the forward's handle is busy on another thread
+        self.e = make_engine() if make_engine is not None else eng.Engine(device=device, max_batch=64, slots=1)
+        try:
+            self.e.freq_begin_stream(initial_slots, batch_rows, prob_cf)
+        except eng.FreqNoMemory as exc:
+            self.close()
+            raise _CpuRoute("the site table does not fit the device (%s)" % exc)
+        except BaseException:
+            self.close()
+            raise
+
+    def push(self, info, info_off, act, pred, kmer) -> None:
+        """The rows format_rows(info, info_off, act, pred, kmer) would print, in that order. They are copied and go to the device
+        batch_rows at a time (the writer hands over a few thousand rows at once; a device batch of 65,536 rows costs a fixed ~140 kernel launches, 136 of them the bitonic network's)."""
+        import numpy as np
+        n = int(len(pred))
+        if not n:
+            return
+        off = np.asarray(info_off, np.int64)
+        self._buf.append((np.array(np.asarray(info, np.uint8)[int(off[0]):int(off[n])]), np.diff(off[:n + 1]), np.array(act, np.float32),
+                          np.array(pred, np.int32), np.array(kmer, np.int32)))
+        self._nbuf += n
+        if self._nbuf >= self.batch_rows:
+            self._flush(self.batch_rows)
+
+    def _flush(self, full: int = 0) -> None:
+        """Batches of `full` rows from the buffer while it holds that many; full == 0: everything."""
+        import numpy as np
+        if not self._nbuf:
+            return
+        info, lens, act, pred, kmer = (np.concatenate([b[j] for b in self._buf]) for j in range(5))
+        off = np.zeros(self._nbuf + 1, np.int64)
+        np.cumsum(lens, out=off[1:])
+        self._buf, done = [], 0
+        while self._nbuf - done >= max(full, 1):
+            t = min(self._nbuf, done + (full or self.batch_rows))
+            self._batch(info, off[done:t + 1], act[done:t], pred[done:t], kmer[done:t])
+            done = t
+        if done < self._nbuf:
+            self._buf = [(info[int(off[done]):], lens[done:], act[done:], pred[done:], kmer[done:])]
+        self._nbuf -= done
+
+    def _batch(self, info, off, act, pred, kmer) -> None:
+        import numpy as np
+        from . import engine as eng
+        from . import fastio
+        n = int(len(pred))
+        if self.rows + n > eng.FREQ_MAX_ROWS:
+            raise _CpuRoute("more than 2^30 rows")
+        local, pos, flags, names = eng.freq_keys(info, off)
+        to_run = np.array([self.chrom_id(nm.decode("ascii")) for nm in names] + [-1], np.int32)
+        try:
+            status = self.e.freq_push(to_run[local], pos, act, pred)
+        except eng.FreqNoMemory as exc:
+            raise _CpuRoute("the site table cannot grow on the device (%s)" % exc)
+        host_w: Dict[int, List[str]] = {}
+        o_row, o_chrom, o_pos, o_p0, o_p1, o_met = [], [], [], [], [], []
+        for i in np.flatnonzero(status != eng.TEXT_ROW_OK).tolist():
+            row = fastio.format_rows(info, off[i:i + 2], act[i:i + 1], pred[i:i + 1], kmer[i:i + 1])
+            w = _python_row(row[:-1])
+            cid, q, prob_0, prob_1, met, used = _host_row_values(w, self.prob_cf, self.chrom_id)
+            if used:
+                host_w[i] = w
+            o_row.append(i); o_chrom.append(cid); o_pos.append(q); o_p0.append(prob_0); o_p1.append(prob_1); o_met.append(met)
+        opened = self.e.freq_accumulate(o_row, o_chrom, o_pos, o_p0, o_p1, o_met)
+        self.host_rows += len(o_row)
+        # the rows that open a site: their strand, pos_in_strand and k-mer (codes -> letters as ds_format_rows writes them)
+        idx = np.flatnonzero(opened)
+        codes = np.asarray(kmer, np.int64)[idx]
+        K = codes.shape[1] if codes.ndim == 2 else 0
+        letters = np.frombuffer(_KMER_BASES, np.uint8)[np.where((codes >= 0) & (codes < 5), codes, 4)].tobytes().decode("ascii")
+        base, blob, offs = int(off[0]), np.asarray(info, np.uint8)[int(off[0]):int(off[n])].tobytes(), off.tolist()
+        for j, i in enumerate(idx.tolist()):
+            w = host_w.get(i)
+            if w is None:
+                c = blob[offs[i] - base:offs[i + 1] - base].decode("ascii").split("\t")
+                w2, w3, w9 = c[2], c[3], letters[j * K:(j + 1) * K]
+            else:
+                w2, w3, w9 = w[2], w[3], w[9]
+            self.first[self.rows + i] = (w2, int(w3), w9)
+        self.rows += n
+
+    def finish(self) -> Dict[SiteKey, SiteStats]:
+        """The sites in the order of their first used row, and the "calls used" line."""
+        import numpy as np
+        self._flush()
+        res = self.e.freq_result()
+        self.info.update(self.e.freq_times())
+        if hasattr(self.e, "freq_stream_times"):
+            self.info.update(self.e.freq_stream_times())
+        self.e.freq_end()
+        if res["rows"] != self.rows:
+            raise RuntimeError("freq stream: %d rows accumulated, %d pushed" % (res["rows"], self.rows))
+        stats: Dict[SiteKey, SiteStats] = {}
+        for k in np.argsort(res["first_row"], kind="stable").tolist():
+            strand, pis, kmer = self.first[int(res["first_row"][k])]
+            name = self.names[int(res["chrom"][k])]
+            key = name if isinstance(name, tuple) else (name, int(res["pos"][k]))
+            st = stats[key] = SiteStats(strand, pis, kmer)
+            st.prob_0, st.prob_1 = float(res["sum0"][k]), float(res["sum1"][k])
+            st.met, st.unmet = int(res["met"][k]), int(res["unmet"][k])
+            st.coverage = st.met + st.unmet
+        self.info.update(host_rows=self.host_rows, rows=self.rows, used=res["used"])
+        _print_used(self.host_rows, res["used"], self.rows)
+        return stats
+
+    def close(self) -> None:
+        e, self.e = getattr(self, "e", None), None
+        if e is not None:
+            e.close()
+
+
 def calculate_mods_frequency_gpu(mods_files: Iterable[str], prob_cf: float = 0.0, device: int = 0, batch_rows: int = 1 << 20,
                                  info: dict = None, make_engine=None) -> Dict[SiteKey, SiteStats]:
     """calculate_mods_frequency on the GPU: the same dict -- same keys in the same order, same doubles, same counts -- and the
@@ -114,17 +298,7 @@ def calculate_mods_frequency_gpu(mods_files: Iterable[str], prob_cf: float = 0.0
         raise ValueError("batch_rows must be in [1, 2^24]")
     if prob_cf != prob_cf:
         raise ValueError("prob_cf must not be NaN")
-    names: list = []                  # chromosome id -> its name, or (name, pos) for a site whose position does not fit the key
-    ids: dict = {}
-
-    def chrom_id(name):
-        i = ids.get(name)
-        if i is None:
-            i = ids[name] = len(names)
-            names.append(name)
-            if i >= eng.FREQ_CHROM_LIMIT:
-                raise _CpuRoute("more than 2^23 chromosome names")
-        return i
+    names, chrom_id = _chrom_table()
 
     # host pass: every file's rows (the table is sized from their number). A file that cannot be read raises when its turn
     # comes, after the rows of the files in front of it, as on the cpu route.
@@ -164,15 +338,8 @@ def calculate_mods_frequency_gpu(mods_files: Iterable[str], prob_cf: float = 0.0
                     o_row, o_chrom, o_pos, o_p0, o_p1, o_met = [], [], [], [], [], []
                     for i in np.flatnonzero(status != eng.TEXT_ROW_OK).tolist():
                         w = _python_row(f.row_bytes(s + i))
-                        prob_0, prob_1 = float(w[6]), float(w[7])
-                        cid, pos, met = 0, 0, 0
-                        if not abs(prob_0 - prob_1) < prob_cf:         # the device makes the same comparison on these doubles
-                            name, pos = w[0], int(w[1])
-                            if 0 <= pos < eng.FREQ_POS_LIMIT:
-                                cid = chrom_id(name)
-                            else:                                      # a position outside the key: a site under an id of its own
-                                cid, pos = chrom_id((name, pos)), 0
-                            met = 1 if int(w[8]) == 1 else 0
+                        cid, pos, prob_0, prob_1, met, is_used = _host_row_values(w, prob_cf, chrom_id)
+                        if is_used:
                             host_w[base + s + i] = w
                         o_row.append(i); o_chrom.append(cid); o_pos.append(pos); o_p0.append(prob_0); o_p1.append(prob_1); o_met.append(met)
                     e.freq_accumulate(o_row, o_chrom, o_pos, o_p0, o_p1, o_met)
@@ -206,9 +373,7 @@ def calculate_mods_frequency_gpu(mods_files: Iterable[str], prob_cf: float = 0.0
     used = res["used"] if res is not None else 0
     if info is not None:
         info.update(host_rows=host_rows, rows=total, used=used, **times)
-    if host_rows:
-        print("{} row(s) parsed on the host (a form the device does not take)..".format(host_rows))
-    print("{:.2f}% ({} of {}) calls used..".format(used / float(total) * 100 if total else 0.0, used, total))
+    _print_used(host_rows, used, total)
     return stats
 
 

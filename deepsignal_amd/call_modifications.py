@@ -10,6 +10,7 @@ prob_0, prob_1, called_label, seq          (reference call_modifications.py:4-5,
 """
 from __future__ import absolute_import
 
+import contextlib
 import os
 import sys
 import time
@@ -94,8 +95,20 @@ def _features_item(features_list):
     return (sampleinfo, kmers, base_means, base_stds, base_signal_lens, cent_signals, labels)
 
 
-def _call_mods(features_batch: FeaturesBatch, engine, batch_size: int):
+def _rows_to_sink(rows_sink, sampleinfo, act, pred, kmers):
+    """One batch of the Python-list routes in the arguments of fastio.format_rows (see _FreqTap.rows). The sampleinfo strings are
+    encoded as open(result_file, "w") encodes them."""
+    import locale
+    enc = [s.encode(locale.getpreferredencoding(False)) for s in sampleinfo]
+    off = np.zeros(len(enc) + 1, np.int64)
+    off[1:] = np.cumsum([len(b) for b in enc])
+    rows_sink(np.frombuffer(b"".join(enc), np.uint8), off, np.asarray(act, np.float32), np.asarray(pred, np.int32),
+              np.asarray(kmers, np.int32).reshape(len(enc), -1))
+
+
+def _call_mods(features_batch: FeaturesBatch, engine, batch_size: int, rows_sink=None, text=True):
     """One queue item -> output rows. Reference: call_modifications.py:149-194.
+    rows_sink (call_mods --freq_file): also handed every batch as arrays; text=False: no row text is made (pred_str stays empty).
 
     Slices the item into batch_size chunks (last one partial), runs the engine on each, normalises
     the two sigmoid outputs in float32 (p_k / (p_0 + p_1)) and formats
@@ -115,7 +128,9 @@ def _call_mods(features_batch: FeaturesBatch, engine, batch_size: int):
                 b_kmers, base_means[batch_s:batch_e], base_stds[batch_s:batch_e],
                 base_signal_lens[batch_s:batch_e], cent_signals[batch_s:batch_e])
             accuracys.append(float(np.mean(np.asarray(b_labels) == np.asarray(prediction))))
-            for idx in range(b_labels.shape[0]):
+            if rows_sink is not None:
+                _rows_to_sink(rows_sink, b_sampleinfo, activation_logits, prediction, b_kmers)
+            for idx in range(b_labels.shape[0] if text else 0):
                 prob_0, prob_1 = activation_logits[idx][0], activation_logits[idx][1]
                 prob_0_norm = prob_0 / (prob_0 + prob_1)
                 prob_1_norm = prob_1 / (prob_0 + prob_1)
@@ -285,6 +300,21 @@ def _distributed_context(dist):
     return tdist, tdist.get_rank(), tdist.get_world_size(), local
 
 
+def _check_freq_file(dist, force_sharded):
+    """call_mods --freq_file is a single-process feature: the per-site sums are added in result-file row order, and with one
+    process per GPU the rows of a site are spread over the ranks; merging per-rank tables in row order is a separate piece of work
+    (DESIGN.md section 7, row f4). A process group of one rank on the ordinary route is a single process; force_sharded takes the
+    multi-process route (row gather through the collectives), which has no hook for the table, so it is refused as well."""
+    world = dist.get_world_size() if dist is not None else int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1:
+        raise ValueError("--freq_file works in a single process only: under a multi-GPU launcher (WORLD_SIZE > 1) the rows of a site "
+                         "are spread over the ranks and the per-rank tables would have to be merged in row order; write the result "
+                         "file and run call_freq --on gpu on it")
+    if force_sharded:
+        raise ValueError("--freq_file works in a single process only: force_sharded takes the multi-process route (byte ranges, row "
+                         "gather), which does not feed the frequency table; write the result file and run call_freq --on gpu on it")
+
+
 class _RowPipeline:
     """Rows of queue items through the engine, results formatted and handed to `sink(tag, row_bytes)` in feed order.
 
@@ -297,12 +327,15 @@ class _RowPipeline:
     Rows still leave in file order, a read's rows together. `tag` travels with every row (the sharded path uses it to
     know which work unit a row belongs to)."""
 
-    def __init__(self, engine, batch_size, sink):
+    def __init__(self, engine, batch_size, sink, rows_sink=None):
         import collections
         import queue
         import threading
         from . import fastio
         self.engine, self.batch_size, self.sink, self.fastio = engine, batch_size, sink, fastio
+        # call_mods --freq_file: rows_sink(info, info_off, act, pred, kmer) sees every batch where the ordered writer does, in the
+        # same order, as the arrays the formatter reads; sink=None: no row text is made at all
+        self.rows_sink = rows_sink
         self.pipelined = hasattr(engine, "submit") and hasattr(engine, "wait") and \
             batch_size <= getattr(engine, "max_batch", 0)
         if self.pipelined:
@@ -319,7 +352,10 @@ class _RowPipeline:
 
     def _emit(self, seg, act, pred):
         tag, it, s, e = seg
-        self.sink(tag, self.fastio.format_rows(it.info, it.info_off[s:e + 1], act, pred, it.kmer[s:e]))
+        if self.sink is not None:
+            self.sink(tag, self.fastio.format_rows(it.info, it.info_off[s:e + 1], act, pred, it.kmer[s:e]))
+        if self.rows_sink is not None:
+            self.rows_sink(it.info, it.info_off[s:e + 1], act, pred, it.kmer[s:e])
 
     def _format_loop(self):
         while True:
@@ -430,8 +466,8 @@ class _TextPipeline(_RowPipeline):
     formatter needs (k-mer codes, the six leading columns). Batches are still filled across items to engine.max_batch and rows
     leave in feed order."""
 
-    def __init__(self, engine, batch_size, sink, reader):
-        _RowPipeline.__init__(self, engine, batch_size, sink)
+    def __init__(self, engine, batch_size, sink, reader, rows_sink=None):
+        _RowPipeline.__init__(self, engine, batch_size, sink, rows_sink)
         if not self.pipelined:
             raise ValueError("parse_on='gpu' needs batch_size <= engine.max_batch")
         self.reader = reader
@@ -476,6 +512,60 @@ class _TextPipeline(_RowPipeline):
                 for seg in out:
                     self._queued[seg[0]] = self._queued.get(seg[0], 0) + 1
             self._outq.put((out, act, pred))
+
+
+class FreqFileError(RuntimeError):
+    """call_mods --freq_file without a result file: the frequency stream cannot go on and there is no text to fall back to."""
+
+
+class _FreqTap:
+    """call_mods --freq_file: between the ordered writer and call_modification_frequency.FreqStream. rows() is the rows_sink of the
+    pipelines; finish() writes the table. When the stream cannot go on (_CpuRoute: no memory for a growth, > 2^23 chromosomes,
+    > 2^30 rows, a sampleinfo that is two lines of text) the reason is printed and the run ends in the cpu route over the result
+    file -- or, with no result file, in FreqFileError at once: never a truncated table."""
+
+    def __init__(self, freq_file, result_file, bed=False, sort=False, prob_cf=0.0, device=0, make_engine=None, info=None):
+        from . import call_modification_frequency as cmf
+        self.cmf, self.freq_file, self.result_file, self.bed, self.sort, self.prob_cf = cmf, freq_file, result_file, bed, sort, prob_cf
+        self.info = info           # when given: receives the stream's counts and device times (FreqStream.info)
+        self.error = None
+        self.stream = None
+        try:
+            self.stream = cmf.FreqStream(prob_cf, device=device, make_engine=make_engine)
+        except cmf._CpuRoute as exc:
+            self._give_up(exc)
+
+    def _give_up(self, exc):
+        self.error = str(exc)
+        self.close()
+        print("--freq_file: {}{}".format(self.error, "; the cpu route will read the result file.." if self.result_file else ""))
+        if not self.result_file:
+            raise FreqFileError("--freq_file: %s (no --result_file to compute the table from)" % self.error)
+
+    def rows(self, info, info_off, act, pred, kmer):
+        if self.error is None and len(pred):
+            try:
+                self.stream.push(info, info_off, act, pred, kmer)
+            except self.cmf._CpuRoute as exc:
+                self._give_up(exc)
+
+    def finish(self):
+        stats = None
+        if self.error is None:
+            try:
+                stats = self.stream.finish()
+                if self.info is not None:
+                    self.info.update(self.stream.info)
+            except self.cmf._CpuRoute as exc:      # the last rows went to the device only now
+                self._give_up(exc)
+        if stats is None:
+            stats = self.cmf.calculate_mods_frequency([self.result_file], self.prob_cf)
+        self.cmf.write_sitekey2stats(stats, self.freq_file, self.sort, self.bed)
+
+    def close(self):
+        stream, self.stream = self.stream, None
+        if stream is not None:
+            stream.close()
 
 
 def _check_parse_on(parse_on, input_path, native_io, engine):
@@ -623,7 +713,8 @@ def _call_mods_sharded(input_path, engine, batch_size, result_file, kmer_len, ce
 def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
               batch_size, learning_rate, class_num, nproc, is_gpu, is_rnn, is_base, is_cnn,
               f5_args, engine=None, f5_batch_num=None, native_io=True, precision="fp32", dist=None, force_sharded=False,
-              engine_batch=0, extract_on="cpu", recheck_margin=0.0, recheck_precision="fp32", parse_on="cpu"):
+              engine_batch=0, extract_on="cpu", recheck_margin=0.0, recheck_precision="fp32", parse_on="cpu",
+              freq_file=None, freq_bed=False, freq_sort=False, freq_prob_cf=0.0, freq_device=None, freq_make_engine=None, freq_info=None):
     """The reference's call_mods (call_modifications.py:417-495), same signature and argument meaning.
 
     learning_rate / is_gpu are accepted for signature compatibility: inference ignores the learning rate
@@ -640,14 +731,25 @@ def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
     comes out below it are run again in `recheck_precision` and take that result (make_engine); every rank of a multi-GPU run
     builds its own pair. parse_on="gpu" (feature-file input with the native reader only): the host only finds the rows; their
     ~411 decimal tokens each are parsed on the GPU straight into the forward's inputs (ds_submit_text). Same output bytes: a
-    row in a form the device does not parse goes through the host parser, and a malformed row raises the same ValueError."""
+    row in a form the device does not parse goes through the host parser, and a malformed row raises the same ValueError.
+    freq_file: also write the per-site frequency table `call_freq` computes from the result file (freq_bed / freq_sort /
+    freq_prob_cf: its --bed / --sort / --prob_cf) -- from the forward's results as they pass the ordered writer, with no row text
+    parsed, on an engine handle of its own on GPU `freq_device` (default: the forward's); byte-identical to `call_freq` on the
+    result file. result_file may then be None: no row text is made at all. Single process only (see _check_freq_file).
+    freq_info, when given, receives the stream's row counts and device times."""
     if extract_on not in ("cpu", "gpu"):
         raise ValueError("extract_on must be 'cpu' or 'gpu'")
+    if result_file is None and freq_file is None:
+        raise ValueError("call_mods needs a result_file (or a freq_file)")
+    if freq_file is not None and freq_prob_cf != freq_prob_cf:
+        raise ValueError("freq_prob_cf must be a number")
     _check_parse_on(parse_on, input_path, native_io, engine)
     if engine is None:
         check_recheck_args(precision, recheck_margin, recheck_precision)
     start = time.time()
     f5 = _unpack_f5_args(f5_args, f5_batch_num)
+    if freq_file is not None:
+        _check_freq_file(dist, force_sharded)
     dist, rank, world, local = _distributed_context(dist)
     if precision in ("bf16", "bf16_all") and rank == 0 and engine is None:
         # measured, DESIGN.md section 9: harmless on random-init weights, NOT on weights at a trained model's scale
@@ -665,11 +767,22 @@ def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
                              is_cnn=is_cnn, is_rnn=is_rnn, is_base=is_base, device=local, precision=precision,
                              engine_batch=engine_batch, recheck_margin=recheck_margin, recheck_precision=recheck_precision)
     recheck = None
-    text0 = engine.text_stats() if parse_on == "gpu" else None
+    tap = None
+    try:
+        if freq_file is not None:
+            tap = _FreqTap(freq_file, result_file, freq_bed, freq_sort, freq_prob_cf, local if freq_device is None else freq_device,
+                           freq_make_engine, freq_info)
+        text0 = engine.text_stats() if parse_on == "gpu" else None
+    except BaseException:
+        if own:
+            engine.close()
+        raise
+    rows_sink = tap.rows if tap is not None else None
     try:
         if os.path.isdir(input_path):
             nsites = _call_mods_from_fast5s(input_path, result_file, kmer_len, cent_signals_len, batch_size, f5, engine,
-                                            nproc=nproc, dist=dist, rank=rank, world=world, device=device, extract_on=extract_on)
+                                            nproc=nproc, dist=dist, rank=rank, world=world, device=device, extract_on=extract_on,
+                                            rows_sink=rows_sink)
         elif world > 1 or (force_sharded and dist is not None):
             # launched as `python -m torch.distributed.run --nproc-per-node N -m deepsignal_amd.deepsignal call_mods ...`
             if not native_io:
@@ -682,12 +795,13 @@ def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
             from . import fastio
             reader = fastio.FeatureReader(input_path, kmer_len, cent_signals_len)
             try:
-                with open(result_file, "wb") as wf:
+                with (open(result_file, "wb") if result_file is not None else contextlib.nullcontext()) as wf:
+                    sink = (lambda tag, data: wf.write(data)) if wf is not None else None
                     if parse_on == "gpu":
-                        pipe = _TextPipeline(engine, batch_size, lambda tag, data: wf.write(data), reader)
+                        pipe = _TextPipeline(engine, batch_size, sink, reader, rows_sink)
                         items = _prefetch(reader.spans(f5.f5_batch_num))
                     else:
-                        pipe = _RowPipeline(engine, batch_size, lambda tag, data: wf.write(data))
+                        pipe = _RowPipeline(engine, batch_size, sink, rows_sink)
                         items = _prefetch(reader.items(f5.f5_batch_num))
                     try:
                         for item in items:
@@ -696,19 +810,23 @@ def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
                     finally:
                         items.close()          # the parser thread has exited before the reader goes away
                         pipe.close()
-                    wf.flush()
+                    if wf is not None:
+                        wf.flush()
                 nsites = pipe.nsites
             finally:
                 reader.close()
         else:
             nsites = 0
-            with open(result_file, "w") as wf:
+            with (open(result_file, "w") if result_file is not None else contextlib.nullcontext()) as wf:
                 for item in iter_features_batches(input_path, f5.f5_batch_num):
-                    pred_str, _, _ = _call_mods(item, engine, batch_size)
+                    pred_str, _, _ = _call_mods(item, engine, batch_size, rows_sink, text=wf is not None)
                     for row in pred_str:
                         wf.write(row + "\n")
-                    wf.flush()
-                    nsites += len(pred_str)
+                    if wf is not None:
+                        wf.flush()
+                    nsites += len(item[0])
+        if tap is not None:
+            tap.finish()
         if own and recheck_margin > 0:
             recheck = engine.recheck_stats()
         if text0 is not None:
@@ -718,6 +836,8 @@ def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
         text0 = None
         raise
     finally:
+        if tap is not None:
+            tap.close()
         if own:
             engine.close()
     if recheck is not None:
@@ -777,10 +897,12 @@ def _fast5_reads_task(task):
     return ef._device_read_records(task, lambda fp: _read_features_from_fast5s([fp], *task[1:]))
 
 
-def _rows_from_device(records, engine, batch_size, normalize_method):
+def _rows_from_device(records, engine, batch_size, normalize_method, rows_sink=None, text=True, nrows_out=None):
     """Rows of one file batch, in file order: the GPU-route reads go through ds_submit_reads in batches of up to
     engine.max_batch sites (a read whose sites straddle two batches is carried by both), several batches in flight, rows
-    formatted by the native formatter; host-route reads run as the default route does."""
+    formatted by the native formatter; host-route reads run as the default route does. Returns the chunks of row text.
+    rows_sink / text: see _call_mods; nrows_out: a one-element list the number of rows is added to (text=False leaves no text to
+    count them in)."""
     import collections
     from . import fastio
     from .engine import ReadBatch
@@ -789,6 +911,7 @@ def _rows_from_device(records, engine, batch_size, normalize_method):
     inflight = collections.deque()
     cur = []                               # (record, first site, end site) of the batch being filled
     ncur = [0]
+    nrows = [0]
 
     def drain(limit):
         while len(inflight) > limit:
@@ -801,8 +924,12 @@ def _rows_from_device(records, engine, batch_size, normalize_method):
                 blob = b"".join(lines)
                 off = np.zeros(e - s + 1, np.int64)
                 off[1:] = np.cumsum([len(l) for l in lines])
-                out.append(fastio.format_rows(np.frombuffer(blob, np.uint8), off, act[o:o + e - s], pred[o:o + e - s],
-                                              rec[4][s:e]).decode())
+                if text:
+                    out.append(fastio.format_rows(np.frombuffer(blob, np.uint8), off, act[o:o + e - s], pred[o:o + e - s],
+                                                  rec[4][s:e]).decode())
+                if rows_sink is not None:
+                    rows_sink(np.frombuffer(blob, np.uint8), off, act[o:o + e - s], pred[o:o + e - s], rec[4][s:e])
+                nrows[0] += e - s
                 o += e - s
 
     def submit():
@@ -824,8 +951,9 @@ def _rows_from_device(records, engine, batch_size, normalize_method):
             submit()
             drain(0)
             for fb in rec[1][0]:
-                pred_str, _, _ = _call_mods(fb, engine, batch_size)
+                pred_str, _, _ = _call_mods(fb, engine, batch_size, rows_sink, text)
                 out.extend(r + "\n" for r in pred_str)
+                nrows[0] += len(fb[0])
             continue
         n, s = len(rec[2]), 0
         while s < n:
@@ -837,11 +965,13 @@ def _rows_from_device(records, engine, batch_size, normalize_method):
                 submit()
     submit()
     drain(0)
+    if nrows_out is not None:
+        nrows_out[0] += nrows[0]
     return out
 
 
 def _call_mods_from_fast5s(fast5_dir, result_file, kmer_len, cent_signals_len, batch_size, f5, engine, nproc=1,
-                           dist=None, rank=0, world=1, device=None, extract_on="cpu"):
+                           dist=None, rank=0, world=1, device=None, extract_on="cpu", rows_sink=None):
     """fast5-directory mode (reference call_modifications.py:431-448 + :300-414): batches of f5_batch_num files ->
     features on the host -> engine -> rows. Needs h5py for the HDF5 files. With world > 1 (one process per GPU) file
     batch k belongs to rank k % world -- extraction, the forward and row formatting all happen on the owning rank -- and
@@ -874,25 +1004,28 @@ def _call_mods_from_fast5s(fast5_dir, result_file, kmer_len, cent_signals_len, b
         from . import sharding
         gather = sharding.OrderedRowGather(dist, rank, world, result_file, nrounds=(len(tasks) + world - 1) // world,
                                            device=device)
-    wf = open(result_file, "w") if gather is None else None
+    wf = open(result_file, "w") if gather is None and result_file is not None else None
+    want_text = wf is not None or gather is not None       # call_mods --freq_file alone: no row text
     try:
         for batches, err in results:
             errors += err
             if extract_on == "gpu":
                 errors += sum(rec[1][1] for rec in batches if rec[0] == "cpu")
-                chunks = _rows_from_device(batches, engine, batch_size, f5.normalize_method)
+                nrows = [0]
+                chunks = _rows_from_device(batches, engine, batch_size, f5.normalize_method, rows_sink, want_text, nrows)
                 text = "".join(chunks)
-                nsites += text.count("\n")
+                nsites += nrows[0]
             else:
                 rows = []
                 for fb in batches:
-                    pred_str, _, _ = _call_mods(fb, engine, batch_size)
+                    pred_str, _, _ = _call_mods(fb, engine, batch_size, rows_sink, want_text)
                     rows.extend(pred_str)
-                nsites += len(rows)
+                    nsites += len(fb[0])
                 text = "".join(r + "\n" for r in rows)
             if gather is None:
-                wf.write(text)
-                wf.flush()
+                if wf is not None:
+                    wf.write(text)
+                    wf.flush()
             else:
                 gather.put(text.encode())
     except BaseException:

@@ -263,6 +263,8 @@ struct ds_handle {
     Times<1> rc_t;        // recheck_select_kernel launches timed while profiling was on
     dsf::Freq* freq = nullptr;            // call_freq --on gpu: the open run (ds_freq_begin .. ds_freq_end); its table and buffers are its own
     Times<4> fq_t;        // batches of the frequency runs ended so far (the open run's are added on top)
+    double fqs_ms[2] = {0, 0};        // streaming runs ended so far: freq_values_kernel, the table growths
+    int64_t fqs_growths = 0;
     // pipelining: consecutive forwards rotate over independent slots (own workspace, streams, graphs), so the
     // dependency chain of one 512-site forward overlaps the next ones'; weights are shared
     std::vector<Slot> slots;
@@ -2445,8 +2447,39 @@ static void freq_close(ds_handle* h)
     if (!h->freq) return;
     h->fq_t.batches += h->freq->batches;
     for (int i = 0; i < 4; ++i) h->fq_t.ms[i] += h->freq->ms[i];
+    for (int i = 0; i < 2; ++i) h->fqs_ms[i] += h->freq->sms[i];
+    h->fqs_growths += h->freq->growths;
     delete h->freq;
     h->freq = nullptr;
+}
+
+static int ds_freq_begin_stream_impl(ds_handle* h, int64_t initial_slots, int32_t batch_rows, double prob_cf)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (h->freq) return fail(h, DS_ERR_INVALID, "ds_freq_begin_stream: a run is open on this handle (ds_freq_end first)");
+    h->freq = new dsf::Freq();
+    std::string err;
+    const int rc = h->freq->begin_stream(h->cfg.device, initial_slots, batch_rows, prob_cf, &err);
+    if (rc) { delete h->freq; h->freq = nullptr; return fail(h, rc, err); }
+    return DS_OK;
+}
+
+static int ds_freq_push_impl(ds_handle* h, int32_t nrows, const int32_t* chrom, const int64_t* pos, const float* act, int32_t class_num,
+                             const int32_t* pred, int32_t* status, int32_t* opened)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (!h->freq) return fail(h, DS_ERR_INVALID, "ds_freq_push: no run is open (ds_freq_begin_stream first)");
+    std::string err;
+    const int rc = h->freq->push(nrows, chrom, pos, act, class_num, pred, status, opened, &err);
+    return rc ? fail(h, rc, err) : DS_OK;
+}
+
+static int ds_freq_values_impl(ds_handle* h, int64_t n, const float* act, int32_t class_num, double* p0, double* p1, int32_t* status)
+{
+    if (!h) return DS_ERR_INVALID;
+    std::string err;
+    const int rc = dsf::values_device(h->cfg.device, n, act, class_num, p0, p1, status, &err);
+    return rc ? fail(h, rc, err) : DS_OK;
 }
 
 static int ds_freq_begin_impl(ds_handle* h, int64_t total_rows, int32_t batch_rows, double prob_cf)
@@ -2507,6 +2540,25 @@ int64_t ds_freq_reference(const char* text, int64_t nrows, const int64_t* begin,
                                           site_pos, sum0, sum1, site_met, site_unmet, used, &err);
         return rc < 0 ? fail(nullptr, DS_ERR_INVALID, err) : rc;
     });
+}
+
+int ds_freq_values_reference(int64_t n, const float* act, int32_t class_num, double* p0, double* p1, int32_t* status)
+{
+    if (n < 0 || class_num < 2 || (n > 0 && (!act || !p0 || !p1 || !status))) return DS_ERR_INVALID;
+    return guarded(nullptr, [&]() -> int { dsf::values_reference(n, act, class_num, p0, p1, status); return DS_OK; });
+}
+
+int ds_get_freq_stream_times(ds_handle* h, int32_t reset, int64_t* growths, double* ms)
+{
+    if (!h || !growths || !ms) return DS_ERR_INVALID;
+    *growths = h->fqs_growths + (h->freq ? h->freq->growths : 0);
+    for (int i = 0; i < 2; ++i) ms[i] = h->fqs_ms[i] + (h->freq ? h->freq->sms[i] : 0.0);
+    if (reset) {
+        h->fqs_growths = 0;
+        h->fqs_ms[0] = h->fqs_ms[1] = 0;
+        if (h->freq) { h->freq->growths = 0; for (double& v : h->freq->sms) v = 0; }
+    }
+    return DS_OK;
 }
 
 int ds_get_freq_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms)
@@ -2992,6 +3044,9 @@ int64_t ds_extract_rows(ds_handle* h, const ds_reads* reads, const char* info, c
 int ds_set_recheck(ds_handle* coarse, ds_handle* fine, float margin) { return guarded(coarse, [&] { return ds_set_recheck_impl(coarse, fine, margin); }); }
 int ds_recheck_select(ds_handle* h, int32_t n, const float* act, float margin, int32_t* count, int32_t* index) { return guarded(h, [&] { return ds_recheck_select_impl(h, n, act, margin, count, index); }); }
 int64_t ds_format_values(ds_handle* h, int64_t n, const double* values, char* out, int64_t cap) { return guarded(h, [&] { return ds_format_values_impl(h, n, values, out, cap); }); }
+int ds_freq_begin_stream(ds_handle* h, int64_t initial_slots, int32_t batch_rows, double prob_cf) { return guarded(h, [&] { return ds_freq_begin_stream_impl(h, initial_slots, batch_rows, prob_cf); }); }
+int ds_freq_push(ds_handle* h, int32_t nrows, const int32_t* chrom, const int64_t* pos, const float* act, int32_t class_num, const int32_t* pred, int32_t* status, int32_t* opened) { return guarded(h, [&] { return ds_freq_push_impl(h, nrows, chrom, pos, act, class_num, pred, status, opened); }); }
+int ds_freq_values(ds_handle* h, int64_t n, const float* act, int32_t class_num, double* p0, double* p1, int32_t* status) { return guarded(h, [&] { return ds_freq_values_impl(h, n, act, class_num, p0, p1, status); }); }
 int ds_freq_begin(ds_handle* h, int64_t total_rows, int32_t batch_rows, double prob_cf) { return guarded(h, [&] { return ds_freq_begin_impl(h, total_rows, batch_rows, prob_cf); }); }
 int ds_freq_parse(ds_handle* h, const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, const int32_t* chrom, const uint8_t* flags, int32_t* status) { return guarded(h, [&] { return ds_freq_parse_impl(h, text, nrows, row_begin, row_end, chrom, flags, status); }); }
 int ds_freq_accumulate(ds_handle* h, int32_t nover, const int32_t* row, const int32_t* chrom, const int64_t* pos, const double* p0, const double* p1, const int32_t* met) { return guarded(h, [&] { return ds_freq_accumulate_impl(h, nover, row, chrom, pos, p0, p1, met); }); }

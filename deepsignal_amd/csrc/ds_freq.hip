@@ -133,6 +133,54 @@ __global__ __launch_bounds__(TPB) void freq_result_kernel(unsigned long long cap
     sum0[o] = t_sum0[s]; sum1[o] = t_sum1[s]; met[o] = t_met[s]; unmet[o] = t_unmet[s];
 }
 
+// call_mods --freq_file: a batch's values straight from the forward's act rows (call_value of ds_freq.h, the code the host
+// checker runs). chrom == nullptr: no key to check (ds_freq_values)
+__global__ __launch_bounds__(TPB) void freq_values_kernel(int n, const int32_t* chrom, const int64_t* pos, const float* act, int class_num,
+                                                          const int32_t* pred, double* p0, double* p1, int32_t* met, int32_t* status)
+{
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    double a = 0, c = 0;
+    int st = ROW_HOST;
+    if (!chrom || key_ok(chrom[i], pos[i])) st = call_value(act[(size_t)i * class_num], act[(size_t)i * class_num + 1], &a, &c);
+    p0[i] = a; p1[i] = c;
+    if (met) met[i] = pred[i] == 1;
+    status[i] = st;
+}
+
+// after freq_insert_kernel, before the sort permutes `sort`: row i opened its site when it is the site's first row of the run
+__global__ __launch_bounds__(TPB) void freq_opened_kernel(int n, unsigned long long row_base, const unsigned long long* sort,
+                                                          const unsigned long long* t_first, int32_t* opened)
+{
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long sk = sort[i];
+    opened[i] = sk != SORT_PAD && t_first[sk >> 32] == row_base + (unsigned long long)i;
+}
+
+// the table doubles: every occupied slot of the old table finds its slot in the new one (the same exact-key atomicCAS probe as
+// freq_insert_kernel; the keys are distinct and the new table is at most a quarter full) and takes its sums and counts along
+__global__ __launch_bounds__(TPB) void freq_rehash_kernel(unsigned long long old_cap, const unsigned long long* o_key, const unsigned long long* o_first,
+                                                          const double* o_sum0, const double* o_sum1, const int32_t* o_met, const int32_t* o_unmet,
+                                                          unsigned long long mask, unsigned long long* t_key, unsigned long long* t_first,
+                                                          double* t_sum0, double* t_sum1, int32_t* t_met, int32_t* t_unmet,
+                                                          unsigned long long* counters)
+{
+    const unsigned long long o = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
+    if (o >= old_cap) return;
+    const unsigned long long k = o_key[o];
+    if (k == EMPTY) return;
+    unsigned long long s = hash_key(k) & mask;
+    for (unsigned long long probe = 0; probe <= mask; ++probe) {
+        if (atomicCAS(&t_key[s], (unsigned long long)EMPTY, k) == EMPTY) {
+            t_first[s] = o_first[o]; t_sum0[s] = o_sum0[o]; t_sum1[s] = o_sum1[o]; t_met[s] = o_met[o]; t_unmet[s] = o_unmet[o];
+            return;
+        }
+        s = (s + 1) & mask;
+    }
+    atomicAdd(&counters[2], 1ull);      // no slot: cannot happen below a load of one half; the next accumulate reports it
+}
+
 int blocks(uint64_t n) { return (int)((n + TPB - 1) / TPB); }
 
 int seterr(std::string* err, int code, const std::string& msg)
@@ -156,6 +204,14 @@ void book(Freq* f, int slot, hipEvent_t a, hipEvent_t b)
     if (hipEventElapsedTime(&ms, a, b) == hipSuccess) f->ms[slot] += ms; else (void)hipGetLastError();
 }
 
+double span(hipEvent_t a, hipEvent_t b)
+{
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) return ms;
+    (void)hipGetLastError();
+    return 0;
+}
+
 }  // namespace
 
 int Freq::begin(int dev, int64_t total, int32_t batch, double prob_cf, std::string* err)
@@ -164,12 +220,38 @@ int Freq::begin(int dev, int64_t total, int32_t batch, double prob_cf, std::stri
     if (total < 1 || total > MAX_TOTAL_ROWS) return seterr(err, DS_ERR_INVALID, "ds_freq_begin: total_rows must be in [1, 2^30]");
     if (batch < 1 || batch > (1 << 24)) return seterr(err, DS_ERR_INVALID, "ds_freq_begin: batch_rows must be in [1, 2^24]");
     if (prob_cf != prob_cf) return seterr(err, DS_ERR_INVALID, "ds_freq_begin: prob_cf is NaN");
-    device = dev;
-    total_rows = total; rows_done = 0; batch_rows = batch; pending = -1; cf = prob_cf;
-    batches = 0;
-    for (double& v : ms) v = 0;
+    total_rows = total;
+    streaming = false;
     cap = 64;
     while (cap < 2 * (uint64_t)total) cap <<= 1;
+    return open(dev, batch, prob_cf, err);
+}
+
+int Freq::begin_stream(int dev, int64_t initial_slots, int32_t batch, double prob_cf, std::string* err)
+{
+    if (s) return seterr(err, DS_ERR_INVALID, "ds_freq_begin_stream: a run is open on this handle (ds_freq_end first)");
+    if (initial_slots < 1 || initial_slots > 2 * MAX_TOTAL_ROWS) return seterr(err, DS_ERR_INVALID, "ds_freq_begin_stream: initial_slots must be in [1, 2^31]");
+    if (batch < 1 || batch > (1 << 24)) return seterr(err, DS_ERR_INVALID, "ds_freq_begin_stream: batch_rows must be in [1, 2^24]");
+    if (prob_cf != prob_cf) return seterr(err, DS_ERR_INVALID, "ds_freq_begin_stream: prob_cf is NaN");
+    total_rows = MAX_TOTAL_ROWS;
+    streaming = true;
+    cap = 1;
+    while (cap < (uint64_t)initial_slots) cap <<= 1;
+    const int rc = open(dev, batch, prob_cf, err);
+    if (rc) return rc;
+    const size_t B = (size_t)batch;
+    FQ(hipMalloc((void**)&d_pred, B * 4));
+    FQ(hipMalloc((void**)&d_opened, B * 4));
+    return DS_OK;
+}
+
+int Freq::open(int dev, int32_t batch, double prob_cf, std::string* err)
+{
+    device = dev;
+    rows_done = 0; batch_rows = batch; pending = -1; cf = prob_cf;
+    batches = 0; sites = 0; growths = 0; opened_out = nullptr;
+    for (double& v : ms) v = 0;
+    for (double& v : sms) v = 0;
     P = 1;
     while (P < batch) P <<= 1;
     FQ(hipSetDevice(device));
@@ -204,10 +286,91 @@ int Freq::begin(int dev, int64_t total, int32_t batch, double prob_cf, std::stri
     return DS_OK;
 }
 
+// the table doubles until the batch's rows, were each a new site, leave it at most half full. The new table is complete before the
+// old one goes: a growth that does not fit the device leaves the run as it was (DS_ERR_NOMEM)
+int Freq::grow(int32_t n, std::string* err)
+{
+    uint64_t want = cap;
+    int doublings = 0;
+    while (2 * ((uint64_t)sites + (uint64_t)n) > want) { want <<= 1; ++doublings; }
+    if (want == cap) return DS_OK;
+    void* fresh[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t width[6] = {8, 8, 8, 8, 4, 4};
+    const int fill[6] = {0xff, 0xff, 0, 0, 0, 0};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipMalloc(&fresh[i], want * width[i]);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], s);
+    for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipMemsetAsync(fresh[i], fill[i], want * width[i], s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(freq_rehash_kernel, dim3(blocks(cap)), dim3(TPB), 0, s, (unsigned long long)cap, reinterpret_cast<const unsigned long long*>(t_key),
+                           reinterpret_cast<const unsigned long long*>(t_first), t_sum0, t_sum1, t_met, t_unmet, (unsigned long long)(want - 1),
+                           static_cast<unsigned long long*>(fresh[0]), static_cast<unsigned long long*>(fresh[1]), static_cast<double*>(fresh[2]),
+                           static_cast<double*>(fresh[3]), static_cast<int32_t*>(fresh[4]), static_cast<int32_t*>(fresh[5]), counters);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[1], s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (void* p : fresh) if (p) (void)hipFree(p);
+        return seterr(err, e == hipErrorOutOfMemory ? DS_ERR_NOMEM : DS_ERR_HIP,
+                      "ds_freq_push: growing the site table to " + std::to_string(want) + " slots: " + hipGetErrorString(e));
+    }
+    sms[1] += span(ev[0], ev[1]);
+    void* old[6] = {t_key, t_first, t_sum0, t_sum1, t_met, t_unmet};
+    for (void* p : old) (void)hipFree(p);
+    t_key = static_cast<uint64_t*>(fresh[0]); t_first = static_cast<uint64_t*>(fresh[1]);
+    t_sum0 = static_cast<double*>(fresh[2]); t_sum1 = static_cast<double*>(fresh[3]);
+    t_met = static_cast<int32_t*>(fresh[4]); t_unmet = static_cast<int32_t*>(fresh[5]);
+    cap = want;
+    growths += doublings;       // several doublings at once are one rehash
+    return DS_OK;
+}
+
+int Freq::push(int32_t n, const int32_t* chrom, const int64_t* pos, const float* act, int32_t class_num, const int32_t* pred, int32_t* status,
+               int32_t* opened, std::string* err)
+{
+    if (!s || !streaming) return seterr(err, DS_ERR_INVALID, "ds_freq_push: no streaming run is open (ds_freq_begin_stream first)");
+    if (pending >= 0) return seterr(err, DS_ERR_INVALID, "ds_freq_push: the previous batch has not been accumulated");
+    if (!chrom || !pos || !act || !pred || !status || !opened) return seterr(err, DS_ERR_INVALID, "ds_freq_push: null argument");
+    if (n < 1 || n > batch_rows) return seterr(err, DS_ERR_INVALID, "ds_freq_push: nrows must be in [1, batch_rows]");
+    if (class_num < 2 || class_num > 1024) return seterr(err, DS_ERR_INVALID, "ds_freq_push: class_num must be in [2, 1024]");
+    if (rows_done + n > total_rows) return seterr(err, DS_ERR_INVALID, "ds_freq_push: more than 2^30 rows in one run");
+    FQ(hipSetDevice(device));
+    const int rc = grow(n, err);
+    if (rc) return rc;
+    const size_t need = (size_t)n * (size_t)class_num;
+    if (need > act_cap) {
+        if (d_act) { FQ(hipFree(d_act)); d_act = nullptr; act_cap = 0; }
+        const size_t want = (size_t)batch_rows * (size_t)class_num;
+        FQ(hipMalloc((void**)&d_act, want * 4));
+        act_cap = want;
+    }
+    FQ(hipEventRecord(ev[0], s));
+    FQ(hipMemcpyAsync(d_chrom, chrom, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    FQ(hipMemcpyAsync(d_pos, pos, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    FQ(hipMemcpyAsync(d_act, act, need * 4, hipMemcpyHostToDevice, s));
+    FQ(hipMemcpyAsync(d_pred, pred, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    FQ(hipEventRecord(ev[1], s));
+    hipLaunchKernelGGL(freq_values_kernel, dim3(blocks(n)), dim3(TPB), 0, s, n, d_chrom, d_pos, d_act, class_num, d_pred, d_p0, d_p1, d_met, d_status);
+    FQ(hipGetLastError());
+    FQ(hipEventRecord(ev[2], s));
+    FQ(hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    FQ(hipEventRecord(ev[3], s));
+    FQ(hipStreamSynchronize(s));
+    book(this, 0, ev[0], ev[1]);
+    sms[0] += span(ev[1], ev[2]);
+    book(this, 0, ev[2], ev[3]);
+    pending = n;
+    opened_out = opened;
+    return DS_OK;
+}
+
 int Freq::parse(const char* text, int32_t n, const int64_t* rb, const int64_t* re, const int32_t* chrom, const uint8_t* flags, int32_t* status,
                 std::string* err)
 {
     if (!s) return seterr(err, DS_ERR_INVALID, "ds_freq_parse: no run is open (ds_freq_begin first)");
+    if (streaming) return seterr(err, DS_ERR_INVALID, "ds_freq_parse: the open run is a streaming one (ds_freq_push)");
     if (pending >= 0) return seterr(err, DS_ERR_INVALID, "ds_freq_parse: the previous batch has not been accumulated");
     if (!text || !rb || !re || !chrom || !flags || !status) return seterr(err, DS_ERR_INVALID, "ds_freq_parse: null argument");
     if (n < 1 || n > batch_rows) return seterr(err, DS_ERR_INVALID, "ds_freq_parse: nrows must be in [1, batch_rows]");
@@ -301,6 +464,12 @@ int Freq::accumulate(int32_t m, const int32_t* row, const int32_t* chrom, const 
                        d_status, reinterpret_cast<unsigned long long*>(t_key), reinterpret_cast<unsigned long long*>(t_first),
                        (unsigned long long)(cap - 1), reinterpret_cast<unsigned long long*>(d_sort), counters);
     FQ(hipGetLastError());
+    if (streaming) {
+        hipLaunchKernelGGL(freq_opened_kernel, dim3(blocks(n)), dim3(TPB), 0, s, n, (unsigned long long)rows_done, reinterpret_cast<const unsigned long long*>(d_sort),
+                           reinterpret_cast<const unsigned long long*>(t_first), d_opened);
+        FQ(hipGetLastError());
+        FQ(hipMemcpyAsync(opened_out, d_opened, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    }
     FQ(hipEventRecord(ev[2], s));
     for (int k = 2; k <= Pn; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
@@ -321,7 +490,9 @@ int Freq::accumulate(int32_t m, const int32_t* row, const int32_t* chrom, const 
     book(this, 3, ev[3], ev[4]);
     batches += 1;
     pending = -1;
+    opened_out = nullptr;
     rows_done += n;
+    sites = (int64_t)c[0];
     if (c[3]) return seterr(err, DS_ERR_INVALID, "ds_freq_accumulate: " + std::to_string(c[3]) + " row(s) of the batch were left to the caller and got no values");
     if (c[2]) return seterr(err, DS_ERR_INVALID, "ds_freq_accumulate: the site table is full");
     return DS_OK;
@@ -380,16 +551,52 @@ void Freq::end()
     (void)hipSetDevice(device);
     if (s) (void)hipStreamSynchronize(s);
     void* ptrs[] = {t_key, t_first, t_sum0, t_sum1, t_met, t_unmet, counters, d_text, d_off, d_len, d_chrom, d_status, d_met, d_flags, d_pos,
-                    d_p0, d_p1, d_sort, d_over};
+                    d_p0, d_p1, d_sort, d_over, d_act, d_pred, d_opened};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     t_key = t_first = nullptr; t_sum0 = t_sum1 = nullptr; t_met = t_unmet = nullptr; counters = nullptr;
     d_text = nullptr; d_off = nullptr; d_len = d_chrom = d_status = d_met = nullptr; d_flags = nullptr; d_pos = nullptr;
     d_p0 = d_p1 = nullptr; d_sort = nullptr; d_over = nullptr;
-    text_cap = over_cap = 0;
+    d_act = nullptr; d_pred = d_opened = nullptr; opened_out = nullptr;
+    text_cap = over_cap = act_cap = 0;
     for (hipEvent_t& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     if (s) { (void)hipStreamDestroy(s); s = nullptr; }
     (void)hipGetLastError();
     pending = -1;
+}
+
+void values_reference(int64_t n, const float* act, int32_t class_num, double* p0, double* p1, int32_t* status)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        double a = 0, c = 0;
+        status[i] = call_value(act[i * class_num], act[i * class_num + 1], &a, &c);
+        p0[i] = a; p1[i] = c;
+    }
+}
+
+int values_device(int device, int64_t n, const float* act, int32_t class_num, double* p0, double* p1, int32_t* status, std::string* err)
+{
+    if (n < 1 || n > (1 << 24) || class_num < 2 || class_num > 1024 || !act || !p0 || !p1 || !status)
+        return seterr(err, DS_ERR_INVALID, "ds_freq_values: bad argument (1 <= n <= 2^24 rows of 2 <= class_num <= 1024 floats)");
+    FQ(hipSetDevice(device));
+    const size_t N = (size_t)n;
+    char* d = nullptr;
+    FQ(hipMalloc((void**)&d, N * (16 + 4 + 4 * (size_t)class_num)));
+    double* d_a = reinterpret_cast<double*>(d);
+    double* d_c = d_a + N;
+    int32_t* d_st = reinterpret_cast<int32_t*>(d_c + N);
+    float* d_in = reinterpret_cast<float*>(d_st + N);
+    hipError_t e = hipMemcpy(d_in, act, N * 4 * (size_t)class_num, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(freq_values_kernel, dim3(blocks(N)), dim3(TPB), 0, nullptr, (int)n, nullptr, nullptr, d_in, class_num, nullptr, d_a, d_c,
+                           nullptr, d_st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(p0, d_a, N * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(p1, d_c, N * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(status, d_st, N * 4, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) { (void)hipGetLastError(); return seterr(err, DS_ERR_HIP, std::string("ds_freq_values: ") + hipGetErrorString(e)); }
+    return DS_OK;
 }
 
 int64_t reference(const char* text, int64_t nrows, const int64_t* begin, const int64_t* end, const int32_t* chrom, const uint8_t* flags, double cf,

@@ -771,4 +771,78 @@ int64_t ds_freq_locate(const char* text, int64_t nbytes, int64_t cap_rows, int64
     return nrows;
 }
 
+// The keys of call_mods --freq_file: the rows are not text yet, each is its sampleinfo [info_off[i], info_off[i + 1]) -- chrom \t pos \t
+// strand \t pos_in_strand \t readname \t read_strand -- and the row call_mods prints starts with those bytes. Column 0 goes through the
+// same name -> id table as ds_freq_locate's (first-appearance order, names '\n'-joined), column 1 is read as plain digits. Flag 1,
+// chromosome -1, no name registered -- the caller formats the row and lets Python read it -- for what Python strips or decodes
+// differently (empty, first or last byte whitespace, a byte >= 0x80, a '\r' or '\n'), for any number of columns but six, and for a position
+// that is not 1 .. 13 digits below 2^40.
+int64_t ds_freq_keys(int64_t n, const char* info, const int64_t* info_off, int32_t* chrom, int64_t* pos, uint8_t* flags, char* names,
+                     int64_t names_cap, int64_t* names_bytes, int32_t* n_names)
+{
+    if (n < 0 || names_cap < 0 || !names_bytes || !n_names || (n > 0 && (!info || !info_off || !chrom || !pos || !flags)) ||
+        (names_cap > 0 && !names))
+        return DS_ERR_INVALID;
+    auto is_space = [](unsigned char c) { return c == ' ' || (c >= 9 && c <= 13) || (c >= 0x1c && c <= 0x1f); };
+    std::unordered_map<std::string_view, int32_t> table;
+    const char* prev = nullptr;
+    size_t prev_len = 0;
+    int32_t prev_id = -1;
+    int64_t nb = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (info_off[i] < 0 || info_off[i + 1] < info_off[i]) return DS_ERR_INVALID;
+        const char* p = info + info_off[i];
+        const char* e = info + info_off[i + 1];
+        bool host = e == p || is_space((unsigned char)p[0]) || is_space((unsigned char)e[-1]);
+        int tabs = 0;
+        const char* c1 = nullptr;      // column 1 = [c1, c1e)
+        const char* c1e = nullptr;
+        for (const char* q = p; q < e && !host; ++q) {
+            const unsigned char c = (unsigned char)*q;
+            if (c >= 0x80 || c == '\r' || c == '\n') host = true;
+            if (c == '\t') {
+                ++tabs;
+                if (tabs == 1) c1 = q + 1;
+                if (tabs == 2) c1e = q;
+            }
+        }
+        int64_t v = 0;
+        if (!host) {
+            host = tabs != 5 || c1e == c1 || c1e - c1 > 13;      // a seventh column would sit where the cpu route reads prob_0
+            for (const char* q = c1; !host && q < c1e; ++q) {
+                if ((unsigned)((unsigned char)*q - '0') > 9u) host = true;
+                v = v * 10 + (*q - '0');
+            }
+            if (v >= ((int64_t)1 << 40)) host = true;
+        }
+        int32_t id = -1;
+        if (!host) {
+            const size_t len = (size_t)(c1 - 1 - p);
+            if (prev && len == prev_len && memcmp(p, prev, len) == 0) {
+                id = prev_id;
+            } else {
+                auto it = table.find(std::string_view(p, len));
+                if (it != table.end()) {
+                    id = it->second;
+                } else {
+                    id = (int32_t)table.size();
+                    table.emplace(std::string_view(p, len), id);
+                    if (nb + (int64_t)len + 1 <= names_cap) {
+                        memcpy(names + nb, p, len);
+                        names[nb + (int64_t)len] = '\n';
+                    }
+                    nb += (int64_t)len + 1;
+                }
+                prev = p; prev_len = len; prev_id = id;
+            }
+        }
+        chrom[i] = id;
+        pos[i] = host ? 0 : v;
+        flags[i] = host ? 1 : 0;
+    }
+    *names_bytes = nb;
+    *n_names = (int32_t)table.size();
+    return n;
+}
+
 }  // extern "C"

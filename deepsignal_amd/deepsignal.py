@@ -26,7 +26,9 @@ def main_call_mods(args):
               args.batch_size, args.learning_rate, args.class_num, args.nproc, str2bool(args.is_gpu),
               str2bool(args.is_rnn), str2bool(args.is_base), str2bool(args.is_cnn), f5_args,
               precision=args.precision, engine_batch=args.engine_batch, extract_on=args.extract_on,
-              recheck_margin=args.recheck_margin, recheck_precision=args.recheck_precision, parse_on=args.parse_on)
+              recheck_margin=args.recheck_margin, recheck_precision=args.recheck_precision, parse_on=args.parse_on,
+              freq_file=args.freq_file, freq_bed=args.freq_bed, freq_sort=args.freq_sort, freq_prob_cf=args.freq_prob_cf,
+              freq_device=args.freq_device)
 
 
 def main_extraction(args):
@@ -52,7 +54,18 @@ def main_call_freq(args):
     return freq_main(argv)
 
 
-def build_parser():
+def _names_freq_file(argv) -> bool:
+    """Does the command line give call_mods' --freq_file (spelled out, abbreviated as argparse allows, or with '=')?"""
+    for a in argv:
+        name = a.split("=", 1)[0]
+        if len(name) >= len("--freq_f") and "--freq_file".startswith(name):
+            return True
+    return False
+
+
+def build_parser(freq_file_given=True):
+    """freq_file_given: call_mods' --result_file is required unless --freq_file is on the command line; main() passes what it sees
+    there, so that without --freq_file argparse raises the error it always raised, with every missing flag in it."""
     parser = argparse.ArgumentParser(prog="deepsignal", description="call_mods on MI355X (gfx950)")
     sub = parser.add_subparsers(title="modules", dest="module")
     # `extract`: the step before the path -- fast5 -> feature TSV (reference deepsignal/deepsignal.py:155-234, same flags)
@@ -128,7 +141,16 @@ def build_parser():
     g.add_argument("--learning_rate", "-l", type=float, default=0.001)
     g.add_argument("--class_num", "-c", type=int, default=2)
     g = p.add_argument_group("OUTPUT")
-    g.add_argument("--result_file", "-o", required=True)
+    g.add_argument("--result_file", "-o", required=not freq_file_given, default=None,
+                   help="the calls, one row per (read, site); may be left out only with --freq_file")
+    g.add_argument("--freq_file", default=None,
+                   help="also write the per-site frequency table `call_freq` computes from the result file, straight from the forward's "
+                        "results (no result text is parsed; without --result_file none is written); same bytes as call_freq on the "
+                        "result file. Single process only")
+    g.add_argument("--freq_bed", action="store_true", default=False, help="--freq_file: bedMethyl (call_freq --bed)")
+    g.add_argument("--freq_sort", action="store_true", default=False, help="--freq_file: sites sorted by (chromosome, position) (call_freq --sort)")
+    g.add_argument("--freq_prob_cf", type=float, default=0.0, help="--freq_file: leave out calls with |prob_0 - prob_1| below this (call_freq --prob_cf)")
+    g.add_argument("--freq_device", type=int, default=None, help="--freq_file: GPU ordinal of the aggregation (default: the forward's)")
     g = p.add_argument_group("EXTRACTION")
     g.add_argument("--recursively", "-r", default="yes")
     g.add_argument("--corrected_group", default="RawGenomeCorrected_000")
@@ -142,6 +164,7 @@ def build_parser():
     p.add_argument("--nproc", "-p", type=int, default=1)
     p.add_argument("--is_gpu", default="no", choices=["yes", "no"])
     p.set_defaults(func=main_call_mods)
+    parser.call_mods_parser = p      # main() raises the usage errors that span several flags
     # `call_freq`: the step after the path -- call_mods result files -> per-site frequency table or bedMethyl (the reference's later
     # releases expose scripts/call_modification_frequency.py under this name; same flags, plus --on / --device)
     f = sub.add_parser("call_freq", description="calculate the modification frequency of every site from call_mods result files")
@@ -160,7 +183,7 @@ def build_parser():
 
 
 def main(argv=None):
-    parser = build_parser()
+    parser = build_parser(_names_freq_file(sys.argv[1:] if argv is None else argv))
     args = parser.parse_args(argv)
     if not getattr(args, "func", None):
         parser.print_help()
@@ -171,6 +194,27 @@ def main(argv=None):
             check_recheck_args(args.precision, args.recheck_margin, args.recheck_precision)
         except ValueError as exc:
             parser.error(str(exc))
+        sub = parser.call_mods_parser
+        if args.result_file is None and args.freq_file is None:      # "--freq_f" given as another flag's value
+            sub.error("the following arguments are required: --result_file/-o")
+        if args.freq_file is None and (args.freq_bed or args.freq_sort or args.freq_prob_cf != 0.0 or args.freq_device is not None):
+            sub.error("--freq_bed / --freq_sort / --freq_prob_cf / --freq_device need --freq_file")
+        if args.freq_file is not None:
+            from .call_modifications import FreqFileError, _check_freq_file
+            if args.freq_prob_cf != args.freq_prob_cf:
+                sub.error("--freq_prob_cf must be a number")
+            if args.freq_device is not None and args.freq_device < 0:
+                sub.error("--freq_device must be >= 0")
+            try:
+                _check_freq_file(None, False)
+            except ValueError as exc:
+                sub.error(str(exc))
+            try:
+                args.func(args)
+            except FreqFileError as exc:
+                print(str(exc), file=sys.stderr)
+                return 1
+            return 0
     if args.module == "call_freq":
         return args.func(args)       # the script's own main: it validates the forwarded flags and returns the exit status
     args.func(args)

@@ -47,6 +47,8 @@ EXPORTED_SYMBOLS = (
     # per-site modification frequency on the device (call_freq --on gpu)
     "ds_freq_locate", "ds_freq_begin", "ds_freq_parse", "ds_freq_accumulate", "ds_freq_result", "ds_freq_end",
     "ds_freq_reference", "ds_get_freq_times",
+    # ... and straight from the forward's results (call_mods --freq_file)
+    "ds_freq_begin_stream", "ds_freq_push", "ds_freq_keys", "ds_freq_values", "ds_freq_values_reference", "ds_get_freq_stream_times",
 )
 
 
@@ -297,6 +299,52 @@ def freq_reference(text, begin, end, chrom, flags, prob_cf: float = 0.0, given=N
     return out
 
 
+def freq_keys(info, info_off):
+    """ds_freq_keys: the site keys of n sampleinfo strings (info: a flat byte buffer, info_off int64[n + 1]) -> (chrom int32[n],
+    pos int64[n], flags uint8[n], names): chrom indexes `names` (bytes, first-appearance order within this call); flags 1 = a row to
+    format and let Python read (chrom -1)."""
+    lib = load_library()
+    info = np.ascontiguousarray(info, np.uint8)
+    off = np.ascontiguousarray(info_off, np.int64)
+    n = int(off.size) - 1
+    if info.ndim != 1 or off.ndim != 1 or n < 0:
+        raise ValueError("info must be a flat byte buffer and info_off hold n + 1 offsets")
+    if n and (int(off[0]) < 0 or int(off[-1]) > info.size or bool((np.diff(off) < 0).any())):
+        raise ValueError("info_off must ascend inside info")
+    chrom, pos, flags = np.empty(n, np.int32), np.empty(n, np.int64), np.empty(n, np.uint8)
+    nb, nn = ctypes.c_int64(), ctypes.c_int32()
+    names_cap = 1 << 12
+    while True:
+        names = np.empty(names_cap, np.uint8)
+        got = int(lib.ds_freq_keys(n, info.ctypes.data if info.size else None, off.ctypes.data, chrom.ctypes.data, pos.ctypes.data,
+                                   flags.ctypes.data, names.ctypes.data, names_cap, ctypes.byref(nb), ctypes.byref(nn)))
+        if got != n:
+            raise RuntimeError("ds_freq_keys failed (%d)" % got)
+        if nb.value <= names_cap:
+            return chrom, pos, flags, names[:nb.value].tobytes().split(b"\n")[:nn.value]
+        names_cap = int(nb.value)
+
+
+def _act_rows(act):
+    act = np.ascontiguousarray(act, np.float32)
+    if act.ndim != 2 or act.shape[1] < 2:
+        raise ValueError("act must be [n, class_num >= 2] float32")
+    return act
+
+
+def freq_values_reference(act) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """ds_freq_values_reference: per act row the two doubles call_freq reads from the row call_mods prints for it, and the status
+    (TEXT_ROW_OK / TEXT_ROW_HOST), by the routine freq_values_kernel runs -- on the CPU. A checker for the tests, not a fall-back."""
+    lib = load_library()
+    act = _act_rows(act)
+    n = act.shape[0]
+    p0, p1, status = np.zeros(n, np.float64), np.zeros(n, np.float64), np.zeros(n, np.int32)
+    rc = lib.ds_freq_values_reference(n, act.ctypes.data, act.shape[1], p0.ctypes.data, p1.ctypes.data, status.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("ds_freq_values_reference failed (%d)" % rc)
+    return p0, p1, status
+
+
 # ds_config.precision (include/deepsignal_hip.h): "bf16" = bf16 conv + FC operands with fp32 accumulation, fp32 BiLSTM;
 # "bf16_all" = also bf16 h / weight operands in the LSTM matmuls (fp32 accumulate, gates, cell state)
 PRECISIONS = {"fp32": 0, "bf16": 1, "bf16_all": 2, "bf16x3": 3}
@@ -412,6 +460,13 @@ def load_library() -> ctypes.CDLL:
                                       ctypes.POINTER(i64)]
     lib.ds_freq_reference.restype = i64
     lib.ds_get_freq_times.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(f64)]
+    lib.ds_freq_begin_stream.argtypes = [vp, i64, i32, f64]
+    lib.ds_freq_push.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp]
+    lib.ds_freq_keys.argtypes = [i64, vp, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i32)]
+    lib.ds_freq_keys.restype = i64
+    lib.ds_freq_values.argtypes = [vp, i64, vp, i32, vp, vp, vp]
+    lib.ds_freq_values_reference.argtypes = [i64, vp, i32, vp, vp, vp]
+    lib.ds_get_freq_stream_times.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(f64)]
     _lib = lib
     return lib
 
@@ -669,6 +724,59 @@ class Engine:
         self._check(rc, "ds_freq_begin")
         self._freq_batch, self._freq_pending = batch_rows, -1
 
+    def freq_begin_stream(self, initial_slots: int, batch_rows: int, prob_cf: float = 0.0) -> None:
+        """ds_freq_begin_stream: open a run whose number of rows is not known: the site table starts with initial_slots slots and
+        doubles as sites arrive; batches come through freq_push. FreqNoMemory when the table or the buffers do not fit the device."""
+        initial_slots, batch_rows, prob_cf = int(initial_slots), int(batch_rows), float(prob_cf)
+        if not 1 <= initial_slots <= 2 * FREQ_MAX_ROWS:
+            raise ValueError("initial_slots must be in [1, 2^31]")
+        if not 1 <= batch_rows <= FREQ_MAX_BATCH:
+            raise ValueError("batch_rows must be in [1, 2^24]")
+        if prob_cf != prob_cf:
+            raise ValueError("prob_cf must not be NaN")
+        rc = self._lib.ds_freq_begin_stream(self._h, initial_slots, batch_rows, prob_cf)
+        if rc == -5:
+            raise FreqNoMemory(self._lib.ds_last_error(self._h).decode())
+        self._check(rc, "ds_freq_begin_stream")
+        self._freq_batch, self._freq_pending, self._freq_opened = batch_rows, -1, None
+
+    def freq_push(self, chrom, pos, act, pred) -> np.ndarray:
+        """ds_freq_push: one batch of a streaming run -- chromosome ids, positions (freq_keys, the ids mapped to one numbering for
+        the run; -1 = a row for Python), the forward's act rows and pred -> the per-row status (TEXT_ROW_OK / TEXT_ROW_HOST).
+        freq_accumulate completes the batch and returns which rows opened a site. FreqNoMemory: the table could not grow."""
+        chrom, pred = np.ascontiguousarray(chrom, np.int32), np.ascontiguousarray(pred, np.int32)
+        pos = np.ascontiguousarray(pos, np.int64)
+        act = _act_rows(act)
+        n = act.shape[0]
+        if chrom.shape != (n,) or pos.shape != (n,) or pred.shape != (n,):
+            raise ValueError("chrom / pos / pred must have one entry per act row")
+        if not 1 <= n <= getattr(self, "_freq_batch", 0):
+            raise ValueError("a batch holds 1 .. batch_rows rows of an open run")
+        status, opened = np.empty(n, np.int32), np.zeros(n, np.int32)
+        rc = self._lib.ds_freq_push(self._h, n, chrom.ctypes.data, pos.ctypes.data, act.ctypes.data, act.shape[1], pred.ctypes.data,
+                                    status.ctypes.data, opened.ctypes.data)
+        if rc == -5:
+            raise FreqNoMemory(self._lib.ds_last_error(self._h).decode())
+        self._check(rc, "ds_freq_push")
+        self._freq_pending, self._freq_opened = n, opened        # the library fills `opened` when the batch is accumulated
+        return status
+
+    def freq_values(self, act) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """ds_freq_values: freq_values_kernel alone over act rows -> (p0, p1, status); what freq_values_reference gives on the CPU."""
+        act = _act_rows(act)
+        n = act.shape[0]
+        p0, p1, status = np.zeros(n, np.float64), np.zeros(n, np.float64), np.zeros(n, np.int32)
+        self._check(self._lib.ds_freq_values(self._h, n, act.ctypes.data, act.shape[1], p0.ctypes.data, p1.ctypes.data,
+                                             status.ctypes.data), "ds_freq_values")
+        return p0, p1, status
+
+    def freq_stream_times(self, reset: bool = False) -> dict:
+        """ds_get_freq_stream_times: device milliseconds of freq_values_kernel and of the table growths, and their number."""
+        n = ctypes.c_int64()
+        ms = (ctypes.c_double * 2)()
+        self._check(self._lib.ds_get_freq_stream_times(self._h, int(reset), ctypes.byref(n), ms), "ds_get_freq_stream_times")
+        return dict(zip(("values_ms", "rehash_ms"), ms), growths=int(n.value))
+
     def freq_parse(self, text, begin, end, chrom, flags) -> np.ndarray:
         """ds_freq_parse: one batch of rows (ascending spans of one buffer; chrom / flags per row as freq_locate gives them, the
         ids mapped to one numbering for the whole run) parsed on the GPU -> the per-row status (TEXT_ROW_OK / TEXT_ROW_HOST)."""
@@ -688,9 +796,10 @@ class Engine:
         self._freq_pending = n
         return status
 
-    def freq_accumulate(self, rows=(), chrom=(), pos=(), p0=(), p1=(), met=()) -> None:
-        """ds_freq_accumulate: add the batch just parsed to the run. rows .. met: the caller's values for the batch's
-        TEXT_ROW_HOST rows (ascending batch row indices, every such row; 0 <= chrom < 2^23, 0 <= pos < 2^40)."""
+    def freq_accumulate(self, rows=(), chrom=(), pos=(), p0=(), p1=(), met=()) -> Optional[np.ndarray]:
+        """ds_freq_accumulate: add the batch just parsed (or pushed) to the run. rows .. met: the caller's values for the batch's
+        TEXT_ROW_HOST rows (ascending batch row indices, every such row; 0 <= chrom < 2^23, 0 <= pos < 2^40). After freq_push:
+        returns int32[n], 1 where the row is the first used row of a new site."""
         rows, chrom, met = (np.ascontiguousarray(a, np.int32) for a in (rows, chrom, met))
         pos = np.ascontiguousarray(pos, np.int64)
         p0, p1 = np.ascontiguousarray(p0, np.float64), np.ascontiguousarray(p1, np.float64)
@@ -705,8 +814,12 @@ class Engine:
         if m and (int(chrom.min()) < 0 or int(chrom.max()) >= FREQ_CHROM_LIMIT or int(pos.min()) < 0 or int(pos.max()) >= FREQ_POS_LIMIT):
             raise ValueError("override chromosome ids / positions must fit the key (2^23 ids, pos < 2^40)")
         self._freq_pending = -1
+        # the library holds the address of `opened` until it has accumulated the batch or the run ends: so does this object
+        opened = getattr(self, "_freq_opened", None)
         self._check(self._lib.ds_freq_accumulate(self._h, m, rows.ctypes.data, chrom.ctypes.data, pos.ctypes.data, p0.ctypes.data,
                                                  p1.ctypes.data, met.ctypes.data), "ds_freq_accumulate")
+        self._freq_opened = None
+        return opened
 
     def freq_result(self) -> Dict[str, np.ndarray]:
         """ds_freq_result: the sites of the run so far, in no particular order -> first_row, chrom, pos, sum0, sum1, met, unmet
@@ -727,6 +840,7 @@ class Engine:
     def freq_end(self) -> None:
         self._freq_batch, self._freq_pending = 0, -1
         self._check(self._lib.ds_freq_end(self._h), "ds_freq_end")
+        self._freq_opened = None
 
     def freq_times(self, reset: bool = False) -> dict:
         """ds_get_freq_times: device milliseconds of the frequency batches so far (copies, parse kernel, sort, insert + accumulate)."""

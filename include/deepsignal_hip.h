@@ -491,6 +491,47 @@ int64_t ds_freq_reference(const char *text, int64_t nrows, const int64_t *row_be
  * timed. reset != 0 clears the sums. */
 int ds_get_freq_times(ds_handle *h, int32_t reset, int64_t *batches, double *ms);
 
+/* ---- the same table straight from the forward's results (call_mods --freq_file) ---------------------------------------------------
+ * A streaming run takes its rows as call_mods has them -- the site key from the row's sampleinfo, the forward's act row and pred
+ * -- in the order the result file has, or would have; no result text is written or parsed. The number of rows is not known up front.
+ *
+ * ds_freq_begin_stream opens it in the place of ds_freq_begin: the table starts with initial_slots slots (1 .. 2^31, rounded up to a
+ * power of two) and doubles, before a batch is inserted, whenever 2 * (sites so far + rows of the batch) exceeds the slots:
+ * freq_rehash_kernel moves every occupied slot -- key, first row, sums, counts -- into the new table by the same exact-key
+ * atomicCAS probe. A growth that does not fit the device returns DS_ERR_NOMEM and leaves the run as it was (a smaller batch may
+ * still fit; ds_freq_result still answers). At most 2^30 rows in a run.
+ *
+ * ds_freq_push takes the place of ds_freq_parse; all arrays are HOST arrays of nrows entries (1 <= nrows <= batch_rows): chromosome
+ * id and position (ds_freq_keys), act (nrows rows of class_num floats, columns 0 and 1 are read) and pred as ds_wait returned them.
+ * freq_values_kernel computes per row, in float32 as the row formatter does, q0 = a0 / (a0 + a1) and q1 = a1 / (a0 + a1), then for
+ * each the double that Python's float() reads from str(numpy.float32(q)): the shortest digits that round-trip float32, found with
+ * integer arithmetic alone, and one exact-operand IEEE division (csrc/ds_freq.h call_value). met = pred == 1. status[i] is
+ * DS_TEXT_ROW_OK, or DS_TEXT_ROW_HOST for a chromosome id outside [0, 2^23) (ds_freq_keys flagged the row), a position outside
+ * [0, 2^40), NaN, inf, |q| > 1 or digits with more than 22 decimal places (q below about 1e-14): the caller formats that row and
+ * supplies what Python reads from it. Every finite q in [1e-14, 1] is DS_TEXT_ROW_OK. status is complete when ds_freq_push
+ * returns. The push itself is completed by ds_freq_accumulate -- with the values of every DS_TEXT_ROW_HOST row, or with nover == 0
+ * when there is none -- which inserts, sorts and adds exactly as for a parsed batch and then fills `opened`, which must stay
+ * valid until then: opened[i] = 1 when row i is the first used row of a site the run had not seen (the caller keeps that row's
+ * strand, pos_in_strand and k-mer for the table). ds_freq_result / ds_freq_end / ds_get_freq_times work unchanged.
+ *
+ * ds_freq_keys (host, no handle): chromosome ids, positions and flags of n sampleinfo strings info[info_off[i] .. info_off[i + 1])
+ * (chrom \t pos \t strand \t pos_in_strand \t readname \t read_strand). Ids count up in first-appearance order WITHIN THE CALL and the
+ * names come back as from ds_freq_locate; flags 1 (chromosome -1, no name registered) = empty, first or last byte whitespace, a byte
+ * >= 0x80, a '\r' or '\n', fewer or more than six columns, or a position that is not 1 .. 13 plain digits below 2^40. Returns n.
+ *
+ * ds_freq_values runs freq_values_kernel alone on the handle's device over n (<= 2^24) act rows and returns p0 / p1 / status;
+ * ds_freq_values_reference is the same call_value on the CPU: a CHECKER, no handle, no GPU, not a fall-back.
+ * ds_get_freq_stream_times: device milliseconds since ds_create of ms[0] freq_values_kernel and ms[1] the growths (the new table's
+ * memsets and freq_rehash_kernel), and the number of doublings (a batch that needs several is one rehash). */
+int ds_freq_begin_stream(ds_handle *h, int64_t initial_slots, int32_t batch_rows, double prob_cf);
+int ds_freq_push(ds_handle *h, int32_t nrows, const int32_t *chrom, const int64_t *pos, const float *act, int32_t class_num,
+                 const int32_t *pred, int32_t *status, int32_t *opened);
+int64_t ds_freq_keys(int64_t n, const char *info, const int64_t *info_off, int32_t *chrom, int64_t *pos, uint8_t *flags, char *names,
+                     int64_t names_cap, int64_t *names_bytes, int32_t *n_names);
+int ds_freq_values(ds_handle *h, int64_t n, const float *act, int32_t class_num, double *p0, double *p1, int32_t *status);
+int ds_freq_values_reference(int64_t n, const float *act, int32_t class_num, double *p0, double *p1, int32_t *status);
+int ds_get_freq_stream_times(ds_handle *h, int32_t reset, int64_t *growths, double *ms);
+
 /* Use a captured hipGraph for the forward (default on). */
 int ds_set_graph(ds_handle *h, int32_t enable);
 

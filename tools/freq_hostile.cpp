@@ -1,4 +1,5 @@
-// freq_hostile.cpp — the host half of call_freq --on gpu (ds_freq_locate, and dsf::reference behind ds_freq_reference) over hostile
+// freq_hostile.cpp — the host half of call_freq --on gpu (ds_freq_locate, and dsf::reference behind ds_freq_reference) and of
+// call_mods --freq_file (ds_freq_keys, and dsf::call_value through dsf::values_reference) over hostile
 // buffers, as a stand-alone program for a host sanitizer build. Every buffer is copied into a heap block of exactly its size, so a
 // read past either end is a report. Build and run (host code only; nothing here touches a GPU):
 //   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
@@ -41,6 +42,79 @@ static int run(const std::string& data, const char* what)
     return n2 == n && sites >= 0 ? 0 : 1;
 }
 
+// ds_freq_keys (call_mods --freq_file): the pieces of `data` between '\n' as sampleinfo strings, packed without separators into a heap
+// block of exactly their size; then every piece once more as the only string of a block of its own
+static int run_keys(const std::string& data, const char* what)
+{
+    std::vector<std::string> pieces;
+    size_t at = 0;
+    while (at <= data.size()) {
+        const size_t nl = data.find('\n', at);
+        pieces.push_back(data.substr(at, nl == std::string::npos ? std::string::npos : nl - at));
+        if (nl == std::string::npos) break;
+        at = nl + 1;
+    }
+    int bad = 0;
+    long long flagged = 0;
+    for (size_t round = 0; round <= pieces.size(); ++round) {      // round 0: all pieces in one call
+        std::string packed;
+        std::vector<int64_t> off = {0};
+        for (size_t i = 0; i < pieces.size(); ++i) {
+            if (round && i + 1 != round) continue;
+            packed += pieces[i];
+            off.push_back((int64_t)packed.size());
+        }
+        const int64_t n = (int64_t)off.size() - 1;
+        char* buf = static_cast<char*>(malloc(packed.size() ? packed.size() : 1));
+        memcpy(buf, packed.data(), packed.size());
+        std::vector<int32_t> chrom((size_t)n + 1);
+        std::vector<int64_t> pos((size_t)n + 1);
+        std::vector<uint8_t> flags((size_t)n + 1);
+        int64_t nb = 0;
+        int32_t nn = 0;
+        if (ds_freq_keys(n, buf, off.data(), chrom.data(), pos.data(), flags.data(), nullptr, 0, &nb, &nn) != n) bad = 1;
+        char* names = static_cast<char*>(malloc(nb ? (size_t)nb : 1));
+        if (ds_freq_keys(n, buf, off.data(), chrom.data(), pos.data(), flags.data(), names, nb, &nb, &nn) != n) bad = 1;
+        for (int64_t i = 0; i < n; ++i) {
+            if (flags[(size_t)i] ? chrom[(size_t)i] != -1 : !dsf::key_ok(chrom[(size_t)i], pos[(size_t)i]) || chrom[(size_t)i] >= nn) bad = 1;
+            if (!round) flagged += flags[(size_t)i];
+        }
+        free(names);
+        free(buf);
+    }
+    printf("%-28s keys: %4zu strings %4lld flagged%s\n", what, pieces.size(), flagged, bad ? "  BAD" : "");
+    return bad;
+}
+
+// dsf::call_value over the float32 patterns where its exponent arithmetic and table indices sit at their ends
+static int run_values()
+{
+    const uint32_t patterns[] = {0x00000000u, 0x80000000u, 0x00000001u, 0x007fffffu, 0x00800000u, 0x0d800000u, 0x0dffffffu, 0x19000000u, 0x19800000u,
+                                 0x1a000000u, 0x283424dcu, 0x28342000u, 0x33800000u, 0x3effffffu, 0x3f000000u, 0x3f7fffffu, 0x3f800000u, 0x3f800001u,
+                                 0x40000000u, 0x7f7fffffu, 0x7f800000u, 0x7fc00000u, 0xff800000u, 0xbf800000u, 0xbf000000u};
+    std::vector<float> act;
+    for (uint32_t a : patterns)
+        for (uint32_t b : patterns) {
+            float x, y;
+            memcpy(&x, &a, 4);
+            memcpy(&y, &b, 4);
+            act.push_back(x);
+            act.push_back(y);
+        }
+    const int64_t n = (int64_t)act.size() / 2;
+    std::vector<double> p0((size_t)n), p1((size_t)n);
+    std::vector<int32_t> status((size_t)n);
+    int bad = 0;
+    dsf::values_reference(n, act.data(), 2, p0.data(), p1.data(), status.data());
+    long long host = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        host += status[(size_t)i] != 0;
+        if (!status[(size_t)i] && !(p0[(size_t)i] >= -1.0 && p0[(size_t)i] <= 1.0 && p1[(size_t)i] >= -1.0 && p1[(size_t)i] <= 1.0)) bad = 1;
+    }
+    printf("%-28s %4lld act rows %4lld host rows%s\n", "value patterns", (long long)n, host, bad ? "  BAD" : "");
+    return bad;
+}
+
 int main()
 {
     const std::string good = "chr1\t10\t+\t990\tread0\tt\t0.25\t0.75\t1\tACGTACGTCGACGTACG";
@@ -63,6 +137,11 @@ int main()
     bad += run(good, "one row, no newline");
     for (size_t cut = 0; cut <= good.size() + 1; ++cut) bad += run((good + "\n" + good).substr(0, good.size() + 1 + cut), "truncated");
     for (size_t cut = 1; cut < all.size(); cut += 37) bad += run(all.substr(0, cut), "truncated hostile");
+    bad += run_keys(all, "hostile rows");
+    bad += run_keys("", "empty");
+    bad += run_keys(good, "one row");
+    for (size_t cut = 1; cut < all.size(); cut += 37) bad += run_keys(all.substr(0, cut), "truncated hostile");
+    bad += run_values();
     printf(bad ? "FAILED\n" : "all buffers done\n");
     return bad ? 1 : 0;
 }
