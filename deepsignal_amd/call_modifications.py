@@ -95,20 +95,8 @@ def _features_item(features_list):
     return (sampleinfo, kmers, base_means, base_stds, base_signal_lens, cent_signals, labels)
 
 
-def _rows_to_sink(rows_sink, sampleinfo, act, pred, kmers):
-    """One batch of the Python-list routes in the arguments of fastio.format_rows (see _FreqTap.rows). The sampleinfo strings are
-    encoded as open(result_file, "w") encodes them."""
-    import locale
-    enc = [s.encode(locale.getpreferredencoding(False)) for s in sampleinfo]
-    off = np.zeros(len(enc) + 1, np.int64)
-    off[1:] = np.cumsum([len(b) for b in enc])
-    rows_sink(np.frombuffer(b"".join(enc), np.uint8), off, np.asarray(act, np.float32), np.asarray(pred, np.int32),
-              np.asarray(kmers, np.int32).reshape(len(enc), -1))
-
-
-def _call_mods(features_batch: FeaturesBatch, engine, batch_size: int, rows_sink=None, text=True):
+def _call_mods(features_batch: FeaturesBatch, engine, batch_size: int):
     """One queue item -> output rows. Reference: call_modifications.py:149-194.
-    rows_sink (call_mods --freq_file): also handed every batch as arrays; text=False: no row text is made (pred_str stays empty).
 
     Slices the item into batch_size chunks (last one partial), runs the engine on each, normalises
     the two sigmoid outputs in float32 (p_k / (p_0 + p_1)) and formats
@@ -128,9 +116,7 @@ def _call_mods(features_batch: FeaturesBatch, engine, batch_size: int, rows_sink
                 b_kmers, base_means[batch_s:batch_e], base_stds[batch_s:batch_e],
                 base_signal_lens[batch_s:batch_e], cent_signals[batch_s:batch_e])
             accuracys.append(float(np.mean(np.asarray(b_labels) == np.asarray(prediction))))
-            if rows_sink is not None:
-                _rows_to_sink(rows_sink, b_sampleinfo, activation_logits, prediction, b_kmers)
-            for idx in range(b_labels.shape[0] if text else 0):
+            for idx in range(b_labels.shape[0]):
                 prob_0, prob_1 = activation_logits[idx][0], activation_logits[idx][1]
                 prob_0_norm = prob_0 / (prob_0 + prob_1)
                 prob_1_norm = prob_1 / (prob_0 + prob_1)
@@ -140,6 +126,34 @@ def _call_mods(features_batch: FeaturesBatch, engine, batch_size: int, rows_sink
             batch_num += 1
     accuracy = np.mean(accuracys) if accuracys else float("nan")
     return pred_str, accuracy, batch_num
+
+
+class _TappedRuns:
+    """An engine for _call_mods (call_mods --freq_file on the Python-list routes): run() also hands its batch to rows_sink in the
+    arguments of fastio.format_rows (see _FreqTap.rows), the sampleinfo strings encoded as open(result_file, "w") encodes them."""
+
+    def __init__(self, engine, rows_sink, sampleinfo):
+        self.engine, self.rows_sink, self.sampleinfo, self.at = engine, rows_sink, sampleinfo, 0
+
+    def run(self, kmers, *rest):
+        import locale
+        from .engine import pack_info
+        act, pred = self.engine.run(kmers, *rest)
+        n, self.at = len(kmers), self.at + len(kmers)
+        info, off = pack_info([s.encode(locale.getpreferredencoding(False)) for s in self.sampleinfo[self.at - n:self.at]])
+        self.rows_sink(info, off, np.asarray(act, np.float32), np.asarray(pred, np.int32), np.asarray(kmers, np.int32).reshape(n, -1))
+        return act, pred
+
+
+def _call_mods_tapped(features_batch: FeaturesBatch, engine, batch_size: int, rows_sink, text: bool):
+    """The rows of _call_mods; rows_sink, when given, sees every batch. text=False: the same batches, no row text, no rows."""
+    if rows_sink is not None:
+        engine = _TappedRuns(engine, rows_sink, features_batch[0])
+    if text:
+        return _call_mods(features_batch, engine, batch_size)[0]
+    for s in range(0, len(features_batch[0]), batch_size):
+        engine.run(*(col[s:s + batch_size] for col in features_batch[1:6]))
+    return []
 
 
 def _call_mods_q(engine, features_batch_q, pred_str_q, batch_size):
@@ -332,7 +346,8 @@ class _RowPipeline:
         import queue
         import threading
         from . import fastio
-        self.engine, self.batch_size, self.sink, self.fastio = engine, batch_size, sink, fastio
+        from .extract_features import _pieces
+        self.engine, self.batch_size, self.sink, self.fastio, self._pieces = engine, batch_size, sink, fastio, _pieces
         # call_mods --freq_file: rows_sink(info, info_off, act, pred, kmer) sees every batch where the ordered writer does, in the
         # same order, as the arrays the formatter reads; sink=None: no row text is made at all
         self.rows_sink = rows_sink
@@ -390,7 +405,7 @@ class _RowPipeline:
     def _drain(self, limit):
         while len(self.inflight) > limit:
             ticket, segs = self.inflight.popleft()
-            act, pred = self.engine.wait(ticket)
+            act, pred, segs = self._collect(ticket, segs)
             self._check_worker()
             with self._qlock:
                 for seg in segs:
@@ -408,17 +423,27 @@ class _RowPipeline:
     def _submit(self):
         segs, self.segs, self.count = self.segs, [], 0
         self._drain(self.engine.slots - 1)
+        self.inflight.append((self._submit_segs(segs), segs))
+
+    # What a route is, here for parsed items (fastio.FeatureItem): _item(fed item) -> (the item its segments (tag, item, first, end)
+    # carry, its number of sites); _submit_segs(segs) -> what the in-flight entry holds beside the segments;
+    # _collect(that, segs) -> (act, pred, the segments as _emit reads them: items with info / info_off / kmer)
+    def _item(self, item):
+        return item, len(item.labels)
+
+    def _submit_segs(self, segs):
         parts = [(it.kmer[s:e], it.means[s:e], it.stds[s:e], it.lens[s:e], it.signals[s:e]) for _, it, s, e in segs]
         if len(parts) == 1:
-            ticket = self.engine.submit(*parts[0])
-        elif hasattr(self.engine, "submit_parts"):
-            ticket = self.engine.submit_parts(parts)
-        else:
-            ticket = self.engine.submit(*(np.concatenate([p[j] for p in parts]) for j in range(5)))
-        self.inflight.append((ticket, segs))
+            return self.engine.submit(*parts[0])
+        if hasattr(self.engine, "submit_parts"):
+            return self.engine.submit_parts(parts)
+        return self.engine.submit(*(np.concatenate([p[j] for p in parts]) for j in range(5)))
+
+    def _collect(self, ticket, segs):
+        return self.engine.wait(ticket) + (segs,)
 
     def feed(self, item, tag=None):
-        n = len(item.labels)
+        item, n = self._item(item)
         self.nsites += n
         if not self.pipelined:
             for s in range(0, n, self.batch_size):
@@ -427,12 +452,9 @@ class _RowPipeline:
                                             item.signals[s:e])
                 self._emit((tag, item, s, e), act, pred)
             return
-        s = 0
-        while s < n:
-            take = min(n - s, self.batch_size - self.count)
-            self.segs.append((tag, item, s, s + take))
-            self.count += take
-            s += take
+        for s, e in self._pieces(n, self.batch_size - self.count, self.batch_size):
+            self.segs.append((tag, item, s, e))
+            self.count += e - s
             if self.count == self.batch_size:
                 self._submit()
 
@@ -446,25 +468,30 @@ class _RowPipeline:
             self._check_worker()
 
     def close(self):
-        """Stop the helper thread (after a flush; idempotent)."""
+        """Stop the helper thread (after a flush; idempotent). After a failure the tickets still in flight are waited and
+        dropped, so the engine's slots are free again."""
         if self._worker is not None:
             self._outq.put(None)
             self._worker.join()
             self._worker = None
+        while self.inflight:
+            with contextlib.suppress(Exception):
+                self._collect(*self.inflight.popleft())
 
 
-class _TicketRows(NamedTuple):
-    """What wait_text returns for one ticket, in the shape _RowPipeline._emit reads from an item."""
+class _RowsView(NamedTuple):
+    """What _RowPipeline._emit reads from a segment's item, for the routes whose items are not parsed arrays: the rows of one
+    wait_text ticket, or of one device-route read (rec: its record)."""
     info: np.ndarray
     info_off: np.ndarray
     kmer: np.ndarray
+    rec: tuple = ()
 
 
 class _TextPipeline(_RowPipeline):
     """_RowPipeline fed with located-but-unparsed items (fastio.SpanItem): a batch is handed to the engine as row spans of the
     mapped file (submit_text), the GPU parses them straight into the forward's inputs, and wait_text brings back what the
-    formatter needs (k-mer codes, the six leading columns). Batches are still filled across items to engine.max_batch and rows
-    leave in feed order."""
+    formatter needs (k-mer codes, the six leading columns)."""
 
     def __init__(self, engine, batch_size, sink, reader, rows_sink=None):
         _RowPipeline.__init__(self, engine, batch_size, sink, rows_sink)
@@ -472,46 +499,54 @@ class _TextPipeline(_RowPipeline):
             raise ValueError("parse_on='gpu' needs batch_size <= engine.max_batch")
         self.reader = reader
 
-    def feed(self, item, tag=None):
-        n = len(item.begin)
-        self.nsites += n
-        s = 0
-        while s < n:
-            take = min(n - s, self.batch_size - self.count)
-            self.segs.append((tag, item, s, s + take))
-            self.count += take
-            s += take
-            if self.count == self.batch_size:
-                self._submit()
+    def _item(self, item):
+        return item, len(item.begin)
 
-    def _submit(self):
-        segs, self.segs, self.count = self.segs, [], 0
-        self._drain(self.engine.slots - 1)
+    def _submit_segs(self, segs):
         begin = np.concatenate([it.begin[s:e] for _, it, s, e in segs])
         end = np.concatenate([it.end[s:e] for _, it, s, e in segs])
-        self.inflight.append((self.engine.submit_text(self.reader.data, begin, end), segs))
+        return self.engine.submit_text(self.reader.data, begin, end)
 
-    def _drain(self, limit):
-        while len(self.inflight) > limit:
-            ticket, segs = self.inflight.popleft()
-            try:
-                act, pred, kmer, _, info, info_off = self.engine.wait_text(ticket)
-            except ValueError as exc:
-                row = getattr(exc, "row", -1)
-                for _, it, s, e in segs:       # the message the host route gives for this row (ds_io.cpp ds_tsv_parse_into)
-                    if 0 <= row < e - s:
-                        raise ValueError("feature file: %s: malformed feature row" % it.where(s + row))
-                    row -= e - s
-                raise
-            self._check_worker()
-            rows, out, o = _TicketRows(info, info_off, kmer), [], 0
-            for tag, _, s, e in segs:
-                out.append((tag, rows, o, o + e - s))
-                o += e - s
-            with self._qlock:
-                for seg in out:
-                    self._queued[seg[0]] = self._queued.get(seg[0], 0) + 1
-            self._outq.put((out, act, pred))
+    def _collect(self, ticket, segs):
+        try:
+            act, pred, kmer, _, info, info_off = self.engine.wait_text(ticket)
+        except ValueError as exc:
+            row = getattr(exc, "row", -1)
+            for _, it, s, e in segs:       # the message the host route gives for this row (ds_io.cpp ds_tsv_parse_into)
+                if 0 <= row < e - s:
+                    raise ValueError("feature file: %s: malformed feature row" % it.where(s + row))
+                row -= e - s
+            raise
+        rows, out, o = _RowsView(info, info_off, kmer), [], 0
+        for tag, _, s, e in segs:
+            out.append((tag, rows, o, o + e - s))
+            o += e - s
+        return act, pred, out
+
+
+class _ReadsPipeline(_RowPipeline):
+    """_RowPipeline fed with the device-route records of extract_features._device_read_record (call_mods --extract_on gpu): a
+    batch travels as the reads it touches and its site list (submit_reads), the GPU extracts the features straight into the
+    forward's inputs; a read whose sites straddle two batches is carried by both. The rows are kept as chunks of bytes in
+    `chunks` (text=False: none are made) for _rows_from_device."""
+
+    def __init__(self, engine, normalize_method, rows_sink=None, text=True):
+        self.norm, self.chunks = normalize_method, []
+        _RowPipeline.__init__(self, engine, int(engine.max_batch), (lambda tag, data: self.chunks.append(data)) if text else None,
+                              rows_sink)
+
+    def _item(self, rec):
+        from .engine import pack_info
+        info, info_off = pack_info(rec[3].split(b"\n")[:-1])       # the read's sampleinfo lines and their offsets, once per read
+        return _RowsView(info, info_off, rec[4], rec), len(rec[2])
+
+    def _submit_segs(self, segs):
+        from .extract_features import _read_batch
+        batch = _read_batch([(it.rec, s, e) for _, it, s, e in segs], self.norm)
+        return self.engine.submit_reads(batch), batch       # the batch stays beside its ticket until the wait: see _read_batch
+
+    def _collect(self, held, segs):
+        return self.engine.wait(held[0]) + (segs,)
 
 
 class FreqFileError(RuntimeError):
@@ -819,8 +854,7 @@ def call_mods(input_path, model_path, result_file, kmer_len, cent_signals_len,
             nsites = 0
             with (open(result_file, "w") if result_file is not None else contextlib.nullcontext()) as wf:
                 for item in iter_features_batches(input_path, f5.f5_batch_num):
-                    pred_str, _, _ = _call_mods(item, engine, batch_size, rows_sink, text=wf is not None)
-                    for row in pred_str:
+                    for row in _call_mods_tapped(item, engine, batch_size, rows_sink, wf is not None):
                         wf.write(row + "\n")
                     if wf is not None:
                         wf.flush()
@@ -897,77 +931,22 @@ def _fast5_reads_task(task):
     return ef._device_read_records(task, lambda fp: _read_features_from_fast5s([fp], *task[1:]))
 
 
-def _rows_from_device(records, engine, batch_size, normalize_method, rows_sink=None, text=True, nrows_out=None):
-    """Rows of one file batch, in file order: the GPU-route reads go through ds_submit_reads in batches of up to
-    engine.max_batch sites (a read whose sites straddle two batches is carried by both), several batches in flight, rows
-    formatted by the native formatter; host-route reads run as the default route does. Returns the chunks of row text.
-    rows_sink / text: see _call_mods; nrows_out: a one-element list the number of rows is added to (text=False leaves no text to
-    count them in)."""
-    import collections
-    from . import fastio
-    from .engine import ReadBatch
-    cap = int(engine.max_batch)
-    out = []
-    inflight = collections.deque()
-    cur = []                               # (record, first site, end site) of the batch being filled
-    ncur = [0]
-    nrows = [0]
-
-    def drain(limit):
-        while len(inflight) > limit:
-            ticket, segs = inflight.popleft()
-            act, pred = engine.wait(ticket)
-            o = 0
-            for rec, s, e in segs:
-                info = rec[3]
-                lines = info.split(b"\n")[s:e]
-                blob = b"".join(lines)
-                off = np.zeros(e - s + 1, np.int64)
-                off[1:] = np.cumsum([len(l) for l in lines])
-                if text:
-                    out.append(fastio.format_rows(np.frombuffer(blob, np.uint8), off, act[o:o + e - s], pred[o:o + e - s],
-                                                  rec[4][s:e]).decode())
-                if rows_sink is not None:
-                    rows_sink(np.frombuffer(blob, np.uint8), off, act[o:o + e - s], pred[o:o + e - s], rec[4][s:e])
-                nrows[0] += e - s
-                o += e - s
-
-    def submit():
-        if not cur:
-            return
-        drain(engine.slots - 1)
-        reads = [rec[1] for rec, _, _ in cur]
-        sr = np.concatenate([np.full(e - s, i, np.int32) for i, (rec, s, e) in enumerate(cur)])
-        sl = np.concatenate([rec[2][s:e] for rec, s, e in cur])
-        batch = ReadBatch(reads, sr, sl, norm=normalize_method)
-        inflight.append((engine.submit_reads(batch), list(cur)))
-        keep.append(batch)
-        del cur[:]
-        ncur[0] = 0
-
-    keep = collections.deque(maxlen=2 * max(1, engine.slots))     # descriptors stay alive while their copies may run
+def _rows_from_device(records, pipe, batch_size):
+    """Rows of one file batch, in file order, as chunks of bytes: the GPU-route reads go through `pipe` (a _ReadsPipeline) in
+    batches of up to engine.max_batch sites; a host-route read waits for the rows before it and runs as the default route does
+    (_call_mods, batch_size rows at a time). Every ticket has been waited when this returns: a file batch's rows are complete."""
     for rec in records:
-        if rec[0] == "cpu":
-            submit()
-            drain(0)
-            for fb in rec[1][0]:
-                pred_str, _, _ = _call_mods(fb, engine, batch_size, rows_sink, text)
-                out.extend(r + "\n" for r in pred_str)
-                nrows[0] += len(fb[0])
+        if rec[0] == "gpu":
+            pipe.feed(rec)
             continue
-        n, s = len(rec[2]), 0
-        while s < n:
-            take = min(n - s, cap - ncur[0])
-            cur.append((rec, s, s + take))
-            ncur[0] += take
-            s += take
-            if ncur[0] == cap:
-                submit()
-    submit()
-    drain(0)
-    if nrows_out is not None:
-        nrows_out[0] += nrows[0]
-    return out
+        pipe.flush()
+        for fb in rec[1][0]:
+            rows = _call_mods_tapped(fb, pipe.engine, batch_size, pipe.rows_sink, pipe.sink is not None)
+            pipe.chunks.append("".join(r + "\n" for r in rows).encode())
+            pipe.nsites += len(fb[0])
+    pipe.flush()
+    chunks, pipe.chunks = pipe.chunks, []
+    return chunks
 
 
 def _call_mods_from_fast5s(fast5_dir, result_file, kmer_len, cent_signals_len, batch_size, f5, engine, nproc=1,
@@ -1006,21 +985,19 @@ def _call_mods_from_fast5s(fast5_dir, result_file, kmer_len, cent_signals_len, b
                                            device=device)
     wf = open(result_file, "w") if gather is None and result_file is not None else None
     want_text = wf is not None or gather is not None       # call_mods --freq_file alone: no row text
+    pipe = None
     try:
+        if extract_on == "gpu":
+            pipe = _ReadsPipeline(engine, f5.normalize_method, rows_sink, want_text)
         for batches, err in results:
             errors += err
-            if extract_on == "gpu":
+            if pipe is not None:
                 errors += sum(rec[1][1] for rec in batches if rec[0] == "cpu")
-                nrows = [0]
-                chunks = _rows_from_device(batches, engine, batch_size, f5.normalize_method, rows_sink, want_text, nrows)
-                text = "".join(chunks)
-                nsites += nrows[0]
+                text = b"".join(_rows_from_device(batches, pipe, batch_size)).decode()
+                nsites = pipe.nsites
             else:
-                rows = []
-                for fb in batches:
-                    pred_str, _, _ = _call_mods(fb, engine, batch_size, rows_sink, want_text)
-                    rows.extend(pred_str)
-                    nsites += len(fb[0])
+                rows = [r for fb in batches for r in _call_mods_tapped(fb, engine, batch_size, rows_sink, want_text)]
+                nsites += sum(len(fb[0]) for fb in batches)
                 text = "".join(r + "\n" for r in rows)
             if gather is None:
                 if wf is not None:
@@ -1035,6 +1012,8 @@ def _call_mods_from_fast5s(fast5_dir, result_file, kmer_len, cent_signals_len, b
         if pool is not None:
             pool.close()
             pool.join()
+        if pipe is not None:
+            pipe.close()
         if wf is not None:
             wf.close()
         if gather is not None:

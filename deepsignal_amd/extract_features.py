@@ -311,6 +311,16 @@ def _device_read_records(task, host_route):
     return out, 0
 
 
+def _pieces(n, room, cap):
+    """Cut n sites into (first, end) pieces in order: the first fills the `room` left in the batch being filled, every later one
+    a whole batch of `cap`. The one fill loop of the package: _device_site_batches and call_modifications._RowPipeline.feed."""
+    s = 0
+    while s < n:
+        take = min(n - s, room)
+        yield s, s + take
+        s, room = s + take, cap
+
+
 def _device_site_batches(records, cap):
     """Pack the device-route records of one file batch into batches of up to `cap` sites, in order: yields ("gpu", [(record,
     first site, end site), ...]) -- a read whose sites straddle two batches is carried by both -- and ("cpu", record) for a
@@ -323,17 +333,27 @@ def _device_site_batches(records, cap):
                 cur, ncur = [], 0
             yield "cpu", rec
             continue
-        n, s = len(rec[2]), 0
-        while s < n:
-            take = min(n - s, cap - ncur)
-            cur.append((rec, s, s + take))
-            ncur += take
-            s += take
+        for s, e in _pieces(len(rec[2]), cap - ncur, cap):
+            cur.append((rec, s, e))
+            ncur += e - s
             if ncur == cap:
                 yield "gpu", cur
                 cur, ncur = [], 0
     if cur:
         yield "gpu", cur
+
+
+def _read_batch(segs, normalize_method):
+    """The engine.ReadBatch of one batch of (record, first site, end site) segments: only the reads the batch touches travel.
+    Its host arrays must live until submit_reads / submit_rows returns, no longer: ds_submit_reads and ds_submit_rows
+    (csrc/ds_engine.cpp) go through stage_reads_block, where dsx::stage (csrc/ds_extract.hip) copies every array of the
+    descriptor into the slot's pinned block and the asynchronous copy reads THAT block (enqueue_rows does the same with info /
+    info_off); the handle stores no ds_reads pointer. Both drivers hold the batch in their in-flight entry beside its ticket
+    until the wait all the same: it costs nothing and would keep a library that staged lazily safe."""
+    from .engine import ReadBatch
+    sr = np.concatenate([np.full(e - s, i, np.int32) for i, (_, s, e) in enumerate(segs)])
+    sl = np.concatenate([rec[2][s:e] for rec, s, e in segs])
+    return ReadBatch([rec[1] for rec, _, _ in segs], sr, sl, norm=normalize_method)
 
 
 def _fast5_rows_task(task):
@@ -345,14 +365,13 @@ def _rows_from_device(records, engine, normalize_method, methy_label):
     """The feature rows of one file batch as chunks of newline-terminated bytes, in the order the host route writes them: the
     device-route reads go through ds_submit_rows in batches of up to engine.max_batch sites, several in flight."""
     import collections
-    from .engine import ReadBatch, pack_info
+    from .engine import pack_info
     out, errors = [], 0
-    inflight = collections.deque()
-    keep = collections.deque(maxlen=2 * max(1, engine.slots))     # descriptors stay alive while their copies may run
+    inflight = collections.deque()         # (ticket, its ReadBatch: see _read_batch)
 
     def drain(limit):
         while len(inflight) > limit:
-            out.append(engine.wait_rows(inflight.popleft())[0])
+            out.append(engine.wait_rows(inflight.popleft()[0])[0])
 
     for kind, item in _device_site_batches(records, int(engine.max_batch)):
         if kind == "cpu":
@@ -362,12 +381,9 @@ def _rows_from_device(records, engine, normalize_method, methy_label):
             out.append("".join(r + "\n" for r in rows).encode())
             continue
         drain(engine.slots - 1)
-        sr = np.concatenate([np.full(e - s, i, np.int32) for i, (_, s, e) in enumerate(item)])
-        sl = np.concatenate([rec[2][s:e] for rec, s, e in item])
         info, info_off = pack_info([line for rec, s, e in item for line in rec[3].split(b"\n")[s:e]])
-        batch = ReadBatch([rec[1] for rec, _, _ in item], sr, sl, norm=normalize_method)
-        inflight.append(engine.submit_rows(batch, info, info_off, methy_label))
-        keep.append(batch)
+        batch = _read_batch(item, normalize_method)
+        inflight.append((engine.submit_rows(batch, info, info_off, methy_label), batch))
     drain(0)
     return out, errors
 

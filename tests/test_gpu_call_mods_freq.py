@@ -185,3 +185,20 @@ def test_cli_fast5_directory_with_extraction_on_the_gpu(tmp_path, small_weights)
     assert open(freq, "rb").read() == want and want
     assert main(base + ["--freq_file", alone]) == 0
     assert open(alone, "rb").read() == want
+
+
+def test_fast5_reads_straddling_engine_batches(tmp_path, small_weights):
+    """--extract_on gpu with an engine of 7 sites per forward: the file batch's reads (9 .. 17 sites each) straddle batches and need
+    more tickets than the engine has slots; rows and table are those of an engine that takes the file batch in one forward."""
+    from deepsignal_amd import call_modifications as cm
+    d = os.path.join(os.path.dirname(__file__), "golden", "fast5", "plain")
+    dsw = str(tmp_path / "model.dsw")
+    W.save_weights(dsw, small_weights)
+    f5_args = (True, "RawGenomeCorrected_000", "BaseCalled_template", None, True, "mad", "CG", 0, 1, 5, None)
+    out = {}
+    for cap in (7, 4096):
+        calls, freq = str(tmp_path / ("calls%d.tsv" % cap)), str(tmp_path / ("freq%d.tsv" % cap))
+        n = cm.call_mods(d, dsw, calls, 17, 360, 16, 0.001, 2, 1, True, True, True, True, f5_args, engine_batch=cap, extract_on="gpu",
+                         freq_file=freq)
+        out[cap] = (n, open(calls, "rb").read(), open(freq, "rb").read())
+    assert out[7] == out[4096] and out[7][0] == out[7][1].count(b"\n") == 68 and out[7][2]

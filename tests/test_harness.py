@@ -199,12 +199,13 @@ def test_cli_builds_the_references_f5_args(monkeypatch):
 
 
 class _AsyncStandIn:
-    """CPU stand-in with the engine's asynchronous boundary (submit / submit_parts / wait, `slots` in flight): outputs
-    are a deterministic function of each site's own inputs, computed at wait() time."""
+    """CPU stand-in with the engine's asynchronous boundary (submit / submit_parts / submit_text / submit_reads and their waits,
+    `slots` in flight): outputs are a deterministic function of each site's own inputs, computed at wait() time."""
     class_num, max_batch, slots = 2, 64, 3
 
-    def __init__(self):
+    def __init__(self, fail_wait=0, max_batch=64):
         self.pending, self.next, self.parts_calls, self.batches = {}, 0, 0, []
+        self.waits, self.fail_wait, self.max_batch = 0, fail_wait, max_batch       # fail_wait = k: the k-th wait raises
 
     @staticmethod
     def _f(means, signals):
@@ -228,8 +229,38 @@ class _AsyncStandIn:
 
     def wait(self, ticket):
         assert ticket[0] == min(self.pending), "tickets must be waited in submission order"
-        means, signals = self.pending.pop(ticket[0])
+        means, signals = self.pending.pop(ticket[0])[:2]
+        self.waits += 1
+        if self.waits == self.fail_wait:
+            raise RuntimeError("wait %d failed" % self.waits)
         return self._f(means, signals)
+
+    # the other submit / wait pairs of Engine, on the library's CPU checkers
+    def _hold(self, n, *held):
+        assert len(self.pending) < self.slots, "more batches in flight than slots"
+        t = self.next; self.next += 1
+        self.pending[t] = held
+        self.batches.append(n)
+        return t
+
+    def submit_reads(self, batch):
+        from deepsignal_amd.engine import extract_reference
+        f = extract_reference(batch)
+        return (self._hold(batch.nsites, f["means"], f["signals"]), batch.nsites)
+
+    def submit_text(self, text, begin, end):
+        from deepsignal_amd.engine import parse_text_reference
+        p = parse_text_reference(text, begin, end)
+        info = [bytes(text[b:b + n]) for b, n in zip(begin, p["info_len"])]
+        return (self._hold(len(begin), p["means"], p["signals"], p["kmer"], p["labels"], info, p["status"]), len(begin))
+
+    def wait_text(self, ticket):
+        from deepsignal_amd.engine import TextRowError, pack_info
+        kmer, labels, info, status = self.pending[ticket[0]][2:]
+        act, pred = self.wait(ticket)
+        if status.any():              # a row outside the device's grammar: the stand-in has no host parser, so it is malformed
+            raise TextRowError(int(np.flatnonzero(status)[0]), "row %d of the ticket" % np.flatnonzero(status)[0])
+        return (act, pred, kmer, labels) + pack_info(info)
 
 
 def _items_for_pipeline(n, cuts):

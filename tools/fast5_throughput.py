@@ -7,7 +7,7 @@ HDF5 reading is bypassed: each worker synthesises the reads (deepsignal_amd.synt
 samples per base, random ACGT, CG sites) before the clock starts, then runs the route's own per-read code on them --
 extract_features.extract_read_features + call_modifications._features_item for the host route,
 extract_features._device_read_record (motif scan, site list, packing) for the device route -- and the main process drives the
-engine exactly as _call_mods_from_fast5s does (_call_mods / _rows_from_device). As there, --nproc > 2 runs nproc - 1 worker
+engine exactly as _call_mods_from_fast5s does (_call_mods; one _ReadsPipeline fed through _rows_from_device per task). As there, --nproc > 2 runs nproc - 1 worker
 processes next to the engine process; otherwise the workers' part runs inline.
 
 Printed (one JSON line): sites/s of both routes; the device route's worker-side rate (sites per worker-second times workers:
@@ -104,6 +104,7 @@ def _run_route(route, eng, tasks, nproc, args):
         pool.map(_ready, range(4 * workers))          # every worker has synthesised its reads before the clock starts
     else:
         _init(args.reads, args.seed, args.norm)
+    pipe = cm._ReadsPipeline(eng, args.norm) if route == "gpu" else None
     try:
         nsites, worker_s = 0, 0.0
         t0 = time.perf_counter()
@@ -114,9 +115,11 @@ def _run_route(route, eng, tasks, nproc, args):
                 rows, _, _ = cm._call_mods(payload, eng, args.batch_size)
                 nsites += len(rows)
             else:
-                nsites += sum(c.count("\n") for c in cm._rows_from_device(payload, eng, args.batch_size, args.norm))
+                nsites += sum(c.count(b"\n") for c in cm._rows_from_device(payload, pipe, args.batch_size))
         wall = time.perf_counter() - t0
     finally:
+        if pipe is not None:
+            pipe.close()
         if pool is not None:
             pool.close()
             pool.join()
