@@ -423,7 +423,13 @@ def main(argv=None) -> int:
                     help="gpu: the rows are parsed and aggregated on the GPU (the host only finds them); the table is "
                          "byte-identical to the cpu route's")
     ap.add_argument("--device", type=int, default=None, help="GPU ordinal of --on gpu (default 0)")
+    ap.add_argument("--combine_ref", type=str, default=None,
+                    help="a genome reference (FASTA): after the result file is written, combine its two strands per CpG "
+                         "(`combine_strands` on that file, honouring --on / --device) into <name>.fb_combined<ext>")
+    ap.add_argument("--combine_contig", type=str, default=None, help="--combine_ref: only this contig (combine_strands --contig)")
     a = ap.parse_args(argv)
+    if a.combine_contig is not None and a.combine_ref is None:
+        ap.error("--combine_contig needs --combine_ref")
     if a.device is not None and a.on != "gpu":
         ap.error("--device needs --on gpu")
     if a.device is not None and a.device < 0:
@@ -442,6 +448,9 @@ def main(argv=None) -> int:
     else:
         stats = calculate_mods_frequency(files, a.prob_cf)
     write_sitekey2stats(stats, a.result_file, a.sort, a.bed)
+    if a.combine_ref is not None:
+        from .combine_strands import combine_strands
+        combine_strands(a.result_file, a.combine_ref, a.combine_contig or "", None, a.on, a.device or 0)
     return 0
 
 

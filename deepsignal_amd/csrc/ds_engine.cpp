@@ -7,6 +7,7 @@
 #include "ds_extract.h"
 #include "ds_tsv_device.h"
 #include "ds_freq.h"
+#include "ds_combine.h"
 
 #include <algorithm>
 #include <cmath>
@@ -265,6 +266,9 @@ struct ds_handle {
     Times<4> fq_t;        // batches of the frequency runs ended so far (the open run's are added on top)
     double fqs_ms[2] = {0, 0};        // streaming runs ended so far: freq_values_kernel, the table growths
     int64_t fqs_growths = 0;
+    dsc::Combine* combine = nullptr;      // combine_strands --on gpu: the open run (ds_combine_begin .. ds_combine_end); bitmap, table and buffers are its own
+    Times<5> cb_t;        // genome chunks and batches of the combine runs ended so far (the open run's are added on top)
+    int64_t cb_chunks = 0;
     // pipelining: consecutive forwards rotate over independent slots (own workspace, streams, graphs), so the
     // dependency chain of one 512-site forward overlaps the next ones'; weights are shared
     std::vector<Slot> slots;
@@ -1606,6 +1610,7 @@ void ds_destroy(ds_handle* h)
         if (sl.s1 && sl.owns_s1) hipStreamDestroy(sl.s1);
     }
     delete h->freq;
+    delete h->combine;
     for (void* p : h->allocs) hipFree(p);
     (void)hipGetLastError();      // nothing a teardown call returned may surface in a later handle's first launch
     delete h;
@@ -2573,6 +2578,122 @@ int ds_get_freq_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms)
     return DS_OK;
 }
 
+// ---- both strands of a CpG table combined on the device (ds_combine.hip; combine_strands --on gpu) ---------------------------------
+// The run's state is a dsc::Combine of its own (bitmap, table, row buffers, stream): no pipeline slot, no weights.
+static void combine_close(ds_handle* h)
+{
+    if (!h->combine) return;
+    h->cb_t.batches += h->combine->batches;
+    h->cb_chunks += h->combine->chunks;
+    for (int i = 0; i < 5; ++i) h->cb_t.ms[i] += h->combine->ms[i];
+    delete h->combine;
+    h->combine = nullptr;
+}
+
+static int ds_combine_begin_impl(ds_handle* h, int32_t form, int32_t nrec, const int64_t* rec_len, int64_t total_rows, int32_t batch_rows)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (h->combine) return fail(h, DS_ERR_INVALID, "ds_combine_begin: a run is open on this handle (ds_combine_end first)");
+    h->combine = new dsc::Combine();
+    std::string err;
+    const int rc = h->combine->begin(h->cfg.device, form, nrec, rec_len, total_rows, batch_rows, &err);
+    if (rc) { delete h->combine; h->combine = nullptr; return fail(h, rc, err); }
+    return DS_OK;
+}
+
+static int ds_combine_genome_impl(ds_handle* h, const char* text, int64_t nseg, const int64_t* seg_begin, const int64_t* seg_end, const int64_t* seg_bit,
+                                  const uint8_t* seg_carry)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (!h->combine) return fail(h, DS_ERR_INVALID, "ds_combine_genome: no run is open (ds_combine_begin first)");
+    std::string err;
+    const int rc = h->combine->genome(text, nseg, seg_begin, seg_end, seg_bit, seg_carry, &err);
+    return rc ? fail(h, rc, err) : DS_OK;
+}
+
+static int ds_combine_bitmap_impl(ds_handle* h, int64_t cap_words, uint32_t* bitmap)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (!h->combine) return fail(h, DS_ERR_INVALID, "ds_combine_bitmap: no run is open (ds_combine_begin first)");
+    std::string err;
+    const int rc = h->combine->get_bitmap(cap_words, bitmap, &err);
+    return rc ? fail(h, rc, err) : DS_OK;
+}
+
+static int ds_combine_parse_impl(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, const int32_t* chrom,
+                                 const uint8_t* flags, int32_t* status)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (!h->combine) return fail(h, DS_ERR_INVALID, "ds_combine_parse: no run is open (ds_combine_begin first)");
+    std::string err;
+    const int rc = h->combine->parse(text, nrows, begin, end, chrom, flags, status, &err);
+    return rc ? fail(h, rc, err) : DS_OK;
+}
+
+static int ds_combine_accumulate_impl(ds_handle* h, int32_t nover, const int32_t* row, const int32_t* status, const int32_t* chrom, const int64_t* pos,
+                                      const int32_t* plus, const double* a, const double* b, const int64_t* met, const int64_t* unmet, const int64_t* cov)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (!h->combine) return fail(h, DS_ERR_INVALID, "ds_combine_accumulate: no run is open (ds_combine_begin first)");
+    std::string err;
+    const int rc = h->combine->accumulate(nover, row, status, chrom, pos, plus, a, b, met, unmet, cov, &err);
+    return rc ? fail(h, rc, err) : DS_OK;
+}
+
+static int64_t ds_combine_result_impl(ds_handle* h, int64_t cap, int32_t* chrom, int64_t* pos, double* sum0, double* sum1, int64_t* met, int64_t* unmet,
+                                      int64_t* cov, int64_t* last_plus, int64_t* rows)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (!h->combine) return fail(h, DS_ERR_INVALID, "ds_combine_result: no run is open (ds_combine_begin first)");
+    std::string err;
+    const int64_t rc = h->combine->result(cap, chrom, pos, sum0, sum1, met, unmet, cov, last_plus, rows, &err);
+    return rc < 0 ? fail(h, (int)rc, err) : rc;
+}
+
+int ds_combine_end(ds_handle* h)
+{
+    if (!h) return DS_ERR_INVALID;
+    combine_close(h);
+    return DS_OK;
+}
+
+int ds_motif_reference(const char* text, int64_t nseg, const int64_t* seg_begin, const int64_t* seg_end, const int64_t* seg_bit, const uint8_t* seg_carry,
+                       int64_t nbits, uint32_t* bitmap)
+{
+    return guarded(nullptr, [&]() -> int {
+        std::string err;
+        return dsc::motif_reference(text, nseg, seg_begin, seg_end, seg_bit, seg_carry, nbits, bitmap, &err) ? DS_OK
+                                                                                                             : fail(nullptr, DS_ERR_INVALID, "ds_motif_reference: " + err);
+    });
+}
+
+int64_t ds_combine_reference(int32_t form, const char* text, int64_t nrows, const int64_t* begin, const int64_t* end, int32_t* chrom, const uint8_t* flags,
+                             int32_t nrec, const int64_t* rec_len, const uint32_t* bitmap, int32_t* status, int64_t* pos, int32_t* plus, double* a,
+                             double* b, int64_t* met, int64_t* unmet, int64_t* cov, int64_t cap, int32_t* site_chrom, int64_t* site_pos, double* sum0,
+                             double* sum1, int64_t* site_met, int64_t* site_unmet, int64_t* site_cov, int64_t* last_plus)
+{
+    return guarded(nullptr, [&]() -> int64_t {
+        std::string err;
+        const int64_t rc = dsc::reference(form, text, nrows, begin, end, chrom, flags, nrec, rec_len, bitmap, status, pos, plus, a, b, met, unmet, cov, cap,
+                                          site_chrom, site_pos, sum0, sum1, site_met, site_unmet, site_cov, last_plus, &err);
+        return rc < 0 ? fail(nullptr, DS_ERR_INVALID, err) : rc;
+    });
+}
+
+int ds_get_combine_times(ds_handle* h, int32_t reset, int64_t* chunks, int64_t* batches, double* ms)
+{
+    if (!h || !chunks || !batches || !ms) return DS_ERR_INVALID;
+    *chunks = h->cb_chunks + (h->combine ? h->combine->chunks : 0);
+    *batches = h->cb_t.batches + (h->combine ? h->combine->batches : 0);
+    for (int i = 0; i < 5; ++i) ms[i] = h->cb_t.ms[i] + (h->combine ? h->combine->ms[i] : 0.0);
+    if (reset) {
+        h->cb_t = Times<5>();
+        h->cb_chunks = 0;
+        if (h->combine) { h->combine->batches = h->combine->chunks = 0; for (double& v : h->combine->ms) v = 0; }
+    }
+    return DS_OK;
+}
+
 // ---- feature rows: float64 values and their text on the device (ds_extract.hip rows_*_kernel) ---------------------------------
 // Needs no weights: the slot's streams and the blocks below are all it uses. The rows path enqueues, on sl.s0: H2D of the packed
 // reads and of info / info_off, the statistics, values, length, scan and format kernels, D2H of the row offsets.
@@ -3051,6 +3172,12 @@ int ds_freq_begin(ds_handle* h, int64_t total_rows, int32_t batch_rows, double p
 int ds_freq_parse(ds_handle* h, const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, const int32_t* chrom, const uint8_t* flags, int32_t* status) { return guarded(h, [&] { return ds_freq_parse_impl(h, text, nrows, row_begin, row_end, chrom, flags, status); }); }
 int ds_freq_accumulate(ds_handle* h, int32_t nover, const int32_t* row, const int32_t* chrom, const int64_t* pos, const double* p0, const double* p1, const int32_t* met) { return guarded(h, [&] { return ds_freq_accumulate_impl(h, nover, row, chrom, pos, p0, p1, met); }); }
 int64_t ds_freq_result(ds_handle* h, int64_t cap, int64_t* first_row, int32_t* chrom, int64_t* pos, double* sum0, double* sum1, int32_t* met, int32_t* unmet, int64_t* rows, int64_t* used) { return guarded(h, [&] { return ds_freq_result_impl(h, cap, first_row, chrom, pos, sum0, sum1, met, unmet, rows, used); }); }
+int ds_combine_begin(ds_handle* h, int32_t form, int32_t nrec, const int64_t* rec_len, int64_t total_rows, int32_t batch_rows) { return guarded(h, [&] { return ds_combine_begin_impl(h, form, nrec, rec_len, total_rows, batch_rows); }); }
+int ds_combine_genome(ds_handle* h, const char* text, int64_t nseg, const int64_t* seg_begin, const int64_t* seg_end, const int64_t* seg_bit, const uint8_t* seg_carry) { return guarded(h, [&] { return ds_combine_genome_impl(h, text, nseg, seg_begin, seg_end, seg_bit, seg_carry); }); }
+int ds_combine_bitmap(ds_handle* h, int64_t cap_words, uint32_t* bitmap) { return guarded(h, [&] { return ds_combine_bitmap_impl(h, cap_words, bitmap); }); }
+int ds_combine_parse(ds_handle* h, const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, const int32_t* chrom, const uint8_t* flags, int32_t* status) { return guarded(h, [&] { return ds_combine_parse_impl(h, text, nrows, row_begin, row_end, chrom, flags, status); }); }
+int ds_combine_accumulate(ds_handle* h, int32_t nover, const int32_t* row, const int32_t* status, const int32_t* chrom, const int64_t* pos, const int32_t* plus, const double* a, const double* b, const int64_t* met, const int64_t* unmet, const int64_t* cov) { return guarded(h, [&] { return ds_combine_accumulate_impl(h, nover, row, status, chrom, pos, plus, a, b, met, unmet, cov); }); }
+int64_t ds_combine_result(ds_handle* h, int64_t cap, int32_t* chrom, int64_t* pos, double* sum0, double* sum1, int64_t* met, int64_t* unmet, int64_t* cov, int64_t* last_plus, int64_t* rows) { return guarded(h, [&] { return ds_combine_result_impl(h, cap, chrom, pos, sum0, sum1, met, unmet, cov, last_plus, rows); }); }
 int ds_submit_text(ds_handle* h, const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, int32_t* ticket) { return guarded(h, [&] { return ds_submit_text_impl(h, text, nrows, row_begin, row_end, ticket); }); }
 int ds_wait_text(ds_handle* h, int32_t ticket, float* act, int32_t* pred, int32_t* kmer, int32_t* labels, char* info, int64_t info_cap, int64_t* info_off) { return guarded(h, [&] { return ds_wait_text_impl(h, ticket, act, pred, kmer, labels, info, info_cap, info_off); }); }
 int ds_parse_text(ds_handle* h, const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, int32_t* kmer, float* means, float* stds, float* lens, float* signals, int32_t* labels, int32_t* info_len, int32_t* status) { return guarded(h, [&] { return ds_parse_text_impl(h, text, nrows, row_begin, row_end, kmer, means, stds, lens, signals, labels, info_len, status); }); }

@@ -147,6 +147,9 @@ void values_reference(int64_t n, const float* act, int32_t class_num, double* p0
 // freq_values_kernel alone on `device` over n act rows: what the tests hold against values_reference (ds_freq_values)
 int values_device(int device, int64_t n, const float* act, int32_t class_num, double* p0, double* p1, int32_t* status, std::string* err);
 
+// freq_bitonic_kernel's network over Pn = 2^q keys on stream s, ascending (shared with ds_combine.hip): the first launch error, or hipSuccess
+hipError_t bitonic_sort(uint64_t* keys, int Pn, hipStream_t s);
+
 // ---- one run on the device ------------------------------------------------------------------------------------------------
 // begin() sizes the table for total_rows (load <= 0.5) and the row buffers for batch_rows; parse() copies a batch's text and
 // parses it; accumulate() applies the caller's values for ROW_HOST rows, inserts the used rows' keys, sorts (site, row) and

@@ -214,6 +214,17 @@ double span(hipEvent_t a, hipEvent_t b)
 
 }  // namespace
 
+hipError_t bitonic_sort(uint64_t* keys, int Pn, hipStream_t s)
+{
+    for (int k = 2; k <= Pn; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            hipLaunchKernelGGL(freq_bitonic_kernel, dim3(blocks(Pn)), dim3(TPB), 0, s, reinterpret_cast<unsigned long long*>(keys), Pn, j, k);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+    return hipSuccess;
+}
+
 int Freq::begin(int dev, int64_t total, int32_t batch, double prob_cf, std::string* err)
 {
     if (s) return seterr(err, DS_ERR_INVALID, "ds_freq_begin: a run is open on this handle (ds_freq_end first)");
@@ -471,11 +482,7 @@ int Freq::accumulate(int32_t m, const int32_t* row, const int32_t* chrom, const 
         FQ(hipMemcpyAsync(opened_out, d_opened, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     }
     FQ(hipEventRecord(ev[2], s));
-    for (int k = 2; k <= Pn; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            hipLaunchKernelGGL(freq_bitonic_kernel, dim3(blocks(Pn)), dim3(TPB), 0, s, reinterpret_cast<unsigned long long*>(d_sort), Pn, j, k);
-            FQ(hipGetLastError());
-        }
+    FQ(bitonic_sort(d_sort, Pn, s));
     FQ(hipEventRecord(ev[3], s));
     hipLaunchKernelGGL(freq_accumulate_kernel, dim3(blocks(Pn)), dim3(TPB), 0, s, Pn, reinterpret_cast<const unsigned long long*>(d_sort), d_p0, d_p1,
                        d_met, t_sum0, t_sum1, t_met, t_unmet);

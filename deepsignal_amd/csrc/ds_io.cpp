@@ -845,4 +845,65 @@ int64_t ds_freq_keys(int64_t n, const char* info, const int64_t* info_off, int32
     return n;
 }
 
+// The host half of combine_strands --on gpu (ds_combine.hip): one pass over a FASTA buffer as Python's text layer reads it. A line
+// is what lies between two '\n' (a last line needs none; the '\r' of a "\r\n" goes with what strip() removes). A line whose first raw
+// byte is '>' opens a record: its name is line.strip()[1:].split(' ')[0]. Record 0 is what lies in front of the first header and has
+// no name. Every other line, stripped by str.strip()'s ASCII set and not empty, is a piece of its record's sequence: its byte span
+// and its offset inside the record's sequence. Flags: 1 = a byte >= 0x80 (the file may decode to other characters), 2 = a '\r'
+// that is not followed by '\n' (universal newlines end a line there). Returns the sequence lines found; arrays are filled up to
+// their capacities and *n_recs is the number of records (>= 1): call again with room when short.
+int64_t ds_fasta_locate(const char* text, int64_t nbytes, int64_t cap_lines, int64_t* line_begin, int64_t* line_end, int32_t* line_rec,
+                        int64_t* line_off, int64_t cap_recs, int64_t* name_begin, int64_t* name_end, int64_t* rec_len, int64_t* n_recs,
+                        int32_t* flags)
+{
+    if (nbytes < 0 || (nbytes > 0 && !text) || cap_lines < 0 || cap_recs < 0 || !n_recs || !flags ||
+        (cap_lines > 0 && (!line_begin || !line_end || !line_rec || !line_off)) || (cap_recs > 0 && (!name_begin || !name_end || !rec_len)))
+        return DS_ERR_INVALID;
+    auto is_space = [](unsigned char c) { return c == ' ' || (c >= 9 && c <= 13) || (c >= 0x1c && c <= 0x1f); };
+    int64_t nlines = 0, nrec = 1, cur_len = 0;
+    int32_t fl = 0;
+    if (cap_recs > 0) { name_begin[0] = name_end[0] = 0; rec_len[0] = 0; }
+    const char* p = text;
+    const char* const end = text + nbytes;
+    while (p < end) {
+        const char* nl = static_cast<const char*>(memchr(p, '\n', (size_t)(end - p)));
+        const char* e = nl ? nl : end;
+        const char* cr = static_cast<const char*>(memchr(p, '\r', (size_t)(e - p)));
+        if (cr && !(nl && cr == e - 1)) fl |= 2;
+        unsigned char hi = 0;
+        for (const char* q = p; q < e; ++q) hi |= (unsigned char)*q;
+        if (hi & 0x80) fl |= 1;
+        const char* b = p;
+        const char* en = e;
+        while (b < en && is_space((unsigned char)*b)) ++b;
+        while (en > b && is_space((unsigned char)en[-1])) --en;
+        if (e > p && *p == '>') {
+            if (nrec >= 0x7fffffff) return DS_ERR_UNSUPPORTED;
+            if (nrec - 1 < cap_recs) rec_len[nrec - 1] = cur_len;
+            const char* sp = static_cast<const char*>(memchr(b + 1, ' ', (size_t)(en - (b + 1))));
+            if (nrec < cap_recs) {
+                name_begin[nrec] = (int64_t)(b + 1 - text);
+                name_end[nrec] = (int64_t)((sp ? sp : en) - text);
+                rec_len[nrec] = 0;
+            }
+            ++nrec;
+            cur_len = 0;
+        } else if (en > b) {
+            if (nlines < cap_lines) {
+                line_begin[nlines] = (int64_t)(b - text);
+                line_end[nlines] = (int64_t)(en - text);
+                line_rec[nlines] = (int32_t)(nrec - 1);
+                line_off[nlines] = cur_len;
+            }
+            ++nlines;
+            cur_len += (int64_t)(en - b);
+        }
+        p = nl ? nl + 1 : end;
+    }
+    if (nrec - 1 < cap_recs) rec_len[nrec - 1] = cur_len;
+    *n_recs = nrec;
+    *flags = fl;
+    return nlines;
+}
+
 }  // extern "C"

@@ -1,7 +1,8 @@
 """`deepsignal call_mods` command line — the reference's flag surface for this sub-command
 (reference deepsignal/deepsignal.py:236-326, defaults included), driving the MI355X engine — plus `extract`, the
 host-side step that produces call_mods' feature-TSV input (deepsignal.py:155-234), and `call_freq`, the per-site frequency table
-from call_mods' result files (scripts/call_modification_frequency.py).
+from call_mods' result files (scripts/call_modification_frequency.py), and `combine_strands`, both strands of each CpG of that
+table combined (scripts/combine_two_strands_frequency.py).
 
 Multi-GPU: one process per GPU, e.g.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
@@ -51,7 +52,15 @@ def main_call_freq(args):
     argv += ["--sort"] if args.sort else []
     argv += ["--file_uid", args.file_uid] if args.file_uid is not None else []
     argv += ["--device", str(args.device)] if args.device is not None else []
+    argv += ["--combine_ref", args.combine_ref] if args.combine_ref is not None else []
+    argv += ["--combine_contig", args.combine_contig] if args.combine_contig is not None else []
     return freq_main(argv)
+
+
+def main_combine_strands(args):
+    from .combine_strands import combine_strands
+    combine_strands(args.frequency_fp, args.ref_fp, args.contig, args.result_file, args.on, args.device or 0)
+    return 0
 
 
 def _names_freq_file(argv) -> bool:
@@ -178,7 +187,18 @@ def build_parser(freq_file_given=True):
     f.add_argument("--on", default="cpu", choices=["cpu", "gpu"],
                    help="gpu: rows parsed and aggregated on the GPU (the host only finds them); same output bytes")
     f.add_argument("--device", type=int, default=None, help="GPU ordinal of --on gpu (default 0)")
+    f.add_argument("--combine_ref", type=str, default=None,
+                   help="a genome reference (FASTA): also write the table with both strands of each CpG combined "
+                        "(`combine_strands` on the result file; honours --on / --device)")
+    f.add_argument("--combine_contig", type=str, default=None, help="--combine_ref: only this contig")
     f.set_defaults(func=main_call_freq)
+    # `combine_strands`: the last step -- the '-' strand row of each CpG folded onto the '+' strand cytosine, CGs of the genome
+    # only (the reference's scripts/combine_two_strands_frequency.py; same flags, plus -o / --on / --device)
+    from .combine_strands import add_arguments as combine_arguments
+    c = sub.add_parser("combine_strands", description="combine the modification frequency of CG in the forward and backward strand")
+    combine_arguments(c)
+    c.set_defaults(func=main_combine_strands)
+    parser.combine_parser = c
     return parser
 
 
@@ -215,6 +235,10 @@ def main(argv=None):
                 print(str(exc), file=sys.stderr)
                 return 1
             return 0
+    if args.module == "combine_strands":
+        from .combine_strands import check_arguments
+        check_arguments(parser.combine_parser, args)
+        return args.func(args)
     if args.module == "call_freq":
         return args.func(args)       # the script's own main: it validates the forwarded flags and returns the exit status
     args.func(args)

@@ -49,6 +49,9 @@ EXPORTED_SYMBOLS = (
     "ds_freq_reference", "ds_get_freq_times",
     # ... and straight from the forward's results (call_mods --freq_file)
     "ds_freq_begin_stream", "ds_freq_push", "ds_freq_keys", "ds_freq_values", "ds_freq_values_reference", "ds_get_freq_stream_times",
+    # both strands of a CpG table combined on the device (combine_strands --on gpu)
+    "ds_fasta_locate", "ds_combine_begin", "ds_combine_genome", "ds_combine_bitmap", "ds_combine_parse", "ds_combine_accumulate",
+    "ds_combine_result", "ds_combine_end", "ds_motif_reference", "ds_combine_reference", "ds_get_combine_times",
 )
 
 
@@ -345,6 +348,113 @@ def freq_values_reference(act) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     return p0, p1, status
 
 
+COMBINE_TABLE, COMBINE_BED = 0, 1      # DS_COMBINE_TABLE / DS_COMBINE_BED: the form of the rows
+COMBINE_ROW_SKIP, COMBINE_ROW_GIVEN, COMBINE_ROW_GIVEN_SKIP = 2, 3, 4      # DS_COMBINE_ROW_*
+COMBINE_COUNT_LIMIT = 1 << 32          # a count the caller gives for a row stays below this in magnitude
+COMBINE_MAX_CHUNK = 1 << 30            # bytes one genome chunk may span
+FASTA_NON_ASCII, FASTA_BARE_CR = 1, 2  # ds_fasta_locate's flags
+
+
+def fasta_locate(text) -> Dict[str, np.ndarray]:
+    """ds_fasta_locate: the sequence lines and records of a FASTA buffer (bytes, or a uint8 array such as a memory map) ->
+    line_begin / line_end (stripped byte spans), line_rec, line_off (offset inside the record's sequence), name_begin / name_end,
+    rec_len (record 0 = what lies in front of the first header), and `flags` (FASTA_NON_ASCII | FASTA_BARE_CR)."""
+    lib = load_library()
+    if isinstance(text, (bytes, bytearray)):
+        text = np.frombuffer(text, np.uint8)
+    text = np.ascontiguousarray(text, np.uint8)
+    if text.ndim != 1:
+        raise ValueError("text must be a flat byte buffer")
+    nrec, flags = ctypes.c_int64(), ctypes.c_int32()
+    cap, cap_recs = text.size // 48 + 16, 1 << 10
+    while True:
+        lines = {"line_begin": np.empty(cap, np.int64), "line_end": np.empty(cap, np.int64), "line_rec": np.empty(cap, np.int32),
+                 "line_off": np.empty(cap, np.int64)}
+        recs = {"name_begin": np.empty(cap_recs, np.int64), "name_end": np.empty(cap_recs, np.int64), "rec_len": np.empty(cap_recs, np.int64)}
+        n = int(lib.ds_fasta_locate(text.ctypes.data if text.size else None, text.size, cap, *(v.ctypes.data for v in lines.values()),
+                                    cap_recs, *(v.ctypes.data for v in recs.values()), ctypes.byref(nrec), ctypes.byref(flags)))
+        if n < 0:
+            raise RuntimeError("ds_fasta_locate failed (%d)" % n)
+        if n <= cap and nrec.value <= cap_recs:
+            out = {k: v[:n] for k, v in lines.items()}
+            out.update({k: v[:nrec.value] for k, v in recs.items()})
+            out["flags"] = int(flags.value)
+            return out
+        cap, cap_recs = max(cap, n), max(cap_recs, int(nrec.value))
+
+
+def _segment_args(text, seg_begin, seg_end, seg_bit, seg_carry):
+    keep, addr, seg_begin, seg_end = _text_args(text, seg_begin, seg_end)
+    seg_bit = np.ascontiguousarray(seg_bit, np.int64)
+    seg_carry = np.ascontiguousarray(seg_carry, np.uint8)
+    if seg_bit.shape != seg_begin.shape or seg_carry.shape != seg_begin.shape:
+        raise ValueError("seg_bit / seg_carry must have one entry per segment")
+    return keep, addr, seg_begin, seg_end, seg_bit, seg_carry
+
+
+def motif_reference(text, seg_begin, seg_end, seg_bit, seg_carry, nbits: int, bitmap: Optional[np.ndarray] = None) -> np.ndarray:
+    """ds_motif_reference: the genome scan of motif_bitmap_kernel on the CPU, from the same routine -> the bitmap, uint32[(nbits + 31)
+    // 32] (ORed into `bitmap` when given). A checker for the tests (no GPU needed), not a fall-back."""
+    lib = load_library()
+    keep, addr, seg_begin, seg_end, seg_bit, seg_carry = _segment_args(text, seg_begin, seg_end, seg_bit, seg_carry)
+    if bitmap is None:
+        bitmap = np.zeros((int(nbits) + 31) // 32, np.uint32)
+    if bitmap.dtype != np.uint32 or bitmap.size < (int(nbits) + 31) // 32 or not bitmap.flags.c_contiguous:
+        raise ValueError("bitmap must be a contiguous uint32 array of (nbits + 31) // 32 words")
+    rc = lib.ds_motif_reference(addr, seg_begin.size, seg_begin.ctypes.data, seg_end.ctypes.data, seg_bit.ctypes.data, seg_carry.ctypes.data,
+                                int(nbits), bitmap.ctypes.data if bitmap.size else None)
+    if rc != 0:
+        raise RuntimeError("ds_motif_reference failed (%d): %s" % (rc, lib.ds_last_error(None).decode()))
+    return bitmap
+
+
+_COMBINE_ROW_FIELDS = (("pos", np.int64), ("plus", np.int32), ("a", np.float64), ("b", np.float64), ("met", np.int64), ("unmet", np.int64),
+                       ("cov", np.int64))
+_COMBINE_SITE_FIELDS = (("chrom", np.int32), ("pos", np.int64), ("sum0", np.float64), ("sum1", np.float64), ("met", np.int64),
+                        ("unmet", np.int64), ("cov", np.int64), ("last_plus", np.int64))
+
+
+def combine_reference(form: int, text, begin, end, chrom, flags, rec_len, bitmap, given=None, sites: bool = True) -> Dict[str, np.ndarray]:
+    """ds_combine_reference: the device route's row grammar and aggregation on the CPU from the same routines, one pass in row order.
+    A checker for the tests (no GPU needed), not a fall-back. `given`: {row index: None (the caller found the key to be no CG) or
+    (record, pos, plus, a, b, met, unmet, cov)} for the rows whose values the caller supplies. Returns the per-row status and values
+    (row_*) and, with `sites`, the sites in the order of their first row (chrom, pos, sum0, sum1, met, unmet, cov, last_plus)."""
+    lib = load_library()
+    keep, addr, begin, end = _text_args(text, begin, end)
+    n = int(begin.size)
+    chrom = np.array(chrom, np.int32)              # a copy: the given rows' records go in
+    flags = np.ascontiguousarray(flags, np.uint8)
+    rec_len = np.ascontiguousarray(rec_len, np.int64)
+    bitmap = np.ascontiguousarray(bitmap, np.uint32)
+    if chrom.shape != (n,) or flags.shape != (n,):
+        raise ValueError("chrom / flags must have one entry per row")
+    if bitmap.size < (int(rec_len.sum()) + 31) // 32:
+        raise ValueError("the bitmap is shorter than the records")
+    if bitmap.size == 0:
+        bitmap = np.zeros(1, np.uint32)
+    status = np.zeros(n, np.int32)
+    rows = {k: np.zeros(n, dt) for k, dt in _COMBINE_ROW_FIELDS}
+    for i, v in (given or {}).items():
+        if v is None:
+            status[i] = COMBINE_ROW_GIVEN_SKIP
+        else:
+            status[i], chrom[i] = COMBINE_ROW_GIVEN, v[0]
+            for (k, _), x in zip(_COMBINE_ROW_FIELDS, v[1:]):
+                rows[k][i] = x
+    cap = n if sites else 0
+    out = {k: np.empty(cap, dt) for k, dt in _COMBINE_SITE_FIELDS}
+    got = int(lib.ds_combine_reference(int(form), addr, n, begin.ctypes.data, end.ctypes.data, chrom.ctypes.data, flags.ctypes.data,
+                                       rec_len.size, rec_len.ctypes.data, bitmap.ctypes.data, status.ctypes.data,
+                                       *(rows[k].ctypes.data for k, _ in _COMBINE_ROW_FIELDS), cap,
+                                       *(out[k].ctypes.data for k, _ in _COMBINE_SITE_FIELDS)))
+    if got < 0:
+        raise RuntimeError("ds_combine_reference failed (%d): %s" % (got, lib.ds_last_error(None).decode()))
+    out = {k: v[:got] for k, v in out.items()}
+    out.update({"row_" + k: v for k, v in rows.items()})
+    out.update(status=status, row_chrom=chrom)
+    return out
+
+
 # ds_config.precision (include/deepsignal_hip.h): "bf16" = bf16 conv + FC operands with fp32 accumulation, fp32 BiLSTM;
 # "bf16_all" = also bf16 h / weight operands in the LSTM matmuls (fp32 accumulate, gates, cell state)
 PRECISIONS = {"fp32": 0, "bf16": 1, "bf16_all": 2, "bf16x3": 3}
@@ -467,6 +577,21 @@ def load_library() -> ctypes.CDLL:
     lib.ds_freq_values.argtypes = [vp, i64, vp, i32, vp, vp, vp]
     lib.ds_freq_values_reference.argtypes = [i64, vp, i32, vp, vp, vp]
     lib.ds_get_freq_stream_times.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(f64)]
+    u8p = vp
+    lib.ds_fasta_locate.argtypes = [vp, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i32)]
+    lib.ds_fasta_locate.restype = i64
+    lib.ds_combine_begin.argtypes = [vp, i32, i32, vp, i64, i32]
+    lib.ds_combine_genome.argtypes = [vp, vp, i64, vp, vp, vp, u8p]
+    lib.ds_combine_bitmap.argtypes = [vp, i64, vp]
+    lib.ds_combine_parse.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.ds_combine_accumulate.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.ds_combine_result.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(i64)]
+    lib.ds_combine_result.restype = i64
+    lib.ds_combine_end.argtypes = [vp]
+    lib.ds_motif_reference.argtypes = [vp, i64, vp, vp, vp, u8p, i64, vp]
+    lib.ds_combine_reference.argtypes = [i32, vp, i64, vp, vp, vp, vp, i32, vp, vp] + [vp] * 8 + [i64] + [vp] * 8
+    lib.ds_combine_reference.restype = i64
+    lib.ds_get_combine_times.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(f64)]
     _lib = lib
     return lib
 
@@ -848,6 +973,113 @@ class Engine:
         ms = (ctypes.c_double * 4)()
         self._check(self._lib.ds_get_freq_times(self._h, int(reset), ctypes.byref(n), ms), "ds_get_freq_times")
         return dict(zip(("copy_ms", "parse_ms", "sort_ms", "accumulate_ms"), ms), batches=int(n.value))
+
+    # -- both strands of a CpG table combined on the device (ds_combine_*; combine_strands --on gpu) ----------
+    def combine_begin(self, form: int, rec_len, total_rows: int, batch_rows: int) -> None:
+        """ds_combine_begin: open a run over the records whose lengths are rec_len (the bitmap holds one bit per base), with
+        total_rows rows in all in batches of at most batch_rows. FreqNoMemory when the bitmap, the table or the buffers do not fit
+        the device. Needs no weights."""
+        rec_len = np.ascontiguousarray(rec_len, np.int64)
+        form, total_rows, batch_rows = int(form), int(total_rows), int(batch_rows)
+        if form not in (COMBINE_TABLE, COMBINE_BED):
+            raise ValueError("form must be COMBINE_TABLE or COMBINE_BED")
+        if rec_len.ndim != 1 or not 1 <= rec_len.size <= FREQ_CHROM_LIMIT or int(rec_len.min()) < 0 or int(rec_len.max()) > FREQ_POS_LIMIT:
+            raise ValueError("rec_len must hold 1 .. 2^23 lengths in [0, 2^40]")
+        if not 0 <= total_rows <= FREQ_MAX_ROWS:
+            raise ValueError("total_rows must be in [0, 2^30]")
+        if not 1 <= batch_rows <= FREQ_MAX_BATCH:
+            raise ValueError("batch_rows must be in [1, 2^24]")
+        rc = self._lib.ds_combine_begin(self._h, form, rec_len.size, rec_len.ctypes.data, total_rows, batch_rows)
+        if rc == -5:
+            raise FreqNoMemory(self._lib.ds_last_error(self._h).decode())
+        self._check(rc, "ds_combine_begin")
+        self._combine_batch, self._combine_pending, self._combine_words = batch_rows, -1, (int(rec_len.sum()) + 31) // 32
+
+    def combine_genome(self, text, seg_begin, seg_end, seg_bit, seg_carry) -> None:
+        """ds_combine_genome: one chunk of the FASTA (segments ascending and disjoint, at most 2^30 bytes from the first begin to the
+        last end) through motif_bitmap_kernel into the run's bitmap."""
+        keep, addr, seg_begin, seg_end, seg_bit, seg_carry = _segment_args(text, seg_begin, seg_end, seg_bit, seg_carry)
+        if seg_begin.size < 1:
+            raise ValueError("a chunk holds at least one segment")
+        rc = self._lib.ds_combine_genome(self._h, addr, seg_begin.size, seg_begin.ctypes.data, seg_end.ctypes.data, seg_bit.ctypes.data,
+                                         seg_carry.ctypes.data)
+        if rc == -5:
+            raise FreqNoMemory(self._lib.ds_last_error(self._h).decode())
+        self._check(rc, "ds_combine_genome")
+
+    def combine_bitmap(self) -> np.ndarray:
+        """ds_combine_bitmap: the run's bitmap, uint32[(bases + 31) // 32]; what motif_reference gives on the CPU."""
+        out = np.zeros(getattr(self, "_combine_words", 0), np.uint32)
+        self._check(self._lib.ds_combine_bitmap(self._h, out.size, out.ctypes.data if out.size else None), "ds_combine_bitmap")
+        return out
+
+    def combine_parse(self, text, begin, end, chrom, flags) -> np.ndarray:
+        """ds_combine_parse: one batch of rows (ascending spans of one buffer; chrom = the record column 0 names, -1 for none; flags
+        as freq_locate gives them) -> the per-row status (TEXT_ROW_OK / TEXT_ROW_HOST / COMBINE_ROW_SKIP)."""
+        keep, addr, begin, end = _text_args(text, begin, end)
+        chrom = np.ascontiguousarray(chrom, np.int32)
+        flags = np.ascontiguousarray(flags, np.uint8)
+        n = int(begin.size)
+        if chrom.shape != (n,) or flags.shape != (n,):
+            raise ValueError("chrom / flags must have one entry per row")
+        if not 1 <= n <= getattr(self, "_combine_batch", 0):
+            raise ValueError("a batch holds 1 .. batch_rows rows of an open run")
+        if n > 1 and bool((begin[1:] < end[:-1]).any()):
+            raise ValueError("the rows of a batch must be ascending and disjoint")
+        status = np.empty(n, np.int32)
+        self._check(self._lib.ds_combine_parse(self._h, addr, n, begin.ctypes.data, end.ctypes.data, chrom.ctypes.data, flags.ctypes.data,
+                                               status.ctypes.data), "ds_combine_parse")
+        self._combine_pending = n
+        return status
+
+    def combine_accumulate(self, rows=(), given=()) -> None:
+        """ds_combine_accumulate: add the batch just parsed to the run. rows: the ascending batch indices of every TEXT_ROW_HOST
+        row; given: per such row None (its key is no CG) or (record, pos, plus, a, b, met, unmet, cov)."""
+        rows = np.ascontiguousarray(rows, np.int32)
+        m = int(rows.size)
+        if len(given) != m:
+            raise ValueError("one entry of `given` per override row")
+        n = getattr(self, "_combine_pending", -1)
+        if n < 0:
+            raise ValueError("combine_accumulate needs a batch from combine_parse")
+        if m and (int(rows.min()) < 0 or int(rows.max()) >= n or bool((np.diff(rows) <= 0).any())):
+            raise ValueError("override rows must be ascending indices of the batch")
+        status = np.array([COMBINE_ROW_SKIP if v is None else TEXT_ROW_OK for v in given], np.int32)
+        vals = [(0, 0, 0, 0.0, 0.0, 0, 0, 0) if v is None else v for v in given]
+        if any(abs(int(c)) >= COMBINE_COUNT_LIMIT for v in vals for c in v[5:8]):
+            raise ValueError("override counts must be below 2^32 in magnitude")
+        cols = [np.ascontiguousarray([v[k] for v in vals], dt) for k, dt in enumerate((np.int32, np.int64, np.int32, np.float64, np.float64,
+                                                                                         np.int64, np.int64, np.int64))]
+        self._combine_pending = -1
+        self._check(self._lib.ds_combine_accumulate(self._h, m, rows.ctypes.data, status.ctypes.data, *(c.ctypes.data for c in cols)),
+                    "ds_combine_accumulate")
+
+    def combine_result(self) -> Dict[str, np.ndarray]:
+        """ds_combine_result: the sites of the run so far, in no particular order -> chrom, pos, sum0, sum1, met, unmet, cov,
+        last_plus arrays, and the scalar rows (accumulated)."""
+        rows = ctypes.c_int64()
+        n = int(self._lib.ds_combine_result(self._h, 0, None, None, None, None, None, None, None, None, ctypes.byref(rows)))
+        self._check(n, "ds_combine_result")
+        out = {k: np.empty(n, dt) for k, dt in _COMBINE_SITE_FIELDS}
+        if n:
+            got = int(self._lib.ds_combine_result(self._h, n, *(out[k].ctypes.data for k, _ in _COMBINE_SITE_FIELDS), ctypes.byref(rows)))
+            self._check(got, "ds_combine_result")
+            if got != n:
+                raise RuntimeError("ds_combine_result: %d sites announced, %d returned" % (n, got))
+        out.update(rows=int(rows.value))
+        return out
+
+    def combine_end(self) -> None:
+        self._combine_batch, self._combine_pending = 0, -1
+        self._check(self._lib.ds_combine_end(self._h), "ds_combine_end")
+
+    def combine_times(self, reset: bool = False) -> dict:
+        """ds_get_combine_times: device milliseconds of the combine runs so far (copies, motif kernel, parse kernel, sort, insert +
+        accumulate), the genome chunks and the batches."""
+        c, n = ctypes.c_int64(), ctypes.c_int64()
+        ms = (ctypes.c_double * 5)()
+        self._check(self._lib.ds_get_combine_times(self._h, int(reset), ctypes.byref(c), ctypes.byref(n), ms), "ds_get_combine_times")
+        return dict(zip(("copy_ms", "motif_ms", "parse_ms", "sort_ms", "accumulate_ms"), ms), chunks=int(c.value), batches=int(n.value))
 
     def rows_times(self, reset: bool = False) -> dict:
         """ds_get_rows_times: device milliseconds of the extract_rows() calls made while profiling was on."""

@@ -532,6 +532,78 @@ int ds_freq_values(ds_handle *h, int64_t n, const float *act, int32_t class_num,
 int ds_freq_values_reference(int64_t n, const float *act, int32_t class_num, double *p0, double *p1, int32_t *status);
 int ds_get_freq_stream_times(ds_handle *h, int32_t reset, int64_t *growths, double *ms);
 
+/* ---- both strands of a CpG table combined on the device (ds_combine.hip; combine_strands --on gpu) ----------------------------------
+ * The work of scripts/combine_two_strands_frequency.py: the '-' strand row of a CpG is folded onto the '+' strand cytosine one base
+ * upstream, and only positions that are a CG of the reference genome are kept. None of this needs weights.
+ *
+ * ds_fasta_locate (host, no handle): one pass over a FASTA buffer as Python's text layer reads it. A line is what lies between two
+ * '\n' (a last line needs none). A line whose first raw byte is '>' opens a record; its name, line.strip()[1:].split(' ')[0], comes
+ * back as the span name_begin / name_end. Record 0 is what lies in front of the first header (name span 0, 0). Every other line,
+ * stripped of str.strip()'s ASCII set (space, 0x09 .. 0x0d, 0x1c .. 0x1f) and not empty, is a sequence line: its stripped byte span
+ * line_begin / line_end, its record line_rec and its offset line_off inside the record's sequence; rec_len is every record's
+ * length. *flags: 1 = a byte >= 0x80, 2 = a '\r' not followed by '\n' (Python reads such a file differently: the caller takes
+ * another route). Returns the sequence lines found; arrays are filled up to cap_lines / cap_recs and *n_recs (>= 1) is the number
+ * of records: call again with room when short. Which records count (empty, replaced by a later one of the same name, --contig) is
+ * the caller's decision; the device sees only the surviving ones, numbered 0 .. nrec - 1.
+ *
+ * One run on a handle: ds_combine_begin takes the form (DS_COMBINE_TABLE: the 11-column frequency table; DS_COMBINE_BED:
+ * bedMethyl), the surviving records' lengths (1 <= nrec <= 2^23, each <= 2^40; bit base(r) + i of the bitmap is base i of record
+ * r, base(r) the sum of the lengths in front: records lie back to back and may share a 32-bit word) and sizes the site table for
+ * total_rows (<= 2^30) and the buffers of a batch (1 <= nrows <= batch_rows <= 2^24); DS_ERR_NOMEM when they do not fit the device.
+ * ds_combine_genome takes one chunk of the FASTA: segments [seg_begin, seg_end) of `text`, ascending and disjoint, spanning at most
+ * 2^30 bytes from the first begin to the last end (those bytes travel as one copy and do not stay), each a piece of one sequence
+ * line whose first base is bit seg_bit; seg_carry is the base in front of the segment in the same record -- the last base of the
+ * previous line or chunk -- and 0 where the segment opens its record. motif_bitmap_kernel upper-cases (ASCII) and sets the bit of
+ * base i iff base i is C and base i + 1 of the same record is G, by 32-bit atomicOr. ds_combine_bitmap copies the bitmap out
+ * ((bits + 31) / 32 words; for the tests). Then the rows, strictly in sequence per batch and after the last chunk:
+ * ds_combine_parse (rows as for ds_freq_parse; chrom = the record column 0 names, -1 when it names none) gives the per-row status:
+ * DS_TEXT_ROW_OK; DS_COMBINE_ROW_SKIP -- the key (record, pos, or pos - 1 when the strand column is exactly "-") is unknown, outside
+ * [0, length) or no CG: decided before any number is read, as in the script; DS_TEXT_ROW_HOST -- a form outside the device grammar
+ * (pos not [-]digits of at most 18 digits, a count not [-]digits of at most nine, a double outside ds_freq_parse's grammar, too few
+ * columns, a flagged row). Table: prob0, prob1 as doubles, met / unmet / coverage as counts, and a '+' row must have its k-mer
+ * column. Bed: coverage (column 9) and met = percent (column 10) / 100 * coverage, two IEEE operations.
+ * ds_combine_accumulate first takes the caller's word on every DS_TEXT_ROW_HOST row (ascending batch row indices; status
+ * DS_TEXT_ROW_OK with record, pos inside it, plus, the two doubles and three counts below 2^32 in magnitude, or
+ * DS_COMBINE_ROW_SKIP), then inserts the OK rows' keys record << 40 | pos (the exact-key atomicCAS probe of ds_freq_accumulate),
+ * sorts (site, row) and adds each site's run IN ROW ORDER to two double sums and three 64-bit counts; the greatest '+' row of a
+ * site is kept (its k-mer is the site's). ds_combine_result: as ds_freq_result; per site record, pos, the sums and last_plus (a
+ * global row number, -1: no '+' row). ds_combine_end closes the run (ds_destroy does too). Every call blocks.
+ *
+ * ds_motif_reference / ds_combine_reference: the same scan and aggregation on the CPU from the same routines (csrc/ds_combine.h):
+ * CHECKERS, no handle, no GPU, not a fall-back. The scan ORs into `bitmap` (nbits bits; zero it first). The aggregation's status is
+ * in / out: DS_COMBINE_ROW_GIVEN on entry takes the row's values from the caller's arrays, DS_COMBINE_ROW_GIVEN_SKIP becomes
+ * DS_COMBINE_ROW_SKIP, every other row is parsed. Sites come out in the order of their first row; cap == 0 asks for the rows alone.
+ * ds_get_combine_times: device milliseconds since ds_create of ms[0] the copies, ms[1] motif_bitmap_kernel, ms[2]
+ * combine_parse_kernel, ms[3] the bitonic sort, ms[4] combine_insert_kernel + combine_accumulate_kernel. */
+#define DS_COMBINE_TABLE 0
+#define DS_COMBINE_BED 1
+#define DS_COMBINE_ROW_SKIP 2
+#define DS_COMBINE_ROW_GIVEN 3
+#define DS_COMBINE_ROW_GIVEN_SKIP 4
+int64_t ds_fasta_locate(const char *text, int64_t nbytes, int64_t cap_lines, int64_t *line_begin, int64_t *line_end, int32_t *line_rec,
+                        int64_t *line_off, int64_t cap_recs, int64_t *name_begin, int64_t *name_end, int64_t *rec_len, int64_t *n_recs,
+                        int32_t *flags);
+int ds_combine_begin(ds_handle *h, int32_t form, int32_t nrec, const int64_t *rec_len, int64_t total_rows, int32_t batch_rows);
+int ds_combine_genome(ds_handle *h, const char *text, int64_t nseg, const int64_t *seg_begin, const int64_t *seg_end,
+                      const int64_t *seg_bit, const uint8_t *seg_carry);
+int ds_combine_bitmap(ds_handle *h, int64_t cap_words, uint32_t *bitmap);
+int ds_combine_parse(ds_handle *h, const char *text, int32_t nrows, const int64_t *row_begin, const int64_t *row_end, const int32_t *chrom,
+                     const uint8_t *flags, int32_t *status);
+int ds_combine_accumulate(ds_handle *h, int32_t nover, const int32_t *row, const int32_t *status, const int32_t *chrom, const int64_t *pos,
+                          const int32_t *plus, const double *a, const double *b, const int64_t *met, const int64_t *unmet,
+                          const int64_t *cov);
+int64_t ds_combine_result(ds_handle *h, int64_t cap, int32_t *chrom, int64_t *pos, double *sum0, double *sum1, int64_t *met,
+                          int64_t *unmet, int64_t *cov, int64_t *last_plus, int64_t *rows);
+int ds_combine_end(ds_handle *h);
+int ds_motif_reference(const char *text, int64_t nseg, const int64_t *seg_begin, const int64_t *seg_end, const int64_t *seg_bit,
+                       const uint8_t *seg_carry, int64_t nbits, uint32_t *bitmap);
+int64_t ds_combine_reference(int32_t form, const char *text, int64_t nrows, const int64_t *row_begin, const int64_t *row_end,
+                             int32_t *chrom, const uint8_t *flags, int32_t nrec, const int64_t *rec_len, const uint32_t *bitmap,
+                             int32_t *status, int64_t *pos, int32_t *plus, double *a, double *b, int64_t *met, int64_t *unmet,
+                             int64_t *cov, int64_t cap, int32_t *site_chrom, int64_t *site_pos, double *sum0, double *sum1,
+                             int64_t *site_met, int64_t *site_unmet, int64_t *site_cov, int64_t *last_plus);
+int ds_get_combine_times(ds_handle *h, int32_t reset, int64_t *chunks, int64_t *batches, double *ms);
+
 /* Use a captured hipGraph for the forward (default on). */
 int ds_set_graph(ds_handle *h, int32_t enable);
 
