@@ -46,6 +46,7 @@ struct PackedGemm {      // device-resident packed weights of one GEMM
     float* bias = nullptr;
     int K = 0, N = 0;
     float* Bps = nullptr;   // DS_PRECISION_BF16X3: the same matrix as three bf16 term panels (pack_b_split)
+    float* Bp16 = nullptr;  // native fp32: the columns of 16-wide tiles as 16x16x4 fragments (pack_b_rem16): 32..47 of b3b / b4b, b1 of the P1 panel
 };
 
 enum OpKind { OP_GEMM, OP_STEM1, OP_MAXPOOL, OP_AVGPOOL, OP_HEAD, OP_FUSED, OP_PACKEV, OP_LSTM, OP_STEM23, OP_HEADF, OP_DENSES, OP_XPROJ };
@@ -386,6 +387,22 @@ std::vector<float> pack_b(int K, int N, const std::function<float(int, int)>& w_
     return out;
 }
 
+// Columns col0 .. col0 + 15 of a logical [K][N] matrix (K a multiple of 16) as v_mfma_f32_16x16x4_f32 fragments:
+// [kgroup of 16][lane][4] where lane (j = lane&15, q = lane>>4) element e holds W[kgroup*16 + 4*q + e][col0 + j] -- the
+// operand of the e-th of four MFMAs whose other operand is element e of one 16-byte read of four consecutive channels.
+// ntiles such column tiles follow one another: [tile][kgroup][lane][4].
+std::vector<float> pack_b_rem16(int K, int col0, int ntiles, const std::function<float(int, int)>& w)
+{
+    const int kg = K / 16;
+    std::vector<float> out((size_t)ntiles * kg * 256, 0.0f);
+    for (int t = 0; t < ntiles; ++t)
+        for (int g = 0; g < kg; ++g)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int e = 0; e < 4; ++e)
+                    out[(((size_t)t * kg + g) * 64 + lane) * 4 + e] = w(g * 16 + 4 * (lane >> 4) + e, col0 + 16 * t + (lane & 15));
+    return out;
+}
+
 uint16_t f32_to_bf16(float f)      // round to nearest even, like v_cvt_pk_bf16_f32
 {
     uint32_t u;
@@ -488,7 +505,8 @@ int fold_conv(ds_handle* h, const std::string& scope, const std::string& conv, c
 }
 
 // upload a GEMM whose columns are the concatenation of several folded convs with identical K
-int upload_concat(ds_handle* h, const std::vector<const FoldedConv*>& parts, PackedGemm* pg, bool split_panel = false)
+int upload_concat(ds_handle* h, const std::vector<const FoldedConv*>& parts, PackedGemm* pg, bool split_panel = false, int rem16_col0 = -1,
+                  int rem16_tiles = 1)
 {
     const int K = parts[0]->k * parts[0]->cin;
     int N = 0;
@@ -512,6 +530,7 @@ int upload_concat(ds_handle* h, const std::vector<const FoldedConv*>& parts, Pac
     int rc = upload(h, &pg->Bp, packed);
     if (rc) return rc;
     if (split_panel && (rc = upload(h, &pg->Bps, pack_b_split(K, N, wfun)))) return rc;
+    if (rem16_col0 >= 0 && !h->bf16 && (rc = upload(h, &pg->Bp16, pack_b_rem16(K, rem16_col0, rem16_tiles, wfun)))) return rc;
     return upload(h, &pg->bias, bias);
 }
 
@@ -553,9 +572,9 @@ int finalize_weights(ds_handle* h)
         // the five 1x1 convs that read the module input share one GEMM: [b2 | b5s | b3a | b4a | b5a]
         if ((rc = upload_concat(h, {&b2, &b5s, &b3a, &b4a, &b5a}, &h->m_s1[m]))) return rc;
         if ((rc = upload_concat(h, {&b1}, &h->m_b1[m]))) return rc;
-        if ((rc = upload_concat(h, {&b5s, &b2, &b3a, &b4a, &b5a, &b1}, &h->m_f1[m], h->split))) return rc;
-        if ((rc = upload_concat(h, {&b3b}, &h->m_b3b[m], h->split))) return rc;
-        if ((rc = upload_concat(h, {&b4b}, &h->m_b4b[m], h->split))) return rc;
+        if ((rc = upload_concat(h, {&b5s, &b2, &b3a, &b4a, &b5a, &b1}, &h->m_f1[m], h->split, 192, 3))) return rc;
+        if ((rc = upload_concat(h, {&b3b}, &h->m_b3b[m], h->split, 32))) return rc;
+        if ((rc = upload_concat(h, {&b4b}, &h->m_b4b[m], h->split, 32))) return rc;
         if ((rc = upload_concat(h, {&b5b}, &h->m_b5b[m], h->split))) return rc;
         if ((rc = upload_concat(h, {&b5c}, &h->m_b5c[m], h->split))) return rc;
     }
@@ -932,6 +951,7 @@ void plan_module_fused(Planner& P, int m, int st, const float* x, float* y, int 
     fa.Bp1 = sp ? h->m_f1[m].Bps : h->m_f1[m].Bp; fa.bias1 = h->m_f1[m].bias;
     fa.Bp3b = sp ? h->m_b3b[m].Bps : h->m_b3b[m].Bp; fa.bias3b = h->m_b3b[m].bias;
     fa.Bp4b = sp ? h->m_b4b[m].Bps : h->m_b4b[m].Bp; fa.bias4b = h->m_b4b[m].bias;
+    fa.Bp3r = h->m_b3b[m].Bp16; fa.Bp4r = h->m_b4b[m].Bp16; fa.Bp1r = h->m_f1[m].Bp16;
     fa.Bp5b = sp ? h->m_b5b[m].Bps : h->m_b5b[m].Bp; fa.bias5b = h->m_b5b[m].bias;
     fa.Bp5c = sp ? h->m_b5c[m].Bps : h->m_b5c[m].Bp; fa.bias5c = h->m_b5c[m].bias;
     fa.dbg = h->dbg_stamps ? h->dbg_stamps + (size_t)m * 1024 * 16 : nullptr;

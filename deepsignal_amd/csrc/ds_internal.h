@@ -192,6 +192,8 @@ struct FusedArgs {
     const float* Bp1;    // packed [cin x 256]: columns b5s(48)|b2(48)|b3a(32)|b4a(32)|b5a(32)|b1(48, pooled input)|pad
     const float* bias1;  // [256]
     const float *Bp3b, *bias3b, *Bp4b, *bias4b, *Bp5b, *bias5b, *Bp5c, *bias5c;
+    const float *Bp3r, *Bp4r;  // native fp32 kernel: output channels 32..47 of b3b / b4b as 16x16x4 fragments (ds_engine.cpp pack_b_rem16)
+    const float* Bp1r;         // native fp32 kernel: b1's 48 columns of the P1 panel (192..239) as three such column tiles
     unsigned long long* dbg;   // diagnostic: per-workgroup phase time stamps (null in normal runs)
     int write_rows;      // bf16 chain: 1 = this module's rows go to Y (the chain's last module; every module when taps are on), 0 = they
                          // stay in LDS as the next module's input. The fp32 kernel writes every module's rows.

@@ -934,13 +934,17 @@ hipError_t launch_lstm_cells(LstmTile tile, const LstmLaunch& L, hipStream_t s)
 
 // ---------------------------------------------------------------------------------------------
 // Fused inception module. One workgroup (8 waves) owns a tile of whole sites (<= 96 rows):
-//   P1  [rows x cin] x [cin x 256]: the six 1x1 convs that read the module input in ONE pass over
-//       it (branch 1 reads the 3-tap max-pooled rows, staged next to the plain rows). Wave w owns
-//       n-tile w for all m-tiles. b2/b1 go straight to HBM, the three 32-channel intermediates go
+//   P1  [rows x cin] x [cin x 240]: the six 1x1 convs that read the module input in ONE pass over
+//       it (branch 1 reads the 3-tap max-pooled rows, staged next to the plain rows). Wave w < 6 owns
+//       32-wide n-tile w for all m-tiles; waves 6, 7 share branch 1's 48 channels by ROWS, on 16-wide
+//       tiles. b2/b1 go straight to HBM, the three 32-channel intermediates go
 //       to LDS (T1, with zero halo rows = SAME padding), the residual stem stays in accumulators.
 //   P2a 1x3 64-ch conv of branch 5 (T1 -> T2 in LDS) + part of branch 3.
 //   P2b branch 5's last 1x1 accumulates ON TOP of the stem accumulators (waves 0,1) while the other
 //       waves finish the 1x3 / 1x5 convs of branches 3 and 4.
+// The 48-channel outputs (b1, b3b, b4b) are 32 + 16: channels 32..47 run on v_mfma_f32_16x16x4_f32 (the same FLOP per
+// clock as 32x32x2), so only the residual tail still pays for padded columns. Issued MFMA time per 96-row tile and module
+// (cin = 240), in units of 64 cycles: 3756 (P1 2700 + P2 1056), of which 3708 are real channels; 32-wide tiles alone took 4128.
 // HBM traffic per module = read input once + write output once (module-granular bytes).
 #ifndef DS_FUSED_WPS
 #define DS_FUSED_WPS 2
@@ -973,12 +977,13 @@ size_t inception_fused_lds_bytes(int tm, int W, int spt)
 
 // All weights of a conv unit (ntaps x 4 k-groups, <= 20 float4): requested EARLY — before the barrier or
 // the epilogue in front of the unit — so their L2 latency is off the unit's critical path.
-__device__ __forceinline__ void fused_unit_prefetch(const float* __restrict__ Bp, int ntaps, int nt, int lane, float4 (&ub)[20])
+// (NFRAG fragments: ntaps x 4 of a unit on 32-wide tiles, ntaps x 2 of a 16-channel remainder unit)
+template <int NFRAG>
+__device__ __forceinline__ void fused_unit_prefetch(const float* __restrict__ Bp, int lane, float4 (&ub)[20])
 {
-    const float* bsrc = Bp + ((size_t)(nt * ntaps * 4) * 64 + lane) * 4;
+    const float* bsrc = Bp + lane * 4;
 #pragma unroll
-    for (int g = 0; g < 20; ++g)
-        if (g < ntaps * 4) ub[g] = gload4(bsrc + g * 256);
+    for (int g = 0; g < NFRAG; ++g) ub[g] = gload4(bsrc + g * 256);
 }
 
 template <int NTAPS>
@@ -999,8 +1004,42 @@ __device__ __forceinline__ void fused_conv_unit(const float* T1, int rm, int col
     }
 }
 
+// Output channels 32..47 of a 48-channel conv (b3b, b4b) for one 32-row m-tile: two 16-row x 16-channel tiles on
+// v_mfma_f32_16x16x4_f32 -- the same FLOP per clock as the 32x32x2 form, and 48 = 32 + 16 leaves no padded columns. Transposed
+// like every MFMA here: lane (r = lane & 15, q = lane >> 4) reads channels 16g + 4q .. + 3 of activation row r with one
+// ds_read_b128 and feeds element e to the e-th of four MFMAs, whose weight fragment element e holds k = 16g + 4q + e
+// (ds_engine.cpp pack_b_rem16); it ends up with output channels 32 + 4q .. + 3 of its row. rm0 / rm1: T1 rows of the lane's row
+// in the upper / lower tile. The two tiles' MFMAs alternate, so no MFMA waits for the one before it.
+template <int NTAPS>
+__device__ __forceinline__ void fused_conv_unit16(const float* T1, int rm0, int rm1, int coloff, int lane, const float4 (&ub)[20], v4f& acc0, v4f& acc1)
+{
+    const float* base0 = T1 + rm0 * F_LD1 + coloff + (lane >> 4) * 4;
+    const float* base1 = T1 + rm1 * F_LD1 + coloff + (lane >> 4) * 4;
+#pragma unroll
+    for (int t = 0; t < NTAPS; ++t) {
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            const float4 a0 = *reinterpret_cast<const float4*>(base0 + (t - NTAPS / 2) * F_LD1 + g * 16);
+            const float4 a1 = *reinterpret_cast<const float4*>(base1 + (t - NTAPS / 2) * F_LD1 + g * 16);
+            const float4 w = ub[t * 2 + g];
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, a0.x, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, a1.x, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, a0.y, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, a1.y, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, a0.z, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, a1.z, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, a0.w, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, a1.w, acc1, 0, 0, 0);
+        }
+    }
+}
+
+__device__ __forceinline__ float f4elem(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
+
 struct FusedTagT { static constexpr bool value = true; };
 struct FusedTagF { static constexpr bool value = false; };
+struct FusedTaps3 { static constexpr int value = 3; };
+struct FusedTaps5 { static constexpr int value = 5; };
 
 template <int TM>
 __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
@@ -1069,19 +1108,25 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
         pq = sb + (size_t)ib * cin;
         pr = sb + (size_t)ic * cin;
     }
-    const float* bp = a.Bp1 + ((size_t)wave * ((cin + 31) / 32 * 4) * 64 + lane) * 4;   // K padded to 32 in the pack
+    // waves 0..5: n-tile `wave` of the 32-wide panel (K padded to 32 in the pack); waves 6, 7: b1's three 16-wide column tiles
+    const float* bp = wave < 6 ? a.Bp1 + ((size_t)wave * ((cin + 31) / 32 * 4) * 64 + lane) * 4 : a.Bp1r + lane * 4;
 
     // Every MFMA of this kernel is issued TRANSPOSED -- mfma(weight fragment, activation fragment) computes (X W)^T --
     // so a lane ends up holding, for ONE activation row (lane & 31), 4 x 4 consecutive output channels
     // (register 4g+e <-> channel 32*ntile + 8g + 4*(lane >> 5) + e). Results leave as float4 groups (LDS and HBM)
     // instead of scalars, and the bias is simply the accumulator's initial value.
+    // Waves 6, 7 (branch 1, 48 channels) instead split the tile's ROWS between them and run 16x16x4 MFMAs, so that no matrix
+    // cycle goes to the 16 padded columns of an eighth 32-wide n-tile: wave 6 + i owns rows i * TM * 16 .. + TM * 16 - 1 as TM row
+    // tiles x 3 column tiles. Its lane (r = lane & 15, q = lane >> 4) holds, for row tile mt and column tile g, channels
+    // 16g + 4q .. + 3 of row 16 mt + r in acc[mt][4g .. 4g + 3] -- again one float4 per (mt, g), so the epilogue is shared.
     const int h4 = 4 * (lane >> 5), rlane = lane & 31;
+    const int q4 = 4 * (lane >> 4), r15 = lane & 15, rbase16 = (wave - 6) * (TM * 16);
     floatx16 acc[TM];
     {
         float4 bv[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            bv[g] = gload4(a.bias1 + wave * 32 + 8 * g + h4);                  // bias1 is zero-padded to 256
+            bv[g] = gload4(a.bias1 + (wave < 6 ? wave * 32 + 8 * g + h4 : 192 + 16 * g + q4));   // bias1 is zero-padded to 256
             if (wave < 2) {                                                     // b5 stem columns also carry the tail's BN shift
                 const float4 t = gload4(a.bias5c + wave * 32 + 8 * g + h4);     // (zero-padded to 64)
                 bv[g].x += t.x; bv[g].y += t.y; bv[g].z += t.z; bv[g].w += t.w;
@@ -1102,7 +1147,7 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
     int offm[TM], offp[TM];
 #pragma unroll
     for (int mt = 0; mt < TM; ++mt) {
-        const int row = mt * 32 + (lane & 31);
+        const int row = rbase16 + mt * 16 + r15;      // (only waves 6, 7 use these)
         const int w = row % W;
         offm[mt] = (row < TRv && w > 0) ? -F_LDA : 0;
         offp[mt] = (row < TRv && w < W - 1) ? F_LDA : 0;
@@ -1120,8 +1165,8 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
         constexpr int VD = DS_FUSED_VD;
         float4 vc[VD];
         constexpr int BD = DS_FUSED_BD;                  // register stages of the weight fragments (chunk c's are requested BD - 1 steps ahead)
-        float4 bq[BD][2];
-        float4 af[2][2][TM];
+        float4 bq[BD][POOL ? 3 : 2];                     // pooling waves: one fragment per 16-wide column tile
+        float4 af[2][POOL ? 1 : 2][TM];                  // pooling waves: one 16-row x 16-k fragment per row tile
         // (the pooling waves 6, 7 hold threads 384 .. 511 and a tile has at most 96 x 4 = 384 staging slots: they never stage,
         // and their variant carries neither the staging registers nor the row pointers)
         auto load_a = [&](int V) __attribute__((always_inline)) {
@@ -1137,22 +1182,50 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
             if (!POOL && stager) *reinterpret_cast<float4*>(Ad + X * TR32 * F_LDA + sr * F_LDA + sq * 4) = vc[V];
         };
         auto load_b = [&](int Bi) __attribute__((always_inline)) {
-            bq[Bi][0] = gload4(bp);
-            bq[Bi][1] = gload4(bp + 256);
-            bp += 512;
+            if (POOL) {
+#pragma unroll
+                for (int ct = 0; ct < 3; ++ct) bq[Bi][ct] = gload4(bp + ct * cin * 16);      // a column tile's image is cin / 16 KiB
+                bp += 256;
+            } else {
+                bq[Bi][0] = gload4(bp);
+                bq[Bi][1] = gload4(bp + 256);
+                bp += 512;
+            }
         };
         auto read_frags = [&](int X) __attribute__((always_inline)) {
+            if (POOL) {
+#pragma unroll
+                for (int mt = 0; mt < TM; ++mt) {
+                    const float* q = Ad + X * TR32 * F_LDA + (rbase16 + mt * 16 + r15) * F_LDA + q4;
+                    af[X][0][mt] = f4max_relu(f4max_relu(*reinterpret_cast<const float4*>(q), *reinterpret_cast<const float4*>(q + offm[mt])),
+                                              *reinterpret_cast<const float4*>(q + offp[mt]));
+                }
+                return;
+            }
 #pragma unroll
             for (int rs = 0; rs < 2; ++rs)
 #pragma unroll
                 for (int mt = 0; mt < TM; ++mt) {
                     const float* q = Ad + X * TR32 * F_LDA + (mt * 32 + (lane & 31)) * F_LDA + rs * 8 + (lane >> 5) * 4;
-                    float4 v = *reinterpret_cast<const float4*>(q);
-                    if (POOL) v = f4max_relu(f4max_relu(v, *reinterpret_cast<const float4*>(q + offm[mt])), *reinterpret_cast<const float4*>(q + offp[mt]));
-                    af[X][rs][mt] = v;
+                    af[X][rs][mt] = *reinterpret_cast<const float4*>(q);
                 }
         };
         auto mfma_rs = [&](int X, int Bi, int rs) __attribute__((always_inline)) {
+            if (POOL) {
+                // half rs of a chunk = elements 2 rs, 2 rs + 1 of every fragment (k = 4q + e); the 3 TM accumulators take turns,
+                // so no MFMA waits for the one before it
+#pragma unroll
+                for (int e = 2 * rs; e < 2 * rs + 2; ++e)
+#pragma unroll
+                    for (int mt = 0; mt < TM; ++mt)
+#pragma unroll
+                        for (int ct = 0; ct < 3; ++ct) {
+                            v4f t = {acc[mt][4 * ct], acc[mt][4 * ct + 1], acc[mt][4 * ct + 2], acc[mt][4 * ct + 3]};
+                            t = __builtin_amdgcn_mfma_f32_16x16x4f32(f4elem(bq[Bi][ct], e), f4elem(af[X][0][mt], e), t, 0, 0, 0);
+                            acc[mt][4 * ct] = t[0]; acc[mt][4 * ct + 1] = t[1]; acc[mt][4 * ct + 2] = t[2]; acc[mt][4 * ct + 3] = t[3];
+                        }
+                return;
+            }
 #pragma unroll
             for (int mt = 0; mt < TM; ++mt) {
                 acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(bq[Bi][rs].x, af[X][rs][mt].x, acc[mt], 0, 0, 0);
@@ -1182,8 +1255,8 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
                 if (has1) read_frags(X ^ 1);
                 mfma_rs(X, c % BD, 1);
                 __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                if (has1) __builtin_amdgcn_sched_group_barrier(0x100, (POOL ? 6 : 2) * TM, 0);
-                __builtin_amdgcn_sched_group_barrier(0x8, 4 * TM, 0);
+                if (has1) __builtin_amdgcn_sched_group_barrier(0x100, (POOL ? 3 : 2) * TM, 0);
+                __builtin_amdgcn_sched_group_barrier(0x8, (POOL ? 6 : 4) * TM, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -1196,32 +1269,41 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
     __syncthreads();   // all fragment reads of the staging area are done before T2 aliases it
     DS_STAMP(2);
 
-    // ---- static wave -> unit assignment of P2 (wave-uniform). kind: 0 none, 1 b5b, 2 b3b, 3 b4b. Waves w and w+4 share
-    // a SIMD; the table keeps the MFMA count per SIMD within 5 % across P2a + P2b.
-    int a1k = 0, a1m = 0, a1n = 0, a2k = 0, a2m = 0, a2n = 0;      // P2a units
-    int b1k = 0, b1m = 0, b1n = 0, b2k = 0, b2m = 0, b2n = 0;      // P2b units (waves 0,1 run the residual tail first)
+    // ---- static wave -> unit assignment of P2 (wave-uniform). Units, in 64-cycle MFMA units: b5b (1x3, 32 -> 64; 48 per
+    // m-tile and n-tile), b3b / b4b channels 0..31 on 32x32x2 tiles (48 / 80 per m-tile), b3b / b4b channels 32..47 on 16x16x4
+    // tiles (24 / 40), the tail (TM x 32 on waves 0, 1, in P2b). b5b must run in P2a; the others are free. Every wave walks
+    // the same sequence of SITES, each with one tile shape and one tap count, and runs or skips each of them:
+    //   P2a  A1 1x3 on 32-wide tiles (kind 1 = b5b, 2 = b3b) | A2 b3b remainder
+    //   P2b  B1 1x5 (kind 3 = b4b on 32-wide tiles, 5 = its remainder) | B2 b3b on 32-wide tiles | B3 b3b remainder
+    // (a site whose weights differ in number from wave to wave costs registers: see pf below). Waves w and w+4 share a SIMD.
+    // Three m-tiles, per SIMD: P2a 96 96 120 96, P2b 160 160 160 168 -- 1056 in all, where 32-wide tiles alone took 1248.
+    int a1k = 0, a1m = 0, a1n = 0, a2m = -1;                        // P2a
+    int b1k = 0, b1m = 0, b2m = -1, b3m = -1;                       // P2b (waves 0, 1 run the residual tail)
     if (TM == 3) {
         if (wave < 6) { a1k = 1; a1m = wave % 3; a1n = wave / 3; }
-        else { a1k = 2; a1m = 0; a1n = wave - 6; }
-        if (wave >= 2) { b1k = 3; b1m = (wave - 2) % 3; b1n = (wave - 2) / 3; }
-        if (wave >= 4) { b2k = 2; b2m = 1 + ((wave - 4) >> 1); b2n = (wave - 4) & 1; }
+        else { a1k = 2; a1m = wave - 6; }
+        if (wave == 6) a2m = 0;
+        if (wave == 2 || wave == 3) { b1k = 3; b1m = wave - 2; }
+        else if (wave == 6) { b1k = 3; b1m = 2; }
+        else if (wave == 4 || wave == 5) { b1k = 5; b1m = wave - 4; b3m = wave - 3; }
+        else if (wave == 7) { b1k = 5; b1m = 2; b2m = 2; }
     } else if (TM == 2) {
         if (wave < 4) { a1k = 1; a1m = wave & 1; a1n = wave >> 1; }
-        else { a1k = 2; a1m = wave & 1; a1n = (wave - 4) >> 1; }
-        if (wave >= 2 && wave < 6) { b1k = 3; b1m = (wave - 2) & 1; b1n = (wave - 2) >> 1; }
+        else if (wave < 6) { a1k = 2; a1m = wave & 1; }
+        else a2m = wave & 1;
+        if (wave >= 2 && wave < 6) { b1k = wave < 4 ? 3 : 5; b1m = wave & 1; }
     } else {
         if (wave < 2) { a1k = 1; a1n = wave; }
-        else if (wave < 4) { a1k = 2; a1n = wave - 2; }
-        else if (wave < 6) { a1k = 3; a1n = wave - 4; }
+        else if (wave == 2) a1k = 2;
+        else if (wave == 3) a2m = 0;
+        else if (wave < 6) b1k = wave == 4 ? 3 : 5;
     }
-    auto unit_Bp = [&](int k) { return k == 1 ? a.Bp5b : k == 2 ? a.Bp3b : a.Bp4b; };
-    auto unit_taps = [&](int k) { return k == 3 ? 5 : 3; };
     float4 pf[20];                                   // prefetched weights of the next unit
     // (defined on every path: a register array that is only loaded under a wave-uniform condition is "undefined on some
     // paths", and hipcc keeps such a value live around the whole module loop -- 80 + 32 VGPRs of phantom live range here)
 #pragma unroll
     for (int g = 0; g < 20; ++g) pf[g] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a1k) fused_unit_prefetch(unit_Bp(a1k), unit_taps(a1k), a1n, lane, pf);
+    if (a1k) fused_unit_prefetch<12>(a1k == 1 ? a.Bp5b + a1n * (12 * 256) : a.Bp3b, lane, pf);
 
     // ---- P1 epilogue (bias already inside acc): route the 256 columns. b1|b2 go through an LDS tile and leave as
     // whole 384-B row segments.
@@ -1235,15 +1317,16 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
                     make_float4(relu_f(acc[mt][4 * g]), relu_f(acc[mt][4 * g + 1]), relu_f(acc[mt][4 * g + 2]),
                                 relu_f(acc[mt][4 * g + 3]));
         }
-    } else if (wave != 0) {                  // n-tiles 1,2 (b5s tail | b2) and 6,7 (b1 | padding) -> output tile
+    } else if (wave != 0) {                  // n-tiles 1,2 (b5s tail | b2) and b1 (waves 6, 7: rows split, 16-wide tiles) -> output tile
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const int col = wave * 32 + 8 * g + h4;          // groups of 4 never straddle 48 / 240
-            if (col >= 48 && col < 240) {
-                const int ycol = col < 96 ? col : col - 192;        // position inside Y[:, 0:96) (b1 first, then b2)
+            // waves 1, 2: columns 32 .. 95 of the panel, of which 48 .. 95 are b2 = Y[:, 48:96) (groups of 4 never straddle 48);
+            // waves 6, 7: b1 = Y[:, 0:48), column tile g (there is no fourth)
+            const int ycol = wave < 6 ? wave * 32 + 8 * g + h4 : 16 * g + q4;
+            if (wave < 6 ? ycol >= 48 : g < 3) {
 #pragma unroll
                 for (int mt = 0; mt < TM; ++mt)
-                    *reinterpret_cast<float4*>(Ys + (mt * 32 + rlane) * F_LD1 + ycol) =
+                    *reinterpret_cast<float4*>(Ys + (wave < 6 ? mt * 32 + rlane : rbase16 + mt * 16 + r15) * F_LD1 + ycol) =
                         make_float4(relu_f(acc[mt][4 * g]), relu_f(acc[mt][4 * g + 1]), relu_f(acc[mt][4 * g + 2]),
                                     relu_f(acc[mt][4 * g + 3]));
             }
@@ -1261,61 +1344,110 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
         }
     }
 
-    auto run_unit = [&](int kind, int mt, int nt) {
+    // 1x3 on a 32-row x 32-channel tile. kind 1: b5b, 32 -> 64, ReLU, to T2 (n-tile nt)     layers.py:127-131
+    //                                    kind 2: b3b, 32 -> 48, ReLU, channels 0..31 to Y[96,128)   layers.py:106-110
+    auto unit_full3 = [&](int kind, int mt, int nt) {
         floatx16 u;
-        const float* bsrc = Bs + (kind == 1 ? 0 : kind == 2 ? 64 : 128) + nt * 32 + h4;
+        const float* bsrc = Bs + (kind == 1 ? nt * 32 : 64) + h4;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const float4 t = *reinterpret_cast<const float4*>(bsrc + 8 * g);
             u[4 * g] = t.x; u[4 * g + 1] = t.y; u[4 * g + 2] = t.z; u[4 * g + 3] = t.w;
         }
         const int row = mt * 32 + rlane;
-        const int rm = rowmap[row];
-        if (kind == 1) {          // 1x3, 32 -> 64, ReLU, to T2                            layers.py:127-131
-            fused_conv_unit<3>(T1, rm, 64, lane, pf, u);
+        fused_conv_unit<3>(T1, rowmap[row], kind == 1 ? 64 : 0, lane, pf, u);
+        if (kind == 1) {
 #pragma unroll
             for (int g = 0; g < 4; ++g)
                 *reinterpret_cast<float4*>(T2 + row * F_LD2 + nt * 32 + 8 * g + h4) =
                     make_float4(relu_f(u[4 * g]), relu_f(u[4 * g + 1]), relu_f(u[4 * g + 2]), relu_f(u[4 * g + 3]));
-        } else {
-            // kind 2: 1x3, 32 -> 48, ReLU, to Y[96,144)   layers.py:106-110
-            // kind 3: 1x5, 32 -> 48, ReLU, to Y[144,192)  layers.py:115-119
-            if (kind == 2) fused_conv_unit<3>(T1, rm, 0, lane, pf, u);
-            else fused_conv_unit<5>(T1, rm, 32, lane, pf, u);
-            const int ybase = kind == 2 ? 96 : 144;
-            if (row < TRv) {
+        } else if (row < TRv) {
 #pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    if (nt * 32 + 8 * g < 48) {      // wave-uniform: 48 output channels = n-tile 0 and half of n-tile 1
-                        v4f o = {relu_f(u[4 * g]), relu_f(u[4 * g + 1]), relu_f(u[4 * g + 2]), relu_f(u[4 * g + 3])};
-                        *(__attribute__((address_space(1))) v4f*)(Yg + (unsigned)(row * 240 + ybase + nt * 32 + 8 * g + h4)) = o;
-                    }
+            for (int g = 0; g < 4; ++g) {
+                v4f o = {relu_f(u[4 * g]), relu_f(u[4 * g + 1]), relu_f(u[4 * g + 2]), relu_f(u[4 * g + 3])};
+                *(__attribute__((address_space(1))) v4f*)(Yg + (unsigned)(row * 240 + 96 + 8 * g + h4)) = o;
             }
         }
     };
-
-    // ---- P2a
-    if (a1k) run_unit(a1k, a1m, a1n);
-    if (a2k) {
-        fused_unit_prefetch(unit_Bp(a2k), unit_taps(a2k), a2n, lane, pf);
-        run_unit(a2k, a2m, a2n);
-    }
-    // weights of the first P2b job are requested before the barrier
-    float4 b5c[8];
+    // b4b: 1x5, 32 -> 48, ReLU, channels 0..31 to Y[144,176)                                  layers.py:115-119
+    auto unit_full5 = [&](int mt) {
+        floatx16 u;
 #pragma unroll
-    for (int g = 0; g < 8; ++g) b5c[g] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (wave < 2) {
+        for (int g = 0; g < 4; ++g) {
+            const float4 t = *reinterpret_cast<const float4*>(Bs + 128 + h4 + 8 * g);
+            u[4 * g] = t.x; u[4 * g + 1] = t.y; u[4 * g + 2] = t.z; u[4 * g + 3] = t.w;
+        }
+        const int row = mt * 32 + rlane;
+        fused_conv_unit<5>(T1, rowmap[row], 32, lane, pf, u);
+        if (row < TRv) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                v4f o = {relu_f(u[4 * g]), relu_f(u[4 * g + 1]), relu_f(u[4 * g + 2]), relu_f(u[4 * g + 3])};
+                *(__attribute__((address_space(1))) v4f*)(Yg + (unsigned)(row * 240 + 144 + 8 * g + h4)) = o;
+            }
+        }
+    };
+    // channels 32..47 of b3b (NTAPS 3, to Y[128,144)) or b4b (NTAPS 5, to Y[176,192)) on 16-wide tiles
+    auto unit_rem = [&](auto ntaps_tag, int mt) {
+        constexpr int NTAPS = decltype(ntaps_tag)::value;
+        const int q4 = 4 * (lane >> 4), row0 = mt * 32 + (lane & 15), row1 = row0 + 16;
+        const float4 t = *reinterpret_cast<const float4*>(Bs + (NTAPS == 3 ? 64 : 128) + 32 + q4);
+        v4f u0 = {t.x, t.y, t.z, t.w}, u1 = u0;
+        fused_conv_unit16<NTAPS>(T1, rowmap[row0], rowmap[row1], NTAPS == 3 ? 0 : 32, lane, pf, u0, u1);
+        const int ycol = (NTAPS == 3 ? 96 : 144) + 32 + q4;
+        if (row0 < TRv) {
+            v4f o = {relu_f(u0[0]), relu_f(u0[1]), relu_f(u0[2]), relu_f(u0[3])};
+            *(__attribute__((address_space(1))) v4f*)(Yg + (unsigned)(row0 * 240 + ycol)) = o;
+        }
+        if (row1 < TRv) {
+            v4f o = {relu_f(u1[0]), relu_f(u1[1]), relu_f(u1[2]), relu_f(u1[3])};
+            *(__attribute__((address_space(1))) v4f*)(Yg + (unsigned)(row1 * 240 + ycol)) = o;
+        }
+    };
+
+    // Waves 0, 1 keep the stem accumulators through P2a for the tail; the other waves' accumulators are dead after the P1
+    // epilogue. The two groups take separate (wave-uniform) paths, each with its own copy of the T2 barrier, so that the
+    // registers of acc are free where the 1x5 units run (80 registers of weights).
+    if (wave >= 2) {
+        // ---- P2a
+        if (a1k) unit_full3(a1k, a1m, a1n);
+        if (a2m >= 0) {
+            fused_unit_prefetch<6>(a.Bp3r, lane, pf);
+            unit_rem(FusedTaps3{}, a2m);
+        }
+        // ---- P2b behind the T2 barrier (the same barrier as waves 0, 1's). The weights of a wave's 1x5 unit are requested before
+        // it. Request, barrier and unit sit in ONE branch per kind: were the request under one condition and the unit under
+        // another, hipcc would keep the previous unit's weights alive across the barrier for the paths it cannot rule out.
+        if (b1k == 3) {
+            fused_unit_prefetch<20>(a.Bp4b, lane, pf);
+            DS_STAMP(5); __syncthreads(); DS_STAMP(6);
+            unit_full5(b1m);
+        } else if (b1k == 5) {
+            fused_unit_prefetch<10>(a.Bp4r, lane, pf);
+            DS_STAMP(5); __syncthreads(); DS_STAMP(6);
+            unit_rem(FusedTaps5{}, b1m);
+        } else {
+            DS_STAMP(5); __syncthreads(); DS_STAMP(6);
+        }
+        if (b2m >= 0) {
+            fused_unit_prefetch<12>(a.Bp3b, lane, pf);
+            unit_full3(2, b2m, 0);
+        }
+        if (b3m >= 0) {
+            fused_unit_prefetch<6>(a.Bp3r, lane, pf);
+            unit_rem(FusedTaps3{}, b3m);
+        }
+    } else {
+        // ---- P2a: one b5b unit (every table above gives waves 0, 1 kind 1 and nothing else)
+        unit_full3(1, a1m, a1n);
+        // weights of the tail are requested before the barrier
+        float4 b5c[8];
 #pragma unroll
         for (int g = 0; g < 8; ++g) b5c[g] = gload4(a.Bp5c + ((size_t)(wave * 8 + g) * 64 + lane) * 4);
-    } else if (b1k) {
-        fused_unit_prefetch(unit_Bp(b1k), unit_taps(b1k), b1n, lane, pf);
-    }
-    DS_STAMP(5);
-    __syncthreads();   // T2 complete
-    DS_STAMP(6);
-
-    // ---- P2b
-    if (wave < 2) {
+        DS_STAMP(5);
+        __syncthreads();   // T2 complete
+        DS_STAMP(6);
+        // ---- P2b
         // branch 5 tail: 1x1 64 -> 48 (BN, no ReLU) accumulated on top of the stem conv held in acc,
         // then relu(stem + tail)                                                         layers.py:132-138
 #pragma unroll
@@ -1342,12 +1474,6 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
                         *(__attribute__((address_space(1))) v4f*)(Yg + (unsigned)(row * 240 + 192 + wave * 32 + 8 * g + h4)) = o;
                     }
             }
-        }
-    } else {
-        if (b1k) run_unit(b1k, b1m, b1n);
-        if (b2k) {
-            fused_unit_prefetch(unit_Bp(b2k), unit_taps(b2k), b2n, lane, pf);
-            run_unit(b2k, b2m, b2n);
         }
     }
     DS_STAMP(7);

@@ -31,6 +31,10 @@ def kernel_resources():
         res[name] = {"vgprs": get("next_free_vgpr"), "scratch_bytes": get("private_segment_fixed_size"),
                      "static_lds_bytes": get("group_segment_fixed_size"), "sgpr_spills": 0, "vgpr_spills": 0}
         res[name]["mangled"] = m.group(1)
+        # static fp32 MFMA mix of the kernel's code (instructions in the text, not issued counts): which tile shapes it uses
+        code = re.search(r"^%s:.*?s_endpgm" % re.escape(m.group(1)), text, re.S | re.M)
+        for shape in ("32x32x2", "16x16x4"):
+            res[name]["mfma_f32_" + shape] = len(re.findall(r"v_mfma_f32_%s_f32" % shape, code.group(0))) if code else -1
     # spill counts live in the amdhsa.kernels metadata (one YAML entry per kernel)
     by_mangled = {r.pop("mangled"): r for r in res.values()}
     for m in re.finditer(r"- \.agpr_count:.*?(?=\n  - \.agpr_count:|\namdhsa\.target|\Z)", text, re.S):
