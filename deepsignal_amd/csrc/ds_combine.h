@@ -1,12 +1,12 @@
 // ds_combine.h — both strands of a CpG table folded onto the '+' cytosine (combine_strands --on gpu; ds_combine.hip): the motif
 // test of the genome scan, the row grammar of a frequency table / bedMethyl file as the DEVICE reads it, and the host-side state of
-// one run. The routines are __host__ __device__ and built from the token routines of ds_tsv_device.h and the site key of ds_freq.h,
+// one run. The routines are __host__ __device__ and built from the token routines of ds_tsv_device.h and the site key of ds_site_table.h,
 // so the CPU checkers (dsc::motif_reference, dsc::reference, behind ds_motif_reference / ds_combine_reference) run the code the
 // kernels run. Compiled with -ffp-contract=off and without fast-math (csrc/Makefile): the bed form's a / 100 * b and the sums after
 // it are separate IEEE operations. A row in any form outside the grammar is not an error here: its status says ROW_HOST and the
 // caller supplies its values. Not part of the public ABI.
 #pragma once
-#include "ds_freq.h"
+#include "ds_site_table.h"
 
 #include <vector>
 
@@ -51,7 +51,7 @@ struct Row {
 DST_HD int parse_row(int form, const char* b, const char* e, int32_t chrom, unsigned flags, int32_t nrec, const int64_t* rec_base,
                      const int64_t* rec_len, const uint32_t* bitmap, Row* r)
 {
-    if ((flags & dsf::FLAG_HOST) || chrom >= nrec) return ROW_HOST;
+    if ((flags & dss::FLAG_HOST) || chrom >= nrec) return ROW_HOST;
     const char* cb[11];        // column c = [cb[c], ce[c])
     const char* ce[11];
     int nc = 0;
@@ -116,10 +116,9 @@ int64_t reference(int form, const char* text, int64_t nrows, const int64_t* begi
 // applies the caller's values for ROW_HOST rows, inserts the ROW_OK rows' keys, sorts (site, row) and adds each site's run in row
 // order; result() compacts the occupied slots. Every call blocks; batches go strictly in sequence, after the last genome chunk.
 struct Combine {
-    int device = 0, form = FORM_TABLE;
-    hipStream_t s = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    int64_t total_rows = 0, rows_done = 0, nbits = 0, chunk_bytes = 0;
+    int form = FORM_TABLE;
+    dss::Run run;                // the stream, the events and every device allocation of the run
+    int64_t total_rows = 0, rows_done = 0, nbits = 0;
     int32_t batch_rows = 0, pending = -1, nrec = 0;
     bool rows_begun = false;
     std::vector<int64_t> h_len;
@@ -127,24 +126,19 @@ struct Combine {
     // genome
     uint32_t* bitmap = nullptr;
     int64_t *d_rec_base = nullptr, *d_rec_len = nullptr;
-    char* d_seg = nullptr;       // a chunk's [seg_off | seg_end | seg_bit | seg_carry]
-    size_t seg_cap = 0;
+    dss::Buf seg;                // a chunk's [seg_off | seg_end | seg_bit | seg_carry]
     // table
     uint64_t *t_key = nullptr, *t_plus = nullptr;      // t_plus: the greatest '+' row of the site + 1, 0 = none
     double *t_sum0 = nullptr, *t_sum1 = nullptr;
     int64_t *t_met = nullptr, *t_unmet = nullptr, *t_cov = nullptr;
     unsigned long long* counters = nullptr;       // [0] sites, [1] rows added, [2] probe sequences that found no slot, [3] ROW_HOST rows left
     // batch
-    char* d_text = nullptr;
-    size_t text_cap = 0;
-    int64_t* d_off = nullptr;
-    int32_t *d_len = nullptr, *d_chrom = nullptr, *d_status = nullptr, *d_plus = nullptr;
-    uint8_t* d_flags = nullptr;
+    dss::RowText rows;
+    int32_t* d_plus = nullptr;
     int64_t *d_pos = nullptr, *d_c0 = nullptr, *d_c1 = nullptr, *d_c2 = nullptr;
     double *d_a = nullptr, *d_b = nullptr;
     uint64_t* d_sort = nullptr;
-    char* d_over = nullptr;
-    size_t over_cap = 0;
+    dss::Buf over;               // the caller's word on a batch's ROW_HOST rows
     int64_t batches = 0, chunks = 0;
     double ms[5] = {0, 0, 0, 0, 0};     // copies, motif_bitmap_kernel, combine_parse_kernel, the sort, insert + accumulate
 

@@ -4,23 +4,22 @@
 // found across line breaks and chunk boundaries and never across two records; the C's bit may lie in a word another lane or chunk
 // also writes: 32-bit atomicOr). One bit per base stays, the bytes do not. Then the rows, a batch at a time: combine_parse_kernel
 // (one row per lane; the key test against the bitmap comes before the numbers, as in the script), combine_insert_kernel (the exact
-// keys record << 40 | pos into an open-addressing table by 64-bit atomicCAS, the probe of ds_freq.hip; the greatest '+' row of a site
-// by atomicMax), the bitonic sort of site << 32 | row (dsf::bitonic_sort) and combine_accumulate_kernel (the lane at the head of a
-// site's run adds the run IN ROW ORDER: no floating-point atomics). Built with -ffp-contract=off and no fast-math (csrc/Makefile).
+// keys record << 40 | pos into the site table of ds_site_table.h; the greatest '+' row of a site by atomicMax), the bitonic sort of
+// site << 32 | row and combine_accumulate_kernel (the lane at the head of a site's run adds the run IN ROW ORDER: no floating-point
+// atomics). Built with -ffp-contract=off and no fast-math (csrc/Makefile).
 #include "ds_combine.h"
-#include "../../include/deepsignal_hip.h"
-
-#include <string.h>
 
 #include <unordered_map>
-#include <vector>
 
 namespace dsc {
 
 namespace {
 
-constexpr int TPB = 256;
-constexpr uint64_t SORT_PAD = ~(uint64_t)0;      // rows that take no part sort behind every site
+using dss::TPB;
+using dss::blocks;
+using dss::seterr;
+using dss::u64;
+using dss::ull;
 
 // lane t looks at bytes [t * LANE_BYTES, (t + 1) * LANE_BYTES) of the chunk: the segment of its first byte by bisection, the next
 // ones by walking on. Bytes outside every segment (line ends, what strip() removes, header lines) are passed over.
@@ -77,102 +76,50 @@ __global__ __launch_bounds__(TPB) void combine_override_kernel(int m, const int3
     r.status[i] = ostatus[k];
 }
 
-__global__ __launch_bounds__(TPB) void combine_insert_kernel(int n, int P, unsigned long long row_base, const int32_t* chrom, const int64_t* pos,
-                                                             const int32_t* plus, const int32_t* status, unsigned long long* t_key,
-                                                             unsigned long long* t_plus, unsigned long long mask, unsigned long long* sort,
-                                                             unsigned long long* counters)
+__global__ __launch_bounds__(TPB) void combine_insert_kernel(int n, int P, ull row_base, const int32_t* chrom, const int64_t* pos, const int32_t* plus,
+                                                             const int32_t* status, ull* t_key, ull* t_plus, ull mask, ull* sort, ull* counters)
 {
     const int i = blockIdx.x * TPB + threadIdx.x;
     if (i >= P) return;
-    unsigned long long sk = SORT_PAD;
+    ull sk = dss::SORT_PAD;
     if (i < n && status[i] != ROW_SKIP) {
-        if (status[i] != ROW_OK || !dsf::key_ok(chrom[i], pos[i])) {
+        if (status[i] != ROW_OK || !dss::key_ok(chrom[i], pos[i])) {
             atomicAdd(&counters[3], 1ull);
         } else {
-            const unsigned long long k = dsf::make_key(chrom[i], pos[i]);
-            unsigned long long s = dsf::hash_key(k) & mask;
-            bool found = false;
-            for (unsigned long long probe = 0; probe <= mask; ++probe) {
-                const unsigned long long prev = atomicCAS(&t_key[s], (unsigned long long)dsf::EMPTY, k);
-                if (prev == dsf::EMPTY) { atomicAdd(&counters[0], 1ull); found = true; break; }
-                if (prev == k) { found = true; break; }
-                s = (s + 1) & mask;
-            }
-            if (found) {
-                if (plus[i]) atomicMax(&t_plus[s], row_base + (unsigned long long)i + 1ull);
-                atomicAdd(&counters[1], 1ull);
-                sk = (s << 32) | (unsigned long long)i;
-            } else {
-                atomicAdd(&counters[2], 1ull);
-            }
+            const ull s = dss::insert_row(t_key, mask, dss::make_key(chrom[i], pos[i]), i, counters, &sk);
+            if (s != dss::NO_SLOT && plus[i]) atomicMax(&t_plus[s], row_base + (ull)i + 1ull);
         }
     }
     sort[i] = sk;
 }
 
-// the lane that sees the first key of a site's run walks the run in row order
-__global__ __launch_bounds__(TPB) void combine_accumulate_kernel(int P, const unsigned long long* sorted, const double* a, const double* b,
-                                                                 const int64_t* c0, const int64_t* c1, const int64_t* c2, double* t_sum0,
-                                                                 double* t_sum1, int64_t* t_met, int64_t* t_unmet, int64_t* t_cov)
+__global__ __launch_bounds__(TPB) void combine_accumulate_kernel(int P, const ull* sorted, const double* a, const double* b, const int64_t* c0,
+                                                                 const int64_t* c1, const int64_t* c2, double* t_sum0, double* t_sum1, int64_t* t_met,
+                                                                 int64_t* t_unmet, int64_t* t_cov)
 {
     const int t = blockIdx.x * TPB + threadIdx.x;
-    if (t >= P) return;
-    const unsigned long long v = sorted[t];
-    if (v == SORT_PAD) return;
-    const unsigned long long site = v >> 32;
-    if (t > 0 && (sorted[t - 1] >> 32) == site) return;
+    ull site;
+    if (!dss::run_head(sorted, P, t, &site)) return;
     double x = t_sum0[site], y = t_sum1[site];
     int64_t m = t_met[site], u = t_unmet[site], c = t_cov[site];
-    for (int q = t; q < P; ++q) {
-        const unsigned long long w = sorted[q];
-        if (w == SORT_PAD || (w >> 32) != site) break;
-        const unsigned i = (unsigned)(w & 0xffffffffull);
+    dss::walk_run(sorted, P, t, site, [&](unsigned i) {
         x += a[i];
         y += b[i];
         m += c0[i]; u += c1[i]; c += c2[i];
-    }
+    });
     t_sum0[site] = x; t_sum1[site] = y; t_met[site] = m; t_unmet[site] = u; t_cov[site] = c;
 }
 
-__global__ __launch_bounds__(TPB) void combine_result_kernel(unsigned long long cap, const unsigned long long* t_key, const unsigned long long* t_plus,
-                                                             const double* t_sum0, const double* t_sum1, const int64_t* t_met, const int64_t* t_unmet,
-                                                             const int64_t* t_cov, unsigned long long* cursor, unsigned long long out_cap, int32_t* chrom,
-                                                             int64_t* pos, double* sum0, double* sum1, int64_t* met, int64_t* unmet, int64_t* cov,
-                                                             int64_t* last_plus)
+__global__ __launch_bounds__(TPB) void combine_result_kernel(ull cap, const ull* t_key, const ull* t_plus, const double* t_sum0, const double* t_sum1,
+                                                             const int64_t* t_met, const int64_t* t_unmet, const int64_t* t_cov, ull* cursor, ull out_cap,
+                                                             int32_t* chrom, int64_t* pos, double* sum0, double* sum1, int64_t* met, int64_t* unmet,
+                                                             int64_t* cov, int64_t* last_plus)
 {
-    const unsigned long long s = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
-    if (s >= cap) return;
-    const unsigned long long k = t_key[s];
-    if (k == dsf::EMPTY) return;
-    const unsigned long long o = atomicAdd(cursor, 1ull);
-    if (o >= out_cap) return;
-    chrom[o] = (int32_t)(k >> dsf::POS_BITS);
-    pos[o] = (int64_t)(k & (((unsigned long long)1 << dsf::POS_BITS) - 1));
+    const ull s = (ull)blockIdx.x * TPB + threadIdx.x;
+    ull o;
+    if (!dss::compact_slot(cap, t_key, s, cursor, out_cap, chrom, pos, &o)) return;
     sum0[o] = t_sum0[s]; sum1[o] = t_sum1[s]; met[o] = t_met[s]; unmet[o] = t_unmet[s]; cov[o] = t_cov[s];
     last_plus[o] = (int64_t)t_plus[s] - 1;
-}
-
-int blocks(uint64_t n) { return (int)((n + TPB - 1) / TPB); }
-
-int seterr(std::string* err, int code, const std::string& msg)
-{
-    if (err) *err = msg;
-    return code;
-}
-
-#define CQ(expr)                                                                                     \
-    do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            (void)hipGetLastError();                                                                 \
-            return seterr(err, e_ == hipErrorOutOfMemory ? DS_ERR_NOMEM : DS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-        }                                                                                            \
-    } while (0)
-
-void book(Combine* f, int slot, hipEvent_t a, hipEvent_t b)
-{
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) f->ms[slot] += ms; else (void)hipGetLastError();
 }
 
 // ascending, disjoint, inside [0, limit) and landing inside the bitmap; a carried base needs a base in front of it
@@ -193,75 +140,61 @@ bool segments_ok(int64_t nseg, const int64_t* sb, const int64_t* se, const int64
 
 int Combine::begin(int dev, int fm, int32_t nr, const int64_t* rec_len, int64_t total, int32_t batch, std::string* err)
 {
-    if (s) return seterr(err, DS_ERR_INVALID, "ds_combine_begin: a run is open on this handle (ds_combine_end first)");
+    if (run.s) return seterr(err, DS_ERR_INVALID, "ds_combine_begin: a run is open on this handle (ds_combine_end first)");
     if (fm != FORM_TABLE && fm != FORM_BED) return seterr(err, DS_ERR_INVALID, "ds_combine_begin: form must be DS_COMBINE_TABLE or DS_COMBINE_BED");
-    if (nr < 1 || nr > dsf::CHROM_LIMIT || !rec_len) return seterr(err, DS_ERR_INVALID, "ds_combine_begin: 1 .. 2^23 records");
-    if (total < 0 || total > dsf::MAX_TOTAL_ROWS) return seterr(err, DS_ERR_INVALID, "ds_combine_begin: total_rows must be in [0, 2^30]");
+    if (nr < 1 || nr > dss::CHROM_LIMIT || !rec_len) return seterr(err, DS_ERR_INVALID, "ds_combine_begin: 1 .. 2^23 records");
+    if (total < 0 || total > dss::MAX_TOTAL_ROWS) return seterr(err, DS_ERR_INVALID, "ds_combine_begin: total_rows must be in [0, 2^30]");
     if (batch < 1 || batch > (1 << 24)) return seterr(err, DS_ERR_INVALID, "ds_combine_begin: batch_rows must be in [1, 2^24]");
     std::vector<int64_t> base((size_t)nr);
     int64_t bits = 0;
     for (int32_t i = 0; i < nr; ++i) {
-        if (rec_len[i] < 0 || rec_len[i] > dsf::POS_LIMIT) return seterr(err, DS_ERR_INVALID, "ds_combine_begin: a record's length must be in [0, 2^40]");
+        if (rec_len[i] < 0 || rec_len[i] > dss::POS_LIMIT) return seterr(err, DS_ERR_INVALID, "ds_combine_begin: a record's length must be in [0, 2^40]");
         base[(size_t)i] = bits;
         bits += rec_len[i];
         if (bits > MAX_GENOME_BITS) return seterr(err, DS_ERR_NOMEM, "ds_combine_begin: a genome of more than 2^46 bases");
     }
-    device = dev; form = fm; nrec = nr; nbits = bits;
+    form = fm; nrec = nr; nbits = bits;
     h_len.assign(rec_len, rec_len + nr);
     total_rows = total; rows_done = 0; batch_rows = batch; pending = -1; rows_begun = false;
     batches = chunks = 0;
     for (double& v : ms) v = 0;
     cap = 64;
     while (cap < 2 * (uint64_t)total) cap <<= 1;
-    int P = 1;
-    while (P < batch) P <<= 1;
+    size_t P = 1;                 // the sort's keys: batch_rows rounded up to a power of two
+    while (P < (size_t)batch) P <<= 1;
     const size_t words = (size_t)((bits + 31) >> 5) + 1;
     const size_t B = (size_t)batch;
-    CQ(hipSetDevice(device));
-    CQ(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    for (hipEvent_t& e : ev) CQ(hipEventCreate(&e));
-    CQ(hipMalloc((void**)&bitmap, words * 4));
-    CQ(hipMalloc((void**)&d_rec_base, (size_t)nr * 8));
-    CQ(hipMalloc((void**)&d_rec_len, (size_t)nr * 8));
-    CQ(hipMalloc((void**)&t_key, cap * 8));
-    CQ(hipMalloc((void**)&t_plus, cap * 8));
-    CQ(hipMalloc((void**)&t_sum0, cap * 8));
-    CQ(hipMalloc((void**)&t_sum1, cap * 8));
-    CQ(hipMalloc((void**)&t_met, cap * 8));
-    CQ(hipMalloc((void**)&t_unmet, cap * 8));
-    CQ(hipMalloc((void**)&t_cov, cap * 8));
-    CQ(hipMalloc((void**)&counters, 8 * 8));
-    CQ(hipMalloc((void**)&d_off, B * 8));
-    CQ(hipMalloc((void**)&d_len, B * 4));
-    CQ(hipMalloc((void**)&d_chrom, B * 4));
-    CQ(hipMalloc((void**)&d_flags, B));
-    CQ(hipMalloc((void**)&d_status, B * 4));
-    CQ(hipMalloc((void**)&d_plus, B * 4));
-    CQ(hipMalloc((void**)&d_pos, B * 8));
-    CQ(hipMalloc((void**)&d_c0, B * 8));
-    CQ(hipMalloc((void**)&d_c1, B * 8));
-    CQ(hipMalloc((void**)&d_c2, B * 8));
-    CQ(hipMalloc((void**)&d_a, B * 8));
-    CQ(hipMalloc((void**)&d_b, B * 8));
-    CQ(hipMalloc((void**)&d_sort, (size_t)P * 8));
-    CQ(hipMemsetAsync(bitmap, 0, words * 4, s));
-    CQ(hipMemcpyAsync(d_rec_base, base.data(), (size_t)nr * 8, hipMemcpyHostToDevice, s));
-    CQ(hipMemcpyAsync(d_rec_len, h_len.data(), (size_t)nr * 8, hipMemcpyHostToDevice, s));
-    CQ(hipMemsetAsync(t_key, 0xff, cap * 8, s));
-    CQ(hipMemsetAsync(t_plus, 0, cap * 8, s));
-    CQ(hipMemsetAsync(t_sum0, 0, cap * 8, s));
-    CQ(hipMemsetAsync(t_sum1, 0, cap * 8, s));
-    CQ(hipMemsetAsync(t_met, 0, cap * 8, s));
-    CQ(hipMemsetAsync(t_unmet, 0, cap * 8, s));
-    CQ(hipMemsetAsync(t_cov, 0, cap * 8, s));
-    CQ(hipMemsetAsync(counters, 0, 8 * 8, s));
-    CQ(hipStreamSynchronize(s));      // also: `base` may go away now
+    DSS_TRY(run.open(dev));
+    hipStream_t s = run.s;
+    DSS_TRY(run.alloc(&bitmap, words * 4, 0));
+    DSS_TRY(run.alloc(&d_rec_base, (size_t)nr * 8));
+    DSS_TRY(run.alloc(&d_rec_len, (size_t)nr * 8));
+    DSS_TRY(run.alloc(&t_key, cap * 8, 0xff));
+    DSS_TRY(run.alloc(&t_plus, cap * 8, 0));
+    DSS_TRY(run.alloc(&t_sum0, cap * 8, 0));
+    DSS_TRY(run.alloc(&t_sum1, cap * 8, 0));
+    DSS_TRY(run.alloc(&t_met, cap * 8, 0));
+    DSS_TRY(run.alloc(&t_unmet, cap * 8, 0));
+    DSS_TRY(run.alloc(&t_cov, cap * 8, 0));
+    DSS_TRY(run.alloc(&counters, 8 * 8, 0));
+    DSS_TRY(rows.alloc(&run, B));
+    DSS_TRY(run.alloc(&d_plus, B * 4));
+    DSS_TRY(run.alloc(&d_pos, B * 8));
+    DSS_TRY(run.alloc(&d_c0, B * 8));
+    DSS_TRY(run.alloc(&d_c1, B * 8));
+    DSS_TRY(run.alloc(&d_c2, B * 8));
+    DSS_TRY(run.alloc(&d_a, B * 8));
+    DSS_TRY(run.alloc(&d_b, B * 8));
+    DSS_TRY(run.alloc(&d_sort, P * 8));
+    DSS_TRY(hipMemcpyAsync(d_rec_base, base.data(), (size_t)nr * 8, hipMemcpyHostToDevice, s));
+    DSS_TRY(hipMemcpyAsync(d_rec_len, h_len.data(), (size_t)nr * 8, hipMemcpyHostToDevice, s));
+    DSS_TRY(hipStreamSynchronize(s));      // also: `base` may go away now
     return DS_OK;
 }
 
 int Combine::genome(const char* text, int64_t nseg, const int64_t* sb, const int64_t* se, const int64_t* bit, const uint8_t* carry, std::string* err)
 {
-    if (!s) return seterr(err, DS_ERR_INVALID, "ds_combine_genome: no run is open (ds_combine_begin first)");
+    if (!run.s) return seterr(err, DS_ERR_INVALID, "ds_combine_genome: no run is open (ds_combine_begin first)");
     if (rows_begun) return seterr(err, DS_ERR_INVALID, "ds_combine_genome: the rows have begun; the genome comes first");
     if (!text || !sb || !se || !bit || !carry) return seterr(err, DS_ERR_INVALID, "ds_combine_genome: null argument");
     if (nseg < 1 || nseg > 0x7fffffff) return seterr(err, DS_ERR_INVALID, "ds_combine_genome: 1 .. 2^31 - 1 segments in a chunk");
@@ -273,98 +206,60 @@ int Combine::genome(const char* text, int64_t nseg, const int64_t* sb, const int
     const size_t N = (size_t)nseg;
     std::vector<int64_t> off(N), end(N);
     for (size_t i = 0; i < N; ++i) { off[i] = sb[i] - base; end[i] = se[i] - base; }
-    CQ(hipSetDevice(device));
-    if ((size_t)bytes > text_cap) {
-        if (d_text) { CQ(hipFree(d_text)); d_text = nullptr; text_cap = 0; }
-        const size_t want = (size_t)bytes + (size_t)bytes / 4 + 4096;
-        CQ(hipMalloc((void**)&d_text, want));
-        text_cap = want;
-    }
-    const size_t need = N * 25;
-    if (need > seg_cap) {
-        if (d_seg) { CQ(hipFree(d_seg)); d_seg = nullptr; seg_cap = 0; }
-        CQ(hipMalloc((void**)&d_seg, need + need / 4 + 4096));
-        seg_cap = need + need / 4 + 4096;
-    }
-    long long* g_off = reinterpret_cast<long long*>(d_seg);
+    hipStream_t s = run.s;
+    DSS_TRY(hipSetDevice(run.device));
+    DSS_TRY(rows.text.grow(&run, (size_t)bytes));
+    DSS_TRY(seg.grow(&run, N * 25));
+    long long* g_off = reinterpret_cast<long long*>(seg.p);
     long long* g_end = g_off + N;
     long long* g_bit = g_end + N;
     uint8_t* g_carry = reinterpret_cast<uint8_t*>(g_bit + N);
-    CQ(hipEventRecord(ev[0], s));
-    CQ(hipMemcpyAsync(d_text, text + base, (size_t)bytes, hipMemcpyHostToDevice, s));
-    CQ(hipMemcpyAsync(g_off, off.data(), N * 8, hipMemcpyHostToDevice, s));
-    CQ(hipMemcpyAsync(g_end, end.data(), N * 8, hipMemcpyHostToDevice, s));
-    CQ(hipMemcpyAsync(g_bit, bit, N * 8, hipMemcpyHostToDevice, s));
-    CQ(hipMemcpyAsync(g_carry, carry, N, hipMemcpyHostToDevice, s));
-    CQ(hipEventRecord(ev[1], s));
+    DSS_TRY(hipEventRecord(run.ev[0], s));
+    DSS_TRY(hipMemcpyAsync(rows.text.p, text + base, (size_t)bytes, hipMemcpyHostToDevice, s));
+    DSS_TRY(hipMemcpyAsync(g_off, off.data(), N * 8, hipMemcpyHostToDevice, s));
+    DSS_TRY(hipMemcpyAsync(g_end, end.data(), N * 8, hipMemcpyHostToDevice, s));
+    DSS_TRY(hipMemcpyAsync(g_bit, bit, N * 8, hipMemcpyHostToDevice, s));
+    DSS_TRY(hipMemcpyAsync(g_carry, carry, N, hipMemcpyHostToDevice, s));
+    DSS_TRY(hipEventRecord(run.ev[1], s));
     const uint64_t lanes = ((uint64_t)bytes + LANE_BYTES - 1) / LANE_BYTES;
-    hipLaunchKernelGGL(motif_bitmap_kernel, dim3(blocks(lanes)), dim3(TPB), 0, s, reinterpret_cast<const unsigned char*>(d_text), (long long)bytes,
+    hipLaunchKernelGGL(motif_bitmap_kernel, dim3(blocks(lanes)), dim3(TPB), 0, s, reinterpret_cast<const unsigned char*>(rows.text.p), (long long)bytes,
                        g_off, g_end, g_bit, g_carry, (int)nseg, bitmap, (long long)nbits);
-    CQ(hipGetLastError());
-    CQ(hipEventRecord(ev[2], s));
-    CQ(hipStreamSynchronize(s));      // also: off / end and the caller's arrays may go away now
-    book(this, 0, ev[0], ev[1]);
-    book(this, 1, ev[1], ev[2]);
+    DSS_TRY(hipGetLastError());
+    DSS_TRY(hipEventRecord(run.ev[2], s));
+    DSS_TRY(hipStreamSynchronize(s));      // also: off / end and the caller's arrays may go away now
+    dss::book(&ms[0], run.ev[0], run.ev[1]);
+    dss::book(&ms[1], run.ev[1], run.ev[2]);
     chunks += 1;
     return DS_OK;
 }
 
 int Combine::get_bitmap(int64_t cap_words, uint32_t* out, std::string* err)
 {
-    if (!s) return seterr(err, DS_ERR_INVALID, "ds_combine_bitmap: no run is open (ds_combine_begin first)");
+    if (!run.s) return seterr(err, DS_ERR_INVALID, "ds_combine_bitmap: no run is open (ds_combine_begin first)");
     const int64_t words = (nbits + 31) >> 5;
     if (cap_words < words || (words > 0 && !out)) return seterr(err, DS_ERR_INVALID, "ds_combine_bitmap: " + std::to_string(words) + " words, the array holds fewer");
-    CQ(hipSetDevice(device));
-    if (words) CQ(hipMemcpyAsync(out, bitmap, (size_t)words * 4, hipMemcpyDeviceToHost, s));
-    CQ(hipStreamSynchronize(s));
+    DSS_TRY(hipSetDevice(run.device));
+    if (words) DSS_TRY(hipMemcpyAsync(out, bitmap, (size_t)words * 4, hipMemcpyDeviceToHost, run.s));
+    DSS_TRY(hipStreamSynchronize(run.s));
     return DS_OK;
 }
 
 int Combine::parse(const char* text, int32_t n, const int64_t* rb, const int64_t* re, const int32_t* chrom, const uint8_t* flags, int32_t* status,
                    std::string* err)
 {
-    if (!s) return seterr(err, DS_ERR_INVALID, "ds_combine_parse: no run is open (ds_combine_begin first)");
+    if (!run.s) return seterr(err, DS_ERR_INVALID, "ds_combine_parse: no run is open (ds_combine_begin first)");
     if (pending >= 0) return seterr(err, DS_ERR_INVALID, "ds_combine_parse: the previous batch has not been accumulated");
     if (!text || !rb || !re || !chrom || !flags || !status) return seterr(err, DS_ERR_INVALID, "ds_combine_parse: null argument");
     if (n < 1 || n > batch_rows) return seterr(err, DS_ERR_INVALID, "ds_combine_parse: nrows must be in [1, batch_rows]");
     if (rows_done + n > total_rows) return seterr(err, DS_ERR_INVALID, "ds_combine_parse: more rows than ds_combine_begin was told of");
-    if (rb[0] < 0) return seterr(err, DS_ERR_INVALID, "ds_combine_parse: row 0 has a bad span");
-    std::vector<int64_t> off((size_t)n);
-    std::vector<int32_t> len((size_t)n);
-    const int64_t base = rb[0];
-    for (int i = 0; i < n; ++i) {
-        if (re[i] < rb[i] || (i > 0 && rb[i] < re[i - 1]) || re[i] - rb[i] > 0x7fffffff)
-            return seterr(err, DS_ERR_INVALID, "ds_combine_parse: row " + std::to_string(i) + " has a bad span (rows must be ascending and disjoint)");
-        off[(size_t)i] = rb[i] - base;
-        len[(size_t)i] = (int32_t)(re[i] - rb[i]);
-    }
-    const size_t bytes = (size_t)(re[n - 1] - base);
-    CQ(hipSetDevice(device));
-    if (bytes > text_cap) {
-        if (d_text) { CQ(hipFree(d_text)); d_text = nullptr; text_cap = 0; }
-        const size_t want = bytes + bytes / 4 + 4096;
-        CQ(hipMalloc((void**)&d_text, want));
-        text_cap = want;
-    }
+    int rc = rows.upload("ds_combine_parse", &run, text, n, rb, re, chrom, flags, err);
+    if (rc) return rc;
     rows_begun = true;
-    CQ(hipEventRecord(ev[0], s));
-    if (bytes) CQ(hipMemcpyAsync(d_text, text + base, bytes, hipMemcpyHostToDevice, s));
-    CQ(hipMemcpyAsync(d_off, off.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
-    CQ(hipMemcpyAsync(d_len, len.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-    CQ(hipMemcpyAsync(d_chrom, chrom, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    CQ(hipMemcpyAsync(d_flags, flags, (size_t)n, hipMemcpyHostToDevice, s));
-    CQ(hipEventRecord(ev[1], s));
-    const RowArrays r = {d_chrom, d_plus, d_status, d_pos, d_c0, d_c1, d_c2, d_a, d_b};
-    hipLaunchKernelGGL(combine_parse_kernel, dim3(blocks(n)), dim3(TPB), 0, s, form, d_text, d_off, d_len, d_flags, n, nrec, d_rec_base, d_rec_len,
-                       bitmap, r);
-    CQ(hipGetLastError());
-    CQ(hipEventRecord(ev[2], s));
-    CQ(hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    CQ(hipEventRecord(ev[3], s));
-    CQ(hipStreamSynchronize(s));      // also: off / len and the caller's arrays may go away now
-    book(this, 0, ev[0], ev[1]);
-    book(this, 2, ev[1], ev[2]);
-    book(this, 0, ev[2], ev[3]);
+    const RowArrays r = {rows.d_chrom, d_plus, rows.d_status, d_pos, d_c0, d_c1, d_c2, d_a, d_b};
+    hipLaunchKernelGGL(combine_parse_kernel, dim3(blocks(n)), dim3(TPB), 0, run.s, form, rows.text.p, rows.d_off, rows.d_len, rows.d_flags, n, nrec, d_rec_base,
+                       d_rec_len, bitmap, r);
+    rc = rows.finish(&run, n, status, &ms[0], &ms[2], err);
+    if (rc) return rc;
     pending = n;
     return DS_OK;
 }
@@ -372,149 +267,81 @@ int Combine::parse(const char* text, int32_t n, const int64_t* rb, const int64_t
 int Combine::accumulate(int32_t m, const int32_t* row, const int32_t* ostatus, const int32_t* chrom, const int64_t* pos, const int32_t* plus,
                         const double* a, const double* b, const int64_t* c0, const int64_t* c1, const int64_t* c2, std::string* err)
 {
-    if (!s) return seterr(err, DS_ERR_INVALID, "ds_combine_accumulate: no run is open (ds_combine_begin first)");
+    if (!run.s) return seterr(err, DS_ERR_INVALID, "ds_combine_accumulate: no run is open (ds_combine_begin first)");
     if (pending < 0) return seterr(err, DS_ERR_INVALID, "ds_combine_accumulate: no parsed batch (ds_combine_parse first)");
     const int n = pending;
     if (m < 0 || m > n) return seterr(err, DS_ERR_INVALID, "ds_combine_accumulate: nover must be in [0, rows of the batch]");
     if (m > 0 && (!row || !ostatus || !chrom || !pos || !plus || !a || !b || !c0 || !c1 || !c2))
         return seterr(err, DS_ERR_INVALID, "ds_combine_accumulate: null argument");
     for (int k = 0; k < m; ++k) {
-        if (row[k] < 0 || row[k] >= n || (k > 0 && row[k] <= row[k - 1]))
+        if (!dss::override_row_ok(row, k, n))
             return seterr(err, DS_ERR_INVALID, "ds_combine_accumulate: override rows must be ascending indices of the batch");
         if (ostatus[k] == ROW_SKIP) continue;
         if (ostatus[k] != ROW_OK || chrom[k] < 0 || chrom[k] >= nrec || pos[k] < 0 || pos[k] >= h_len[(size_t)chrom[k]] || !count_ok(c0[k]) ||
             !count_ok(c1[k]) || !count_ok(c2[k]))
             return seterr(err, DS_ERR_INVALID, "ds_combine_accumulate: override " + std::to_string(k) + " has a status, record, position or count outside its range");
     }
-    CQ(hipSetDevice(device));
-    const size_t M = (size_t)m;
-    // [pos | a | b | c0 | c1 | c2 | row | status | chrom | plus], eight-byte arrays first
-    const size_t need = M * (8 * 6 + 4 * 4);
-    if (need > over_cap) {
-        if (d_over) { CQ(hipFree(d_over)); d_over = nullptr; over_cap = 0; }
-        CQ(hipMalloc((void**)&d_over, need + 4096));
-        over_cap = need + 4096;
-    }
-    CQ(hipEventRecord(ev[0], s));
-    const RowArrays r = {d_chrom, d_plus, d_status, d_pos, d_c0, d_c1, d_c2, d_a, d_b};
+    const dss::Column in[10] = {dss::col(pos), dss::col(a), dss::col(b), dss::col(c0), dss::col(c1), dss::col(c2), dss::col(row), dss::col(ostatus),
+                                dss::col(chrom), dss::col(plus)};
+    dss::Columns o;
+    DSS_TRY(o.stage(&run, &over, (size_t)m, in, 10));
+    hipStream_t s = run.s;
     if (m > 0) {
-        int64_t* o_pos = reinterpret_cast<int64_t*>(d_over);
-        double* o_a = reinterpret_cast<double*>(d_over + M * 8);
-        double* o_b = reinterpret_cast<double*>(d_over + M * 16);
-        int64_t* o_c0 = reinterpret_cast<int64_t*>(d_over + M * 24);
-        int64_t* o_c1 = o_c0 + M;
-        int64_t* o_c2 = o_c1 + M;
-        int32_t* o_row = reinterpret_cast<int32_t*>(d_over + M * 48);
-        int32_t* o_status = o_row + M;
-        int32_t* o_chrom = o_status + M;
-        int32_t* o_plus = o_chrom + M;
-        CQ(hipMemcpyAsync(o_pos, pos, M * 8, hipMemcpyHostToDevice, s));
-        CQ(hipMemcpyAsync(o_a, a, M * 8, hipMemcpyHostToDevice, s));
-        CQ(hipMemcpyAsync(o_b, b, M * 8, hipMemcpyHostToDevice, s));
-        CQ(hipMemcpyAsync(o_c0, c0, M * 8, hipMemcpyHostToDevice, s));
-        CQ(hipMemcpyAsync(o_c1, c1, M * 8, hipMemcpyHostToDevice, s));
-        CQ(hipMemcpyAsync(o_c2, c2, M * 8, hipMemcpyHostToDevice, s));
-        CQ(hipMemcpyAsync(o_row, row, M * 4, hipMemcpyHostToDevice, s));
-        CQ(hipMemcpyAsync(o_status, ostatus, M * 4, hipMemcpyHostToDevice, s));
-        CQ(hipMemcpyAsync(o_chrom, chrom, M * 4, hipMemcpyHostToDevice, s));
-        CQ(hipMemcpyAsync(o_plus, plus, M * 4, hipMemcpyHostToDevice, s));
-        const RowArrays o = {o_chrom, o_plus, o_status, o_pos, o_c0, o_c1, o_c2, o_a, o_b};
-        hipLaunchKernelGGL(combine_override_kernel, dim3(blocks(M)), dim3(TPB), 0, s, m, o_row, o_status, o, r);
-        CQ(hipGetLastError());
+        const RowArrays r = {rows.d_chrom, d_plus, rows.d_status, d_pos, d_c0, d_c1, d_c2, d_a, d_b};
+        const RowArrays g = {o.at<int32_t>(8), o.at<int32_t>(9), o.at<int32_t>(7), o.at<int64_t>(0), o.at<int64_t>(3), o.at<int64_t>(4), o.at<int64_t>(5),
+                             o.at<double>(1), o.at<double>(2)};
+        hipLaunchKernelGGL(combine_override_kernel, dim3(blocks(m)), dim3(TPB), 0, s, m, o.at<int32_t>(6), o.at<int32_t>(7), g, r);
+        DSS_TRY(hipGetLastError());
     }
-    CQ(hipEventRecord(ev[1], s));
+    DSS_TRY(hipEventRecord(run.ev[1], s));
     int Pn = 1;                   // the network sorts the smallest power of two that holds the batch
     while (Pn < n) Pn <<= 1;
-    hipLaunchKernelGGL(combine_insert_kernel, dim3(blocks(Pn)), dim3(TPB), 0, s, n, Pn, (unsigned long long)rows_done, d_chrom, d_pos, d_plus, d_status,
-                       reinterpret_cast<unsigned long long*>(t_key), reinterpret_cast<unsigned long long*>(t_plus), (unsigned long long)(cap - 1),
-                       reinterpret_cast<unsigned long long*>(d_sort), counters);
-    CQ(hipGetLastError());
-    CQ(hipEventRecord(ev[2], s));
-    CQ(dsf::bitonic_sort(d_sort, Pn, s));
-    CQ(hipEventRecord(ev[3], s));
-    hipLaunchKernelGGL(combine_accumulate_kernel, dim3(blocks(Pn)), dim3(TPB), 0, s, Pn, reinterpret_cast<const unsigned long long*>(d_sort), d_a, d_b,
-                       d_c0, d_c1, d_c2, t_sum0, t_sum1, t_met, t_unmet, t_cov);
-    CQ(hipGetLastError());
-    CQ(hipEventRecord(ev[4], s));
-    unsigned long long c[4] = {0, 0, 0, 0};
-    CQ(hipMemcpyAsync(c, counters, sizeof(c), hipMemcpyDeviceToHost, s));
-    CQ(hipStreamSynchronize(s));
-    book(this, 0, ev[0], ev[1]);
-    book(this, 4, ev[1], ev[2]);
-    book(this, 3, ev[2], ev[3]);
-    book(this, 4, ev[3], ev[4]);
+    hipLaunchKernelGGL(combine_insert_kernel, dim3(blocks(Pn)), dim3(TPB), 0, s, n, Pn, (ull)rows_done, rows.d_chrom, d_pos, d_plus, rows.d_status, u64(t_key),
+                       u64(t_plus), (ull)(cap - 1), u64(d_sort), counters);
+    DSS_TRY(hipGetLastError());
+    DSS_TRY(hipEventRecord(run.ev[2], s));
+    DSS_TRY(dss::bitonic_sort(d_sort, Pn, s));
+    DSS_TRY(hipEventRecord(run.ev[3], s));
+    hipLaunchKernelGGL(combine_accumulate_kernel, dim3(blocks(Pn)), dim3(TPB), 0, s, Pn, u64(d_sort), d_a, d_b, d_c0, d_c1, d_c2, t_sum0, t_sum1, t_met,
+                       t_unmet, t_cov);
+    ull c[4] = {0, 0, 0, 0};
+    const int rc = dss::finish_batch(&run, counters, c, &ms[0], &ms[3], &ms[4], err);
+    if (rc) return rc;
     batches += 1;
     pending = -1;
     rows_done += n;
-    if (c[3]) return seterr(err, DS_ERR_INVALID, "ds_combine_accumulate: " + std::to_string(c[3]) + " row(s) of the batch were left to the caller and got no values");
-    if (c[2]) return seterr(err, DS_ERR_INVALID, "ds_combine_accumulate: the site table is full");
-    return DS_OK;
+    return dss::batch_verdict("ds_combine_accumulate", c, err);
 }
 
 int64_t Combine::result(int64_t cap_sites, int32_t* chrom, int64_t* pos, double* sum0, double* sum1, int64_t* met, int64_t* unmet, int64_t* cov,
-                        int64_t* last_plus, int64_t* rows, std::string* err)
+                        int64_t* last_plus, int64_t* nrows, std::string* err)
 {
-    if (!s) return seterr(err, DS_ERR_INVALID, "ds_combine_result: no run is open (ds_combine_begin first)");
+    if (!run.s) return seterr(err, DS_ERR_INVALID, "ds_combine_result: no run is open (ds_combine_begin first)");
     if (pending >= 0) return seterr(err, DS_ERR_INVALID, "ds_combine_result: a parsed batch has not been accumulated");
-    CQ(hipSetDevice(device));
-    unsigned long long c[4] = {0, 0, 0, 0};
-    CQ(hipMemcpy(c, counters, sizeof(c), hipMemcpyDeviceToHost));
+    DSS_TRY(hipSetDevice(run.device));
+    ull c[4] = {0, 0, 0, 0};
+    DSS_TRY(hipMemcpy(c, counters, sizeof(c), hipMemcpyDeviceToHost));
     const int64_t nsites = (int64_t)c[0];
-    if (rows) *rows = rows_done;
+    if (nrows) *nrows = rows_done;
     if (cap_sites == 0 && !chrom) return nsites;        // the size query
     if (!chrom || !pos || !sum0 || !sum1 || !met || !unmet || !cov || !last_plus) return seterr(err, DS_ERR_INVALID, "ds_combine_result: null argument");
     if (cap_sites < nsites) return seterr(err, DS_ERR_INVALID, "ds_combine_result: " + std::to_string(nsites) + " sites, the arrays hold fewer");
     if (nsites == 0) return 0;
-    const size_t N = (size_t)nsites;
-    char* d_out = nullptr;
-    CQ(hipMalloc((void**)&d_out, N * (8 * 7 + 4) + 8));
-    unsigned long long* cursor = reinterpret_cast<unsigned long long*>(d_out);
-    int64_t* o_pos = reinterpret_cast<int64_t*>(d_out + 8);
-    double* o_s0 = reinterpret_cast<double*>(o_pos + N);
-    double* o_s1 = o_s0 + N;
-    int64_t* o_met = reinterpret_cast<int64_t*>(o_s1 + N);
-    int64_t* o_unmet = o_met + N;
-    int64_t* o_cov = o_unmet + N;
-    int64_t* o_plus = o_cov + N;
-    int32_t* o_chrom = reinterpret_cast<int32_t*>(o_plus + N);
-    hipError_t e = hipMemsetAsync(cursor, 0, 8, s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(combine_result_kernel, dim3(blocks(cap)), dim3(TPB), 0, s, (unsigned long long)cap, reinterpret_cast<const unsigned long long*>(t_key),
-                           reinterpret_cast<const unsigned long long*>(t_plus), t_sum0, t_sum1, t_met, t_unmet, t_cov, cursor, (unsigned long long)nsites,
-                           o_chrom, o_pos, o_s0, o_s1, o_met, o_unmet, o_cov, o_plus);
-        e = hipGetLastError();
-    }
-    auto d2h = [&](void* dst, const void* src, size_t b) { return hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, s); };
-    if (e == hipSuccess) e = d2h(pos, o_pos, N * 8);
-    if (e == hipSuccess) e = d2h(sum0, o_s0, N * 8);
-    if (e == hipSuccess) e = d2h(sum1, o_s1, N * 8);
-    if (e == hipSuccess) e = d2h(met, o_met, N * 8);
-    if (e == hipSuccess) e = d2h(unmet, o_unmet, N * 8);
-    if (e == hipSuccess) e = d2h(cov, o_cov, N * 8);
-    if (e == hipSuccess) e = d2h(last_plus, o_plus, N * 8);
-    if (e == hipSuccess) e = d2h(chrom, o_chrom, N * 4);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) { (void)hipGetLastError(); return seterr(err, DS_ERR_HIP, std::string("ds_combine_result: ") + hipGetErrorString(e)); }
+    const dss::Column out[8] = {dss::col(pos), dss::col(sum0), dss::col(sum1), dss::col(met), dss::col(unmet), dss::col(cov), dss::col(last_plus),
+                                dss::col(chrom)};
+    dss::Columns o;
+    DSS_TRY(o.carve(&run, (size_t)nsites, out, 8));
+    hipLaunchKernelGGL(combine_result_kernel, dim3(blocks(cap)), dim3(TPB), 0, run.s, (ull)cap, u64(t_key), u64(t_plus), t_sum0, t_sum1, t_met, t_unmet, t_cov,
+                       o.cursor(), (ull)nsites, o.at<int32_t>(7), o.at<int64_t>(0), o.at<double>(1), o.at<double>(2), o.at<int64_t>(3), o.at<int64_t>(4),
+                       o.at<int64_t>(5), o.at<int64_t>(6));
+    const hipError_t e = o.fetch(&run, hipGetLastError(), (size_t)nsites, out, 8);
+    if (e != hipSuccess) return seterr(err, DS_ERR_HIP, std::string("ds_combine_result: ") + hipGetErrorString(e));
     return nsites;
 }
 
 void Combine::end()
 {
-    if (!s && !bitmap) return;
-    (void)hipSetDevice(device);
-    if (s) (void)hipStreamSynchronize(s);
-    void* ptrs[] = {bitmap, d_rec_base, d_rec_len, d_seg, t_key, t_plus, t_sum0, t_sum1, t_met, t_unmet, t_cov, counters, d_text, d_off, d_len, d_chrom,
-                    d_status, d_plus, d_flags, d_pos, d_c0, d_c1, d_c2, d_a, d_b, d_sort, d_over};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    bitmap = nullptr; d_rec_base = d_rec_len = nullptr; d_seg = nullptr; t_key = t_plus = nullptr; t_sum0 = t_sum1 = nullptr;
-    t_met = t_unmet = t_cov = nullptr; counters = nullptr; d_text = nullptr; d_off = nullptr; d_len = d_chrom = d_status = d_plus = nullptr;
-    d_flags = nullptr; d_pos = d_c0 = d_c1 = d_c2 = nullptr; d_a = d_b = nullptr; d_sort = nullptr; d_over = nullptr;
-    text_cap = over_cap = seg_cap = 0;
-    for (hipEvent_t& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    if (s) { (void)hipStreamDestroy(s); s = nullptr; }
-    (void)hipGetLastError();
-    pending = -1;
+    if (run.close()) pending = -1;
 }
 
 bool motif_reference(const char* text, int64_t nseg, const int64_t* sb, const int64_t* se, const int64_t* bit, const uint8_t* carry, int64_t nbits,
@@ -542,7 +369,7 @@ int64_t reference(int form, const char* text, int64_t nrows, const int64_t* begi
                   int64_t* met, int64_t* unmet, int64_t* cov, int64_t* last_plus, std::string* err)
 {
     if (nrows == 0) return 0;
-    if (nrows < 0 || (form != FORM_TABLE && form != FORM_BED) || !text || !begin || !end || !chrom || !flags || nrec < 1 || nrec > dsf::CHROM_LIMIT ||
+    if (nrows < 0 || (form != FORM_TABLE && form != FORM_BED) || !text || !begin || !end || !chrom || !flags || nrec < 1 || nrec > dss::CHROM_LIMIT ||
         !rec_len || !bitmap || !status || !pos || !plus || !a || !b || !c0 || !c1 || !c2 || cap < 0 ||
         (cap > 0 && (!site_chrom || !site_pos || !sum0 || !sum1 || !met || !unmet || !cov || !last_plus))) {
         seterr(err, -1, "ds_combine_reference: bad argument");
@@ -551,7 +378,7 @@ int64_t reference(int form, const char* text, int64_t nrows, const int64_t* begi
     std::vector<int64_t> base((size_t)nrec);
     int64_t bits = 0;
     for (int32_t i = 0; i < nrec; ++i) {
-        if (rec_len[i] < 0 || rec_len[i] > dsf::POS_LIMIT || bits + rec_len[i] > MAX_GENOME_BITS) {
+        if (rec_len[i] < 0 || rec_len[i] > dss::POS_LIMIT || bits + rec_len[i] > MAX_GENOME_BITS) {
             seterr(err, -1, "ds_combine_reference: a record's length is outside [0, 2^40], or more than 2^46 bases in all");
             return -1;
         }
@@ -579,7 +406,7 @@ int64_t reference(int form, const char* text, int64_t nrows, const int64_t* begi
             pos[r] = v.pos; plus[r] = v.plus; a[r] = v.a; b[r] = v.b; c0[r] = v.c0; c1[r] = v.c1; c2[r] = v.c2;
         }
         if (status[r] != ROW_OK || cap == 0) continue;
-        const uint64_t k = dsf::make_key(chrom[r], pos[r]);
+        const uint64_t k = dss::make_key(chrom[r], pos[r]);
         auto it = index.find(k);
         int64_t sidx;
         if (it == index.end()) {

@@ -210,6 +210,27 @@ def _text_args(text, begin, end):
     return text, text.ctypes.data, begin, end
 
 
+def _batch_rows_args(text, begin, end, chrom, flags, batch_rows: int):
+    """The arguments of freq_parse / combine_parse: (keep-alive object, address, begin, end, chrom, flags) of a batch's rows."""
+    keep, addr, begin, end = _text_args(text, begin, end)
+    chrom = np.ascontiguousarray(chrom, np.int32)
+    flags = np.ascontiguousarray(flags, np.uint8)
+    n = int(begin.size)
+    if chrom.shape != (n,) or flags.shape != (n,):
+        raise ValueError("chrom / flags must have one entry per row")
+    if not 1 <= n <= batch_rows:
+        raise ValueError("a batch holds 1 .. batch_rows rows of an open run")
+    if n > 1 and bool((begin[1:] < end[:-1]).any()):
+        raise ValueError("the rows of a batch must be ascending and disjoint")
+    return keep, addr, begin, end, chrom, flags
+
+
+def _check_override_rows(rows: np.ndarray, n: int) -> None:
+    """freq_accumulate / combine_accumulate: the caller's rows are ascending indices of a batch of n rows."""
+    if rows.size and (int(rows.min()) < 0 or int(rows.max()) >= n or bool((np.diff(rows) <= 0).any())):
+        raise ValueError("override rows must be ascending indices of the batch")
+
+
 def _text_arrays(n: int, kmer_len: int, signal_len: int):
     out = _feature_arrays(n, kmer_len, signal_len)
     out["lens"] = out.pop("sanums")
@@ -661,6 +682,26 @@ class Engine:
         if rc < 0:
             raise RuntimeError("%s failed (%d): %s" % (what, rc, self._lib.ds_last_error(self._h).decode()))
 
+    def _check_memory(self, rc: int, what: str) -> None:
+        """_check for the calls that allocate for a site-table run: DS_ERR_NOMEM is FreqNoMemory."""
+        if rc == -5:
+            raise FreqNoMemory(self._lib.ds_last_error(self._h).decode())
+        self._check(rc, what)
+
+    def _sites_result(self, fn, what: str, fields, *scalars) -> Dict[str, np.ndarray]:
+        """The two calls of ds_freq_result / ds_combine_result: the number of sites, then arrays of that size filled."""
+        nulls = (None,) * len(fields)
+        tail = [ctypes.byref(v) for v in scalars]
+        n = int(fn(self._h, 0, *nulls, *tail))
+        self._check(n, what)
+        out = {k: np.empty(n, dt) for k, dt in fields}
+        if n:
+            got = int(fn(self._h, n, *(out[k].ctypes.data for k, _ in fields), *tail))
+            self._check(got, what)
+            if got != n:
+                raise RuntimeError("%s: %d sites announced, %d returned" % (what, n, got))
+        return out
+
     # -- weights (Saver.restore, call_modifications.py:210-211) --------------------------------
     def load_weights_file(self, path: str) -> None:
         self._check(self._lib.ds_load_weights(self._h, path.encode()), "ds_load_weights")
@@ -844,9 +885,7 @@ class Engine:
         if prob_cf != prob_cf:
             raise ValueError("prob_cf must not be NaN")
         rc = self._lib.ds_freq_begin(self._h, total_rows, batch_rows, prob_cf)
-        if rc == -5:
-            raise FreqNoMemory(self._lib.ds_last_error(self._h).decode())
-        self._check(rc, "ds_freq_begin")
+        self._check_memory(rc, "ds_freq_begin")
         self._freq_batch, self._freq_pending = batch_rows, -1
 
     def freq_begin_stream(self, initial_slots: int, batch_rows: int, prob_cf: float = 0.0) -> None:
@@ -860,9 +899,7 @@ class Engine:
         if prob_cf != prob_cf:
             raise ValueError("prob_cf must not be NaN")
         rc = self._lib.ds_freq_begin_stream(self._h, initial_slots, batch_rows, prob_cf)
-        if rc == -5:
-            raise FreqNoMemory(self._lib.ds_last_error(self._h).decode())
-        self._check(rc, "ds_freq_begin_stream")
+        self._check_memory(rc, "ds_freq_begin_stream")
         self._freq_batch, self._freq_pending, self._freq_opened = batch_rows, -1, None
 
     def freq_push(self, chrom, pos, act, pred) -> np.ndarray:
@@ -880,9 +917,7 @@ class Engine:
         status, opened = np.empty(n, np.int32), np.zeros(n, np.int32)
         rc = self._lib.ds_freq_push(self._h, n, chrom.ctypes.data, pos.ctypes.data, act.ctypes.data, act.shape[1], pred.ctypes.data,
                                     status.ctypes.data, opened.ctypes.data)
-        if rc == -5:
-            raise FreqNoMemory(self._lib.ds_last_error(self._h).decode())
-        self._check(rc, "ds_freq_push")
+        self._check_memory(rc, "ds_freq_push")
         self._freq_pending, self._freq_opened = n, opened        # the library fills `opened` when the batch is accumulated
         return status
 
@@ -905,16 +940,8 @@ class Engine:
     def freq_parse(self, text, begin, end, chrom, flags) -> np.ndarray:
         """ds_freq_parse: one batch of rows (ascending spans of one buffer; chrom / flags per row as freq_locate gives them, the
         ids mapped to one numbering for the whole run) parsed on the GPU -> the per-row status (TEXT_ROW_OK / TEXT_ROW_HOST)."""
-        keep, addr, begin, end = _text_args(text, begin, end)
-        chrom = np.ascontiguousarray(chrom, np.int32)
-        flags = np.ascontiguousarray(flags, np.uint8)
+        keep, addr, begin, end, chrom, flags = _batch_rows_args(text, begin, end, chrom, flags, getattr(self, "_freq_batch", 0))
         n = int(begin.size)
-        if chrom.shape != (n,) or flags.shape != (n,):
-            raise ValueError("chrom / flags must have one entry per row")
-        if not 1 <= n <= getattr(self, "_freq_batch", 0):
-            raise ValueError("a batch holds 1 .. batch_rows rows of an open run")
-        if n > 1 and bool((begin[1:] < end[:-1]).any()):
-            raise ValueError("the rows of a batch must be ascending and disjoint")
         status = np.empty(n, np.int32)
         self._check(self._lib.ds_freq_parse(self._h, addr, n, begin.ctypes.data, end.ctypes.data, chrom.ctypes.data,
                                             flags.ctypes.data, status.ctypes.data), "ds_freq_parse")
@@ -934,8 +961,7 @@ class Engine:
         n = getattr(self, "_freq_pending", -1)
         if n < 0:
             raise ValueError("freq_accumulate needs a batch from freq_parse")
-        if m and (int(rows.min()) < 0 or int(rows.max()) >= n or bool((np.diff(rows) <= 0).any())):
-            raise ValueError("override rows must be ascending indices of the batch")
+        _check_override_rows(rows, n)
         if m and (int(chrom.min()) < 0 or int(chrom.max()) >= FREQ_CHROM_LIMIT or int(pos.min()) < 0 or int(pos.max()) >= FREQ_POS_LIMIT):
             raise ValueError("override chromosome ids / positions must fit the key (2^23 ids, pos < 2^40)")
         self._freq_pending = -1
@@ -950,15 +976,7 @@ class Engine:
         """ds_freq_result: the sites of the run so far, in no particular order -> first_row, chrom, pos, sum0, sum1, met, unmet
         arrays, and the scalars rows (accumulated) and used (rows that passed the threshold)."""
         rows, used = ctypes.c_int64(), ctypes.c_int64()
-        n = int(self._lib.ds_freq_result(self._h, 0, None, None, None, None, None, None, None, ctypes.byref(rows), ctypes.byref(used)))
-        self._check(n, "ds_freq_result")
-        out = {k: np.empty(n, dt) for k, dt in _FREQ_SITE_FIELDS}
-        if n:
-            got = int(self._lib.ds_freq_result(self._h, n, *(out[k].ctypes.data for k, _ in _FREQ_SITE_FIELDS), ctypes.byref(rows),
-                                               ctypes.byref(used)))
-            self._check(got, "ds_freq_result")
-            if got != n:
-                raise RuntimeError("ds_freq_result: %d sites announced, %d returned" % (n, got))
+        out = self._sites_result(self._lib.ds_freq_result, "ds_freq_result", _FREQ_SITE_FIELDS, rows, used)
         out.update(rows=int(rows.value), used=int(used.value))
         return out
 
@@ -990,9 +1008,7 @@ class Engine:
         if not 1 <= batch_rows <= FREQ_MAX_BATCH:
             raise ValueError("batch_rows must be in [1, 2^24]")
         rc = self._lib.ds_combine_begin(self._h, form, rec_len.size, rec_len.ctypes.data, total_rows, batch_rows)
-        if rc == -5:
-            raise FreqNoMemory(self._lib.ds_last_error(self._h).decode())
-        self._check(rc, "ds_combine_begin")
+        self._check_memory(rc, "ds_combine_begin")
         self._combine_batch, self._combine_pending, self._combine_words = batch_rows, -1, (int(rec_len.sum()) + 31) // 32
 
     def combine_genome(self, text, seg_begin, seg_end, seg_bit, seg_carry) -> None:
@@ -1003,9 +1019,7 @@ class Engine:
             raise ValueError("a chunk holds at least one segment")
         rc = self._lib.ds_combine_genome(self._h, addr, seg_begin.size, seg_begin.ctypes.data, seg_end.ctypes.data, seg_bit.ctypes.data,
                                          seg_carry.ctypes.data)
-        if rc == -5:
-            raise FreqNoMemory(self._lib.ds_last_error(self._h).decode())
-        self._check(rc, "ds_combine_genome")
+        self._check_memory(rc, "ds_combine_genome")
 
     def combine_bitmap(self) -> np.ndarray:
         """ds_combine_bitmap: the run's bitmap, uint32[(bases + 31) // 32]; what motif_reference gives on the CPU."""
@@ -1016,16 +1030,8 @@ class Engine:
     def combine_parse(self, text, begin, end, chrom, flags) -> np.ndarray:
         """ds_combine_parse: one batch of rows (ascending spans of one buffer; chrom = the record column 0 names, -1 for none; flags
         as freq_locate gives them) -> the per-row status (TEXT_ROW_OK / TEXT_ROW_HOST / COMBINE_ROW_SKIP)."""
-        keep, addr, begin, end = _text_args(text, begin, end)
-        chrom = np.ascontiguousarray(chrom, np.int32)
-        flags = np.ascontiguousarray(flags, np.uint8)
+        keep, addr, begin, end, chrom, flags = _batch_rows_args(text, begin, end, chrom, flags, getattr(self, "_combine_batch", 0))
         n = int(begin.size)
-        if chrom.shape != (n,) or flags.shape != (n,):
-            raise ValueError("chrom / flags must have one entry per row")
-        if not 1 <= n <= getattr(self, "_combine_batch", 0):
-            raise ValueError("a batch holds 1 .. batch_rows rows of an open run")
-        if n > 1 and bool((begin[1:] < end[:-1]).any()):
-            raise ValueError("the rows of a batch must be ascending and disjoint")
         status = np.empty(n, np.int32)
         self._check(self._lib.ds_combine_parse(self._h, addr, n, begin.ctypes.data, end.ctypes.data, chrom.ctypes.data, flags.ctypes.data,
                                                status.ctypes.data), "ds_combine_parse")
@@ -1042,8 +1048,7 @@ class Engine:
         n = getattr(self, "_combine_pending", -1)
         if n < 0:
             raise ValueError("combine_accumulate needs a batch from combine_parse")
-        if m and (int(rows.min()) < 0 or int(rows.max()) >= n or bool((np.diff(rows) <= 0).any())):
-            raise ValueError("override rows must be ascending indices of the batch")
+        _check_override_rows(rows, n)
         status = np.array([COMBINE_ROW_SKIP if v is None else TEXT_ROW_OK for v in given], np.int32)
         vals = [(0, 0, 0, 0.0, 0.0, 0, 0, 0) if v is None else v for v in given]
         if any(abs(int(c)) >= COMBINE_COUNT_LIMIT for v in vals for c in v[5:8]):
@@ -1058,14 +1063,7 @@ class Engine:
         """ds_combine_result: the sites of the run so far, in no particular order -> chrom, pos, sum0, sum1, met, unmet, cov,
         last_plus arrays, and the scalar rows (accumulated)."""
         rows = ctypes.c_int64()
-        n = int(self._lib.ds_combine_result(self._h, 0, None, None, None, None, None, None, None, None, ctypes.byref(rows)))
-        self._check(n, "ds_combine_result")
-        out = {k: np.empty(n, dt) for k, dt in _COMBINE_SITE_FIELDS}
-        if n:
-            got = int(self._lib.ds_combine_result(self._h, n, *(out[k].ctypes.data for k, _ in _COMBINE_SITE_FIELDS), ctypes.byref(rows)))
-            self._check(got, "ds_combine_result")
-            if got != n:
-                raise RuntimeError("ds_combine_result: %d sites announced, %d returned" % (n, got))
+        out = self._sites_result(self._lib.ds_combine_result, "ds_combine_result", _COMBINE_SITE_FIELDS, rows)
         out.update(rows=int(rows.value))
         return out
 

@@ -564,7 +564,7 @@ int ds_get_freq_stream_times(ds_handle *h, int32_t reset, int64_t *growths, doub
  * column. Bed: coverage (column 9) and met = percent (column 10) / 100 * coverage, two IEEE operations.
  * ds_combine_accumulate first takes the caller's word on every DS_TEXT_ROW_HOST row (ascending batch row indices; status
  * DS_TEXT_ROW_OK with record, pos inside it, plus, the two doubles and three counts below 2^32 in magnitude, or
- * DS_COMBINE_ROW_SKIP), then inserts the OK rows' keys record << 40 | pos (the exact-key atomicCAS probe of ds_freq_accumulate),
+ * DS_COMBINE_ROW_SKIP), then inserts the OK rows' keys record << 40 | pos (the exact-key atomicCAS probe of ds_freq_accumulate: one site table, csrc/ds_site_table.h),
  * sorts (site, row) and adds each site's run IN ROW ORDER to two double sums and three 64-bit counts; the greatest '+' row of a
  * site is kept (its k-mer is the site's). ds_combine_result: as ds_freq_result; per site record, pos, the sums and last_plus (a
  * global row number, -1: no '+' row). ds_combine_end closes the run (ds_destroy does too). Every call blocks.

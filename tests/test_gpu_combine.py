@@ -150,6 +150,30 @@ def test_sums_follow_the_row_order(engine, tmp_path):
         assert got["met"].tolist() == [3000] and got["cov"].tolist() == [9000] and got["last_plus"].tolist() == [2998]
 
 
+def test_run_heads_on_workgroup_edges(engine, tmp_path):
+    """Three CGs of 256 rows each, interleaved in file order, '+' and '-' rows mixed: whatever order the hash gives the sites, their
+    runs begin on sorted lanes 0, 256 and 512, the first lanes of three workgroups, with 256 pad keys behind. Then in batches of 256,
+    where every run goes on from the sums the batch before it stored."""
+    rng = np.random.default_rng(11)
+    vals = ["%.3f" % x for x in 10.0 ** rng.uniform(-3, 3, 768)]
+    differs = False
+    for site in range(3):
+        fwd = rev = 0.0
+        for v in vals[site::3]:
+            fwd += float(v)
+        for v in reversed(vals[site::3]):
+            rev += float(v)
+        differs = differs or bits(fwd) != bits(rev)
+    assert differs                             # otherwise the input proves nothing
+    g = genome_of(tmp_path, b">c1\nACGACGACGT\n")
+    rows = [table_row("c1", 1 + 3 * (i % 3) + (i // 3) % 2, "+-"[(i // 3) % 2], v, "0.5", i, 2, 3, kmer="K%d" % i) for i, v in enumerate(vals)]
+    for batch in (768, 256):
+        status, got, ref_status, ref = device_sites(engine, eng.COMBINE_TABLE, g, rows, batch)
+        assert status == ref_status == [OK] * 768
+        assert_sites_equal(got, ref)
+        assert got["pos"].tolist() == [1, 4, 7] and got["cov"].tolist() == [768] * 3 and got["last_plus"].tolist() == [762, 763, 764]
+
+
 def test_keys_at_the_edges(engine, tmp_path):
     """A '-' row at position 0, positions len - 1, len and 2^40, an unknown chromosome, coverage 0, a site with '-' rows only."""
     g = genome_of(tmp_path, b">c1\nCGACG\n>c2\nCG\n")

@@ -109,6 +109,30 @@ def test_sums_follow_the_row_order(engine):
         assert got["met"].tolist() == [3000]
 
 
+def test_run_heads_on_workgroup_edges(engine):
+    """Three sites of 256 rows each, interleaved in file order: whatever order the hash gives the sites, their runs begin on sorted
+    lanes 0, 256 and 512, the first lanes of three workgroups, with 256 pad keys behind (768 rows sort as 1,024 keys). Then in
+    batches of 256, where every run goes on from the sums the batch before it stored."""
+    rng = np.random.default_rng(11)
+    p = np.float32(10.0 ** rng.uniform(-7, 0, 768))
+    differs = False
+    for site in range(3):
+        vals = [float(str(x)) for x in p[site::3]]
+        fwd = rev = 0.0
+        for v in vals:
+            fwd += v
+        for v in reversed(vals):
+            rev += v
+        differs = differs or bits(fwd) != bits(rev)
+    assert differs                             # otherwise the input proves nothing
+    rows = [call_row("chr1", 100 + i % 3, str(x), "0.0", label=i % 2) for i, x in enumerate(p)]
+    text = ("\n".join(rows) + "\n").encode()
+    for batch in (768, 256):
+        got, ref = device_sites(engine, text, batch)
+        assert_sites_equal(got, ref)
+        assert got["first_row"].tolist() == [0, 1, 2] and (got["met"] + got["unmet"]).tolist() == [256] * 3
+
+
 def test_table_at_its_load_cap(engine):
     pos = [0, (1 << 40) - 1] + list(range(1, 2047))
     rows = [call_row("chr%d" % (i % 3), q, 0.25, 0.75, pis=1) for i, q in enumerate(pos)]

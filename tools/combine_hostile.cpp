@@ -3,7 +3,7 @@
 // buffer is copied into a heap block of exactly its size, so a read past either end is a report. Build and run (host code only;
 // nothing here touches a GPU):
 //   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -ffp-contract=off -Xarch_host -fsanitize=address,undefined -x hip tools/combine_hostile.cpp \
-//         deepsignal_amd/csrc/ds_combine.hip deepsignal_amd/csrc/ds_freq.hip deepsignal_amd/csrc/ds_io.cpp -o combine_hostile && ./combine_hostile
+//         deepsignal_amd/csrc/ds_combine.hip deepsignal_amd/csrc/ds_site_table.hip deepsignal_amd/csrc/ds_io.cpp -o combine_hostile && ./combine_hostile
 #include "../include/deepsignal_hip.h"
 #include "../deepsignal_amd/csrc/ds_combine.h"
 
@@ -72,7 +72,7 @@ static int run(const std::string& fasta, const std::string& table, int form, int
     for (int64_t i = 0; i < n; ++i)
         if (chrom[(size_t)i] >= 0) chrom[(size_t)i] = chrom[(size_t)i] % (int32_t)(nrec < 1000 ? nrec : 1000) - (i % 7 == 0);      // now and then -1: no record
     int64_t sites = 0;
-    if (!bad && nrec <= dsf::CHROM_LIMIT)
+    if (!bad && nrec <= dss::CHROM_LIMIT)
         sites = dsc::reference(form, ttext ? ttext : "", n, b.data(), e.data(), chrom.data(), flags.data(), (int32_t)nrec, len.data(), bitmap.data(), status.data(),
                                pos.data(), plus.data(), a.data(), bb.data(), c0.data(), c1.data(), c2.data(), n, schrom.data(), spos.data(), s0.data(),
                                s1.data(), smet.data(), sunmet.data(), scov.data(), slast.data(), &err);

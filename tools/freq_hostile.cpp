@@ -3,7 +3,8 @@
 // buffers, as a stand-alone program for a host sanitizer build. Every buffer is copied into a heap block of exactly its size, so a
 // read past either end is a report. Build and run (host code only; nothing here touches a GPU):
 //   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
-//         -x hip tools/freq_hostile.cpp deepsignal_amd/csrc/ds_freq.hip deepsignal_amd/csrc/ds_io.cpp -o freq_hostile && ./freq_hostile
+//         -x hip tools/freq_hostile.cpp deepsignal_amd/csrc/ds_freq.hip deepsignal_amd/csrc/ds_site_table.hip deepsignal_amd/csrc/ds_io.cpp \
+//         -o freq_hostile && ./freq_hostile
 #include "../include/deepsignal_hip.h"
 #include "../deepsignal_amd/csrc/ds_freq.h"
 
@@ -76,7 +77,7 @@ static int run_keys(const std::string& data, const char* what)
         char* names = static_cast<char*>(malloc(nb ? (size_t)nb : 1));
         if (ds_freq_keys(n, buf, off.data(), chrom.data(), pos.data(), flags.data(), names, nb, &nb, &nn) != n) bad = 1;
         for (int64_t i = 0; i < n; ++i) {
-            if (flags[(size_t)i] ? chrom[(size_t)i] != -1 : !dsf::key_ok(chrom[(size_t)i], pos[(size_t)i]) || chrom[(size_t)i] >= nn) bad = 1;
+            if (flags[(size_t)i] ? chrom[(size_t)i] != -1 : !dss::key_ok(chrom[(size_t)i], pos[(size_t)i]) || chrom[(size_t)i] >= nn) bad = 1;
             if (!round) flagged += flags[(size_t)i];
         }
         free(names);
@@ -84,6 +85,34 @@ static int run_keys(const std::string& data, const char* what)
     }
     printf("%-28s keys: %4zu strings %4lld flagged%s\n", what, pieces.size(), flagged, bad ? "  BAD" : "");
     return bad;
+}
+
+// dss::row_spans, the span check of ds_freq_parse / ds_combine_parse: heap blocks of exactly n entries; the first bad row, or none
+static int run_spans()
+{
+    struct Case { std::vector<int64_t> b, e; int bad; };
+    const int64_t big = (int64_t)1 << 31;
+    const Case cases[] = {{{0}, {0}, -1}, {{5, 9, 9}, {9, 9, 20}, -1}, {{0, 4}, {5, 8}, 1}, {{3, 2}, {3, 2}, 1}, {{7}, {6}, 0}, {{0, 10}, {10, 10 + big}, 1},
+                          {{0, 10}, {10, 9 + big}, -1}, {{INT64_MAX - 1, INT64_MAX}, {INT64_MAX, INT64_MAX}, -1}, {{0, 1, 2, 3}, {1, 2, 3, 2}, 3}};
+    int wrong = 0;
+    for (const Case& c : cases) {
+        const int32_t n = (int32_t)c.b.size();
+        int64_t* b = static_cast<int64_t*>(malloc((size_t)n * 8));
+        int64_t* e = static_cast<int64_t*>(malloc((size_t)n * 8));
+        memcpy(b, c.b.data(), (size_t)n * 8);
+        memcpy(e, c.e.data(), (size_t)n * 8);
+        std::vector<int64_t> off;
+        std::vector<int32_t> len;
+        int bad = -1;
+        const bool ok = dss::row_spans(n, b, e, &off, &len, &bad);
+        if (ok != (c.bad < 0) || (!ok && bad != c.bad)) wrong = 1;
+        for (int32_t i = 0; ok && i < n; ++i)
+            if (off[(size_t)i] != c.b[(size_t)i] - c.b[0] || len[(size_t)i] != c.e[(size_t)i] - c.b[(size_t)i]) wrong = 1;
+        free(b);
+        free(e);
+    }
+    printf("%-28s %4zu cases%s\n", "row spans", sizeof(cases) / sizeof(cases[0]), wrong ? "  BAD" : "");
+    return wrong;
 }
 
 // dsf::call_value over the float32 patterns where its exponent arithmetic and table indices sit at their ends
@@ -142,6 +171,7 @@ int main()
     bad += run_keys(good, "one row");
     for (size_t cut = 1; cut < all.size(); cut += 37) bad += run_keys(all.substr(0, cut), "truncated hostile");
     bad += run_values();
+    bad += run_spans();
     printf(bad ? "FAILED\n" : "all buffers done\n");
     return bad ? 1 : 0;
 }
