@@ -8,6 +8,7 @@
 #include "ds_tsv_device.h"
 #include "ds_freq.h"
 #include "ds_combine.h"
+#include "ds_eval.h"
 
 #include <algorithm>
 #include <cmath>
@@ -270,6 +271,8 @@ struct ds_handle {
     dsc::Combine* combine = nullptr;      // combine_strands --on gpu: the open run (ds_combine_begin .. ds_combine_end); bitmap, table and buffers are its own
     Times<5> cb_t;        // genome chunks and batches of the combine runs ended so far (the open run's are added on top)
     int64_t cb_chunks = 0;
+    dse::Eval* eval = nullptr;            // evaluate --on gpu: the open run (ds_eval_begin .. ds_eval_end); table, counters and buffers are its own
+    Times<4> ev_t;        // batches of the evaluate runs ended so far (the open run's are added on top)
     // pipelining: consecutive forwards rotate over independent slots (own workspace, streams, graphs), so the
     // dependency chain of one 512-site forward overlaps the next ones'; weights are shared
     std::vector<Slot> slots;
@@ -1631,6 +1634,7 @@ void ds_destroy(ds_handle* h)
     }
     delete h->freq;
     delete h->combine;
+    delete h->eval;
     for (void* p : h->allocs) hipFree(p);
     (void)hipGetLastError();      // nothing a teardown call returned may surface in a later handle's first launch
     delete h;
@@ -2714,6 +2718,85 @@ int ds_get_combine_times(ds_handle* h, int32_t reset, int64_t* chunks, int64_t* 
     return DS_OK;
 }
 
+// ---- call accuracy and AUROC of labelled call rows on the device (ds_eval.hip; evaluate --on gpu) ----------------------------------
+// The run's state is a dse::Eval of its own (score table, counters, row buffers, stream): no pipeline slot, no weights.
+static void eval_close(ds_handle* h)
+{
+    if (!h->eval) return;
+    h->ev_t.batches += h->eval->batches;
+    for (int i = 0; i < 4; ++i) h->ev_t.ms[i] += h->eval->ms[i];
+    delete h->eval;
+    h->eval = nullptr;
+}
+
+static int ds_eval_begin_impl(ds_handle* h, int64_t total_rows, int32_t batch_rows, int32_t ncf, const double* cf)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (h->eval) return fail(h, DS_ERR_INVALID, "ds_eval_begin: a run is open on this handle (ds_eval_end first)");
+    h->eval = new dse::Eval();
+    std::string err;
+    const int rc = h->eval->begin(h->cfg.device, total_rows, batch_rows, ncf, cf, &err);
+    if (rc) { delete h->eval; h->eval = nullptr; return fail(h, rc, err); }
+    return DS_OK;
+}
+
+static int ds_eval_parse_impl(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, const uint8_t* flags, int32_t* status)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (!h->eval) return fail(h, DS_ERR_INVALID, "ds_eval_parse: no run is open (ds_eval_begin first)");
+    std::string err;
+    const int rc = h->eval->parse(text, nrows, begin, end, flags, status, &err);
+    return rc ? fail(h, rc, err) : DS_OK;
+}
+
+static int ds_eval_accumulate_impl(ds_handle* h, const uint8_t* mask, int32_t nover, const int32_t* row, const double* p0, const double* p1,
+                                   const int32_t* called)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (!h->eval) return fail(h, DS_ERR_INVALID, "ds_eval_accumulate: no run is open (ds_eval_begin first)");
+    std::string err;
+    const int rc = h->eval->accumulate(mask, nover, row, p0, p1, called, &err);
+    return rc ? fail(h, rc, err) : DS_OK;
+}
+
+static int ds_eval_result_impl(ds_handle* h, int64_t* counts, uint64_t* u2, int64_t* pn, int64_t* nn, int64_t* rows, int64_t* distinct)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (!h->eval) return fail(h, DS_ERR_INVALID, "ds_eval_result: no run is open (ds_eval_begin first)");
+    std::string err;
+    const int rc = h->eval->result(counts, u2, pn, nn, rows, distinct, &err);
+    return rc ? fail(h, rc, err) : DS_OK;
+}
+
+int ds_eval_end(ds_handle* h)
+{
+    if (!h) return DS_ERR_INVALID;
+    eval_close(h);
+    return DS_OK;
+}
+
+int ds_eval_reference(const char* text, int64_t nrows, const int64_t* begin, const int64_t* end, const uint8_t* flags, const uint8_t* mask, int32_t ncf,
+                      const double* cf, int32_t* status, double* p0, double* p1, int32_t* called, int64_t* counts, uint64_t* u2, int64_t* pn, int64_t* nn)
+{
+    return guarded(nullptr, [&]() -> int {
+        std::string err;
+        return dse::reference(text, nrows, begin, end, flags, mask, ncf, cf, status, p0, p1, called, counts, u2, pn, nn, &err) ? DS_OK
+                                                                                                                               : fail(nullptr, DS_ERR_INVALID, err);
+    });
+}
+
+int ds_get_eval_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms)
+{
+    if (!h || !batches || !ms) return DS_ERR_INVALID;
+    *batches = h->ev_t.batches + (h->eval ? h->eval->batches : 0);
+    for (int i = 0; i < 4; ++i) ms[i] = h->ev_t.ms[i] + (h->eval ? h->eval->ms[i] : 0.0);
+    if (reset) {
+        h->ev_t = Times<4>();
+        if (h->eval) { h->eval->batches = 0; for (double& v : h->eval->ms) v = 0; }
+    }
+    return DS_OK;
+}
+
 // ---- feature rows: float64 values and their text on the device (ds_extract.hip rows_*_kernel) ---------------------------------
 // Needs no weights: the slot's streams and the blocks below are all it uses. The rows path enqueues, on sl.s0: H2D of the packed
 // reads and of info / info_off, the statistics, values, length, scan and format kernels, D2H of the row offsets.
@@ -3192,6 +3275,10 @@ int ds_freq_begin(ds_handle* h, int64_t total_rows, int32_t batch_rows, double p
 int ds_freq_parse(ds_handle* h, const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, const int32_t* chrom, const uint8_t* flags, int32_t* status) { return guarded(h, [&] { return ds_freq_parse_impl(h, text, nrows, row_begin, row_end, chrom, flags, status); }); }
 int ds_freq_accumulate(ds_handle* h, int32_t nover, const int32_t* row, const int32_t* chrom, const int64_t* pos, const double* p0, const double* p1, const int32_t* met) { return guarded(h, [&] { return ds_freq_accumulate_impl(h, nover, row, chrom, pos, p0, p1, met); }); }
 int64_t ds_freq_result(ds_handle* h, int64_t cap, int64_t* first_row, int32_t* chrom, int64_t* pos, double* sum0, double* sum1, int32_t* met, int32_t* unmet, int64_t* rows, int64_t* used) { return guarded(h, [&] { return ds_freq_result_impl(h, cap, first_row, chrom, pos, sum0, sum1, met, unmet, rows, used); }); }
+int ds_eval_begin(ds_handle* h, int64_t total_rows, int32_t batch_rows, int32_t ncf, const double* cf) { return guarded(h, [&] { return ds_eval_begin_impl(h, total_rows, batch_rows, ncf, cf); }); }
+int ds_eval_parse(ds_handle* h, const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, const uint8_t* flags, int32_t* status) { return guarded(h, [&] { return ds_eval_parse_impl(h, text, nrows, row_begin, row_end, flags, status); }); }
+int ds_eval_accumulate(ds_handle* h, const uint8_t* mask, int32_t nover, const int32_t* row, const double* p0, const double* p1, const int32_t* called) { return guarded(h, [&] { return ds_eval_accumulate_impl(h, mask, nover, row, p0, p1, called); }); }
+int ds_eval_result(ds_handle* h, int64_t* counts, uint64_t* u2, int64_t* pn, int64_t* nn, int64_t* rows, int64_t* distinct) { return guarded(h, [&] { return ds_eval_result_impl(h, counts, u2, pn, nn, rows, distinct); }); }
 int ds_combine_begin(ds_handle* h, int32_t form, int32_t nrec, const int64_t* rec_len, int64_t total_rows, int32_t batch_rows) { return guarded(h, [&] { return ds_combine_begin_impl(h, form, nrec, rec_len, total_rows, batch_rows); }); }
 int ds_combine_genome(ds_handle* h, const char* text, int64_t nseg, const int64_t* seg_begin, const int64_t* seg_end, const int64_t* seg_bit, const uint8_t* seg_carry) { return guarded(h, [&] { return ds_combine_genome_impl(h, text, nseg, seg_begin, seg_end, seg_bit, seg_carry); }); }
 int ds_combine_bitmap(ds_handle* h, int64_t cap_words, uint32_t* bitmap) { return guarded(h, [&] { return ds_combine_bitmap_impl(h, cap_words, bitmap); }); }

@@ -906,4 +906,39 @@ int64_t ds_fasta_locate(const char* text, int64_t nbytes, int64_t cap_lines, int
     return nlines;
 }
 
+// The host half of evaluate --on gpu (ds_eval.hip): the rows of a call_mods result buffer -- what lies between two '\n'; a last row
+// needs none -- for a reader that cuts a row with line.rstrip().split(). Flag 1: Python would tokenise or decode the row differently
+// from "fields separated by runs of space or tab" -- a byte >= 0x80, one of the other bytes str.split() takes for whitespace ('\r',
+// 0x0b, 0x0c, 0x1c .. 0x1f), or a blank row. Blanks in front and behind are plain. *file_flags bit 0: the buffer holds a '\r' that
+// neither a '\n' nor the end of the buffer follows -- a line end of its own in Python's text mode, which these rows do not show.
+int64_t ds_eval_locate(const char* text, int64_t nbytes, int64_t cap_rows, int64_t* row_begin, int64_t* row_end, uint8_t* flags, int32_t* file_flags)
+{
+    if (nbytes < 0 || (nbytes > 0 && !text) || cap_rows < 0 || !file_flags || (cap_rows > 0 && (!row_begin || !row_end || !flags))) return DS_ERR_INVALID;
+    int64_t nrows = 0;
+    int32_t ff = 0;
+    const char* p = text;
+    const char* const end = text + nbytes;
+    while (p < end) {
+        const char* nl = static_cast<const char*>(memchr(p, '\n', (size_t)(end - p)));
+        const char* e = nl ? nl : end;
+        bool host = false, any = false;
+        for (const char* q = p; q < e; ++q) {
+            const unsigned char c = (unsigned char)*q;
+            if (c >= 0x80 || c == '\r' || c == 0x0b || c == 0x0c || (c >= 0x1c && c <= 0x1f)) host = true;
+            if (c == '\r' && q + 1 < e) ff |= DS_EVAL_BARE_CR;           // behind the last '\r' of a row comes its '\n', or the end of the buffer
+            if (c != ' ' && c != '\t') any = true;
+        }
+        if (!any) host = true;
+        if (nrows < cap_rows) {
+            row_begin[nrows] = (int64_t)(p - text);
+            row_end[nrows] = (int64_t)(e - text);
+            flags[nrows] = host ? 1 : 0;
+        }
+        ++nrows;
+        p = nl ? nl + 1 : end;
+    }
+    *file_flags = ff;
+    return nrows;
+}
+
 }  // extern "C"

@@ -63,6 +63,11 @@ def main_combine_strands(args):
     return 0
 
 
+def main_evaluate(args):
+    from .evaluate_mods_call import run
+    return run(args)
+
+
 def _names_freq_file(argv) -> bool:
     """Does the command line give call_mods' --freq_file (spelled out, abbreviated as argparse allows, or with '=')?"""
     for a in argv:
@@ -199,6 +204,13 @@ def build_parser(freq_file_given=True):
     combine_arguments(c)
     c.set_defaults(func=main_combine_strands)
     parser.combine_parser = c
+    # `evaluate`: the step that judges a set of calls -- accuracy and AUROC from the call_mods results of an unmethylated and a
+    # fully methylated sample (the reference's scripts/evaluate_mods_call.py; same flags, plus --on / --device / --num_sites / --seed)
+    from .evaluate_mods_call import add_arguments as evaluate_arguments
+    v = sub.add_parser("evaluate", description="calculate call accuracy stats of call_mods results for methylated and unmethylated samples")
+    evaluate_arguments(v)
+    v.set_defaults(func=main_evaluate)
+    parser.evaluate_parser = v
     return parser
 
 
@@ -238,6 +250,10 @@ def main(argv=None):
     if args.module == "combine_strands":
         from .combine_strands import check_arguments
         check_arguments(parser.combine_parser, args)
+        return args.func(args)
+    if args.module == "evaluate":
+        from .evaluate_mods_call import check_arguments
+        check_arguments(parser.evaluate_parser, args)
         return args.func(args)
     if args.module == "call_freq":
         return args.func(args)       # the script's own main: it validates the forwarded flags and returns the exit status

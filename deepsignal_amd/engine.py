@@ -52,6 +52,9 @@ EXPORTED_SYMBOLS = (
     # both strands of a CpG table combined on the device (combine_strands --on gpu)
     "ds_fasta_locate", "ds_combine_begin", "ds_combine_genome", "ds_combine_bitmap", "ds_combine_parse", "ds_combine_accumulate",
     "ds_combine_result", "ds_combine_end", "ds_motif_reference", "ds_combine_reference", "ds_get_combine_times",
+    # call accuracy and AUROC of labelled call rows on the device (evaluate --on gpu)
+    "ds_eval_locate", "ds_eval_begin", "ds_eval_parse", "ds_eval_accumulate", "ds_eval_result", "ds_eval_end", "ds_eval_reference",
+    "ds_get_eval_times",
 )
 
 
@@ -369,6 +372,81 @@ def freq_values_reference(act) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     return p0, p1, status
 
 
+EVAL_BARE_CR = 1                       # DS_EVAL_BARE_CR: eval_locate's word on the buffer
+EVAL_ROW_GIVEN = 2                     # DS_EVAL_ROW_GIVEN: eval_reference takes this row's values from the caller
+EVAL_SET_SAMPLE, EVAL_SET_ALL, EVAL_TRUTH = 1, 2, 4      # DS_EVAL_SET_* / DS_EVAL_TRUTH: the bits of a row's byte
+EVAL_MAX_CF = 32
+
+
+def eval_locate(text):
+    """ds_eval_locate: the rows of a call_mods result buffer (bytes, or a uint8 array such as a memory map) for a reader that cuts
+    them with line.rstrip().split() -> (row_begin int64[n], row_end int64[n], flags uint8[n], file_flags): flags 1 = a row Python
+    tokenises or decodes differently from fields between runs of space or tab; file_flags & EVAL_BARE_CR = a bare carriage return."""
+    lib = load_library()
+    if isinstance(text, (bytes, bytearray)):
+        text = np.frombuffer(text, np.uint8)
+    text = np.ascontiguousarray(text, np.uint8)
+    if text.ndim != 1:
+        raise ValueError("text must be a flat byte buffer")
+    ff = ctypes.c_int32()
+    cap = text.size // 32 + 1
+    while True:
+        begin, end, flags = np.empty(cap, np.int64), np.empty(cap, np.int64), np.empty(cap, np.uint8)
+        n = int(lib.ds_eval_locate(text.ctypes.data if text.size else None, text.size, cap, begin.ctypes.data, end.ctypes.data,
+                                   flags.ctypes.data, ctypes.byref(ff)))
+        if n < 0:
+            raise RuntimeError("ds_eval_locate failed (%d)" % n)
+        if n <= cap:
+            return begin[:n], end[:n], flags[:n], int(ff.value)
+        cap = n
+
+
+def _eval_cutoffs(cf) -> np.ndarray:
+    cf = np.ascontiguousarray(cf, np.float64)
+    if cf.ndim != 1 or not 1 <= cf.size <= EVAL_MAX_CF:
+        raise ValueError("1 .. 32 cut-offs")
+    return cf
+
+
+def _eval_mask(mask, n: int) -> np.ndarray:
+    mask = np.ascontiguousarray(mask, np.uint8)
+    if mask.shape != (n,):
+        raise ValueError("mask must have one byte per row")
+    if n and int(mask.max()) > (EVAL_SET_SAMPLE | EVAL_SET_ALL | EVAL_TRUTH):
+        raise ValueError("a row's byte holds bits 0 .. 2 only")
+    return mask
+
+
+def _eval_result(ncf: int):
+    return np.zeros((2, 4 + 2 * ncf), np.int64), np.zeros(2, np.uint64), np.zeros(2, np.int64), np.zeros(2, np.int64)
+
+
+def eval_reference(text, begin, end, flags, mask, cf, given=None) -> Dict[str, np.ndarray]:
+    """ds_eval_reference: the device route's counts on the CPU from the same row routines, one pass. A checker for the tests (no
+    GPU needed), not a fall-back. mask: a byte per row (EVAL_SET_SAMPLE | EVAL_SET_ALL | EVAL_TRUTH). `given`: {row index: (p0, p1,
+    called)} for rows whose values the caller supplies. Returns the per-row status / p0 / p1 / called, counts int64[2, 4 + 2 ncf]
+    (tp, fp, tn, fn, called per cut-off, correct per cut-off; set 0 the sample, set 1 all) and per set u2 / p / n."""
+    lib = load_library()
+    keep, addr, begin, end = _text_args(text, begin, end)
+    n = int(begin.size)
+    flags = np.ascontiguousarray(flags, np.uint8)
+    if flags.shape != (n,):
+        raise ValueError("flags must have one entry per row")
+    mask, cf = _eval_mask(mask, n), _eval_cutoffs(cf)
+    status = np.zeros(n, np.int32)
+    p0, p1, called = np.zeros(n, np.float64), np.zeros(n, np.float64), np.zeros(n, np.int32)
+    for i, (a, b, c) in (given or {}).items():
+        status[i], p0[i], p1[i], called[i] = EVAL_ROW_GIVEN, a, b, int(c != 0)
+    counts, u2, pn, nn = _eval_result(cf.size)
+    rc = lib.ds_eval_reference(addr, n, begin.ctypes.data, end.ctypes.data, flags.ctypes.data, mask.ctypes.data, cf.size, cf.ctypes.data,
+                               status.ctypes.data, p0.ctypes.data, p1.ctypes.data, called.ctypes.data, counts.ctypes.data, u2.ctypes.data,
+                               pn.ctypes.data, nn.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("ds_eval_reference failed (%d): %s" % (rc, lib.ds_last_error(None).decode()))
+    return dict(status=status, p0=p0, p1=p1, called=called, counts=counts, u2=[int(v) for v in u2], p=[int(v) for v in pn],
+                n=[int(v) for v in nn])
+
+
 COMBINE_TABLE, COMBINE_BED = 0, 1      # DS_COMBINE_TABLE / DS_COMBINE_BED: the form of the rows
 COMBINE_ROW_SKIP, COMBINE_ROW_GIVEN, COMBINE_ROW_GIVEN_SKIP = 2, 3, 4      # DS_COMBINE_ROW_*
 COMBINE_COUNT_LIMIT = 1 << 32          # a count the caller gives for a row stays below this in magnitude
@@ -591,6 +669,15 @@ def load_library() -> ctypes.CDLL:
                                       ctypes.POINTER(i64)]
     lib.ds_freq_reference.restype = i64
     lib.ds_get_freq_times.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(f64)]
+    lib.ds_eval_locate.argtypes = [vp, i64, i64, vp, vp, vp, ctypes.POINTER(i32)]
+    lib.ds_eval_locate.restype = i64
+    lib.ds_eval_begin.argtypes = [vp, i64, i32, i32, vp]
+    lib.ds_eval_parse.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    lib.ds_eval_accumulate.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    lib.ds_eval_result.argtypes = [vp, vp, vp, vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    lib.ds_eval_end.argtypes = [vp]
+    lib.ds_eval_reference.argtypes = [vp, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.ds_get_eval_times.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(f64)]
     lib.ds_freq_begin_stream.argtypes = [vp, i64, i32, f64]
     lib.ds_freq_push.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp]
     lib.ds_freq_keys.argtypes = [i64, vp, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i32)]
@@ -1078,6 +1165,72 @@ class Engine:
         ms = (ctypes.c_double * 5)()
         self._check(self._lib.ds_get_combine_times(self._h, int(reset), ctypes.byref(c), ctypes.byref(n), ms), "ds_get_combine_times")
         return dict(zip(("copy_ms", "motif_ms", "parse_ms", "sort_ms", "accumulate_ms"), ms), chunks=int(c.value), batches=int(n.value))
+
+    # -- call accuracy and AUROC of labelled call rows on the device (ds_eval_*; evaluate --on gpu) ----------
+    def eval_begin(self, total_rows: int, batch_rows: int, cf) -> None:
+        """ds_eval_begin: open a run of total_rows rows in all in batches of at most batch_rows, with the cut-offs cf (1 .. 32
+        doubles). FreqNoMemory when the score table or the buffers do not fit the device. Needs no weights."""
+        total_rows, batch_rows, cf = int(total_rows), int(batch_rows), _eval_cutoffs(cf)
+        if not 1 <= total_rows <= FREQ_MAX_ROWS:
+            raise ValueError("total_rows must be in [1, 2^30]")
+        if not 1 <= batch_rows <= FREQ_MAX_BATCH:
+            raise ValueError("batch_rows must be in [1, 2^24]")
+        rc = self._lib.ds_eval_begin(self._h, total_rows, batch_rows, cf.size, cf.ctypes.data)
+        self._check_memory(rc, "ds_eval_begin")
+        self._eval_batch, self._eval_pending, self._eval_ncf = batch_rows, -1, int(cf.size)
+
+    def eval_parse(self, text, begin, end, flags) -> np.ndarray:
+        """ds_eval_parse: one batch of rows (ascending spans of one buffer; flags as eval_locate gives them) -> the per-row status
+        (TEXT_ROW_OK / TEXT_ROW_HOST)."""
+        keep, addr, begin, end, _, flags = _batch_rows_args(text, begin, end, np.zeros(len(begin), np.int32), flags,
+                                                            getattr(self, "_eval_batch", 0))
+        n = int(begin.size)
+        status = np.empty(n, np.int32)
+        self._check(self._lib.ds_eval_parse(self._h, addr, n, begin.ctypes.data, end.ctypes.data, flags.ctypes.data, status.ctypes.data),
+                    "ds_eval_parse")
+        self._eval_pending = n
+        return status
+
+    def eval_accumulate(self, mask, rows=(), p0=(), p1=(), called=()) -> None:
+        """ds_eval_accumulate: add the batch just parsed to the run. mask: a byte per row of the batch (EVAL_SET_SAMPLE |
+        EVAL_SET_ALL | EVAL_TRUTH). rows .. called: the caller's values for the batch's TEXT_ROW_HOST rows (ascending batch row
+        indices, every such row; called = a non-zero label)."""
+        n = getattr(self, "_eval_pending", -1)
+        if n < 0:
+            raise ValueError("eval_accumulate needs a batch from eval_parse")
+        mask = _eval_mask(mask, n)
+        rows = np.ascontiguousarray(rows, np.int32)
+        p0, p1 = np.ascontiguousarray(p0, np.float64), np.ascontiguousarray(p1, np.float64)
+        called = np.ascontiguousarray(np.asarray(called) != 0, np.int32)
+        m = int(rows.size)
+        if not (p0.shape == p1.shape == called.shape == (m,)):
+            raise ValueError("one value of each kind per override row")
+        _check_override_rows(rows, n)
+        self._eval_pending = -1
+        self._check(self._lib.ds_eval_accumulate(self._h, mask.ctypes.data, m, rows.ctypes.data, p0.ctypes.data, p1.ctypes.data,
+                                                 called.ctypes.data), "ds_eval_accumulate")
+
+    def eval_result(self) -> dict:
+        """ds_eval_result: counts int64[2, 4 + 2 ncf] (tp, fp, tn, fn, called per cut-off, correct per cut-off; set 0 the sample, set 1
+        all), per set u2 / p / n over the rows with a finite prob_1, and the scalars rows (accumulated) and distinct (scores)."""
+        counts, u2, pn, nn = _eval_result(getattr(self, "_eval_ncf", 1))
+        rows, distinct = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._lib.ds_eval_result(self._h, counts.ctypes.data, u2.ctypes.data, pn.ctypes.data, nn.ctypes.data, ctypes.byref(rows),
+                                             ctypes.byref(distinct)), "ds_eval_result")
+        return dict(counts=counts, u2=[int(v) for v in u2], p=[int(v) for v in pn], n=[int(v) for v in nn], rows=int(rows.value),
+                    distinct=int(distinct.value))
+
+    def eval_end(self) -> None:
+        self._eval_batch, self._eval_pending = 0, -1
+        self._check(self._lib.ds_eval_end(self._h), "ds_eval_end")
+
+    def eval_times(self, reset: bool = False) -> dict:
+        """ds_get_eval_times: device milliseconds of the evaluate runs so far (copies, parse kernel, count + insert kernels, the
+        result's sort / scan / reduction) and the batches."""
+        n = ctypes.c_int64()
+        ms = (ctypes.c_double * 4)()
+        self._check(self._lib.ds_get_eval_times(self._h, int(reset), ctypes.byref(n), ms), "ds_get_eval_times")
+        return dict(zip(("copy_ms", "parse_ms", "count_ms", "result_ms"), ms), batches=int(n.value))
 
     def rows_times(self, reset: bool = False) -> dict:
         """ds_get_rows_times: device milliseconds of the extract_rows() calls made while profiling was on."""

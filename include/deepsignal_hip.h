@@ -604,6 +604,53 @@ int64_t ds_combine_reference(int32_t form, const char *text, int64_t nrows, cons
                              int64_t *site_met, int64_t *site_unmet, int64_t *site_cov, int64_t *last_plus);
 int ds_get_combine_times(ds_handle *h, int32_t reset, int64_t *chunks, int64_t *batches, double *ms);
 
+/* ---- call accuracy and AUROC of labelled call rows on the device (ds_eval.hip; evaluate --on gpu) ----------------------------------
+ * The work of scripts/evaluate_mods_call.py over the rows of two call_mods result files, one of an unmethylated and one of a fully
+ * methylated sample: per tested set the confusion matrix, per cut-off how many calls stand (|prob_1 - prob_0| >= cf) and how many of
+ * those are right ((prob_1 - prob_0 >= cf) == truth), both comparisons in double, and the AUROC of prob_1 as integers: over the
+ * distinct scores ascending, U2 = sum pos_i * (2 * sum_{j<i} neg_j + neg_i), auc = U2 / (2 P N). Every sum is an integer.
+ *
+ * ds_eval_locate (host, no handle): the rows of a buffer -- what lies between two '\n'; a last row needs none -- as spans, and a
+ * flag per row: 1 = Python's line.rstrip().split() would cut or decode the row differently from "fields separated by runs of space
+ * or tab" (a byte >= 0x80, '\r', 0x0b, 0x0c, 0x1c .. 0x1f, or a blank row). Returns the number of rows (more than cap_rows: call
+ * again with room). *file_flags bit 0 (DS_EVAL_BARE_CR): a '\r' that neither a '\n' nor the end of the buffer follows.
+ *
+ * One run on a handle: ds_eval_begin sizes the score table (the open-addressing table of csrc/ds_site_table.h, at most half full)
+ * from total_rows (1 .. 2^30) and the row buffers from batch_rows (1 .. 2^24), and takes the ncf (1 .. 32) cut-offs;
+ * DS_ERR_NOMEM when they do not fit the device. Then, strictly in sequence per batch: ds_eval_parse (rows ascending and disjoint
+ * inside one buffer; fields 1 and 3 validated as [-]digits, 6 and 7 by ds_freq_parse's double grammar, 8 as [-]digits of at most
+ * nine, a tenth field must exist; anything else, and every flagged row, is DS_TEXT_ROW_HOST, never an error) and
+ * ds_eval_accumulate: mask holds one byte per row of the batch -- bit 0 the row is in the sample, bit 1 in the set of all rows, bit 2
+ * it comes from the methylated file -- and row / p0 / p1 / called the caller's values for every DS_TEXT_ROW_HOST row (ascending
+ * batch row indices; called = a non-zero label; the probabilities may be anything float() returns). A row whose prob_1 is NaN or
+ * infinite is counted but kept out of the score table: its sets' AUROC is 0 and the caller, who gave the row, knows.
+ * ds_eval_result: counts[set * (4 + 2 ncf) ..] = tp, fp, tn, fn, called[ncf], correct[ncf] for set 0 (sample) and 1 (all), and per
+ * set U2, P and N over the rows in the table; *rows = rows accumulated, *distinct = distinct scores. ds_eval_end closes the run
+ * (ds_destroy does too). Every call blocks.
+ *
+ * ds_eval_reference: the same counts on the CPU from the same row routines (csrc/ds_eval.h), one pass: a CHECKER, no handle, no
+ * GPU, not a fall-back. status is in / out: DS_EVAL_ROW_GIVEN on entry takes p0 / p1 / called from the caller's arrays.
+ * ds_get_eval_times: device milliseconds since ds_create of ms[0] the copies, ms[1] eval_parse_kernel, ms[2] eval_count_kernel +
+ * eval_insert_kernel, ms[3] the result (compaction, bitonic sort, look-up, scans, reduction). */
+#define DS_EVAL_BARE_CR 1
+#define DS_EVAL_ROW_GIVEN 2
+#define DS_EVAL_SET_SAMPLE 1
+#define DS_EVAL_SET_ALL 2
+#define DS_EVAL_TRUTH 4
+int64_t ds_eval_locate(const char *text, int64_t nbytes, int64_t cap_rows, int64_t *row_begin, int64_t *row_end, uint8_t *flags,
+                       int32_t *file_flags);
+int ds_eval_begin(ds_handle *h, int64_t total_rows, int32_t batch_rows, int32_t ncf, const double *cf);
+int ds_eval_parse(ds_handle *h, const char *text, int32_t nrows, const int64_t *row_begin, const int64_t *row_end, const uint8_t *flags,
+                  int32_t *status);
+int ds_eval_accumulate(ds_handle *h, const uint8_t *mask, int32_t nover, const int32_t *row, const double *p0, const double *p1,
+                       const int32_t *called);
+int ds_eval_result(ds_handle *h, int64_t *counts, uint64_t *u2, int64_t *pn, int64_t *nn, int64_t *rows, int64_t *distinct);
+int ds_eval_end(ds_handle *h);
+int ds_eval_reference(const char *text, int64_t nrows, const int64_t *row_begin, const int64_t *row_end, const uint8_t *flags,
+                      const uint8_t *mask, int32_t ncf, const double *cf, int32_t *status, double *p0, double *p1, int32_t *called,
+                      int64_t *counts, uint64_t *u2, int64_t *pn, int64_t *nn);
+int ds_get_eval_times(ds_handle *h, int32_t reset, int64_t *batches, double *ms);
+
 /* Use a captured hipGraph for the forward (default on). */
 int ds_set_graph(ds_handle *h, int32_t enable);
 
