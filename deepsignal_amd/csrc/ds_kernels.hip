@@ -20,6 +20,187 @@
 namespace ds {
 
 
+// ---- K loop of the fp32 dense instantiation (CFG_FC_DENSE: the 6032 x 6032 layer of the three-step joint model, 128 x 96 tile,
+// four waves that own 32 rows each and share the three weight n-tiles).
+// The template's generic loop streams the weights global -> VGPR in every wave: per 16-wide K chunk a workgroup asks for 24 KB of
+// which 6 KB are distinct, and the two-chunk look-ahead is a register ring of 96 VGPRs (212 in all). Here the six 1 KiB weight
+// fragments of a chunk go global -> LDS ONCE per workgroup by LDS-DMA into a ring of DR_SLOTS stages (lstm_cell_lds_kernel's
+// request form: plain requests, counted vmcnt, the chunk's one barrier), and a wave reads them LDS -> VGPR one read step ahead
+// of its MFMAs: two read steps' worth (24 VGPRs) are live. The activations keep their path (global -> VGPR -> ds_write_b128
+// into rows padded to KC + 4 floats, double-buffered; LDS-DMA cannot write padded rows).
+//   * One vmcnt counter serves the requests AND the activation loads, and hipcc does not see the requests: a load it knows of
+//     would get a wait that counts only the loads it knows, i.e. one that also drains every request issued before the youngest
+//     of them. So the activation loads are inline asm too and every vector-memory wait of the loop is counted by hand. Per chunk
+//     a wave issues, in this order, 2 activation loads (chunk c + 2) and 2 requests (chunk c + DR_DIST); memory operations
+//     retire in issue order, so `vmcnt(6)` before the ds_writes of chunk c + 1 leaves exactly {requests of c + 2, loads of
+//     c + 2, requests of c + 3} in flight and has retired the requests of chunk c + 1 as well, which the barrier behind it
+//     publishes to the other waves.
+//   * Six fragments over four waves: waves 0 / 1 request fragments (w, w + 4), waves 2 / 3 request fragment w and refetch it
+//     into a pad (SplitRing's filler), so the count is the same literal in every wave.
+//   * Past the last chunk the cursors stay on it (scalar selects): the loop body has no look-ahead conditionals, the surplus
+//     requests and loads refetch the last chunk into slots nobody reads again, and `vmcnt(0)` behind the loop retires them
+//     before their target registers are reused.
+//   * Sources are wave-uniform scalar bases advanced by scalar adds plus loop-invariant lane offsets: no VALU in the loop.
+//   * The order inside a step is pinned instruction by instruction (sched_barrier): one non-MFMA instruction behind one MFMA.
+//   * Per accumulator the MFMAs run in the generic loop's order (chunk, read step, x y z w): bit-identical results.
+// What it buys: 286 -> 262 us per launch alone (the matrix pipe 82 -> 90 % busy) and a quarter of the weight requests. At 129
+// VGPRs and 46 KB a workgroup would also fit beside a fused inception module (2 x 184 VGPRs per SIMD, 111 KB of LDS); that
+// placement was measured and loses, so the launch keeps one dense workgroup per CU (launch_gemm, DR_SOLO_PAD_BYTES).
+// Ring slot of chunk c is c % 4, activation buffer c & 1; a slot is requested again one barrier after its last read retired
+// (`lgkmcnt(0)` in front of every barrier).
+constexpr int DR_SLOTS = 4;                      // ring stages of one chunk
+constexpr int DR_DIST = 3;                       // chunks between a request and the step that multiplies it
+constexpr int DR_STAGE = 6 * 256;                // floats: 3 n-tiles x 2 k-groups of 1 KiB
+constexpr int DR_A_FLOATS = 2 * 128 * (KC + 4);
+constexpr int DR_LDS_FLOATS = DR_A_FLOATS + DR_SLOTS * DR_STAGE + 2 * 256;      // + the pad of waves 2 and 3: 47,104 B
+constexpr int DR_SOLO_PAD_BYTES = 56 * 1024;      // unused dynamic LDS of the launch (launch_gemm): one dense workgroup per CU
+
+// The load is asynchronous: dst holds the data only behind the hand-counted `s_waitcnt vmcnt` asm that names it as "+v". hipcc
+// takes dst for written here, so a copy or a spill of it between the two statements would carry stale registers. Nothing forces
+// the two together; what holds it is that R[][] has no other use in between (today's code keeps each R in one register quadruple,
+// no v_mov in the loop), tests/test_dense_cotenancy_budget.py (no spills, no scratch) and the bitwise checks of
+// tests/test_gpu_dense_ring.py, which a stale row fails.
+__device__ __forceinline__ void dr_gload4(v4f& dst, unsigned voff, const void* sbase)
+{
+    asm volatile("global_load_dwordx4 %0, %1, %2" : "=&v"(dst) : "v"(voff), "s"(sbase) : "memory");
+}
+template <int E> __device__ __forceinline__ float dr_elem(const v4f& v) { return E == 0 ? v.x : E == 1 ? v.y : E == 2 ? v.z : v.w; }
+
+__device__ __forceinline__ void dense_ring_loop(const GemmProblem& P, float* smem, int m0, int tid, int lane, int wave,
+                                                int t0, int t1, int t2, floatx16 (&acc)[1][3])
+{
+    constexpr int LDA = KC + 4;
+    const int nchunks = P.K / KC;
+    if (nchunks <= 0) return;
+    float* const ring = smem + DR_A_FLOATS;
+    const unsigned ring_lds = (unsigned)(size_t)(__attribute__((address_space(3))) float*)ring;
+    const unsigned lane16 = (unsigned)lane * 16;
+
+    // ---- weight requests: fragment q = 2 nt + kg of a chunk lies at ring slot + q KiB
+    const char* bsrc[2];
+    unsigned bdst[2], bdstep[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int q = wave + 4 * j;
+        const bool own = q < 6;
+        const int qq = own ? q : wave, nt = qq >> 1, kg = qq & 1;
+        const int tile = nt == 0 ? t0 : nt == 1 ? t1 : t2;
+        bsrc[j] = reinterpret_cast<const char*>(P.Bp) + ((size_t)tile * P.kgroups_stride + kg) * 1024;
+        bdst[j] = own ? ring_lds + q * 1024 : ring_lds + DR_SLOTS * DR_STAGE * 4 + (wave - 2) * 1024;
+        bdstep[j] = own ? DR_STAGE * 4 : 0;
+    }
+    int breq_left = nchunks - 1;
+    auto request0 = [&](int slot) __attribute__((always_inline)) { glds16s(bsrc[0], lane16, bdst[0] + slot * bdstep[0]); };
+    auto request1 = [&](int slot) __attribute__((always_inline)) {
+        glds16s(bsrc[1], lane16, bdst[1] + slot * bdstep[1]);
+        const long inc = breq_left > 0 ? 2 * 1024 : 0;
+        --breq_left;
+        bsrc[0] += inc;
+        bsrc[1] += inc;
+    };
+
+    // ---- activation cursor: row tile and chunk in the scalar base, the lane's row and 16 bytes in a 32-bit offset
+    unsigned avoff[2];
+    const char* abase = nullptr;
+    int seg_i = 0, seg_left = 0;
+    const int nseg = P.nseg;
+    auto seg_begin = [&](int si) __attribute__((always_inline)) {
+        const int ld = P.seg[si].ld;
+        seg_left = P.seg[si].klen / KC;
+        abase = reinterpret_cast<const char*>(P.seg[si].base + (size_t)(m0 + P.seg[si].row_shift) * ld);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int idx = tid + i * 256;
+            avoff[i] = ((unsigned)(idx >> 2) * (unsigned)ld + (idx & 3) * 4) * 4;
+        }
+    };
+    auto advance_a = [&]() __attribute__((always_inline)) {
+        if (--seg_left == 0) {
+            if (seg_i + 1 < nseg) seg_begin(++seg_i);
+            else seg_left = 1;                      // past the end: stay on the last chunk
+        } else {
+            abase += KC * 4;
+        }
+    };
+
+    v4f R[2][2];                 // activation rows in flight: chunk k in R[k & 1]
+    v4f af[2][2], b[2][3];       // fragments: af[chunk & 1][read step], b[read step][n-tile]
+    const float* const fa = smem + ((wave * 32 + (lane & 31)) * LDA + (lane >> 5) * 4);
+    float* const wa = smem + ((tid >> 2) * LDA + (tid & 3) * 4);
+    const float* const fb = ring + lane * 4;
+
+    // ---- prologue: the queue is left as every step expects it: ..., loads of chunk 1, requests of chunk 2
+    seg_begin(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    dr_gload4(R[0][0], avoff[0], abase);
+    dr_gload4(R[0][1], avoff[1], abase);
+    advance_a();
+    request0(0); request1(0);
+    request0(1); request1(1);
+    dr_gload4(R[1][0], avoff[0], abase);
+    dr_gload4(R[1][1], avoff[1], abase);
+    advance_a();
+    request0(2); request1(2);
+    asm volatile("s_waitcnt vmcnt(4)" : "+v"(R[0][0]), "+v"(R[0][1]) : : "memory");
+    *reinterpret_cast<v4f*>(wa) = R[0][0];
+    *reinterpret_cast<v4f*>(wa + 64 * LDA) = R[0][1];
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    af[0][0] = *reinterpret_cast<const v4f*>(fa);
+    af[0][1] = *reinterpret_cast<const v4f*>(fa + 8);
+#pragma unroll
+    for (int nt = 0; nt < 3; ++nt) b[0][nt] = *reinterpret_cast<const v4f*>(fb + nt * 512);
+
+    // one chunk: X = its activation buffer, Q = its ring slot. MFMA m of a read step (n-tile m / 4, element m % 4), then one
+    // other instruction, then a scheduling barrier.
+#define DR_MFMA(RS, M_)                                                                                                        \
+    acc[0][(M_) / 4] = __builtin_amdgcn_mfma_f32_32x32x2f32(dr_elem<(M_) % 4>(af[X][RS]), dr_elem<(M_) % 4>(b[RS][(M_) / 4]),                 \
+                                                             acc[0][(M_) / 4], 0, 0, 0)
+#define DR_PIN __builtin_amdgcn_sched_barrier(0)
+    auto step = [&](auto xc, auto qc) __attribute__((always_inline)) {
+        constexpr int X = decltype(xc)::value, Q = decltype(qc)::value;
+        constexpr int XN = X ^ 1, QN = (Q + 1) % DR_SLOTS, QR = (Q + DR_DIST) % DR_SLOTS;
+        DR_PIN;
+        DR_MFMA(0, 0); dr_gload4(R[X][0], avoff[0], abase); DR_PIN;
+        DR_MFMA(0, 1); dr_gload4(R[X][1], avoff[1], abase); DR_PIN;
+        DR_MFMA(0, 2); request0(QR); DR_PIN;
+        DR_MFMA(0, 3); request1(QR); DR_PIN;
+        DR_MFMA(0, 4); b[1][0] = *reinterpret_cast<const v4f*>(fb + Q * DR_STAGE + 256); DR_PIN;
+        DR_MFMA(0, 5); b[1][1] = *reinterpret_cast<const v4f*>(fb + Q * DR_STAGE + 768); DR_PIN;
+        DR_MFMA(0, 6); b[1][2] = *reinterpret_cast<const v4f*>(fb + Q * DR_STAGE + 1280); DR_PIN;
+        DR_MFMA(0, 7);
+        asm volatile("s_waitcnt vmcnt(6)" : "+v"(R[XN][0]), "+v"(R[XN][1]) : : "memory");
+        *reinterpret_cast<v4f*>(wa + XN * 128 * LDA) = R[XN][0]; DR_PIN;
+        DR_MFMA(0, 8); *reinterpret_cast<v4f*>(wa + XN * 128 * LDA + 64 * LDA) = R[XN][1]; DR_PIN;
+        DR_MFMA(0, 9); DR_PIN;
+        DR_MFMA(0, 10); advance_a(); DR_PIN;
+        DR_MFMA(0, 11); DR_PIN;
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        DR_PIN;
+        DR_MFMA(1, 0); af[XN][0] = *reinterpret_cast<const v4f*>(fa + XN * 128 * LDA); DR_PIN;
+        DR_MFMA(1, 1); af[XN][1] = *reinterpret_cast<const v4f*>(fa + XN * 128 * LDA + 8); DR_PIN;
+        DR_MFMA(1, 2); b[0][0] = *reinterpret_cast<const v4f*>(fb + QN * DR_STAGE); DR_PIN;
+        DR_MFMA(1, 3); b[0][1] = *reinterpret_cast<const v4f*>(fb + QN * DR_STAGE + 512); DR_PIN;
+        DR_MFMA(1, 4); b[0][2] = *reinterpret_cast<const v4f*>(fb + QN * DR_STAGE + 1024); DR_PIN;
+        DR_MFMA(1, 5); DR_PIN;
+        DR_MFMA(1, 6); DR_PIN;
+        DR_MFMA(1, 7); DR_PIN;
+        DR_MFMA(1, 8); DR_PIN;
+        DR_MFMA(1, 9); DR_PIN;
+        DR_MFMA(1, 10); DR_PIN;
+        DR_MFMA(1, 11); DR_PIN;
+    };
+    for (int c = 0;;) {
+        step(LdsSlot<0>{}, LdsSlot<0>{}); if (++c >= nchunks) break;
+        step(LdsSlot<1>{}, LdsSlot<1>{}); if (++c >= nchunks) break;
+        step(LdsSlot<0>{}, LdsSlot<2>{}); if (++c >= nchunks) break;
+        step(LdsSlot<1>{}, LdsSlot<3>{}); if (++c >= nchunks) break;
+    }
+#undef DR_MFMA
+#undef DR_PIN
+    // the surplus loads and requests of the last steps: retired before their registers and the ring are given up
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(R[0][0]), "+v"(R[0][1]), "+v"(R[1][0]), "+v"(R[1][1]) : : "memory");
+}
+
 // BF = bf16 operands. The byte geometry is the same as fp32: a "unit" is 4 bytes (one float or two bf16), a
 // K chunk is 16 units = 64 B per row (16 floats / 32 bf16), one 16-B fragment per lane feeds four
 // v_mfma_f32_32x32x2_f32 (fp32) or ONE v_mfma_f32_32x32x16_bf16 (lane half h owns k = 8h..8h+7 of the 16).
@@ -27,14 +208,22 @@ namespace ds {
 // KS is 1 in every instantiation (it was an in-workgroup K split that no plan selected, retired to
 // profiles/experiments/); the parameter stays because the kernel names in the kernel table and the committed profiles carry it.
 template <int MT, int NT, int WM, int WN, int EPI, int AMODE, int BD, int KS, bool BF = false>
-__global__ __launch_bounds__(64 * WM * WN, 1) void gemm_kernel(const GemmLaunch* __restrict__ L)
+__global__ __launch_bounds__(64 * WM * WN, (AMODE == 2 && !BF) ? 3 : 1) void gemm_kernel(const GemmLaunch* __restrict__ L)
 {
     static_assert(KS == 1, "the in-workgroup K split is retired (profiles/EXPERIMENTS.md)");
     constexpr int BM = WM * MT * 32;
     constexpr int LDA = KC + 4;
     constexpr int NTHR = 64 * WM * WN;
     constexpr int SLOTS = (BM * 4 + NTHR - 1) / NTHR;
-    __shared__ __attribute__((aligned(16))) float smem_[2 * BM * LDA];
+    // the fp32 dense instantiation has a K loop of its own (dense_ring_loop): its weights come through an LDS ring behind the A buffers.
+    // AMODE 2 without BF is FC1 of the three-step joint model and nothing else (plan_joint_model: n % 128 == 0, row_shift 0, W = M,
+    // every segment a positive multiple of KC wide); dense_ring_loop relies on all of that -- it has no row masks, no W bounds and
+    // no empty segments. Its __launch_bounds__ second argument (3 waves per SIMD) is a REGISTER budget, not an occupancy: with
+    // 46 KB of static LDS hipcc derives the budget from the LDS-limited occupancy anyway (three workgroups per CU: 168 VGPRs), and 3
+    // states the same; the kernel takes 129. How many workgroups share a CU is decided at the launch (launch_gemm: one).
+    constexpr bool RING = AMODE == 2 && !BF;
+    static_assert(!RING || (MT == 1 && NT == 3 && WM == 4 && WN == 1 && 2 * BM * LDA == DR_A_FLOATS), "dense_ring_loop is written for the 128 x 96 tile");
+    __shared__ __attribute__((aligned(16))) float smem_[RING ? DR_LDS_FLOATS : 2 * BM * LDA];
 
     // the wave index is wave-uniform, but hipcc cannot prove it from threadIdx: readfirstlane keeps the
     // segment-cursor logic on the scalar unit (otherwise it becomes exec-masked vector code)
@@ -100,6 +289,10 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_kernel(const GemmLaunch*
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.0f;
 
+    if constexpr (RING) {
+        auto tile_of = [&](int nt) { return nvalid[nt] ? ntile[nt] : P.ntiles32 - 1; };      // clamp: requests stay in bounds, result unused
+        dense_ring_loop(P, smem_, m0, tid, lane, wave, tile_of(0), tile_of(1), tile_of(2), acc);
+    } else {
     // A cursor: branch-free loads. Every slot always loads from a legal address (its own row when
     // valid, the segment base otherwise) and invalid slots are zeroed by a select afterwards.
     const float* ap[SLOTS];
@@ -365,6 +558,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_kernel(const GemmLaunch*
     }
 #undef DS_STEP
 #undef DS_STEPD
+    }
 
     // ---------------- epilogue ----------------
     const int rbase = m0 + wm * MT * 32 + 4 * (lane >> 5);
@@ -423,7 +617,14 @@ hipError_t launch_gemm(GemmCfg cfg, const GemmLaunch* d_launch, int total_tiles,
     case CFG_CONV: hipLaunchKernelGGL((gemm_kernel<1, 2, 4, 1, 0, 0, 1, 1>), dim3(total_tiles), dim3(256), 0, s, d_launch); break;
     case CFG_FC: hipLaunchKernelGGL((gemm_kernel<1, 3, 4, 1, 0, 0, 2, 1>), dim3(total_tiles), dim3(256), 0, s, d_launch); break;
     case CFG_CONV_POOL: hipLaunchKernelGGL((gemm_kernel<1, 2, 4, 1, 0, 1, 1, 1>), dim3(total_tiles), dim3(256), 0, s, d_launch); break;
-    case CFG_FC_DENSE: hipLaunchKernelGGL((gemm_kernel<1, 3, 4, 1, 0, 2, 2, 1>), dim3(total_tiles), dim3(256), 0, s, d_launch); break;
+    case CFG_FC_DENSE:
+        // ONE dense workgroup per CU, set by an unused dynamic LDS allocation (DR_SOLO_PAD_BYTES; the limit is raised once per device in
+        // configure_fused_kernels). The ring loop's own footprint (129 VGPRs, 46 KB of static LDS) lets the dispatcher stack three dense
+        // workgroups on a CU or put one beside a fused module, where no BiLSTM cell fits any more; launched that way the pipelined step
+        // is SLOWER than the parent's (-1.7 %), with 46 + 56 KB -- room for four cell workgroups beside it and nothing else -- it is
+        // faster (+2.2 %): profiles/dense_ring_ab.json, profiles/EXPERIMENTS.md.
+        hipLaunchKernelGGL((gemm_kernel<1, 3, 4, 1, 0, 2, 2, 1>), dim3(total_tiles), dim3(256), DR_SOLO_PAD_BYTES, s, d_launch);
+        break;
     case CFG_BCONV: hipLaunchKernelGGL((gemm_kernel<1, 2, 4, 1, 0, 0, 1, 1, true>), dim3(total_tiles), dim3(256), 0, s, d_launch); break;
     case CFG_BCONV_POOL: hipLaunchKernelGGL((gemm_kernel<1, 2, 4, 1, 0, 1, 1, 1, true>), dim3(total_tiles), dim3(256), 0, s, d_launch); break;
     case CFG_BFC: hipLaunchKernelGGL((gemm_kernel<4, 2, 1, 4, 0, 0, 2, 1, true>), dim3(total_tiles), dim3(256), 0, s, d_launch); break;
@@ -2266,6 +2467,9 @@ hipError_t configure_fused_kernels()
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
     }
+    // the fp32 dense instantiation: static ring + the launch's pad (launch_gemm, CFG_FC_DENSE) pass the default 64 KB
+    const hipError_t e1 = hipFuncSetAttribute((const void*)gemm_kernel<1, 3, 4, 1, 0, 2, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, DR_SOLO_PAD_BYTES);
+    if (e1 != hipSuccess) return e1;
     const hipError_t e2 = hipFuncSetAttribute((const void*)stem23_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)STEM23_MAX_LDS);
     if (e2 != hipSuccess) return e2;
     return hipFuncSetAttribute((const void*)stem23_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)STEM23_MAX_LDS);
