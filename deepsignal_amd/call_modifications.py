@@ -204,7 +204,7 @@ COLLECTIVE_TIMEOUT_S = 600.0      # process-group timeout of a multi-GPU call_mo
 # sites per forward the engine is created for (see make_engine). TSV -> TSV on MI355X, 327,680 rows (tools/e2e_profile.py): fp32
 # 505 / 504 / 526 / 532 k sites/s at 512 / 1024 / 2048 / 4096 (fewer, larger H2D copies and Python round trips per site; the
 # resident-input rate itself gains 2 %); bf16_all 1.3 M at 512 against 1.9 M at 4096
-ENGINE_BATCH = {"fp32": 4096, "bf16": 4096, "bf16_all": 4096, "bf16x3": 4096}
+ENGINE_BATCH = {"fp32": 4096, "bf16": 4096, "bf16_all": 4096, "bf16x3": 4096, "fp16x2": 4096}
 
 
 def engine_batch_for(batch_size: int, precision: str, engine_batch: int = 0) -> int:
@@ -269,7 +269,7 @@ def make_engine(model_path: str, kmer_len: int, cent_signals_len: int, class_num
     return eng
 
 
-FINE_PRECISIONS = ("fp32", "bf16x3")      # the fp32-class modes: held to the fp32 parity bars
+FINE_PRECISIONS = ("fp32", "bf16x3", "fp16x2")      # the fp32-class modes: held to the fp32 parity bars
 
 
 def check_recheck_args(precision: str, recheck_margin: float, recheck_precision: str) -> None:

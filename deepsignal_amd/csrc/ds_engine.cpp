@@ -46,7 +46,7 @@ struct PackedGemm {      // device-resident packed weights of one GEMM
     float* Bp = nullptr;
     float* bias = nullptr;
     int K = 0, N = 0;
-    float* Bps = nullptr;   // DS_PRECISION_BF16X3: the same matrix as three bf16 term panels (pack_b_split)
+    float* Bps = nullptr;   // DS_PRECISION_BF16X3 / FP16X2: the same matrix as three bf16 / two fp16 term panels (pack_b_split)
     float* Bp16 = nullptr;  // native fp32: the columns of 16-wide tiles as 16x16x4 fragments (pack_b_rem16): 32..47 of b3b / b4b, b1 of the P1 panel
 };
 
@@ -162,7 +162,7 @@ struct Slot {
     float *fc1o = nullptr, *logits = nullptr, *act = nullptr;
     int* pred = nullptr;
     float* joint = nullptr;              // bf16 mode: [B][JP] bf16 FC operand (event features | signal features | zero pad)
-    char* jsplit = nullptr;              // DS_PRECISION_BF16X3, three-step joint model: the joint rows as a fragment-major term image
+    char* jsplit = nullptr;              // DS_PRECISION_BF16X3 / FP16X2, three-step joint model: the joint rows as a fragment-major term image
 
     // The ticket in flight and its site count: read and written only by the helpers under "pipeline slots" below. A submit takes
     // the idle slot next_slot points at, stages its inputs, advances next_slot and holds the slot; the wait of the ticket's kind
@@ -216,7 +216,8 @@ struct ds_handle {
     bool lstm_xproj = false;              // split cells: the first step's layer-0 cells (no matrix product) by lstm_xproj_kernel instead of a diagonal of their own
     bool lstm_xproj_all = false;          // ... and layer 0's accumulator-initial values of ALL steps as an image (DS_TUNE_LSTM_XPROJ_ALL)
     int split_dense_min_n = DS_SPLIT_DENSE_MIN_N;   // sites per forward from which dense(J, J) runs split (below: the native fp32 GEMM)
-    bool split = false;   // DS_PRECISION_BF16X3: fp32 activations / weights carried as three bf16 terms through the bf16 matrix pipe
+    bool split = false;   // DS_PRECISION_BF16X3 / FP16X2: fp32 activations / weights carried as terms through the 16-bit matrix pipe ...
+    TermFormat terms = TERMS_BF16X3;      // ... three bf16 terms, six products per MAC | two fp16 terms, three products (ds_split.hip)
                           // (six products per MAC, fp32 accumulate) in the fused inception chains; everything else as fp32
     int lstm_variant = 0;     // ds_config.reserved[3] as given (DS_LSTM_TILING_*)
     // per-handle tuning / diagnostic knobs, all from ds_config.reserved[2..5] (include/deepsignal_hip.h)
@@ -437,13 +438,74 @@ std::vector<float> pack_b_bf16(int K, int N, const std::function<float(int, int)
     return raw;
 }
 
+// fp16 <-> fp32 on the host, as v_cvt_f16_f32 / v_cvt_f32_f16 do it: round to nearest even, subnormal results kept, no saturation
+// (beyond 65504 + half an ulp: Inf)
+uint16_t f32_to_f16(float f)
+{
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
+    u &= 0x7fffffffu;
+    if (u > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);            // quiet NaN
+    if (u >= 0x47800000u) return (uint16_t)(sign | 0x7c00u);           // >= 65536 (and Inf)
+    if (u < 0x38800000u) {                                             // below 2^-14: a multiple of 2^-24, rounded by the fp32 adder
+        float a;
+        memcpy(&a, &u, 4);
+        const float r = a * 16777216.0f + 8388608.0f;                  // a 2^24 + 2^23: the integer lands in the low mantissa bits
+        uint32_t ri;
+        memcpy(&ri, &r, 4);
+        return (uint16_t)(sign | (ri & 0x7ffu));                       // (1024 = the smallest normal number, by the carry)
+    }
+    uint32_t hbits = ((u >> 23) - 112) << 10 | ((u >> 13) & 0x3ffu);
+    const uint32_t rem = u & 0x1fffu;
+    if (rem > 0x1000u || (rem == 0x1000u && (hbits & 1))) ++hbits;      // (a carry out of the mantissa moves the exponent; 0x7c00 = Inf)
+    return (uint16_t)(sign | hbits);
+}
+float f16_to_f32(uint16_t hv)
+{
+    const uint32_t sign = (uint32_t)(hv & 0x8000u) << 16, e = (hv >> 10) & 0x1f, m = hv & 0x3ffu;
+    uint32_t u;
+    if (e == 0) {
+        const float f = (float)m * (1.0f / 16777216.0f);               // subnormal: m 2^-24, exact
+        memcpy(&u, &f, 4);
+        u |= sign;
+    } else if (e == 31) u = sign | 0x7f800000u | (m << 13);
+    else u = sign | ((e + 112) << 23) | (m << 13);
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
 // Split-operand packing (DS_PRECISION_BF16X3, ds_split.hip): every weight w as three bf16 terms t0 = bf16(w), t1 = bf16(w - t0),
 // t2 = bf16(w - t0 - t1) (the differences are exact in fp32, the terms sum to w exactly); layout [ntile][kstep of 16][term][lane][8 bf16],
 // i.e. pack_b_bf16's fragments with the three terms of a k-step next to each other (3 KiB per wave and k-step, contiguous).
-std::vector<float> pack_b_split(int K, int N, const std::function<float(int, int)>& w_in)
+// DS_PRECISION_FP16X2: two fp16 terms h0 = fp16(w), h1 = fp16(w - h0) in the same layout (2 KiB per wave and k-step).
+std::vector<float> pack_b_split(TermFormat fmt, int K, int N, const std::function<float(int, int)>& w_in)
 {
     const int Kp = (K + 63) / 64 * 64;
     const int ntiles = (N + 31) / 32, ks = Kp / 16;
+    if (fmt == TERMS_FP16X2) {
+        std::vector<uint16_t> out((size_t)ntiles * ks * 2 * 64 * 8, 0);
+        for (int nt = 0; nt < ntiles; ++nt)
+            for (int g = 0; g < ks; ++g)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int col = nt * 32 + (lane & 31);
+                    if (col >= N) continue;
+                    const int k0 = g * 16 + 8 * (lane >> 5);
+                    for (int q = 0; q < 8; ++q) {
+                        if (k0 + q >= K) continue;
+                        float r = w_in(k0 + q, col);
+                        for (int t = 0; t < 2; ++t) {
+                            const uint16_t b = f32_to_f16(r);
+                            out[((((size_t)nt * ks + g) * 2 + t) * 64 + lane) * 8 + q] = b;
+                            r -= f16_to_f32(b);
+                        }
+                    }
+                }
+        std::vector<float> raw(out.size() / 2);
+        memcpy(raw.data(), out.data(), out.size() * 2);
+        return raw;
+    }
     std::vector<uint16_t> out((size_t)ntiles * ks * 3 * 64 * 8, 0);
     for (int nt = 0; nt < ntiles; ++nt)
         for (int g = 0; g < ks; ++g)
@@ -532,7 +594,7 @@ int upload_concat(ds_handle* h, const std::vector<const FoldedConv*>& parts, Pac
     pg->K = h->bf16 ? (K + 1) / 2 : K; pg->N = N;
     int rc = upload(h, &pg->Bp, packed);
     if (rc) return rc;
-    if (split_panel && (rc = upload(h, &pg->Bps, pack_b_split(K, N, wfun)))) return rc;
+    if (split_panel && (rc = upload(h, &pg->Bps, pack_b_split(h->terms, K, N, wfun)))) return rc;
     if (rem16_col0 >= 0 && !h->bf16 && (rc = upload(h, &pg->Bp16, pack_b_rem16(K, rem16_col0, rem16_tiles, wfun)))) return rc;
     return upload(h, &pg->bias, bias);
 }
@@ -618,7 +680,7 @@ int finalize_weights(ds_handle* h)
                 std::vector<float> packed = h->lstm_bf16 ? pack_b_bf16(K, 4 * HID, wfun) : pack_b(K, 4 * HID, wfun);
                 pg.K = h->lstm_bf16 ? K / 2 : K; pg.N = 4 * HID;
                 if ((rc = upload(h, &pg.Bp, packed))) return rc;
-                if (h->split && (rc = upload(h, &pg.Bps, pack_b_split(K, 4 * HID, wfun)))) return rc;
+                if (h->split && (rc = upload(h, &pg.Bps, pack_b_split(h->terms, K, 4 * HID, wfun)))) return rc;
                 if ((rc = upload(h, &pg.bias, bias->data))) return rc;
             }
             if (l == 0) {
@@ -683,7 +745,7 @@ int finalize_weights(ds_handle* h)
         std::vector<float> packed = h->bf16 ? pack_b_bf16(J, J, wfun) : pack_b(J, J, wfun);
         h->fc1.K = h->bf16 ? h->JP / 2 : J; h->fc1.N = J;
         if ((rc = upload(h, &h->fc1.Bp, packed))) return rc;
-        if (h->split && J % 16 == 0 && (rc = upload(h, &h->fc1.Bps, pack_b_split(J, J, wfun)))) return rc;
+        if (h->split && J % 16 == 0 && (rc = upload(h, &h->fc1.Bps, pack_b_split(h->terms, J, J, wfun)))) return rc;
         h->fc1.bias = nullptr;
         if ((rc = upload(h, &h->fc2, w2->data))) return rc;
     }
@@ -713,8 +775,8 @@ int alloc_workspace(ds_handle* h)
     A(&h->cur->sigfeat, B * h->SF);
     for (int d = 0; d < 2; ++d)
         for (int l = 0; l < NLAYER; ++l) {
-            // split cells keep h as three bf16 terms (6 bytes per unit) where the fp32 cells keep a float
-            A(&h->cur->H[d][l], (size_t)h->T * h->Bp32 * HID * (h->split ? 3 : 2) / 2); A(&h->cur->Cst[d][l], (size_t)h->Bp32 * HID);
+            // split cells keep h as three bf16 terms (6 bytes per unit; two fp16 terms: 4) where the fp32 cells keep a float
+            A(&h->cur->H[d][l], (size_t)h->T * h->Bp32 * HID * (h->split ? term_count(h->terms) : 2) / 2); A(&h->cur->Cst[d][l], (size_t)h->Bp32 * HID);
             if (l == 0 && h->lstm_xproj_all) A(&h->cur->xproj[d], (size_t)h->T * h->Bp32 * 4 * HID);
         }
     if (h->is_rnn)
@@ -723,7 +785,7 @@ int alloc_workspace(ds_handle* h)
     A(&h->cur->act, B * h->C + B);            // [act | pred]: one block, one D2H copy
     if (!rc) h->cur->pred = reinterpret_cast<int*>(h->cur->act + B * h->C);
     if (h->bf16) A(&h->cur->joint, B * (size_t)h->JP / 2);
-    if (h->split && !h->fold_fc && h->J % 16 == 0) A(&h->cur->jsplit, (size_t)(h->Bp32 / 32) * (h->J / 16) * 3 * 1024);
+    if (h->split && !h->fold_fc && h->J % 16 == 0) A(&h->cur->jsplit, (size_t)(h->Bp32 / 32) * (h->J / 16) * term_count(h->terms) * 1024);
     // module outputs: ping-pong pair normally; one buffer per module in debug mode (for taps)
     // the modules of a width class run as a chain inside one launch (ds_internal.h FusedChain): a workgroup that is already
     // in module 5 must not write into the buffer a slower workgroup still reads module 4's (stride-2 pooled, differently
@@ -1084,8 +1146,8 @@ void plan_event_model(Planner& P)
         const LstmTile tile = choose_lstm_tile(h->lstm_variant, cells, n);
         const int mtiles = (n + 31) / 32, per_cell = lstm_tiles_per_cell(tile, mtiles);
         const bool lsp = cells == OPS_SPLIT, lbf = cells == OPS_BF16;
-        // floats of one time step in H (bf16 h: two units per float; split h: 3/2)
-        const size_t step = lsp ? (size_t)h->Bp32 * HID * 3 / 2 : (size_t)h->Bp32 * (lbf ? HID / 2 : HID);
+        // floats of one time step in H (bf16 h: two units per float; split h: 3/2, or 1 in two fp16 terms)
+        const size_t step = lsp ? (size_t)h->Bp32 * HID * term_count(h->terms) / 2 : (size_t)h->Bp32 * (lbf ? HID / 2 : HID);
         const bool xpj = h->lstm_xproj && lsp;
         const size_t xstep = (size_t)h->Bp32 * 4 * HID;
         if (xpj) {
@@ -1265,16 +1327,16 @@ int issue_op(ds_handle* h, Plan& plan, const Op& op, hipStream_t s)
         break;
     case OP_PACKEV: HIPCHK(h, launch_pack_event_feat_bf16(h->cur->hlast[0], h->cur->hlast[1], h->cur->joint, n, h->JP, 0, s)); break;
     case OP_LSTM:
-        if (lstm_tile_is_split(op.lstm.tile)) HIPCHK(h, launch_lstm_cells_split(op.lstm.tile, plan.lstm_launches[op.lstm.launch_index], s));
+        if (lstm_tile_is_split(op.lstm.tile)) HIPCHK(h, launch_lstm_cells_split(op.lstm.tile, h->terms, plan.lstm_launches[op.lstm.launch_index], s));
         else HIPCHK(h, launch_lstm_cells(op.lstm.tile, plan.lstm_launches[op.lstm.launch_index], s));
         break;
-    case OP_DENSES: HIPCHK(h, launch_dense_split(op.sd, s)); break;
-    case OP_XPROJ: HIPCHK(h, launch_lstm_xproj(op.xp, s)); break;
+    case OP_DENSES: HIPCHK(h, launch_dense_split(h->terms, op.sd, s)); break;
+    case OP_XPROJ: HIPCHK(h, launch_lstm_xproj(h->terms, op.xp, s)); break;
     case OP_STEM23:
         switch (op.operands) {
         case OPS_FP32: HIPCHK(h, launch_stem23(op.sa, s)); break;
         case OPS_BF16: HIPCHK(h, launch_stem23_bf16(op.sa, s)); break;
-        case OPS_SPLIT: HIPCHK(h, launch_stem23_split(op.sa, s)); break;
+        case OPS_SPLIT: HIPCHK(h, launch_stem23_split(h->terms, op.sa, s)); break;
         }
         break;
     case OP_HEADF: HIPCHK(h, launch_head_folded(op.ha, s)); break;
@@ -1282,7 +1344,7 @@ int issue_op(ds_handle* h, Plan& plan, const Op& op, hipStream_t s)
         switch (op.operands) {
         case OPS_FP32: HIPCHK(h, launch_inception_fused(op.tm, op.fc, s)); break;
         case OPS_BF16: HIPCHK(h, launch_inception_fused_bf16(op.tm, op.fc, s)); break;
-        case OPS_SPLIT: HIPCHK(h, launch_inception_fused_split(op.tm, op.fc, s)); break;
+        case OPS_SPLIT: HIPCHK(h, launch_inception_fused_split(h->terms, op.tm, op.fc, s)); break;
         }
         break;
     case OP_HEAD:
@@ -1509,7 +1571,7 @@ const char* ds_version(void)
 {
     return "deepsignal_amd 0.4 (gfx950; fp32 MFMA, bf16 conv + FC and bf16_all operand modes; bf16x3 = fp32 operands as three bf16 "
            "terms, six products per MAC, in: conv_layer2 / 3, the eleven inception modules, the BiLSTM cells' recurrent and lower-layer products, dense(J, J) of the three-step "
-           "joint model)";
+           "joint model; fp16x2 = the same scope on two fp16 terms, three products per MAC, operands within +-65504)";
 }
 
 const char* ds_last_error(const ds_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
@@ -1521,10 +1583,12 @@ static int ds_create_impl(const ds_config* cfg, ds_handle** out)
     if (!(cfg->is_cnn || cfg->is_rnn))
         return fail(nullptr, DS_ERR_INVALID, "at least one of is_cnn/is_rnn should be True");      // model.py:28-29
     if (cfg->precision != DS_PRECISION_FP32 && cfg->precision != DS_PRECISION_BF16 && cfg->precision != DS_PRECISION_BF16_ALL &&
-        cfg->precision != DS_PRECISION_BF16X3)
-        return fail(nullptr, DS_ERR_UNSUPPORTED, "precision must be DS_PRECISION_FP32, DS_PRECISION_BF16, DS_PRECISION_BF16_ALL or DS_PRECISION_BF16X3");
+        cfg->precision != DS_PRECISION_BF16X3 && cfg->precision != DS_PRECISION_FP16X2)
+        return fail(nullptr, DS_ERR_UNSUPPORTED, "precision must be DS_PRECISION_FP32, DS_PRECISION_BF16, DS_PRECISION_BF16_ALL, DS_PRECISION_BF16X3 or DS_PRECISION_FP16X2");
     if (cfg->precision == DS_PRECISION_BF16X3 && (cfg->reserved[2] & DS_TUNE_NO_FUSED))
         return fail(nullptr, DS_ERR_UNSUPPORTED, "DS_PRECISION_BF16X3 runs the fused inception kernels only (DS_TUNE_NO_FUSED asks for the layer-granular fp32 path)");
+    if (cfg->precision == DS_PRECISION_FP16X2 && (cfg->reserved[2] & DS_TUNE_NO_FUSED))
+        return fail(nullptr, DS_ERR_UNSUPPORTED, "DS_PRECISION_FP16X2 runs the fused inception kernels only (DS_TUNE_NO_FUSED asks for the layer-granular fp32 path)");
     if (cfg->kmer_len < 1 || cfg->kmer_len > 255 || (cfg->kmer_len & 1) == 0)
         return fail(nullptr, DS_ERR_INVALID, "kmer_len must be odd and in [1,255]");
     if (cfg->signal_len < 16 || cfg->class_num < 1 || cfg->class_num > 16)
@@ -1552,7 +1616,8 @@ static int ds_create_impl(const ds_config* cfg, ds_handle** out)
     h->J = (h->is_rnn ? 2 * HID : 0) + (h->is_cnn ? h->SF : 0);     // layers.py:248-255
     h->bf16 = cfg->precision == DS_PRECISION_BF16 || cfg->precision == DS_PRECISION_BF16_ALL;
     h->lstm_bf16 = cfg->precision == DS_PRECISION_BF16_ALL && h->is_rnn;
-    h->split = cfg->precision == DS_PRECISION_BF16X3;
+    h->split = cfg->precision == DS_PRECISION_BF16X3 || cfg->precision == DS_PRECISION_FP16X2;
+    h->terms = cfg->precision == DS_PRECISION_FP16X2 ? TERMS_FP16X2 : TERMS_BF16X3;
     // tuning / diagnostic knobs live in the handle's own config (no process-global state): reserved[2] = flags,
     // reserved[3] = LSTM tiling override, reserved[4] / [5] = fused-module tile bounds
     const int32_t flags = cfg->reserved[2];
@@ -3053,21 +3118,26 @@ int64_t ds_get_intermediate(ds_handle* h, const char* name, float* out, int64_t 
         const int64_t count = (int64_t)n * h->T * HID;
         if (count > capacity) return fail(h, DS_ERR_INVALID, "capacity too small");
         if (h->split) {
-            // split cells keep h fragment-major in three bf16 terms: [T][m-tile][k-step s of 16 units][term][lane = 32 * half + r][8]
+            // split cells keep h fragment-major in three bf16 (two fp16) terms: [T][m-tile][k-step s of 16 units][term][lane = 32 * half + r][8]
             // holds term p of units 16 s + 8 half .. + 7 of site 32 * mtile + r (lstm_cell_split_kernel); h = the terms' sum, exactly
-            const size_t per_t = (size_t)h->Bp32 * HID * 3;
+            // (two fp16 terms: to 22 bits)
+            const int nt = term_count(h->terms);
+            const size_t per_t = (size_t)h->Bp32 * HID * nt;
             std::vector<uint16_t> tb((size_t)h->T * per_t);
             if (hipMemcpy(tb.data(), h->cur->H[d][l], tb.size() * 2, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, DS_ERR_HIP, "hipMemcpy D2H");
             for (int i = 0; i < n; ++i)
                 for (int t = 0; t < h->T; ++t)
                     for (int c = 0; c < HID; ++c) {
                         float v = 0.0f;
-                        for (int p = 2; p >= 0; --p) {
-                            const size_t idx = (size_t)t * per_t + (size_t)(i / 32) * 32 * HID * 3 +
-                                               (((size_t)(c / 16) * 3 + p) * 64 + ((c % 16) / 8) * 32 + i % 32) * 8 + c % 8;
-                            const uint32_t u = (uint32_t)tb[idx] << 16;
+                        for (int p = nt - 1; p >= 0; --p) {
+                            const size_t idx = (size_t)t * per_t + (size_t)(i / 32) * 32 * HID * nt +
+                                               (((size_t)(c / 16) * nt + p) * 64 + ((c % 16) / 8) * 32 + i % 32) * 8 + c % 8;
                             float f;
-                            memcpy(&f, &u, 4);
+                            if (h->terms == TERMS_FP16X2) f = f16_to_f32(tb[idx]);
+                            else {
+                                const uint32_t u = (uint32_t)tb[idx] << 16;
+                                memcpy(&f, &u, 4);
+                            }
                             v += f;
                         }
                         out[((size_t)i * h->T + t) * HID + c] = v;
@@ -3236,7 +3306,12 @@ int ds_get_kernel_stat(ds_handle* h, int32_t index, char* name, int32_t name_cap
                        double* flops)
 {
     if (!h || index < 0 || index >= K_COUNT) return DS_ERR_INVALID;
-    if (name && name_cap > 0) { strncpy(name, kKernelNames[index], name_cap - 1); name[name_cap - 1] = 0; }
+    if (name && name_cap > 0) {
+        // (a DS_PRECISION_FP16X2 handle runs the two-term instantiation of every split kernel: the entry carries that name)
+        const char* hn = h->terms == TERMS_FP16X2 ? fp16x2_kernel_name((KernelClass)index) : nullptr;
+        strncpy(name, hn ? hn : kKernelNames[index], name_cap - 1);
+        name[name_cap - 1] = 0;
+    }
     if (launches) *launches = h->kstat[index].launches;
     if (total_ms) *total_ms = h->kstat[index].total_ms;
     if (flops) *flops = h->kstat[index].flops;

@@ -97,6 +97,24 @@ enum GemmCfg { CFG_CONV = 0, CFG_FC = 1, CFG_CONV_POOL = 4, CFG_FC_DENSE = 5,
 enum KernelClass { DS_KERNEL_TABLE(DS_KERNEL_ID) K_COUNT };
 #undef DS_KERNEL_ID
 static_assert(K_GEMM_CONV == 0 && K_EXTRACT_SITES == 50 && K_COUNT == 51, "the kernel table is ABI: append only");
+// Term format of the split-operand kernels (ds_split.hip): three bf16 terms and six products per MAC (DS_PRECISION_BF16X3), or two fp16
+// terms and three products (DS_PRECISION_FP16X2). Buffers, panels and images have the same layout in both with NT terms per k-step.
+// A handle has ONE format, so the two instantiations of a split kernel share the kernel's entry of the table above (same tile, same
+// launches, same place in a plan); ds_get_kernel_stat reports the entry under the name of the instantiation the handle runs.
+enum TermFormat { TERMS_BF16X3 = 0, TERMS_FP16X2 = 1 };
+inline int term_count(TermFormat f) { return f == TERMS_FP16X2 ? 2 : 3; }
+// what the profiler prints for a split kernel's entry on a DS_PRECISION_FP16X2 handle (nullptr: the entry has one instantiation)
+inline const char* fp16x2_kernel_name(KernelClass k)
+{
+    switch (k) {
+    case K_FUSEDS1: return "inception_fused_fp16x2_kernel<1>"; case K_FUSEDS2: return "inception_fused_fp16x2_kernel<2>";
+    case K_FUSEDS3: return "inception_fused_fp16x2_kernel<3>"; case K_LSTM_S11: return "lstm_cell_fp16x2_kernel<1,1>";
+    case K_LSTM_S12: return "lstm_cell_fp16x2_kernel<1,2>"; case K_LSTM_S22: return "lstm_cell_fp16x2_kernel<2,2>";
+    case K_LSTM_S28: return "lstm_cell_fp16x2_kernel<1,2,4,2>"; case K_DENSE_SPLIT: return "dense_fp16x2_kernel (+ pack_joint_fp16x2_kernel)";
+    case K_STEM23S: return "stem23_fp16x2_kernel"; case K_LSTM_XPROJ: return "lstm_xproj_fp16x2_kernel";
+    default: return nullptr;
+    }
+}
 
 // ---- fp32 BiLSTM cell launch (lstm_cell_kernel) ---------------------------------------------------------------
 // h and c of the fp32 BiLSTM live in MFMA-FRAGMENT-MAJOR buffers: [m-tile of 32 sites][k-group of 8 units][64 lanes][4]
@@ -148,7 +166,7 @@ struct LstmXproj {
     int nsteps;                // steps the launch covers: 1 = the first step's cells only (no image: the later cells compute their own initial
                                // values), T = all of them
 };
-hipError_t launch_lstm_xproj(const LstmXproj& X, hipStream_t s);
+hipError_t launch_lstm_xproj(TermFormat fmt, const LstmXproj& X, hipStream_t s);
 // Workgroup tile of a BiLSTM cell launch = the kernel instantiation that runs it. One cell's [mtiles x 32 sites] x [1024 gate columns]
 // product is cut into blocks of mtiles_per_wg m-tiles, each shared by wgs_per_mblock workgroups along the columns. Every tile of a
 // family gives the same bits (same K order per output element).
@@ -218,27 +236,27 @@ hipError_t launch_inception_fused(int tm, const FusedChain& c, hipStream_t s);
 size_t inception_fused_bf16_lds_bytes(int tm, int W, int spt);
 // split-operand form (ds_split.hip, DS_PRECISION_BF16X3): X / Y are the fp32 engine's fp32 rows, Bp1 / Bp3b / Bp4b / Bp5b / Bp5c point at
 // three-term panels (ds_engine.cpp pack_b_split); as in the fp32 form only the chain's first module may pool its input
-hipError_t launch_inception_fused_split(int tm, const FusedChain& c, hipStream_t s);
+hipError_t launch_inception_fused_split(TermFormat fmt, int tm, const FusedChain& c, hipStream_t s);
 size_t inception_fused_split_lds_bytes(int tm, int W, int spt);
 hipError_t configure_split_kernels();
 // BiLSTM cells of one diagonal with split operands (ds_split.hip): h buffers are fragment-major term images
-// [m-tile][k-step of 16 units][term][64 lanes][8 bf16] (48 KiB per m-tile), C.Bp points at pack_b_split panels, kg_stride = k-steps per
+// [m-tile][k-step of 16 units][term][64 lanes][8 bf16] (48 KiB per m-tile; two fp16 terms: 32 KiB), C.Bp points at pack_b_split panels, kg_stride = k-steps per
 // n-tile panel; c, bias, table, the gates and h_row as in the fp32 cells. tile = one of LT_S11 .. LT_S28.
-hipError_t launch_lstm_cells_split(LstmTile tile, const LstmLaunch& L, hipStream_t s);
+hipError_t launch_lstm_cells_split(LstmTile tile, TermFormat fmt, const LstmLaunch& L, hipStream_t s);
 // dense(J, J) of the three-step joint model with split operands: pack_joint_split_kernel writes the joint rows (three fp32 row
 // segments per site) as a fragment-major term image A, dense_split_kernel multiplies it with W1's pack_b_split panels into C [n][N]
 struct SplitDense {
     const float* seg[3];   // joint row segments, row-major fp32 [n][len]; unused ones have len 0 (lengths: multiples of 8)
     int len[3];
-    char* A;               // [mtiles][ksteps][3][1 KiB] workspace
-    const char* Bp;        // [ntiles_alloc][kg_stride][3][1 KiB]
+    char* A;               // [mtiles][ksteps][terms][1 KiB] workspace
+    const char* Bp;        // [ntiles_alloc][kg_stride][terms][1 KiB]
     float* C;              // [splits][n][N] fp32: partial sums over `splits` ranges of K (1: the product itself)
     int n, N, mtiles, ntiles, ntiles_alloc, ksteps, kg_stride;
     int splits;            // K in `splits` ranges (256 x 192 tile only); the reader sums the partial products in order (launch_head)
     size_t part_stride;    // floats between two partial products
     bool wide;             // the 256 x 192 tile (K in `splits` ranges); false: 128 x 96, one range
 };
-hipError_t launch_dense_split(const SplitDense& d, hipStream_t s);
+hipError_t launch_dense_split(TermFormat fmt, const SplitDense& d, hipStream_t s);
 
 // conv_layer2 (1x1, 64 -> 128) + conv_layer3 (1x3, 128 -> 256), both with folded BN + ReLU        layers.py:192-203
 struct Stem23Args {
@@ -251,7 +269,7 @@ struct Stem23Args {
 };
 hipError_t launch_stem23(const Stem23Args& a, hipStream_t s);
 // conv_layer2 + conv_layer3 with split operands (ds_split.hip): X / Y / C2 as the fp32 kernel, Bp2 / Bp3 = pack_b_split panels
-hipError_t launch_stem23_split(const Stem23Args& a, hipStream_t s);
+hipError_t launch_stem23_split(TermFormat fmt, const Stem23Args& a, hipStream_t s);
 size_t stem23_split_lds_bytes(int W, int spt);
 size_t stem23_lds_bytes(int W, int spt);
 // bf16 form (DS_PRECISION_BF16*): X / Y / C2 are bf16 rows (64 / 256 / 128 channels), Bp2 / Bp3 packed by pack_b_bf16

@@ -122,15 +122,17 @@ def build_parser(freq_file_given=True):
     g.add_argument("--model_path", "-m", required=True,
                    help="TensorFlow checkpoint prefix of a reference-trained model (<prefix>.index + .data-*), "
                         "or a DSAMDW01 weight file")
-    g.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3", "bf16", "bf16_all"],
+    g.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3", "fp16x2", "bf16", "bf16_all"],
                    help="fp32 (reference numerics, native fp32 matrix instructions); bf16x3 (fp32-class results: fp32 operands carried "
-                        "as three bf16 terms on the bf16 matrix pipe, held to the fp32 parity bars); bf16 / bf16_all (bf16 conv+FC "
+                        "as three bf16 terms on the bf16 matrix pipe, held to the fp32 parity bars); fp16x2 (fp32-class results on two fp16 "
+                        "terms and three products per MAC, held to the same bars; matrix operands -- folded weights and the activations "
+                        "of conv_layer2 onwards -- must stay within +-65504, a site beyond that comes out NaN); bf16 / bf16_all (bf16 conv+FC "
                         "operands with fp32 accumulate: fast, probabilities good to ~1e-2 only)")
     g.add_argument("--recheck_margin", type=float, default=0.0,
                    help="cascaded precision, with --precision bf16 / bf16_all: sites whose |prob_1 - prob_0| comes out below this "
                         "margin are run again in --recheck_precision and take that result (default 0 = off; an fp32-class "
                         "--precision has nothing to recheck and is refused)")
-    g.add_argument("--recheck_precision", default="fp32", choices=["fp32", "bf16x3"],
+    g.add_argument("--recheck_precision", default="fp32", choices=["fp32", "bf16x3", "fp16x2"],
                    help="the mode of the second forward of --recheck_margin")
     g.add_argument("--extract_on", default="cpu", choices=["cpu", "gpu"],
                    help="fast5-directory input only: compute the per-site features on the host (cpu, default) or on the GPU next "

@@ -556,7 +556,7 @@ def combine_reference(form: int, text, begin, end, chrom, flags, rec_len, bitmap
 
 # ds_config.precision (include/deepsignal_hip.h): "bf16" = bf16 conv + FC operands with fp32 accumulation, fp32 BiLSTM;
 # "bf16_all" = also bf16 h / weight operands in the LSTM matmuls (fp32 accumulate, gates, cell state)
-PRECISIONS = {"fp32": 0, "bf16": 1, "bf16_all": 2, "bf16x3": 3}
+PRECISIONS = {"fp32": 0, "bf16": 1, "bf16_all": 2, "bf16x3": 3, "fp16x2": 4}
 TUNE_NO_FUSED, TUNE_SERIAL, TUNE_DEBUG_STAMPS, TUNE_NO_FOLD_FC, TUNE_NO_CHAIN, TUNE_SHARED_EVENT_STREAM, TUNE_SPLIT_DENSE_NARROW, TUNE_NO_LSTM_XPROJ, TUNE_LSTM_XPROJ_ALL = 1, 2, 4, 8, 16, 32, 64, 128, 256     # ds_config.reserved[2]
 LSTM_TILINGS = {"auto": 0, "narrow": 1, "wide": 2, "lds1": 3, "lds2": 4, "wide8": 5}     # ds_config.reserved[3]
 

@@ -45,6 +45,18 @@ extern "C" {
  * DS_PRECISION_FP32 (tests/test_gpu_split.py; CPU statement oracle/torch_statement.py::forward_split). Which layers run
  * split is listed by ds_version() / DESIGN.md section 11; the rest runs the DS_PRECISION_FP32 kernels. */
 #define DS_PRECISION_BF16X3 3
+/* fp32-class results on TWO fp16 terms and three products per MAC, in the layers DS_PRECISION_BF16X3 runs split (conv_layer2 / 3,
+ * the eleven modules, the BiLSTM recurrent and lower-layer products, dense(J, J)); weights are split at load, activations where
+ * DS_PRECISION_BF16X3 splits them. The contract:
+ *   h0 = fp16(x), h1 = fp16(x - h0): round to nearest even, subnormal terms kept, the difference taken in fp32 (22 significant bits);
+ *   per MAC the products a1 b0, a0 b1, a0 b0 in that order (small first), fp32 accumulation, no scaling;
+ *   the conversion does not saturate: a matrix operand beyond +-65504 becomes Inf and its site comes out NaN -- visible, never a
+ *   wrong finite number (trained-regime activations stay below 20);
+ *   bias, ReLU, pools, the residual add, gates, state and the head are fp32 as in DS_PRECISION_BF16X3.
+ * Held to the DS_PRECISION_FP32 parity bars (tests/test_gpu_fp16x2.py; CPU statement tests/fp16x2_statement.py). v_mfma_f32_32x32x16_f16
+ * runs at the cycles of the bf16 form: half the matrix instructions and two thirds of the operand bytes of DS_PRECISION_BF16X3.
+ * DS_TUNE_NO_FUSED is refused (DS_ERR_UNSUPPORTED), as for DS_PRECISION_BF16X3. */
+#define DS_PRECISION_FP16X2 4
 
 typedef struct ds_handle ds_handle;
 
@@ -61,7 +73,7 @@ typedef struct ds_config {
     int32_t is_rnn;
     int32_t is_base;
     int32_t device;       /* HIP device ordinal */
-    int32_t precision;    /* DS_PRECISION_FP32 | DS_PRECISION_BF16 | DS_PRECISION_BF16_ALL | DS_PRECISION_BF16X3 */
+    int32_t precision;    /* DS_PRECISION_FP32 | DS_PRECISION_BF16 | DS_PRECISION_BF16_ALL | DS_PRECISION_BF16X3 | DS_PRECISION_FP16X2 */
     int32_t max_batch;    /* largest n per device pass (workspaces are sized for it); larger n is looped */
     int32_t reserved[7];  /* reserved[0] != 0: debug mode — keep every module output for ds_get_intermediate;
                              reserved[1]: forwards in flight for ds_forward_device / ds_submit (pipeline slots, each
@@ -212,7 +224,9 @@ int ds_reset_stage_times(ds_handle *h);
 /* Per-kernel accumulators of the same profiling mode: every launch is bracketed by its own HIP
  * event pair on the stream it runs on. name = the __global__ function (as rocprofv3 prints it),
  * launches / total_ms / flops = launch count, summed device time and summed ALGORITHMIC FLOPs
- * (2*M*N*K of the GEMMs the launch carries) since the last reset. */
+ * (2*M*N*K of the GEMMs the launch carries) since the last reset. Count and order of the entries are the same for every handle;
+ * the entries of the split-operand kernels carry the name of the instantiation the handle's precision runs (`..._split_kernel` with
+ * DS_PRECISION_BF16X3, `..._fp16x2_kernel` with DS_PRECISION_FP16X2). */
 int ds_num_kernels(ds_handle *h);
 int ds_get_kernel_stat(ds_handle *h, int32_t index, char *name, int32_t name_cap, int64_t *launches,
                        double *total_ms, double *flops);

@@ -5,7 +5,8 @@
 compares, per kernel, the text from its label to .end_amdhsa_kernel and its amdhsa.kernels metadata entry, ignoring only lines that
 carry the __hip_cuid_ symbol (a hash of the source text). Prints a markdown table; exit status 1 if a kernel present in both differs
 or one exists only in the change. --normalise-label-ordinals: local labels (.LBB<n>_<m>, .Lfunc_end<n>) carry the function's ordinal
-in the module, which shifts for every later kernel when an instantiation is removed; the option replaces <n>."""
+in the module, which shifts for every later kernel when an instantiation is added or removed; the option replaces <n> (and the
+padding between such a label and its comment, which follows the label's length)."""
 import re, sys, subprocess
 
 def demangle(names):
@@ -16,6 +17,8 @@ def kernels(path):
     lines = [l for l in open(path).read().split("\n") if "__hip_cuid_" not in l]
     if NORM:      # local labels carry the function's ordinal in the module, which shifts when an instantiation leaves
         lines = [re.sub(r"BB\d+_", "BBn_", re.sub(r"\.Lfunc_end\d+", ".Lfunc_endn", l)) for l in lines]
+        # ... and a label's trailing comment is aligned to a column, so the padding moves when the ordinal gains or loses a digit
+        lines = [re.sub(r"^(\.LBBn_\d+:)\s+;", r"\1 ;", l) for l in lines]
     body, meta = {}, {}
     names = [m.group(1) for l in lines if (m := re.match(r"\s*\.amdhsa_kernel\s+(\S+)", l))]
     idx = {m.group(1): i for i, l in enumerate(lines) if (m := re.match(r"(_Z\w+):", l))}

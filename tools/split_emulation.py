@@ -6,7 +6,9 @@ fp32-accumulated bf16-term arithmetic land on the three weight sets of the parit
 Rows: the native fp32 oracle (what the fp32 engine is held to), oracle/torch_statement.forward_split with three terms /
 six products and two terms / three products, split in the fused inception chain only (stage 1 of the plan) and in every
 matrix product of the path (modules + conv_layer2/3 + BiLSTM + dense 6032 x 6032), and forward_bf16 (the shipped bf16 modes'
-rounding points). Columns per weight set: mean / max abs difference of the sigmoid outputs to the float64 oracle, and the share
+rounding points), and the DS_PRECISION_FP16X2 arms: tests/fp16x2_statement.forward_fp16x2 (two fp16 terms, three products, subnormal
+terms kept) in every matrix product, and the same with every term below 2^-14 flushed to zero (what an MFMA that drops fp16 subnormal
+inputs would compute: not the contract, the measure of what rests on the subnormals). Columns per weight set: mean / max abs difference of the sigmoid outputs to the float64 oracle, and the share
 of sites whose label differs from float64's. No GPU involved."""
 import json
 import os
@@ -17,8 +19,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from deepsignal_amd import synth, weights  # noqa: E402
 from oracle import oracle, torch_statement as ts  # noqa: E402
+import fp16x2_statement as hs  # noqa: E402
 
 
 def weight_sets():
@@ -42,6 +46,9 @@ def main():
         ("split2 (3 products), inception chain only", dict(terms=2, scope=("modules",))),
         ("split2 (3 products), every matrix product", dict(terms=2, scope=everything)),
         ("split3, every matrix product, float64 accumulate (the dropped products alone)", dict(terms=3, scope=everything, acc_dtype=torch.float64)),
+        ("fp16x2 (2 fp16 terms, 3 products), every matrix product", dict(fp16=True)),
+        ("fp16x2, every matrix product, terms below 2^-14 flushed to zero (NOT the contract)", dict(fp16=True, flush=True)),
+        ("fp16x2, every matrix product, float64 accumulate (the dropped products and bits alone)", dict(fp16=True, acc_dtype=torch.float64)),
         ("bf16 (shipped rounding points)", "bf16"),
         ("bf16_all (shipped rounding points)", "bf16_all"),
     ]
@@ -56,6 +63,8 @@ def main():
                 act, pred = ts.forward_bf16(w, feats)
             elif kw == "bf16_all":
                 act, pred = ts.forward_bf16(w, feats, lstm_bf16=True)
+            elif kw.get("fp16"):
+                act, pred = hs.forward_fp16x2(w, feats, **{k: v for k, v in kw.items() if k != "fp16"})
             else:
                 act, pred = ts.forward_split(w, feats, **kw)
             d = np.abs(act.astype(np.float64) - a64)
