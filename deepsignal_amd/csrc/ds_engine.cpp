@@ -9,6 +9,7 @@
 #include "ds_freq.h"
 #include "ds_combine.h"
 #include "ds_eval.h"
+#include "ds_train.h"
 
 #include <algorithm>
 #include <cmath>
@@ -274,6 +275,13 @@ struct ds_handle {
     int64_t cb_chunks = 0;
     dse::Eval* eval = nullptr;            // evaluate --on gpu: the open run (ds_eval_begin .. ds_eval_end); table, counters and buffers are its own
     Times<4> ev_t;        // batches of the evaluate runs ended so far (the open run's are added on top)
+    // training (ds_train_begin .. ds_train_end, ds_train.hip): the RNN-only, no-embedding variant keeps the tensors it was loaded with
+    // (`kept`: what ds_train_begin starts from and ds_train_set_tensor replaces) and remembers which device blocks hold the packed
+    // weights (`weight_allocs`), so that ds_train_sync_weights can pack the current parameters in their place
+    std::map<std::string, HostTensor> kept;
+    std::vector<void*> weight_allocs;
+    dstr::Trainer* train = nullptr;
+    bool training = false;
     // pipelining: consecutive forwards rotate over independent slots (own workspace, streams, graphs), so the
     // dependency chain of one 512-site forward overlaps the next ones'; weights are shared
     std::vector<Slot> slots;
@@ -750,6 +758,7 @@ int finalize_weights(ds_handle* h)
         if ((rc = upload(h, &h->fc2, w2->data))) return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->cur->s0));
+    if (h->is_rnn && !h->is_cnn && !h->is_base) h->kept = h->host;      // the trainable variant (ds_train_begin)
     h->host.clear();
     h->finalized = true;
     return DS_OK;
@@ -1700,6 +1709,7 @@ void ds_destroy(ds_handle* h)
     delete h->freq;
     delete h->combine;
     delete h->eval;
+    delete h->train;
     for (void* p : h->allocs) hipFree(p);
     (void)hipGetLastError();      // nothing a teardown call returned may surface in a later handle's first launch
     delete h;
@@ -1723,7 +1733,9 @@ static int ds_finalize_weights_impl(ds_handle* h)
     if (!h) return DS_ERR_INVALID;
     if (h->finalized) return fail(h, DS_ERR_INVALID, "weights already finalized");
     hipSetDevice(h->cfg.device);
+    const size_t allocs_before = h->allocs.size();
     int rc = finalize_weights(h);
+    h->weight_allocs.assign(h->allocs.begin() + allocs_before, h->allocs.end());
     if (!rc) prepare_slots(h);
     return rc;
 }
@@ -3325,6 +3337,168 @@ int ds_set_graph(ds_handle* h, int32_t enable)
     return DS_OK;
 }
 
+// ---- training step of the RNN-only model (ds_train.hip; model.py:70-116 with the optimiser of train.py / denoise.py) ------------
+// The run's state is a dstr::Trainer of its own (parameters, moments, stored activations, stream): the inference plan and the
+// pipeline slots are untouched until ds_train_sync_weights packs the current parameters for them.
+static int train_ready(ds_handle* h, const char* who)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (!h->train || !h->training) return fail(h, DS_ERR_INVALID, std::string(who) + ": no training run is open (ds_train_begin first)");
+    if (tickets_in_flight(h)) return fail(h, DS_ERR_INVALID, std::string(who) + ": pipeline tickets are still in flight");
+    return DS_OK;
+}
+
+static int ds_train_begin_impl(ds_handle* h, const ds_train_config* cfg)
+{
+    if (!h) return DS_ERR_INVALID;
+    if (!cfg) return fail(h, DS_ERR_INVALID, "ds_train_begin: null config");
+    if (h->is_cnn) return fail(h, DS_ERR_UNSUPPORTED, "ds_train_begin: this release trains the RNN-only model (is_cnn must be 0: the signal model has no backward)");
+    if (h->is_base) return fail(h, DS_ERR_UNSUPPORTED, "ds_train_begin: this release trains the RNN-only model (is_base must be 0: the embedding has no gradient)");
+    if (h->C != 2) return fail(h, DS_ERR_UNSUPPORTED, "ds_train_begin: class_num must be 2");
+    if (h->cfg.precision != DS_PRECISION_FP32) return fail(h, DS_ERR_UNSUPPORTED, "ds_train_begin: precision must be DS_PRECISION_FP32");
+    if (!h->finalized) return fail(h, DS_ERR_INVALID, "ds_train_begin: weights not loaded");
+    if (tickets_in_flight(h)) return fail(h, DS_ERR_INVALID, "ds_train_begin: pipeline tickets are still in flight");
+    if (!(cfg->keep_prob > 0.f && cfg->keep_prob <= 1.f)) return fail(h, DS_ERR_INVALID, "ds_train_begin: keep_prob must lie in (0, 1]");
+    if (!(cfg->pos_weight > 0.f) || std::isinf(cfg->pos_weight)) return fail(h, DS_ERR_INVALID, "ds_train_begin: pos_weight must be positive and finite");
+    if (cfg->beta1 < 0.f || cfg->beta1 >= 1.f || cfg->beta2 < 0.f || cfg->beta2 >= 1.f || cfg->epsilon < 0.f || std::isnan(cfg->beta1 + cfg->beta2 + cfg->epsilon))
+        return fail(h, DS_ERR_INVALID, "ds_train_begin: beta1, beta2 must lie in [0, 1) and epsilon must not be negative");
+    std::vector<float> params((size_t)dstr::PARAM_FLOATS);
+    for (int i = 0; i < dstr::NTENSOR; ++i) {
+        const std::string name = dstr::tensor_name(i);
+        auto it = h->kept.find(name);
+        if (it == h->kept.end() || (int64_t)it->second.data.size() != dstr::tensor_floats(i))
+            return fail(h, DS_ERR_INVALID, "ds_train_begin: missing/bad tensor " + name);
+        std::copy(it->second.data.begin(), it->second.data.end(), params.begin() + dstr::tensor_off(i));
+    }
+    dstr::Config c;
+    c.keep_prob = cfg->keep_prob; c.pos_weight = cfg->pos_weight; c.seed = cfg->seed;
+    if (cfg->beta1 != 0.f) c.beta1 = cfg->beta1;
+    if (cfg->beta2 != 0.f) c.beta2 = cfg->beta2;
+    if (cfg->epsilon != 0.f) c.epsilon = cfg->epsilon;
+    if (!h->train) h->train = new dstr::Trainer();
+    std::string err;
+    const int rc = h->train->begin(h->cfg.device, h->T, h->B, c, params.data(), &err);
+    if (rc) { delete h->train; h->train = nullptr; h->training = false; return fail(h, rc, "ds_train_begin: " + err); }
+    h->training = true;
+    return DS_OK;
+}
+
+static int ds_train_set_tensor_impl(ds_handle* h, const char* name, const float* data, int64_t count)
+{
+    if (!h || !name || !data) return fail(h, DS_ERR_INVALID, "ds_train_set_tensor: bad argument");
+    if (!h->finalized || h->kept.empty()) return fail(h, DS_ERR_INVALID, "ds_train_set_tensor: the handle holds no trainable weights (RNN-only, is_base 0, loaded)");
+    const int idx = dstr::tensor_index(name);
+    if (idx < 0 || count != dstr::tensor_floats(idx)) return fail(h, DS_ERR_INVALID, std::string("ds_train_set_tensor: unknown tensor or wrong size: ") + name);
+    h->kept[name].data.assign(data, data + count);
+    return DS_OK;
+}
+
+static int ds_train_step_impl(ds_handle* h, int32_t n, const float* means, const float* stds, const float* sanums, const int32_t* labels, float lr,
+                              float* loss, int32_t* pred)
+{
+    if (int rc = train_ready(h, "ds_train_step")) return rc;
+    if (n < 1 || n > h->B) return fail(h, DS_ERR_INVALID, "ds_train_step: n must lie in [1, max_batch]");
+    if (!means || !stds || !sanums || !labels) return fail(h, DS_ERR_INVALID, "ds_train_step: null buffer");
+    if (std::isnan(lr)) return fail(h, DS_ERR_INVALID, "ds_train_step: lr is NaN");
+    for (int32_t i = 0; i < n; ++i)
+        if (labels[i] != 0 && labels[i] != 1) return fail(h, DS_ERR_INVALID, "ds_train_step: label " + std::to_string(labels[i]) + " of row " + std::to_string(i) + " is outside {0, 1}");
+    std::string err;
+    const int rc = h->train->step(n, means, stds, sanums, labels, lr, loss, pred, &err);
+    return rc ? fail(h, rc, "ds_train_step: " + err) : DS_OK;
+}
+
+static int ds_train_sync_weights_impl(ds_handle* h)
+{
+    if (int rc = train_ready(h, "ds_train_sync_weights")) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    std::vector<float> params((size_t)dstr::PARAM_FLOATS);
+    std::string err;
+    if (int rc = h->train->read_params(params.data(), &err)) return fail(h, rc, "ds_train_sync_weights: " + err);
+    // nothing enqueued may still read the packed weights; the plans (launch descriptors, captured graphs) name them and go too
+    for (Slot& sl : h->slots) {
+        HIPCHK(h, hipStreamSynchronize(sl.s0));
+        HIPCHK(h, hipStreamSynchronize(sl.s1));
+    }
+    for (Slot& sl : h->slots) {
+        for (auto& kv : sl.plans) destroy_plan(h, kv.second);
+        sl.plans.clear();
+    }
+    for (void* p : h->weight_allocs) {
+        auto it = std::find(h->allocs.begin(), h->allocs.end(), p);
+        if (it != h->allocs.end()) { h->allocs.erase(it); hipFree(p); }
+    }
+    h->weight_allocs.clear();
+    std::map<std::string, HostTensor> loaded = std::move(h->kept);      // what ds_train_begin starts from stays what was loaded
+    h->host.clear();
+    for (int i = 0; i < dstr::NTENSOR; ++i) {
+        const std::string name = dstr::tensor_name(i);
+        HostTensor t;
+        t.shape = loaded[name].shape;
+        t.data.assign(params.begin() + dstr::tensor_off(i), params.begin() + dstr::tensor_off(i) + dstr::tensor_floats(i));
+        h->host[name] = std::move(t);
+    }
+    h->finalized = false;
+    h->cur = &h->slots[0];
+    const int rc = ds_finalize_weights_impl(h);
+    h->kept = std::move(loaded);
+    return rc;
+}
+
+static int64_t train_get(ds_handle* h, const char* who, const char* name, float* out, int64_t cap, bool grad)
+{
+    if (int rc = train_ready(h, who)) return rc;
+    const int idx = dstr::tensor_index(name);
+    if (idx < 0 || !out) return fail(h, DS_ERR_INVALID, std::string(who) + ": unknown tensor " + (name ? name : "(null)"));
+    std::string err;
+    const int64_t rc = h->train->get(grad ? h->train->G : h->train->P, idx, out, cap, &err);
+    return rc < 0 ? fail(h, (int)rc, std::string(who) + ": " + err) : rc;
+}
+
+static int64_t ds_train_get_mask_impl(ds_handle* h, const char* stream, uint8_t* out, int64_t cap)
+{
+    if (int rc = train_ready(h, "ds_train_get_mask")) return rc;
+    const int sid = dstr::stream_index(stream);
+    if (sid < 0 || !out) return fail(h, DS_ERR_INVALID, std::string("ds_train_get_mask: unknown stream ") + (stream ? stream : "(null)"));
+    if (h->train->last_n == 0) return fail(h, DS_ERR_INVALID, "ds_train_get_mask: no step has run yet");
+    std::string err;
+    const int64_t rc = h->train->get_mask(sid, out, cap, &err);
+    return rc < 0 ? fail(h, (int)rc, "ds_train_get_mask: " + err) : rc;
+}
+
+int ds_train_end(ds_handle* h)
+{
+    if (!h) return DS_ERR_INVALID;
+    hipSetDevice(h->cfg.device);
+    delete h->train;
+    h->train = nullptr;
+    h->training = false;
+    return DS_OK;
+}
+
+int ds_train_mask_reference(uint64_t seed, int64_t step, const char* stream, int32_t n, int32_t kmer_len, float keep_prob, uint8_t* out)
+{
+    const int sid = dstr::stream_index(stream);
+    if (sid < 0 || n < 0 || kmer_len < 1 || !out || !(keep_prob > 0.f && keep_prob <= 1.f)) return DS_ERR_INVALID;
+    dstr::mask_reference(seed, step, sid, n, kmer_len, keep_prob, out);
+    return DS_OK;
+}
+
+int ds_get_train_times(ds_handle* h, int32_t reset, int64_t* steps, double* ms)
+{
+    if (!h || !steps || !ms) return DS_ERR_INVALID;
+    *steps = h->train ? h->train->steps_timed : 0;
+    for (int i = 0; i < dstr::NPHASE; ++i) ms[i] = h->train ? h->train->ms[i] : 0.0;
+    if (reset && h->train) { h->train->steps_timed = 0; for (double& v : h->train->ms) v = 0; }
+    return DS_OK;
+}
+
+int ds_train_begin(ds_handle* h, const ds_train_config* cfg) { return guarded(h, [&] { return ds_train_begin_impl(h, cfg); }); }
+int ds_train_set_tensor(ds_handle* h, const char* name, const float* data, int64_t count) { return guarded(h, [&] { return ds_train_set_tensor_impl(h, name, data, count); }); }
+int ds_train_step(ds_handle* h, int32_t n, const float* means, const float* stds, const float* sanums, const int32_t* labels, float lr, float* loss, int32_t* pred) { return guarded(h, [&] { return ds_train_step_impl(h, n, means, stds, sanums, labels, lr, loss, pred); }); }
+int ds_train_sync_weights(ds_handle* h) { return guarded(h, [&] { return ds_train_sync_weights_impl(h); }); }
+int64_t ds_train_get_tensor(ds_handle* h, const char* name, float* out, int64_t cap) { return guarded(h, [&] { return train_get(h, "ds_train_get_tensor", name, out, cap, false); }); }
+int64_t ds_train_get_grad(ds_handle* h, const char* name, float* out, int64_t cap) { return guarded(h, [&] { return train_get(h, "ds_train_get_grad", name, out, cap, true); }); }
+int64_t ds_train_get_mask(ds_handle* h, const char* stream, uint8_t* out, int64_t cap) { return guarded(h, [&] { return ds_train_get_mask_impl(h, stream, out, cap); }); }
 
 int ds_create(const ds_config* cfg, ds_handle** out) { return guarded(nullptr, [&] { return ds_create_impl(cfg, out); }); }
 int ds_set_tensor(ds_handle* h, const char* name, const float* data, const int64_t* shape, int32_t ndim) { return guarded(h, [&] { return ds_set_tensor_impl(h, name, data, shape, ndim); }); }

@@ -1,0 +1,593 @@
+// ds_train.hip — one training step of the RNN-only model on gfx950 (denoise; model.py:70-116, layers.py:45-72,247-264 restated):
+// forward with dropout, weighted cross entropy, back-propagation through time, Adam. fp32 throughout, every matrix product on
+// v_mfma_f32_32x32x2_f32. No floating-point atomics: a reduction that is split over workgroups writes its partial sums as slabs
+// and reduce_slabs_kernel adds them in a fixed order, so a step is a pure function of (weights, batch, seed, step).
+//
+// Layout. Activations are time-major per (direction d, layer l): element ((d * 3 + l) * T + t) * B + row, B = max_batch, t = the step
+// in the order the stack processes the sequence (bw: t = 0 is the last base). A step of one cell is then a dense [n][width] matrix
+// and the same launch serves both directions through a batch stride. Z holds a cell's pre-activations, which cell_forward_kernel
+// replaces by the gate activations (sigmoid i, tanh j, sigmoid (f + 1), sigmoid o) and cell_backward_kernel by the gate gradients
+// dz, the operand of every later product: d[x | h] = dz K^T during the sweep, dK = [X | H_prev]^T dZ and db after it.
+#include "ds_train.h"
+
+#include "../../include/deepsignal_hip.h"
+
+#include <algorithm>
+#include <vector>
+
+namespace dstr {
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int TM = 64, TN = 64, KC = 16;      // workgroup tile of train_gemm_kernel (four waves, 32 x 32 each), K staged per LDS chunk
+
+// C[z] (+)= op(A[z]) op(B[z]) (+ bias[z]), op = identity or transpose, z = (z1, z2) a two-level batch with element strides. Every
+// operand element is fetched under a bounds check (M, N, K need not be multiples of the tile) and rows >= M are never touched.
+struct GemmArgs {
+    const float* A;
+    const float* Bm;
+    float* C;
+    const float* bias;       // [N] per z2 (stride sBias2), or nullptr
+    int M, N, K, lda, ldb, ldc, transA, transB, acc;
+    int nb1, nb2;
+    long long sA1, sA2, sB1, sB2, sC1, sC2, sBias2;
+};
+
+__global__ __launch_bounds__(256) void train_gemm_kernel(GemmArgs g)
+{
+    __shared__ float As[KC][TM + 1];
+    __shared__ float Bs[KC][TN + 1];
+    const int z1 = blockIdx.z / g.nb2, z2 = blockIdx.z % g.nb2;
+    const float* A = g.A + z1 * g.sA1 + z2 * g.sA2;
+    const float* Bm = g.Bm + z1 * g.sB1 + z2 * g.sB2;
+    float* C = g.C + z1 * g.sC1 + z2 * g.sC2;
+    const int m0 = blockIdx.y * TM, n0 = blockIdx.x * TN;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    f32x16 acc;
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int k0 = 0; k0 < g.K; k0 += KC) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int e = tid + 256 * r;
+            int i, k;
+            if (g.transA) { i = e & 63; k = e >> 6; } else { k = e & 15; i = e >> 4; }
+            const int gi = m0 + i, gk = k0 + k;
+            float v = 0.f;
+            if (gi < g.M && gk < g.K) v = g.transA ? A[(size_t)gk * g.lda + gi] : A[(size_t)gi * g.lda + gk];
+            As[k][i] = v;
+            int j;
+            if (g.transB) { k = e & 15; j = e >> 4; } else { j = e & 63; k = e >> 6; }
+            const int gj = n0 + j, gk2 = k0 + k;
+            v = 0.f;
+            if (gj < g.N && gk2 < g.K) v = g.transB ? Bm[(size_t)gj * g.ldb + gk2] : Bm[(size_t)gk2 * g.ldb + gj];
+            Bs[k][j] = v;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < KC; kk += 2) {
+            const float a = As[kk + (lane >> 5)][wm * 32 + (lane & 31)];
+            const float b = Bs[kk + (lane >> 5)][wn * 32 + (lane & 31)];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    const int col = n0 + wn * 32 + (lane & 31);
+    if (col >= g.N) return;
+    const float bv = g.bias ? g.bias[z2 * g.sBias2 + col] : 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (row >= g.M) continue;
+        float* p = C + (size_t)row * g.ldc + col;
+        float v = acc[r] + bv;
+        if (g.acc) v += *p;
+        *p = v;
+    }
+}
+
+__device__ inline float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
+
+// layer-0 inputs in processing order: X0[d][t][row] = (mean, std, length, 0) of base t (fw) or T - 1 - t (bw)
+__global__ void gather_x0_kernel(const float* in, float* X0, int n, int T, int B)
+{
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= 2 * T * n) return;
+    const int row = idx % n, t = (idx / n) % T, d = idx / (n * T);
+    const int src = d == 0 ? t : T - 1 - t;
+    float4 v;
+    v.x = in[((size_t)0 * B + row) * T + src];
+    v.y = in[((size_t)1 * B + row) * T + src];
+    v.z = in[((size_t)2 * B + row) * T + src];
+    v.w = 0.f;
+    reinterpret_cast<float4*>(X0)[((size_t)d * T + t) * B + row] = v;
+}
+
+struct CellArgs {
+    float *Z, *Cs, *H, *Y;          // this step's [B][1024] / [B][256] blocks of direction 0; direction 1 lies sZ / sH floats further
+    const float* Cprev;             // c_{t-1} of direction 0, nullptr at the first step
+    long long sZ, sH;
+    int n, t, stream0;              // mask stream of direction 0 (direction 1: + 3)
+    float inv_keep;
+    uint32_t thr;
+    uint64_t seed;
+    long long step;
+};
+
+// gates, state and output of one step (layers.py:45-72): c = sigmoid(f + 1) c_prev + sigmoid(i) tanh(j), h = sigmoid(o) tanh(c),
+// y = h / keep_prob * mask (DropoutWrapper, output only: the recurrent h is not dropped)
+__global__ void cell_forward_kernel(CellArgs a)
+{
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x, d = blockIdx.y;
+    if (idx >= a.n * HID) return;
+    const int row = idx / HID, u = idx % HID;
+    float* z = a.Z + d * a.sZ + (size_t)row * GATES;
+    const size_t o = d * a.sH + (size_t)row * HID + u;
+    const float si = sigmoidf_(z[u]), tj = tanhf(z[HID + u]), sf = sigmoidf_(z[2 * HID + u] + FORGET_BIAS), so = sigmoidf_(z[3 * HID + u]);
+    const float cp = a.Cprev ? a.Cprev[o] : 0.f;
+    const float c = sf * cp + si * tj;
+    const float h = so * tanhf(c);
+    z[u] = si; z[HID + u] = tj; z[2 * HID + u] = sf; z[3 * HID + u] = so;
+    a.Cs[o] = c;
+    a.H[o] = h;
+    const uint64_t rk = row_key(stream_key(a.seed, a.step, a.stream0 + 3 * d), row);
+    a.Y[o] = kept(rk, a.t, u, a.thr) ? h * a.inv_keep : 0.f;
+}
+
+struct CellBackArgs {
+    float* Z;                       // gate activations in, gate gradients out
+    const float *Cs, *Cprev;        // c_t, c_{t-1} (nullptr at the first step)
+    const float* dY;                // gradient of y_t, [row][ldY] of direction 0 (direction 1: + sdY), or nullptr
+    const float* DH;                // recurrent gradient from step t + 1 [2][B][256], nullptr at the last step
+    float* DC;                      // [2][B][256] carried dc (read unless `last`, written always)
+    long long sZ, sH, sdY, sD;
+    int n, t, stream0, ldY, last;
+    float inv_keep;
+    uint32_t thr;
+    uint64_t seed;
+    long long step;
+};
+
+__global__ void cell_backward_kernel(CellBackArgs a)
+{
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x, d = blockIdx.y;
+    if (idx >= a.n * HID) return;
+    const int row = idx / HID, u = idx % HID;
+    float* z = a.Z + d * a.sZ + (size_t)row * GATES;
+    const size_t o = d * a.sH + (size_t)row * HID + u, od = d * a.sD + (size_t)row * HID + u;
+    float dh = 0.f;
+    if (a.dY) {
+        const uint64_t rk = row_key(stream_key(a.seed, a.step, a.stream0 + 3 * d), row);
+        if (kept(rk, a.t, u, a.thr)) dh = a.dY[d * a.sdY + (size_t)row * a.ldY + u] * a.inv_keep;
+    }
+    if (a.DH) dh += a.DH[od];
+    const float si = z[u], tj = z[HID + u], sf = z[2 * HID + u], so = z[3 * HID + u];
+    const float tc = tanhf(a.Cs[o]);
+    const float cp = a.Cprev ? a.Cprev[o] : 0.f;
+    float dc = dh * so * (1.f - tc * tc);
+    if (!a.last) dc += a.DC[od];
+    z[u] = dc * tj * si * (1.f - si);
+    z[HID + u] = dc * si * (1.f - tj * tj);
+    z[2 * HID + u] = dc * cp * sf * (1.f - sf);
+    z[3 * HID + u] = dh * tc * so * (1.f - so);
+    a.DC[od] = dc * sf;
+}
+
+struct HeadArgs {
+    const float *fc1, *W2;
+    float *drop1, *dfc1, *logits, *dfc2, *rowloss;
+    const int32_t* labels;
+    int32_t* pred;
+    int n;
+    float inv_keep, pos_weight, grad_scale;     // grad_scale = 1 / (number of loss terms)
+    uint32_t thr;
+    uint64_t seed;
+    long long step;
+};
+
+// stable weighted cross entropy on one logit (tf.nn.weighted_cross_entropy_with_logits) and its derivative
+__device__ inline float wce(float x, float zt, float pw, float* dx)
+{
+    const float q = 1.f + (pw - 1.f) * zt;
+    const float sp = log1pf(expf(-fabsf(x))) + fmaxf(-x, 0.f);      // softplus(-x)
+    *dx = (1.f - zt) - q * sigmoidf_(-x);
+    return (1.f - zt) * x + q * sp;
+}
+
+// one workgroup per row: dropout of fc1, fc2 = drop1 W2, dropout of the logits (layers.py:257-264), the row's loss terms and
+// prediction (model.py:100-116), and the gradient back to fc1. The 512-term sums are a fixed tree over the workgroup.
+__global__ __launch_bounds__(256) void train_head_kernel(HeadArgs a)
+{
+    __shared__ float red[2][256];
+    __shared__ float dl[2];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const uint64_t rk1 = row_key(stream_key(a.seed, a.step, STREAM_FC1), row);
+    float dv[2], p0 = 0.f, p1 = 0.f;
+    bool k1[2];
+    for (int s = 0; s < 2; ++s) {
+        const int k = tid + 256 * s;
+        k1[s] = kept(rk1, 0, k, a.thr);
+        dv[s] = k1[s] ? a.fc1[(size_t)row * FC + k] * a.inv_keep : 0.f;
+        a.drop1[(size_t)row * FC + k] = dv[s];
+        p0 = fmaf(dv[s], a.W2[k * 2], p0);
+        p1 = fmaf(dv[s], a.W2[k * 2 + 1], p1);
+    }
+    red[0][tid] = p0; red[1][tid] = p1;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) { red[0][tid] += red[0][tid + w]; red[1][tid] += red[1][tid + w]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const uint64_t rk2 = row_key(stream_key(a.seed, a.step, STREAM_FC2), row);
+        const bool m0 = kept(rk2, 0, 0, a.thr), m1 = kept(rk2, 0, 1, a.thr);
+        const float l0 = m0 ? red[0][0] * a.inv_keep : 0.f, l1 = m1 ? red[1][0] * a.inv_keep : 0.f;
+        a.logits[row * 2] = l0; a.logits[row * 2 + 1] = l1;
+        const int lab = a.labels[row];
+        float d0 = 0.f, d1 = 0.f, loss;
+        if (a.pos_weight == 1.f) {
+            loss = wce(l0, lab == 0 ? 1.f : 0.f, 1.f, &d0) + wce(l1, lab == 1 ? 1.f : 0.f, 1.f, &d1);
+            a.pred[row] = l1 > l0 ? 1 : 0;
+        } else {
+            loss = wce(l1, (float)lab, a.pos_weight, &d1);
+            a.pred[row] = l1 > 0.f ? 1 : 0;
+        }
+        a.rowloss[row] = loss;
+        d0 = m0 ? d0 * a.grad_scale * a.inv_keep : 0.f;
+        d1 = m1 ? d1 * a.grad_scale * a.inv_keep : 0.f;
+        a.dfc2[row * 2] = d0; a.dfc2[row * 2 + 1] = d1;
+        dl[0] = d0; dl[1] = d1;
+    }
+    __syncthreads();
+    for (int s = 0; s < 2; ++s) {
+        const int k = tid + 256 * s;
+        const float dd = dl[0] * a.W2[k * 2] + dl[1] * a.W2[k * 2 + 1];
+        a.dfc1[(size_t)row * FC + k] = k1[s] ? dd * a.inv_keep : 0.f;
+    }
+}
+
+// loss = sum of the rows' terms in row order, times `scale`; dW2[k][c] = sum over rows of drop1[row][k] dfc2[row][c] in row order
+__global__ void train_head_reduce_kernel(const float* rowloss, const float* drop1, const float* dfc2, float* loss, float* dW2, int n, float scale)
+{
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < FC * NCLASS) {
+        const int k = idx >> 1, c = idx & 1;
+        float s = 0.f;
+        for (int r = 0; r < n; ++r) s = fmaf(drop1[(size_t)r * FC + k], dfc2[r * 2 + c], s);
+        dW2[idx] = s;
+    } else if (idx == FC * NCLASS) {
+        float s = 0.f;
+        for (int r = 0; r < n; ++r) s += rowloss[r];
+        *loss = s * scale;
+    }
+}
+
+// partial[d][t][col] = sum over rows of dZ(d, t)[row][col], in row order
+__global__ void bias_partial_kernel(const float* Z, float* partial, long long sZd, long long sZt, int n, int T)
+{
+    const int col = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y, d = blockIdx.z;
+    const float* z = Z + d * sZd + t * sZt + col;
+    float s = 0.f;
+    for (int r = 0; r < n; ++r) s += z[(size_t)r * GATES];
+    partial[((size_t)d * T + t) * GATES + col] = s;
+}
+
+// out[d * so + e] = slab[d][0][e] + slab[d][1][e] + ... in that order (ns slabs of `stride` floats, `sd` floats between directions)
+__global__ void reduce_slabs_kernel(const float* slab, float* out, long long count, int ns, long long stride, long long sd, long long so)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int d = blockIdx.y;
+    if (e >= count) return;
+    const float* p = slab + d * sd + e;
+    float s = 0.f;
+    for (int k = 0; k < ns; ++k) s += p[k * stride];
+    out[d * so + e] = s;
+}
+
+// Adam in TF's form: epsilon outside the bias correction, which lr_t carries
+__global__ void adam_kernel(float* P, const float* G, float* M, float* V, long long count, float lr_t, float b1, float b2, float eps)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= count) return;
+    const float g = G[e];
+    const float m = b1 * M[e] + (1.f - b1) * g;
+    const float v = b2 * V[e] + (1.f - b2) * g * g;
+    M[e] = m; V[e] = v;
+    P[e] = P[e] - lr_t * m / (sqrtf(v) + eps);
+}
+
+__global__ void mask_kernel(uint8_t* out, int n, int steps, int W, int stream, uint32_t thr, uint64_t seed, long long step)
+{
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)n * steps * W) return;
+    const int u = idx % W, t = (idx / W) % steps, row = idx / ((long long)W * steps);
+    out[idx] = kept(row_key(stream_key(seed, step, stream), row), t, u, thr) ? 1 : 0;
+}
+
+int hip_fail(std::string* err, const char* what, hipError_t e)
+{
+    (void)hipGetLastError();
+    if (err) *err = std::string(what) + ": " + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? DS_ERR_NOMEM : DS_ERR_HIP;
+}
+#define TCK(expr)                                                   \
+    do {                                                            \
+        hipError_t e_ = (expr);                                     \
+        if (e_ != hipSuccess) return hip_fail(err, #expr, e_);      \
+    } while (0)
+
+hipError_t gemm(hipStream_t s, const GemmArgs& g)
+{
+    dim3 grid((g.N + TN - 1) / TN, (g.M + TM - 1) / TM, g.nb1 * g.nb2);
+    hipLaunchKernelGGL(train_gemm_kernel, grid, dim3(256), 0, s, g);
+    return hipGetLastError();
+}
+
+GemmArgs gemm_args(const float* A, int lda, int transA, const float* Bm, int ldb, int transB, float* C, int ldc, int M, int N, int K, int acc)
+{
+    GemmArgs g{};
+    g.A = A; g.Bm = Bm; g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.transA = transA; g.transB = transB;
+    g.M = M; g.N = N; g.K = K; g.acc = acc; g.nb1 = 1; g.nb2 = 1;
+    return g;
+}
+
+}  // namespace
+
+void Trainer::release()
+{
+    if (device >= 0) hipSetDevice(device);
+    if (stream) hipStreamSynchronize(stream);
+    for (void* p : {(void*)P, (void*)G, (void*)M, (void*)V, (void*)X0, (void*)H, (void*)Y, (void*)Cs, (void*)Z, (void*)DX, (void*)DH, (void*)DC,
+                    (void*)slab, (void*)fc1, (void*)drop1, (void*)dfc1, (void*)djoint, (void*)logits, (void*)dfc2, (void*)rowloss, (void*)d_in,
+                    (void*)d_lab, (void*)d_pred, (void*)d_loss, (void*)d_mask})
+        if (p) hipFree(p);
+    P = G = M = V = X0 = H = Y = Cs = Z = DX = DH = DC = slab = fc1 = drop1 = dfc1 = djoint = logits = dfc2 = rowloss = d_in = d_loss = nullptr;
+    d_lab = d_pred = nullptr;
+    d_mask = nullptr;
+    if (pin) hipHostFree(pin);
+    pin = nullptr;
+    for (hipEvent_t& e : ev) { if (e) hipEventDestroy(e); e = nullptr; }
+    if (stream) hipStreamDestroy(stream);
+    stream = nullptr;
+    (void)hipGetLastError();
+    T = B = 0;
+}
+
+Trainer::~Trainer() { release(); }
+
+int Trainer::begin(int dev, int T_, int B_, const Config& c, const float* params, std::string* err)
+{
+    TCK(hipSetDevice(dev));
+    if (T_ != T || B_ != B || dev != device || !P) {
+        release();
+        device = dev;
+        TCK(hipSetDevice(dev));
+        const size_t cells = (size_t)NDIR * NLAYER * T_ * B_;
+        auto alloc = [&](auto** p, size_t count) { return hipMalloc((void**)p, std::max<size_t>(count * sizeof(**p), 256)); };
+        TCK(alloc(&P, PARAM_FLOATS)); TCK(alloc(&G, PARAM_FLOATS)); TCK(alloc(&M, PARAM_FLOATS)); TCK(alloc(&V, PARAM_FLOATS));
+        TCK(alloc(&X0, (size_t)NDIR * T_ * B_ * 4));
+        TCK(alloc(&H, cells * HID)); TCK(alloc(&Y, cells * HID)); TCK(alloc(&Cs, cells * HID)); TCK(alloc(&Z, cells * GATES));
+        TCK(alloc(&DX, (size_t)NDIR * T_ * B_ * HID)); TCK(alloc(&DH, (size_t)NDIR * B_ * HID)); TCK(alloc(&DC, (size_t)NDIR * B_ * HID));
+        TCK(alloc(&slab, (size_t)NDIR * T_ * HID * GATES));
+        TCK(alloc(&fc1, (size_t)B_ * FC)); TCK(alloc(&drop1, (size_t)B_ * FC)); TCK(alloc(&dfc1, (size_t)B_ * FC)); TCK(alloc(&djoint, (size_t)B_ * FC));
+        TCK(alloc(&logits, (size_t)B_ * 2)); TCK(alloc(&dfc2, (size_t)B_ * 2)); TCK(alloc(&rowloss, (size_t)B_));
+        TCK(alloc(&d_in, (size_t)3 * B_ * T_)); TCK(alloc(&d_lab, (size_t)B_)); TCK(alloc(&d_pred, (size_t)B_)); TCK(alloc(&d_loss, 1));
+        TCK(alloc(&d_mask, (size_t)B_ * T_ * FC));
+        TCK(hipHostMalloc((void**)&pin, ((size_t)3 * B_ * T_ + 2 * (size_t)B_ + 4) * 4, hipHostMallocDefault));
+        TCK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        for (hipEvent_t& e : ev) TCK(hipEventCreate(&e));
+        T = T_; B = B_;
+    }
+    TCK(hipStreamSynchronize(stream));
+    cfg = c;
+    TCK(hipMemcpy(P, params, PARAM_FLOATS * sizeof(float), hipMemcpyHostToDevice));
+    TCK(hipMemset(G, 0, PARAM_FLOATS * sizeof(float)));
+    TCK(hipMemset(M, 0, PARAM_FLOATS * sizeof(float)));
+    TCK(hipMemset(V, 0, PARAM_FLOATS * sizeof(float)));
+    step_count = 0;
+    last_n = 0;
+    return DS_OK;
+}
+
+int Trainer::step(int n, const float* means, const float* stds, const float* lens, const int32_t* labels, float lr, float* loss, int32_t* pred,
+                  std::string* err)
+{
+    TCK(hipSetDevice(device));
+    hipStream_t s = stream;
+    const long long sAct = (long long)B * HID, sZt = (long long)B * GATES;               // floats per step
+    const long long sActD = (long long)NLAYER * T * sAct, sZD = (long long)NLAYER * T * sZt;   // floats per direction
+    auto act = [&](float* base, int l, int t) { return base + ((size_t)l * T + t) * sAct; };      // direction 0
+    auto zat = [&](int l, int t) { return Z + ((size_t)l * T + t) * sZt; };
+    const float inv_keep = 1.f / cfg.keep_prob;
+    const uint32_t thr = keep_threshold(cfg.keep_prob);
+    const long long mstep = step_count;
+    const dim3 cell_grid((n * HID + 255) / 256, 2);
+
+    // inputs: [means | stds | lengths] pitched for B rows, then the labels
+    float* pf = pin;
+    const float* srcs[3] = {means, stds, lens};
+    for (int k = 0; k < 3; ++k) memcpy(pf + (size_t)k * B * T, srcs[k], (size_t)n * T * sizeof(float));
+    int32_t* plab = reinterpret_cast<int32_t*>(pf + (size_t)3 * B * T);
+    memcpy(plab, labels, (size_t)n * sizeof(int32_t));
+    TCK(hipMemcpyAsync(d_in, pf, (size_t)3 * B * T * sizeof(float), hipMemcpyHostToDevice, s));
+    TCK(hipMemcpyAsync(d_lab, plab, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+
+    // ---- forward sweep
+    TCK(hipEventRecord(ev[0], s));
+    hipLaunchKernelGGL(gather_x0_kernel, dim3((2 * T * n + 255) / 256), dim3(256), 0, s, d_in, X0, n, T, B);
+    TCK(hipGetLastError());
+    for (int l = 0; l < NLAYER; ++l) {
+        const int in = layer_in(l);
+        // the input half of every step's pre-activation in one batched product: Z(d, l, t) = X_t K[0:in] + b
+        GemmArgs g = l == 0 ? gemm_args(X0, 4, 0, P + kernel_off(l), GATES, 0, zat(l, 0), GATES, n, GATES, in, 0)
+                            : gemm_args(act(Y, l - 1, 0), HID, 0, P + kernel_off(l), GATES, 0, zat(l, 0), GATES, n, GATES, in, 0);
+        g.nb1 = T; g.nb2 = 2;
+        g.sA1 = l == 0 ? (long long)B * 4 : sAct; g.sA2 = l == 0 ? (long long)T * B * 4 : sActD;
+        g.sB2 = DIR_FLOATS; g.sC1 = sZt; g.sC2 = sZD;
+        g.bias = P + bias_off(l); g.sBias2 = DIR_FLOATS;
+        TCK(gemm(s, g));
+        for (int t = 0; t < T; ++t) {
+            if (t > 0) {      // ... and the recurrent half step by step: Z(d, l, t) += h_{t-1} K[in:]
+                GemmArgs r = gemm_args(act(H, l, t - 1), HID, 0, P + kernel_off(l) + (size_t)in * GATES, GATES, 0, zat(l, t), GATES, n, GATES, HID, 1);
+                r.nb2 = 2; r.sA2 = sActD; r.sB2 = DIR_FLOATS; r.sC2 = sZD;
+                TCK(gemm(s, r));
+            }
+            CellArgs c{};
+            c.Z = zat(l, t); c.Cs = act(Cs, l, t); c.H = act(H, l, t); c.Y = act(Y, l, t);
+            c.Cprev = t > 0 ? act(Cs, l, t - 1) : nullptr;
+            c.sZ = sZD; c.sH = sActD; c.n = n; c.t = t; c.stream0 = l; c.inv_keep = inv_keep; c.thr = thr; c.seed = cfg.seed; c.step = mstep;
+            hipLaunchKernelGGL(cell_forward_kernel, cell_grid, dim3(256), 0, s, c);
+            TCK(hipGetLastError());
+        }
+    }
+    TCK(hipEventRecord(ev[1], s));
+
+    // ---- head: fc1 = [y_fw(T - 1) | y_bw(T - 1)] W1, dropout, fc2, dropout, loss, and the gradient back to the joint row
+    float* W1 = P + W1_OFF;
+    float* W2 = P + W2_OFF;
+    for (int d = 0; d < 2; ++d)
+        TCK(gemm(s, gemm_args(act(Y, NLAYER - 1, T - 1) + d * sActD, HID, 0, W1 + (size_t)d * HID * FC, FC, 0, fc1, FC, n, FC, HID, d)));
+    const bool two_col = cfg.pos_weight == 1.f;
+    const float scale = 1.f / (float)(two_col ? 2 * n : n);
+    HeadArgs ha{};
+    ha.fc1 = fc1; ha.W2 = W2; ha.drop1 = drop1; ha.dfc1 = dfc1; ha.logits = logits; ha.dfc2 = dfc2; ha.rowloss = rowloss; ha.labels = d_lab;
+    ha.pred = d_pred; ha.n = n; ha.inv_keep = inv_keep; ha.pos_weight = cfg.pos_weight; ha.grad_scale = scale; ha.thr = thr; ha.seed = cfg.seed;
+    ha.step = mstep;
+    hipLaunchKernelGGL(train_head_kernel, dim3(n), dim3(256), 0, s, ha);
+    TCK(hipGetLastError());
+    hipLaunchKernelGGL(train_head_reduce_kernel, dim3((FC * NCLASS + 1 + 255) / 256), dim3(256), 0, s, rowloss, drop1, dfc2, d_loss, G + W2_OFF, n, scale);
+    TCK(hipGetLastError());
+    {   // dW1 = joint^T dfc1 (rows 0 .. 255 from y_fw, 256 .. 511 from y_bw); djoint = dfc1 W1^T
+        GemmArgs g = gemm_args(act(Y, NLAYER - 1, T - 1), HID, 1, dfc1, FC, 0, G + W1_OFF, FC, HID, FC, n, 0);
+        g.nb2 = 2; g.sA2 = sActD; g.sC2 = (long long)HID * FC;
+        TCK(gemm(s, g));
+        TCK(gemm(s, gemm_args(dfc1, FC, 0, W1, FC, 1, djoint, FC, n, FC, FC, 0)));
+    }
+    TCK(hipEventRecord(ev[2], s));
+
+    // ---- backward sweep, top layer first; every step leaves its gate gradients dz in Z
+    for (int l = NLAYER - 1; l >= 0; --l) {
+        const int in = layer_in(l);
+        for (int t = T - 1; t >= 0; --t) {
+            CellBackArgs c{};
+            c.Z = zat(l, t); c.Cs = act(Cs, l, t); c.Cprev = t > 0 ? act(Cs, l, t - 1) : nullptr;
+            if (l == NLAYER - 1) {
+                if (t == T - 1) { c.dY = djoint; c.ldY = FC; c.sdY = HID; }
+            } else {
+                c.dY = DX + (size_t)t * sAct; c.ldY = HID; c.sdY = (long long)T * sAct;
+            }
+            c.last = t == T - 1;
+            c.DH = c.last ? nullptr : DH;
+            c.DC = DC;
+            c.sZ = sZD; c.sH = sActD; c.sD = sAct; c.n = n; c.t = t; c.stream0 = l; c.inv_keep = inv_keep; c.thr = thr; c.seed = cfg.seed;
+            c.step = mstep;
+            hipLaunchKernelGGL(cell_backward_kernel, cell_grid, dim3(256), 0, s, c);
+            TCK(hipGetLastError());
+            if (t > 0) {      // dh_{t-1} += dz_t K[in:]^T
+                GemmArgs r = gemm_args(zat(l, t), GATES, 0, P + kernel_off(l) + (size_t)in * GATES, GATES, 1, DH, HID, n, HID, GATES, 0);
+                r.nb2 = 2; r.sA2 = sZD; r.sB2 = DIR_FLOATS; r.sC2 = sAct;
+                TCK(gemm(s, r));
+            }
+        }
+        if (l > 0) {          // what the layer below receives, all steps at once: dy_t = dz_t K[0:in]^T
+            GemmArgs g = gemm_args(zat(l, 0), GATES, 0, P + kernel_off(l), GATES, 1, DX, HID, n, HID, GATES, 0);
+            g.nb1 = T; g.nb2 = 2; g.sA1 = sZt; g.sA2 = sZD; g.sB2 = DIR_FLOATS; g.sC1 = sAct; g.sC2 = (long long)T * sAct;
+            TCK(gemm(s, g));
+        }
+    }
+    TCK(hipEventRecord(ev[3], s));
+
+    // ---- weight gradients: per cell one product per step into a slab, the slabs added in step order
+    const long long slab_step = (long long)HID * GATES, slab_dir = (long long)T * slab_step;
+    for (int l = 0; l < NLAYER; ++l) {
+        const int in = layer_in(l);
+        {   // dK[0:in] = sum_t X_t^T dz_t
+            GemmArgs g = l == 0 ? gemm_args(X0, 4, 1, zat(l, 0), GATES, 0, slab, GATES, in, GATES, n, 0)
+                                : gemm_args(act(Y, l - 1, 0), HID, 1, zat(l, 0), GATES, 0, slab, GATES, in, GATES, n, 0);
+            g.nb1 = T; g.nb2 = 2;
+            g.sA1 = l == 0 ? (long long)B * 4 : sAct; g.sA2 = l == 0 ? (long long)T * B * 4 : sActD;
+            g.sB1 = sZt; g.sB2 = sZD; g.sC1 = slab_step; g.sC2 = slab_dir;
+            TCK(gemm(s, g));
+            const long long count = (long long)in * GATES;
+            hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((count + 255) / 256), 2), dim3(256), 0, s, slab, G + kernel_off(l), count, T, slab_step,
+                               slab_dir, DIR_FLOATS);
+            TCK(hipGetLastError());
+        }
+        {   // dK[in:] = sum_{t >= 1} h_{t-1}^T dz_t
+            const long long count = (long long)HID * GATES;
+            if (T > 1) {
+                GemmArgs g = gemm_args(act(H, l, 0), HID, 1, zat(l, 1), GATES, 0, slab, GATES, HID, GATES, n, 0);
+                g.nb1 = T - 1; g.nb2 = 2; g.sA1 = sAct; g.sA2 = sActD; g.sB1 = sZt; g.sB2 = sZD; g.sC1 = slab_step; g.sC2 = slab_dir;
+                TCK(gemm(s, g));
+            }
+            hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((count + 255) / 256), 2), dim3(256), 0, s, slab, G + kernel_off(l) + (size_t)in * GATES,
+                               count, T - 1, slab_step, slab_dir, DIR_FLOATS);
+            TCK(hipGetLastError());
+        }
+        // db = column sums of dz over steps and rows
+        hipLaunchKernelGGL(bias_partial_kernel, dim3(GATES / 256, T, 2), dim3(256), 0, s, zat(l, 0), slab, sZD, sZt, n, T);
+        TCK(hipGetLastError());
+        hipLaunchKernelGGL(reduce_slabs_kernel, dim3(GATES / 256, 2), dim3(256), 0, s, slab, G + bias_off(l), (long long)GATES, T, (long long)GATES,
+                           (long long)T * GATES, DIR_FLOATS);
+        TCK(hipGetLastError());
+    }
+    TCK(hipEventRecord(ev[4], s));
+
+    // ---- Adam on all 14 tensors
+    const float lr_t = adam_step_size(lr, cfg.beta1, cfg.beta2, step_count + 1);
+    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((PARAM_FLOATS + 255) / 256)), dim3(256), 0, s, P, G, M, V, (long long)PARAM_FLOATS, lr_t, cfg.beta1,
+                       cfg.beta2, cfg.epsilon);
+    TCK(hipGetLastError());
+    TCK(hipEventRecord(ev[5], s));
+
+    float* pout = pin + (size_t)3 * B * T + B;
+    TCK(hipMemcpyAsync(pout, d_loss, sizeof(float), hipMemcpyDeviceToHost, s));
+    TCK(hipMemcpyAsync(pout + 1, d_pred, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    TCK(hipStreamSynchronize(s));
+    if (loss) *loss = pout[0];
+    if (pred) memcpy(pred, pout + 1, (size_t)n * sizeof(int32_t));
+    // phases in the order ds_get_train_times reports them: forward sweep, backward sweep, weight gradients, head, Adam
+    const int from[NPHASE] = {0, 2, 3, 1, 4};
+    for (int k = 0; k < NPHASE; ++k) {
+        float t_ms = 0.f;
+        TCK(hipEventElapsedTime(&t_ms, ev[from[k]], ev[from[k] + 1]));
+        ms[k] += t_ms;
+    }
+    steps_timed += 1;
+    step_count += 1;
+    last_n = n;
+    return DS_OK;
+}
+
+int Trainer::read_params(float* out, std::string* err)
+{
+    TCK(hipSetDevice(device));
+    TCK(hipMemcpy(out, P, PARAM_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
+    return DS_OK;
+}
+
+int64_t Trainer::get(const float* block, int idx, float* out, int64_t cap, std::string* err)
+{
+    const int64_t count = tensor_floats(idx);
+    if (cap < count) { if (err) *err = "buffer too small for " + tensor_name(idx); return DS_ERR_INVALID; }
+    TCK(hipSetDevice(device));
+    TCK(hipMemcpy(out, block + tensor_off(idx), count * sizeof(float), hipMemcpyDeviceToHost));
+    return count;
+}
+
+int64_t Trainer::get_mask(int stream_id, uint8_t* out, int64_t cap, std::string* err)
+{
+    const int W = stream_width(stream_id), steps = stream_id < 6 ? T : 1;
+    const int64_t count = (int64_t)last_n * steps * W;
+    if (cap < count) { if (err) *err = "mask buffer too small"; return DS_ERR_INVALID; }
+    TCK(hipSetDevice(device));
+    hipLaunchKernelGGL(mask_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, d_mask, last_n, steps, W, stream_id,
+                       keep_threshold(cfg.keep_prob), cfg.seed, (long long)(step_count - 1));
+    TCK(hipGetLastError());
+    TCK(hipMemcpyAsync(out, d_mask, count, hipMemcpyDeviceToHost, stream));
+    TCK(hipStreamSynchronize(stream));
+    return count;
+}
+
+}  // namespace dstr

@@ -68,6 +68,11 @@ def main_evaluate(args):
     return run(args)
 
 
+def main_denoise(args):
+    from .denoise import run
+    return run(args)
+
+
 def _names_freq_file(argv) -> bool:
     """Does the command line give call_mods' --freq_file (spelled out, abbreviated as argparse allows, or with '=')?"""
     for a in argv:
@@ -213,6 +218,13 @@ def build_parser(freq_file_given=True):
     evaluate_arguments(v)
     v.set_defaults(func=main_evaluate)
     parser.evaluate_parser = v
+    # `denoise`: the training-side module -- false positive samples of a training file filtered by cross-ranking, the models trained
+    # on the GPU (the reference's flags and defaults, deepsignal.py:389-418, plus --seed / --device / --scores_file)
+    from .denoise import add_arguments as denoise_arguments
+    d = sub.add_parser("denoise", description="denoise training samples by deep-learning, filter false positive samples")
+    denoise_arguments(d)
+    d.set_defaults(func=main_denoise)
+    parser.denoise_parser = d
     return parser
 
 
@@ -256,6 +268,10 @@ def main(argv=None):
     if args.module == "evaluate":
         from .evaluate_mods_call import check_arguments
         check_arguments(parser.evaluate_parser, args)
+        return args.func(args)
+    if args.module == "denoise":
+        from .denoise import check_arguments
+        check_arguments(parser.denoise_parser, args)
         return args.func(args)
     if args.module == "call_freq":
         return args.func(args)       # the script's own main: it validates the forwarded flags and returns the exit status

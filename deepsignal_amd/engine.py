@@ -55,6 +55,9 @@ EXPORTED_SYMBOLS = (
     # call accuracy and AUROC of labelled call rows on the device (evaluate --on gpu)
     "ds_eval_locate", "ds_eval_begin", "ds_eval_parse", "ds_eval_accumulate", "ds_eval_result", "ds_eval_end", "ds_eval_reference",
     "ds_get_eval_times",
+    # training step of the RNN-only model (denoise)
+    "ds_train_begin", "ds_train_set_tensor", "ds_train_step", "ds_train_sync_weights", "ds_train_get_tensor", "ds_train_get_grad",
+    "ds_train_get_mask", "ds_train_end", "ds_train_mask_reference", "ds_get_train_times",
 )
 
 
@@ -74,6 +77,14 @@ class DsReads(ctypes.Structure):
         ("length", ctypes.c_void_p), ("base", ctypes.c_void_p), ("base_off", ctypes.c_void_p), ("scaling", ctypes.c_void_p),
         ("offset", ctypes.c_void_p), ("key", ctypes.c_void_p), ("nsites", ctypes.c_int32), ("site_read", ctypes.c_void_p),
         ("site_loc", ctypes.c_void_p), ("norm", ctypes.c_int32), ("seed", ctypes.c_uint64),
+    ]
+
+
+class DsTrainConfig(ctypes.Structure):
+    """include/deepsignal_hip.h ds_train_config"""
+    _fields_ = [
+        ("keep_prob", ctypes.c_float), ("pos_weight", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float),
+        ("epsilon", ctypes.c_float), ("seed", ctypes.c_uint64),
     ]
 
 
@@ -700,8 +711,45 @@ def load_library() -> ctypes.CDLL:
     lib.ds_combine_reference.argtypes = [i32, vp, i64, vp, vp, vp, vp, i32, vp, vp] + [vp] * 8 + [i64] + [vp] * 8
     lib.ds_combine_reference.restype = i64
     lib.ds_get_combine_times.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(f64)]
+    lib.ds_train_begin.argtypes = [vp, ctypes.POINTER(DsTrainConfig)]
+    lib.ds_train_set_tensor.argtypes = [vp, ctypes.c_char_p, vp, i64]
+    lib.ds_train_step.argtypes = [vp, i32, vp, vp, vp, vp, ctypes.c_float, ctypes.POINTER(ctypes.c_float), vp]
+    lib.ds_train_sync_weights.argtypes = [vp]
+    for fn in (lib.ds_train_get_tensor, lib.ds_train_get_grad, lib.ds_train_get_mask):
+        fn.argtypes = [vp, ctypes.c_char_p, vp, i64]
+        fn.restype = i64
+    lib.ds_train_end.argtypes = [vp]
+    lib.ds_train_mask_reference.argtypes = [ctypes.c_uint64, i64, ctypes.c_char_p, i32, i32, ctypes.c_float, vp]
+    lib.ds_get_train_times.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(f64)]
     _lib = lib
     return lib
+
+
+# ---- training step of the RNN-only model (include/deepsignal_hip.h, "training step") --------------------------------------------
+MASK_STREAMS = ("fw_l0", "fw_l1", "fw_l2", "bw_l0", "bw_l1", "bw_l2", "fc1", "fc2")
+TRAIN_PHASES = ("forward_sweep", "backward_sweep", "weight_gradients", "head", "adam")
+
+
+def mask_shape(stream: str, n: int, kmer_len: int) -> Tuple[int, ...]:
+    if stream not in MASK_STREAMS:
+        raise ValueError("mask stream must be one of %s" % (MASK_STREAMS,))
+    return (n, kmer_len, 256) if stream[2] == "_" else (n, 512 if stream == "fc1" else 2)
+
+
+def train_mask_reference(seed: int, step: int, stream: str, n: int, kmer_len: int, keep_prob: float) -> np.ndarray:
+    """The dropout mask of `stream` for rows 0 .. n - 1 of step `step` (counted from 0), computed on the CPU by the function
+    the kernels run: a checker, no handle, no GPU."""
+    out = np.empty(mask_shape(stream, n, kmer_len), np.uint8)
+    rc = load_library().ds_train_mask_reference(seed, step, stream.encode(), n, kmer_len, keep_prob, out.ctypes.data)
+    if rc != 0:
+        raise ValueError("ds_train_mask_reference failed (%d): bad stream, size or keep_prob" % rc)
+    return out
+
+
+def trainable_names() -> List[str]:
+    """TF names of the 14 tensors the RNN-only model trains, in the order of `spec.tensor_table`."""
+    from . import spec
+    return [name for name, _ in spec.tensor_table(17, 360, 2, is_cnn=False, is_rnn=True, is_base=False)]
 
 
 class Engine:
@@ -799,6 +847,78 @@ class Engine:
             shape = (ctypes.c_int64 * a.ndim)(*a.shape)
             self._check(self._lib.ds_set_tensor(self._h, name.encode(), a.ctypes.data, shape, a.ndim), "ds_set_tensor")
         self._check(self._lib.ds_finalize_weights(self._h), "ds_finalize_weights")
+
+    # -- training step of the RNN-only model (denoise.py:97-110) -------------------------------
+    def train_begin(self, keep_prob: float = 0.5, pos_weight: float = 1.0, seed: int = 0, beta1: float = 0.0, beta2: float = 0.0,
+                    epsilon: float = 0.0, weights: Optional[Dict[str, np.ndarray]] = None) -> None:
+        """Start (or start over) from the loaded weights, or from `weights` installed in their place: fp32 master
+        parameters, zero Adam moments, step 0. beta1 / beta2 / epsilon 0 = TF's defaults."""
+        if weights is not None:
+            for name, arr in weights.items():
+                a = np.ascontiguousarray(arr, dtype=np.float32)
+                self._check(self._lib.ds_train_set_tensor(self._h, name.encode(), a.ctypes.data, a.size), "ds_train_set_tensor")
+        cfg = DsTrainConfig(keep_prob, pos_weight, beta1, beta2, epsilon, seed & 0xFFFFFFFFFFFFFFFF)
+        self._check(self._lib.ds_train_begin(self._h, ctypes.byref(cfg)), "ds_train_begin")
+
+    def train_step(self, means, stds, sanums, labels, lr: float) -> Tuple[float, np.ndarray]:
+        """One step on these rows: (cost, prediction int32[n])."""
+        means = np.ascontiguousarray(means, dtype=np.float32)
+        stds = np.ascontiguousarray(stds, dtype=np.float32)
+        sanums = np.ascontiguousarray(sanums, dtype=np.float32)
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        n = int(labels.shape[0]) if labels.ndim == 1 else -1
+        if means.ndim != 2 or means.shape != (n, self.kmer_len) or stds.shape != means.shape or sanums.shape != means.shape:
+            raise ValueError("training arrays have inconsistent shapes")
+        loss = ctypes.c_float()
+        pred = np.empty((n,), np.int32)
+        rc = self._lib.ds_train_step(self._h, n, means.ctypes.data, stds.ctypes.data, sanums.ctypes.data, labels.ctypes.data,
+                                     lr, ctypes.byref(loss), pred.ctypes.data)
+        self._check(rc, "ds_train_step")
+        return float(loss.value), pred
+
+    def train_sync_weights(self) -> None:
+        self._check(self._lib.ds_train_sync_weights(self._h), "ds_train_sync_weights")
+
+    def _train_tensor(self, fn, what: str, name: str) -> np.ndarray:
+        from . import spec
+        shapes = dict(spec.tensor_table(self.kmer_len, self.signal_len, self.class_num, is_cnn=False, is_rnn=True, is_base=False))
+        if name not in shapes:
+            raise KeyError(name)
+        out = np.empty(shapes[name], np.float32)
+        got = int(fn(self._h, name.encode(), out.ctypes.data, out.size))
+        self._check(got, what)
+        if got != out.size:
+            raise RuntimeError("%s: %d floats expected, %d returned" % (what, out.size, got))
+        return out
+
+    def train_tensor(self, name: str) -> np.ndarray:
+        return self._train_tensor(self._lib.ds_train_get_tensor, "ds_train_get_tensor", name)
+
+    def train_grad(self, name: str) -> np.ndarray:
+        return self._train_tensor(self._lib.ds_train_get_grad, "ds_train_get_grad", name)
+
+    def train_tensors(self) -> Dict[str, np.ndarray]:
+        return {name: self.train_tensor(name) for name in trainable_names()}
+
+    def train_grads(self) -> Dict[str, np.ndarray]:
+        return {name: self.train_grad(name) for name in trainable_names()}
+
+    def train_mask(self, stream: str, n: int) -> np.ndarray:
+        out = np.empty(mask_shape(stream, n, self.kmer_len), np.uint8)
+        got = int(self._lib.ds_train_get_mask(self._h, stream.encode(), out.ctypes.data, out.size))
+        self._check(got, "ds_train_get_mask")
+        if got != out.size:
+            raise RuntimeError("ds_train_get_mask: the last step had %d mask elements, %d asked for" % (got, out.size))
+        return out
+
+    def train_end(self) -> None:
+        self._check(self._lib.ds_train_end(self._h), "ds_train_end")
+
+    def train_times(self, reset: bool = False) -> dict:
+        steps = ctypes.c_int64()
+        ms = (ctypes.c_double * len(TRAIN_PHASES))()
+        self._check(self._lib.ds_get_train_times(self._h, int(reset), ctypes.byref(steps), ms), "ds_get_train_times")
+        return {"steps": int(steps.value), "ms": dict(zip(TRAIN_PHASES, (float(v) for v in ms)))}
 
     # -- forward (sess.run, call_modifications.py:177-178) -------------------------------------
     def run(self, kmer, means, stds, sanums, signals) -> Tuple[np.ndarray, np.ndarray]:

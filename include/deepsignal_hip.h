@@ -665,6 +665,54 @@ int ds_eval_reference(const char *text, int64_t nrows, const int64_t *row_begin,
                       int64_t *counts, uint64_t *u2, int64_t *pn, int64_t *nn);
 int ds_get_eval_times(ds_handle *h, int32_t reset, int64_t *batches, double *ms);
 
+/* ---- training step of the RNN-only model (`denoise`; csrc/ds_train.hip) ------------------------------------------------
+ * Replaces sess.run([train_opt, cost, prediction], feed_dict) of denoise.py:97-110 for the variant denoise trains: is_cnn 0,
+ * is_base 0, is_rnn 1, class_num 2 (two independent 3-layer LSTM stacks over (mean, std, length), dense(512, 512), dense(512, 2);
+ * model.py:70-116), DS_PRECISION_FP32. Any other handle: DS_ERR_UNSUPPORTED from ds_train_begin, with the reason.
+ * The arithmetic is the training graph: DropoutWrapper(output_keep_prob) on every cell (what goes up and out is h / keep_prob *
+ * mask, the recurrent h is not dropped), dropout after both dense layers (the logits too, layers.py:257-264),
+ * tf.nn.weighted_cross_entropy_with_logits in its stable form, tf.train.AdamOptimizer (epsilon outside the bias correction) on
+ * all 14 tensors. pos_weight == 1 selects the two-column loss (mean over n x 2 logits against the one-hot labels, pred = argmax
+ * with ties to 0; model.py:107-110), any other value the one on logits[:, 1] (mean over n, pred = logits[:, 1] > 0;
+ * model.py:111-116). fp32 on v_mfma_f32_32x32x2_f32, no floating-point atomics: the same weights, rows, seed and step give the
+ * same bits.
+ *
+ * ds_train_begin: needs loaded weights; copies them into fp32 master parameters, zeroes the Adam moments and the step counter.
+ *   beta1 / beta2 / epsilon = 0 select 0.9 / 0.999 / 1e-8. ds_train_set_tensor replaces one of the 14 loaded tensors (TF name, exact
+ *   size) on a loaded handle; the next ds_train_begin starts from it, so one handle trains any number of models from scratch.
+ * ds_train_step: one step on n rows (1 .. max_batch) of host arrays means / stds / sanums float[n, kmer_len] and labels int32[n]
+ *   in {0, 1}; writes the scalar cost and model.prediction int32[n]. The mean is over exactly these rows. Blocking.
+ * ds_train_sync_weights: packs the current parameters for the inference plan, so that ds_forward / ds_submit on this handle use
+ *   them. Until it is called the forward keeps the weights it had.
+ * Diagnostics: ds_train_get_tensor (a current parameter by TF name), ds_train_get_grad (its loss gradient in the last step),
+ *   ds_train_get_mask (the dropout masks of the last step as 0 / 1 bytes: streams "fw_l0" .. "fw_l2", "bw_l0" .. "bw_l2" of shape
+ *   [n, kmer_len, 256] with the time index in the order the stack processes the sequence (bw: index 0 is the last base), "fc1"
+ *   [n, 512], "fc2" [n, 2]); each returns the number of elements written or a negative code.
+ * ds_train_mask_reference: the same mask function on the CPU (csrc/ds_train.h): a CHECKER, no handle, no GPU. A row's mask
+ *   depends on (seed, step, stream, row, t, unit) only, step counting the steps since ds_train_begin from 0.
+ * ds_get_train_times: steps timed and summed device milliseconds of ms[0] the forward sweep, ms[1] the backward sweep, ms[2] the
+ *   weight gradients, ms[3] the head (forward, loss, backward), ms[4] Adam.
+ * DS_ERR_INVALID: n out of range, a label outside {0, 1}, keep_prob outside (0, 1], a non-positive or NaN pos_weight, a call
+ * before ds_train_begin, pipeline tickets in flight. ds_train_end closes the run (ds_destroy does too). */
+typedef struct ds_train_config {
+    float keep_prob;     /* (0, 1]; 1 = no dropout */
+    float pos_weight;    /* > 0; 1.0 selects the two-column loss */
+    float beta1, beta2, epsilon;   /* 0 -> 0.9, 0.999, 1e-8 */
+    uint64_t seed;       /* dropout masks */
+} ds_train_config;
+int ds_train_begin(ds_handle *h, const ds_train_config *cfg);
+int ds_train_set_tensor(ds_handle *h, const char *name, const float *data, int64_t count);
+int ds_train_step(ds_handle *h, int32_t n, const float *means, const float *stds, const float *sanums, const int32_t *labels,
+                  float lr, float *loss, int32_t *pred);
+int ds_train_sync_weights(ds_handle *h);
+int64_t ds_train_get_tensor(ds_handle *h, const char *name, float *out, int64_t cap);
+int64_t ds_train_get_grad(ds_handle *h, const char *name, float *out, int64_t cap);
+int64_t ds_train_get_mask(ds_handle *h, const char *stream, uint8_t *out, int64_t cap);
+int ds_train_end(ds_handle *h);
+int ds_train_mask_reference(uint64_t seed, int64_t step, const char *stream, int32_t n, int32_t kmer_len, float keep_prob,
+                            uint8_t *out);
+int ds_get_train_times(ds_handle *h, int32_t reset, int64_t *steps, double *ms);
+
 /* Use a captured hipGraph for the forward (default on). */
 int ds_set_graph(ds_handle *h, int32_t enable);
 

@@ -1,0 +1,128 @@
+"""Throughput of the training step (ds_train_step) at denoise's defaults -- batch 512, T = 17, keep_prob 0.5 -- in steps/s and
+samples/s from wall time, device milliseconds per phase from ds_get_train_times, and the fraction of the fp32 matrix peak on the
+step's algorithmic FLOPs. The only baseline there is: the float32 torch statement (tests/train_statement.py) on the usable CPU
+cores. Writes profiles/train_throughput.json.
+
+    python tools/train_throughput.py [--steps 30] [--warmup 5] [--cpu_steps 2] [--out profiles/train_throughput.json]
+    python tools/train_throughput.py --parity [--out profiles/train_parity.json]
+
+--parity writes the distances tests/test_gpu_train_grad.py asserts on (GPU and float32 statement against the float64 statement,
+per case and tensor) instead."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+FP32_MATRIX_PEAK = 157.3e12      # MI355X, v_mfma_f32_32x32x2_f32
+
+
+def step_flops(n, T):
+    """Algorithmic FLOPs of one step: the forward's matrix products, and twice that for the backward (d[x | h] and dK)."""
+    rows = (3 + 256) + 2 * (256 + 256)
+    fwd = 2 * T * n * 2 * rows * 1024 + 2 * n * 512 * 512 + 2 * n * 512 * 2
+    return fwd, 2 * fwd
+
+
+def usable_cores():
+    n = os.cpu_count() or 1
+    try:
+        n = min(n, len(os.sched_getaffinity(0)))
+    except (AttributeError, OSError):
+        pass
+    return max(1, min(n, 16))
+
+
+def throughput(a):
+    import torch
+    import train_statement as ts
+    from deepsignal_amd import weights
+    from deepsignal_amd.engine import Engine
+    n, T = a.batch, a.kmer_len
+    w = weights.random_weights(seed=7, is_cnn=False, is_base=False, kmer_len=T)
+    feats = ts.train_features(n, T, seed=1)
+    labels = np.random.default_rng(2).integers(0, 2, n).astype(np.int32)
+    eng = Engine(kmer_len=T, max_batch=n, is_cnn=False, is_base=False, device=a.device)
+    eng.load_weights(w)
+    eng.train_begin(keep_prob=a.keep_prob, seed=3)
+    for _ in range(a.warmup):
+        eng.train_step(feats["means"], feats["stds"], feats["sanums"], labels, 1e-3)
+    eng.train_times(reset=True)
+    t0 = time.perf_counter()
+    for _ in range(a.steps):
+        loss, _ = eng.train_step(feats["means"], feats["stds"], feats["sanums"], labels, 1e-3)
+    wall = time.perf_counter() - t0
+    times = eng.train_times()
+    eng.close()
+    fwd, bwd = step_flops(n, T)
+    device_ms = sum(times["ms"].values()) / times["steps"]
+    out = {"batch": n, "kmer_len": T, "keep_prob": a.keep_prob, "steps": a.steps, "warmup": a.warmup, "last_loss": loss,
+           "steps_per_s": a.steps / wall, "samples_per_s": a.steps * n / wall, "wall_ms_per_step": 1e3 * wall / a.steps,
+           "device_ms_per_step": device_ms, "device_ms_per_phase": {k: v / times["steps"] for k, v in times["ms"].items()},
+           "gflop_per_step": {"forward": fwd / 1e9, "backward": bwd / 1e9},
+           "fraction_of_fp32_matrix_peak": (fwd + bwd) / (device_ms * 1e-3) / FP32_MATRIX_PEAK}
+    if a.cpu_steps > 0:
+        cores = usable_cores()
+        torch.set_num_threads(cores)
+        ts.step(w, feats, labels, None, 1.0, 1.0, torch.float32)          # warm-up
+        t0 = time.perf_counter()
+        for _ in range(a.cpu_steps):
+            ts.step(w, feats, labels, None, 1.0, 1.0, torch.float32)
+        cpu = (time.perf_counter() - t0) / a.cpu_steps
+        out["cpu_statement"] = {"what": "tests/train_statement.py, float32, forward + autograd backward (no optimiser)", "cores": cores,
+                                "s_per_step": cpu, "samples_per_s": n / cpu}
+    return out
+
+
+def parity(a):
+    import torch
+    import test_gpu_train_grad as cases
+    import train_statement as ts
+    from deepsignal_amd import engine
+    out = []
+    for n, T, keep_prob, pos_weight, wkind, lkind in cases.CASES:
+        w, feats, labels = cases._weights(wkind, T), ts.train_features(n, T, seed=1000 + n), cases._labels(lkind, n)
+        eng = engine.Engine(kmer_len=T, max_batch=cases.MAX_BATCH, is_cnn=False, is_base=False, device=a.device)
+        eng.load_weights(w)
+        eng.train_begin(keep_prob=keep_prob, pos_weight=pos_weight, seed=cases.SEED)
+        loss, _ = eng.train_step(feats["means"], feats["stds"], feats["sanums"], labels, 0.0)
+        masks = {s: eng.train_mask(s, n) for s in engine.MASK_STREAMS}
+        grads = eng.train_grads()
+        eng.close()
+        l64, _, g64 = ts.step(w, feats, labels, masks, keep_prob, pos_weight, torch.float64)
+        l32, _, g32 = ts.step(w, feats, labels, masks, keep_prob, pos_weight, torch.float32)
+        out.append({"n": n, "T": T, "keep_prob": keep_prob, "pos_weight": pos_weight, "weights": wkind, "labels": lkind,
+                    "loss": {"gpu": loss, "f64": l64, "gpu_distance": abs(loss - l64), "f32_statement_distance": abs(l32 - l64)},
+                    "gradient": {k: {"gpu": ts.rel_err(grads[k], g64[k]), "f32_statement": ts.rel_err(g32[k], g64[k])} for k in ts.tensor_names()}})
+    return {"distance": "max |g - g_64| / max |g_64| per tensor; bar of the test: 4 x max(f32_statement, 1e-6)", "cases": out}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--batch", type=int, default=512)
+    ap.add_argument("--kmer_len", type=int, default=17)
+    ap.add_argument("--keep_prob", type=float, default=0.5)
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--cpu_steps", type=int, default=2, help="steps of the CPU statement to time (0: skip)")
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--parity", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    result = parity(a) if a.parity else throughput(a)
+    path = a.out or os.path.join(ROOT, "profiles", "train_parity.json" if a.parity else "train_throughput.json")
+    with open(path, "w") as f:
+        json.dump(result, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps(result if not a.parity else {"cases": len(result["cases"]), "written": path}, sort_keys=True))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
