@@ -54,6 +54,10 @@ __device__ __forceinline__ float4 gload4_at(const float* base, unsigned byte_off
     return make_float4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ float gload_at(const float* base, unsigned byte_off) { return *(gptr1)(reinterpret_cast<const char*>(base) + byte_off); }
+__device__ __forceinline__ void gstore4_at(gptr1w base, unsigned byte_off, const v4f& v)      // global_store ... v, v[n:n+3], s[n:n+1]
+{
+    *(__attribute__((address_space(1))) v4f*)(reinterpret_cast<__attribute__((address_space(1))) char*>(base) + byte_off) = v;
+}
 
 // ---- bf16 helpers (mixed-precision mode: bf16 operands, fp32 accumulate) ----
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

@@ -1179,18 +1179,31 @@ size_t inception_fused_lds_bytes(int tm, int W, int spt)
 // All weights of a conv unit (ntaps x 4 k-groups, <= 20 float4): requested EARLY — before the barrier or
 // the epilogue in front of the unit — so their L2 latency is off the unit's critical path.
 // (NFRAG fragments: ntaps x 4 of a unit on 32-wide tiles, ntaps x 2 of a 16-channel remainder unit)
-template <int NFRAG>
-__device__ __forceinline__ void fused_unit_prefetch(const float* __restrict__ Bp, int lane, float4 (&ub)[20])
+// (Bp is wave-uniform: fragment g is the scalar base + g KiB, and the lane adds lane16 = 16 lane as a 32-bit offset -- no 64-bit
+// vector address. DS_LANE_OFFSET: see inception_fused_body)
+#define DS_LANE_OFFSET(v) asm volatile("" : "+v"(v))
+// a wave-uniform address the same way: the sum stays one SGPR pair (scalar adds), in reach of the load's immediate
+template <typename P> __device__ __forceinline__ P sbase(P p)
 {
-    const float* bsrc = Bp + lane * 4;
+    asm volatile("" : "+s"(p));
+    return p;
+}
+template <int NFRAG>
+__device__ __forceinline__ void fused_unit_prefetch(const float* __restrict__ Bp, unsigned& lane16, float4 (&ub)[20])
+{
+    DS_LANE_OFFSET(lane16);
+    const float* b4 = Bp;                   // 4 KiB of fragments per scalar base
 #pragma unroll
-    for (int g = 0; g < NFRAG; ++g) ub[g] = gload4(bsrc + g * 256);
+    for (int g = 0; g < NFRAG; ++g) {
+        if (g % 4 == 0) b4 = sbase(Bp + g * 256);
+        ub[g] = gload4_at(b4 + (g % 4) * 256, lane16);
+    }
 }
 
 template <int NTAPS>
 __device__ __forceinline__ void fused_conv_unit(const float* T1, int rm, int coloff, int lane, const float4 (&ub)[20], floatx16& acc)
 {
-    const float* base = T1 + rm * F_LD1 + coloff + (lane >> 5) * 4;
+    const float* base = T1 + rm + coloff + (lane >> 5) * 4;        // rm: the row's offset in T1, in floats (the row map holds it so)
 #pragma unroll
     for (int t = 0; t < NTAPS; ++t) {
         const float* arow = base + (t - NTAPS / 2) * F_LD1;
@@ -1210,12 +1223,12 @@ __device__ __forceinline__ void fused_conv_unit(const float* T1, int rm, int col
 // like every MFMA here: lane (r = lane & 15, q = lane >> 4) reads channels 16g + 4q .. + 3 of activation row r with one
 // ds_read_b128 and feeds element e to the e-th of four MFMAs, whose weight fragment element e holds k = 16g + 4q + e
 // (ds_engine.cpp pack_b_rem16); it ends up with output channels 32 + 4q .. + 3 of its row. rm0 / rm1: T1 rows of the lane's row
-// in the upper / lower tile. The two tiles' MFMAs alternate, so no MFMA waits for the one before it.
+// (as offsets in floats, as the row map holds them) in the upper / lower tile. The two tiles' MFMAs alternate, so no MFMA waits for the one before it.
 template <int NTAPS>
 __device__ __forceinline__ void fused_conv_unit16(const float* T1, int rm0, int rm1, int coloff, int lane, const float4 (&ub)[20], v4f& acc0, v4f& acc1)
 {
-    const float* base0 = T1 + rm0 * F_LD1 + coloff + (lane >> 4) * 4;
-    const float* base1 = T1 + rm1 * F_LD1 + coloff + (lane >> 4) * 4;
+    const float* base0 = T1 + rm0 + coloff + (lane >> 4) * 4;
+    const float* base1 = T1 + rm1 + coloff + (lane >> 4) * 4;
 #pragma unroll
     for (int t = 0; t < NTAPS; ++t) {
 #pragma unroll
@@ -1252,7 +1265,7 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
     float* T1 = smem + TR32 * F_LD1;          // [spt*(W+4)][F_LD1]   (TR32*F_LD1 >= 4*TR32*F_LDA)
     const int W = c.m[0].W, spt = c.m[0].spt;          // the same for every module of a chain (ds_internal.h FusedChain)
     float* T2 = T1 + (spt * (W + 4) + 5) * F_LD1;   // [TR32*F_LD2]  (T1 has 5 spare rows: a dump row for padding rows + its halo)
-    int* rowmap = reinterpret_cast<int*>(T2 + TR32 * F_LD2);   // [TR32] tile row -> T1 row
+    int* rowmap = reinterpret_cast<int*>(T2 + TR32 * F_LD2);   // [TR32] tile row -> offset of its T1 row, in floats (no multiply per use)
     float* const Bs = reinterpret_cast<float*>(rowmap + TR32); // [3][64] biases of b5b | b3b | b4b
     const int site0 = blockIdx.x * spt;
     const int nhere = min(spt, c.m[0].n_sites - site0);
@@ -1263,7 +1276,7 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
     for (int i = threadIdx.x; i < (spt * (W + 4) + 5) * (F_LD1 / 4); i += 512)
         reinterpret_cast<float4*>(T1)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (threadIdx.x < TR32)   // rows past the tile's last site map to the dump row, so LDS writes need no predicate
-        rowmap[threadIdx.x] = (int)threadIdx.x < TRv ? ((int)threadIdx.x / W) * (W + 4) + 2 + (int)threadIdx.x % W : spt * (W + 4) + 2;
+        rowmap[threadIdx.x] = ((int)threadIdx.x < TRv ? ((int)threadIdx.x / W) * (W + 4) + 2 + (int)threadIdx.x % W : spt * (W + 4) + 2) * F_LD1;
 
     // ---- the modules of the chain, one after the other on THIS tile (one module per launch in the diagnostic modes): module
     // k + 1 reads the rows module k has just written -- same workgroup, so they come back from this XCD's L2 and no launch
@@ -1285,7 +1298,7 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
     DS_STAMP(0);
     if (tid >= 256 && tid < 448) {
         const int q = tid - 256;
-        Bs[q] = gload((q < 64 ? a.bias5b : q < 128 ? a.bias3b : a.bias4b) + (q & 63));
+        Bs[q] = gload_at(q < 64 ? a.bias5b : q < 128 ? a.bias3b : a.bias4b, (unsigned)(q & 63) * 4u);
     }
 
     // ---- P1 staging cursor: thread -> (row, 16-byte slot); rows past the tile end re-read row TRv-1
@@ -1294,23 +1307,32 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
     const int rr = sr < TRv ? sr : TRv - 1;
     // plain input: one row per staged row. Pooled input (modules right after maxpool_layer2/3): the staged
     // row (site s, w) is the max of input rows 2w - pad + {0,1,2} of site s that exist (padded taps ignored).
+    // Every global address of P1 is (wave-uniform base: the tile's first input row / the wave's weight panel, in SGPRs) +
+    // (32-bit byte offset of the lane, the same for all chunks) + (the chunk, a literal of the unrolled loop): a vector
+    // instruction does not run in the shadow of an fp32 MFMA, so a per-lane 64-bit pointer bumped in every chunk is matrix time.
+    // (a tile's rows span < 2 MB: 8 sites x pool_win rows x 1 KB)
+    // DS_LANE_OFFSET(v) in front of a group of loads is an empty asm statement that "rewrites" the offset in place: no
+    // instruction, but hipcc can then no longer widen the offset to a 64-bit pair once per module, add the base to it there and
+    // carry that pair (two registers, and v_add_co / v_addc per chunk for whatever the 13-bit immediate does not reach).
     const bool pooled_in = a.pool_win > 0;
-    const float *pc, *pq = nullptr, *pr = nullptr;
+    const float* const xs = a.X + (pooled_in ? (size_t)site0 * a.pool_win : grow0) * cin;
+    unsigned oc, oq = 0, orr = 0;
     if (!pooled_in) {
-        pc = a.X + (grow0 + rr) * cin + sq * 4;
+        oc = (unsigned)(rr * cin + sq * 4) * 4u;
     } else {
         const int s_ = rr / W, w_ = rr % W;
         const int i0 = 2 * w_ - a.pool_pad;
         const int ia = i0 < 0 ? i0 + 1 : i0;                               // first existing tap
         const int ib = i0 + 1 < a.pool_win ? (i0 + 1 < 0 ? ia : i0 + 1) : ia;
         const int ic = i0 + 2 < a.pool_win ? i0 + 2 : ib;
-        const float* sb = a.X + ((size_t)(site0 + s_) * a.pool_win) * cin + sq * 4;
-        pc = sb + (size_t)ia * cin;
-        pq = sb + (size_t)ib * cin;
-        pr = sb + (size_t)ic * cin;
+        const int sb = s_ * a.pool_win;
+        oc = (unsigned)((sb + ia) * cin + sq * 4) * 4u;
+        oq = (unsigned)((sb + ib) * cin + sq * 4) * 4u;
+        orr = (unsigned)((sb + ic) * cin + sq * 4) * 4u;
     }
     // waves 0..5: n-tile `wave` of the 32-wide panel (K padded to 32 in the pack); waves 6, 7: b1's three 16-wide column tiles
-    const float* bp = wave < 6 ? a.Bp1 + ((size_t)wave * ((cin + 31) / 32 * 4) * 64 + lane) * 4 : a.Bp1r + lane * 4;
+    const float* const bs = wave < 6 ? a.Bp1 + (size_t)wave * ((cin + 31) / 32 * 4) * 256 : a.Bp1r;
+    unsigned lane16 = (unsigned)lane * 16u;
 
     // Every MFMA of this kernel is issued TRANSPOSED -- mfma(weight fragment, activation fragment) computes (X W)^T --
     // so a lane ends up holding, for ONE activation row (lane & 31), 4 x 4 consecutive output channels
@@ -1327,9 +1349,9 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
         float4 bv[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            bv[g] = gload4(a.bias1 + (wave < 6 ? wave * 32 + 8 * g + h4 : 192 + 16 * g + q4));   // bias1 is zero-padded to 256
+            bv[g] = gload4_at(a.bias1, (unsigned)(wave < 6 ? wave * 32 + 8 * g + h4 : 192 + 16 * g + q4) * 4u);   // bias1 is zero-padded to 256
             if (wave < 2) {                                                     // b5 stem columns also carry the tail's BN shift
-                const float4 t = gload4(a.bias5c + wave * 32 + 8 * g + h4);     // (zero-padded to 64)
+                const float4 t = gload4_at(a.bias5c, (unsigned)(wave * 32 + 8 * g + h4) * 4u);     // (zero-padded to 64)
                 bv[g].x += t.x; bv[g].y += t.y; bv[g].z += t.z; bv[g].w += t.w;
             }
         }
@@ -1370,27 +1392,28 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
         float4 af[2][POOL ? 1 : 2][TM];                  // pooling waves: one 16-row x 16-k fragment per row tile
         // (the pooling waves 6, 7 hold threads 384 .. 511 and a tile has at most 96 x 4 = 384 staging slots: they never stage,
         // and their variant carries neither the staging registers nor the row pointers)
-        auto load_a = [&](int V) __attribute__((always_inline)) {
+        auto load_a = [&](int V, int ch) __attribute__((always_inline)) {      // chunk ch into stage V
             if (!POOL && stager) {
-                vc[V] = gload4(pc); pc += KC;
+                DS_LANE_OFFSET(oc);
+                vc[V] = gload4_at(xs + ch * KC, oc);
                 if (pooled_in) {       // wave-uniform per launch
-                    vc[V] = f4max_relu(f4max_relu(vc[V], gload4(pq)), gload4(pr));
-                    pq += KC; pr += KC;
+                    DS_LANE_OFFSET(oq); DS_LANE_OFFSET(orr);
+                    vc[V] = f4max_relu(f4max_relu(vc[V], gload4_at(xs + ch * KC, oq)), gload4_at(xs + ch * KC, orr));
                 }
             }
         };
         auto store_a = [&](int X, int V) __attribute__((always_inline)) {
             if (!POOL && stager) *reinterpret_cast<float4*>(Ad + X * TR32 * F_LDA + sr * F_LDA + sq * 4) = vc[V];
         };
-        auto load_b = [&](int Bi) __attribute__((always_inline)) {
+        auto load_b = [&](int Bi, int ch) __attribute__((always_inline)) {     // chunk ch's fragments into stage Bi
+            DS_LANE_OFFSET(lane16);
             if (POOL) {
 #pragma unroll
-                for (int ct = 0; ct < 3; ++ct) bq[Bi][ct] = gload4(bp + ct * cin * 16);      // a column tile's image is cin / 16 KiB
-                bp += 256;
+                for (int ct = 0; ct < 3; ++ct) bq[Bi][ct] = gload4_at(sbase(bs + ct * cin * 16 + ch * 256), lane16);      // a column tile's image is cin / 16 KiB
             } else {
-                bq[Bi][0] = gload4(bp);
-                bq[Bi][1] = gload4(bp + 256);
-                bp += 512;
+                const float* const b = sbase(bs + ch * 512);
+                bq[Bi][0] = gload4_at(b, lane16);
+                bq[Bi][1] = gload4_at(b + 256, lane16);
             }
         };
         auto read_frags = [&](int X) __attribute__((always_inline)) {
@@ -1436,9 +1459,9 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
             }
         };
 #pragma unroll
-        for (int i = 0; i < VD; ++i) load_a(i);                  // chunks 0 .. VD - 1 (nchunks >= 15)
+        for (int i = 0; i < VD; ++i) load_a(i, i);               // chunks 0 .. VD - 1 (nchunks >= 15)
 #pragma unroll
-        for (int i = 0; i < BD - 1; ++i) load_b(i);              // weight fragments of chunks 0 .. BD - 2
+        for (int i = 0; i < BD - 1; ++i) load_b(i, i);           // weight fragments of chunks 0 .. BD - 2
         store_a(0, 0);
         __syncthreads();
         read_frags(0);
@@ -1447,8 +1470,8 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
             if (c < nchunks) {                                    // wave-uniform; only c = 15 is really conditional
                 const int X = c & 1;
                 const bool has1 = c + 1 < nchunks;
-                if (c + VD < nchunks) load_a(c % VD);             // chunk c + VD into the stage chunk c left (written at step c - 1)
-                if (c + BD - 1 < nchunks) load_b((c + BD - 1) % BD);
+                if (c + VD < nchunks) load_a(c % VD, c + VD);     // chunk c + VD into the stage chunk c left (written at step c - 1)
+                if (c + BD - 1 < nchunks) load_b((c + BD - 1) % BD, c + BD - 1);
                 if (has1) store_a(X ^ 1, (c + 1) % VD);
                 mfma_rs(X, c % BD, 0);
                 __builtin_amdgcn_sched_barrier(0);
@@ -1504,7 +1527,7 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
     // paths", and hipcc keeps such a value live around the whole module loop -- 80 + 32 VGPRs of phantom live range here)
 #pragma unroll
     for (int g = 0; g < 20; ++g) pf[g] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a1k) fused_unit_prefetch<12>(a1k == 1 ? a.Bp5b + a1n * (12 * 256) : a.Bp3b, lane, pf);
+    if (a1k) fused_unit_prefetch<12>(a1k == 1 ? a.Bp5b + a1n * (12 * 256) : a.Bp3b, lane16, pf);
 
     // ---- P1 epilogue (bias already inside acc): route the 256 columns. b1|b2 go through an LDS tile and leave as
     // whole 384-B row segments.
@@ -1514,7 +1537,7 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
             const int rm = rowmap[mt * 32 + rlane];
 #pragma unroll
             for (int g = 0; g < 4; ++g)
-                *reinterpret_cast<float4*>(T1 + rm * F_LD1 + (wave * 32 - 96) + 8 * g + h4) =
+                *reinterpret_cast<float4*>(T1 + rm + (wave * 32 - 96) + 8 * g + h4) =
                     make_float4(relu_f(acc[mt][4 * g]), relu_f(acc[mt][4 * g + 1]), relu_f(acc[mt][4 * g + 2]),
                                 relu_f(acc[mt][4 * g + 3]));
         }
@@ -1541,7 +1564,7 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
         if (row < TRv) {
             const float4 v = *reinterpret_cast<const float4*>(Ys + row * F_LD1 + q * 4);
             v4f o = {v.x, v.y, v.z, v.w};
-            *(__attribute__((address_space(1))) v4f*)(Yg + (unsigned)(row * 240 + q * 4)) = o;
+            gstore4_at(Yg, (unsigned)(row * 240 + q * 4) * 4u, o);
         }
     }
 
@@ -1560,13 +1583,13 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
         if (kind == 1) {
 #pragma unroll
             for (int g = 0; g < 4; ++g)
-                *reinterpret_cast<float4*>(T2 + row * F_LD2 + nt * 32 + 8 * g + h4) =
+                *reinterpret_cast<float4*>(T2 + (mt * 32 * F_LD2 + nt * 32) + (rlane * F_LD2 + h4) + 8 * g) =      // scalar part | lane part
                     make_float4(relu_f(u[4 * g]), relu_f(u[4 * g + 1]), relu_f(u[4 * g + 2]), relu_f(u[4 * g + 3]));
         } else if (row < TRv) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 v4f o = {relu_f(u[4 * g]), relu_f(u[4 * g + 1]), relu_f(u[4 * g + 2]), relu_f(u[4 * g + 3])};
-                *(__attribute__((address_space(1))) v4f*)(Yg + (unsigned)(row * 240 + 96 + 8 * g + h4)) = o;
+                gstore4_at(Yg + 96 + 8 * g, (unsigned)(row * 240 + h4) * 4u, o);      // the literal rides in the store's immediate
             }
         }
     };
@@ -1584,7 +1607,7 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 v4f o = {relu_f(u[4 * g]), relu_f(u[4 * g + 1]), relu_f(u[4 * g + 2]), relu_f(u[4 * g + 3])};
-                *(__attribute__((address_space(1))) v4f*)(Yg + (unsigned)(row * 240 + 144 + 8 * g + h4)) = o;
+                gstore4_at(Yg + 144 + 8 * g, (unsigned)(row * 240 + h4) * 4u, o);
             }
         }
     };
@@ -1595,14 +1618,14 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
         const float4 t = *reinterpret_cast<const float4*>(Bs + (NTAPS == 3 ? 64 : 128) + 32 + q4);
         v4f u0 = {t.x, t.y, t.z, t.w}, u1 = u0;
         fused_conv_unit16<NTAPS>(T1, rowmap[row0], rowmap[row1], NTAPS == 3 ? 0 : 32, lane, pf, u0, u1);
-        const int ycol = (NTAPS == 3 ? 96 : 144) + 32 + q4;
+        constexpr int ycol = (NTAPS == 3 ? 96 : 144) + 32;
         if (row0 < TRv) {
             v4f o = {relu_f(u0[0]), relu_f(u0[1]), relu_f(u0[2]), relu_f(u0[3])};
-            *(__attribute__((address_space(1))) v4f*)(Yg + (unsigned)(row0 * 240 + ycol)) = o;
+            gstore4_at(Yg + ycol, (unsigned)(row0 * 240 + q4) * 4u, o);
         }
         if (row1 < TRv) {
             v4f o = {relu_f(u1[0]), relu_f(u1[1]), relu_f(u1[2]), relu_f(u1[3])};
-            *(__attribute__((address_space(1))) v4f*)(Yg + (unsigned)(row1 * 240 + ycol)) = o;
+            gstore4_at(Yg + ycol, (unsigned)(row1 * 240 + q4) * 4u, o);
         }
     };
 
@@ -1613,29 +1636,29 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
         // ---- P2a
         if (a1k) unit_full3(a1k, a1m, a1n);
         if (a2m >= 0) {
-            fused_unit_prefetch<6>(a.Bp3r, lane, pf);
+            fused_unit_prefetch<6>(a.Bp3r, lane16, pf);
             unit_rem(FusedTaps3{}, a2m);
         }
         // ---- P2b behind the T2 barrier (the same barrier as waves 0, 1's). The weights of a wave's 1x5 unit are requested before
         // it. Request, barrier and unit sit in ONE branch per kind: were the request under one condition and the unit under
         // another, hipcc would keep the previous unit's weights alive across the barrier for the paths it cannot rule out.
         if (b1k == 3) {
-            fused_unit_prefetch<20>(a.Bp4b, lane, pf);
+            fused_unit_prefetch<20>(a.Bp4b, lane16, pf);
             DS_STAMP(5); __syncthreads(); DS_STAMP(6);
             unit_full5(b1m);
         } else if (b1k == 5) {
-            fused_unit_prefetch<10>(a.Bp4r, lane, pf);
+            fused_unit_prefetch<10>(a.Bp4r, lane16, pf);
             DS_STAMP(5); __syncthreads(); DS_STAMP(6);
             unit_rem(FusedTaps5{}, b1m);
         } else {
             DS_STAMP(5); __syncthreads(); DS_STAMP(6);
         }
         if (b2m >= 0) {
-            fused_unit_prefetch<12>(a.Bp3b, lane, pf);
+            fused_unit_prefetch<12>(a.Bp3b, lane16, pf);
             unit_full3(2, b2m, 0);
         }
         if (b3m >= 0) {
-            fused_unit_prefetch<6>(a.Bp3r, lane, pf);
+            fused_unit_prefetch<6>(a.Bp3r, lane16, pf);
             unit_rem(FusedTaps3{}, b3m);
         }
     } else {
@@ -1643,8 +1666,9 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
         unit_full3(1, a1m, a1n);
         // weights of the tail are requested before the barrier
         float4 b5c[8];
+        DS_LANE_OFFSET(lane16);
 #pragma unroll
-        for (int g = 0; g < 8; ++g) b5c[g] = gload4(a.Bp5c + ((size_t)(wave * 8 + g) * 64 + lane) * 4);
+        for (int g = 0; g < 8; ++g) b5c[g] = gload4_at(sbase(a.Bp5c + (size_t)(wave * 8 + g / 4 * 4) * 256) + (g % 4) * 256, lane16);
         DS_STAMP(5);
         __syncthreads();   // T2 complete
         DS_STAMP(6);
@@ -1663,16 +1687,19 @@ __device__ __forceinline__ void inception_fused_body(const FusedChain& c)
                 acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(b5c[g].w, av.w, acc[mt], 0, 0, 0);
             }
         }
+        const gptr1w Yt = sbase(Yg + 192 + wave * 32);
 #pragma unroll
         for (int mt = 0; mt < TM; ++mt) {
             const int row = mt * 32 + rlane;
             if (row < TRv) {
+                unsigned yo = (unsigned)(row * 240 + h4) * 4u;
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
                     if (wave * 32 + 8 * g < 48) {
+                        DS_LANE_OFFSET(yo);
                         v4f o = {relu_f(acc[mt][4 * g]), relu_f(acc[mt][4 * g + 1]), relu_f(acc[mt][4 * g + 2]),
                                  relu_f(acc[mt][4 * g + 3])};
-                        *(__attribute__((address_space(1))) v4f*)(Yg + (unsigned)(row * 240 + 192 + wave * 32 + 8 * g + h4)) = o;
+                        gstore4_at(Yt + 8 * g, yo, o);
                     }
             }
         }
