@@ -275,7 +275,7 @@ struct ds_handle {
     int64_t cb_chunks = 0;
     dse::Eval* eval = nullptr;            // evaluate --on gpu: the open run (ds_eval_begin .. ds_eval_end); table, counters and buffers are its own
     Times<4> ev_t;        // batches of the evaluate runs ended so far (the open run's are added on top)
-    // training (ds_train_begin .. ds_train_end, ds_train.hip): the RNN-only, no-embedding variant keeps the tensors it was loaded with
+    // training (ds_train_begin .. ds_train_end, ds_train.hip): the RNN-only variants (is_base 0 and 1) keep the tensors they were loaded with
     // (`kept`: what ds_train_begin starts from and ds_train_set_tensor replaces) and remembers which device blocks hold the packed
     // weights (`weight_allocs`), so that ds_train_sync_weights can pack the current parameters in their place
     std::map<std::string, HostTensor> kept;
@@ -758,7 +758,7 @@ int finalize_weights(ds_handle* h)
         if ((rc = upload(h, &h->fc2, w2->data))) return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->cur->s0));
-    if (h->is_rnn && !h->is_cnn && !h->is_base) h->kept = h->host;      // the trainable variant (ds_train_begin)
+    if (h->is_rnn && !h->is_cnn) h->kept = h->host;      // the trainable variants (ds_train_begin, ds_train_begin_base)
     h->host.clear();
     h->finalized = true;
     return DS_OK;
@@ -3348,12 +3348,15 @@ static int train_ready(ds_handle* h, const char* who)
     return DS_OK;
 }
 
-static int ds_train_begin_impl(ds_handle* h, const ds_train_config* cfg)
+// `with_base`: ds_train_begin_base, which takes an is_base 1 handle too; ds_train_begin keeps refusing it
+static int ds_train_begin_impl(ds_handle* h, const ds_train_config* cfg, bool with_base)
 {
     if (!h) return DS_ERR_INVALID;
     if (!cfg) return fail(h, DS_ERR_INVALID, "ds_train_begin: null config");
     if (h->is_cnn) return fail(h, DS_ERR_UNSUPPORTED, "ds_train_begin: this release trains the RNN-only model (is_cnn must be 0: the signal model has no backward)");
-    if (h->is_base) return fail(h, DS_ERR_UNSUPPORTED, "ds_train_begin: this release trains the RNN-only model (is_base must be 0: the embedding has no gradient)");
+    if (!h->is_rnn) return fail(h, DS_ERR_UNSUPPORTED, "ds_train_begin: this release trains the RNN-only model (is_rnn must be 1)");
+    if (h->is_base && !with_base)
+        return fail(h, DS_ERR_UNSUPPORTED, "ds_train_begin: is_base must be 0 here (the embedding is trained through ds_train_begin_base / ds_train_step_base)");
     if (h->C != 2) return fail(h, DS_ERR_UNSUPPORTED, "ds_train_begin: class_num must be 2");
     if (h->cfg.precision != DS_PRECISION_FP32) return fail(h, DS_ERR_UNSUPPORTED, "ds_train_begin: precision must be DS_PRECISION_FP32");
     if (!h->finalized) return fail(h, DS_ERR_INVALID, "ds_train_begin: weights not loaded");
@@ -3362,13 +3365,14 @@ static int ds_train_begin_impl(ds_handle* h, const ds_train_config* cfg)
     if (!(cfg->pos_weight > 0.f) || std::isinf(cfg->pos_weight)) return fail(h, DS_ERR_INVALID, "ds_train_begin: pos_weight must be positive and finite");
     if (cfg->beta1 < 0.f || cfg->beta1 >= 1.f || cfg->beta2 < 0.f || cfg->beta2 >= 1.f || cfg->epsilon < 0.f || std::isnan(cfg->beta1 + cfg->beta2 + cfg->epsilon))
         return fail(h, DS_ERR_INVALID, "ds_train_begin: beta1, beta2 must lie in [0, 1) and epsilon must not be negative");
-    std::vector<float> params((size_t)dstr::PARAM_FLOATS);
-    for (int i = 0; i < dstr::NTENSOR; ++i) {
+    const int in0 = dstr::in0_of(h->is_base);
+    std::vector<float> params((size_t)dstr::param_floats(in0));
+    for (int i = 0; i < dstr::ntensor(in0); ++i) {
         const std::string name = dstr::tensor_name(i);
         auto it = h->kept.find(name);
-        if (it == h->kept.end() || (int64_t)it->second.data.size() != dstr::tensor_floats(i))
+        if (it == h->kept.end() || (int64_t)it->second.data.size() != dstr::tensor_floats(i, in0))
             return fail(h, DS_ERR_INVALID, "ds_train_begin: missing/bad tensor " + name);
-        std::copy(it->second.data.begin(), it->second.data.end(), params.begin() + dstr::tensor_off(i));
+        std::copy(it->second.data.begin(), it->second.data.end(), params.begin() + dstr::tensor_off(i, in0));
     }
     dstr::Config c;
     c.keep_prob = cfg->keep_prob; c.pos_weight = cfg->pos_weight; c.seed = cfg->seed;
@@ -3377,7 +3381,7 @@ static int ds_train_begin_impl(ds_handle* h, const ds_train_config* cfg)
     if (cfg->epsilon != 0.f) c.epsilon = cfg->epsilon;
     if (!h->train) h->train = new dstr::Trainer();
     std::string err;
-    const int rc = h->train->begin(h->cfg.device, h->T, h->B, c, params.data(), &err);
+    const int rc = h->train->begin(h->cfg.device, h->T, h->B, in0, c, params.data(), &err);
     if (rc) { delete h->train; h->train = nullptr; h->training = false; return fail(h, rc, "ds_train_begin: " + err); }
     h->training = true;
     return DS_OK;
@@ -3386,32 +3390,37 @@ static int ds_train_begin_impl(ds_handle* h, const ds_train_config* cfg)
 static int ds_train_set_tensor_impl(ds_handle* h, const char* name, const float* data, int64_t count)
 {
     if (!h || !name || !data) return fail(h, DS_ERR_INVALID, "ds_train_set_tensor: bad argument");
-    if (!h->finalized || h->kept.empty()) return fail(h, DS_ERR_INVALID, "ds_train_set_tensor: the handle holds no trainable weights (RNN-only, is_base 0, loaded)");
-    const int idx = dstr::tensor_index(name);
-    if (idx < 0 || count != dstr::tensor_floats(idx)) return fail(h, DS_ERR_INVALID, std::string("ds_train_set_tensor: unknown tensor or wrong size: ") + name);
+    if (!h->finalized || h->kept.empty()) return fail(h, DS_ERR_INVALID, "ds_train_set_tensor: the handle holds no trainable weights (RNN-only, loaded)");
+    const int idx = dstr::tensor_index(name), in0 = dstr::in0_of(h->is_base);
+    if (idx < 0 || idx >= dstr::ntensor(in0) || count != dstr::tensor_floats(idx, in0)) return fail(h, DS_ERR_INVALID, std::string("ds_train_set_tensor: unknown tensor or wrong size: ") + name);
     h->kept[name].data.assign(data, data + count);
     return DS_OK;
 }
 
-static int ds_train_step_impl(ds_handle* h, int32_t n, const float* means, const float* stds, const float* sanums, const int32_t* labels, float lr,
-                              float* loss, int32_t* pred)
+// ds_train_step (kmer = nullptr, no codes to give), ds_train_step_base and ds_train_eval (`eval`; lr unused)
+static int ds_train_step_impl(ds_handle* h, const char* who, bool eval, int32_t n, const int32_t* kmer, const float* means, const float* stds,
+                              const float* sanums, const int32_t* labels, float lr, float* loss, int32_t* pred, float* logits)
 {
-    if (int rc = train_ready(h, "ds_train_step")) return rc;
-    if (n < 1 || n > h->B) return fail(h, DS_ERR_INVALID, "ds_train_step: n must lie in [1, max_batch]");
-    if (!means || !stds || !sanums || !labels) return fail(h, DS_ERR_INVALID, "ds_train_step: null buffer");
-    if (std::isnan(lr)) return fail(h, DS_ERR_INVALID, "ds_train_step: lr is NaN");
+    const std::string me = who;
+    if (int rc = train_ready(h, who)) return rc;
+    if (n < 1 || n > h->B) return fail(h, DS_ERR_INVALID, me + ": n must lie in [1, max_batch]");
+    if (!means || !stds || !sanums || !labels) return fail(h, DS_ERR_INVALID, me + ": null buffer");
+    if (h->train->in0 != dstr::NFEAT && !kmer)
+        return fail(h, DS_ERR_INVALID, me + ": this run trains the embedding (is_base 1) and needs the k-mer codes: ds_train_step_base");
+    if (std::isnan(lr)) return fail(h, DS_ERR_INVALID, me + ": lr is NaN");
     for (int32_t i = 0; i < n; ++i)
-        if (labels[i] != 0 && labels[i] != 1) return fail(h, DS_ERR_INVALID, "ds_train_step: label " + std::to_string(labels[i]) + " of row " + std::to_string(i) + " is outside {0, 1}");
+        if (labels[i] != 0 && labels[i] != 1) return fail(h, DS_ERR_INVALID, me + ": label " + std::to_string(labels[i]) + " of row " + std::to_string(i) + " is outside {0, 1}");
     std::string err;
-    const int rc = h->train->step(n, means, stds, sanums, labels, lr, loss, pred, &err);
-    return rc ? fail(h, rc, "ds_train_step: " + err) : DS_OK;
+    const int rc = h->train->run(eval, n, kmer, means, stds, sanums, labels, lr, loss, pred, logits, &err);
+    return rc ? fail(h, rc, me + ": " + err) : DS_OK;
 }
 
 static int ds_train_sync_weights_impl(ds_handle* h)
 {
     if (int rc = train_ready(h, "ds_train_sync_weights")) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    std::vector<float> params((size_t)dstr::PARAM_FLOATS);
+    const int in0 = h->train->in0;
+    std::vector<float> params((size_t)dstr::param_floats(in0));
     std::string err;
     if (int rc = h->train->read_params(params.data(), &err)) return fail(h, rc, "ds_train_sync_weights: " + err);
     // nothing enqueued may still read the packed weights; the plans (launch descriptors, captured graphs) name them and go too
@@ -3430,11 +3439,11 @@ static int ds_train_sync_weights_impl(ds_handle* h)
     h->weight_allocs.clear();
     std::map<std::string, HostTensor> loaded = std::move(h->kept);      // what ds_train_begin starts from stays what was loaded
     h->host.clear();
-    for (int i = 0; i < dstr::NTENSOR; ++i) {
+    for (int i = 0; i < dstr::ntensor(in0); ++i) {
         const std::string name = dstr::tensor_name(i);
         HostTensor t;
         t.shape = loaded[name].shape;
-        t.data.assign(params.begin() + dstr::tensor_off(i), params.begin() + dstr::tensor_off(i) + dstr::tensor_floats(i));
+        t.data.assign(params.begin() + dstr::tensor_off(i, in0), params.begin() + dstr::tensor_off(i, in0) + dstr::tensor_floats(i, in0));
         h->host[name] = std::move(t);
     }
     h->finalized = false;
@@ -3448,7 +3457,7 @@ static int64_t train_get(ds_handle* h, const char* who, const char* name, float*
 {
     if (int rc = train_ready(h, who)) return rc;
     const int idx = dstr::tensor_index(name);
-    if (idx < 0 || !out) return fail(h, DS_ERR_INVALID, std::string(who) + ": unknown tensor " + (name ? name : "(null)"));
+    if (idx < 0 || idx >= dstr::ntensor(h->train->in0) || !out) return fail(h, DS_ERR_INVALID, std::string(who) + ": unknown tensor " + (name ? name : "(null)"));
     std::string err;
     const int64_t rc = h->train->get(grad ? h->train->G : h->train->P, idx, out, cap, &err);
     return rc < 0 ? fail(h, (int)rc, std::string(who) + ": " + err) : rc;
@@ -3492,9 +3501,12 @@ int ds_get_train_times(ds_handle* h, int32_t reset, int64_t* steps, double* ms)
     return DS_OK;
 }
 
-int ds_train_begin(ds_handle* h, const ds_train_config* cfg) { return guarded(h, [&] { return ds_train_begin_impl(h, cfg); }); }
+int ds_train_begin(ds_handle* h, const ds_train_config* cfg) { return guarded(h, [&] { return ds_train_begin_impl(h, cfg, false); }); }
+int ds_train_begin_base(ds_handle* h, const ds_train_config* cfg) { return guarded(h, [&] { return ds_train_begin_impl(h, cfg, true); }); }
+int ds_train_step_base(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums, const int32_t* labels, float lr, float* loss, int32_t* pred) { return guarded(h, [&] { return ds_train_step_impl(h, "ds_train_step_base", false, n, kmer, means, stds, sanums, labels, lr, loss, pred, nullptr); }); }
+int ds_train_eval(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums, const int32_t* labels, float* loss, int32_t* pred, float* logits) { return guarded(h, [&] { return ds_train_step_impl(h, "ds_train_eval", true, n, kmer, means, stds, sanums, labels, 0.f, loss, pred, logits); }); }
 int ds_train_set_tensor(ds_handle* h, const char* name, const float* data, int64_t count) { return guarded(h, [&] { return ds_train_set_tensor_impl(h, name, data, count); }); }
-int ds_train_step(ds_handle* h, int32_t n, const float* means, const float* stds, const float* sanums, const int32_t* labels, float lr, float* loss, int32_t* pred) { return guarded(h, [&] { return ds_train_step_impl(h, n, means, stds, sanums, labels, lr, loss, pred); }); }
+int ds_train_step(ds_handle* h, int32_t n, const float* means, const float* stds, const float* sanums, const int32_t* labels, float lr, float* loss, int32_t* pred) { return guarded(h, [&] { return ds_train_step_impl(h, "ds_train_step", false, n, nullptr, means, stds, sanums, labels, lr, loss, pred, nullptr); }); }
 int ds_train_sync_weights(ds_handle* h) { return guarded(h, [&] { return ds_train_sync_weights_impl(h); }); }
 int64_t ds_train_get_tensor(ds_handle* h, const char* name, float* out, int64_t cap) { return guarded(h, [&] { return train_get(h, "ds_train_get_tensor", name, out, cap, false); }); }
 int64_t ds_train_get_grad(ds_handle* h, const char* name, float* out, int64_t cap) { return guarded(h, [&] { return train_get(h, "ds_train_get_grad", name, out, cap, true); }); }

@@ -1,4 +1,4 @@
-// ds_train.h — the training step of the RNN-only model (denoise; ds_train.hip): the formulas the host and the device share
+// ds_train.h — the training step of the RNN-only model, with or without the embedding (denoise, train; ds_train.hip): the formulas the host and the device share
 // (tensor order, dropout mask function, Adam step size) and the host-side state of one training run on a handle. The mask
 // function is __host__ __device__, so the CPU checker behind ds_train_mask_reference runs the code the kernels run.
 // Not part of the public ABI.
@@ -14,40 +14,50 @@ namespace dstr {
 
 #define DSTR_HD __host__ __device__ inline
 
-constexpr int HID = 256, GATES = 4 * HID, NLAYER = 3, NDIR = 2, FC = 2 * HID, NCLASS = 2, IN0 = 3;
+constexpr int HID = 256, GATES = 4 * HID, NLAYER = 3, NDIR = 2, FC = 2 * HID, NCLASS = 2;
+constexpr int NFEAT = 3, VOCAB = 1024, EMB = 128;      // (mean, std, length) per base; the embedding table [VOCAB][EMB]
 constexpr float FORGET_BIAS = 1.0f;
 
-// ---- the 14 trainable tensors, in the order of the parameter block: per direction (fw, bw) and layer kernel [in + 256][1024] then
-// bias [1024]; then dense/kernel [512][512] and dense_1/kernel [512][2]. Both directions have the same layout, so the bw block is the
-// fw block shifted by DIR_FLOATS.
-constexpr int NTENSOR = 14;
-DSTR_HD int layer_in(int l) { return l == 0 ? IN0 : HID; }
-DSTR_HD int64_t kernel_off(int l)        // floats from a direction's start to layer l's kernel
+// ---- the trainable tensors, in the order of the parameter block: per direction (fw, bw) and layer kernel [in + 256][1024] then
+// bias [1024]; then dense/kernel [512][512] and dense_1/kernel [512][2]; then, on an is_base 1 run only, modelembedding [1024][128].
+// Both directions have the same layout, so the bw block is the fw block shifted by dir_floats. `in0` is the layer-0 input width of
+// the run: NFEAT (is_base 0) or EMB + NFEAT (is_base 1: the embedding row, then the three features, as model.py:64-69 concatenates
+// them). With in0 = NFEAT the block is the 14 tensors alone; the embedding comes last so that they keep their places among themselves.
+constexpr int NTENSOR = 14, TENSOR_EMB = 14;
+DSTR_HD int in0_of(bool is_base) { return is_base ? EMB + NFEAT : NFEAT; }
+DSTR_HD int ntensor(int in0) { return in0 == NFEAT ? NTENSOR : NTENSOR + 1; }
+DSTR_HD int x0_pitch(int in0) { return (in0 + 3) & ~3; }      // floats per layer-0 input row: 4 or 132 (whole float4s, zero padded)
+DSTR_HD int layer_in(int l, int in0) { return l == 0 ? in0 : HID; }
+DSTR_HD int64_t kernel_off(int l, int in0)        // floats from a direction's start to layer l's kernel
 {
     int64_t o = 0;
-    for (int k = 0; k < l; ++k) o += (int64_t)(layer_in(k) + HID) * GATES + GATES;
+    for (int k = 0; k < l; ++k) o += (int64_t)(layer_in(k, in0) + HID) * GATES + GATES;
     return o;
 }
-DSTR_HD int64_t bias_off(int l) { return kernel_off(l) + (int64_t)(layer_in(l) + HID) * GATES; }
-constexpr int64_t DIR_FLOATS = (int64_t)(IN0 + HID) * GATES + 2 * (int64_t)(2 * HID) * GATES + 3 * GATES;
-constexpr int64_t W1_OFF = 2 * DIR_FLOATS, W2_OFF = W1_OFF + (int64_t)FC * FC, PARAM_FLOATS = W2_OFF + (int64_t)FC * NCLASS;
+DSTR_HD int64_t bias_off(int l, int in0) { return kernel_off(l, in0) + (int64_t)(layer_in(l, in0) + HID) * GATES; }
+DSTR_HD int64_t dir_floats(int in0) { return (int64_t)(in0 + HID) * GATES + 2 * (int64_t)(2 * HID) * GATES + 3 * GATES; }
+DSTR_HD int64_t w1_off(int in0) { return 2 * dir_floats(in0); }
+DSTR_HD int64_t w2_off(int in0) { return w1_off(in0) + (int64_t)FC * FC; }
+DSTR_HD int64_t emb_off(int in0) { return w2_off(in0) + (int64_t)FC * NCLASS; }
+DSTR_HD int64_t param_floats(int in0) { return emb_off(in0) + (in0 == NFEAT ? 0 : (int64_t)VOCAB * EMB); }
 
-inline int64_t tensor_off(int idx)
+inline int64_t tensor_off(int idx, int in0)
 {
-    if (idx < 12) return (idx / 6) * DIR_FLOATS + ((idx & 1) ? bias_off((idx % 6) / 2) : kernel_off((idx % 6) / 2));
-    return idx == 12 ? W1_OFF : W2_OFF;
+    if (idx < 12) return (idx / 6) * dir_floats(in0) + ((idx & 1) ? bias_off((idx % 6) / 2, in0) : kernel_off((idx % 6) / 2, in0));
+    return idx == 12 ? w1_off(in0) : idx == 13 ? w2_off(in0) : emb_off(in0);
 }
-inline int64_t tensor_floats(int idx)
+inline int64_t tensor_floats(int idx, int in0)
 {
-    if (idx < 12) return (idx & 1) ? GATES : (int64_t)(layer_in((idx % 6) / 2) + HID) * GATES;
-    return idx == 12 ? (int64_t)FC * FC : (int64_t)FC * NCLASS;
+    if (idx < 12) return (idx & 1) ? GATES : (int64_t)(layer_in((idx % 6) / 2, in0) + HID) * GATES;
+    return idx == 12 ? (int64_t)FC * FC : idx == 13 ? (int64_t)FC * NCLASS : (int64_t)VOCAB * EMB;
 }
-// TF variable name -> index, -1 when it is none of the 14
+// TF variable name -> index, -1 when it is none of the 15
 inline int tensor_index(const char* name)
 {
     if (!name) return -1;
     if (!strcmp(name, "dense/kernel")) return 12;
     if (!strcmp(name, "dense_1/kernel")) return 13;
+    if (!strcmp(name, "modelembedding")) return TENSOR_EMB;
     const char* dirs[2] = {"fw", "bw"};
     const char* leaf[2] = {"kernel", "bias"};
     for (int d = 0; d < 2; ++d)
@@ -63,10 +73,13 @@ inline std::string tensor_name(int idx)
 {
     if (idx == 12) return "dense/kernel";
     if (idx == 13) return "dense_1/kernel";
+    if (idx == TENSOR_EMB) return "modelembedding";
     char nm[160];
     snprintf(nm, sizeof nm, "modelem/%s/multi_rnn_cell/cell_%d/lstm_cell/%s", idx / 6 ? "bw" : "fw", (idx % 6) / 2, (idx & 1) ? "bias" : "kernel");
     return nm;
 }
+// a k-mer code as the forward reads it (include/deepsignal_hip.h, "CODES"): below 0 acts as 0, above VOCAB - 1 as VOCAB - 1
+DSTR_HD int clamp_code(int32_t c) { return c < 0 ? 0 : c > VOCAB - 1 ? VOCAB - 1 : c; }
 
 // ---- dropout masks -----------------------------------------------------------------------------------------------------------
 // Streams: 0 .. 5 = "fw_l0", "fw_l1", "fw_l2", "bw_l0", "bw_l1", "bw_l2" (the DropoutWrapper of that cell: [n][T][256], t = the
@@ -127,15 +140,16 @@ constexpr int NPHASE = 5;      // forward sweep, backward sweep, weight gradient
 
 struct Trainer {
     int device = 0, T = 0, B = 0;
+    int in0 = NFEAT;                 // layer-0 input width of the run: NFEAT, or EMB + NFEAT with the embedding trained too
     Config cfg;
     int64_t step_count = 0;          // steps taken since begin(); the masks of step s use the counter s (first step: 0)
     int last_n = 0;                  // rows of the last step (0: none yet)
     hipStream_t stream = nullptr;
     hipEvent_t ev[NPHASE + 1] = {};       // phase boundaries of the last step
-    // parameter-shaped blocks [PARAM_FLOATS]
+    // parameter-shaped blocks [param_floats(in0)]
     float *P = nullptr, *G = nullptr, *M = nullptr, *V = nullptr;
     // per (direction, layer) activations, time-major: index ((d * NLAYER + l) * T + t) * B + row
-    float* X0 = nullptr;             // [2][T][B][4] layer-0 inputs (mean, std, length, 0) in processing order
+    float* X0 = nullptr;             // [2][T][B][x0_pitch] layer-0 inputs ([embedding row |] mean, std, length, 0) in processing order
     float* H = nullptr;              // [2][3][T][B][256] h_t
     float* Y = nullptr;              // [2][3][T][B][256] dropped output y_t
     float* Cs = nullptr;             // [2][3][T][B][256] c_t
@@ -147,18 +161,28 @@ struct Trainer {
     float *fc1 = nullptr, *drop1 = nullptr, *dfc1 = nullptr, *djoint = nullptr;   // [B][512]
     float *logits = nullptr, *dfc2 = nullptr, *rowloss = nullptr;                 // [B][2], [B][2], [B]
     float* d_in = nullptr;           // [3][B][T] means | stds | lengths
+    // is_base 1 only: the codes, the gradient of the embedded layer-0 inputs and the workspace of the embedding-gradient reduction
+    int32_t* d_kmer = nullptr;       // [B][T]
+    float* DX0 = nullptr;            // [2][T][B][128] dz_0 K0[0:128]^T
+    int32_t* eg_count = nullptr;     // [entry blocks][VOCAB] codes per block of 256 entries, then each (block, code)'s first slot
+    int32_t* eg_run = nullptr;       // [VOCAB + 1] first slot of a code's run | [VOCAB + 1] first chunk of a code
+    int32_t* eg_entry = nullptr;     // [B * T] entries e = row * T + p sorted by code, ascending in e within a code
+    int32_t* eg_chunk_code = nullptr;   // [chunks] the code a chunk belongs to
+    float* eg_partial = nullptr;     // [chunks][128] a chunk's sum
     int32_t* d_lab = nullptr;        // [B]
     int32_t* d_pred = nullptr;       // [B]
     float* d_loss = nullptr;
     uint8_t* d_mask = nullptr;       // ds_train_get_mask staging [B][T][512]
-    float* pin = nullptr;            // pinned staging: inputs in, [loss | pred] out
+    float* pin = nullptr;            // pinned staging: inputs in, [loss | pred] out, then codes in and logits out
     int64_t steps_timed = 0;
     double ms[NPHASE] = {};
 
     ~Trainer();
-    int begin(int device, int T, int B, const Config& cfg, const float* params, std::string* err);   // params: host block [PARAM_FLOATS]
-    int step(int n, const float* means, const float* stds, const float* lens, const int32_t* labels, float lr, float* loss, int32_t* pred,
-             std::string* err);
+    int begin(int device, int T, int B, int in0, const Config& cfg, const float* params, std::string* err);   // params: host block [param_floats(in0)]
+    // one step (eval = false), or the forward alone with every mask kept, which changes nothing but scratch (eval = true; lr unused)
+    int run(bool eval, int n, const int32_t* kmer, const float* means, const float* stds, const float* lens, const int32_t* labels, float lr,
+            float* loss, int32_t* pred, float* logits_out, std::string* err);
+    int max_chunks() const { return (B * T + 63) / 64 + (B * T < VOCAB ? B * T : VOCAB); }      // chunks of 64 entries, one partly filled per code
     int read_params(float* out, std::string* err);                 // the whole block, to the host
     int64_t get(const float* block, int idx, float* out, int64_t cap, std::string* err);
     int64_t get_mask(int stream, uint8_t* out, int64_t cap, std::string* err);

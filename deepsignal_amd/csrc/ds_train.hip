@@ -2,6 +2,9 @@
 // forward with dropout, weighted cross entropy, back-propagation through time, Adam. fp32 throughout, every matrix product on
 // v_mfma_f32_32x32x2_f32. No floating-point atomics: a reduction that is split over workgroups writes its partial sums as slabs
 // and reduce_slabs_kernel adds them in a fixed order, so a step is a pure function of (weights, batch, seed, step).
+// With is_base 1 (train; model.py:61-69) layer 0 reads [embedding row of the base's code | mean, std, length] and the embedding is a
+// 15th trained tensor: gather_x0_base_kernel in front, and after layer 0's backward sweep DX0 = dz_0 K0[0:128]^T summed per code in
+// an order the codes alone decide (emb_count_kernel .. emb_reduce_kernel). run(eval = true) is the forward alone with every mask kept.
 //
 // Layout. Activations are time-major per (direction d, layer l): element ((d * 3 + l) * T + t) * B + row, B = max_batch, t = the step
 // in the order the stack processes the sequence (bw: t = 0 is the last base). A step of one cell is then a dense [n][width] matrix
@@ -102,6 +105,112 @@ __global__ void gather_x0_kernel(const float* in, float* X0, int n, int T, int B
     v.z = in[((size_t)2 * B + row) * T + src];
     v.w = 0.f;
     reinterpret_cast<float4*>(X0)[((size_t)d * T + t) * B + row] = v;
+}
+
+// the same with the embedding (is_base 1): X0[d][t][row] = (embedding row of the base's code [128], mean, std, length, 0), one float4
+// per thread. The code is clamped into the table (clamp_code), so no value of it reads outside E.
+__global__ void gather_x0_base_kernel(const float* in, const int32_t* kmer, const float* E, float* X0, int n, int T, int B)
+{
+    constexpr int Q = EMB / 4 + 1;      // float4s per row
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= 2 * T * n * Q) return;
+    const int q = idx % Q, row = (idx / Q) % n, t = (idx / (Q * n)) % T, d = idx / (Q * n * T);
+    const int src = d == 0 ? t : T - 1 - t;
+    float4 v;
+    if (q < EMB / 4) {
+        v = reinterpret_cast<const float4*>(E)[(size_t)clamp_code(kmer[(size_t)row * T + src]) * (EMB / 4) + q];
+    } else {
+        v.x = in[((size_t)0 * B + row) * T + src];
+        v.y = in[((size_t)1 * B + row) * T + src];
+        v.z = in[((size_t)2 * B + row) * T + src];
+        v.w = 0.f;
+    }
+    reinterpret_cast<float4*>(X0)[(((size_t)d * T + t) * B + row) * Q + q] = v;
+}
+
+// ---- gradient of the embedding: dE[c] = sum over the entries e = row * T + p whose clamped code is c, ascending in e, of
+// DX0[fw][p][row] + DX0[bw][T - 1 - p][row]. The entries are sorted by code with a stable counting sort (integer counts only), a
+// code's run is cut into chunks of EG_CHUNK entries that are summed in parallel, and a code's chunk sums are added in chunk order:
+// the order of every floating-point addition is a function of the codes alone.
+constexpr int EG_BLOCK = 256, EG_CHUNK = 64;
+
+// count[blk][c] = entries of block blk (EG_BLOCK consecutive entries) with code c
+__global__ __launch_bounds__(EG_BLOCK) void emb_count_kernel(const int32_t* kmer, int32_t* count, int total)
+{
+    __shared__ int hist[VOCAB];
+    for (int c = threadIdx.x; c < VOCAB; c += EG_BLOCK) hist[c] = 0;
+    __syncthreads();
+    const int e = blockIdx.x * EG_BLOCK + threadIdx.x;
+    if (e < total) atomicAdd(&hist[clamp_code(kmer[e])], 1);
+    __syncthreads();
+    for (int c = threadIdx.x; c < VOCAB; c += EG_BLOCK) count[(size_t)blockIdx.x * VOCAB + c] = hist[c];
+}
+
+// one workgroup, one thread per code: count[blk][c] becomes the number of entries of code c in earlier blocks, run[c] the first slot
+// of code c's run (run[VOCAB] = total), chunk0[c] its first chunk (chunk0[VOCAB] = chunks in all), chunk_code[j] the code of chunk j
+__global__ __launch_bounds__(VOCAB) void emb_scan_kernel(int32_t* count, int32_t* run, int32_t* chunk0, int32_t* chunk_code, int nblk)
+{
+    __shared__ int a[VOCAB], b[VOCAB];
+    const int c = threadIdx.x;
+    int mine = 0;
+    for (int k = 0; k < nblk; ++k) {
+        const int v = count[(size_t)k * VOCAB + c];
+        count[(size_t)k * VOCAB + c] = mine;
+        mine += v;
+    }
+    const int chunks = (mine + EG_CHUNK - 1) / EG_CHUNK;
+    a[c] = mine; b[c] = chunks;
+    __syncthreads();
+    for (int off = 1; off < VOCAB; off <<= 1) {      // inclusive scans of both
+        const int x = c >= off ? a[c - off] : 0, y = c >= off ? b[c - off] : 0;
+        __syncthreads();
+        a[c] += x; b[c] += y;
+        __syncthreads();
+    }
+    run[c] = a[c] - mine;
+    chunk0[c] = b[c] - chunks;
+    if (c == VOCAB - 1) { run[VOCAB] = a[c]; chunk0[VOCAB] = b[c]; }
+    for (int k = 0; k < chunks; ++k) chunk_code[b[c] - chunks + k] = c;
+}
+
+// entry[slot] = e, slot = run[c] + (entries of c in earlier blocks) + (entries of c earlier in this block): stable
+__global__ __launch_bounds__(EG_BLOCK) void emb_scatter_kernel(const int32_t* kmer, const int32_t* count, const int32_t* run, int32_t* entry, int total)
+{
+    __shared__ int codes[EG_BLOCK];
+    const int e = blockIdx.x * EG_BLOCK + threadIdx.x;
+    const int c = e < total ? clamp_code(kmer[e]) : -1;
+    codes[threadIdx.x] = c;
+    __syncthreads();
+    if (c < 0) return;
+    int rank = 0;
+    for (int j = 0; j < (int)threadIdx.x; ++j) rank += codes[j] == c;
+    entry[run[c] + count[(size_t)blockIdx.x * VOCAB + c] + rank] = e;
+}
+
+// one workgroup per chunk, one lane per column: the chunk's entries in run order
+__global__ __launch_bounds__(EMB) void emb_partial_kernel(const float* DX0, const int32_t* entry, const int32_t* run, const int32_t* chunk0,
+                                                          const int32_t* chunk_code, float* partial, int T, int B)
+{
+    const int j = blockIdx.x, col = threadIdx.x;
+    if (j >= chunk0[VOCAB]) return;
+    const int c = chunk_code[j];
+    const int beg = run[c] + (j - chunk0[c]) * EG_CHUNK, end = min(run[c + 1], beg + EG_CHUNK);
+    const float* bw = DX0 + (size_t)T * B * EMB;
+    float s = 0.f;
+    for (int i = beg; i < end; ++i) {
+        const int e = entry[i], row = e / T, p = e % T;
+        s += DX0[((size_t)p * B + row) * EMB + col] + bw[((size_t)(T - 1 - p) * B + row) * EMB + col];
+    }
+    partial[(size_t)j * EMB + col] = s;
+}
+
+// dE[c] = its chunks' sums in chunk order; a code without entries has no chunk and gets +0.0
+__global__ __launch_bounds__(EMB) void emb_reduce_kernel(const float* partial, const int32_t* chunk0, float* dE)
+{
+    const int c = blockIdx.x, col = threadIdx.x;
+    float s = 0.f;
+    for (int j = chunk0[c]; j < chunk0[c + 1]; ++j) s += partial[(size_t)j * EMB + col];
+    dE[(size_t)c * EMB + col] = s;
 }
 
 struct CellArgs {
@@ -248,10 +357,12 @@ __global__ __launch_bounds__(256) void train_head_kernel(HeadArgs a)
 }
 
 // loss = sum of the rows' terms in row order, times `scale`; dW2[k][c] = sum over rows of drop1[row][k] dfc2[row][c] in row order
+// (dW2 = nullptr: the loss alone, for ds_train_eval)
 __global__ void train_head_reduce_kernel(const float* rowloss, const float* drop1, const float* dfc2, float* loss, float* dW2, int n, float scale)
 {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < FC * NCLASS) {
+        if (!dW2) return;
         const int k = idx >> 1, c = idx & 1;
         float s = 0.f;
         for (int r = 0; r < n; ++r) s = fmaf(drop1[(size_t)r * FC + k], dfc2[r * 2 + c], s);
@@ -340,10 +451,12 @@ void Trainer::release()
     if (stream) hipStreamSynchronize(stream);
     for (void* p : {(void*)P, (void*)G, (void*)M, (void*)V, (void*)X0, (void*)H, (void*)Y, (void*)Cs, (void*)Z, (void*)DX, (void*)DH, (void*)DC,
                     (void*)slab, (void*)fc1, (void*)drop1, (void*)dfc1, (void*)djoint, (void*)logits, (void*)dfc2, (void*)rowloss, (void*)d_in,
-                    (void*)d_lab, (void*)d_pred, (void*)d_loss, (void*)d_mask})
+                    (void*)d_lab, (void*)d_pred, (void*)d_loss, (void*)d_mask, (void*)d_kmer, (void*)DX0, (void*)eg_count, (void*)eg_run, (void*)eg_entry,
+                    (void*)eg_chunk_code, (void*)eg_partial})
         if (p) hipFree(p);
     P = G = M = V = X0 = H = Y = Cs = Z = DX = DH = DC = slab = fc1 = drop1 = dfc1 = djoint = logits = dfc2 = rowloss = d_in = d_loss = nullptr;
-    d_lab = d_pred = nullptr;
+    DX0 = eg_partial = nullptr;
+    d_lab = d_pred = d_kmer = eg_count = eg_run = eg_entry = eg_chunk_code = nullptr;
     d_mask = nullptr;
     if (pin) hipHostFree(pin);
     pin = nullptr;
@@ -356,17 +469,19 @@ void Trainer::release()
 
 Trainer::~Trainer() { release(); }
 
-int Trainer::begin(int dev, int T_, int B_, const Config& c, const float* params, std::string* err)
+int Trainer::begin(int dev, int T_, int B_, int in0_, const Config& c, const float* params, std::string* err)
 {
     TCK(hipSetDevice(dev));
-    if (T_ != T || B_ != B || dev != device || !P) {
+    const size_t PF = (size_t)param_floats(in0_);
+    if (T_ != T || B_ != B || in0_ != in0 || dev != device || !P) {
         release();
         device = dev;
+        in0 = in0_;
         TCK(hipSetDevice(dev));
         const size_t cells = (size_t)NDIR * NLAYER * T_ * B_;
         auto alloc = [&](auto** p, size_t count) { return hipMalloc((void**)p, std::max<size_t>(count * sizeof(**p), 256)); };
-        TCK(alloc(&P, PARAM_FLOATS)); TCK(alloc(&G, PARAM_FLOATS)); TCK(alloc(&M, PARAM_FLOATS)); TCK(alloc(&V, PARAM_FLOATS));
-        TCK(alloc(&X0, (size_t)NDIR * T_ * B_ * 4));
+        TCK(alloc(&P, PF)); TCK(alloc(&G, PF)); TCK(alloc(&M, PF)); TCK(alloc(&V, PF));
+        TCK(alloc(&X0, (size_t)NDIR * T_ * B_ * x0_pitch(in0)));
         TCK(alloc(&H, cells * HID)); TCK(alloc(&Y, cells * HID)); TCK(alloc(&Cs, cells * HID)); TCK(alloc(&Z, cells * GATES));
         TCK(alloc(&DX, (size_t)NDIR * T_ * B_ * HID)); TCK(alloc(&DH, (size_t)NDIR * B_ * HID)); TCK(alloc(&DC, (size_t)NDIR * B_ * HID));
         TCK(alloc(&slab, (size_t)NDIR * T_ * HID * GATES));
@@ -374,33 +489,43 @@ int Trainer::begin(int dev, int T_, int B_, const Config& c, const float* params
         TCK(alloc(&logits, (size_t)B_ * 2)); TCK(alloc(&dfc2, (size_t)B_ * 2)); TCK(alloc(&rowloss, (size_t)B_));
         TCK(alloc(&d_in, (size_t)3 * B_ * T_)); TCK(alloc(&d_lab, (size_t)B_)); TCK(alloc(&d_pred, (size_t)B_)); TCK(alloc(&d_loss, 1));
         TCK(alloc(&d_mask, (size_t)B_ * T_ * FC));
-        TCK(hipHostMalloc((void**)&pin, ((size_t)3 * B_ * T_ + 2 * (size_t)B_ + 4) * 4, hipHostMallocDefault));
+        TCK(hipHostMalloc((void**)&pin, ((size_t)4 * B_ * T_ + 4 * (size_t)B_ + 4) * 4, hipHostMallocDefault));
         TCK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         for (hipEvent_t& e : ev) TCK(hipEventCreate(&e));
         T = T_; B = B_;
+        if (in0 != NFEAT) {
+            TCK(alloc(&d_kmer, (size_t)B * T)); TCK(alloc(&DX0, (size_t)NDIR * T * B * EMB));
+            TCK(alloc(&eg_count, (size_t)((B * T + EG_BLOCK - 1) / EG_BLOCK) * VOCAB)); TCK(alloc(&eg_run, (size_t)2 * (VOCAB + 1)));
+            TCK(alloc(&eg_entry, (size_t)B * T)); TCK(alloc(&eg_chunk_code, (size_t)max_chunks())); TCK(alloc(&eg_partial, (size_t)max_chunks() * EMB));
+        }
     }
     TCK(hipStreamSynchronize(stream));
     cfg = c;
-    TCK(hipMemcpy(P, params, PARAM_FLOATS * sizeof(float), hipMemcpyHostToDevice));
-    TCK(hipMemset(G, 0, PARAM_FLOATS * sizeof(float)));
-    TCK(hipMemset(M, 0, PARAM_FLOATS * sizeof(float)));
-    TCK(hipMemset(V, 0, PARAM_FLOATS * sizeof(float)));
+    TCK(hipMemcpy(P, params, PF * sizeof(float), hipMemcpyHostToDevice));
+    TCK(hipMemset(G, 0, PF * sizeof(float)));
+    TCK(hipMemset(M, 0, PF * sizeof(float)));
+    TCK(hipMemset(V, 0, PF * sizeof(float)));
     step_count = 0;
     last_n = 0;
     return DS_OK;
 }
 
-int Trainer::step(int n, const float* means, const float* stds, const float* lens, const int32_t* labels, float lr, float* loss, int32_t* pred,
-                  std::string* err)
+int Trainer::run(bool eval, int n, const int32_t* kmer, const float* means, const float* stds, const float* lens, const int32_t* labels, float lr,
+                 float* loss, int32_t* pred, float* logits_out, std::string* err)
 {
     TCK(hipSetDevice(device));
     hipStream_t s = stream;
+    const bool base = in0 != NFEAT;
+    const int ldx = x0_pitch(in0);
+    const long long DF = dir_floats(in0), PF = param_floats(in0);
     const long long sAct = (long long)B * HID, sZt = (long long)B * GATES;               // floats per step
     const long long sActD = (long long)NLAYER * T * sAct, sZD = (long long)NLAYER * T * sZt;   // floats per direction
     auto act = [&](float* base, int l, int t) { return base + ((size_t)l * T + t) * sAct; };      // direction 0
     auto zat = [&](int l, int t) { return Z + ((size_t)l * T + t) * sZt; };
-    const float inv_keep = 1.f / cfg.keep_prob;
-    const uint32_t thr = keep_threshold(cfg.keep_prob);
+    // eval: keep_prob 1, under which inv_keep is 1 and the threshold 2^24 keeps every element whatever the step's masks are
+    const float keep_prob = eval ? 1.f : cfg.keep_prob;
+    const float inv_keep = 1.f / keep_prob;
+    const uint32_t thr = keep_threshold(keep_prob);
     const long long mstep = step_count;
     const dim3 cell_grid((n * HID + 255) / 256, 2);
 
@@ -412,25 +537,33 @@ int Trainer::step(int n, const float* means, const float* stds, const float* len
     memcpy(plab, labels, (size_t)n * sizeof(int32_t));
     TCK(hipMemcpyAsync(d_in, pf, (size_t)3 * B * T * sizeof(float), hipMemcpyHostToDevice, s));
     TCK(hipMemcpyAsync(d_lab, plab, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    float* ptail = pf + (size_t)3 * B * T + 2 * (size_t)B + 4;      // past [loss | pred]: the codes [B * T] in, the logits [B][2] out
+    if (base) {
+        memcpy(ptail, kmer, (size_t)n * T * sizeof(int32_t));
+        TCK(hipMemcpyAsync(d_kmer, ptail, (size_t)n * T * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
 
     // ---- forward sweep
-    TCK(hipEventRecord(ev[0], s));
-    hipLaunchKernelGGL(gather_x0_kernel, dim3((2 * T * n + 255) / 256), dim3(256), 0, s, d_in, X0, n, T, B);
+    if (!eval) TCK(hipEventRecord(ev[0], s));
+    if (base)
+        hipLaunchKernelGGL(gather_x0_base_kernel, dim3((2 * T * n * (EMB / 4 + 1) + 255) / 256), dim3(256), 0, s, d_in, d_kmer, P + emb_off(in0), X0, n, T, B);
+    else
+        hipLaunchKernelGGL(gather_x0_kernel, dim3((2 * T * n + 255) / 256), dim3(256), 0, s, d_in, X0, n, T, B);
     TCK(hipGetLastError());
     for (int l = 0; l < NLAYER; ++l) {
-        const int in = layer_in(l);
+        const int in = layer_in(l, in0);
         // the input half of every step's pre-activation in one batched product: Z(d, l, t) = X_t K[0:in] + b
-        GemmArgs g = l == 0 ? gemm_args(X0, 4, 0, P + kernel_off(l), GATES, 0, zat(l, 0), GATES, n, GATES, in, 0)
-                            : gemm_args(act(Y, l - 1, 0), HID, 0, P + kernel_off(l), GATES, 0, zat(l, 0), GATES, n, GATES, in, 0);
+        GemmArgs g = l == 0 ? gemm_args(X0, ldx, 0, P + kernel_off(l, in0), GATES, 0, zat(l, 0), GATES, n, GATES, in, 0)
+                            : gemm_args(act(Y, l - 1, 0), HID, 0, P + kernel_off(l, in0), GATES, 0, zat(l, 0), GATES, n, GATES, in, 0);
         g.nb1 = T; g.nb2 = 2;
-        g.sA1 = l == 0 ? (long long)B * 4 : sAct; g.sA2 = l == 0 ? (long long)T * B * 4 : sActD;
-        g.sB2 = DIR_FLOATS; g.sC1 = sZt; g.sC2 = sZD;
-        g.bias = P + bias_off(l); g.sBias2 = DIR_FLOATS;
+        g.sA1 = l == 0 ? (long long)B * ldx : sAct; g.sA2 = l == 0 ? (long long)T * B * ldx : sActD;
+        g.sB2 = DF; g.sC1 = sZt; g.sC2 = sZD;
+        g.bias = P + bias_off(l, in0); g.sBias2 = DF;
         TCK(gemm(s, g));
         for (int t = 0; t < T; ++t) {
             if (t > 0) {      // ... and the recurrent half step by step: Z(d, l, t) += h_{t-1} K[in:]
-                GemmArgs r = gemm_args(act(H, l, t - 1), HID, 0, P + kernel_off(l) + (size_t)in * GATES, GATES, 0, zat(l, t), GATES, n, GATES, HID, 1);
-                r.nb2 = 2; r.sA2 = sActD; r.sB2 = DIR_FLOATS; r.sC2 = sZD;
+                GemmArgs r = gemm_args(act(H, l, t - 1), HID, 0, P + kernel_off(l, in0) + (size_t)in * GATES, GATES, 0, zat(l, t), GATES, n, GATES, HID, 1);
+                r.nb2 = 2; r.sA2 = sActD; r.sB2 = DF; r.sC2 = sZD;
                 TCK(gemm(s, r));
             }
             CellArgs c{};
@@ -441,11 +574,11 @@ int Trainer::step(int n, const float* means, const float* stds, const float* len
             TCK(hipGetLastError());
         }
     }
-    TCK(hipEventRecord(ev[1], s));
+    if (!eval) TCK(hipEventRecord(ev[1], s));
 
     // ---- head: fc1 = [y_fw(T - 1) | y_bw(T - 1)] W1, dropout, fc2, dropout, loss, and the gradient back to the joint row
-    float* W1 = P + W1_OFF;
-    float* W2 = P + W2_OFF;
+    float* W1 = P + w1_off(in0);
+    float* W2 = P + w2_off(in0);
     for (int d = 0; d < 2; ++d)
         TCK(gemm(s, gemm_args(act(Y, NLAYER - 1, T - 1) + d * sActD, HID, 0, W1 + (size_t)d * HID * FC, FC, 0, fc1, FC, n, FC, HID, d)));
     const bool two_col = cfg.pos_weight == 1.f;
@@ -456,10 +589,22 @@ int Trainer::step(int n, const float* means, const float* stds, const float* len
     ha.step = mstep;
     hipLaunchKernelGGL(train_head_kernel, dim3(n), dim3(256), 0, s, ha);
     TCK(hipGetLastError());
-    hipLaunchKernelGGL(train_head_reduce_kernel, dim3((FC * NCLASS + 1 + 255) / 256), dim3(256), 0, s, rowloss, drop1, dfc2, d_loss, G + W2_OFF, n, scale);
+    hipLaunchKernelGGL(train_head_reduce_kernel, dim3((FC * NCLASS + 1 + 255) / 256), dim3(256), 0, s, rowloss, drop1, dfc2, d_loss,
+                       eval ? nullptr : G + w2_off(in0), n, scale);
     TCK(hipGetLastError());
+    float* pout = pin + (size_t)3 * B * T + B;
+    if (eval) {      // the forward, its loss and prediction alone: no gradient, moment, parameter or counter is written
+        TCK(hipMemcpyAsync(pout, d_loss, sizeof(float), hipMemcpyDeviceToHost, s));
+        TCK(hipMemcpyAsync(pout + 1, d_pred, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        TCK(hipMemcpyAsync(ptail + (size_t)B * T, logits, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, s));
+        TCK(hipStreamSynchronize(s));
+        if (loss) *loss = pout[0];
+        if (pred) memcpy(pred, pout + 1, (size_t)n * sizeof(int32_t));
+        if (logits_out) memcpy(logits_out, ptail + (size_t)B * T, (size_t)n * 2 * sizeof(float));
+        return DS_OK;
+    }
     {   // dW1 = joint^T dfc1 (rows 0 .. 255 from y_fw, 256 .. 511 from y_bw); djoint = dfc1 W1^T
-        GemmArgs g = gemm_args(act(Y, NLAYER - 1, T - 1), HID, 1, dfc1, FC, 0, G + W1_OFF, FC, HID, FC, n, 0);
+        GemmArgs g = gemm_args(act(Y, NLAYER - 1, T - 1), HID, 1, dfc1, FC, 0, G + w1_off(in0), FC, HID, FC, n, 0);
         g.nb2 = 2; g.sA2 = sActD; g.sC2 = (long long)HID * FC;
         TCK(gemm(s, g));
         TCK(gemm(s, gemm_args(dfc1, FC, 0, W1, FC, 1, djoint, FC, n, FC, FC, 0)));
@@ -468,7 +613,7 @@ int Trainer::step(int n, const float* means, const float* stds, const float* len
 
     // ---- backward sweep, top layer first; every step leaves its gate gradients dz in Z
     for (int l = NLAYER - 1; l >= 0; --l) {
-        const int in = layer_in(l);
+        const int in = layer_in(l, in0);
         for (int t = T - 1; t >= 0; --t) {
             CellBackArgs c{};
             c.Z = zat(l, t); c.Cs = act(Cs, l, t); c.Cprev = t > 0 ? act(Cs, l, t - 1) : nullptr;
@@ -485,14 +630,14 @@ int Trainer::step(int n, const float* means, const float* stds, const float* len
             hipLaunchKernelGGL(cell_backward_kernel, cell_grid, dim3(256), 0, s, c);
             TCK(hipGetLastError());
             if (t > 0) {      // dh_{t-1} += dz_t K[in:]^T
-                GemmArgs r = gemm_args(zat(l, t), GATES, 0, P + kernel_off(l) + (size_t)in * GATES, GATES, 1, DH, HID, n, HID, GATES, 0);
-                r.nb2 = 2; r.sA2 = sZD; r.sB2 = DIR_FLOATS; r.sC2 = sAct;
+                GemmArgs r = gemm_args(zat(l, t), GATES, 0, P + kernel_off(l, in0) + (size_t)in * GATES, GATES, 1, DH, HID, n, HID, GATES, 0);
+                r.nb2 = 2; r.sA2 = sZD; r.sB2 = DF; r.sC2 = sAct;
                 TCK(gemm(s, r));
             }
         }
         if (l > 0) {          // what the layer below receives, all steps at once: dy_t = dz_t K[0:in]^T
-            GemmArgs g = gemm_args(zat(l, 0), GATES, 0, P + kernel_off(l), GATES, 1, DX, HID, n, HID, GATES, 0);
-            g.nb1 = T; g.nb2 = 2; g.sA1 = sZt; g.sA2 = sZD; g.sB2 = DIR_FLOATS; g.sC1 = sAct; g.sC2 = (long long)T * sAct;
+            GemmArgs g = gemm_args(zat(l, 0), GATES, 0, P + kernel_off(l, in0), GATES, 1, DX, HID, n, HID, GATES, 0);
+            g.nb1 = T; g.nb2 = 2; g.sA1 = sZt; g.sA2 = sZD; g.sB2 = DF; g.sC1 = sAct; g.sC2 = (long long)T * sAct;
             TCK(gemm(s, g));
         }
     }
@@ -501,17 +646,17 @@ int Trainer::step(int n, const float* means, const float* stds, const float* len
     // ---- weight gradients: per cell one product per step into a slab, the slabs added in step order
     const long long slab_step = (long long)HID * GATES, slab_dir = (long long)T * slab_step;
     for (int l = 0; l < NLAYER; ++l) {
-        const int in = layer_in(l);
+        const int in = layer_in(l, in0);
         {   // dK[0:in] = sum_t X_t^T dz_t
-            GemmArgs g = l == 0 ? gemm_args(X0, 4, 1, zat(l, 0), GATES, 0, slab, GATES, in, GATES, n, 0)
+            GemmArgs g = l == 0 ? gemm_args(X0, ldx, 1, zat(l, 0), GATES, 0, slab, GATES, in, GATES, n, 0)
                                 : gemm_args(act(Y, l - 1, 0), HID, 1, zat(l, 0), GATES, 0, slab, GATES, in, GATES, n, 0);
             g.nb1 = T; g.nb2 = 2;
-            g.sA1 = l == 0 ? (long long)B * 4 : sAct; g.sA2 = l == 0 ? (long long)T * B * 4 : sActD;
+            g.sA1 = l == 0 ? (long long)B * ldx : sAct; g.sA2 = l == 0 ? (long long)T * B * ldx : sActD;
             g.sB1 = sZt; g.sB2 = sZD; g.sC1 = slab_step; g.sC2 = slab_dir;
             TCK(gemm(s, g));
             const long long count = (long long)in * GATES;
-            hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((count + 255) / 256), 2), dim3(256), 0, s, slab, G + kernel_off(l), count, T, slab_step,
-                               slab_dir, DIR_FLOATS);
+            hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((count + 255) / 256), 2), dim3(256), 0, s, slab, G + kernel_off(l, in0), count, T, slab_step,
+                               slab_dir, DF);
             TCK(hipGetLastError());
         }
         {   // dK[in:] = sum_{t >= 1} h_{t-1}^T dz_t
@@ -521,27 +666,45 @@ int Trainer::step(int n, const float* means, const float* stds, const float* len
                 g.nb1 = T - 1; g.nb2 = 2; g.sA1 = sAct; g.sA2 = sActD; g.sB1 = sZt; g.sB2 = sZD; g.sC1 = slab_step; g.sC2 = slab_dir;
                 TCK(gemm(s, g));
             }
-            hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((count + 255) / 256), 2), dim3(256), 0, s, slab, G + kernel_off(l) + (size_t)in * GATES,
-                               count, T - 1, slab_step, slab_dir, DIR_FLOATS);
+            hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((count + 255) / 256), 2), dim3(256), 0, s, slab, G + kernel_off(l, in0) + (size_t)in * GATES,
+                               count, T - 1, slab_step, slab_dir, DF);
             TCK(hipGetLastError());
         }
         // db = column sums of dz over steps and rows
         hipLaunchKernelGGL(bias_partial_kernel, dim3(GATES / 256, T, 2), dim3(256), 0, s, zat(l, 0), slab, sZD, sZt, n, T);
         TCK(hipGetLastError());
-        hipLaunchKernelGGL(reduce_slabs_kernel, dim3(GATES / 256, 2), dim3(256), 0, s, slab, G + bias_off(l), (long long)GATES, T, (long long)GATES,
-                           (long long)T * GATES, DIR_FLOATS);
+        hipLaunchKernelGGL(reduce_slabs_kernel, dim3(GATES / 256, 2), dim3(256), 0, s, slab, G + bias_off(l, in0), (long long)GATES, T, (long long)GATES,
+                           (long long)T * GATES, DF);
+        TCK(hipGetLastError());
+    }
+    if (base) {
+        // what the embedded inputs receive, both directions and all steps at once: DX0(d, t) = dz_0(d, t) K0[0:128]^T ...
+        GemmArgs g = gemm_args(zat(0, 0), GATES, 0, P + kernel_off(0, in0), GATES, 1, DX0, EMB, n, EMB, GATES, 0);
+        g.nb1 = T; g.nb2 = 2; g.sA1 = sZt; g.sA2 = sZD; g.sB2 = DF; g.sC1 = (long long)B * EMB; g.sC2 = (long long)T * B * EMB;
+        TCK(gemm(s, g));
+        // ... and their sum per code, in an order the codes alone decide (emb_count_kernel .. emb_reduce_kernel)
+        const int total = n * T, nblk = (total + EG_BLOCK - 1) / EG_BLOCK, chunks = (total + EG_CHUNK - 1) / EG_CHUNK + std::min(total, VOCAB);
+        int32_t* chunk0 = eg_run + VOCAB + 1;
+        hipLaunchKernelGGL(emb_count_kernel, dim3(nblk), dim3(EG_BLOCK), 0, s, d_kmer, eg_count, total);
+        TCK(hipGetLastError());
+        hipLaunchKernelGGL(emb_scan_kernel, dim3(1), dim3(VOCAB), 0, s, eg_count, eg_run, chunk0, eg_chunk_code, nblk);
+        TCK(hipGetLastError());
+        hipLaunchKernelGGL(emb_scatter_kernel, dim3(nblk), dim3(EG_BLOCK), 0, s, d_kmer, eg_count, eg_run, eg_entry, total);
+        TCK(hipGetLastError());
+        hipLaunchKernelGGL(emb_partial_kernel, dim3(chunks), dim3(EMB), 0, s, DX0, eg_entry, eg_run, chunk0, eg_chunk_code, eg_partial, T, B);
+        TCK(hipGetLastError());
+        hipLaunchKernelGGL(emb_reduce_kernel, dim3(VOCAB), dim3(EMB), 0, s, eg_partial, chunk0, G + emb_off(in0));
         TCK(hipGetLastError());
     }
     TCK(hipEventRecord(ev[4], s));
 
-    // ---- Adam on all 14 tensors
+    // ---- Adam on every tensor of the block
     const float lr_t = adam_step_size(lr, cfg.beta1, cfg.beta2, step_count + 1);
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((PARAM_FLOATS + 255) / 256)), dim3(256), 0, s, P, G, M, V, (long long)PARAM_FLOATS, lr_t, cfg.beta1,
+    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((PF + 255) / 256)), dim3(256), 0, s, P, G, M, V, (long long)PF, lr_t, cfg.beta1,
                        cfg.beta2, cfg.epsilon);
     TCK(hipGetLastError());
     TCK(hipEventRecord(ev[5], s));
 
-    float* pout = pin + (size_t)3 * B * T + B;
     TCK(hipMemcpyAsync(pout, d_loss, sizeof(float), hipMemcpyDeviceToHost, s));
     TCK(hipMemcpyAsync(pout + 1, d_pred, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     TCK(hipStreamSynchronize(s));
@@ -563,16 +726,16 @@ int Trainer::step(int n, const float* means, const float* stds, const float* len
 int Trainer::read_params(float* out, std::string* err)
 {
     TCK(hipSetDevice(device));
-    TCK(hipMemcpy(out, P, PARAM_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
+    TCK(hipMemcpy(out, P, param_floats(in0) * sizeof(float), hipMemcpyDeviceToHost));
     return DS_OK;
 }
 
 int64_t Trainer::get(const float* block, int idx, float* out, int64_t cap, std::string* err)
 {
-    const int64_t count = tensor_floats(idx);
+    const int64_t count = tensor_floats(idx, in0);
     if (cap < count) { if (err) *err = "buffer too small for " + tensor_name(idx); return DS_ERR_INVALID; }
     TCK(hipSetDevice(device));
-    TCK(hipMemcpy(out, block + tensor_off(idx), count * sizeof(float), hipMemcpyDeviceToHost));
+    TCK(hipMemcpy(out, block + tensor_off(idx, in0), count * sizeof(float), hipMemcpyDeviceToHost));
     return count;
 }
 

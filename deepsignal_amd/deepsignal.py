@@ -73,6 +73,11 @@ def main_denoise(args):
     return run(args)
 
 
+def main_train(args):
+    from .train_model import run
+    return run(args)
+
+
 def _names_freq_file(argv) -> bool:
     """Does the command line give call_mods' --freq_file (spelled out, abbreviated as argparse allows, or with '=')?"""
     for a in argv:
@@ -225,6 +230,13 @@ def build_parser(freq_file_given=True):
     denoise_arguments(d)
     d.set_defaults(func=main_denoise)
     parser.denoise_parser = d
+    # `train`: fit the BiLSTM variants (--is_cnn no) on the GPU and save TF checkpoints (the reference's flags and defaults,
+    # train_model.py:288-346, plus --seed / --device)
+    from .train_model import SCOPE_NOTE, add_arguments as train_arguments
+    t = sub.add_parser("train", description="train a model, need two independent datasets for training and validating. " + SCOPE_NOTE)
+    train_arguments(t)
+    t.set_defaults(func=main_train)
+    parser.train_parser = t
     return parser
 
 
@@ -272,6 +284,10 @@ def main(argv=None):
     if args.module == "denoise":
         from .denoise import check_arguments
         check_arguments(parser.denoise_parser, args)
+        return args.func(args)
+    if args.module == "train":
+        from .train_model import check_arguments
+        check_arguments(parser.train_parser, args)
         return args.func(args)
     if args.module == "call_freq":
         return args.func(args)       # the script's own main: it validates the forwarded flags and returns the exit status

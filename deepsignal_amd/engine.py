@@ -58,6 +58,8 @@ EXPORTED_SYMBOLS = (
     # training step of the RNN-only model (denoise)
     "ds_train_begin", "ds_train_set_tensor", "ds_train_step", "ds_train_sync_weights", "ds_train_get_tensor", "ds_train_get_grad",
     "ds_train_get_mask", "ds_train_end", "ds_train_mask_reference", "ds_get_train_times",
+    # ... with the embedding trained too, and the evaluation pass (train)
+    "ds_train_begin_base", "ds_train_step_base", "ds_train_eval",
 )
 
 
@@ -715,6 +717,9 @@ def load_library() -> ctypes.CDLL:
     lib.ds_train_set_tensor.argtypes = [vp, ctypes.c_char_p, vp, i64]
     lib.ds_train_step.argtypes = [vp, i32, vp, vp, vp, vp, ctypes.c_float, ctypes.POINTER(ctypes.c_float), vp]
     lib.ds_train_sync_weights.argtypes = [vp]
+    lib.ds_train_begin_base.argtypes = [vp, ctypes.POINTER(DsTrainConfig)]
+    lib.ds_train_step_base.argtypes = [vp, i32, vp, vp, vp, vp, vp, ctypes.c_float, ctypes.POINTER(ctypes.c_float), vp]
+    lib.ds_train_eval.argtypes = [vp, i32, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_float), vp, vp]
     for fn in (lib.ds_train_get_tensor, lib.ds_train_get_grad, lib.ds_train_get_mask):
         fn.argtypes = [vp, ctypes.c_char_p, vp, i64]
         fn.restype = i64
@@ -746,10 +751,11 @@ def train_mask_reference(seed: int, step: int, stream: str, n: int, kmer_len: in
     return out
 
 
-def trainable_names() -> List[str]:
-    """TF names of the 14 tensors the RNN-only model trains, in the order of `spec.tensor_table`."""
+def trainable_names(is_base: bool = False) -> List[str]:
+    """TF names of the tensors the RNN-only model trains, in the order of `spec.tensor_table`: 14, and `modelembedding` before
+    them with is_base."""
     from . import spec
-    return [name for name, _ in spec.tensor_table(17, 360, 2, is_cnn=False, is_rnn=True, is_base=False)]
+    return [name for name, _ in spec.tensor_table(17, 360, 2, is_cnn=False, is_rnn=True, is_base=is_base)]
 
 
 class Engine:
@@ -792,6 +798,7 @@ class Engine:
         self._lib.ds_num_slots.argtypes = [ctypes.c_void_p]
         self._slots = int(self._lib.ds_num_slots(self._h))
         self.device, self.max_batch = device, max_batch
+        self.is_base = bool(is_base)
         self._fine: Optional["Engine"] = None      # set_recheck: the attached engine stays referenced here
         self._owns_fine = False
 
@@ -850,18 +857,21 @@ class Engine:
 
     # -- training step of the RNN-only model (denoise.py:97-110) -------------------------------
     def train_begin(self, keep_prob: float = 0.5, pos_weight: float = 1.0, seed: int = 0, beta1: float = 0.0, beta2: float = 0.0,
-                    epsilon: float = 0.0, weights: Optional[Dict[str, np.ndarray]] = None) -> None:
+                    epsilon: float = 0.0, weights: Optional[Dict[str, np.ndarray]] = None, base: bool = False) -> None:
         """Start (or start over) from the loaded weights, or from `weights` installed in their place: fp32 master
-        parameters, zero Adam moments, step 0. beta1 / beta2 / epsilon 0 = TF's defaults."""
+        parameters, zero Adam moments, step 0. beta1 / beta2 / epsilon 0 = TF's defaults. base=True opens the run through
+        ds_train_begin_base, which also takes an is_base handle (the embedding is trained; train_step then needs `kmer`)."""
         if weights is not None:
             for name, arr in weights.items():
                 a = np.ascontiguousarray(arr, dtype=np.float32)
                 self._check(self._lib.ds_train_set_tensor(self._h, name.encode(), a.ctypes.data, a.size), "ds_train_set_tensor")
         cfg = DsTrainConfig(keep_prob, pos_weight, beta1, beta2, epsilon, seed & 0xFFFFFFFFFFFFFFFF)
-        self._check(self._lib.ds_train_begin(self._h, ctypes.byref(cfg)), "ds_train_begin")
+        if base:
+            self._check(self._lib.ds_train_begin_base(self._h, ctypes.byref(cfg)), "ds_train_begin_base")
+        else:
+            self._check(self._lib.ds_train_begin(self._h, ctypes.byref(cfg)), "ds_train_begin")
 
-    def train_step(self, means, stds, sanums, labels, lr: float) -> Tuple[float, np.ndarray]:
-        """One step on these rows: (cost, prediction int32[n])."""
+    def _train_arrays(self, means, stds, sanums, labels, kmer):
         means = np.ascontiguousarray(means, dtype=np.float32)
         stds = np.ascontiguousarray(stds, dtype=np.float32)
         sanums = np.ascontiguousarray(sanums, dtype=np.float32)
@@ -869,19 +879,46 @@ class Engine:
         n = int(labels.shape[0]) if labels.ndim == 1 else -1
         if means.ndim != 2 or means.shape != (n, self.kmer_len) or stds.shape != means.shape or sanums.shape != means.shape:
             raise ValueError("training arrays have inconsistent shapes")
+        if kmer is not None:
+            kmer = np.ascontiguousarray(kmer, dtype=np.int32)
+            if kmer.shape != means.shape:
+                raise ValueError("training arrays have inconsistent shapes")
+        return n, means, stds, sanums, labels, kmer
+
+    def train_step(self, means, stds, sanums, labels, lr: float, kmer=None) -> Tuple[float, np.ndarray]:
+        """One step on these rows: (cost, prediction int32[n]). `kmer` int32[n, kmer_len]: the codes, which a run that trains
+        the embedding needs (without them it is refused); given, the step goes through ds_train_step_base."""
+        n, means, stds, sanums, labels, kmer = self._train_arrays(means, stds, sanums, labels, kmer)
         loss = ctypes.c_float()
         pred = np.empty((n,), np.int32)
-        rc = self._lib.ds_train_step(self._h, n, means.ctypes.data, stds.ctypes.data, sanums.ctypes.data, labels.ctypes.data,
-                                     lr, ctypes.byref(loss), pred.ctypes.data)
-        self._check(rc, "ds_train_step")
+        if kmer is not None:
+            rc = self._lib.ds_train_step_base(self._h, n, kmer.ctypes.data, means.ctypes.data, stds.ctypes.data,
+                                              sanums.ctypes.data, labels.ctypes.data, lr, ctypes.byref(loss), pred.ctypes.data)
+            self._check(rc, "ds_train_step_base")
+        else:
+            rc = self._lib.ds_train_step(self._h, n, means.ctypes.data, stds.ctypes.data, sanums.ctypes.data, labels.ctypes.data,
+                                         lr, ctypes.byref(loss), pred.ctypes.data)
+            self._check(rc, "ds_train_step")
         return float(loss.value), pred
+
+    def train_eval(self, means, stds, sanums, labels, kmer=None) -> Tuple[float, np.ndarray, np.ndarray]:
+        """The training forward on the current parameters with keep_prob 1 and nothing changed: (cost, prediction int32[n],
+        logits float32[n, 2])."""
+        n, means, stds, sanums, labels, kmer = self._train_arrays(means, stds, sanums, labels, kmer)
+        loss = ctypes.c_float()
+        pred = np.empty((n,), np.int32)
+        logits = np.empty((n, 2), np.float32)
+        rc = self._lib.ds_train_eval(self._h, n, None if kmer is None else kmer.ctypes.data, means.ctypes.data, stds.ctypes.data,
+                                     sanums.ctypes.data, labels.ctypes.data, ctypes.byref(loss), pred.ctypes.data, logits.ctypes.data)
+        self._check(rc, "ds_train_eval")
+        return float(loss.value), pred, logits
 
     def train_sync_weights(self) -> None:
         self._check(self._lib.ds_train_sync_weights(self._h), "ds_train_sync_weights")
 
     def _train_tensor(self, fn, what: str, name: str) -> np.ndarray:
         from . import spec
-        shapes = dict(spec.tensor_table(self.kmer_len, self.signal_len, self.class_num, is_cnn=False, is_rnn=True, is_base=False))
+        shapes = dict(spec.tensor_table(self.kmer_len, self.signal_len, self.class_num, is_cnn=False, is_rnn=True, is_base=self.is_base))
         if name not in shapes:
             raise KeyError(name)
         out = np.empty(shapes[name], np.float32)
@@ -898,10 +935,10 @@ class Engine:
         return self._train_tensor(self._lib.ds_train_get_grad, "ds_train_get_grad", name)
 
     def train_tensors(self) -> Dict[str, np.ndarray]:
-        return {name: self.train_tensor(name) for name in trainable_names()}
+        return {name: self.train_tensor(name) for name in trainable_names(self.is_base)}
 
     def train_grads(self) -> Dict[str, np.ndarray]:
-        return {name: self.train_grad(name) for name in trainable_names()}
+        return {name: self.train_grad(name) for name in trainable_names(self.is_base)}
 
     def train_mask(self, stream: str, n: int) -> np.ndarray:
         out = np.empty(mask_shape(stream, n, self.kmer_len), np.uint8)

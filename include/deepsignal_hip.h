@@ -713,6 +713,31 @@ int ds_train_mask_reference(uint64_t seed, int64_t step, const char *stream, int
                             uint8_t *out);
 int ds_get_train_times(ds_handle *h, int32_t reset, int64_t *steps, double *ms);
 
+/* ---- ... with the embedding trained too (`train`; csrc/ds_train.hip) -----------------------------------------------------
+ * The same run for both RNN-only variants: is_cnn 0, is_rnn 1, class_num 2, DS_PRECISION_FP32 and is_base 0 or 1. With is_base 1
+ * layer 0 reads [embedding row of the base's code (128) | mean, std, length] (model.py:61-69), and modelembedding [1024, 128] is a
+ * 15th trained tensor: ds_train_set_tensor / ds_train_get_tensor / ds_train_get_grad accept its name on such a handle, and
+ * ds_train_sync_weights hands it to the inference plan with the rest. Codes follow CODES above: below 0 acts as 0, above 1023 as
+ * 1023, in the lookup and in the row the gradient lands in; no value reads or writes outside the table. The embedding's gradient
+ * is the sum of its rows' input gradients in ascending (row, base) order per code, cut into chunks of 64 that are added in chunk
+ * order: no floating-point atomics, the same bits on every run; rows of codes that do not occur get +0.0, and Adam then runs over
+ * the whole table as over every other tensor (their moments decay, as TF's sparse Adam update does it too).
+ *
+ * ds_train_begin_base: ds_train_begin for such a handle; every other refusal is ds_train_begin's. ds_train_begin itself keeps
+ *   refusing is_base 1 (DS_ERR_UNSUPPORTED).
+ * ds_train_step_base: ds_train_step with kmer int32[n, kmer_len]. On an is_base 0 run kmer is ignored and may be NULL, and the
+ *   step is ds_train_step's, bit for bit. On an is_base 1 run ds_train_step, which has no codes to give, returns DS_ERR_INVALID.
+ * ds_train_eval: model.cost_pw and model.prediction under training = False, keep_prob = 1 (train_model.py:200-210): the training
+ *   forward on the current master parameters with every mask kept, the run's pos_weight choosing loss and prediction rule as in a
+ *   step. logits float[n, 2] may be NULL. It changes nothing: no parameter, moment or gradient bit, not the step counter (the
+ *   next step's masks are what they would have been), not what ds_train_get_grad / ds_train_get_mask return. Not timed.
+ * In ds_get_train_times the layer-0 gather counts as forward sweep, the embedding's gradient as weight gradients. */
+int ds_train_begin_base(ds_handle *h, const ds_train_config *cfg);
+int ds_train_step_base(ds_handle *h, int32_t n, const int32_t *kmer, const float *means, const float *stds, const float *sanums,
+                       const int32_t *labels, float lr, float *loss, int32_t *pred);
+int ds_train_eval(ds_handle *h, int32_t n, const int32_t *kmer, const float *means, const float *stds, const float *sanums,
+                  const int32_t *labels, float *loss, int32_t *pred, float *logits);
+
 /* Use a captured hipGraph for the forward (default on). */
 int ds_set_graph(ds_handle *h, int32_t enable);
 

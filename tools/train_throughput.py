@@ -3,11 +3,12 @@ samples/s from wall time, device milliseconds per phase from ds_get_train_times,
 step's algorithmic FLOPs. The only baseline there is: the float32 torch statement (tests/train_statement.py) on the usable CPU
 cores. Writes profiles/train_throughput.json.
 
-    python tools/train_throughput.py [--steps 30] [--warmup 5] [--cpu_steps 2] [--out profiles/train_throughput.json]
+    python tools/train_throughput.py [--steps 30] [--warmup 5] [--cpu_steps 2] [--is_base no] [--out profiles/train_throughput.json]
     python tools/train_throughput.py --parity [--out profiles/train_parity.json]
 
 --parity writes the distances tests/test_gpu_train_grad.py asserts on (GPU and float32 statement against the float64 statement,
-per case and tensor) instead."""
+per case and tensor) instead. --is_base yes times the step with the embedding trained (ds_train_step_base, codes uniform over
+A, C, G, T); the default no is the step denoise runs, through ds_train_step."""
 import argparse
 import json
 import os
@@ -23,9 +24,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 FP32_MATRIX_PEAK = 157.3e12      # MI355X, v_mfma_f32_32x32x2_f32
 
 
-def step_flops(n, T):
+def step_flops(n, T, in0=3):
     """Algorithmic FLOPs of one step: the forward's matrix products, and twice that for the backward (d[x | h] and dK)."""
-    rows = (3 + 256) + 2 * (256 + 256)
+    rows = (in0 + 256) + 2 * (256 + 256)
     fwd = 2 * T * n * 2 * rows * 1024 + 2 * n * 512 * 512 + 2 * n * 512 * 2
     return fwd, 2 * fwd
 
@@ -45,24 +46,28 @@ def throughput(a):
     from deepsignal_amd import weights
     from deepsignal_amd.engine import Engine
     n, T = a.batch, a.kmer_len
-    w = weights.random_weights(seed=7, is_cnn=False, is_base=False, kmer_len=T)
+    base = a.is_base == "yes"
+    if base:
+        import train_statement_base as ts
+    w = weights.random_weights(seed=7, is_cnn=False, is_base=base, kmer_len=T)
     feats = ts.train_features(n, T, seed=1)
     labels = np.random.default_rng(2).integers(0, 2, n).astype(np.int32)
-    eng = Engine(kmer_len=T, max_batch=n, is_cnn=False, is_base=False, device=a.device)
+    eng = Engine(kmer_len=T, max_batch=n, is_cnn=False, is_base=base, device=a.device)
     eng.load_weights(w)
-    eng.train_begin(keep_prob=a.keep_prob, seed=3)
+    eng.train_begin(keep_prob=a.keep_prob, seed=3, base=base)
+    kmer = feats["kmer"] if base else None
     for _ in range(a.warmup):
-        eng.train_step(feats["means"], feats["stds"], feats["sanums"], labels, 1e-3)
+        eng.train_step(feats["means"], feats["stds"], feats["sanums"], labels, 1e-3, kmer=kmer)
     eng.train_times(reset=True)
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        loss, _ = eng.train_step(feats["means"], feats["stds"], feats["sanums"], labels, 1e-3)
+        loss, _ = eng.train_step(feats["means"], feats["stds"], feats["sanums"], labels, 1e-3, kmer=kmer)
     wall = time.perf_counter() - t0
     times = eng.train_times()
     eng.close()
-    fwd, bwd = step_flops(n, T)
+    fwd, bwd = step_flops(n, T, 131 if base else 3)
     device_ms = sum(times["ms"].values()) / times["steps"]
-    out = {"batch": n, "kmer_len": T, "keep_prob": a.keep_prob, "steps": a.steps, "warmup": a.warmup, "last_loss": loss,
+    out = {"is_base": a.is_base, "batch": n, "kmer_len": T, "keep_prob": a.keep_prob, "steps": a.steps, "warmup": a.warmup, "last_loss": loss,
            "steps_per_s": a.steps / wall, "samples_per_s": a.steps * n / wall, "wall_ms_per_step": 1e3 * wall / a.steps,
            "device_ms_per_step": device_ms, "device_ms_per_phase": {k: v / times["steps"] for k, v in times["ms"].items()},
            "gflop_per_step": {"forward": fwd / 1e9, "backward": bwd / 1e9},
@@ -75,7 +80,7 @@ def throughput(a):
         for _ in range(a.cpu_steps):
             ts.step(w, feats, labels, None, 1.0, 1.0, torch.float32)
         cpu = (time.perf_counter() - t0) / a.cpu_steps
-        out["cpu_statement"] = {"what": "tests/train_statement.py, float32, forward + autograd backward (no optimiser)", "cores": cores,
+        out["cpu_statement"] = {"what": "tests/%s.py, float32" % ts.__name__ + ", forward + autograd backward (no optimiser)", "cores": cores,
                                 "s_per_step": cpu, "samples_per_s": n / cpu}
     return out
 
@@ -112,6 +117,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--cpu_steps", type=int, default=2, help="steps of the CPU statement to time (0: skip)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--is_base", default="no", choices=["yes", "no"], help="yes: the embedding is trained too (default no: denoise's step)")
     ap.add_argument("--parity", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
