@@ -15,11 +15,12 @@ from __future__ import annotations
 
 import argparse
 import gzip
-import io
-import mmap
 import os
 import sys
 from typing import Dict, Iterable, List, Tuple
+
+from . import table_route as tr
+from .table_route import _CpuRoute      # noqa: F401 -- the name call_modifications.py and the tests catch it under
 
 
 class SiteStats:
@@ -63,55 +64,28 @@ def calculate_mods_frequency(mods_files: Iterable[str], prob_cf: float = 0.0) ->
     return stats
 
 
-class _CpuRoute(Exception):
-    """--on gpu cannot take this input as it is; the message says why and the cpu route runs instead (never a truncated table)."""
-
-
-class _CallFile:
+class _CallFile(tr.RowFile):
     """One input file of the gpu route: its bytes (memory map, or the gunzipped text), row spans, chromosome ids, flags."""
 
     def __init__(self, path: str, chrom_id):
         from . import engine as eng
         import numpy as np
-        self.keep = None
-        if path.endswith(".gz"):
-            with gzip.open(path, "rb") as f:
-                self.data = np.frombuffer(f.read(), np.uint8)
-        else:
-            with open(path, "rb") as f:
-                size = os.fstat(f.fileno()).st_size
-                if size:
-                    self.keep = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
-                    self.data = np.frombuffer(self.keep, np.uint8)
-                else:
-                    self.data = np.zeros(0, np.uint8)
-        self.begin, self.end, local, self.flags, names = eng.freq_locate(self.data)
+        tr.RowFile.__init__(self, path, gunzip=True)
+        begin, end, local, flags, names = eng.freq_locate(self.data)
+        self.set_rows(begin, end, flags)
         # the file's ids -> the run's (names of unflagged rows are ASCII)
         to_run = np.array([chrom_id(n.decode("ascii")) for n in names] + [-1], np.int32)
         self.chrom = to_run[local]               # -1 (a flagged row) picks the -1 at the end
-        self.n = int(self.begin.size)
-
-    def row_bytes(self, i: int) -> bytes:
-        return self.data[int(self.begin[i]):int(self.end[i])].tobytes()
 
 
-def _python_row(raw: bytes) -> List[str]:
-    """A row's bytes -> the `w` of the cpu route: decoded and split into lines by the very text layer open(path, "r") uses, then
-    line.strip().split("\t"). A row that holds a line break of its own (a bare carriage return) is more than one line there."""
-    lines = list(io.TextIOWrapper(io.BytesIO(raw + b"\n")))
-    if len(lines) != 1:
-        raise _CpuRoute("a row holds a bare carriage return, which ends a line in Python's text mode")
-    return lines[0].strip().split("\t")
-
-
-def _host_row_values(w: List[str], prob_cf: float, chrom_id):
+def _host_row_values(w: List[str], prob_cf: float, chrom_id, used_w: dict, row: int):
     """One row `w` the device left to Python, through the expressions of the cpu route -> what ds_freq_accumulate takes for it:
-    (chromosome id, pos, prob_0, prob_1, met, used). `used`: the row passes the threshold (the device makes the same comparison on
-    these doubles) and its key has been looked up -- chrom_id(name), or chrom_id((name, pos)) with pos 0 for a position outside
-    the key: a site under an id of its own. Shared by `call_freq --on gpu` and `call_mods --freq_file`."""
+    (chromosome id, pos, prob_0, prob_1, met). A row that passes the threshold (the device makes the same comparison on these
+    doubles) is used: its key is looked up -- chrom_id(name), or chrom_id((name, pos)) with pos 0 for a position outside the key: a
+    site under an id of its own -- and used_w[row] = w. Shared by `call_freq --on gpu` and `call_mods --freq_file`."""
     from . import engine as eng
     prob_0, prob_1 = float(w[6]), float(w[7])
-    cid, pos, met, used = 0, 0, 0, False
+    cid, pos, met = 0, 0, 0
     if not abs(prob_0 - prob_1) < prob_cf:
         name, pos = w[0], int(w[1])
         if 0 <= pos < eng.FREQ_POS_LIMIT:
@@ -119,8 +93,8 @@ def _host_row_values(w: List[str], prob_cf: float, chrom_id):
         else:
             cid, pos = chrom_id((name, pos)), 0
         met = 1 if int(w[8]) == 1 else 0
-        used = True
-    return cid, pos, prob_0, prob_1, met, used
+        used_w[row] = w
+    return cid, pos, prob_0, prob_1, met
 
 
 def _chrom_table():
@@ -162,9 +136,7 @@ class FreqStream:
     make_engine: what provides freq_begin_stream .. freq_end (default: an Engine of its own on `device`, never the forward's)."""
 
     def __init__(self, prob_cf: float = 0.0, device: int = 0, batch_rows: int = 1 << 16, initial_slots: int = 1 << 16, make_engine=None):
-        from . import engine as eng
-        if not 1 <= batch_rows <= eng.FREQ_MAX_BATCH:
-            raise ValueError("batch_rows must be in [1, 2^24]")
+        tr.check_batch_rows(batch_rows)
         if prob_cf != prob_cf:
             raise ValueError("prob_cf must not be NaN")
         self.prob_cf, self.batch_rows = prob_cf, batch_rows
@@ -173,13 +145,11 @@ class FreqStream:
         self._buf, self._nbuf = [], 0                        # rows pushed, not yet on the device
         self.first: Dict[int, Tuple[str, int, str]] = {}     # a site's first used row -> its strand, pos_in_strand, k-mer
         self.info: dict = {}
-        # a handle of its own, the smallest there is (see calculate_mods_frequency_gpu): the forward's handle is busy on another thread
-        self.e = make_engine() if make_engine is not None else eng.Engine(device=device, max_batch=64, slots=1)
+        # a handle of its own, the smallest there is: the forward's handle is busy on another thread
+        self.e = tr.open_engine(make_engine, device)
         try:
-            self.e.freq_begin_stream(initial_slots, batch_rows, prob_cf)
-        except eng.FreqNoMemory as exc:
-            self.close()
-            raise _CpuRoute("the site table does not fit the device (%s)" % exc)
+            with tr.fits("the site table does not fit the device"):
+                self.e.freq_begin_stream(initial_slots, batch_rows, prob_cf)
         except BaseException:
             self.close()
             raise
@@ -224,20 +194,16 @@ class FreqStream:
             raise _CpuRoute("more than 2^30 rows")
         local, pos, flags, names = eng.freq_keys(info, off)
         to_run = np.array([self.chrom_id(nm.decode("ascii")) for nm in names] + [-1], np.int32)
-        try:
+        with tr.fits("the site table cannot grow on the device"):
             status = self.e.freq_push(to_run[local], pos, act, pred)
-        except eng.FreqNoMemory as exc:
-            raise _CpuRoute("the site table cannot grow on the device (%s)" % exc)
         host_w: Dict[int, List[str]] = {}
-        o_row, o_chrom, o_pos, o_p0, o_p1, o_met = [], [], [], [], [], []
-        for i in np.flatnonzero(status != eng.TEXT_ROW_OK).tolist():
+
+        def host_row(i: int, _status: int):
             row = fastio.format_rows(info, off[i:i + 2], act[i:i + 1], pred[i:i + 1], kmer[i:i + 1])
-            w = _python_row(row[:-1])
-            cid, q, prob_0, prob_1, met, used = _host_row_values(w, self.prob_cf, self.chrom_id)
-            if used:
-                host_w[i] = w
-            o_row.append(i); o_chrom.append(cid); o_pos.append(q); o_p0.append(prob_0); o_p1.append(prob_1); o_met.append(met)
-        opened = self.e.freq_accumulate(o_row, o_chrom, o_pos, o_p0, o_p1, o_met)
+            return _host_row_values(tr.python_row(row[:-1]), self.prob_cf, self.chrom_id, host_w, i)
+
+        o_row, values = tr.host_values(status, host_row)
+        opened = self.e.freq_accumulate(o_row, *tr.columns(values, 5))
         self.host_rows += len(o_row)
         # the rows that open a site: their strand, pos_in_strand and k-mer (codes -> letters as ds_format_rows writes them)
         idx = np.flatnonzero(opened)
@@ -259,11 +225,9 @@ class FreqStream:
         """The sites in the order of their first used row, and the "calls used" line."""
         import numpy as np
         self._flush()
-        res = self.e.freq_result()
-        self.info.update(self.e.freq_times())
-        if hasattr(self.e, "freq_stream_times"):
-            self.info.update(self.e.freq_stream_times())
-        self.e.freq_end()
+        stream_times = self.e.freq_stream_times() if hasattr(self.e, "freq_stream_times") else {}
+        res, times = tr.finish(self.e, "freq")
+        self.info.update(times, **stream_times)
         if res["rows"] != self.rows:
             raise RuntimeError("freq stream: %d rows accumulated, %d pushed" % (res["rows"], self.rows))
         stats: Dict[SiteKey, SiteStats] = {}
@@ -294,8 +258,7 @@ def calculate_mods_frequency_gpu(mods_files: Iterable[str], prob_cf: float = 0.0
     import numpy as np
     from . import engine as eng
     mods_files = list(mods_files)
-    if not 1 <= batch_rows <= eng.FREQ_MAX_BATCH:
-        raise ValueError("batch_rows must be in [1, 2^24]")
+    tr.check_batch_rows(batch_rows)
     if prob_cf != prob_cf:
         raise ValueError("prob_cf must not be NaN")
     names, chrom_id = _chrom_table()
@@ -320,43 +283,25 @@ def calculate_mods_frequency_gpu(mods_files: Iterable[str], prob_cf: float = 0.0
     times = {}
     host_rows = 0
     if total:
-        # the ds_freq_* calls need no weights, but they hang off a handle, and a handle carries the forward's workspace and streams:
-        # the smallest one (64 sites, one slot) keeps that cost to a few MB, as `extract --extract_on gpu` does
-        e = make_engine() if make_engine is not None else eng.Engine(device=device, max_batch=64, slots=1)
-        try:
-            try:
+        with tr.small_engine(make_engine, device) as e:
+            with tr.fits("the site table of %d rows does not fit the device" % total):
                 e.freq_begin(total, min(batch_rows, max(total, 1)), prob_cf)
-            except eng.FreqNoMemory as exc:
-                raise _CpuRoute("the site table of %d rows does not fit the device (%s)" % (total, exc))
             base = 0
             for f in files:
                 if not isinstance(f, _CallFile):
                     raise f
-                for s in range(0, f.n, batch_rows):
-                    t = min(f.n, s + batch_rows)
-                    status = e.freq_parse(f.data, f.begin[s:t], f.end[s:t], f.chrom[s:t], f.flags[s:t])
-                    o_row, o_chrom, o_pos, o_p0, o_p1, o_met = [], [], [], [], [], []
-                    for i in np.flatnonzero(status != eng.TEXT_ROW_OK).tolist():
-                        w = _python_row(f.row_bytes(s + i))
-                        cid, pos, prob_0, prob_1, met, is_used = _host_row_values(w, prob_cf, chrom_id)
-                        if is_used:
-                            host_w[base + s + i] = w
-                        o_row.append(i); o_chrom.append(cid); o_pos.append(pos); o_p0.append(prob_0); o_p1.append(prob_1); o_met.append(met)
-                    e.freq_accumulate(o_row, o_chrom, o_pos, o_p0, o_p1, o_met)
-                    host_rows += len(o_row)
+                host_rows += tr.walk(
+                    f.n, batch_rows, lambda s, t: e.freq_parse(f.data, f.begin[s:t], f.end[s:t], f.chrom[s:t], f.flags[s:t]),
+                    lambda row, _status: _host_row_values(tr.python_row(f.row_bytes(row)), prob_cf, chrom_id, host_w, base + row),
+                    lambda s, t, rows, values: e.freq_accumulate(rows, *tr.columns(values, 5)))
                 base += f.n
-            res = e.freq_result()
-            times = e.freq_times()
-            e.freq_end()
-        finally:
-            e.close()
+            res, times = tr.finish(e, "freq")
     else:
         for f in files:
             if not isinstance(f, _CallFile):
                 raise f
     if res is not None:
-        if res["rows"] != total:
-            raise RuntimeError("gpu route: %d rows accumulated, %d located" % (res["rows"], total))
+        tr.check_rows(res, total)
         bases = np.cumsum([0] + [f.n for f in files])
         for k in np.argsort(res["first_row"], kind="stable").tolist():
             row = int(res["first_row"][k])

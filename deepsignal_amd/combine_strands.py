@@ -13,12 +13,12 @@ not parse go through the expressions of the cpu route right here. File and stdou
 from __future__ import annotations
 
 import argparse
-import mmap
 import os
 import sys
 from typing import Callable, Dict, List, Optional, Tuple
 
-from .call_modification_frequency import _CpuRoute, _python_row
+from . import table_route as tr
+from .table_route import _CpuRoute
 
 MOTIF = "CG"
 MSG_GENOME = "start to get genome reference info.."
@@ -146,16 +146,6 @@ def write_rows(rows: list, out_fp: str) -> None:
 
 
 # ---- the gpu route ----------------------------------------------------------------------------------------------------------
-def _map_file(path: str):
-    """(keep-alive object, uint8 array) of a file's bytes: a read-only memory map, or an empty array."""
-    import numpy as np
-    with open(path, "rb") as f:
-        if os.fstat(f.fileno()).st_size:
-            keep = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
-            return keep, np.frombuffer(keep, np.uint8)
-    return None, np.zeros(0, np.uint8)
-
-
 class _Genome:
     """The host's view of a FASTA for the gpu route: which records count, their lines, and the bases of a few positions (the rows
     the device leaves to Python). Nothing here looks at every base: that is the device's part."""
@@ -163,7 +153,7 @@ class _Genome:
     def __init__(self, ref_fp: str):
         import numpy as np
         from . import engine as eng
-        self.keep, self.data = _map_file(ref_fp)
+        self.keep, self.data = tr.map_file(ref_fp)
         loc = eng.fasta_locate(self.data)
         if loc["flags"] & eng.FASTA_NON_ASCII:
             raise _CpuRoute("the FASTA holds a byte >= 0x80, which Python's text layer may read as another character")
@@ -249,20 +239,17 @@ class _Genome:
             s = t
 
 
-class _Rows:
+class _Rows(tr.RowFile):
     """The rows of the input table for the gpu route: bytes, spans, flags, and per row the record its column 0 names (-1: none)."""
 
     def __init__(self, report_fp: str, rec_id: Dict[str, int]):
         import numpy as np
         from . import engine as eng
-        self.keep, self.data = _map_file(report_fp)
-        self.begin, self.end, local, self.flags, names = eng.freq_locate(self.data)
+        tr.RowFile.__init__(self, report_fp)
+        begin, end, local, flags, names = eng.freq_locate(self.data)
+        self.set_rows(begin, end, flags)
         to_rec = np.array([rec_id.get(n.decode("ascii"), -1) for n in names] + [-1], np.int32)
         self.chrom = to_rec[local]               # -1 (a flagged row) picks the -1 at the end
-        self.n = int(self.begin.size)
-
-    def row_bytes(self, i: int) -> bytes:
-        return self.data[int(self.begin[i]):int(self.end[i])].tobytes()
 
 
 def combine_strands_gpu(report_fp: str, ref_fp: str, contig: str = "", device: int = 0, batch_rows: int = 1 << 20,
@@ -272,15 +259,13 @@ def combine_strands_gpu(report_fp: str, ref_fp: str, contig: str = "", device: i
     rows and the device times. Raises what the cpu route raises on a malformed row. _CpuRoute: the input cannot be taken as it
     is; the message says why. make_engine: what provides combine_begin .. combine_end (default: an Engine on `device`; the tests put
     the CPU checkers behind it)."""
-    import numpy as np
     from . import engine as eng
-    if not 1 <= batch_rows <= eng.FREQ_MAX_BATCH:
-        raise ValueError("batch_rows must be in [1, 2^24]")
+    tr.check_batch_rows(batch_rows)
     if not 1 <= chunk_bytes <= eng.COMBINE_MAX_CHUNK:
         raise ValueError("chunk_bytes must be in [1, 2^30]")
     out: List[str] = []          # the stdout so far
     try:
-        rows = _combine_gpu(report_fp, ref_fp, contig, device, batch_rows, chunk_bytes, info, make_engine, out, np, eng)
+        rows = _combine_gpu(report_fp, ref_fp, contig, device, batch_rows, chunk_bytes, info, make_engine, out, eng)
     except _CpuRoute:
         raise
     except BaseException:
@@ -295,7 +280,7 @@ def _flush(out: List[str]) -> None:
         sys.stdout.write("\n".join(out) + "\n")
 
 
-def _combine_gpu(report_fp, ref_fp, contig, device, batch_rows, chunk_bytes, info, make_engine, out, np, eng) -> list:
+def _combine_gpu(report_fp, ref_fp, contig, device, batch_rows, chunk_bytes, info, make_engine, out, eng) -> list:
     bed = is_bed(report_fp)
     out.append(MSG_GENOME)
     genome = _Genome(ref_fp)
@@ -307,55 +292,42 @@ def _combine_gpu(report_fp, ref_fp, contig, device, batch_rows, chunk_bytes, inf
         raise _CpuRoute("more than 2^30 rows")
     names = list(genome.rec_id)
     host_w: Dict[int, List[str]] = {}     # global row -> w, for the '+' rows read here
-    host_rows = skipped = 0
+    host_rows, skips = 0, len(out)        # every line of `out` from here on is a skipped row's
     res, times = None, {}
+
+    def host_row(row: int, status: int):
+        """What combine_accumulate takes for a row the device did not add: nothing for one it found to be no CG itself."""
+        if status == eng.COMBINE_ROW_SKIP:
+            out.append(MSG_SKIP.format(rows.row_bytes(row).decode("ascii").split("\t")))
+            return tr.NO_HOST_ROW
+        w = tr.python_row(rows.row_bytes(row))
+        got = _read_row(w, bed, genome.in_motif)
+        if got is None:
+            out.append(MSG_SKIP.format(w))
+            return None
+        name, pos, plus, v = got
+        counts = (0, 0, v[0]) if bed else v[2:5]
+        if any(abs(c) >= eng.COMBINE_COUNT_LIMIT for c in counts):
+            raise _CpuRoute("a count of row %d does not fit the device's 64-bit sums" % row)
+        if plus and not bed:
+            host_w[row] = w
+        return (genome.rec_id[name], pos, int(plus)) + ((v[1], 0.0) if bed else v[0:2]) + tuple(counts)
+
     if rows.n:
-        # the ds_combine_* calls need no weights, but they hang off a handle: the smallest one, as call_freq --on gpu
-        e = make_engine() if make_engine is not None else eng.Engine(device=device, max_batch=64, slots=1)
-        try:
-            try:
+        with tr.small_engine(make_engine, device) as e:
+            with tr.fits("the genome's bitmap or the table of %d rows does not fit the device" % rows.n):
                 e.combine_begin(eng.COMBINE_BED if bed else eng.COMBINE_TABLE, genome.rec_len, rows.n, min(batch_rows, rows.n))
                 for sb, se, sbit, scarry in genome.chunks(chunk_bytes):
                     e.combine_genome(genome.data, sb, se, sbit, scarry)
-            except eng.FreqNoMemory as exc:
-                raise _CpuRoute("the genome's bitmap or the table of %d rows does not fit the device (%s)" % (rows.n, exc))
-            for s in range(0, rows.n, batch_rows):
-                t = min(rows.n, s + batch_rows)
-                status = e.combine_parse(rows.data, rows.begin[s:t], rows.end[s:t], rows.chrom[s:t], rows.flags[s:t])
-                o_row, given = [], []
-                for i in np.flatnonzero(status != eng.TEXT_ROW_OK).tolist():
-                    if status[i] == eng.COMBINE_ROW_SKIP:
-                        out.append(MSG_SKIP.format(rows.row_bytes(s + i).decode("ascii").split("\t")))
-                        skipped += 1
-                        continue
-                    w = _python_row(rows.row_bytes(s + i))
-                    got = _read_row(w, bed, genome.in_motif)
-                    o_row.append(i)
-                    host_rows += 1
-                    if got is None:
-                        out.append(MSG_SKIP.format(w))
-                        skipped += 1
-                        given.append(None)
-                        continue
-                    name, pos, plus, v = got
-                    counts = (0, 0, v[0]) if bed else v[2:5]
-                    if any(abs(c) >= eng.COMBINE_COUNT_LIMIT for c in counts):
-                        raise _CpuRoute("a count of row %d does not fit the device's 64-bit sums" % (s + i))
-                    if plus and not bed:
-                        host_w[s + i] = w
-                    given.append((genome.rec_id[name], pos, int(plus)) + ((v[1], 0.0) if bed else v[0:2]) + tuple(counts))
-                e.combine_accumulate(o_row, given)
-            res = e.combine_result()
-            times = e.combine_times()
-            e.combine_end()
-        finally:
-            e.close()
+            host_rows = tr.walk(rows.n, batch_rows,
+                                lambda s, t: e.combine_parse(rows.data, rows.begin[s:t], rows.end[s:t], rows.chrom[s:t], rows.flags[s:t]),
+                                host_row, lambda s, t, o_row, given: e.combine_accumulate(o_row, given))
+            res, times = tr.finish(e, "combine")
     if info is not None:
-        info.update(host_rows=host_rows, skipped=skipped, rows=rows.n, **times)
+        info.update(host_rows=host_rows, skipped=len(out) - skips, rows=rows.n, **times)
     if res is None:
         return []
-    if res["rows"] != rows.n:
-        raise RuntimeError("gpu route: %d rows accumulated, %d located" % (res["rows"], rows.n))
+    tr.check_rows(res, rows.n)
     table: Dict[Tuple[str, int], list] = {}
     for k in range(len(res["pos"])):
         key = (names[int(res["chrom"][k])], int(res["pos"][k]))

@@ -114,12 +114,15 @@ int64_t reference(int form, const char* text, int64_t nrows, const int64_t* begi
 // so two may share a word), sizes the site table for total_rows (load <= 0.5) and the row buffers for batch_rows. genome() copies one
 // chunk of FASTA bytes and ORs its motif bits in; the bytes do not stay. parse() copies a batch's text and parses it; accumulate()
 // applies the caller's values for ROW_HOST rows, inserts the ROW_OK rows' keys, sorts (site, row) and adds each site's run in row
-// order; result() compacts the occupied slots. Every call blocks; batches go strictly in sequence, after the last genome chunk.
-struct Combine {
+// order; result() compacts the occupied slots. Every call blocks; batches go strictly in sequence (dss::Batches), after the last
+// genome chunk. The handle holds a Combine from a begin() that succeeded to ds_combine_end: no call here asks whether a run is open.
+struct Combine : dss::Batches {
+    static constexpr const char* ROUTE = "ds_combine";
+    typedef dss::Times<5, 2> Tally;      // n: batches, genome chunks; ms: copies, motif_bitmap_kernel, combine_parse_kernel, the sort, insert + accumulate
     int form = FORM_TABLE;
     dss::Run run;                // the stream, the events and every device allocation of the run
-    int64_t total_rows = 0, rows_done = 0, nbits = 0;
-    int32_t batch_rows = 0, pending = -1, nrec = 0;
+    int64_t nbits = 0;
+    int32_t nrec = 0;
     bool rows_begun = false;
     std::vector<int64_t> h_len;
     uint64_t cap = 0;            // table slots, a power of two >= 2 * total_rows
@@ -139,8 +142,7 @@ struct Combine {
     double *d_a = nullptr, *d_b = nullptr;
     uint64_t* d_sort = nullptr;
     dss::Buf over;               // the caller's word on a batch's ROW_HOST rows
-    int64_t batches = 0, chunks = 0;
-    double ms[5] = {0, 0, 0, 0, 0};     // copies, motif_bitmap_kernel, combine_parse_kernel, the sort, insert + accumulate
+    Tally t;
 
     int begin(int device, int form, int32_t nrec, const int64_t* rec_len, int64_t total_rows, int32_t batch_rows, std::string* err);
     int genome(const char* text, int64_t nseg, const int64_t* seg_begin, const int64_t* seg_end, const int64_t* seg_bit,

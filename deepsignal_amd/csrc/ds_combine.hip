@@ -140,11 +140,10 @@ bool segments_ok(int64_t nseg, const int64_t* sb, const int64_t* se, const int64
 
 int Combine::begin(int dev, int fm, int32_t nr, const int64_t* rec_len, int64_t total, int32_t batch, std::string* err)
 {
-    if (run.s) return seterr(err, DS_ERR_INVALID, "ds_combine_begin: a run is open on this handle (ds_combine_end first)");
     if (fm != FORM_TABLE && fm != FORM_BED) return seterr(err, DS_ERR_INVALID, "ds_combine_begin: form must be DS_COMBINE_TABLE or DS_COMBINE_BED");
     if (nr < 1 || nr > dss::CHROM_LIMIT || !rec_len) return seterr(err, DS_ERR_INVALID, "ds_combine_begin: 1 .. 2^23 records");
-    if (total < 0 || total > dss::MAX_TOTAL_ROWS) return seterr(err, DS_ERR_INVALID, "ds_combine_begin: total_rows must be in [0, 2^30]");
-    if (batch < 1 || batch > (1 << 24)) return seterr(err, DS_ERR_INVALID, "ds_combine_begin: batch_rows must be in [1, 2^24]");
+    const int rc = sizes(ROUTE, 0, total, batch, err);
+    if (rc) return rc;
     std::vector<int64_t> base((size_t)nr);
     int64_t bits = 0;
     for (int32_t i = 0; i < nr; ++i) {
@@ -155,9 +154,6 @@ int Combine::begin(int dev, int fm, int32_t nr, const int64_t* rec_len, int64_t 
     }
     form = fm; nrec = nr; nbits = bits;
     h_len.assign(rec_len, rec_len + nr);
-    total_rows = total; rows_done = 0; batch_rows = batch; pending = -1; rows_begun = false;
-    batches = chunks = 0;
-    for (double& v : ms) v = 0;
     cap = 64;
     while (cap < 2 * (uint64_t)total) cap <<= 1;
     size_t P = 1;                 // the sort's keys: batch_rows rounded up to a power of two
@@ -194,7 +190,6 @@ int Combine::begin(int dev, int fm, int32_t nr, const int64_t* rec_len, int64_t 
 
 int Combine::genome(const char* text, int64_t nseg, const int64_t* sb, const int64_t* se, const int64_t* bit, const uint8_t* carry, std::string* err)
 {
-    if (!run.s) return seterr(err, DS_ERR_INVALID, "ds_combine_genome: no run is open (ds_combine_begin first)");
     if (rows_begun) return seterr(err, DS_ERR_INVALID, "ds_combine_genome: the rows have begun; the genome comes first");
     if (!text || !sb || !se || !bit || !carry) return seterr(err, DS_ERR_INVALID, "ds_combine_genome: null argument");
     if (nseg < 1 || nseg > 0x7fffffff) return seterr(err, DS_ERR_INVALID, "ds_combine_genome: 1 .. 2^31 - 1 segments in a chunk");
@@ -227,15 +222,14 @@ int Combine::genome(const char* text, int64_t nseg, const int64_t* sb, const int
     DSS_TRY(hipGetLastError());
     DSS_TRY(hipEventRecord(run.ev[2], s));
     DSS_TRY(hipStreamSynchronize(s));      // also: off / end and the caller's arrays may go away now
-    dss::book(&ms[0], run.ev[0], run.ev[1]);
-    dss::book(&ms[1], run.ev[1], run.ev[2]);
-    chunks += 1;
+    dss::book(&t.ms[0], run.ev[0], run.ev[1]);
+    dss::book(&t.ms[1], run.ev[1], run.ev[2]);
+    t.n[1] += 1;
     return DS_OK;
 }
 
 int Combine::get_bitmap(int64_t cap_words, uint32_t* out, std::string* err)
 {
-    if (!run.s) return seterr(err, DS_ERR_INVALID, "ds_combine_bitmap: no run is open (ds_combine_begin first)");
     const int64_t words = (nbits + 31) >> 5;
     if (cap_words < words || (words > 0 && !out)) return seterr(err, DS_ERR_INVALID, "ds_combine_bitmap: " + std::to_string(words) + " words, the array holds fewer");
     DSS_TRY(hipSetDevice(run.device));
@@ -247,18 +241,15 @@ int Combine::get_bitmap(int64_t cap_words, uint32_t* out, std::string* err)
 int Combine::parse(const char* text, int32_t n, const int64_t* rb, const int64_t* re, const int32_t* chrom, const uint8_t* flags, int32_t* status,
                    std::string* err)
 {
-    if (!run.s) return seterr(err, DS_ERR_INVALID, "ds_combine_parse: no run is open (ds_combine_begin first)");
-    if (pending >= 0) return seterr(err, DS_ERR_INVALID, "ds_combine_parse: the previous batch has not been accumulated");
-    if (!text || !rb || !re || !chrom || !flags || !status) return seterr(err, DS_ERR_INVALID, "ds_combine_parse: null argument");
-    if (n < 1 || n > batch_rows) return seterr(err, DS_ERR_INVALID, "ds_combine_parse: nrows must be in [1, batch_rows]");
-    if (rows_done + n > total_rows) return seterr(err, DS_ERR_INVALID, "ds_combine_parse: more rows than ds_combine_begin was told of");
-    int rc = rows.upload("ds_combine_parse", &run, text, n, rb, re, chrom, flags, err);
+    int rc = can_parse(ROUTE, n, text && rb && re && chrom && flags && status, err);
+    if (rc) return rc;
+    rc = rows.upload("ds_combine_parse", &run, text, n, rb, re, chrom, flags, err);
     if (rc) return rc;
     rows_begun = true;
     const RowArrays r = {rows.d_chrom, d_plus, rows.d_status, d_pos, d_c0, d_c1, d_c2, d_a, d_b};
     hipLaunchKernelGGL(combine_parse_kernel, dim3(blocks(n)), dim3(TPB), 0, run.s, form, rows.text.p, rows.d_off, rows.d_len, rows.d_flags, n, nrec, d_rec_base,
                        d_rec_len, bitmap, r);
-    rc = rows.finish(&run, n, status, &ms[0], &ms[2], err);
+    rc = rows.finish(&run, n, status, &t.ms[0], &t.ms[2], err);
     if (rc) return rc;
     pending = n;
     return DS_OK;
@@ -267,8 +258,8 @@ int Combine::parse(const char* text, int32_t n, const int64_t* rb, const int64_t
 int Combine::accumulate(int32_t m, const int32_t* row, const int32_t* ostatus, const int32_t* chrom, const int64_t* pos, const int32_t* plus,
                         const double* a, const double* b, const int64_t* c0, const int64_t* c1, const int64_t* c2, std::string* err)
 {
-    if (!run.s) return seterr(err, DS_ERR_INVALID, "ds_combine_accumulate: no run is open (ds_combine_begin first)");
-    if (pending < 0) return seterr(err, DS_ERR_INVALID, "ds_combine_accumulate: no parsed batch (ds_combine_parse first)");
+    const int ready = can_accumulate(ROUTE, err);
+    if (ready) return ready;
     const int n = pending;
     if (m < 0 || m > n) return seterr(err, DS_ERR_INVALID, "ds_combine_accumulate: nover must be in [0, rows of the batch]");
     if (m > 0 && (!row || !ostatus || !chrom || !pos || !plus || !a || !b || !c0 || !c1 || !c2))
@@ -305,9 +296,9 @@ int Combine::accumulate(int32_t m, const int32_t* row, const int32_t* ostatus, c
     hipLaunchKernelGGL(combine_accumulate_kernel, dim3(blocks(Pn)), dim3(TPB), 0, s, Pn, u64(d_sort), d_a, d_b, d_c0, d_c1, d_c2, t_sum0, t_sum1, t_met,
                        t_unmet, t_cov);
     ull c[4] = {0, 0, 0, 0};
-    const int rc = dss::finish_batch(&run, counters, c, &ms[0], &ms[3], &ms[4], err);
+    const int rc = dss::finish_batch(&run, counters, c, &t.ms[0], &t.ms[3], &t.ms[4], err);
     if (rc) return rc;
-    batches += 1;
+    t.n[0] += 1;
     pending = -1;
     rows_done += n;
     return dss::batch_verdict("ds_combine_accumulate", c, err);
@@ -316,8 +307,8 @@ int Combine::accumulate(int32_t m, const int32_t* row, const int32_t* ostatus, c
 int64_t Combine::result(int64_t cap_sites, int32_t* chrom, int64_t* pos, double* sum0, double* sum1, int64_t* met, int64_t* unmet, int64_t* cov,
                         int64_t* last_plus, int64_t* nrows, std::string* err)
 {
-    if (!run.s) return seterr(err, DS_ERR_INVALID, "ds_combine_result: no run is open (ds_combine_begin first)");
-    if (pending >= 0) return seterr(err, DS_ERR_INVALID, "ds_combine_result: a parsed batch has not been accumulated");
+    const int ready = can_result(ROUTE, err);
+    if (ready) return ready;
     DSS_TRY(hipSetDevice(run.device));
     ull c[4] = {0, 0, 0, 0};
     DSS_TRY(hipMemcpy(c, counters, sizeof(c), hipMemcpyDeviceToHost));

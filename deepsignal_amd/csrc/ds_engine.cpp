@@ -124,17 +124,20 @@ struct Plan {
 };
 
 enum class Ticket { Idle, Forward, Text, Rows };      // what a slot carries: nothing, or a ticket for ds_wait | ds_wait_text | ds_wait_rows
-template <int K>
-struct Times {           // what a ds_get_*_times getter reports: batches timed so far and their summed device milliseconds
-    int64_t batches = 0;
-    double ms[K] = {};
-    int get(int32_t reset, int64_t* n, double* out)
+using dss::Times;        // what a ds_get_*_times getter reports: batches timed so far and their summed device milliseconds
+
+// A table route on a handle (call_freq, combine_strands, evaluate --on gpu): the open run, from a begin that succeeded to the route's
+// end -- its table, row buffers and stream are its own: no pipeline slot, no weights -- and the time tally of the runs ended so far.
+template <class R>
+struct TableRuns {
+    R* open = nullptr;
+    typename R::Tally ended;
+    void close()
     {
-        if (!n || !out) return DS_ERR_INVALID;
-        *n = batches;
-        std::copy(ms, ms + K, out);
-        if (reset) *this = Times();
-        return DS_OK;
+        if (!open) return;
+        ended.add(open->t);
+        delete open;
+        open = nullptr;
     }
 };
 struct Block { char* p = nullptr; size_t cap = 0; };   // pinned host or device memory of a slot that grows with its batches (grow())
@@ -266,15 +269,9 @@ struct ds_handle {
     int64_t tx_rows = 0, tx_host_rows = 0;   // rows through ds_submit_text / ds_parse_text, and those the host parser took
     Times<3> tx_t;        // text batches, every one: H2D of the text, tsv_parse_kernel, D2H of status / label / info length / k-mer
     Times<1> rc_t;        // recheck_select_kernel launches timed while profiling was on
-    dsf::Freq* freq = nullptr;            // call_freq --on gpu: the open run (ds_freq_begin .. ds_freq_end); its table and buffers are its own
-    Times<4> fq_t;        // batches of the frequency runs ended so far (the open run's are added on top)
-    double fqs_ms[2] = {0, 0};        // streaming runs ended so far: freq_values_kernel, the table growths
-    int64_t fqs_growths = 0;
-    dsc::Combine* combine = nullptr;      // combine_strands --on gpu: the open run (ds_combine_begin .. ds_combine_end); bitmap, table and buffers are its own
-    Times<5> cb_t;        // genome chunks and batches of the combine runs ended so far (the open run's are added on top)
-    int64_t cb_chunks = 0;
-    dse::Eval* eval = nullptr;            // evaluate --on gpu: the open run (ds_eval_begin .. ds_eval_end); table, counters and buffers are its own
-    Times<4> ev_t;        // batches of the evaluate runs ended so far (the open run's are added on top)
+    TableRuns<dsf::Freq> freq;            // call_freq --on gpu (ds_freq_begin | ds_freq_begin_stream .. ds_freq_end)
+    TableRuns<dsc::Combine> combine;      // combine_strands --on gpu (ds_combine_begin .. ds_combine_end)
+    TableRuns<dse::Eval> eval;            // evaluate --on gpu (ds_eval_begin .. ds_eval_end)
     // training (ds_train_begin .. ds_train_end, ds_train.hip): the RNN-only variants (is_base 0 and 1) keep the tensors they were loaded with
     // (`kept`: what ds_train_begin starts from and ds_train_set_tensor replaces) and remembers which device blocks hold the packed
     // weights (`weight_allocs`), so that ds_train_sync_weights can pack the current parameters in their place
@@ -1571,6 +1568,47 @@ auto guarded(ds_handle* h, F&& body) -> decltype(body())      // int, or the int
         return fail(h, DS_ERR_INVALID, "internal error");
     }
 }
+
+// ---- table runs: call_freq, combine_strands and evaluate --on gpu (ds_freq.hip, ds_combine.hip, ds_eval.hip) ---------------------
+// One lifecycle for the three routes (TableRuns): a begin opens the route's run, every other call goes to the open run, the route's
+// end closes it. `route` is R::ROUTE ("ds_freq"), `call` the entry's name behind it.
+// ds_<route>_<call>, a begin: refused while a run is open; a run whose begin fails is gone again
+template <class R, class Begin>
+int open_run(ds_handle* h, TableRuns<R> ds_handle::*runs, const char* call, Begin begin)
+{
+    if (!h) return DS_ERR_INVALID;
+    TableRuns<R>& r = h->*runs;
+    if (r.open) return fail(h, DS_ERR_INVALID, std::string(R::ROUTE) + "_" + call + ": a run is open on this handle (" + R::ROUTE + "_end first)");
+    r.open = new R();
+    std::string err;
+    const int rc = begin(*r.open, &err);
+    if (rc == DS_OK) return DS_OK;
+    delete r.open;
+    r.open = nullptr;
+    return fail(h, rc, err);
+}
+
+// ds_<route>_<call> of the open run (opened by ds_<route>_<opener>): its DS_* code, or the count it returns
+template <class R, class Call>
+auto in_run(ds_handle* h, TableRuns<R> ds_handle::*runs, const char* call, Call body, const char* opener = "begin")
+    -> decltype(body(std::declval<R&>(), (std::string*)nullptr))
+{
+    if (!h) return DS_ERR_INVALID;
+    R* r = (h->*runs).open;
+    if (!r) return fail(h, DS_ERR_INVALID, std::string(R::ROUTE) + "_" + call + ": no run is open (" + R::ROUTE + "_" + opener + " first)");
+    std::string err;
+    const auto rc = body(*r, &err);
+    return rc < 0 ? fail(h, (int)rc, err) : rc;
+}
+
+// ds_<route>_end: DS_OK with or without a run
+template <class R>
+int end_run(ds_handle* h, TableRuns<R> ds_handle::*runs)
+{
+    if (!h) return DS_ERR_INVALID;
+    (h->*runs).close();
+    return DS_OK;
+}
 }  // namespace
 
 // ======================================= C ABI =======================================
@@ -1706,9 +1744,9 @@ void ds_destroy(ds_handle* h)
         if (sl.s0) hipStreamDestroy(sl.s0);
         if (sl.s1 && sl.owns_s1) hipStreamDestroy(sl.s1);
     }
-    delete h->freq;
-    delete h->combine;
-    delete h->eval;
+    h->freq.close();
+    h->combine.close();
+    h->eval.close();
     delete h->train;
     for (void* p : h->allocs) hipFree(p);
     (void)hipGetLastError();      // nothing a teardown call returned may surface in a later handle's first launch
@@ -2091,7 +2129,7 @@ static int finish_recheck(ds_handle* h, Slot& sl, int n, float* act, int32_t* pr
     if (!f) return fail(h, DS_ERR_INVALID, "recheck: the fine handle was detached while a forward was in flight");
     if (sl.rc_timed) {
         float ms = 0;
-        if (hipEventElapsedTime(&ms, sl.rc_ev[0], sl.rc_ev[1]) == hipSuccess) { h->rc_t.batches += 1; h->rc_t.ms[0] += ms; }
+        if (hipEventElapsedTime(&ms, sl.rc_ev[0], sl.rc_ev[1]) == hipSuccess) { h->rc_t.n[0] += 1; h->rc_t.ms[0] += ms; }
         else (void)hipGetLastError();
     }
     const RcLayout L = rc_layout(h);
@@ -2382,7 +2420,7 @@ static void book_text_times(ds_handle* h, Slot& sl)
         (void)hipGetLastError();
         return;
     }
-    h->tx_t.batches += 1;
+    h->tx_t.n[0] += 1;
     for (int i = 0; i < 3; ++i) h->tx_t.ms[i] += ms[i];
 }
 
@@ -2546,38 +2584,19 @@ int ds_get_text_stats(ds_handle* h, int64_t* rows, int64_t* host_rows)
 
 int ds_get_text_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms) { return h ? h->tx_t.get(reset, batches, ms) : DS_ERR_INVALID; }
 
-// ---- per-site modification frequency on the device (ds_freq.hip; call_freq --on gpu) ------------------------------------------------
-// The run's state is a dsf::Freq of its own (table, row buffers, stream): no pipeline slot, no weights.
-static void freq_close(ds_handle* h)
-{
-    if (!h->freq) return;
-    h->fq_t.batches += h->freq->batches;
-    for (int i = 0; i < 4; ++i) h->fq_t.ms[i] += h->freq->ms[i];
-    for (int i = 0; i < 2; ++i) h->fqs_ms[i] += h->freq->sms[i];
-    h->fqs_growths += h->freq->growths;
-    delete h->freq;
-    h->freq = nullptr;
-}
-
+// ---- table runs: call_freq, combine_strands and evaluate --on gpu (ds_freq.hip, ds_combine.hip, ds_eval.hip; open_run, in_run, end_run) ----
+// per-site modification frequency (dsf::Freq)
 static int ds_freq_begin_stream_impl(ds_handle* h, int64_t initial_slots, int32_t batch_rows, double prob_cf)
 {
-    if (!h) return DS_ERR_INVALID;
-    if (h->freq) return fail(h, DS_ERR_INVALID, "ds_freq_begin_stream: a run is open on this handle (ds_freq_end first)");
-    h->freq = new dsf::Freq();
-    std::string err;
-    const int rc = h->freq->begin_stream(h->cfg.device, initial_slots, batch_rows, prob_cf, &err);
-    if (rc) { delete h->freq; h->freq = nullptr; return fail(h, rc, err); }
-    return DS_OK;
+    return open_run(h, &ds_handle::freq, "begin_stream",
+                    [&](dsf::Freq& r, std::string* err) { return r.begin_stream(h->cfg.device, initial_slots, batch_rows, prob_cf, err); });
 }
 
 static int ds_freq_push_impl(ds_handle* h, int32_t nrows, const int32_t* chrom, const int64_t* pos, const float* act, int32_t class_num,
                              const int32_t* pred, int32_t* status, int32_t* opened)
 {
-    if (!h) return DS_ERR_INVALID;
-    if (!h->freq) return fail(h, DS_ERR_INVALID, "ds_freq_push: no run is open (ds_freq_begin_stream first)");
-    std::string err;
-    const int rc = h->freq->push(nrows, chrom, pos, act, class_num, pred, status, opened, &err);
-    return rc ? fail(h, rc, err) : DS_OK;
+    return in_run(h, &ds_handle::freq, "push",
+                  [&](dsf::Freq& r, std::string* err) { return r.push(nrows, chrom, pos, act, class_num, pred, status, opened, err); }, "begin_stream");
 }
 
 static int ds_freq_values_impl(ds_handle* h, int64_t n, const float* act, int32_t class_num, double* p0, double* p1, int32_t* status)
@@ -2590,51 +2609,32 @@ static int ds_freq_values_impl(ds_handle* h, int64_t n, const float* act, int32_
 
 static int ds_freq_begin_impl(ds_handle* h, int64_t total_rows, int32_t batch_rows, double prob_cf)
 {
-    if (!h) return DS_ERR_INVALID;
-    if (h->freq) return fail(h, DS_ERR_INVALID, "ds_freq_begin: a run is open on this handle (ds_freq_end first)");
-    h->freq = new dsf::Freq();
-    std::string err;
-    const int rc = h->freq->begin(h->cfg.device, total_rows, batch_rows, prob_cf, &err);
-    if (rc) { delete h->freq; h->freq = nullptr; return fail(h, rc, err); }
-    return DS_OK;
+    return open_run(h, &ds_handle::freq, "begin",
+                    [&](dsf::Freq& r, std::string* err) { return r.begin(h->cfg.device, total_rows, batch_rows, prob_cf, err); });
 }
 
 static int ds_freq_parse_impl(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, const int32_t* chrom,
                               const uint8_t* flags, int32_t* status)
 {
-    if (!h) return DS_ERR_INVALID;
-    if (!h->freq) return fail(h, DS_ERR_INVALID, "ds_freq_parse: no run is open (ds_freq_begin first)");
-    std::string err;
-    const int rc = h->freq->parse(text, nrows, begin, end, chrom, flags, status, &err);
-    return rc ? fail(h, rc, err) : DS_OK;
+    return in_run(h, &ds_handle::freq, "parse",
+                  [&](dsf::Freq& r, std::string* err) { return r.parse(text, nrows, begin, end, chrom, flags, status, err); });
 }
 
 static int ds_freq_accumulate_impl(ds_handle* h, int32_t nover, const int32_t* row, const int32_t* chrom, const int64_t* pos, const double* p0,
                                    const double* p1, const int32_t* met)
 {
-    if (!h) return DS_ERR_INVALID;
-    if (!h->freq) return fail(h, DS_ERR_INVALID, "ds_freq_accumulate: no run is open (ds_freq_begin first)");
-    std::string err;
-    const int rc = h->freq->accumulate(nover, row, chrom, pos, p0, p1, met, &err);
-    return rc ? fail(h, rc, err) : DS_OK;
+    return in_run(h, &ds_handle::freq, "accumulate",
+                  [&](dsf::Freq& r, std::string* err) { return r.accumulate(nover, row, chrom, pos, p0, p1, met, err); });
 }
 
 static int64_t ds_freq_result_impl(ds_handle* h, int64_t cap, int64_t* first_row, int32_t* chrom, int64_t* pos, double* sum0, double* sum1,
                                    int32_t* met, int32_t* unmet, int64_t* rows, int64_t* used)
 {
-    if (!h) return DS_ERR_INVALID;
-    if (!h->freq) return fail(h, DS_ERR_INVALID, "ds_freq_result: no run is open (ds_freq_begin first)");
-    std::string err;
-    const int64_t rc = h->freq->result(cap, first_row, chrom, pos, sum0, sum1, met, unmet, rows, used, &err);
-    return rc < 0 ? fail(h, (int)rc, err) : rc;
+    return in_run(h, &ds_handle::freq, "result",
+                  [&](dsf::Freq& r, std::string* err) { return r.result(cap, first_row, chrom, pos, sum0, sum1, met, unmet, rows, used, err); });
 }
 
-int ds_freq_end(ds_handle* h)
-{
-    if (!h) return DS_ERR_INVALID;
-    freq_close(h);
-    return DS_OK;
-}
+int ds_freq_end(ds_handle* h) { return end_run(h, &ds_handle::freq); }
 
 int64_t ds_freq_reference(const char* text, int64_t nrows, const int64_t* begin, const int64_t* end, const int32_t* chrom, const uint8_t* flags,
                           double prob_cf, int32_t* status, int64_t* pos, double* p0, double* p1, int32_t* met, int64_t cap, int64_t* first_row,
@@ -2656,107 +2656,57 @@ int ds_freq_values_reference(int64_t n, const float* act, int32_t class_num, dou
 
 int ds_get_freq_stream_times(ds_handle* h, int32_t reset, int64_t* growths, double* ms)
 {
-    if (!h || !growths || !ms) return DS_ERR_INVALID;
-    *growths = h->fqs_growths + (h->freq ? h->freq->growths : 0);
-    for (int i = 0; i < 2; ++i) ms[i] = h->fqs_ms[i] + (h->freq ? h->freq->sms[i] : 0.0);
-    if (reset) {
-        h->fqs_growths = 0;
-        h->fqs_ms[0] = h->fqs_ms[1] = 0;
-        if (h->freq) { h->freq->growths = 0; for (double& v : h->freq->sms) v = 0; }
-    }
-    return DS_OK;
+    return h ? h->freq.ended.stream.get(reset, growths, ms, h->freq.open ? &h->freq.open->t.stream : nullptr) : DS_ERR_INVALID;
 }
 
 int ds_get_freq_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms)
 {
-    if (!h || !batches || !ms) return DS_ERR_INVALID;
-    *batches = h->fq_t.batches + (h->freq ? h->freq->batches : 0);
-    for (int i = 0; i < 4; ++i) ms[i] = h->fq_t.ms[i] + (h->freq ? h->freq->ms[i] : 0.0);
-    if (reset) {
-        h->fq_t = Times<4>();
-        if (h->freq) { h->freq->batches = 0; for (double& v : h->freq->ms) v = 0; }
-    }
-    return DS_OK;
+    return h ? h->freq.ended.batch.get(reset, batches, ms, h->freq.open ? &h->freq.open->t.batch : nullptr) : DS_ERR_INVALID;
 }
 
-// ---- both strands of a CpG table combined on the device (ds_combine.hip; combine_strands --on gpu) ---------------------------------
-// The run's state is a dsc::Combine of its own (bitmap, table, row buffers, stream): no pipeline slot, no weights.
-static void combine_close(ds_handle* h)
-{
-    if (!h->combine) return;
-    h->cb_t.batches += h->combine->batches;
-    h->cb_chunks += h->combine->chunks;
-    for (int i = 0; i < 5; ++i) h->cb_t.ms[i] += h->combine->ms[i];
-    delete h->combine;
-    h->combine = nullptr;
-}
-
+// both strands of a CpG table combined (dsc::Combine)
 static int ds_combine_begin_impl(ds_handle* h, int32_t form, int32_t nrec, const int64_t* rec_len, int64_t total_rows, int32_t batch_rows)
 {
-    if (!h) return DS_ERR_INVALID;
-    if (h->combine) return fail(h, DS_ERR_INVALID, "ds_combine_begin: a run is open on this handle (ds_combine_end first)");
-    h->combine = new dsc::Combine();
-    std::string err;
-    const int rc = h->combine->begin(h->cfg.device, form, nrec, rec_len, total_rows, batch_rows, &err);
-    if (rc) { delete h->combine; h->combine = nullptr; return fail(h, rc, err); }
-    return DS_OK;
+    return open_run(h, &ds_handle::combine, "begin",
+                    [&](dsc::Combine& r, std::string* err) { return r.begin(h->cfg.device, form, nrec, rec_len, total_rows, batch_rows, err); });
 }
 
 static int ds_combine_genome_impl(ds_handle* h, const char* text, int64_t nseg, const int64_t* seg_begin, const int64_t* seg_end, const int64_t* seg_bit,
                                   const uint8_t* seg_carry)
 {
-    if (!h) return DS_ERR_INVALID;
-    if (!h->combine) return fail(h, DS_ERR_INVALID, "ds_combine_genome: no run is open (ds_combine_begin first)");
-    std::string err;
-    const int rc = h->combine->genome(text, nseg, seg_begin, seg_end, seg_bit, seg_carry, &err);
-    return rc ? fail(h, rc, err) : DS_OK;
+    return in_run(h, &ds_handle::combine, "genome",
+                  [&](dsc::Combine& r, std::string* err) { return r.genome(text, nseg, seg_begin, seg_end, seg_bit, seg_carry, err); });
 }
 
 static int ds_combine_bitmap_impl(ds_handle* h, int64_t cap_words, uint32_t* bitmap)
 {
-    if (!h) return DS_ERR_INVALID;
-    if (!h->combine) return fail(h, DS_ERR_INVALID, "ds_combine_bitmap: no run is open (ds_combine_begin first)");
-    std::string err;
-    const int rc = h->combine->get_bitmap(cap_words, bitmap, &err);
-    return rc ? fail(h, rc, err) : DS_OK;
+    return in_run(h, &ds_handle::combine, "bitmap", [&](dsc::Combine& r, std::string* err) { return r.get_bitmap(cap_words, bitmap, err); });
 }
 
 static int ds_combine_parse_impl(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, const int32_t* chrom,
                                  const uint8_t* flags, int32_t* status)
 {
-    if (!h) return DS_ERR_INVALID;
-    if (!h->combine) return fail(h, DS_ERR_INVALID, "ds_combine_parse: no run is open (ds_combine_begin first)");
-    std::string err;
-    const int rc = h->combine->parse(text, nrows, begin, end, chrom, flags, status, &err);
-    return rc ? fail(h, rc, err) : DS_OK;
+    return in_run(h, &ds_handle::combine, "parse",
+                  [&](dsc::Combine& r, std::string* err) { return r.parse(text, nrows, begin, end, chrom, flags, status, err); });
 }
 
 static int ds_combine_accumulate_impl(ds_handle* h, int32_t nover, const int32_t* row, const int32_t* status, const int32_t* chrom, const int64_t* pos,
                                       const int32_t* plus, const double* a, const double* b, const int64_t* met, const int64_t* unmet, const int64_t* cov)
 {
-    if (!h) return DS_ERR_INVALID;
-    if (!h->combine) return fail(h, DS_ERR_INVALID, "ds_combine_accumulate: no run is open (ds_combine_begin first)");
-    std::string err;
-    const int rc = h->combine->accumulate(nover, row, status, chrom, pos, plus, a, b, met, unmet, cov, &err);
-    return rc ? fail(h, rc, err) : DS_OK;
+    return in_run(h, &ds_handle::combine, "accumulate", [&](dsc::Combine& r, std::string* err) {
+        return r.accumulate(nover, row, status, chrom, pos, plus, a, b, met, unmet, cov, err);
+    });
 }
 
 static int64_t ds_combine_result_impl(ds_handle* h, int64_t cap, int32_t* chrom, int64_t* pos, double* sum0, double* sum1, int64_t* met, int64_t* unmet,
                                       int64_t* cov, int64_t* last_plus, int64_t* rows)
 {
-    if (!h) return DS_ERR_INVALID;
-    if (!h->combine) return fail(h, DS_ERR_INVALID, "ds_combine_result: no run is open (ds_combine_begin first)");
-    std::string err;
-    const int64_t rc = h->combine->result(cap, chrom, pos, sum0, sum1, met, unmet, cov, last_plus, rows, &err);
-    return rc < 0 ? fail(h, (int)rc, err) : rc;
+    return in_run(h, &ds_handle::combine, "result", [&](dsc::Combine& r, std::string* err) {
+        return r.result(cap, chrom, pos, sum0, sum1, met, unmet, cov, last_plus, rows, err);
+    });
 }
 
-int ds_combine_end(ds_handle* h)
-{
-    if (!h) return DS_ERR_INVALID;
-    combine_close(h);
-    return DS_OK;
-}
+int ds_combine_end(ds_handle* h) { return end_run(h, &ds_handle::combine); }
 
 int ds_motif_reference(const char* text, int64_t nseg, const int64_t* seg_begin, const int64_t* seg_end, const int64_t* seg_bit, const uint8_t* seg_carry,
                        int64_t nbits, uint32_t* bitmap)
@@ -2784,73 +2734,39 @@ int64_t ds_combine_reference(int32_t form, const char* text, int64_t nrows, cons
 int ds_get_combine_times(ds_handle* h, int32_t reset, int64_t* chunks, int64_t* batches, double* ms)
 {
     if (!h || !chunks || !batches || !ms) return DS_ERR_INVALID;
-    *chunks = h->cb_chunks + (h->combine ? h->combine->chunks : 0);
-    *batches = h->cb_t.batches + (h->combine ? h->combine->batches : 0);
-    for (int i = 0; i < 5; ++i) ms[i] = h->cb_t.ms[i] + (h->combine ? h->combine->ms[i] : 0.0);
-    if (reset) {
-        h->cb_t = Times<5>();
-        h->cb_chunks = 0;
-        if (h->combine) { h->combine->batches = h->combine->chunks = 0; for (double& v : h->combine->ms) v = 0; }
-    }
+    const dsc::Combine::Tally t = h->combine.ended.take(reset, h->combine.open ? &h->combine.open->t : nullptr);
+    *batches = t.n[0];
+    *chunks = t.n[1];
+    std::copy(t.ms, t.ms + 5, ms);
     return DS_OK;
 }
 
-// ---- call accuracy and AUROC of labelled call rows on the device (ds_eval.hip; evaluate --on gpu) ----------------------------------
-// The run's state is a dse::Eval of its own (score table, counters, row buffers, stream): no pipeline slot, no weights.
-static void eval_close(ds_handle* h)
-{
-    if (!h->eval) return;
-    h->ev_t.batches += h->eval->batches;
-    for (int i = 0; i < 4; ++i) h->ev_t.ms[i] += h->eval->ms[i];
-    delete h->eval;
-    h->eval = nullptr;
-}
-
+// call accuracy and AUROC of labelled call rows (dse::Eval)
 static int ds_eval_begin_impl(ds_handle* h, int64_t total_rows, int32_t batch_rows, int32_t ncf, const double* cf)
 {
-    if (!h) return DS_ERR_INVALID;
-    if (h->eval) return fail(h, DS_ERR_INVALID, "ds_eval_begin: a run is open on this handle (ds_eval_end first)");
-    h->eval = new dse::Eval();
-    std::string err;
-    const int rc = h->eval->begin(h->cfg.device, total_rows, batch_rows, ncf, cf, &err);
-    if (rc) { delete h->eval; h->eval = nullptr; return fail(h, rc, err); }
-    return DS_OK;
+    return open_run(h, &ds_handle::eval, "begin",
+                    [&](dse::Eval& r, std::string* err) { return r.begin(h->cfg.device, total_rows, batch_rows, ncf, cf, err); });
 }
 
 static int ds_eval_parse_impl(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, const uint8_t* flags, int32_t* status)
 {
-    if (!h) return DS_ERR_INVALID;
-    if (!h->eval) return fail(h, DS_ERR_INVALID, "ds_eval_parse: no run is open (ds_eval_begin first)");
-    std::string err;
-    const int rc = h->eval->parse(text, nrows, begin, end, flags, status, &err);
-    return rc ? fail(h, rc, err) : DS_OK;
+    return in_run(h, &ds_handle::eval, "parse", [&](dse::Eval& r, std::string* err) { return r.parse(text, nrows, begin, end, flags, status, err); });
 }
 
 static int ds_eval_accumulate_impl(ds_handle* h, const uint8_t* mask, int32_t nover, const int32_t* row, const double* p0, const double* p1,
                                    const int32_t* called)
 {
-    if (!h) return DS_ERR_INVALID;
-    if (!h->eval) return fail(h, DS_ERR_INVALID, "ds_eval_accumulate: no run is open (ds_eval_begin first)");
-    std::string err;
-    const int rc = h->eval->accumulate(mask, nover, row, p0, p1, called, &err);
-    return rc ? fail(h, rc, err) : DS_OK;
+    return in_run(h, &ds_handle::eval, "accumulate",
+                  [&](dse::Eval& r, std::string* err) { return r.accumulate(mask, nover, row, p0, p1, called, err); });
 }
 
 static int ds_eval_result_impl(ds_handle* h, int64_t* counts, uint64_t* u2, int64_t* pn, int64_t* nn, int64_t* rows, int64_t* distinct)
 {
-    if (!h) return DS_ERR_INVALID;
-    if (!h->eval) return fail(h, DS_ERR_INVALID, "ds_eval_result: no run is open (ds_eval_begin first)");
-    std::string err;
-    const int rc = h->eval->result(counts, u2, pn, nn, rows, distinct, &err);
-    return rc ? fail(h, rc, err) : DS_OK;
+    return in_run(h, &ds_handle::eval, "result",
+                  [&](dse::Eval& r, std::string* err) { return r.result(counts, u2, pn, nn, rows, distinct, err); });
 }
 
-int ds_eval_end(ds_handle* h)
-{
-    if (!h) return DS_ERR_INVALID;
-    eval_close(h);
-    return DS_OK;
-}
+int ds_eval_end(ds_handle* h) { return end_run(h, &ds_handle::eval); }
 
 int ds_eval_reference(const char* text, int64_t nrows, const int64_t* begin, const int64_t* end, const uint8_t* flags, const uint8_t* mask, int32_t ncf,
                       const double* cf, int32_t* status, double* p0, double* p1, int32_t* called, int64_t* counts, uint64_t* u2, int64_t* pn, int64_t* nn)
@@ -2864,14 +2780,7 @@ int ds_eval_reference(const char* text, int64_t nrows, const int64_t* begin, con
 
 int ds_get_eval_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms)
 {
-    if (!h || !batches || !ms) return DS_ERR_INVALID;
-    *batches = h->ev_t.batches + (h->eval ? h->eval->batches : 0);
-    for (int i = 0; i < 4; ++i) ms[i] = h->ev_t.ms[i] + (h->eval ? h->eval->ms[i] : 0.0);
-    if (reset) {
-        h->ev_t = Times<4>();
-        if (h->eval) { h->eval->batches = 0; for (double& v : h->eval->ms) v = 0; }
-    }
-    return DS_OK;
+    return h ? h->eval.ended.get(reset, batches, ms, h->eval.open ? &h->eval.open->t : nullptr) : DS_ERR_INVALID;
 }
 
 // ---- feature rows: float64 values and their text on the device (ds_extract.hip rows_*_kernel) ---------------------------------
@@ -2984,7 +2893,7 @@ static int64_t ds_extract_rows_impl(ds_handle* h, const ds_reads* r, const char*
     if (rc) return rc;
     const int64_t got = collect_rows(h, *sl, p.nsites, out, cap, row_off, timed ? ev.ev + 5 : nullptr);
     if (got >= 0 && timed) {
-        h->rows_t.batches += 1;
+        h->rows_t.n[0] += 1;
         for (int i = 0; i < 4; ++i) { float ms = 0; hipEventElapsedTime(&ms, ev.ev[i], ev.ev[i + 1]); h->rows_t.ms[i] += ms; }
         float ms = 0;
         hipEventElapsedTime(&ms, ev.ev[5], ev.ev[6]);

@@ -101,11 +101,13 @@ bool reference(const char* text, int64_t nrows, const int64_t* begin, const int6
 // ---- one run on the device ------------------------------------------------------------------------------------------------
 // begin() sizes the table for total_rows (load <= 0.5) and the row buffers for batch_rows; parse() copies a batch's text and parses
 // it; accumulate() applies the caller's values for ROW_HOST rows, counts, and adds the rows' scores to the table; result() sorts the
-// distinct scores, scans the negatives below each and reduces U2. Every call blocks; batches go strictly in sequence.
-struct Eval {
+// distinct scores, scans the negatives below each and reduces U2. Every call blocks; batches go strictly in sequence (dss::Batches).
+// The handle holds an Eval from a begin() that succeeded to ds_eval_end: no call here asks whether a run is open.
+struct Eval : dss::Batches {
+    static constexpr const char* ROUTE = "ds_eval";
+    typedef dss::Times<4> Tally;     // copies, eval_parse_kernel, eval_count_kernel + eval_insert_kernel, the result (sort, scan, reduce)
     dss::Run run;
-    int64_t total_rows = 0, rows_done = 0;
-    int32_t batch_rows = 0, pending = -1, ncf = 0;
+    int32_t ncf = 0;
     uint64_t cap = 0;            // table slots, a power of two >= 2 * total_rows
     uint64_t* t_key = nullptr;
     uint32_t* t_cnt = nullptr;   // four counts per slot (count_index)
@@ -118,8 +120,7 @@ struct Eval {
     int32_t* d_called = nullptr;
     double *d_p0 = nullptr, *d_p1 = nullptr;
     dss::Buf over, res;          // the caller's values of a batch's ROW_HOST rows; the result's sorted keys, counts, scans
-    int64_t batches = 0;
-    double ms[4] = {0, 0, 0, 0};     // copies, eval_parse_kernel, eval_count_kernel + eval_insert_kernel, the result (sort, scan, reduce)
+    Tally t;
 
     int begin(int device, int64_t total_rows, int32_t batch_rows, int32_t ncf, const double* cf, std::string* err);
     int parse(const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, const uint8_t* flags, int32_t* status,

@@ -225,13 +225,10 @@ bool cutoffs_ok(int32_t ncf, const double* cf) { return ncf >= 1 && ncf <= MAX_C
 
 int Eval::begin(int dev, int64_t total, int32_t batch, int32_t n_cf, const double* cf, std::string* err)
 {
-    if (run.s) return seterr(err, DS_ERR_INVALID, "ds_eval_begin: a run is open on this handle (ds_eval_end first)");
-    if (total < 1 || total > dss::MAX_TOTAL_ROWS) return seterr(err, DS_ERR_INVALID, "ds_eval_begin: total_rows must be in [1, 2^30]");
-    if (batch < 1 || batch > (1 << 24)) return seterr(err, DS_ERR_INVALID, "ds_eval_begin: batch_rows must be in [1, 2^24]");
+    const int rc = sizes(ROUTE, 1, total, batch, err);
+    if (rc) return rc;
     if (!cutoffs_ok(n_cf, cf)) return seterr(err, DS_ERR_INVALID, "ds_eval_begin: 1 .. 32 cut-offs");
-    total_rows = total; rows_done = 0; batch_rows = batch; pending = -1; ncf = n_cf;
-    batches = 0;
-    for (double& v : ms) v = 0;
+    ncf = n_cf;
     cap = 64;
     while (cap < 2 * (uint64_t)total) cap <<= 1;
     const size_t B = (size_t)batch;
@@ -253,16 +250,13 @@ int Eval::begin(int dev, int64_t total, int32_t batch, int32_t n_cf, const doubl
 
 int Eval::parse(const char* text, int32_t n, const int64_t* rb, const int64_t* re, const uint8_t* flags, int32_t* status, std::string* err)
 {
-    if (!run.s) return seterr(err, DS_ERR_INVALID, "ds_eval_parse: no run is open (ds_eval_begin first)");
-    if (pending >= 0) return seterr(err, DS_ERR_INVALID, "ds_eval_parse: the previous batch has not been accumulated");
-    if (!text || !rb || !re || !flags || !status) return seterr(err, DS_ERR_INVALID, "ds_eval_parse: null argument");
-    if (n < 1 || n > batch_rows) return seterr(err, DS_ERR_INVALID, "ds_eval_parse: nrows must be in [1, batch_rows]");
-    if (rows_done + n > total_rows) return seterr(err, DS_ERR_INVALID, "ds_eval_parse: more rows than ds_eval_begin was told of");
-    int rc = rows.upload("ds_eval_parse", &run, text, n, rb, re, zeros.data(), flags, err);      // the rows name no chromosome here
+    int rc = can_parse(ROUTE, n, text && rb && re && flags && status, err);
+    if (rc) return rc;
+    rc = rows.upload("ds_eval_parse", &run, text, n, rb, re, zeros.data(), flags, err);      // the rows name no chromosome here
     if (rc) return rc;
     hipLaunchKernelGGL(eval_parse_kernel, dim3(blocks(n)), dim3(TPB), 0, run.s, rows.text.p, rows.d_off, rows.d_len, rows.d_flags, n, d_p0, d_p1, d_called,
                        rows.d_status);
-    rc = rows.finish(&run, n, status, &ms[0], &ms[1], err);
+    rc = rows.finish(&run, n, status, &t.ms[0], &t.ms[1], err);
     if (rc) return rc;
     pending = n;
     return DS_OK;
@@ -270,8 +264,8 @@ int Eval::parse(const char* text, int32_t n, const int64_t* rb, const int64_t* r
 
 int Eval::accumulate(const uint8_t* mask, int32_t m, const int32_t* row, const double* p0, const double* p1, const int32_t* called, std::string* err)
 {
-    if (!run.s) return seterr(err, DS_ERR_INVALID, "ds_eval_accumulate: no run is open (ds_eval_begin first)");
-    if (pending < 0) return seterr(err, DS_ERR_INVALID, "ds_eval_accumulate: no parsed batch (ds_eval_parse first)");
+    const int ready = can_accumulate(ROUTE, err);
+    if (ready) return ready;
     const int n = pending;
     if (!mask) return seterr(err, DS_ERR_INVALID, "ds_eval_accumulate: null argument");
     if (m < 0 || m > n) return seterr(err, DS_ERR_INVALID, "ds_eval_accumulate: nover must be in [0, rows of the batch]");
@@ -299,9 +293,9 @@ int Eval::accumulate(const uint8_t* mask, int32_t m, const int32_t* row, const d
     ull c[4] = {0, 0, 0, 0};
     DSS_TRY(hipMemcpyAsync(c, counters, sizeof(c), hipMemcpyDeviceToHost, s));
     DSS_TRY(hipStreamSynchronize(s));          // also: the caller's arrays may go away now
-    dss::book(&ms[0], run.ev[0], run.ev[1]);
-    dss::book(&ms[2], run.ev[1], run.ev[2]);
-    batches += 1;
+    dss::book(&t.ms[0], run.ev[0], run.ev[1]);
+    dss::book(&t.ms[2], run.ev[1], run.ev[2]);
+    t.n[0] += 1;
     pending = -1;
     rows_done += n;
     return dss::batch_verdict("ds_eval_accumulate", c, err);
@@ -309,8 +303,8 @@ int Eval::accumulate(const uint8_t* mask, int32_t m, const int32_t* row, const d
 
 int Eval::result(int64_t* counts, uint64_t* u2, int64_t* pn, int64_t* nn, int64_t* nrows, int64_t* distinct, std::string* err)
 {
-    if (!run.s) return seterr(err, DS_ERR_INVALID, "ds_eval_result: no run is open (ds_eval_begin first)");
-    if (pending >= 0) return seterr(err, DS_ERR_INVALID, "ds_eval_result: a parsed batch has not been accumulated");
+    const int ready = can_result(ROUTE, err);
+    if (ready) return ready;
     if (!counts || !u2 || !pn || !nn) return seterr(err, DS_ERR_INVALID, "ds_eval_result: null argument");
     hipStream_t s = run.s;
     DSS_TRY(hipSetDevice(run.device));
@@ -346,7 +340,7 @@ int Eval::result(int64_t* counts, uint64_t* u2, int64_t* pn, int64_t* nn, int64_
         DSS_TRY(hipEventRecord(run.ev[1], s));
         DSS_TRY(hipMemcpyAsync(c + COUNTERS_U2, counters + COUNTERS_U2, 3 * NSETS * 8, hipMemcpyDeviceToHost, s));
         DSS_TRY(hipStreamSynchronize(s));
-        dss::book(&ms[3], run.ev[0], run.ev[1]);
+        dss::book(&t.ms[3], run.ev[0], run.ev[1]);
     } else {
         for (int k = 0; k < 3 * NSETS; ++k) c[COUNTERS_U2 + k] = 0;
     }

@@ -136,11 +136,16 @@ int values_device(int device, int64_t n, const float* act, int32_t class_num, do
 // adds each site's run in row order; result() compacts the occupied slots. Every call blocks; batches go strictly in sequence.
 // A streaming run (begin_stream) takes push() in the place of parse(): keys, act rows and labels from the host, the values by
 // freq_values_kernel, and before that a doubling of the table (grow) whenever 2 * (sites + rows of the batch) > slots.
-// Return codes are the DS_* of the public header; the message goes to *err.
-struct Freq {
+// Return codes are the DS_* of the public header; the message goes to *err. Batches go strictly in sequence (dss::Batches). The
+// handle holds a Freq from a begin() that succeeded to ds_freq_end: no call here asks whether a run is open.
+struct Freq : dss::Batches {
+    static constexpr const char* ROUTE = "ds_freq";
+    struct Tally {
+        dss::Times<4> batch;     // batches: copies, freq_parse_kernel, the sort, insert + accumulate
+        dss::Times<2> stream;    // doublings of a streaming run's table: freq_values_kernel, the growths (freq_rehash_kernel and the new table's memsets)
+        void add(const Tally& o) { batch.add(o.batch); stream.add(o.stream); }
+    };
     dss::Run run;                // the stream, the events and every device allocation of the run
-    int64_t total_rows = 0, rows_done = 0;
-    int32_t batch_rows = 0, pending = -1;      // pending = rows parsed, not accumulated
     double cf = 0;
     uint64_t cap = 0;            // table slots, a power of two >= 2 * total_rows
     // table
@@ -155,8 +160,7 @@ struct Freq {
     double *d_p0 = nullptr, *d_p1 = nullptr;
     uint64_t* d_sort = nullptr;
     dss::Buf over;               // the caller's values of a batch's ROW_HOST rows
-    int64_t batches = 0;
-    double ms[4] = {0, 0, 0, 0};     // copies, freq_parse_kernel, the sort, insert + accumulate
+    Tally t;
 
     // streaming (begin_stream / push): the number of rows is not known, the table doubles when a batch might fill it past one half
     bool streaming = false;
@@ -164,8 +168,6 @@ struct Freq {
     dss::Buf act;                // a batch's act rows, float32
     int32_t *d_pred = nullptr, *d_opened = nullptr;
     int32_t* opened_out = nullptr;       // the caller's array of the pending push: filled when accumulate() completes it
-    int64_t growths = 0;         // doublings of the table
-    double sms[2] = {0, 0};      // freq_values_kernel, the growths (freq_rehash_kernel and the new table's memsets)
 
     int begin(int device, int64_t total_rows, int32_t batch_rows, double prob_cf, std::string* err);
     int begin_stream(int device, int64_t initial_slots, int32_t batch_rows, double prob_cf, std::string* err);

@@ -138,12 +138,9 @@ __global__ __launch_bounds__(TPB) void freq_rehash_kernel(ull old_cap, const ull
 
 int Freq::begin(int dev, int64_t total, int32_t batch, double prob_cf, std::string* err)
 {
-    if (run.s) return seterr(err, DS_ERR_INVALID, "ds_freq_begin: a run is open on this handle (ds_freq_end first)");
-    if (total < 1 || total > dss::MAX_TOTAL_ROWS) return seterr(err, DS_ERR_INVALID, "ds_freq_begin: total_rows must be in [1, 2^30]");
-    if (batch < 1 || batch > (1 << 24)) return seterr(err, DS_ERR_INVALID, "ds_freq_begin: batch_rows must be in [1, 2^24]");
+    const int rc = sizes(ROUTE, 1, total, batch, err);
+    if (rc) return rc;
     if (prob_cf != prob_cf) return seterr(err, DS_ERR_INVALID, "ds_freq_begin: prob_cf is NaN");
-    total_rows = total;
-    streaming = false;
     cap = 64;
     while (cap < 2 * (uint64_t)total) cap <<= 1;
     return open(dev, batch, prob_cf, err);
@@ -151,7 +148,6 @@ int Freq::begin(int dev, int64_t total, int32_t batch, double prob_cf, std::stri
 
 int Freq::begin_stream(int dev, int64_t initial_slots, int32_t batch, double prob_cf, std::string* err)
 {
-    if (run.s) return seterr(err, DS_ERR_INVALID, "ds_freq_begin_stream: a run is open on this handle (ds_freq_end first)");
     if (initial_slots < 1 || initial_slots > 2 * dss::MAX_TOTAL_ROWS) return seterr(err, DS_ERR_INVALID, "ds_freq_begin_stream: initial_slots must be in [1, 2^31]");
     if (batch < 1 || batch > (1 << 24)) return seterr(err, DS_ERR_INVALID, "ds_freq_begin_stream: batch_rows must be in [1, 2^24]");
     if (prob_cf != prob_cf) return seterr(err, DS_ERR_INVALID, "ds_freq_begin_stream: prob_cf is NaN");
@@ -168,10 +164,7 @@ int Freq::begin_stream(int dev, int64_t initial_slots, int32_t batch, double pro
 
 int Freq::open(int dev, int32_t batch, double prob_cf, std::string* err)
 {
-    rows_done = 0; batch_rows = batch; pending = -1; cf = prob_cf;
-    batches = 0; sites = 0; growths = 0; opened_out = nullptr;
-    for (double& v : ms) v = 0;
-    for (double& v : sms) v = 0;
+    batch_rows = batch; cf = prob_cf;
     size_t P = 1;                 // the sort's keys: batch_rows rounded up to a power of two
     while (P < (size_t)batch) P <<= 1;
     DSS_TRY(run.open(dev));
@@ -224,17 +217,17 @@ int Freq::grow(int32_t n, std::string* err)
         return seterr(err, e == hipErrorOutOfMemory ? DS_ERR_NOMEM : DS_ERR_HIP,
                       "ds_freq_push: growing the site table to " + std::to_string(want) + " slots: " + hipGetErrorString(e));
     }
-    dss::book(&sms[1], run.ev[0], run.ev[1]);
+    dss::book(&t.stream.ms[1], run.ev[0], run.ev[1]);
     for (int i = 0; i < 6; ++i) { (void)hipFree(*col[i]); *col[i] = fresh[i]; }      // `run` holds the members' addresses: the new table is its own now
     cap = want;
-    growths += doublings;       // several doublings at once are one rehash
+    t.stream.n[0] += doublings;       // several doublings at once are one rehash
     return DS_OK;
 }
 
 int Freq::push(int32_t n, const int32_t* chrom, const int64_t* pos, const float* act_rows, int32_t class_num, const int32_t* pred, int32_t* status,
                int32_t* opened, std::string* err)
 {
-    if (!run.s || !streaming) return seterr(err, DS_ERR_INVALID, "ds_freq_push: no streaming run is open (ds_freq_begin_stream first)");
+    if (!streaming) return seterr(err, DS_ERR_INVALID, "ds_freq_push: no streaming run is open (ds_freq_begin_stream first)");
     if (pending >= 0) return seterr(err, DS_ERR_INVALID, "ds_freq_push: the previous batch has not been accumulated");
     if (!chrom || !pos || !act_rows || !pred || !status || !opened) return seterr(err, DS_ERR_INVALID, "ds_freq_push: null argument");
     if (n < 1 || n > batch_rows) return seterr(err, DS_ERR_INVALID, "ds_freq_push: nrows must be in [1, batch_rows]");
@@ -254,7 +247,7 @@ int Freq::push(int32_t n, const int32_t* chrom, const int64_t* pos, const float*
     DSS_TRY(hipEventRecord(run.ev[1], s));
     hipLaunchKernelGGL(freq_values_kernel, dim3(blocks(n)), dim3(TPB), 0, s, n, rows.d_chrom, d_pos, d_act, class_num, d_pred, d_p0, d_p1, d_met,
                        rows.d_status);
-    const int rc2 = rows.finish(&run, n, status, &ms[0], &sms[0], err);
+    const int rc2 = rows.finish(&run, n, status, &t.batch.ms[0], &t.stream.ms[0], err);
     if (rc2) return rc2;
     pending = n;
     opened_out = opened;
@@ -264,17 +257,14 @@ int Freq::push(int32_t n, const int32_t* chrom, const int64_t* pos, const float*
 int Freq::parse(const char* text, int32_t n, const int64_t* rb, const int64_t* re, const int32_t* chrom, const uint8_t* flags, int32_t* status,
                 std::string* err)
 {
-    if (!run.s) return seterr(err, DS_ERR_INVALID, "ds_freq_parse: no run is open (ds_freq_begin first)");
     if (streaming) return seterr(err, DS_ERR_INVALID, "ds_freq_parse: the open run is a streaming one (ds_freq_push)");
-    if (pending >= 0) return seterr(err, DS_ERR_INVALID, "ds_freq_parse: the previous batch has not been accumulated");
-    if (!text || !rb || !re || !chrom || !flags || !status) return seterr(err, DS_ERR_INVALID, "ds_freq_parse: null argument");
-    if (n < 1 || n > batch_rows) return seterr(err, DS_ERR_INVALID, "ds_freq_parse: nrows must be in [1, batch_rows]");
-    if (rows_done + n > total_rows) return seterr(err, DS_ERR_INVALID, "ds_freq_parse: more rows than ds_freq_begin was told of");
-    int rc = rows.upload("ds_freq_parse", &run, text, n, rb, re, chrom, flags, err);
+    int rc = can_parse(ROUTE, n, text && rb && re && chrom && flags && status, err);
+    if (rc) return rc;
+    rc = rows.upload("ds_freq_parse", &run, text, n, rb, re, chrom, flags, err);
     if (rc) return rc;
     hipLaunchKernelGGL(freq_parse_kernel, dim3(blocks(n)), dim3(TPB), 0, run.s, rows.text.p, rows.d_off, rows.d_len, rows.d_chrom, rows.d_flags, n, d_pos,
                        d_p0, d_p1, d_met, rows.d_status);
-    rc = rows.finish(&run, n, status, &ms[0], &ms[1], err);
+    rc = rows.finish(&run, n, status, &t.batch.ms[0], &t.batch.ms[1], err);
     if (rc) return rc;
     pending = n;
     return DS_OK;
@@ -283,8 +273,8 @@ int Freq::parse(const char* text, int32_t n, const int64_t* rb, const int64_t* r
 int Freq::accumulate(int32_t m, const int32_t* row, const int32_t* chrom, const int64_t* pos, const double* p0, const double* p1,
                      const int32_t* met, std::string* err)
 {
-    if (!run.s) return seterr(err, DS_ERR_INVALID, "ds_freq_accumulate: no run is open (ds_freq_begin first)");
-    if (pending < 0) return seterr(err, DS_ERR_INVALID, "ds_freq_accumulate: no parsed batch (ds_freq_parse first)");
+    const int ready = can_accumulate(ROUTE, err);
+    if (ready) return ready;
     const int n = pending;
     if (m < 0 || m > n) return seterr(err, DS_ERR_INVALID, "ds_freq_accumulate: nover must be in [0, rows of the batch]");
     if (m > 0 && (!row || !chrom || !pos || !p0 || !p1 || !met)) return seterr(err, DS_ERR_INVALID, "ds_freq_accumulate: null argument");
@@ -320,9 +310,9 @@ int Freq::accumulate(int32_t m, const int32_t* row, const int32_t* chrom, const 
     DSS_TRY(hipEventRecord(run.ev[3], s));
     hipLaunchKernelGGL(freq_accumulate_kernel, dim3(blocks(Pn)), dim3(TPB), 0, s, Pn, u64(d_sort), d_p0, d_p1, d_met, t_sum0, t_sum1, t_met, t_unmet);
     ull c[4] = {0, 0, 0, 0};
-    const int rc = dss::finish_batch(&run, counters, c, &ms[0], &ms[2], &ms[3], err);
+    const int rc = dss::finish_batch(&run, counters, c, &t.batch.ms[0], &t.batch.ms[2], &t.batch.ms[3], err);
     if (rc) return rc;
-    batches += 1;
+    t.batch.n[0] += 1;
     pending = -1;
     opened_out = nullptr;
     rows_done += n;
@@ -333,8 +323,8 @@ int Freq::accumulate(int32_t m, const int32_t* row, const int32_t* chrom, const 
 int64_t Freq::result(int64_t cap_sites, int64_t* first_row, int32_t* chrom, int64_t* pos, double* sum0, double* sum1, int32_t* met, int32_t* unmet,
                      int64_t* nrows, int64_t* used, std::string* err)
 {
-    if (!run.s) return seterr(err, DS_ERR_INVALID, "ds_freq_result: no run is open (ds_freq_begin first)");
-    if (pending >= 0) return seterr(err, DS_ERR_INVALID, "ds_freq_result: a parsed batch has not been accumulated");
+    const int ready = can_result(ROUTE, err);
+    if (ready) return ready;
     DSS_TRY(hipSetDevice(run.device));
     ull c[4] = {0, 0, 0, 0};
     DSS_TRY(hipMemcpy(c, counters, sizeof(c), hipMemcpyDeviceToHost));

@@ -2,7 +2,8 @@
 // open-addressing table of exact 64-bit site keys whose slot is the site id, a bitonic sort of site << 32 | row over a batch, and a
 // walk in which the lane at the head of a site's run adds the run IN ROW ORDER (no floating-point atomics: the order of addition is
 // the contract). Here: the key, the device routines both routes' kernels are built from, and the plain host pieces of a run (its
-// device allocations, its stream and events, a batch's row text, the result's columns). What a site holds is the route's own.
+// device allocations, its stream and events, the call order of its batches, its time tally, a batch's row text, the result's
+// columns); evaluate --on gpu (ds_eval.hip) takes the table, the sort and the host pieces. What a site holds is the route's own.
 // Not part of the public ABI.
 #pragma once
 #include "ds_tsv_device.h"
@@ -143,6 +144,51 @@ struct Run {
 };
 // *ms += the device milliseconds from a to b
 void book(double* ms, hipEvent_t a, hipEvent_t b);
+
+// What a ds_get_*_times getter reports: n[0] = the batches timed (n[1], where there is one, what else was counted) and their summed
+// device milliseconds. A run owns one; the handle owns the sum of the runs ended. take(): this tally with the open run's on top, and
+// on reset both are cleared.
+template <int K, int C = 1>
+struct Times {
+    int64_t n[C] = {};
+    double ms[K] = {};
+    void add(const Times& o)
+    {
+        for (int i = 0; i < C; ++i) n[i] += o.n[i];
+        for (int i = 0; i < K; ++i) ms[i] += o.ms[i];
+    }
+    Times take(int32_t reset, Times* open = nullptr)
+    {
+        Times sum = *this;
+        if (open) sum.add(*open);
+        if (reset) {
+            *this = Times();
+            if (open) *open = Times();
+        }
+        return sum;
+    }
+    int get(int32_t reset, int64_t* count, double* out, Times* open = nullptr)
+    {
+        if (!count || !out) return DS_ERR_INVALID;
+        const Times t = take(reset, open);
+        *count = t.n[0];
+        for (int i = 0; i < K; ++i) out[i] = t.ms[i];
+        return DS_OK;
+    }
+};
+
+// The call order of a run's batches: parse, accumulate, parse, ... and a result only between batches. The checks that open the three
+// calls of `route` ("ds_freq"): DS_OK, or DS_ERR_INVALID with the refusal in *err and nothing changed.
+struct Batches {
+    int64_t total_rows = 0, rows_done = 0;
+    int32_t batch_rows = 0, pending = -1;      // pending = rows parsed, not accumulated
+    // begin(): total_rows in [min_total, 2^30] and batch_rows in [1, 2^24]; no row of the run has been seen
+    int sizes(const char* route, int64_t min_total, int64_t total, int32_t batch, std::string* err);
+    // parse() of n rows; args_ok: none of the call's arrays is null
+    int can_parse(const char* route, int32_t n, bool args_ok, std::string* err) const;
+    int can_accumulate(const char* route, std::string* err) const;
+    int can_result(const char* route, std::string* err) const;
+};
 
 // a buffer that grows to at least `need` bytes, with a quarter of slack; what it held is gone after a growth
 struct Buf {

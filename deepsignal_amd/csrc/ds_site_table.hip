@@ -80,6 +80,37 @@ void book(double* ms, hipEvent_t a, hipEvent_t b)
     if (hipEventElapsedTime(&v, a, b) == hipSuccess) *ms += v; else (void)hipGetLastError();
 }
 
+int Batches::sizes(const char* route, int64_t min_total, int64_t total, int32_t batch, std::string* err)
+{
+    const std::string who = std::string(route) + "_begin: ";
+    if (total < min_total || total > MAX_TOTAL_ROWS) return seterr(err, DS_ERR_INVALID, who + "total_rows must be in [" + std::to_string(min_total) + ", 2^30]");
+    if (batch < 1 || batch > (1 << 24)) return seterr(err, DS_ERR_INVALID, who + "batch_rows must be in [1, 2^24]");
+    total_rows = total; batch_rows = batch;
+    return DS_OK;
+}
+
+int Batches::can_parse(const char* route, int32_t n, bool args_ok, std::string* err) const
+{
+    const std::string who = std::string(route) + "_parse: ";
+    if (pending >= 0) return seterr(err, DS_ERR_INVALID, who + "the previous batch has not been accumulated");
+    if (!args_ok) return seterr(err, DS_ERR_INVALID, who + "null argument");
+    if (n < 1 || n > batch_rows) return seterr(err, DS_ERR_INVALID, who + "nrows must be in [1, batch_rows]");
+    if (rows_done + n > total_rows) return seterr(err, DS_ERR_INVALID, who + "more rows than " + route + "_begin was told of");
+    return DS_OK;
+}
+
+int Batches::can_accumulate(const char* route, std::string* err) const
+{
+    if (pending < 0) return seterr(err, DS_ERR_INVALID, std::string(route) + "_accumulate: no parsed batch (" + route + "_parse first)");
+    return DS_OK;
+}
+
+int Batches::can_result(const char* route, std::string* err) const
+{
+    if (pending >= 0) return seterr(err, DS_ERR_INVALID, std::string(route) + "_result: a parsed batch has not been accumulated");
+    return DS_OK;
+}
+
 hipError_t RowText::alloc(Run* run, size_t B)
 {
     hipError_t e = run->alloc(&d_off, B * 8);

@@ -280,6 +280,31 @@ class FreqNoMemory(RuntimeError):
     """freq_begin: the site table or the batch buffers do not fit the device."""
 
 
+class _TableRun:
+    """What Engine keeps of one table route's run (freq, combine, eval): batch = the batch_rows of the open run (0: none), pending =
+    the rows parsed or pushed and not yet accumulated (-1: none), and the route's extras."""
+
+    def __init__(self, **extras):
+        self.begin(0, **extras)
+
+    def begin(self, batch_rows: int, **extras) -> None:
+        self.batch, self.pending = batch_rows, -1
+        self.__dict__.update(extras)
+
+    def end(self) -> None:
+        self.begin(0)
+
+
+def _run_sizes(total_rows, batch_rows, min_total: int = 1) -> Tuple[int, int]:
+    """The total_rows / batch_rows of a *_begin, as ints in their ranges."""
+    total_rows, batch_rows = int(total_rows), int(batch_rows)
+    if not min_total <= total_rows <= FREQ_MAX_ROWS:
+        raise ValueError("total_rows must be in [%d, 2^30]" % min_total)
+    if not 1 <= batch_rows <= FREQ_MAX_BATCH:
+        raise ValueError("batch_rows must be in [1, 2^24]")
+    return total_rows, batch_rows
+
+
 def freq_locate(text):
     """ds_freq_locate: the rows of a call_mods result buffer (bytes, or a uint8 array such as a memory map) -> (row_begin int64[n],
     row_end int64[n], chrom int32[n], flags uint8[n], names): chrom = the row's chromosome id, an index into `names` (bytes, in
@@ -769,6 +794,8 @@ class Engine:
                  split_dense_min_n: int = 0, split_dense_narrow: bool = False, lstm_xproj=True):
         self._lib = load_library()
         self._h = ctypes.c_void_p()
+        # opened: the array of a freq_push, alive until the library has filled it; words: the combine run's bitmap
+        self._freq, self._combine, self._eval = _TableRun(opened=None), _TableRun(words=0), _TableRun(ncf=1)
         if precision not in PRECISIONS:
             raise ValueError("precision must be one of %s" % (sorted(PRECISIONS),))
         self.precision = precision
@@ -829,6 +856,32 @@ class Engine:
         if rc == -5:
             raise FreqNoMemory(self._lib.ds_last_error(self._h).decode())
         self._check(rc, what)
+
+    def _times(self, fn, what: str, names, counters=("batches",), reset: bool = False) -> dict:
+        """A ds_get_*_times getter: the summed device milliseconds under `names` and the counts under `counters`."""
+        counts = [ctypes.c_int64() for _ in counters]
+        ms = (ctypes.c_double * len(names))()
+        self._check(fn(self._h, int(reset), *(ctypes.byref(c) for c in counts), ms), what)
+        return dict(zip(names, ms), **{k: int(c.value) for k, c in zip(counters, counts)})
+
+    def _run_parse(self, run: _TableRun, fn, what: str, text, begin, end, chrom, flags) -> np.ndarray:
+        """A *_parse: the batch's rows to the library (chrom None: the route's rows name no chromosome) -> the per-row status."""
+        keep, addr, begin, end, ids, flags = _batch_rows_args(text, begin, end, np.zeros(len(begin), np.int32) if chrom is None else chrom,
+                                                              flags, run.batch)
+        n = int(begin.size)
+        status = np.empty(n, np.int32)
+        cols = (flags,) if chrom is None else (ids, flags)
+        self._check(fn(self._h, addr, n, begin.ctypes.data, end.ctypes.data, *(c.ctypes.data for c in cols), status.ctypes.data), what)
+        run.pending = n
+        return status
+
+    @staticmethod
+    def _run_batch(run: _TableRun, route: str, rows: np.ndarray) -> int:
+        """The head of a *_accumulate: the rows of the batch parsed last, of which `rows` must be ascending indices."""
+        if run.pending < 0:
+            raise ValueError("%s_accumulate needs a batch from %s_parse" % (route, route))
+        _check_override_rows(rows, run.pending)
+        return run.pending
 
     def _sites_result(self, fn, what: str, fields, *scalars) -> Dict[str, np.ndarray]:
         """The two calls of ds_freq_result / ds_combine_result: the number of sites, then arrays of that size filled."""
@@ -1112,25 +1165,18 @@ class Engine:
 
     def text_times(self, reset: bool = False) -> dict:
         """ds_get_text_times: device milliseconds of the text batches so far (H2D of the text, the parse kernel, D2H)."""
-        n = ctypes.c_int64()
-        ms = (ctypes.c_double * 3)()
-        self._check(self._lib.ds_get_text_times(self._h, int(reset), ctypes.byref(n), ms), "ds_get_text_times")
-        return dict(zip(("h2d_ms", "kernel_ms", "d2h_ms"), ms), batches=int(n.value))
+        return self._times(self._lib.ds_get_text_times, "ds_get_text_times", ("h2d_ms", "kernel_ms", "d2h_ms"), reset=reset)
 
     # -- per-site modification frequency on the device (ds_freq_*; call_freq --on gpu) ----------
     def freq_begin(self, total_rows: int, batch_rows: int, prob_cf: float = 0.0) -> None:
         """ds_freq_begin: open a run whose batches hold at most batch_rows rows and total_rows rows in all (the site table is
         sized from it, at most half full). FreqNoMemory when the table or the buffers do not fit the device. Needs no weights."""
-        total_rows, batch_rows, prob_cf = int(total_rows), int(batch_rows), float(prob_cf)
-        if not 1 <= total_rows <= FREQ_MAX_ROWS:
-            raise ValueError("total_rows must be in [1, 2^30]")
-        if not 1 <= batch_rows <= FREQ_MAX_BATCH:
-            raise ValueError("batch_rows must be in [1, 2^24]")
+        (total_rows, batch_rows), prob_cf = _run_sizes(total_rows, batch_rows), float(prob_cf)
         if prob_cf != prob_cf:
             raise ValueError("prob_cf must not be NaN")
         rc = self._lib.ds_freq_begin(self._h, total_rows, batch_rows, prob_cf)
         self._check_memory(rc, "ds_freq_begin")
-        self._freq_batch, self._freq_pending = batch_rows, -1
+        self._freq.begin(batch_rows)
 
     def freq_begin_stream(self, initial_slots: int, batch_rows: int, prob_cf: float = 0.0) -> None:
         """ds_freq_begin_stream: open a run whose number of rows is not known: the site table starts with initial_slots slots and
@@ -1144,7 +1190,7 @@ class Engine:
             raise ValueError("prob_cf must not be NaN")
         rc = self._lib.ds_freq_begin_stream(self._h, initial_slots, batch_rows, prob_cf)
         self._check_memory(rc, "ds_freq_begin_stream")
-        self._freq_batch, self._freq_pending, self._freq_opened = batch_rows, -1, None
+        self._freq.begin(batch_rows, opened=None)
 
     def freq_push(self, chrom, pos, act, pred) -> np.ndarray:
         """ds_freq_push: one batch of a streaming run -- chromosome ids, positions (freq_keys, the ids mapped to one numbering for
@@ -1156,13 +1202,13 @@ class Engine:
         n = act.shape[0]
         if chrom.shape != (n,) or pos.shape != (n,) or pred.shape != (n,):
             raise ValueError("chrom / pos / pred must have one entry per act row")
-        if not 1 <= n <= getattr(self, "_freq_batch", 0):
+        if not 1 <= n <= self._freq.batch:
             raise ValueError("a batch holds 1 .. batch_rows rows of an open run")
         status, opened = np.empty(n, np.int32), np.zeros(n, np.int32)
         rc = self._lib.ds_freq_push(self._h, n, chrom.ctypes.data, pos.ctypes.data, act.ctypes.data, act.shape[1], pred.ctypes.data,
                                     status.ctypes.data, opened.ctypes.data)
         self._check_memory(rc, "ds_freq_push")
-        self._freq_pending, self._freq_opened = n, opened        # the library fills `opened` when the batch is accumulated
+        self._freq.pending, self._freq.opened = n, opened        # the library fills `opened` when the batch is accumulated
         return status
 
     def freq_values(self, act) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -1176,21 +1222,12 @@ class Engine:
 
     def freq_stream_times(self, reset: bool = False) -> dict:
         """ds_get_freq_stream_times: device milliseconds of freq_values_kernel and of the table growths, and their number."""
-        n = ctypes.c_int64()
-        ms = (ctypes.c_double * 2)()
-        self._check(self._lib.ds_get_freq_stream_times(self._h, int(reset), ctypes.byref(n), ms), "ds_get_freq_stream_times")
-        return dict(zip(("values_ms", "rehash_ms"), ms), growths=int(n.value))
+        return self._times(self._lib.ds_get_freq_stream_times, "ds_get_freq_stream_times", ("values_ms", "rehash_ms"), ("growths",), reset)
 
     def freq_parse(self, text, begin, end, chrom, flags) -> np.ndarray:
         """ds_freq_parse: one batch of rows (ascending spans of one buffer; chrom / flags per row as freq_locate gives them, the
         ids mapped to one numbering for the whole run) parsed on the GPU -> the per-row status (TEXT_ROW_OK / TEXT_ROW_HOST)."""
-        keep, addr, begin, end, chrom, flags = _batch_rows_args(text, begin, end, chrom, flags, getattr(self, "_freq_batch", 0))
-        n = int(begin.size)
-        status = np.empty(n, np.int32)
-        self._check(self._lib.ds_freq_parse(self._h, addr, n, begin.ctypes.data, end.ctypes.data, chrom.ctypes.data,
-                                            flags.ctypes.data, status.ctypes.data), "ds_freq_parse")
-        self._freq_pending = n
-        return status
+        return self._run_parse(self._freq, self._lib.ds_freq_parse, "ds_freq_parse", text, begin, end, chrom, flags)
 
     def freq_accumulate(self, rows=(), chrom=(), pos=(), p0=(), p1=(), met=()) -> Optional[np.ndarray]:
         """ds_freq_accumulate: add the batch just parsed (or pushed) to the run. rows .. met: the caller's values for the batch's
@@ -1202,18 +1239,15 @@ class Engine:
         m = int(rows.size)
         if any(a.shape != (m,) for a in (chrom, pos, p0, p1, met)):
             raise ValueError("the override arrays must have one length")
-        n = getattr(self, "_freq_pending", -1)
-        if n < 0:
-            raise ValueError("freq_accumulate needs a batch from freq_parse")
-        _check_override_rows(rows, n)
+        self._run_batch(self._freq, "freq", rows)
         if m and (int(chrom.min()) < 0 or int(chrom.max()) >= FREQ_CHROM_LIMIT or int(pos.min()) < 0 or int(pos.max()) >= FREQ_POS_LIMIT):
             raise ValueError("override chromosome ids / positions must fit the key (2^23 ids, pos < 2^40)")
-        self._freq_pending = -1
+        self._freq.pending = -1
         # the library holds the address of `opened` until it has accumulated the batch or the run ends: so does this object
-        opened = getattr(self, "_freq_opened", None)
+        opened = self._freq.opened
         self._check(self._lib.ds_freq_accumulate(self._h, m, rows.ctypes.data, chrom.ctypes.data, pos.ctypes.data, p0.ctypes.data,
                                                  p1.ctypes.data, met.ctypes.data), "ds_freq_accumulate")
-        self._freq_opened = None
+        self._freq.opened = None
         return opened
 
     def freq_result(self) -> Dict[str, np.ndarray]:
@@ -1225,16 +1259,13 @@ class Engine:
         return out
 
     def freq_end(self) -> None:
-        self._freq_batch, self._freq_pending = 0, -1
+        self._freq.end()
         self._check(self._lib.ds_freq_end(self._h), "ds_freq_end")
-        self._freq_opened = None
+        self._freq.opened = None
 
     def freq_times(self, reset: bool = False) -> dict:
         """ds_get_freq_times: device milliseconds of the frequency batches so far (copies, parse kernel, sort, insert + accumulate)."""
-        n = ctypes.c_int64()
-        ms = (ctypes.c_double * 4)()
-        self._check(self._lib.ds_get_freq_times(self._h, int(reset), ctypes.byref(n), ms), "ds_get_freq_times")
-        return dict(zip(("copy_ms", "parse_ms", "sort_ms", "accumulate_ms"), ms), batches=int(n.value))
+        return self._times(self._lib.ds_get_freq_times, "ds_get_freq_times", ("copy_ms", "parse_ms", "sort_ms", "accumulate_ms"), reset=reset)
 
     # -- both strands of a CpG table combined on the device (ds_combine_*; combine_strands --on gpu) ----------
     def combine_begin(self, form: int, rec_len, total_rows: int, batch_rows: int) -> None:
@@ -1242,18 +1273,15 @@ class Engine:
         total_rows rows in all in batches of at most batch_rows. FreqNoMemory when the bitmap, the table or the buffers do not fit
         the device. Needs no weights."""
         rec_len = np.ascontiguousarray(rec_len, np.int64)
-        form, total_rows, batch_rows = int(form), int(total_rows), int(batch_rows)
+        form = int(form)
         if form not in (COMBINE_TABLE, COMBINE_BED):
             raise ValueError("form must be COMBINE_TABLE or COMBINE_BED")
         if rec_len.ndim != 1 or not 1 <= rec_len.size <= FREQ_CHROM_LIMIT or int(rec_len.min()) < 0 or int(rec_len.max()) > FREQ_POS_LIMIT:
             raise ValueError("rec_len must hold 1 .. 2^23 lengths in [0, 2^40]")
-        if not 0 <= total_rows <= FREQ_MAX_ROWS:
-            raise ValueError("total_rows must be in [0, 2^30]")
-        if not 1 <= batch_rows <= FREQ_MAX_BATCH:
-            raise ValueError("batch_rows must be in [1, 2^24]")
+        total_rows, batch_rows = _run_sizes(total_rows, batch_rows, 0)
         rc = self._lib.ds_combine_begin(self._h, form, rec_len.size, rec_len.ctypes.data, total_rows, batch_rows)
         self._check_memory(rc, "ds_combine_begin")
-        self._combine_batch, self._combine_pending, self._combine_words = batch_rows, -1, (int(rec_len.sum()) + 31) // 32
+        self._combine.begin(batch_rows, words=(int(rec_len.sum()) + 31) // 32)
 
     def combine_genome(self, text, seg_begin, seg_end, seg_bit, seg_carry) -> None:
         """ds_combine_genome: one chunk of the FASTA (segments ascending and disjoint, at most 2^30 bytes from the first begin to the
@@ -1267,20 +1295,14 @@ class Engine:
 
     def combine_bitmap(self) -> np.ndarray:
         """ds_combine_bitmap: the run's bitmap, uint32[(bases + 31) // 32]; what motif_reference gives on the CPU."""
-        out = np.zeros(getattr(self, "_combine_words", 0), np.uint32)
+        out = np.zeros(self._combine.words, np.uint32)
         self._check(self._lib.ds_combine_bitmap(self._h, out.size, out.ctypes.data if out.size else None), "ds_combine_bitmap")
         return out
 
     def combine_parse(self, text, begin, end, chrom, flags) -> np.ndarray:
         """ds_combine_parse: one batch of rows (ascending spans of one buffer; chrom = the record column 0 names, -1 for none; flags
         as freq_locate gives them) -> the per-row status (TEXT_ROW_OK / TEXT_ROW_HOST / COMBINE_ROW_SKIP)."""
-        keep, addr, begin, end, chrom, flags = _batch_rows_args(text, begin, end, chrom, flags, getattr(self, "_combine_batch", 0))
-        n = int(begin.size)
-        status = np.empty(n, np.int32)
-        self._check(self._lib.ds_combine_parse(self._h, addr, n, begin.ctypes.data, end.ctypes.data, chrom.ctypes.data, flags.ctypes.data,
-                                               status.ctypes.data), "ds_combine_parse")
-        self._combine_pending = n
-        return status
+        return self._run_parse(self._combine, self._lib.ds_combine_parse, "ds_combine_parse", text, begin, end, chrom, flags)
 
     def combine_accumulate(self, rows=(), given=()) -> None:
         """ds_combine_accumulate: add the batch just parsed to the run. rows: the ascending batch indices of every TEXT_ROW_HOST
@@ -1289,17 +1311,14 @@ class Engine:
         m = int(rows.size)
         if len(given) != m:
             raise ValueError("one entry of `given` per override row")
-        n = getattr(self, "_combine_pending", -1)
-        if n < 0:
-            raise ValueError("combine_accumulate needs a batch from combine_parse")
-        _check_override_rows(rows, n)
+        self._run_batch(self._combine, "combine", rows)
         status = np.array([COMBINE_ROW_SKIP if v is None else TEXT_ROW_OK for v in given], np.int32)
         vals = [(0, 0, 0, 0.0, 0.0, 0, 0, 0) if v is None else v for v in given]
         if any(abs(int(c)) >= COMBINE_COUNT_LIMIT for v in vals for c in v[5:8]):
             raise ValueError("override counts must be below 2^32 in magnitude")
         cols = [np.ascontiguousarray([v[k] for v in vals], dt) for k, dt in enumerate((np.int32, np.int64, np.int32, np.float64, np.float64,
                                                                                          np.int64, np.int64, np.int64))]
-        self._combine_pending = -1
+        self._combine.pending = -1
         self._check(self._lib.ds_combine_accumulate(self._h, m, rows.ctypes.data, status.ctypes.data, *(c.ctypes.data for c in cols)),
                     "ds_combine_accumulate")
 
@@ -1312,65 +1331,49 @@ class Engine:
         return out
 
     def combine_end(self) -> None:
-        self._combine_batch, self._combine_pending = 0, -1
+        self._combine.end()
         self._check(self._lib.ds_combine_end(self._h), "ds_combine_end")
 
     def combine_times(self, reset: bool = False) -> dict:
         """ds_get_combine_times: device milliseconds of the combine runs so far (copies, motif kernel, parse kernel, sort, insert +
         accumulate), the genome chunks and the batches."""
-        c, n = ctypes.c_int64(), ctypes.c_int64()
-        ms = (ctypes.c_double * 5)()
-        self._check(self._lib.ds_get_combine_times(self._h, int(reset), ctypes.byref(c), ctypes.byref(n), ms), "ds_get_combine_times")
-        return dict(zip(("copy_ms", "motif_ms", "parse_ms", "sort_ms", "accumulate_ms"), ms), chunks=int(c.value), batches=int(n.value))
+        return self._times(self._lib.ds_get_combine_times, "ds_get_combine_times", ("copy_ms", "motif_ms", "parse_ms", "sort_ms", "accumulate_ms"),
+                           ("chunks", "batches"), reset)
 
     # -- call accuracy and AUROC of labelled call rows on the device (ds_eval_*; evaluate --on gpu) ----------
     def eval_begin(self, total_rows: int, batch_rows: int, cf) -> None:
         """ds_eval_begin: open a run of total_rows rows in all in batches of at most batch_rows, with the cut-offs cf (1 .. 32
         doubles). FreqNoMemory when the score table or the buffers do not fit the device. Needs no weights."""
-        total_rows, batch_rows, cf = int(total_rows), int(batch_rows), _eval_cutoffs(cf)
-        if not 1 <= total_rows <= FREQ_MAX_ROWS:
-            raise ValueError("total_rows must be in [1, 2^30]")
-        if not 1 <= batch_rows <= FREQ_MAX_BATCH:
-            raise ValueError("batch_rows must be in [1, 2^24]")
+        cf = _eval_cutoffs(cf)
+        total_rows, batch_rows = _run_sizes(total_rows, batch_rows)
         rc = self._lib.ds_eval_begin(self._h, total_rows, batch_rows, cf.size, cf.ctypes.data)
         self._check_memory(rc, "ds_eval_begin")
-        self._eval_batch, self._eval_pending, self._eval_ncf = batch_rows, -1, int(cf.size)
+        self._eval.begin(batch_rows, ncf=int(cf.size))
 
     def eval_parse(self, text, begin, end, flags) -> np.ndarray:
         """ds_eval_parse: one batch of rows (ascending spans of one buffer; flags as eval_locate gives them) -> the per-row status
         (TEXT_ROW_OK / TEXT_ROW_HOST)."""
-        keep, addr, begin, end, _, flags = _batch_rows_args(text, begin, end, np.zeros(len(begin), np.int32), flags,
-                                                            getattr(self, "_eval_batch", 0))
-        n = int(begin.size)
-        status = np.empty(n, np.int32)
-        self._check(self._lib.ds_eval_parse(self._h, addr, n, begin.ctypes.data, end.ctypes.data, flags.ctypes.data, status.ctypes.data),
-                    "ds_eval_parse")
-        self._eval_pending = n
-        return status
+        return self._run_parse(self._eval, self._lib.ds_eval_parse, "ds_eval_parse", text, begin, end, None, flags)
 
     def eval_accumulate(self, mask, rows=(), p0=(), p1=(), called=()) -> None:
         """ds_eval_accumulate: add the batch just parsed to the run. mask: a byte per row of the batch (EVAL_SET_SAMPLE |
         EVAL_SET_ALL | EVAL_TRUTH). rows .. called: the caller's values for the batch's TEXT_ROW_HOST rows (ascending batch row
         indices, every such row; called = a non-zero label)."""
-        n = getattr(self, "_eval_pending", -1)
-        if n < 0:
-            raise ValueError("eval_accumulate needs a batch from eval_parse")
-        mask = _eval_mask(mask, n)
         rows = np.ascontiguousarray(rows, np.int32)
+        mask = _eval_mask(mask, self._run_batch(self._eval, "eval", rows))
         p0, p1 = np.ascontiguousarray(p0, np.float64), np.ascontiguousarray(p1, np.float64)
         called = np.ascontiguousarray(np.asarray(called) != 0, np.int32)
         m = int(rows.size)
         if not (p0.shape == p1.shape == called.shape == (m,)):
             raise ValueError("one value of each kind per override row")
-        _check_override_rows(rows, n)
-        self._eval_pending = -1
+        self._eval.pending = -1
         self._check(self._lib.ds_eval_accumulate(self._h, mask.ctypes.data, m, rows.ctypes.data, p0.ctypes.data, p1.ctypes.data,
                                                  called.ctypes.data), "ds_eval_accumulate")
 
     def eval_result(self) -> dict:
         """ds_eval_result: counts int64[2, 4 + 2 ncf] (tp, fp, tn, fn, called per cut-off, correct per cut-off; set 0 the sample, set 1
         all), per set u2 / p / n over the rows with a finite prob_1, and the scalars rows (accumulated) and distinct (scores)."""
-        counts, u2, pn, nn = _eval_result(getattr(self, "_eval_ncf", 1))
+        counts, u2, pn, nn = _eval_result(self._eval.ncf)
         rows, distinct = ctypes.c_int64(), ctypes.c_int64()
         self._check(self._lib.ds_eval_result(self._h, counts.ctypes.data, u2.ctypes.data, pn.ctypes.data, nn.ctypes.data, ctypes.byref(rows),
                                              ctypes.byref(distinct)), "ds_eval_result")
@@ -1378,23 +1381,17 @@ class Engine:
                     distinct=int(distinct.value))
 
     def eval_end(self) -> None:
-        self._eval_batch, self._eval_pending = 0, -1
+        self._eval.end()
         self._check(self._lib.ds_eval_end(self._h), "ds_eval_end")
 
     def eval_times(self, reset: bool = False) -> dict:
         """ds_get_eval_times: device milliseconds of the evaluate runs so far (copies, parse kernel, count + insert kernels, the
         result's sort / scan / reduction) and the batches."""
-        n = ctypes.c_int64()
-        ms = (ctypes.c_double * 4)()
-        self._check(self._lib.ds_get_eval_times(self._h, int(reset), ctypes.byref(n), ms), "ds_get_eval_times")
-        return dict(zip(("copy_ms", "parse_ms", "count_ms", "result_ms"), ms), batches=int(n.value))
+        return self._times(self._lib.ds_get_eval_times, "ds_get_eval_times", ("copy_ms", "parse_ms", "count_ms", "result_ms"), reset=reset)
 
     def rows_times(self, reset: bool = False) -> dict:
         """ds_get_rows_times: device milliseconds of the extract_rows() calls made while profiling was on."""
-        n = ctypes.c_int64()
-        ms = (ctypes.c_double * 5)()
-        self._check(self._lib.ds_get_rows_times(self._h, int(reset), ctypes.byref(n), ms), "ds_get_rows_times")
-        return dict(zip(("stats_ms", "values_ms", "length_ms", "format_ms", "d2h_ms"), ms), batches=int(n.value))
+        return self._times(self._lib.ds_get_rows_times, "ds_get_rows_times", ("stats_ms", "values_ms", "length_ms", "format_ms", "d2h_ms"), reset=reset)
 
     # -- cascaded precision (ds_set_recheck) ---------------------------------------------------
     def set_recheck(self, fine: Optional["Engine"], margin: float, own: bool = False) -> None:
@@ -1419,9 +1416,7 @@ class Engine:
 
     def recheck_times(self, reset: bool = False) -> dict:
         """ds_get_recheck_times: device milliseconds of the selection kernel over the run() calls made while profiling was on."""
-        n, ms = ctypes.c_int64(), ctypes.c_double()
-        self._check(self._lib.ds_get_recheck_times(self._h, int(reset), ctypes.byref(n), ctypes.byref(ms)), "ds_get_recheck_times")
-        return {"launches": int(n.value), "select_ms": float(ms.value)}
+        return self._times(self._lib.ds_get_recheck_times, "ds_get_recheck_times", ("select_ms",), ("launches",), reset)
 
     def recheck_select(self, act, margin: float) -> np.ndarray:
         """ds_recheck_select (diagnostic): the ascending indices the selection kernel picks for the given act rows."""

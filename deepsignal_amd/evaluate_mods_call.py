@@ -30,8 +30,8 @@ if __package__ in (None, ""):                       # run as a script: the packa
     import deepsignal_amd  # noqa: F401
     __package__ = "deepsignal_amd"
 
-from .call_modification_frequency import _CpuRoute
-from .combine_strands import _map_file
+from . import table_route as tr
+from .table_route import _CpuRoute
 
 NUM_SITES = 100000                                  # the script's num_sites[0]
 PROB_CFS = numpy.arange(0, 0.70, 0.025)             # the script's own doubles: 0.075 is not the literal
@@ -210,18 +210,15 @@ def _python_fields(raw: bytes) -> List[str]:
     return "".join(io.TextIOWrapper(io.BytesIO(raw + b"\n"))).rstrip().split()
 
 
-class _Calls:
+class _Calls(tr.RowFile):
     """One input file of the gpu route: its bytes, the row spans and the per-row flags."""
 
     def __init__(self, path: str, eng):
-        self.keep, self.data = _map_file(path)
-        self.begin, self.end, self.flags, file_flags = eng.eval_locate(self.data)
+        tr.RowFile.__init__(self, path)
+        begin, end, flags, file_flags = eng.eval_locate(self.data)
         if file_flags & eng.EVAL_BARE_CR:
             raise _CpuRoute("%s holds a bare carriage return, which ends a line in Python's text mode" % path)
-        self.n = int(self.begin.size)
-
-    def row_bytes(self, i: int) -> bytes:
-        return self.data[int(self.begin[i]):int(self.end[i])].tobytes()
+        self.set_rows(begin, end, flags)
 
 
 def evaluate_gpu(unmethylated: str, methylated: str, result_file: str, num_sites: int = NUM_SITES, rng=random, device: int = 0,
@@ -231,8 +228,7 @@ def evaluate_gpu(unmethylated: str, methylated: str, result_file: str, num_sites
     why. `info`, when given, receives host_rows, rows and the device times. make_engine: what provides eval_begin .. eval_end
     (default: an Engine on `device`; the tests put the CPU checker behind it)."""
     from . import engine as eng
-    if not 1 <= batch_rows <= eng.FREQ_MAX_BATCH:
-        raise ValueError("batch_rows must be in [1, 2^24]")
+    tr.check_batch_rows(batch_rows)
     files = [_Calls(path, eng) for path in (unmethylated, methylated)]
     total = files[0].n + files[1].n
     if total > eng.FREQ_MAX_ROWS:
@@ -240,13 +236,9 @@ def evaluate_gpu(unmethylated: str, methylated: str, result_file: str, num_sites
     host_rows, times = 0, {}
     sets: List[Optional[SetStats]] = [None, None]
     if total:
-        # the ds_eval_* calls need no weights, but they hang off a handle: the smallest one, as call_freq --on gpu
-        e = make_engine() if make_engine is not None else eng.Engine(device=device, max_batch=64, slots=1)
-        try:
-            try:
+        with tr.small_engine(make_engine, device) as e:
+            with tr.fits("the score table of %d rows does not fit the device" % total):
                 e.eval_begin(total, min(batch_rows, total), PROB_CFS)
-            except eng.FreqNoMemory as exc:
-                raise _CpuRoute("the score table of %d rows does not fit the device (%s)" % (total, exc))
             picks = sample_rows(files[0].n, files[1].n, num_sites, rng)
             finite = [True, True]                     # per set: no NaN or infinite prob_1 among the rows read here
             set_bits = (eng.EVAL_SET_SAMPLE, eng.EVAL_SET_ALL)
@@ -254,27 +246,20 @@ def evaluate_gpu(unmethylated: str, methylated: str, result_file: str, num_sites
                 # a row's byte: in the _N sample, in all_sites, from --methylated
                 mask = numpy.full(f.n, eng.EVAL_SET_ALL | truth, numpy.uint8)
                 mask[pick] |= eng.EVAL_SET_SAMPLE
-                for s in range(0, f.n, batch_rows):
-                    t = min(f.n, s + batch_rows)
-                    status = e.eval_parse(f.data, f.begin[s:t], f.end[s:t], f.flags[s:t])
-                    o_row, o_p0, o_p1, o_lab = [], [], [], []
-                    for i in numpy.flatnonzero(status != eng.TEXT_ROW_OK).tolist():
-                        prob_0, prob_1, label = row_values(_python_fields(f.row_bytes(s + i)))
-                        if not math.isfinite(prob_1):
-                            for k, bit in enumerate(set_bits):
-                                if mask[s + i] & bit:
-                                    finite[k] = False
-                        o_row.append(i); o_p0.append(prob_0); o_p1.append(prob_1); o_lab.append(int(label != 0))
-                    e.eval_accumulate(mask[s:t], o_row, o_p0, o_p1, o_lab)
-                    host_rows += len(o_row)
+
+                def host_row(row: int, _status: int):
+                    prob_0, prob_1, label = row_values(_python_fields(f.row_bytes(row)))
+                    if not math.isfinite(prob_1):
+                        for k, bit in enumerate(set_bits):
+                            if mask[row] & bit:
+                                finite[k] = False
+                    return prob_0, prob_1, int(label != 0)
+
+                host_rows += tr.walk(f.n, batch_rows, lambda s, t: e.eval_parse(f.data, f.begin[s:t], f.end[s:t], f.flags[s:t]), host_row,
+                                     lambda s, t, rows, values: e.eval_accumulate(mask[s:t], rows, *tr.columns(values, 3)))
                 print(MSG_TOTAL.format(f.n))
-            res = e.eval_result()
-            times = e.eval_times()
-            e.eval_end()
-        finally:
-            e.close()
-        if res["rows"] != total:
-            raise RuntimeError("gpu route: %d rows accumulated, %d located" % (res["rows"], total))
+            res, times = tr.finish(e, "eval")
+        tr.check_rows(res, total)
         ncf = len(PROB_CFS)
         for k in range(2):
             c = res["counts"][k]

@@ -9,6 +9,8 @@ import numpy as np
 from deepsignal_amd import combine_strands as cs
 from deepsignal_amd import engine as eng
 
+from table_backend import RememberedBatches
+
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "combine_golden.json")
 KMER = "ACGTACGTCGACGTACG"
 
@@ -115,17 +117,15 @@ def python_bitmap(seqs) -> np.ndarray:
     return np.packbits(bits.reshape(-1, 32)[:, ::-1], axis=1).view(">u4").astype(np.uint32).ravel()
 
 
-class CheckerBackend:
+class CheckerBackend(RememberedBatches):
     """combine_begin .. combine_end of Engine on top of ds_motif_reference and ds_combine_reference: the chunks go into a host
     bitmap as they come, the batches are remembered, and the checker makes its one pass in row order over all of them when the
     result is asked for."""
 
-    def __init__(self):
-        self.batches = []
-
     def combine_begin(self, form, rec_len, total_rows, batch_rows):
-        self.form, self.rec_len, self.total, self.batch = form, np.array(rec_len, np.int64), total_rows, batch_rows
-        self.nbits, self.batches = int(self.rec_len.sum()), []
+        self.begun(total_rows, batch_rows)
+        self.form, self.rec_len = form, np.array(rec_len, np.int64)
+        self.nbits = int(self.rec_len.sum())
         self.bitmap = np.zeros((self.nbits + 31) // 32, np.uint32)
 
     def combine_genome(self, text, seg_begin, seg_end, seg_bit, seg_carry):
@@ -137,38 +137,21 @@ class CheckerBackend:
         return self.bitmap.copy()
 
     def combine_parse(self, text, begin, end, chrom, flags):
-        assert 1 <= len(begin) <= self.batch
-        lo, hi = int(begin[0]), int(end[-1])
-        chunk = np.asarray(text[lo:hi]).tobytes()
-        b, e = np.asarray(begin, np.int64) - lo, np.asarray(end, np.int64) - lo
-        status = eng.combine_reference(self.form, chunk, b, e, chrom, flags, self.rec_len, self.bitmap, sites=False)["status"]
-        self.batches.append([chunk, b, e, np.array(chrom, np.int32), np.array(flags, np.uint8), {}])
-        return status
+        chunk, b, e = self.remember(text, begin, end, chrom=np.array(chrom, np.int32), flags=np.array(flags, np.uint8))
+        return eng.combine_reference(self.form, chunk, b, e, chrom, flags, self.rec_len, self.bitmap, sites=False)["status"]
 
     def combine_accumulate(self, rows=(), given=()):
-        self.batches[-1][5] = {int(r): v for r, v in zip(rows, given)}
+        self.give({int(r): v for r, v in zip(rows, given)})
 
     def combine_result(self):
-        text, begin, end, chrom, flags, given, off, row = [], [], [], [], [], {}, 0, 0
-        for chunk, b, e, c, f, g in self.batches:
-            text.append(chunk); begin.append(b + off); end.append(e + off); chrom.append(c); flags.append(f)
-            given.update({row + r: v for r, v in g.items()})
-            off += len(chunk); row += len(b)
-        out = eng.combine_reference(self.form, b"".join(text), np.concatenate(begin), np.concatenate(end), np.concatenate(chrom),
-                                    np.concatenate(flags), self.rec_len, self.bitmap, given)
+        text, begin, end, (chrom, flags), given, row = self.joined("chrom", "flags")
+        out = eng.combine_reference(self.form, text, begin, end, chrom, flags, self.rec_len, self.bitmap, given)
         assert not (out["status"] == eng.TEXT_ROW_HOST).any(), "a host row got no values"
         res = {k: out[k] for k in ("chrom", "pos", "sum0", "sum1", "met", "unmet", "cov", "last_plus")}
         res["rows"] = row
         return res
 
-    def combine_times(self, reset=False):
-        return {}
-
-    def combine_end(self):
-        pass
-
-    def close(self):
-        pass
+    combine_times, combine_end = RememberedBatches.times, RememberedBatches.close
 
 
 def run_route(tmp_path, capsys, inp, fa, on, contig="", **kw):

@@ -8,6 +8,8 @@ import numpy as np
 from deepsignal_amd import engine as eng
 from deepsignal_amd import evaluate_mods_call as ev
 
+from table_backend import RememberedBatches
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 KMER = "ACGTACGTCGACGTACG"
 SUBSAMPLE_SEED = 7                                   # random.seed of the reference run, --seed of ours
@@ -73,46 +75,26 @@ def run_route(tmp_path, capsys, paths, on, seed=None, num_sites=ev.NUM_SITES, **
         return f.read(), capsys.readouterr().out
 
 
-class CheckerBackend:
+class CheckerBackend(RememberedBatches):
     """eval_begin .. eval_end of Engine on top of ds_eval_reference: the batches are remembered and the checker makes its one pass
     over all of them when the result is asked for."""
 
-    def __init__(self):
-        self.batches = []
-
     def eval_begin(self, total_rows, batch_rows, cf):
-        self.total, self.batch, self.cf, self.batches = total_rows, batch_rows, np.array(cf, np.float64), []
+        self.begun(total_rows, batch_rows)
+        self.cf = np.array(cf, np.float64)
 
     def eval_parse(self, text, begin, end, flags):
-        assert 1 <= len(begin) <= self.batch
-        lo, hi = int(begin[0]), int(end[-1])
-        chunk = np.asarray(text[lo:hi]).tobytes()
-        b, e = np.asarray(begin, np.int64) - lo, np.asarray(end, np.int64) - lo
-        status = eng.eval_reference(chunk, b, e, flags, np.zeros(len(b), np.uint8), self.cf)["status"]
-        self.batches.append([chunk, b, e, np.array(flags, np.uint8), None, {}])
-        return status
+        chunk, b, e = self.remember(text, begin, end, flags=np.array(flags, np.uint8))
+        return eng.eval_reference(chunk, b, e, flags, np.zeros(len(b), np.uint8), self.cf)["status"]
 
     def eval_accumulate(self, mask, rows=(), p0=(), p1=(), label=()):
-        assert len(mask) == len(self.batches[-1][1])
-        self.batches[-1][4] = np.array(mask, np.uint8)
-        self.batches[-1][5] = {int(r): (a, b, c) for r, a, b, c in zip(rows, p0, p1, label)}
+        assert len(mask) == len(self.batches[-1]["begin"])
+        self.give({int(r): (a, b, c) for r, a, b, c in zip(rows, p0, p1, label)}, mask=np.array(mask, np.uint8))
 
     def eval_result(self):
-        text, begin, end, flags, mask, given, off, row = [], [], [], [], [], {}, 0, 0
-        for chunk, b, e, f, m, g in self.batches:
-            text.append(chunk); begin.append(b + off); end.append(e + off); flags.append(f); mask.append(m)
-            given.update({row + r: v for r, v in g.items()})
-            off += len(chunk); row += len(b)
-        out = eng.eval_reference(b"".join(text), np.concatenate(begin), np.concatenate(end), np.concatenate(flags), np.concatenate(mask),
-                                 self.cf, given)
+        text, begin, end, (flags, mask), given, row = self.joined("flags", "mask")
+        out = eng.eval_reference(text, begin, end, flags, mask, self.cf, given)
         assert not (out["status"] == eng.TEXT_ROW_HOST).any(), "a host row got no values"
         return {"counts": out["counts"], "u2": out["u2"], "p": out["p"], "n": out["n"], "rows": row}
 
-    def eval_times(self, reset=False):
-        return {}
-
-    def eval_end(self):
-        pass
-
-    def close(self):
-        pass
+    eval_times, eval_end = RememberedBatches.times, RememberedBatches.close

@@ -6,6 +6,8 @@ import numpy as np
 
 from deepsignal_amd import engine as eng
 
+from table_backend import RememberedBatches
+
 KMER = "ACGTACGTCGACGTACG"
 
 
@@ -43,47 +45,26 @@ def stats_tuple(stats):
             for k, s in stats.items()]
 
 
-class ReferenceBackend:
+class ReferenceBackend(RememberedBatches):
     """freq_begin .. freq_end of Engine on top of ds_freq_reference: the batches are remembered and the checker makes its one
     pass in row order over all of them when the result is asked for."""
 
-    def __init__(self):
-        self.batches = []
-        self.cf = 0.0
-
     def freq_begin(self, total_rows, batch_rows, prob_cf=0.0):
-        self.total, self.batch, self.cf = total_rows, batch_rows, prob_cf
+        self.begun(total_rows, batch_rows)
+        self.cf = prob_cf
 
     def freq_parse(self, text, begin, end, chrom, flags):
-        assert 1 <= len(begin) <= self.batch
-        lo, hi = int(begin[0]), int(end[-1])
-        chunk = np.asarray(text[lo:hi]).tobytes()
-        b, e = np.asarray(begin, np.int64) - lo, np.asarray(end, np.int64) - lo
-        status = eng.freq_reference(chunk, b, e, chrom, flags, self.cf)["status"]
-        self.batches.append([chunk, b, e, np.array(chrom, np.int32), np.array(flags, np.uint8), {}])
-        return status
+        chunk, b, e = self.remember(text, begin, end, chrom=np.array(chrom, np.int32), flags=np.array(flags, np.uint8))
+        return eng.freq_reference(chunk, b, e, chrom, flags, self.cf)["status"]
 
     def freq_accumulate(self, rows=(), chrom=(), pos=(), p0=(), p1=(), met=()):
-        self.batches[-1][5] = {int(r): (int(c), int(q), float(a), float(b), int(m))
-                               for r, c, q, a, b, m in zip(rows, chrom, pos, p0, p1, met)}
+        self.give({int(r): (int(c), int(q), float(a), float(b), int(m)) for r, c, q, a, b, m in zip(rows, chrom, pos, p0, p1, met)})
 
     def freq_result(self):
-        text, begin, end, chrom, flags, given, off, row = [], [], [], [], [], {}, 0, 0
-        for chunk, b, e, c, f, g in self.batches:
-            text.append(chunk); begin.append(b + off); end.append(e + off); chrom.append(c); flags.append(f)
-            given.update({row + r: v for r, v in g.items()})
-            off += len(chunk); row += len(b)
-        out = eng.freq_reference(b"".join(text), np.concatenate(begin), np.concatenate(end), np.concatenate(chrom),
-                                 np.concatenate(flags), self.cf, given)
+        text, begin, end, (chrom, flags), given, row = self.joined("chrom", "flags")
+        out = eng.freq_reference(text, begin, end, chrom, flags, self.cf, given)
         assert not (out["status"] != eng.TEXT_ROW_OK).any(), "a host row got no values"
         return {"first_row": out["first_row"], "chrom": out["chrom"], "pos": out["pos"], "sum0": out["sum0"], "sum1": out["sum1"],
                 "met": out["met"], "unmet": out["unmet"], "rows": row, "used": out["used"]}
 
-    def freq_times(self, reset=False):
-        return {}
-
-    def freq_end(self):
-        pass
-
-    def close(self):
-        pass
+    freq_times, freq_end = RememberedBatches.times, RememberedBatches.close
