@@ -10,6 +10,7 @@
 #include "ds_combine.h"
 #include "ds_eval.h"
 #include "ds_train.h"
+#include "ds_train_signal.h"
 
 #include <algorithm>
 #include <cmath>
@@ -272,12 +273,14 @@ struct ds_handle {
     TableRuns<dsf::Freq> freq;            // call_freq --on gpu (ds_freq_begin | ds_freq_begin_stream .. ds_freq_end)
     TableRuns<dsc::Combine> combine;      // combine_strands --on gpu (ds_combine_begin .. ds_combine_end)
     TableRuns<dse::Eval> eval;            // evaluate --on gpu (ds_eval_begin .. ds_eval_end)
-    // training (ds_train_begin .. ds_train_end, ds_train.hip): the RNN-only variants (is_base 0 and 1) keep the tensors they were loaded with
+    // training (ds_train_begin .. ds_train_end, ds_train.hip; ds_train_begin_signal, ds_train_signal.hip): the RNN-only variants (is_base 0
+    // and 1) and the signal-only variant keep the tensors they were loaded with
     // (`kept`: what ds_train_begin starts from and ds_train_set_tensor replaces) and remembers which device blocks hold the packed
     // weights (`weight_allocs`), so that ds_train_sync_weights can pack the current parameters in their place
     std::map<std::string, HostTensor> kept;
     std::vector<void*> weight_allocs;
     dstr::Trainer* train = nullptr;
+    dsts::Trainer* strain = nullptr;      // the signal-only variant's run (ds_train_begin_signal, ds_train_signal.hip): one of the two at most
     bool training = false;
     // pipelining: consecutive forwards rotate over independent slots (own workspace, streams, graphs), so the
     // dependency chain of one 512-site forward overlaps the next ones'; weights are shared
@@ -755,7 +758,7 @@ int finalize_weights(ds_handle* h)
         if ((rc = upload(h, &h->fc2, w2->data))) return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->cur->s0));
-    if (h->is_rnn && !h->is_cnn) h->kept = h->host;      // the trainable variants (ds_train_begin, ds_train_begin_base)
+    if (h->is_rnn != h->is_cnn) h->kept = h->host;       // the trainable variants (ds_train_begin, ds_train_begin_base, ds_train_begin_signal)
     h->host.clear();
     h->finalized = true;
     return DS_OK;
@@ -1616,7 +1619,7 @@ extern "C" {
 
 const char* ds_version(void)
 {
-    return "deepsignal_amd 0.4 (gfx950; fp32 MFMA, bf16 conv + FC and bf16_all operand modes; bf16x3 = fp32 operands as three bf16 "
+    return "deepsignal_amd 0.5 (gfx950; fp32 MFMA, bf16 conv + FC and bf16_all operand modes; bf16x3 = fp32 operands as three bf16 "
            "terms, six products per MAC, in: conv_layer2 / 3, the eleven inception modules, the BiLSTM cells' recurrent and lower-layer products, dense(J, J) of the three-step "
            "joint model; fp16x2 = the same scope on two fp16 terms, three products per MAC, operands within +-65504)";
 }
@@ -1748,6 +1751,7 @@ void ds_destroy(ds_handle* h)
     h->combine.close();
     h->eval.close();
     delete h->train;
+    delete h->strain;
     for (void* p : h->allocs) hipFree(p);
     (void)hipGetLastError();      // nothing a teardown call returned may surface in a later handle's first launch
     delete h;
@@ -3252,7 +3256,7 @@ int ds_set_graph(ds_handle* h, int32_t enable)
 static int train_ready(ds_handle* h, const char* who)
 {
     if (!h) return DS_ERR_INVALID;
-    if (!h->train || !h->training) return fail(h, DS_ERR_INVALID, std::string(who) + ": no training run is open (ds_train_begin first)");
+    if ((!h->train && !h->strain) || !h->training) return fail(h, DS_ERR_INVALID, std::string(who) + ": no training run is open (ds_train_begin first)");
     if (tickets_in_flight(h)) return fail(h, DS_ERR_INVALID, std::string(who) + ": pipeline tickets are still in flight");
     return DS_OK;
 }
@@ -3299,7 +3303,13 @@ static int ds_train_begin_impl(ds_handle* h, const ds_train_config* cfg, bool wi
 static int ds_train_set_tensor_impl(ds_handle* h, const char* name, const float* data, int64_t count)
 {
     if (!h || !name || !data) return fail(h, DS_ERR_INVALID, "ds_train_set_tensor: bad argument");
-    if (!h->finalized || h->kept.empty()) return fail(h, DS_ERR_INVALID, "ds_train_set_tensor: the handle holds no trainable weights (RNN-only, loaded)");
+    if (!h->finalized || h->kept.empty()) return fail(h, DS_ERR_INVALID, "ds_train_set_tensor: the handle holds no trainable weights (RNN-only or signal-only, loaded)");
+    if (h->is_cnn) {      // the signal-only variant: any tensor it was loaded with, moving statistics included
+        auto it = h->kept.find(name);
+        if (it == h->kept.end() || count != (int64_t)it->second.data.size()) return fail(h, DS_ERR_INVALID, std::string("ds_train_set_tensor: unknown tensor or wrong size: ") + name);
+        it->second.data.assign(data, data + count);
+        return DS_OK;
+    }
     const int idx = dstr::tensor_index(name), in0 = dstr::in0_of(h->is_base);
     if (idx < 0 || idx >= dstr::ntensor(in0) || count != dstr::tensor_floats(idx, in0)) return fail(h, DS_ERR_INVALID, std::string("ds_train_set_tensor: unknown tensor or wrong size: ") + name);
     h->kept[name].data.assign(data, data + count);
@@ -3312,6 +3322,7 @@ static int ds_train_step_impl(ds_handle* h, const char* who, bool eval, int32_t 
 {
     const std::string me = who;
     if (int rc = train_ready(h, who)) return rc;
+    if (!h->train) return fail(h, DS_ERR_INVALID, me + ": this run trains the signal model (is_cnn 1, is_rnn 0): ds_train_step_signal / ds_train_eval_signal");
     if (n < 1 || n > h->B) return fail(h, DS_ERR_INVALID, me + ": n must lie in [1, max_batch]");
     if (!means || !stds || !sanums || !labels) return fail(h, DS_ERR_INVALID, me + ": null buffer");
     if (h->train->in0 != dstr::NFEAT && !kmer)
@@ -3328,10 +3339,12 @@ static int ds_train_sync_weights_impl(ds_handle* h)
 {
     if (int rc = train_ready(h, "ds_train_sync_weights")) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int in0 = h->train->in0;
-    std::vector<float> params((size_t)dstr::param_floats(in0));
+    const int in0 = h->train ? h->train->in0 : 0;
+    std::vector<float> params(h->train ? (size_t)dstr::param_floats(in0) : 0);
+    std::map<std::string, std::vector<float>> all;      // a signal run: every tensor by name, the moving statistics included
     std::string err;
-    if (int rc = h->train->read_params(params.data(), &err)) return fail(h, rc, "ds_train_sync_weights: " + err);
+    if (h->train) { if (int rc = h->train->read_params(params.data(), &err)) return fail(h, rc, "ds_train_sync_weights: " + err); }
+    else if (int rc = h->strain->read_all(&all, &err)) return fail(h, rc, "ds_train_sync_weights: " + err);
     // nothing enqueued may still read the packed weights; the plans (launch descriptors, captured graphs) name them and go too
     for (Slot& sl : h->slots) {
         HIPCHK(h, hipStreamSynchronize(sl.s0));
@@ -3348,7 +3361,13 @@ static int ds_train_sync_weights_impl(ds_handle* h)
     h->weight_allocs.clear();
     std::map<std::string, HostTensor> loaded = std::move(h->kept);      // what ds_train_begin starts from stays what was loaded
     h->host.clear();
-    for (int i = 0; i < dstr::ntensor(in0); ++i) {
+    for (auto& kv : all) {
+        HostTensor t;
+        t.shape = loaded[kv.first].shape;
+        t.data = std::move(kv.second);
+        h->host[kv.first] = std::move(t);
+    }
+    for (int i = 0; h->train && i < dstr::ntensor(in0); ++i) {
         const std::string name = dstr::tensor_name(i);
         HostTensor t;
         t.shape = loaded[name].shape;
@@ -3365,6 +3384,11 @@ static int ds_train_sync_weights_impl(ds_handle* h)
 static int64_t train_get(ds_handle* h, const char* who, const char* name, float* out, int64_t cap, bool grad)
 {
     if (int rc = train_ready(h, who)) return rc;
+    if (h->strain) {
+        std::string err;
+        const int64_t rc = h->strain->get(name, grad, out, cap, &err);
+        return rc < 0 ? fail(h, (int)rc, std::string(who) + ": " + err) : rc;
+    }
     const int idx = dstr::tensor_index(name);
     if (idx < 0 || idx >= dstr::ntensor(h->train->in0) || !out) return fail(h, DS_ERR_INVALID, std::string(who) + ": unknown tensor " + (name ? name : "(null)"));
     std::string err;
@@ -3377,6 +3401,13 @@ static int64_t ds_train_get_mask_impl(ds_handle* h, const char* stream, uint8_t*
     if (int rc = train_ready(h, "ds_train_get_mask")) return rc;
     const int sid = dstr::stream_index(stream);
     if (sid < 0 || !out) return fail(h, DS_ERR_INVALID, std::string("ds_train_get_mask: unknown stream ") + (stream ? stream : "(null)"));
+    if (h->strain) {
+        if (sid != dstr::STREAM_FC1 && sid != dstr::STREAM_FC2) return fail(h, DS_ERR_INVALID, std::string("ds_train_get_mask: a signal run has the streams fc1 and fc2 only, not ") + stream);
+        if (h->strain->last_n == 0) return fail(h, DS_ERR_INVALID, "ds_train_get_mask: no step has run yet");
+        std::string err;
+        const int64_t rc = h->strain->get_mask(sid, out, cap, &err);
+        return rc < 0 ? fail(h, (int)rc, "ds_train_get_mask: " + err) : rc;
+    }
     if (h->train->last_n == 0) return fail(h, DS_ERR_INVALID, "ds_train_get_mask: no step has run yet");
     std::string err;
     const int64_t rc = h->train->get_mask(sid, out, cap, &err);
@@ -3389,7 +3420,76 @@ int ds_train_end(ds_handle* h)
     hipSetDevice(h->cfg.device);
     delete h->train;
     h->train = nullptr;
+    delete h->strain;
+    h->strain = nullptr;
     h->training = false;
+    return DS_OK;
+}
+
+// ---- training step of the signal-only model (ds_train_signal.hip; model.py:89-95, layers.py:80-139,176-264) -------------------------
+static int ds_train_begin_signal_impl(ds_handle* h, const ds_train_config* cfg)
+{
+    if (!h) return DS_ERR_INVALID;
+    const std::string me = "ds_train_begin_signal";
+    if (!cfg) return fail(h, DS_ERR_INVALID, me + ": null config");
+    if (!h->is_cnn || h->is_rnn)
+        return fail(h, DS_ERR_UNSUPPORTED, me + ": trains the signal model alone (is_cnn must be 1 and is_rnn 0; the BiLSTM variants go through ds_train_begin / ds_train_begin_base)");
+    if (h->C != 2) return fail(h, DS_ERR_UNSUPPORTED, me + ": class_num must be 2");
+    if (h->cfg.precision != DS_PRECISION_FP32) return fail(h, DS_ERR_UNSUPPORTED, me + ": precision must be DS_PRECISION_FP32");
+    if (h->J > dsts::MAX_JOINT)
+        return fail(h, DS_ERR_UNSUPPORTED, me + ": the joint width J = " + std::to_string(h->J) + " exceeds 65535: the dropout mask function packs a row's unit into 16 bits, so wider fc1 rows would repeat masks");
+    if (!h->finalized) return fail(h, DS_ERR_INVALID, me + ": weights not loaded");
+    if (tickets_in_flight(h)) return fail(h, DS_ERR_INVALID, me + ": pipeline tickets are still in flight");
+    if (!(cfg->keep_prob > 0.f && cfg->keep_prob <= 1.f)) return fail(h, DS_ERR_INVALID, me + ": keep_prob must lie in (0, 1]");
+    if (!(cfg->pos_weight > 0.f) || std::isinf(cfg->pos_weight)) return fail(h, DS_ERR_INVALID, me + ": pos_weight must be positive and finite");
+    if (cfg->beta1 < 0.f || cfg->beta1 >= 1.f || cfg->beta2 < 0.f || cfg->beta2 >= 1.f || cfg->epsilon < 0.f || std::isnan(cfg->beta1 + cfg->beta2 + cfg->epsilon))
+        return fail(h, DS_ERR_INVALID, me + ": beta1, beta2 must lie in [0, 1) and epsilon must not be negative");
+    std::map<std::string, std::vector<float>> w;
+    for (const auto& kv : h->kept) w[kv.first] = kv.second.data;
+    dstr::Config c;
+    c.keep_prob = cfg->keep_prob; c.pos_weight = cfg->pos_weight; c.seed = cfg->seed;
+    if (cfg->beta1 != 0.f) c.beta1 = cfg->beta1;
+    if (cfg->beta2 != 0.f) c.beta2 = cfg->beta2;
+    if (cfg->epsilon != 0.f) c.epsilon = cfg->epsilon;
+    if (!h->strain) h->strain = new dsts::Trainer();
+    std::string err;
+    const int rc = h->strain->begin(h->cfg.device, h->S, h->B, c, w, &err);
+    if (rc) { delete h->strain; h->strain = nullptr; h->training = false; return fail(h, rc, me + ": " + err); }
+    h->training = true;
+    return DS_OK;
+}
+
+static int ds_train_run_signal_impl(ds_handle* h, const char* who, bool eval, int32_t n, const float* signals, const int32_t* labels, float lr,
+                                    float* loss, int32_t* pred, float* logits)
+{
+    const std::string me = who;
+    if (int rc = train_ready(h, who)) return rc;
+    if (!h->strain) return fail(h, DS_ERR_INVALID, me + ": this run trains a BiLSTM variant (is_rnn 1): ds_train_step / ds_train_step_base / ds_train_eval");
+    if (n < 1 || n > h->B) return fail(h, DS_ERR_INVALID, me + ": n must lie in [1, max_batch]");
+    if (!signals || !labels) return fail(h, DS_ERR_INVALID, me + ": null buffer");
+    if (std::isnan(lr)) return fail(h, DS_ERR_INVALID, me + ": lr is NaN");
+    for (int32_t i = 0; i < n; ++i)
+        if (labels[i] != 0 && labels[i] != 1) return fail(h, DS_ERR_INVALID, me + ": label " + std::to_string(labels[i]) + " of row " + std::to_string(i) + " is outside {0, 1}");
+    std::string err;
+    const int rc = h->strain->run(eval, n, signals, labels, lr, loss, pred, logits, &err);
+    return rc ? fail(h, rc, me + ": " + err) : DS_OK;
+}
+
+static int64_t ds_train_get_tap_impl(ds_handle* h, const char* name, float* out, int64_t cap)
+{
+    if (int rc = train_ready(h, "ds_train_get_tap")) return rc;
+    if (!h->strain) return fail(h, DS_ERR_INVALID, "ds_train_get_tap: only a signal run (ds_train_begin_signal) keeps taps");
+    std::string err;
+    const int64_t rc = h->strain->get_tap(name, out, cap, &err);
+    return rc < 0 ? fail(h, (int)rc, "ds_train_get_tap: " + err) : rc;
+}
+
+int ds_train_mask_reference_wide(uint64_t seed, int64_t step, const char* stream, int32_t n, int32_t width, float keep_prob, uint8_t* out)
+{
+    const int sid = dstr::stream_index(stream);
+    if ((sid != dstr::STREAM_FC1 && sid != dstr::STREAM_FC2) || n < 0 || width < 1 || width > dsts::MAX_JOINT || !out || !(keep_prob > 0.f && keep_prob <= 1.f))
+        return DS_ERR_INVALID;
+    dsts::mask_reference_wide(seed, step, sid, n, width, keep_prob, out);
     return DS_OK;
 }
 
@@ -3404,12 +3504,17 @@ int ds_train_mask_reference(uint64_t seed, int64_t step, const char* stream, int
 int ds_get_train_times(ds_handle* h, int32_t reset, int64_t* steps, double* ms)
 {
     if (!h || !steps || !ms) return DS_ERR_INVALID;
-    *steps = h->train ? h->train->steps_timed : 0;
-    for (int i = 0; i < dstr::NPHASE; ++i) ms[i] = h->train ? h->train->ms[i] : 0.0;
+    *steps = h->train ? h->train->steps_timed : h->strain ? h->strain->steps_timed : 0;
+    for (int i = 0; i < dstr::NPHASE; ++i) ms[i] = h->train ? h->train->ms[i] : h->strain ? h->strain->ms[i] : 0.0;
     if (reset && h->train) { h->train->steps_timed = 0; for (double& v : h->train->ms) v = 0; }
+    if (reset && h->strain) { h->strain->steps_timed = 0; for (double& v : h->strain->ms) v = 0; }
     return DS_OK;
 }
 
+int ds_train_begin_signal(ds_handle* h, const ds_train_config* cfg) { return guarded(h, [&] { return ds_train_begin_signal_impl(h, cfg); }); }
+int ds_train_step_signal(ds_handle* h, int32_t n, const float* signals, const int32_t* labels, float lr, float* loss, int32_t* pred) { return guarded(h, [&] { return ds_train_run_signal_impl(h, "ds_train_step_signal", false, n, signals, labels, lr, loss, pred, nullptr); }); }
+int ds_train_eval_signal(ds_handle* h, int32_t n, const float* signals, const int32_t* labels, float* loss, int32_t* pred, float* logits) { return guarded(h, [&] { return ds_train_run_signal_impl(h, "ds_train_eval_signal", true, n, signals, labels, 0.f, loss, pred, logits); }); }
+int64_t ds_train_get_tap(ds_handle* h, const char* name, float* out, int64_t cap) { return guarded(h, [&] { return ds_train_get_tap_impl(h, name, out, cap); }); }
 int ds_train_begin(ds_handle* h, const ds_train_config* cfg) { return guarded(h, [&] { return ds_train_begin_impl(h, cfg, false); }); }
 int ds_train_begin_base(ds_handle* h, const ds_train_config* cfg) { return guarded(h, [&] { return ds_train_begin_impl(h, cfg, true); }); }
 int ds_train_step_base(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums, const int32_t* labels, float lr, float* loss, int32_t* pred) { return guarded(h, [&] { return ds_train_step_impl(h, "ds_train_step_base", false, n, kmer, means, stds, sanums, labels, lr, loss, pred, nullptr); }); }

@@ -131,6 +131,24 @@ inline float adam_step_size(float lr, float beta1, float beta2, int64_t t)
     return (float)((double)lr * sqrt(1.0 - pow((double)beta2, (double)t)) / (1.0 - pow((double)beta1, (double)t)));
 }
 
+// ---- train_gemm_kernel's arguments: C[z] (+)= op(A[z]) op(B[z]) (+ bias[z]), op = identity or transpose, z = (z1, z2) a two-level
+// batch with element strides
+struct GemmArgs {
+    const float* A;
+    const float* Bm;
+    float* C;
+    const float* bias;       // [N] per z2 (stride sBias2), or nullptr
+    int M, N, K, lda, ldb, ldc, transA, transB, acc;
+    int nb1, nb2;
+    long long sA1, sA2, sB1, sB2, sC1, sC2, sBias2;
+};
+// ds_train.hip's kernels as the signal trainer launches them (ds_train_signal.hip): the kernels themselves are one copy
+hipError_t launch_gemm(hipStream_t s, const GemmArgs& g);
+GemmArgs make_gemm(const float* A, int lda, int transA, const float* Bm, int ldb, int transB, float* C, int ldc, int M, int N, int K, int acc);
+hipError_t launch_reduce_slabs(hipStream_t s, const float* slab, float* out, long long count, int ns, long long stride);      // out[e] = slab[0][e] + slab[1][e] + ...
+hipError_t launch_adam(hipStream_t s, float* P, const float* G, float* M, float* V, long long count, float lr_t, float b1, float b2, float eps);
+hipError_t launch_mask(hipStream_t s, uint8_t* out, int n, int steps, int W, int stream_id, uint32_t thr, uint64_t seed, long long step);
+
 // ---- one run on a handle ---------------------------------------------------------------------------------------------------------
 struct Config {
     float keep_prob = 1.f, pos_weight = 1.f, beta1 = 0.9f, beta2 = 0.999f, epsilon = 1e-8f;

@@ -26,18 +26,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int TM = 64, TN = 64, KC = 16;      // workgroup tile of train_gemm_kernel (four waves, 32 x 32 each), K staged per LDS chunk
 
-// C[z] (+)= op(A[z]) op(B[z]) (+ bias[z]), op = identity or transpose, z = (z1, z2) a two-level batch with element strides. Every
-// operand element is fetched under a bounds check (M, N, K need not be multiples of the tile) and rows >= M are never touched.
-struct GemmArgs {
-    const float* A;
-    const float* Bm;
-    float* C;
-    const float* bias;       // [N] per z2 (stride sBias2), or nullptr
-    int M, N, K, lda, ldb, ldc, transA, transB, acc;
-    int nb1, nb2;
-    long long sA1, sA2, sB1, sB2, sC1, sC2, sBias2;
-};
-
+// train_gemm_kernel: C[z] (+)= op(A[z]) op(B[z]) (+ bias[z]) as GemmArgs (ds_train.h) states it. Every operand element is fetched under
+// a bounds check (M, N, K need not be multiples of the tile) and rows >= M are never touched.
 __global__ __launch_bounds__(256) void train_gemm_kernel(GemmArgs g)
 {
     __shared__ float As[KC][TM + 1];
@@ -444,6 +434,29 @@ GemmArgs gemm_args(const float* A, int lda, int transA, const float* Bm, int ldb
 }
 
 }  // namespace
+
+// ---- the kernels the signal trainer (ds_train_signal.hip) shares, launched as they are --------------------------------------------
+hipError_t launch_gemm(hipStream_t s, const GemmArgs& g) { return gemm(s, g); }
+GemmArgs make_gemm(const float* A, int lda, int transA, const float* Bm, int ldb, int transB, float* C, int ldc, int M, int N, int K, int acc)
+{
+    return gemm_args(A, lda, transA, Bm, ldb, transB, C, ldc, M, N, K, acc);
+}
+hipError_t launch_reduce_slabs(hipStream_t s, const float* slab, float* out, long long count, int ns, long long stride)
+{
+    hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((count + 255) / 256), 1), dim3(256), 0, s, slab, out, count, ns, stride, 0ll, 0ll);
+    return hipGetLastError();
+}
+hipError_t launch_adam(hipStream_t s, float* P, const float* G, float* M, float* V, long long count, float lr_t, float b1, float b2, float eps)
+{
+    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, P, G, M, V, count, lr_t, b1, b2, eps);
+    return hipGetLastError();
+}
+hipError_t launch_mask(hipStream_t s, uint8_t* out, int n, int steps, int W, int stream_id, uint32_t thr, uint64_t seed, long long step)
+{
+    const long long count = (long long)n * steps * W;
+    hipLaunchKernelGGL(mask_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, out, n, steps, W, stream_id, thr, seed, step);
+    return hipGetLastError();
+}
 
 void Trainer::release()
 {

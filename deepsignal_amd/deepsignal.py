@@ -230,7 +230,7 @@ def build_parser(freq_file_given=True):
     denoise_arguments(d)
     d.set_defaults(func=main_denoise)
     parser.denoise_parser = d
-    # `train`: fit the BiLSTM variants (--is_cnn no) on the GPU and save TF checkpoints (the reference's flags and defaults,
+    # `train`: fit the BiLSTM variants (--is_cnn no) or the signal model alone (--is_rnn no) on the GPU and save TF checkpoints (the reference's flags and defaults,
     # train_model.py:288-346, plus --seed / --device)
     from .train_model import SCOPE_NOTE, add_arguments as train_arguments
     t = sub.add_parser("train", description="train a model, need two independent datasets for training and validating. " + SCOPE_NOTE)

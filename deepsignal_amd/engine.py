@@ -60,6 +60,8 @@ EXPORTED_SYMBOLS = (
     "ds_train_get_mask", "ds_train_end", "ds_train_mask_reference", "ds_get_train_times",
     # ... with the embedding trained too, and the evaluation pass (train)
     "ds_train_begin_base", "ds_train_step_base", "ds_train_eval",
+    # the signal-only model's training step (train --is_cnn yes --is_rnn no)
+    "ds_train_begin_signal", "ds_train_step_signal", "ds_train_eval_signal", "ds_train_get_tap", "ds_train_mask_reference_wide",
 )
 
 
@@ -745,7 +747,11 @@ def load_library() -> ctypes.CDLL:
     lib.ds_train_begin_base.argtypes = [vp, ctypes.POINTER(DsTrainConfig)]
     lib.ds_train_step_base.argtypes = [vp, i32, vp, vp, vp, vp, vp, ctypes.c_float, ctypes.POINTER(ctypes.c_float), vp]
     lib.ds_train_eval.argtypes = [vp, i32, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_float), vp, vp]
-    for fn in (lib.ds_train_get_tensor, lib.ds_train_get_grad, lib.ds_train_get_mask):
+    lib.ds_train_begin_signal.argtypes = [vp, ctypes.POINTER(DsTrainConfig)]
+    lib.ds_train_step_signal.argtypes = [vp, i32, vp, vp, ctypes.c_float, ctypes.POINTER(ctypes.c_float), vp]
+    lib.ds_train_eval_signal.argtypes = [vp, i32, vp, vp, ctypes.POINTER(ctypes.c_float), vp, vp]
+    lib.ds_train_mask_reference_wide.argtypes = [ctypes.c_uint64, i64, ctypes.c_char_p, i32, i32, ctypes.c_float, vp]
+    for fn in (lib.ds_train_get_tensor, lib.ds_train_get_grad, lib.ds_train_get_mask, lib.ds_train_get_tap):
         fn.argtypes = [vp, ctypes.c_char_p, vp, i64]
         fn.restype = i64
     lib.ds_train_end.argtypes = [vp]
@@ -781,6 +787,43 @@ def trainable_names(is_base: bool = False) -> List[str]:
     them with is_base."""
     from . import spec
     return [name for name, _ in spec.tensor_table(17, 360, 2, is_cnn=False, is_rnn=True, is_base=is_base)]
+
+
+# ---- ... of the signal-only model (is_cnn, not is_rnn; include/deepsignal_hip.h, "training step of the signal-only model") ---------
+SIGNAL_MASK_STREAMS = ("fc1", "fc2")
+SIGNAL_TRAIN_PHASES = ("forward", "backward", "weight_gradients", "joint_layers", "adam")
+
+
+def train_mask_reference_wide(seed: int, step: int, stream: str, n: int, width: int, keep_prob: float) -> np.ndarray:
+    """train_mask_reference for a joint-layer stream ("fc1", "fc2") whose rows are `width` units wide (fc1 of the signal-only
+    model: J = w_c x 240): uint8 [n, width]."""
+    if stream not in SIGNAL_MASK_STREAMS:
+        raise ValueError("mask stream must be one of %s" % (SIGNAL_MASK_STREAMS,))
+    out = np.empty((n, width), np.uint8)
+    rc = load_library().ds_train_mask_reference_wide(seed, step, stream.encode(), n, width, keep_prob, out.ctypes.data)
+    if rc != 0:
+        raise ValueError("ds_train_mask_reference_wide failed (%d): bad stream, size (width 1 .. 65535) or keep_prob" % rc)
+    return out
+
+
+def signal_tensor_names(signal_len: int = 360) -> List[str]:
+    """TF names of every tensor of the signal-only model, moving statistics included, in the order of `spec.tensor_table`."""
+    from . import spec
+    return [name for name, _ in spec.tensor_table(17, signal_len, 2, is_cnn=True, is_rnn=False)]
+
+
+def signal_trainable_names(signal_len: int = 360) -> List[str]:
+    """... of the 341 it trains: 113 kernels, 113 beta, 113 gamma, the two dense kernels."""
+    return [name for name in signal_tensor_names(signal_len) if not name.endswith(("/moving_mean", "/moving_variance"))]
+
+
+def signal_tap_names() -> List[str]:
+    """What Engine.train_tap takes: every conv + BN (+ ReLU) output, each module's b5 after the add, feat and logits."""
+    from . import spec
+    names = ["stem1", "stem2", "stem3"]
+    for m in range(1, spec.N_INCEPTION + 1):
+        names += ["m%d.%s" % (m, key) for key in spec.INCEPTION_KEYS] + ["m%d.b5" % m]
+    return names + ["feat", "logits"]
 
 
 class Engine:
@@ -826,6 +869,8 @@ class Engine:
         self._slots = int(self._lib.ds_num_slots(self._h))
         self.device, self.max_batch = device, max_batch
         self.is_base = bool(is_base)
+        self.is_cnn, self.is_rnn = bool(is_cnn), bool(is_rnn)
+        self.signal_only = self.is_cnn and not self.is_rnn      # the variant ds_train_begin_signal trains
         self._fine: Optional["Engine"] = None      # set_recheck: the attached engine stays referenced here
         self._owns_fine = False
 
@@ -919,7 +964,9 @@ class Engine:
                 a = np.ascontiguousarray(arr, dtype=np.float32)
                 self._check(self._lib.ds_train_set_tensor(self._h, name.encode(), a.ctypes.data, a.size), "ds_train_set_tensor")
         cfg = DsTrainConfig(keep_prob, pos_weight, beta1, beta2, epsilon, seed & 0xFFFFFFFFFFFFFFFF)
-        if base:
+        if self.signal_only:
+            self._check(self._lib.ds_train_begin_signal(self._h, ctypes.byref(cfg)), "ds_train_begin_signal")
+        elif base:
             self._check(self._lib.ds_train_begin_base(self._h, ctypes.byref(cfg)), "ds_train_begin_base")
         else:
             self._check(self._lib.ds_train_begin(self._h, ctypes.byref(cfg)), "ds_train_begin")
@@ -966,12 +1013,66 @@ class Engine:
         self._check(rc, "ds_train_eval")
         return float(loss.value), pred, logits
 
+    # -- ... of the signal-only model (train_model.py with --is_cnn yes --is_rnn no) --------------
+    def _signal_arrays(self, signals, labels):
+        signals = np.ascontiguousarray(signals, dtype=np.float32)
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        n = int(labels.shape[0]) if labels.ndim == 1 else -1
+        if signals.shape != (n, self.signal_len):
+            raise ValueError("training arrays have inconsistent shapes")
+        return n, signals, labels
+
+    def train_step_signal(self, signals, labels, lr: float) -> Tuple[float, np.ndarray]:
+        """One step of a signal run on signals float32[n, signal_len]: (cost, prediction int32[n])."""
+        n, signals, labels = self._signal_arrays(signals, labels)
+        loss = ctypes.c_float()
+        pred = np.empty((n,), np.int32)
+        rc = self._lib.ds_train_step_signal(self._h, n, signals.ctypes.data, labels.ctypes.data, lr, ctypes.byref(loss), pred.ctypes.data)
+        self._check(rc, "ds_train_step_signal")
+        return float(loss.value), pred
+
+    def train_eval_signal(self, signals, labels) -> Tuple[float, np.ndarray, np.ndarray]:
+        """training = False, keep_prob = 1: the forward on the current parameters with the moving statistics, nothing changed:
+        (cost, prediction int32[n], logits float32[n, 2])."""
+        n, signals, labels = self._signal_arrays(signals, labels)
+        loss = ctypes.c_float()
+        pred = np.empty((n,), np.int32)
+        logits = np.empty((n, 2), np.float32)
+        rc = self._lib.ds_train_eval_signal(self._h, n, signals.ctypes.data, labels.ctypes.data, ctypes.byref(loss), pred.ctypes.data,
+                                            logits.ctypes.data)
+        self._check(rc, "ds_train_eval_signal")
+        return float(loss.value), pred, logits
+
+    def train_tap(self, name: str, n: int) -> np.ndarray:
+        """A layer output of the last step of a signal run (`signal_tap_names`), float32 [n, W, C] ([n, C] for feat and logits)."""
+        from . import spec
+        d = spec.net_dims(self.kmer_len, self.signal_len, self.class_num, True, False)
+        if name in ("feat", "logits"):
+            shape = (n, d.joint if name == "feat" else 2)
+        elif name == "stem1":
+            shape = (n, d.w_conv1, 64)
+        elif name in ("stem2", "stem3"):
+            shape = (n, d.w_a, 128 if name == "stem2" else 256)
+        else:
+            m, _, key = name.partition(".")
+            if name not in signal_tap_names():
+                raise KeyError(name)
+            k = int(m[1:])
+            shape = (n, d.module_width(k), 48 if key == "b5" else spec.inception_convs(k, d.module_cin(k))[key].cout)
+        out = np.empty(shape, np.float32)
+        got = int(self._lib.ds_train_get_tap(self._h, name.encode(), out.ctypes.data, out.size))
+        self._check(got, "ds_train_get_tap")
+        if got != out.size:
+            raise RuntimeError("ds_train_get_tap: the last step had %d elements of %s, %d asked for" % (got, name, out.size))
+        return out
+
     def train_sync_weights(self) -> None:
         self._check(self._lib.ds_train_sync_weights(self._h), "ds_train_sync_weights")
 
     def _train_tensor(self, fn, what: str, name: str) -> np.ndarray:
         from . import spec
-        shapes = dict(spec.tensor_table(self.kmer_len, self.signal_len, self.class_num, is_cnn=False, is_rnn=True, is_base=self.is_base))
+        shapes = dict(spec.tensor_table(self.kmer_len, self.signal_len, self.class_num, is_cnn=self.signal_only, is_rnn=not self.signal_only,
+                                        is_base=self.is_base))
         if name not in shapes:
             raise KeyError(name)
         out = np.empty(shapes[name], np.float32)
@@ -988,13 +1089,22 @@ class Engine:
         return self._train_tensor(self._lib.ds_train_get_grad, "ds_train_get_grad", name)
 
     def train_tensors(self) -> Dict[str, np.ndarray]:
-        return {name: self.train_tensor(name) for name in trainable_names(self.is_base)}
+        """Every current tensor of the run by name (a signal run: the moving statistics too)."""
+        names = signal_tensor_names(self.signal_len) if self.signal_only else trainable_names(self.is_base)
+        return {name: self.train_tensor(name) for name in names}
 
     def train_grads(self) -> Dict[str, np.ndarray]:
-        return {name: self.train_grad(name) for name in trainable_names(self.is_base)}
+        names = signal_trainable_names(self.signal_len) if self.signal_only else trainable_names(self.is_base)
+        return {name: self.train_grad(name) for name in names}
 
     def train_mask(self, stream: str, n: int) -> np.ndarray:
-        out = np.empty(mask_shape(stream, n, self.kmer_len), np.uint8)
+        if self.signal_only:
+            from . import spec
+            if stream not in SIGNAL_MASK_STREAMS:
+                raise ValueError("mask stream must be one of %s" % (SIGNAL_MASK_STREAMS,))
+            out = np.empty((n, spec.net_dims(self.kmer_len, self.signal_len, self.class_num, True, False).joint if stream == "fc1" else 2), np.uint8)
+        else:
+            out = np.empty(mask_shape(stream, n, self.kmer_len), np.uint8)
         got = int(self._lib.ds_train_get_mask(self._h, stream.encode(), out.ctypes.data, out.size))
         self._check(got, "ds_train_get_mask")
         if got != out.size:
@@ -1008,7 +1118,7 @@ class Engine:
         steps = ctypes.c_int64()
         ms = (ctypes.c_double * len(TRAIN_PHASES))()
         self._check(self._lib.ds_get_train_times(self._h, int(reset), ctypes.byref(steps), ms), "ds_get_train_times")
-        return {"steps": int(steps.value), "ms": dict(zip(TRAIN_PHASES, (float(v) for v in ms)))}
+        return {"steps": int(steps.value), "ms": dict(zip(SIGNAL_TRAIN_PHASES if self.signal_only else TRAIN_PHASES, (float(v) for v in ms)))}
 
     # -- forward (sess.run, call_modifications.py:177-178) -------------------------------------
     def run(self, kmer, means, stds, sanums, signals) -> Tuple[np.ndarray, np.ndarray]:

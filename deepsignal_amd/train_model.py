@@ -1,10 +1,12 @@
 """`deepsignal train`: fit a model on a training file, validate it on a second one, and save the best parameters as TensorFlow
 checkpoints -- the reference's train module (train_model.py:24-285) restated statement for statement, with the steps and the
-validation passes on the GPU (Engine.train_step / Engine.train_eval, csrc/ds_train.hip).
+validation passes on the GPU (Engine.train_step / Engine.train_eval, csrc/ds_train.hip; Engine.train_step_signal /
+Engine.train_eval_signal, csrc/ds_train_signal.hip).
 
-What is trained: the variants without the signal model, `--is_cnn no --is_rnn yes` with `--is_base yes` (embedding + BiLSTM, the
-reference's "RNN-only" model) or `--is_base no` (what `denoise` trains). `--is_cnn yes` is the reference's default and a usage
-error here: the signal model has no backward in this release.
+What is trained: the variants with one sub-model. `--is_cnn no --is_rnn yes` with `--is_base yes` (embedding + BiLSTM, the
+reference's "RNN-only" model) or `--is_base no` (what `denoise` trains); and `--is_cnn yes --is_rnn no`, the signal model alone
+feeding the joint layers (`--is_base` is ignored, as in the reference). `--is_cnn yes --is_rnn yes` is the reference's default and
+a usage error here: joined to the BiLSTM the signal model has no backward in this release.
 
 The loop is the reference's: per epoch the learning rate (epochs 0 and 1: --learning_rate, later ones times --decay_rate), a
 shuffle through a window of 3 x batch_size rows (tf.data's shuffle), per batch accuracy / recall / precision; every
@@ -16,13 +18,16 @@ best is saved over the same `epoch_<id>` prefix. Training stops after an epoch t
 epoch_id >= min_epoch_num - 1.
 
 What is done differently. The training file is read ONCE and held in memory (the reference streams it through tf.data every
-epoch): about 4 x 4 x kmer_len bytes a row, so a few million rows are fine and the reference's "up to 20m" samples are out of
+epoch): about 4 x (4 x kmer_len + cent_signals_len) bytes a row (1.7 KB at the defaults), so a few million rows are fine and the reference's "up to 20m" samples are out of
 scope. The batch metrics are computed here (no scikit-learn; a zero denominator gives 0). TensorFlow's random draws
 (initialisation, dropout, shuffle) are not reproduced, their distributions are; with --seed every draw derives from it and two
 runs write identical files. A save writes `bn_<k>.sn_<s>.epoch_<id>.ckpt` (.index + .data-00000-of-00001) with the variant's
 tensors under the reference graph's names and `modelglobal_step`, and the `checkpoint` state file; like tf.train.Saver's default
-it keeps the five most recent prefixes. These checkpoints are for this project's `call_mods -m <prefix> --is_cnn no [--is_base
-no]`; the reference's own graph always creates the signal model's variables, which they do not hold.
+it keeps the five most recent prefixes. The BiLSTM variants' checkpoints are for this project's `call_mods -m <prefix> --is_cnn no
+[--is_base no]`; the reference's own graph always creates the signal model's variables, which they do not hold. A save of the
+signal-only variant holds all of its tensors, the batch norms' moving statistics included, so `call_mods -m <prefix> --is_rnn no`
+reads it; the zero-debias helper variables that TensorFlow keeps beside each moving mean (`.../biased`, `.../local_step`) are NOT
+written: a TensorFlow run that resumed from such a checkpoint would have to start them over.
 
 The device part is an object with begin / step / eval / weights (GpuDevice); `train()` takes it as an argument, so the workflow
 runs without a GPU under a stand-in (tests/test_train_host.py)."""
@@ -46,23 +51,25 @@ if __package__ in (None, ""):                       # run as a script: the packa
 from .denoise import batch_metrics, windowed_shuffle
 from .utils.process_utils import display_args, str2bool
 
-Rows = Dict[str, np.ndarray]      # kmer int32[n, T], means / stds / sanums float32[n, T], labels int32[n]
+Rows = Dict[str, np.ndarray]      # kmer int32[n, T], means / stds / sanums float32[n, T], signals float32[n, S], labels int32[n]
 MAX_TO_KEEP = 5                   # tf.train.Saver's default
 SCOPE_NOTE = ("The training file is read once and held in memory: a few million rows, not the 20m the reference streams. "
-              "Trains --is_cnn no --is_rnn yes with --is_base yes or no; the signal model's backward is not implemented.")
+              "Trains --is_cnn no --is_rnn yes with --is_base yes or no, and --is_cnn yes --is_rnn no (the signal model alone); "
+              "joined to the BiLSTM the signal model's backward is not implemented.")
 
 
 def read_rows(path: str, kmer_len: int, signal_len: int) -> Rows:
-    """A feature file through the native TSV reader, as denoise.read_features reads it, plus the k-mer codes."""
+    """A feature file through the native TSV reader, as denoise.read_features reads it, plus the k-mer codes and the signals."""
     from .fastio import FeatureReader
     reader = FeatureReader(path, kmer_len, signal_len)
-    parts: Dict[str, List[np.ndarray]] = {"kmer": [], "means": [], "stds": [], "sanums": [], "labels": []}
+    parts: Dict[str, List[np.ndarray]] = {"kmer": [], "means": [], "stds": [], "sanums": [], "signals": [], "labels": []}
     try:
         for item in reader.items(200):
             parts["kmer"].append(item.kmer)
             parts["means"].append(item.means)
             parts["stds"].append(item.stds)
             parts["sanums"].append(item.lens)
+            parts["signals"].append(item.signals)
             parts["labels"].append(item.labels)
     finally:
         reader.close()
@@ -76,32 +83,43 @@ def take(rows: Rows, idx) -> Rows:
 
 
 class GpuDevice:
-    """The model on one engine handle: begin (fresh parameters), step, eval (training = False), weights (for a save)."""
+    """The model on one engine handle: begin (fresh parameters), step, eval (training = False), weights (for a save). The variant
+    follows the flags: the signal model alone (--is_cnn yes --is_rnn no), or a BiLSTM variant."""
 
     def __init__(self, args):
         from .engine import Engine
         self.args = args
-        self.is_base = str2bool(args.is_base)
+        self.signal_only = str2bool(args.is_cnn) and not str2bool(args.is_rnn)
+        self.is_base = str2bool(args.is_base) and not self.signal_only
         self.engine = Engine(kmer_len=args.kmer_len, signal_len=args.cent_signals_len, class_num=2, device=args.device or 0,
-                             max_batch=args.batch_size, is_cnn=False, is_rnn=True, is_base=self.is_base)
+                             max_batch=args.batch_size, is_cnn=self.signal_only, is_rnn=not self.signal_only, is_base=self.is_base)
 
     def begin(self, init_seed: int, mask_seed: int) -> None:
         from . import weights
         a = self.args       # glorot-uniform kernels, zero LSTM bias, truncated-normal embedding: the reference's initialisers
-        init = weights.random_weights(seed=init_seed, kmer_len=a.kmer_len, signal_len=a.cent_signals_len, is_cnn=False, is_rnn=True,
-                                      is_base=self.is_base)
+        if self.signal_only:      # ... and batch_norm's: gamma 1, beta 0, moving mean 0, moving variance 1
+            init = weights.random_weights(seed=init_seed, kmer_len=a.kmer_len, signal_len=a.cent_signals_len, is_cnn=True, is_rnn=False,
+                                          randomize_bn=False)
+        else:
+            init = weights.random_weights(seed=init_seed, kmer_len=a.kmer_len, signal_len=a.cent_signals_len, is_cnn=False, is_rnn=True,
+                                          is_base=self.is_base)
         self.engine.load_weights(init)
         self.engine.train_begin(keep_prob=a.keep_prob, pos_weight=a.pos_weight, seed=mask_seed, base=True)
 
     def step(self, rows: Rows, lr: float) -> Tuple[float, np.ndarray]:
+        if self.signal_only:
+            return self.engine.train_step_signal(rows["signals"], rows["labels"], lr)
         return self.engine.train_step(rows["means"], rows["stds"], rows["sanums"], rows["labels"], lr, kmer=rows["kmer"])
 
     def eval(self, rows: Rows) -> Tuple[float, np.ndarray]:
-        loss, pred, _ = self.engine.train_eval(rows["means"], rows["stds"], rows["sanums"], rows["labels"], kmer=rows["kmer"])
+        if self.signal_only:
+            loss, pred, _ = self.engine.train_eval_signal(rows["signals"], rows["labels"])
+        else:
+            loss, pred, _ = self.engine.train_eval(rows["means"], rows["stds"], rows["sanums"], rows["labels"], kmer=rows["kmer"])
         return loss, pred
 
     def weights(self) -> Dict[str, np.ndarray]:
-        return self.engine.train_tensors()
+        return self.engine.train_tensors()      # the signal-only variant: the moving statistics too
 
     def close(self) -> None:
         self.engine.close()
@@ -274,7 +292,8 @@ def add_arguments(ap) -> None:
     g = ap.add_argument_group("INPUT")
     g.add_argument("--train_file", action="store", type=str, required=True,
                    help="file contains samples for training, from extract_features.py. The file should contain shuffled positive "
-                        "and negative samples. It is read once and held in memory (a few million rows; not the reference's 20m).")
+                        "and negative samples. It is read once and held in memory, signals included: 4 x (4 x kmer_len + "
+                        "cent_signals_len) bytes a row, 1.7 KB at the defaults (a few million rows; not the reference's 20m).")
     g.add_argument("--valid_file", action="store", type=str, required=True,
                    help="file contains samples for testing, from extract_features.py. For CpG, 10k (~5k positive and ~5k negative) "
                         "samples are sufficient.")
@@ -285,8 +304,8 @@ def add_arguments(ap) -> None:
     g.add_argument("--log_dir", "-g", action="store", type=str, required=False, default=None, help="directory for saving the training log")
     g = ap.add_argument_group("TRAIN")
     g.add_argument("--is_cnn", type=str, default="yes", required=False,
-                   help="using inception module of deepsignal or not. The default yes is not implemented (the signal model has no "
-                        "backward): pass --is_cnn no")
+                   help="using inception module of deepsignal or not. yes trains with --is_rnn no (the signal model alone); with the "
+                        "default --is_rnn yes it is not implemented (joined to the BiLSTM the signal model has no backward)")
     g.add_argument("--is_base", type=str, default="yes", required=False, help="using base features in BiLSTM module or not")
     g.add_argument("--is_rnn", type=str, default="yes", required=False, help="using BiLSTM module of deepsignal or not")
     g.add_argument("--kmer_len", "-x", action="store", default=17, type=int, required=False, help="base num of the kmer, default 17")
@@ -314,10 +333,11 @@ def check_arguments(ap, a) -> None:
         is_cnn, is_base, is_rnn = str2bool(a.is_cnn), str2bool(a.is_base), str2bool(a.is_rnn)
     except Exception:
         ap.error("--is_cnn / --is_base / --is_rnn take yes or no")
-    del is_base         # both values are trained
-    if is_cnn:
-        ap.error("--is_cnn yes (the default) is not implemented: the signal model has no backward in this release; pass --is_cnn no")
-    if not is_rnn:
+    del is_base         # both values are trained (ignored without the BiLSTM)
+    if is_cnn and is_rnn:
+        ap.error("--is_cnn yes --is_rnn yes (the default) is not implemented: joined to the BiLSTM the signal model has no backward in "
+                 "this release; pass --is_rnn no to train it alone, or --is_cnn no for the BiLSTM variants")
+    if not is_rnn and not is_cnn:
         ap.error("--is_rnn no is not implemented: without the signal model the BiLSTM is all there is to train")
     if a.class_num != 2:
         ap.error("--class_num other than 2 is not implemented: the training step has the two-class loss only")

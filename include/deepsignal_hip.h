@@ -738,6 +738,41 @@ int ds_train_step_base(ds_handle *h, int32_t n, const int32_t *kmer, const float
 int ds_train_eval(ds_handle *h, int32_t n, const int32_t *kmer, const float *means, const float *stds, const float *sanums,
                   const int32_t *labels, float *loss, int32_t *pred, float *logits);
 
+/* ---- training step of the signal-only model (`train --is_cnn yes --is_rnn no`; csrc/ds_train_signal.hip) ------------------
+ * Valid on a handle with is_cnn 1, is_rnn 0, class_num 2, DS_PRECISION_FP32 and loaded weights: the stem, the eleven inception
+ * modules, the 1x7 average pool and the joint layers dense(J, J), dense(J, 2) with dropout after each (model.py:89-95,
+ * layers.py:80-139,176-264), J = w_c x 240. Batch normalisation runs in training mode: per channel the mean and the biased variance
+ * of the batch's n x W values (two passes), and every step folds them into the moving statistics with decay 0.9 (moving_variance
+ * takes the unbiased variance, moving_mean is zero-debiased). fp32 on the device, no floating-point atomics:
+ * the same weights, rows, seed and step give the same bits. Max pools send their gradient to the first in-bounds maximum.
+ *
+ * ds_train_begin_signal: as ds_train_begin, for such a handle; any other handle: DS_ERR_UNSUPPORTED with the reason. J above 65535
+ *   is refused: the mask function packs a row's unit into 16 bits. The trained tensors are the 341 of
+ *   spec.tensor_table(is_cnn=True, is_rnn=False) that are no moving statistic: 113 kernels, 113 beta, 113 gamma, the two dense kernels.
+ * ds_train_step_signal: one step on n rows (1 .. max_batch) of signals float[n, signal_len] and labels int32[n] in {0, 1}.
+ * ds_train_eval_signal: training = False, keep_prob = 1 (train_model.py:200-210): the forward on the current parameters with the
+ *   MOVING statistics and every mask kept. Nothing is written but scratch (the taps included); logits float[n, 2] may be NULL.
+ * ds_train_get_tap: a layer output of the last step, as its backward read it, float[n, W, C]: "stem1" .. "stem3" and
+ *   "m<k>.<key>" (k = 1 .. 11, key of b1 b2 b3a b3b b4a b4b b5s b5a b5b b5c: that conv's BN (+ ReLU) output), "m<k>.b5" (after the
+ *   add and ReLU), "feat" [n, J], "logits" [n, 2] as dropped. Returns the floats written. The taps are the step's scratch:
+ *   ds_train_eval_signal overwrites them, and until the next step ds_train_get_tap then returns DS_ERR_INVALID.
+ * ds_train_mask_reference_wide: the CPU mask checker for a joint-layer stream ("fc1", "fc2") whose rows are `width` units wide
+ *   (1 .. 65535); ds_train_mask_reference sizes "fc1" at 512.
+ * On such a run ds_train_set_tensor / ds_train_get_tensor take every tensor name of the variant (the moving statistics are readable
+ * and settable but not trained: ds_train_get_grad refuses them), ds_train_get_mask the streams "fc1" [n, J] and "fc2" [n, 2],
+ * ds_train_sync_weights hands parameters and moving statistics to the inference plan, ds_train_end closes it. ds_get_train_times:
+ * ms[0] the signal model's forward, ms[1] its backward (data and batch-norm gradients), ms[2] the kernels' weight gradients, ms[3]
+ * the joint layers (forward, loss, backward), ms[4] Adam. ds_train_step* / ds_train_eval on a signal run, and the *_signal entries
+ * on a BiLSTM run, return DS_ERR_INVALID. A step that fails part-way (a HIP error) leaves moving statistics that are ahead of the
+ * step counter: every later step or evaluation of that run returns DS_ERR_INVALID until ds_train_begin_signal starts it over. */
+int ds_train_begin_signal(ds_handle *h, const ds_train_config *cfg);
+int ds_train_step_signal(ds_handle *h, int32_t n, const float *signals, const int32_t *labels, float lr, float *loss, int32_t *pred);
+int ds_train_eval_signal(ds_handle *h, int32_t n, const float *signals, const int32_t *labels, float *loss, int32_t *pred,
+                         float *logits);
+int64_t ds_train_get_tap(ds_handle *h, const char *name, float *out, int64_t cap);
+int ds_train_mask_reference_wide(uint64_t seed, int64_t step, const char *stream, int32_t n, int32_t width, float keep_prob,
+                                 uint8_t *out);
+
 /* Use a captured hipGraph for the forward (default on). */
 int ds_set_graph(ds_handle *h, int32_t enable);
 

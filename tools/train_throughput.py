@@ -5,10 +5,13 @@ cores. Writes profiles/train_throughput.json.
 
     python tools/train_throughput.py [--steps 30] [--warmup 5] [--cpu_steps 2] [--is_base no] [--out profiles/train_throughput.json]
     python tools/train_throughput.py --parity [--out profiles/train_parity.json]
+    python tools/train_throughput.py --variant signal [--signal_len 360] [--cpu_steps 1] [--out profiles/train_throughput_signal.json]
 
 --parity writes the distances tests/test_gpu_train_grad.py asserts on (GPU and float32 statement against the float64 statement,
 per case and tensor) instead. --is_base yes times the step with the embedding trained (ds_train_step_base, codes uniform over
-A, C, G, T); the default no is the step denoise runs, through ds_train_step."""
+A, C, G, T); the default no is the step denoise runs, through ds_train_step. --variant signal times the signal-only model's step
+(ds_train_step_signal: stem, eleven inception modules, joint layers at J = w_c x 240) on normal signals; its CPU baseline is
+tests/train_statement_signal.py in float32, one step without a warm-up (a step takes far longer than any start-up cost)."""
 import argparse
 import json
 import os
@@ -85,6 +88,50 @@ def throughput(a):
     return out
 
 
+def throughput_signal(a):
+    import torch
+    import train_statement_signal as tss
+    from deepsignal_amd import spec, weights
+    from deepsignal_amd.engine import Engine
+    n, S = a.batch, a.signal_len
+    J = tss.dims(S).joint
+    w = weights.random_weights(seed=7, signal_len=S, is_cnn=True, is_rnn=False, randomize_bn=True)
+    rng = np.random.default_rng(1)
+    signals, labels = rng.normal(0.0, 1.0, (n, S)).astype(np.float32), rng.integers(0, 2, n).astype(np.int32)
+    eng = Engine(signal_len=S, max_batch=n, is_cnn=True, is_rnn=False, device=a.device)
+    eng.load_weights(w)
+    eng.train_begin(keep_prob=a.keep_prob, seed=3)
+    for _ in range(a.warmup):
+        eng.train_step_signal(signals, labels, 1e-3)
+    eng.train_times(reset=True)
+    t0 = time.perf_counter()
+    for _ in range(a.steps):
+        loss, _ = eng.train_step_signal(signals, labels, 1e-3)
+    wall = time.perf_counter() - t0
+    times = eng.train_times()
+    eng.close()
+    # the forward's matrix products: the convolutions (spec.FLOPS_CONV_PER_SITE at signal_len 360, in proportion otherwise) and the
+    # two dense layers; the backward twice that (data and weight gradients)
+    fwd = n * (spec.FLOPS_CONV_PER_SITE * S / 360.0 + 2.0 * J * J + 2.0 * J * 2)
+    device_ms = sum(times["ms"].values()) / times["steps"]
+    out = {"variant": "signal", "note": "measured once, not tuned", "batch": n, "signal_len": S, "joint": J, "keep_prob": a.keep_prob, "steps": a.steps,
+           "warmup": a.warmup, "last_loss": loss, "steps_per_s": a.steps / wall, "samples_per_s": a.steps * n / wall,
+           "wall_ms_per_step": 1e3 * wall / a.steps, "device_ms_per_step": device_ms,
+           "device_ms_per_phase": {k: v / times["steps"] for k, v in times["ms"].items()},
+           "gflop_per_step": {"forward": fwd / 1e9, "backward": 2 * fwd / 1e9},
+           "fraction_of_fp32_matrix_peak": 3 * fwd / (device_ms * 1e-3) / FP32_MATRIX_PEAK}
+    if a.cpu_steps > 0:
+        cores = usable_cores()
+        torch.set_num_threads(cores)
+        t0 = time.perf_counter()
+        for _ in range(a.cpu_steps):
+            tss.step(w, signals, labels, None, 1.0, 1.0, torch.float32)
+        cpu = (time.perf_counter() - t0) / a.cpu_steps
+        out["cpu_statement"] = {"what": "tests/train_statement_signal.py, float32, forward + autograd backward (no optimiser), no warm-up", "cores": cores,
+                                "s_per_step": cpu, "samples_per_s": n / cpu}
+    return out
+
+
 def parity(a):
     import torch
     import test_gpu_train_grad as cases
@@ -118,11 +165,16 @@ def main():
     ap.add_argument("--cpu_steps", type=int, default=2, help="steps of the CPU statement to time (0: skip)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--is_base", default="no", choices=["yes", "no"], help="yes: the embedding is trained too (default no: denoise's step)")
+    ap.add_argument("--variant", default="rnn", choices=["rnn", "signal"], help="signal: the signal-only model's step (ds_train_step_signal)")
+    ap.add_argument("--signal_len", type=int, default=360)
     ap.add_argument("--parity", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    result = parity(a) if a.parity else throughput(a)
-    path = a.out or os.path.join(ROOT, "profiles", "train_parity.json" if a.parity else "train_throughput.json")
+    if a.variant == "signal" and a.parity:
+        ap.error("--parity covers the BiLSTM step; the signal step's distances are printed by tests/test_gpu_train_signal_grad.py")
+    result = parity(a) if a.parity else throughput_signal(a) if a.variant == "signal" else throughput(a)
+    default = "train_parity.json" if a.parity else "train_throughput_signal.json" if a.variant == "signal" else "train_throughput.json"
+    path = a.out or os.path.join(ROOT, "profiles", default)
     with open(path, "w") as f:
         json.dump(result, f, indent=1, sort_keys=True)
         f.write("\n")
