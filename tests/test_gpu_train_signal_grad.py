@@ -14,10 +14,24 @@ statements taken under the GPU's decisions as in (4); (6) the prediction whereve
 lr = 0 not a bit of a parameter moves.
 
 On one MI355X the taps stood at 0.41 - 0.50 of their bars, the gradients at 0.57 - 0.77 of theirs, the loss at 0.003 - 0.06 of its
-bar, with 0 / 0 / 1 / 1 / 3 / 12 differing decisions (offset, real window, one row, dead, odd widths, partial tiles).
+bar, with 0 / 0 / 1 / 1 / 3 / 12 differing decisions (offset, real window, one row, dead, odd widths, partial tiles). "wide slabs"
+and "even slabs" there: the taps at 0.25 / 0.29 of their bars, the gradients at 0.33 / 0.42 of theirs, the loss at 0.0009 / 0.003
+of its bar, with 40 / 29 differing decisions against places_32 = 77 / 66 (caps 154 / 132; on another host's torch build the same
+float32 statement gave places_32 = 70 / 73). With colsum_kernel made to add 128 rows of every slab whatever slab_rows is, the six
+cases above passed unchanged and both wide cases failed at their first tap, stem1, 0.48 / 0.42 from the float64 statement against
+a bar of 4e-6.
 
-Handles have max_batch = 96. randomize_bn weights throughout, so gamma and beta matter."""
+WIDE ROW SLABS. Every reduction over the R = n x W rows of a layer (batch-norm sums, their gradient sums, every weight gradient) is
+cut into slabs of rows by slabs_of (ds_train_signal.hip; NSLAB in ds_train_signal.h), restated here as `slabs_of`. The six cases
+above stay at 128 rows a slab; "wide slabs" and "even slabs" run the stem and modules 1 - 3 at longer slabs, all 64 of them (the
+table at WIDE_SLABS, asserted from the rule). Their graphs take 4.4e7 / 4.1e7 decisions, where the free float32 statement alone
+differs from the float64 one in `places_32` places, so their cap on differing places is max(16, 2 x places_32) -- another summation
+order flips another set of about that size; every differing place is still held to its margin.
+
+Handles have max_batch = 96 (1024 for the two wide cases). randomize_bn weights throughout, so gamma and beta matter."""
 import functools
+import os
+import re
 
 import numpy as np
 import pytest
@@ -28,6 +42,7 @@ import train_statement_signal as tss
 pytestmark = pytest.mark.gpu
 
 MAX_BATCH = 96
+MAX_BATCH_WIDE = 1024
 SEED = 99
 MAX_DIFFERING = 16
 #         kind             signal_len  n  keep  pos_weight
@@ -36,7 +51,47 @@ CASES = [("one row",        360,  1, 1.0, 1.0),      # BN over one row's positio
          ("odd widths",      40,  6, 0.5, 1.0),      # widths 20 / 10 / 5 / 3, odd-length stride-2 pools, asymmetric pads
          ("partial tiles",  100, 70, 0.5, 3.0),      # widths 50 / 25 / 13 / 7, partial row tiles
          ("offset",          40,  6, 0.5, 1.0),      # signals 5 + 0.2 x N(0, 1): |mean| >> std in the stem
-         ("dead",           360,  5, 0.5, 1.0)]      # first and last output channel of every conv kernel zeroed: v = 0
+         ("dead",           360,  5, 0.5, 1.0),      # first and last output channel of every conv kernel zeroed: v = 0
+         ("wide slabs",      40, 900, 0.5, 3.0),     # slab_rows 282 / 141 in the stem and modules 1 - 3, short last slab
+         ("even slabs",      40, 832, 0.5, 1.0)]     # slab_rows 260 / 130, R a multiple of them: no remainder launch
+
+CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "deepsignal_amd", "csrc")
+NSLAB, MIN_SLAB_ROWS = 64, 128
+#                       per width 20 / 10 / 5 / 3:  (R, slab_rows, nslab, rows in the last slab)
+WIDE_SLABS = {"wide slabs": [(18000, 282, 64, 234), (9000, 141, 64, 117), (4500, 128, 36, 20), (2700, 128, 22, 12)],
+              "even slabs": [(16640, 260, 64, 260), (8320, 130, 64, 130), (4160, 128, 33, 64), (2496, 128, 20, 64)]}
+
+
+def slabs_of(R):
+    """(rows per slab, slabs) of a reduction over R rows: slabs_of in ds_train_signal.hip, NSLAB from ds_train_signal.h."""
+    slab_rows = max(MIN_SLAB_ROWS, -(-R // NSLAB))
+    return slab_rows, -(-R // slab_rows)
+
+
+def check_slab_rule(kind, S, n):
+    """The restatement is the source's, and it cuts this case's rows as WIDE_SLABS says: a change of the rule fails here, where
+    it would otherwise quietly take the case out of the regime it is there for."""
+    header = open(os.path.join(CSRC, "ds_train_signal.h")).read()
+    source = open(os.path.join(CSRC, "ds_train_signal.hip")).read()
+    assert re.search(r"constexpr int NSLAB = %d;" % NSLAB, header), "NSLAB of ds_train_signal.h is no longer %d" % NSLAB
+    assert "*slab_rows = std::max(%d, (R + NSLAB - 1) / NSLAB);" % MIN_SLAB_ROWS in source, "slabs_of of ds_train_signal.hip changed"
+    assert "*nslab = (R + *slab_rows - 1) / *slab_rows;" in source, "slabs_of of ds_train_signal.hip changed"
+    from deepsignal_amd import spec
+    widths, W = [], S
+    for k in (7, 3, 3, 3):                                   # the stem conv, then the three stride-2 pools
+        W = spec.same_pad(W, k, 2)[0]
+        widths.append(W)
+    got = []
+    for W in widths:
+        slab_rows, nslab = slabs_of(n * W)
+        got.append((n * W, slab_rows, nslab, n * W - (nslab - 1) * slab_rows))
+    assert got == WIDE_SLABS[kind], got
+    for R, slab_rows, nslab, last in got[:2]:                # the stem and modules 1 - 3: the wide regime, every slab in use
+        assert slab_rows > MIN_SLAB_ROWS and nslab == NSLAB
+    if kind == "wide slabs":                                 # an odd slab, no multiple of the 16-row chunk, lanes split unevenly
+        assert got[1][1] % 2 == 1 and got[1][1] % 16 != 0 and got[0][1] % 4 != 0 and got[0][3] < got[0][1] and got[1][3] < got[1][1]
+    else:                                                    # full == nslab: R / slab_rows exact
+        assert got[0][3] == got[0][1] and got[1][3] == got[1][1]
 
 
 @functools.lru_cache(maxsize=None)
@@ -64,7 +119,10 @@ def test_taps_decisions_gradients_loss_and_masks(kind, S, n, keep_prob, pos_weig
     from deepsignal_amd import engine
     w, signals, labels = case_inputs(kind, S, n)
     J = tss.dims(S).joint
-    eng = engine.Engine(signal_len=S, max_batch=MAX_BATCH, is_cnn=True, is_rnn=False)
+    wide = kind in WIDE_SLABS
+    if wide:
+        check_slab_rule(kind, S, n)
+    eng = engine.Engine(signal_len=S, max_batch=MAX_BATCH_WIDE if wide else MAX_BATCH, is_cnn=True, is_rnn=False)
     try:
         eng.load_weights(w)
         eng.train_begin(keep_prob=keep_prob, pos_weight=pos_weight, seed=SEED)
@@ -107,7 +165,13 @@ def test_taps_decisions_gradients_loss_and_masks(kind, S, n, keep_prob, pos_weig
     diffs = tss.decision_differences(dec, free64)
     places = sum(d[1] for d in diffs)
     print("%s: decisions differ from the float64 statement's in %d places: %s" % (kind, places, diffs))
-    assert places <= MAX_DIFFERING
+    cap = MAX_DIFFERING
+    if wide:      # the float32 statement's own count of differing places sets the scale; a reference value, not the GPU's
+        dec_32 = tss.decisions_from_taps({k: t.numpy() for k, t in free32.taps.items()})
+        places_32 = sum(d[1] for d in tss.decision_differences(dec_32, free64))
+        cap = max(MAX_DIFFERING, 2 * places_32)
+        print("%s: places_32 %d, the GPU's %d, cap %d" % (kind, places_32, places, cap))
+    assert places <= cap
     for name, _, margin, tap in diffs:          # a pool's places are listed per tap that feeds the differing channels
         assert margin <= bars[tap][0] * bars[tap][1], (name, tap, margin)
 

@@ -1,6 +1,6 @@
 """GPU: the signal-only model's training step beyond one gradient (tests/test_gpu_train_signal_grad.py): determinism, one Adam
-step, the moving statistics over three steps, the evaluation pass and what it must leave alone, the hand-over to the inference
-plan, memorisation of a fixed batch, and the refusals."""
+step and three in isolation, a narrow step right after a wide one, the moving statistics over three steps, the evaluation
+pass and what it must leave alone, the hand-over to the inference plan, memorisation of a fixed batch, and the refusals."""
 import numpy as np
 import pytest
 import torch
@@ -100,6 +100,109 @@ def test_one_adam_step():
         assert (np.abs(after[name] - ref) <= ulp + lr * delta * slope).all(), name
         if np.abs(g[name]).max() > 1e-6:          # far above eps': the step is lr in size, far above an ulp of theta
             assert (after[name] != w[name]).any(), name
+
+
+def test_adam_three_steps_in_isolation():
+    """test_adam_in_isolation of test_gpu_train_step.py over this variant's block (113 kernels, beta, gamma, the J x J dense/kernel,
+    dense_1/kernel). Three steps on three batches; after each the expected parameters are the numpy float64 Adam applied to the
+    GPU's own gradients, from the GPU's own fp32 parameters of the step before: steps 2 and 3 run on non-zero moments and a
+    bias-corrected step size. Bar: one ulp of theta plus 1e-5 lr on every element. A fourth step at lr = 0 moves no bit."""
+    import train_statement as ts
+    w, lr, n = _w(), 1e-3, 6
+    names = tss.trainable_names(S)
+    assert len(names) == 341
+    eng = _engine(w)
+    try:
+        eng.train_begin(keep_prob=0.5, seed=1)
+        opt = ts.Adam({k: np.asarray(w[k], np.float32) for k in names})
+        for s in range(3):
+            sig, lab = _batch(n, 50 + s)
+            eng.train_step_signal(sig, lab, lr)
+            g = eng.train_grads()
+            assert set(g) == set(names)
+            opt.update(g, lr)
+            got = eng.train_tensors()
+            worst = 0.0
+            for name in names:
+                bar = np.spacing(np.abs(got[name])).astype(np.float64) + 1e-5 * lr
+                d = np.abs(got[name].astype(np.float64) - opt.p[name])
+                worst = max(worst, float((d / bar).max()))
+                assert (d <= bar).all(), (s, name, float(d.max()))
+            print("step %d: 341 tensors, worst |d| / bar %.3g" % (s, worst))
+            opt.p = {k: got[k].astype(np.float64) for k in names}     # the next step starts from the GPU's own fp32 parameters
+        assert (got["dense/kernel"] != w["dense/kernel"]).any()
+        sig, lab = _batch(n, 60)
+        eng.train_step_signal(sig, lab, 0.0)      # lr = 0: not a bit of a parameter changes (the moments still move)
+        same = eng.train_tensors()
+        for name in names:
+            assert same[name].tobytes() == got[name].tobytes(), name
+    finally:
+        eng.close()
+
+
+def test_a_narrow_step_is_isolated_from_the_wide_one_before():
+    """`part` ([64][2][256]) and `slab` ([64][largest kernel]) are scratch that every step reuses. Handle A takes 900 rows (R = 18000
+    / 9000 / 4500 / 2700: all 64 slabs filled at the first two widths), then 6 rows (R = 120 / 60 / 30 / 18: one slab); handle B
+    takes one unrelated row, then the same 6. Everything at lr = 0, so the parameters stand still, a training-mode forward uses
+    batch statistics only, and the masks depend on (seed, step, row): step 1 agrees bit for bit between the two -- loss,
+    predictions, every tap, all 341 gradients, both masks (the moving statistics legitimately differ). And A's step 1 is the
+    float64 statement's for these 6 rows alone, at the bars of test_gpu_train_signal_grad.py: taps, decisions (at most 16 differing
+    places, each inside its margin), gradients under the GPU's decisions, loss."""
+    from deepsignal_amd import engine
+    w, n, keep, seed = _w(), 6, 0.5, 8
+    wide_s, wide_l = _batch(900, 90)
+    one_s, one_l = _batch(1, 92)
+    sig, lab = _batch(n, 91)
+    out = []
+    for first_s, first_l in ((wide_s, wide_l), (one_s, one_l)):
+        eng = _engine(w, max_batch=1024)
+        try:
+            eng.train_begin(keep_prob=keep, seed=seed)
+            eng.train_step_signal(first_s, first_l, 0.0)
+            loss, pred = eng.train_step_signal(sig, lab, 0.0)
+            out.append((loss, pred, {name: eng.train_tap(name, n) for name in engine.signal_tap_names()}, eng.train_grads(),
+                        {s: eng.train_mask(s, n) for s in engine.SIGNAL_MASK_STREAMS}, eng.train_tensors()))
+        finally:
+            eng.close()
+    (loss, pred, taps, grads, masks, after), other = out
+    assert loss == other[0] and pred.tobytes() == other[1].tobytes()
+    for k in (2, 3, 4):
+        _same_bits(out[0][k], other[k])
+    names = tss.trainable_names(S)
+    assert len(names) == 341 and set(grads) == set(names)
+    for name in names:
+        assert after[name].tobytes() == np.ascontiguousarray(w[name], np.float32).tobytes(), name
+    for s, m in masks.items():
+        assert (m == engine.train_mask_reference_wide(seed, 1, s, n, m.shape[1], keep)).all(), s
+
+    # the statement for the 6 rows alone
+    _, _, _, free64 = tss.step(w, sig, lab, masks, keep, 1.0, torch.float64, grad=False)
+    _, _, _, free32 = tss.step(w, sig, lab, masks, keep, 1.0, torch.float32, grad=False)
+    assert set(taps) == set(free64.taps)
+    bars = {}
+    for name, t in taps.items():
+        ref = free64.taps[name].to(torch.float64).numpy()
+        bars[name] = (4 * max(tss.rel_err(free32.taps[name].to(torch.float64).numpy(), ref), 1e-6), float(np.abs(ref).max()))
+        assert tss.rel_err(t, ref) <= bars[name][0], (name, tss.rel_err(t, ref), bars[name][0])
+    dec = tss.decisions_from_taps(taps)
+    diffs = tss.decision_differences(dec, free64)
+    print("narrow after wide: decisions differ from the float64 statement's in %d places: %s" % (sum(d[1] for d in diffs), diffs))
+    assert sum(d[1] for d in diffs) <= 16
+    for name, _, margin, tap in diffs:
+        assert margin <= bars[tap][0] * bars[tap][1], (name, tap, margin)
+    loss64, logits64, g64, _ = tss.step(w, sig, lab, masks, keep, 1.0, torch.float64, dec=dec)
+    loss32, logits32, g32, _ = tss.step(w, sig, lab, masks, keep, 1.0, torch.float32, dec=dec)
+    worst = 0.0
+    for name in names:
+        e, bar = tss.rel_err(grads[name], g64[name]), 4 * max(tss.rel_err(g32[name], g64[name]), 1e-6)
+        worst = max(worst, e / bar)
+        assert e <= bar, (name, e, bar)
+    loss_bar = 4 * max(float(np.abs(logits32 - logits64).max()), 2.0 ** -22 * float(np.abs(logits64).max()))
+    print("narrow after wide: 341 gradients, worst distance / bar %.3g; loss gpu %.9g f64 %.9g |d| %.3g bar %.3g"
+          % (worst, loss, loss64, abs(loss - loss64), loss_bar))
+    assert abs(loss - loss64) <= loss_bar
+    decided = np.abs(logits64[:, 1] - logits64[:, 0]) > loss_bar
+    assert (pred[decided] == tss.pred_of(logits64, 1.0)[decided]).all()
 
 
 def test_moving_statistics_three_steps():
