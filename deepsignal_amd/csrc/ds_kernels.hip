@@ -622,7 +622,8 @@ hipError_t launch_gemm(GemmCfg cfg, const GemmLaunch* d_launch, int total_tiles,
         // configure_fused_kernels). The ring loop's own footprint (129 VGPRs, 46 KB of static LDS) lets the dispatcher stack three dense
         // workgroups on a CU or put one beside a fused module, where no BiLSTM cell fits any more; launched that way the pipelined step
         // is SLOWER than the parent's (-1.7 %), with 46 + 56 KB -- room for four cell workgroups beside it and nothing else -- it is
-        // faster (+2.2 %): profiles/dense_ring_ab.json, profiles/EXPERIMENTS.md.
+        // faster (+2.2 %): profiles/dense_ring_ab.json, profiles/EXPERIMENTS.md. 46 + 52 KB would seat a FIFTH cell workgroup (158 KB,
+        // 136 + 5 x 72 = 496 registers per SIMD): measured, -0.1 % alone and no better than 56 KB at any cell priority (profiles/cell_guest_ab.json).
         hipLaunchKernelGGL((gemm_kernel<1, 3, 4, 1, 0, 2, 2, 1>), dim3(total_tiles), dim3(256), DR_SOLO_PAD_BYTES, s, d_launch);
         break;
     case CFG_BCONV: hipLaunchKernelGGL((gemm_kernel<1, 2, 4, 1, 0, 0, 1, 1, true>), dim3(total_tiles), dim3(256), 0, s, d_launch); break;
@@ -762,6 +763,24 @@ __global__ __launch_bounds__(256, NT == 1 ? 4 : 2) void lstm_cell_kernel(const L
 // stages of KGS k-groups (1 at NT = 1, 2 at NT = 2), requests two stages ahead, ONE barrier per stage, a counted vmcnt in
 // front of it so the next stage's requests stay in flight across the barrier.
 // (glds16 / glds16s, the LDS-DMA requests, live in ds_device.h)
+//
+// DS_CELL_PRIO: issue priority (s_setprio) of a cell wave from the K loop's entry on; it goes back to 0 behind the loop, or, with
+// DS_CELL_PRIO_GATES = 1, behind the gate arithmetic and the stores. A cell workgroup is a guest on a CU whose fused-module or
+// dense waves live 100 - 300 us, are the oldest, and win every oldest-first arbitration among equals; and the joint model of a
+// forward waits for the 19 dependent cell launches, not for the signal branch (median 582 us, in every forward:
+// profiles/branch_balance_parent.json). Measured on the pipelined 512-site step against the parent (0), libraries alternating,
+// four runs a side, k sites/s (profiles/cell_guest_ab.json): K loop only, level 1 / 2 / 3: 450.1 / 450.1 / 449.7 against 447.8
+// (+0.5 / +0.5 / +0.4 %); held through the gates, level 1: 453.0 (+1.16 %); a session of its own, held through the gates, level
+// 1 / 2 / 3: 455.1 / 454.8 / 455.5 against 450.1 (+1.1 / +1.1 / +1.2 %, the three within the parent's own 0.24 % spread). The
+// epilogue's 40 transcendental instructions are where a guest waits longest for issue, so more than half of the gain is there;
+// the level does not matter, so it is the lowest. The code is the parent's but for the two s_setprio (and one s_nop count behind
+// the loop); results are bit-identical.
+#ifndef DS_CELL_PRIO
+#define DS_CELL_PRIO 1
+#endif
+#ifndef DS_CELL_PRIO_GATES
+#define DS_CELL_PRIO_GATES 1
+#endif
 __device__ __forceinline__ floatx16 mfma_bf_early(float4 a, float4 b, floatx16 c)
 {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
@@ -872,6 +891,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 7 : 2) void lstm_cell_lds_kernel(con
         asm volatile("" : "+v"(acc[nt]));          // bias loads land directly in the accumulator registers
     }
     DS_LSTAMP(2, __builtin_amdgcn_s_memtime());
+    if constexpr (DS_CELL_PRIO != 0) __builtin_amdgcn_s_setprio(DS_CELL_PRIO);      // the K loop's issue priority (see DS_CELL_PRIO)
     // stage st has landed in LDS once every wave's requests for it are done: counted wait (stage st + 1 stays in
     // flight), then the barrier; it also tells everybody that ring slot (st + 2) % 3 -- read during stage st - 1 -- is
     // free again. The ring index is a compile-time constant of each of the three unrolled bodies, so every LDS address
@@ -904,6 +924,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 7 : 2) void lstm_cell_lds_kernel(con
     }
 
     DS_LSTAMP(3, __builtin_amdgcn_s_memtime());
+    if constexpr (DS_CELL_PRIO != 0 && !DS_CELL_PRIO_GATES) __builtin_amdgcn_s_setprio(0);
     if (!valid) return;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -917,6 +938,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 7 : 2) void lstm_cell_lds_kernel(con
         if (C.h_row && row < n)
             *(__attribute__((address_space(1))) v4f*)(C.h_row + (size_t)row * 256 + ntile * 8 + 4 * half) = ho;
     }
+    if constexpr (DS_CELL_PRIO != 0 && DS_CELL_PRIO_GATES) __builtin_amdgcn_s_setprio(0);
     DS_LSTAMP(4, __builtin_amdgcn_s_memtime());
     DS_LSTAMP(5, __builtin_amdgcn_s_memrealtime());
 #undef DS_LSTAMP
@@ -1158,7 +1180,8 @@ hipError_t launch_lstm_cells(LstmTile tile, const LstmLaunch& L, hipStream_t s)
 #ifndef DS_FUSED_BD
 #define DS_FUSED_BD 2
 #endif
-// (s_setprio 2 for the fp32 pooling waves, as in the bf16 kernel, was measured: 625 against 586 us per step)
+// (s_setprio 2 for the fp32 pooling waves, as in the bf16 kernel, was measured: 625 against 586 us per step; the BiLSTM cell
+// waves' own priority is DS_CELL_PRIO, defined in front of lstm_cell_lds_kernel)
 #ifndef DS_FUSED_POOLPRIO
 #define DS_FUSED_POOLPRIO 0
 #endif
