@@ -279,8 +279,7 @@ struct ds_handle {
     // weights (`weight_allocs`), so that ds_train_sync_weights can pack the current parameters in their place
     std::map<std::string, HostTensor> kept;
     std::vector<void*> weight_allocs;
-    dstr::Trainer* train = nullptr;
-    dsts::Trainer* strain = nullptr;      // the signal-only variant's run (ds_train_begin_signal, ds_train_signal.hip): one of the two at most
+    dstr::Run* train = nullptr;           // the open run: a dstr::Trainer (BiLSTM variants) or a dsts::Trainer (signal-only), as the handle's variant decides
     bool training = false;
     // pipelining: consecutive forwards rotate over independent slots (own workspace, streams, graphs), so the
     // dependency chain of one 512-site forward overlaps the next ones'; weights are shared
@@ -1751,7 +1750,6 @@ void ds_destroy(ds_handle* h)
     h->combine.close();
     h->eval.close();
     delete h->train;
-    delete h->strain;
     for (void* p : h->allocs) hipFree(p);
     (void)hipGetLastError();      // nothing a teardown call returned may surface in a later handle's first launch
     delete h;
@@ -3250,52 +3248,64 @@ int ds_set_graph(ds_handle* h, int32_t enable)
     return DS_OK;
 }
 
-// ---- training step of the RNN-only model (ds_train.hip; model.py:70-116 with the optimiser of train.py / denoise.py) ------------
-// The run's state is a dstr::Trainer of its own (parameters, moments, stored activations, stream): the inference plan and the
-// pipeline slots are untouched until ds_train_sync_weights packs the current parameters for them.
+// ---- training (ds_train.hip: the run core and the RNN-only model, model.py:70-116 with the optimiser of train.py / denoise.py;
+// ds_train_signal.hip: the signal-only model, model.py:89-95, layers.py:80-139,176-264) ---------------------------------------------
+// The run's state is a dstr::Run of its own (parameters, moments, stored activations, stream): the inference plan and the
+// pipeline slots are untouched until ds_train_sync_weights packs the current parameters for them. A handle is one variant, so
+// which Trainer h->train is follows from h->is_cnn.
 static int train_ready(ds_handle* h, const char* who)
 {
     if (!h) return DS_ERR_INVALID;
-    if ((!h->train && !h->strain) || !h->training) return fail(h, DS_ERR_INVALID, std::string(who) + ": no training run is open (ds_train_begin first)");
+    if (!h->train || !h->training) return fail(h, DS_ERR_INVALID, std::string(who) + ": no training run is open (ds_train_begin first)");
     if (tickets_in_flight(h)) return fail(h, DS_ERR_INVALID, std::string(who) + ": pipeline tickets are still in flight");
     return DS_OK;
 }
 
-// `with_base`: ds_train_begin_base, which takes an is_base 1 handle too; ds_train_begin keeps refusing it
-static int ds_train_begin_impl(ds_handle* h, const ds_train_config* cfg, bool with_base)
+// what every begin checks once the variant is accepted, and the run's configuration with TF's defaults for beta1, beta2, epsilon 0
+static int check_train_config(ds_handle* h, const std::string& me, const ds_train_config* cfg, dstr::Config* c)
+{
+    if (h->C != 2) return fail(h, DS_ERR_UNSUPPORTED, me + ": class_num must be 2");
+    if (h->cfg.precision != DS_PRECISION_FP32) return fail(h, DS_ERR_UNSUPPORTED, me + ": precision must be DS_PRECISION_FP32");
+    if (h->is_cnn && h->J > dsts::MAX_JOINT)
+        return fail(h, DS_ERR_UNSUPPORTED, me + ": the joint width J = " + std::to_string(h->J) + " exceeds 65535: the dropout mask function packs a row's unit into 16 bits, so wider fc1 rows would repeat masks");
+    if (!h->finalized) return fail(h, DS_ERR_INVALID, me + ": weights not loaded");
+    if (tickets_in_flight(h)) return fail(h, DS_ERR_INVALID, me + ": pipeline tickets are still in flight");
+    if (!(cfg->keep_prob > 0.f && cfg->keep_prob <= 1.f)) return fail(h, DS_ERR_INVALID, me + ": keep_prob must lie in (0, 1]");
+    if (!(cfg->pos_weight > 0.f) || std::isinf(cfg->pos_weight)) return fail(h, DS_ERR_INVALID, me + ": pos_weight must be positive and finite");
+    if (cfg->beta1 < 0.f || cfg->beta1 >= 1.f || cfg->beta2 < 0.f || cfg->beta2 >= 1.f || cfg->epsilon < 0.f || std::isnan(cfg->beta1 + cfg->beta2 + cfg->epsilon))
+        return fail(h, DS_ERR_INVALID, me + ": beta1, beta2 must lie in [0, 1) and epsilon must not be negative");
+    c->keep_prob = cfg->keep_prob; c->pos_weight = cfg->pos_weight; c->seed = cfg->seed;
+    if (cfg->beta1 != 0.f) c->beta1 = cfg->beta1;
+    if (cfg->beta2 != 0.f) c->beta2 = cfg->beta2;
+    if (cfg->epsilon != 0.f) c->epsilon = cfg->epsilon;
+    return DS_OK;
+}
+
+// ds_train_begin (`with_base` 0), ds_train_begin_base (which takes an is_base 1 handle too; ds_train_begin keeps refusing it) and
+// ds_train_begin_signal (`signal`). The run is created once: a re-begin at the same shape keeps its allocations.
+static int ds_train_begin_impl(ds_handle* h, const char* who, const ds_train_config* cfg, bool signal, bool with_base)
 {
     if (!h) return DS_ERR_INVALID;
-    if (!cfg) return fail(h, DS_ERR_INVALID, "ds_train_begin: null config");
-    if (h->is_cnn) return fail(h, DS_ERR_UNSUPPORTED, "ds_train_begin: this release trains the RNN-only model (is_cnn must be 0: the signal model has no backward)");
-    if (!h->is_rnn) return fail(h, DS_ERR_UNSUPPORTED, "ds_train_begin: this release trains the RNN-only model (is_rnn must be 1)");
-    if (h->is_base && !with_base)
-        return fail(h, DS_ERR_UNSUPPORTED, "ds_train_begin: is_base must be 0 here (the embedding is trained through ds_train_begin_base / ds_train_step_base)");
-    if (h->C != 2) return fail(h, DS_ERR_UNSUPPORTED, "ds_train_begin: class_num must be 2");
-    if (h->cfg.precision != DS_PRECISION_FP32) return fail(h, DS_ERR_UNSUPPORTED, "ds_train_begin: precision must be DS_PRECISION_FP32");
-    if (!h->finalized) return fail(h, DS_ERR_INVALID, "ds_train_begin: weights not loaded");
-    if (tickets_in_flight(h)) return fail(h, DS_ERR_INVALID, "ds_train_begin: pipeline tickets are still in flight");
-    if (!(cfg->keep_prob > 0.f && cfg->keep_prob <= 1.f)) return fail(h, DS_ERR_INVALID, "ds_train_begin: keep_prob must lie in (0, 1]");
-    if (!(cfg->pos_weight > 0.f) || std::isinf(cfg->pos_weight)) return fail(h, DS_ERR_INVALID, "ds_train_begin: pos_weight must be positive and finite");
-    if (cfg->beta1 < 0.f || cfg->beta1 >= 1.f || cfg->beta2 < 0.f || cfg->beta2 >= 1.f || cfg->epsilon < 0.f || std::isnan(cfg->beta1 + cfg->beta2 + cfg->epsilon))
-        return fail(h, DS_ERR_INVALID, "ds_train_begin: beta1, beta2 must lie in [0, 1) and epsilon must not be negative");
-    const int in0 = dstr::in0_of(h->is_base);
-    std::vector<float> params((size_t)dstr::param_floats(in0));
-    for (int i = 0; i < dstr::ntensor(in0); ++i) {
-        const std::string name = dstr::tensor_name(i);
-        auto it = h->kept.find(name);
-        if (it == h->kept.end() || (int64_t)it->second.data.size() != dstr::tensor_floats(i, in0))
-            return fail(h, DS_ERR_INVALID, "ds_train_begin: missing/bad tensor " + name);
-        std::copy(it->second.data.begin(), it->second.data.end(), params.begin() + dstr::tensor_off(i, in0));
+    const std::string me = who;
+    if (!cfg) return fail(h, DS_ERR_INVALID, me + ": null config");
+    if (signal) {
+        if (!h->is_cnn || h->is_rnn)
+            return fail(h, DS_ERR_UNSUPPORTED, me + ": trains the signal model alone (is_cnn must be 1 and is_rnn 0; the BiLSTM variants go through ds_train_begin / ds_train_begin_base)");
+    } else {
+        if (h->is_cnn) return fail(h, DS_ERR_UNSUPPORTED, me + ": this release trains the RNN-only model (is_cnn must be 0: the signal model has no backward)");
+        if (!h->is_rnn) return fail(h, DS_ERR_UNSUPPORTED, me + ": this release trains the RNN-only model (is_rnn must be 1)");
+        if (h->is_base && !with_base)
+            return fail(h, DS_ERR_UNSUPPORTED, me + ": is_base must be 0 here (the embedding is trained through ds_train_begin_base / ds_train_step_base)");
     }
     dstr::Config c;
-    c.keep_prob = cfg->keep_prob; c.pos_weight = cfg->pos_weight; c.seed = cfg->seed;
-    if (cfg->beta1 != 0.f) c.beta1 = cfg->beta1;
-    if (cfg->beta2 != 0.f) c.beta2 = cfg->beta2;
-    if (cfg->epsilon != 0.f) c.epsilon = cfg->epsilon;
-    if (!h->train) h->train = new dstr::Trainer();
+    if (int rc = check_train_config(h, me, cfg, &c)) return rc;
+    dstr::TensorMap w;
+    for (const auto& kv : h->kept) w[kv.first] = kv.second.data;
+    if (!h->train) h->train = signal ? static_cast<dstr::Run*>(new dsts::Trainer()) : new dstr::Trainer();
     std::string err;
-    const int rc = h->train->begin(h->cfg.device, h->T, h->B, in0, c, params.data(), &err);
-    if (rc) { delete h->train; h->train = nullptr; h->training = false; return fail(h, rc, "ds_train_begin: " + err); }
+    const int rc = signal ? static_cast<dsts::Trainer*>(h->train)->begin(h->cfg.device, h->S, h->B, c, w, &err)
+                          : static_cast<dstr::Trainer*>(h->train)->begin(h->cfg.device, h->T, h->B, dstr::in0_of(h->is_base), c, w, &err);
+    if (rc) { delete h->train; h->train = nullptr; h->training = false; return fail(h, rc, me + ": " + err); }
     h->training = true;
     return DS_OK;
 }
@@ -3304,34 +3314,32 @@ static int ds_train_set_tensor_impl(ds_handle* h, const char* name, const float*
 {
     if (!h || !name || !data) return fail(h, DS_ERR_INVALID, "ds_train_set_tensor: bad argument");
     if (!h->finalized || h->kept.empty()) return fail(h, DS_ERR_INVALID, "ds_train_set_tensor: the handle holds no trainable weights (RNN-only or signal-only, loaded)");
-    if (h->is_cnn) {      // the signal-only variant: any tensor it was loaded with, moving statistics included
-        auto it = h->kept.find(name);
-        if (it == h->kept.end() || count != (int64_t)it->second.data.size()) return fail(h, DS_ERR_INVALID, std::string("ds_train_set_tensor: unknown tensor or wrong size: ") + name);
-        it->second.data.assign(data, data + count);
-        return DS_OK;
-    }
-    const int idx = dstr::tensor_index(name), in0 = dstr::in0_of(h->is_base);
-    if (idx < 0 || idx >= dstr::ntensor(in0) || count != dstr::tensor_floats(idx, in0)) return fail(h, DS_ERR_INVALID, std::string("ds_train_set_tensor: unknown tensor or wrong size: ") + name);
-    h->kept[name].data.assign(data, data + count);
+    // the signal-only variant: any tensor it was loaded with, moving statistics included; a BiLSTM variant: the tensors it trains
+    auto it = h->kept.find(name);
+    const bool known = it != h->kept.end() && (h->is_cnn || dstr::bilstm_tensors(dstr::in0_of(h->is_base)).count(name));
+    if (!known || count != (int64_t)it->second.data.size()) return fail(h, DS_ERR_INVALID, std::string("ds_train_set_tensor: unknown tensor or wrong size: ") + name);
+    it->second.data.assign(data, data + count);
     return DS_OK;
 }
 
-// ds_train_step (kmer = nullptr, no codes to give), ds_train_step_base and ds_train_eval (`eval`; lr unused)
-static int ds_train_step_impl(ds_handle* h, const char* who, bool eval, int32_t n, const int32_t* kmer, const float* means, const float* stds,
-                              const float* sanums, const int32_t* labels, float lr, float* loss, int32_t* pred, float* logits)
+// every step and evaluation entry (`eval`; lr unused). The entry names the buffers its variant needs: `signal` takes in.signals,
+// the BiLSTM variants in.means, in.stds, in.lens and, with the embedding trained, in.kmer.
+static int ds_train_run_impl(ds_handle* h, const char* who, bool signal, bool eval, int32_t n, const dstr::Inputs& in, float lr, float* loss, int32_t* pred,
+                             float* logits)
 {
     const std::string me = who;
     if (int rc = train_ready(h, who)) return rc;
-    if (!h->train) return fail(h, DS_ERR_INVALID, me + ": this run trains the signal model (is_cnn 1, is_rnn 0): ds_train_step_signal / ds_train_eval_signal");
+    if (signal && !h->is_cnn) return fail(h, DS_ERR_INVALID, me + ": this run trains a BiLSTM variant (is_rnn 1): ds_train_step / ds_train_step_base / ds_train_eval");
+    if (!signal && h->is_cnn) return fail(h, DS_ERR_INVALID, me + ": this run trains the signal model (is_cnn 1, is_rnn 0): ds_train_step_signal / ds_train_eval_signal");
     if (n < 1 || n > h->B) return fail(h, DS_ERR_INVALID, me + ": n must lie in [1, max_batch]");
-    if (!means || !stds || !sanums || !labels) return fail(h, DS_ERR_INVALID, me + ": null buffer");
-    if (h->train->in0 != dstr::NFEAT && !kmer)
+    if (signal ? !in.signals || !in.labels : !in.means || !in.stds || !in.lens || !in.labels) return fail(h, DS_ERR_INVALID, me + ": null buffer");
+    if (!signal && h->is_base && !in.kmer)
         return fail(h, DS_ERR_INVALID, me + ": this run trains the embedding (is_base 1) and needs the k-mer codes: ds_train_step_base");
     if (std::isnan(lr)) return fail(h, DS_ERR_INVALID, me + ": lr is NaN");
     for (int32_t i = 0; i < n; ++i)
-        if (labels[i] != 0 && labels[i] != 1) return fail(h, DS_ERR_INVALID, me + ": label " + std::to_string(labels[i]) + " of row " + std::to_string(i) + " is outside {0, 1}");
+        if (in.labels[i] != 0 && in.labels[i] != 1) return fail(h, DS_ERR_INVALID, me + ": label " + std::to_string(in.labels[i]) + " of row " + std::to_string(i) + " is outside {0, 1}");
     std::string err;
-    const int rc = h->train->run(eval, n, kmer, means, stds, sanums, labels, lr, loss, pred, logits, &err);
+    const int rc = h->train->step(eval, n, in, lr, loss, pred, logits, &err);
     return rc ? fail(h, rc, me + ": " + err) : DS_OK;
 }
 
@@ -3339,12 +3347,9 @@ static int ds_train_sync_weights_impl(ds_handle* h)
 {
     if (int rc = train_ready(h, "ds_train_sync_weights")) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int in0 = h->train ? h->train->in0 : 0;
-    std::vector<float> params(h->train ? (size_t)dstr::param_floats(in0) : 0);
-    std::map<std::string, std::vector<float>> all;      // a signal run: every tensor by name, the moving statistics included
+    dstr::TensorMap all;      // every tensor of the run by name, a signal run's moving statistics included
     std::string err;
-    if (h->train) { if (int rc = h->train->read_params(params.data(), &err)) return fail(h, rc, "ds_train_sync_weights: " + err); }
-    else if (int rc = h->strain->read_all(&all, &err)) return fail(h, rc, "ds_train_sync_weights: " + err);
+    if (int rc = h->train->read_all(&all, &err)) return fail(h, rc, "ds_train_sync_weights: " + err);
     // nothing enqueued may still read the packed weights; the plans (launch descriptors, captured graphs) name them and go too
     for (Slot& sl : h->slots) {
         HIPCHK(h, hipStreamSynchronize(sl.s0));
@@ -3367,13 +3372,6 @@ static int ds_train_sync_weights_impl(ds_handle* h)
         t.data = std::move(kv.second);
         h->host[kv.first] = std::move(t);
     }
-    for (int i = 0; h->train && i < dstr::ntensor(in0); ++i) {
-        const std::string name = dstr::tensor_name(i);
-        HostTensor t;
-        t.shape = loaded[name].shape;
-        t.data.assign(params.begin() + dstr::tensor_off(i, in0), params.begin() + dstr::tensor_off(i, in0) + dstr::tensor_floats(i, in0));
-        h->host[name] = std::move(t);
-    }
     h->finalized = false;
     h->cur = &h->slots[0];
     const int rc = ds_finalize_weights_impl(h);
@@ -3384,15 +3382,8 @@ static int ds_train_sync_weights_impl(ds_handle* h)
 static int64_t train_get(ds_handle* h, const char* who, const char* name, float* out, int64_t cap, bool grad)
 {
     if (int rc = train_ready(h, who)) return rc;
-    if (h->strain) {
-        std::string err;
-        const int64_t rc = h->strain->get(name, grad, out, cap, &err);
-        return rc < 0 ? fail(h, (int)rc, std::string(who) + ": " + err) : rc;
-    }
-    const int idx = dstr::tensor_index(name);
-    if (idx < 0 || idx >= dstr::ntensor(h->train->in0) || !out) return fail(h, DS_ERR_INVALID, std::string(who) + ": unknown tensor " + (name ? name : "(null)"));
     std::string err;
-    const int64_t rc = h->train->get(grad ? h->train->G : h->train->P, idx, out, cap, &err);
+    const int64_t rc = h->train->get(name, grad, out, cap, &err);
     return rc < 0 ? fail(h, (int)rc, std::string(who) + ": " + err) : rc;
 }
 
@@ -3401,16 +3392,12 @@ static int64_t ds_train_get_mask_impl(ds_handle* h, const char* stream, uint8_t*
     if (int rc = train_ready(h, "ds_train_get_mask")) return rc;
     const int sid = dstr::stream_index(stream);
     if (sid < 0 || !out) return fail(h, DS_ERR_INVALID, std::string("ds_train_get_mask: unknown stream ") + (stream ? stream : "(null)"));
-    if (h->strain) {
-        if (sid != dstr::STREAM_FC1 && sid != dstr::STREAM_FC2) return fail(h, DS_ERR_INVALID, std::string("ds_train_get_mask: a signal run has the streams fc1 and fc2 only, not ") + stream);
-        if (h->strain->last_n == 0) return fail(h, DS_ERR_INVALID, "ds_train_get_mask: no step has run yet");
-        std::string err;
-        const int64_t rc = h->strain->get_mask(sid, out, cap, &err);
-        return rc < 0 ? fail(h, (int)rc, "ds_train_get_mask: " + err) : rc;
-    }
+    if (h->is_cnn && sid < dstr::STREAM_FC1) return fail(h, DS_ERR_INVALID, std::string("ds_train_get_mask: a signal run has the streams fc1 and fc2 only, not ") + stream);
     if (h->train->last_n == 0) return fail(h, DS_ERR_INVALID, "ds_train_get_mask: no step has run yet");
+    // a cell's stream: [n][T][256]; fc1: [n][J]; fc2: [n][2]
+    const int steps = sid < dstr::STREAM_FC1 ? h->T : 1, W = sid < dstr::STREAM_FC1 ? dstr::HID : sid == dstr::STREAM_FC1 ? h->train->J : dstr::NCLASS;
     std::string err;
-    const int64_t rc = h->train->get_mask(sid, out, cap, &err);
+    const int64_t rc = h->train->get_mask(sid, steps, W, out, cap, &err);
     return rc < 0 ? fail(h, (int)rc, "ds_train_get_mask: " + err) : rc;
 }
 
@@ -3420,67 +3407,16 @@ int ds_train_end(ds_handle* h)
     hipSetDevice(h->cfg.device);
     delete h->train;
     h->train = nullptr;
-    delete h->strain;
-    h->strain = nullptr;
     h->training = false;
     return DS_OK;
-}
-
-// ---- training step of the signal-only model (ds_train_signal.hip; model.py:89-95, layers.py:80-139,176-264) -------------------------
-static int ds_train_begin_signal_impl(ds_handle* h, const ds_train_config* cfg)
-{
-    if (!h) return DS_ERR_INVALID;
-    const std::string me = "ds_train_begin_signal";
-    if (!cfg) return fail(h, DS_ERR_INVALID, me + ": null config");
-    if (!h->is_cnn || h->is_rnn)
-        return fail(h, DS_ERR_UNSUPPORTED, me + ": trains the signal model alone (is_cnn must be 1 and is_rnn 0; the BiLSTM variants go through ds_train_begin / ds_train_begin_base)");
-    if (h->C != 2) return fail(h, DS_ERR_UNSUPPORTED, me + ": class_num must be 2");
-    if (h->cfg.precision != DS_PRECISION_FP32) return fail(h, DS_ERR_UNSUPPORTED, me + ": precision must be DS_PRECISION_FP32");
-    if (h->J > dsts::MAX_JOINT)
-        return fail(h, DS_ERR_UNSUPPORTED, me + ": the joint width J = " + std::to_string(h->J) + " exceeds 65535: the dropout mask function packs a row's unit into 16 bits, so wider fc1 rows would repeat masks");
-    if (!h->finalized) return fail(h, DS_ERR_INVALID, me + ": weights not loaded");
-    if (tickets_in_flight(h)) return fail(h, DS_ERR_INVALID, me + ": pipeline tickets are still in flight");
-    if (!(cfg->keep_prob > 0.f && cfg->keep_prob <= 1.f)) return fail(h, DS_ERR_INVALID, me + ": keep_prob must lie in (0, 1]");
-    if (!(cfg->pos_weight > 0.f) || std::isinf(cfg->pos_weight)) return fail(h, DS_ERR_INVALID, me + ": pos_weight must be positive and finite");
-    if (cfg->beta1 < 0.f || cfg->beta1 >= 1.f || cfg->beta2 < 0.f || cfg->beta2 >= 1.f || cfg->epsilon < 0.f || std::isnan(cfg->beta1 + cfg->beta2 + cfg->epsilon))
-        return fail(h, DS_ERR_INVALID, me + ": beta1, beta2 must lie in [0, 1) and epsilon must not be negative");
-    std::map<std::string, std::vector<float>> w;
-    for (const auto& kv : h->kept) w[kv.first] = kv.second.data;
-    dstr::Config c;
-    c.keep_prob = cfg->keep_prob; c.pos_weight = cfg->pos_weight; c.seed = cfg->seed;
-    if (cfg->beta1 != 0.f) c.beta1 = cfg->beta1;
-    if (cfg->beta2 != 0.f) c.beta2 = cfg->beta2;
-    if (cfg->epsilon != 0.f) c.epsilon = cfg->epsilon;
-    if (!h->strain) h->strain = new dsts::Trainer();
-    std::string err;
-    const int rc = h->strain->begin(h->cfg.device, h->S, h->B, c, w, &err);
-    if (rc) { delete h->strain; h->strain = nullptr; h->training = false; return fail(h, rc, me + ": " + err); }
-    h->training = true;
-    return DS_OK;
-}
-
-static int ds_train_run_signal_impl(ds_handle* h, const char* who, bool eval, int32_t n, const float* signals, const int32_t* labels, float lr,
-                                    float* loss, int32_t* pred, float* logits)
-{
-    const std::string me = who;
-    if (int rc = train_ready(h, who)) return rc;
-    if (!h->strain) return fail(h, DS_ERR_INVALID, me + ": this run trains a BiLSTM variant (is_rnn 1): ds_train_step / ds_train_step_base / ds_train_eval");
-    if (n < 1 || n > h->B) return fail(h, DS_ERR_INVALID, me + ": n must lie in [1, max_batch]");
-    if (!signals || !labels) return fail(h, DS_ERR_INVALID, me + ": null buffer");
-    if (std::isnan(lr)) return fail(h, DS_ERR_INVALID, me + ": lr is NaN");
-    for (int32_t i = 0; i < n; ++i)
-        if (labels[i] != 0 && labels[i] != 1) return fail(h, DS_ERR_INVALID, me + ": label " + std::to_string(labels[i]) + " of row " + std::to_string(i) + " is outside {0, 1}");
-    std::string err;
-    const int rc = h->strain->run(eval, n, signals, labels, lr, loss, pred, logits, &err);
-    return rc ? fail(h, rc, me + ": " + err) : DS_OK;
 }
 
 static int64_t ds_train_get_tap_impl(ds_handle* h, const char* name, float* out, int64_t cap)
 {
     if (int rc = train_ready(h, "ds_train_get_tap")) return rc;
-    if (!h->strain) return fail(h, DS_ERR_INVALID, "ds_train_get_tap: only a signal run (ds_train_begin_signal) keeps taps");
+    if (!h->is_cnn) return fail(h, DS_ERR_INVALID, "ds_train_get_tap: only a signal run (ds_train_begin_signal) keeps taps");
     std::string err;
-    const int64_t rc = h->strain->get_tap(name, out, cap, &err);
+    const int64_t rc = static_cast<dsts::Trainer*>(h->train)->get_tap(name, out, cap, &err);
     return rc < 0 ? fail(h, (int)rc, "ds_train_get_tap: " + err) : rc;
 }
 
@@ -3489,7 +3425,7 @@ int ds_train_mask_reference_wide(uint64_t seed, int64_t step, const char* stream
     const int sid = dstr::stream_index(stream);
     if ((sid != dstr::STREAM_FC1 && sid != dstr::STREAM_FC2) || n < 0 || width < 1 || width > dsts::MAX_JOINT || !out || !(keep_prob > 0.f && keep_prob <= 1.f))
         return DS_ERR_INVALID;
-    dsts::mask_reference_wide(seed, step, sid, n, width, keep_prob, out);
+    dstr::mask_reference(seed, step, sid, n, 1, width, keep_prob, out);
     return DS_OK;
 }
 
@@ -3497,30 +3433,29 @@ int ds_train_mask_reference(uint64_t seed, int64_t step, const char* stream, int
 {
     const int sid = dstr::stream_index(stream);
     if (sid < 0 || n < 0 || kmer_len < 1 || !out || !(keep_prob > 0.f && keep_prob <= 1.f)) return DS_ERR_INVALID;
-    dstr::mask_reference(seed, step, sid, n, kmer_len, keep_prob, out);
+    dstr::mask_reference(seed, step, sid, n, sid < dstr::STREAM_FC1 ? kmer_len : 1, dstr::stream_width(sid), keep_prob, out);
     return DS_OK;
 }
 
 int ds_get_train_times(ds_handle* h, int32_t reset, int64_t* steps, double* ms)
 {
     if (!h || !steps || !ms) return DS_ERR_INVALID;
-    *steps = h->train ? h->train->steps_timed : h->strain ? h->strain->steps_timed : 0;
-    for (int i = 0; i < dstr::NPHASE; ++i) ms[i] = h->train ? h->train->ms[i] : h->strain ? h->strain->ms[i] : 0.0;
+    *steps = h->train ? h->train->steps_timed : 0;
+    for (int i = 0; i < dstr::NPHASE; ++i) ms[i] = h->train ? h->train->ms[i] : 0.0;
     if (reset && h->train) { h->train->steps_timed = 0; for (double& v : h->train->ms) v = 0; }
-    if (reset && h->strain) { h->strain->steps_timed = 0; for (double& v : h->strain->ms) v = 0; }
     return DS_OK;
 }
 
-int ds_train_begin_signal(ds_handle* h, const ds_train_config* cfg) { return guarded(h, [&] { return ds_train_begin_signal_impl(h, cfg); }); }
-int ds_train_step_signal(ds_handle* h, int32_t n, const float* signals, const int32_t* labels, float lr, float* loss, int32_t* pred) { return guarded(h, [&] { return ds_train_run_signal_impl(h, "ds_train_step_signal", false, n, signals, labels, lr, loss, pred, nullptr); }); }
-int ds_train_eval_signal(ds_handle* h, int32_t n, const float* signals, const int32_t* labels, float* loss, int32_t* pred, float* logits) { return guarded(h, [&] { return ds_train_run_signal_impl(h, "ds_train_eval_signal", true, n, signals, labels, 0.f, loss, pred, logits); }); }
+int ds_train_begin_signal(ds_handle* h, const ds_train_config* cfg) { return guarded(h, [&] { return ds_train_begin_impl(h, "ds_train_begin_signal", cfg, true, false); }); }
+int ds_train_step_signal(ds_handle* h, int32_t n, const float* signals, const int32_t* labels, float lr, float* loss, int32_t* pred) { return guarded(h, [&] { return ds_train_run_impl(h, "ds_train_step_signal", true, false, n, {nullptr, nullptr, nullptr, nullptr, signals, labels}, lr, loss, pred, nullptr); }); }
+int ds_train_eval_signal(ds_handle* h, int32_t n, const float* signals, const int32_t* labels, float* loss, int32_t* pred, float* logits) { return guarded(h, [&] { return ds_train_run_impl(h, "ds_train_eval_signal", true, true, n, {nullptr, nullptr, nullptr, nullptr, signals, labels}, 0.f, loss, pred, logits); }); }
 int64_t ds_train_get_tap(ds_handle* h, const char* name, float* out, int64_t cap) { return guarded(h, [&] { return ds_train_get_tap_impl(h, name, out, cap); }); }
-int ds_train_begin(ds_handle* h, const ds_train_config* cfg) { return guarded(h, [&] { return ds_train_begin_impl(h, cfg, false); }); }
-int ds_train_begin_base(ds_handle* h, const ds_train_config* cfg) { return guarded(h, [&] { return ds_train_begin_impl(h, cfg, true); }); }
-int ds_train_step_base(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums, const int32_t* labels, float lr, float* loss, int32_t* pred) { return guarded(h, [&] { return ds_train_step_impl(h, "ds_train_step_base", false, n, kmer, means, stds, sanums, labels, lr, loss, pred, nullptr); }); }
-int ds_train_eval(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums, const int32_t* labels, float* loss, int32_t* pred, float* logits) { return guarded(h, [&] { return ds_train_step_impl(h, "ds_train_eval", true, n, kmer, means, stds, sanums, labels, 0.f, loss, pred, logits); }); }
+int ds_train_begin(ds_handle* h, const ds_train_config* cfg) { return guarded(h, [&] { return ds_train_begin_impl(h, "ds_train_begin", cfg, false, false); }); }
+int ds_train_begin_base(ds_handle* h, const ds_train_config* cfg) { return guarded(h, [&] { return ds_train_begin_impl(h, "ds_train_begin", cfg, false, true); }); }
+int ds_train_step_base(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums, const int32_t* labels, float lr, float* loss, int32_t* pred) { return guarded(h, [&] { return ds_train_run_impl(h, "ds_train_step_base", false, false, n, {kmer, means, stds, sanums, nullptr, labels}, lr, loss, pred, nullptr); }); }
+int ds_train_eval(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums, const int32_t* labels, float* loss, int32_t* pred, float* logits) { return guarded(h, [&] { return ds_train_run_impl(h, "ds_train_eval", false, true, n, {kmer, means, stds, sanums, nullptr, labels}, 0.f, loss, pred, logits); }); }
 int ds_train_set_tensor(ds_handle* h, const char* name, const float* data, int64_t count) { return guarded(h, [&] { return ds_train_set_tensor_impl(h, name, data, count); }); }
-int ds_train_step(ds_handle* h, int32_t n, const float* means, const float* stds, const float* sanums, const int32_t* labels, float lr, float* loss, int32_t* pred) { return guarded(h, [&] { return ds_train_step_impl(h, "ds_train_step", false, n, nullptr, means, stds, sanums, labels, lr, loss, pred, nullptr); }); }
+int ds_train_step(ds_handle* h, int32_t n, const float* means, const float* stds, const float* sanums, const int32_t* labels, float lr, float* loss, int32_t* pred) { return guarded(h, [&] { return ds_train_run_impl(h, "ds_train_step", false, false, n, {nullptr, means, stds, sanums, nullptr, labels}, lr, loss, pred, nullptr); }); }
 int ds_train_sync_weights(ds_handle* h) { return guarded(h, [&] { return ds_train_sync_weights_impl(h); }); }
 int64_t ds_train_get_tensor(ds_handle* h, const char* name, float* out, int64_t cap) { return guarded(h, [&] { return train_get(h, "ds_train_get_tensor", name, out, cap, false); }); }
 int64_t ds_train_get_grad(ds_handle* h, const char* name, float* out, int64_t cap) { return guarded(h, [&] { return train_get(h, "ds_train_get_grad", name, out, cap, true); }); }

@@ -1,14 +1,19 @@
-// ds_train.h — the training step of the RNN-only model, with or without the embedding (denoise, train; ds_train.hip): the formulas the host and the device share
-// (tensor order, dropout mask function, Adam step size) and the host-side state of one training run on a handle. The mask
-// function is __host__ __device__, so the CPU checker behind ds_train_mask_reference runs the code the kernels run.
-// Not part of the public ABI.
+// ds_train.h — training on a handle (denoise, train). Three parts: the formulas the host and the device share (parameter block
+// layout of the BiLSTM variants, dropout mask function, Adam step size); dstr::Run, the part of a training run that is not the
+// model (stream, phase events, pinned staging, parameter / gradient / moment blocks, the tensor table, the joint layers' second half
+// and the end of a step), which every variant derives from; and dstr::Trainer, the RNN-only model with or without the embedding
+// (ds_train.hip). The signal-only model is dsts::Trainer (ds_train_signal.h). The mask function is __host__ __device__, so the
+// CPU checker behind ds_train_mask_reference runs the code the kernels run. Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
+#include <map>
 #include <string>
+#include <vector>
 
 namespace dstr {
 
@@ -23,9 +28,8 @@ constexpr float FORGET_BIAS = 1.0f;
 // Both directions have the same layout, so the bw block is the fw block shifted by dir_floats. `in0` is the layer-0 input width of
 // the run: NFEAT (is_base 0) or EMB + NFEAT (is_base 1: the embedding row, then the three features, as model.py:64-69 concatenates
 // them). With in0 = NFEAT the block is the 14 tensors alone; the embedding comes last so that they keep their places among themselves.
-constexpr int NTENSOR = 14, TENSOR_EMB = 14;
+// By name the tensors are found through bilstm_tensors (below); the offset functions are what the launches use.
 DSTR_HD int in0_of(bool is_base) { return is_base ? EMB + NFEAT : NFEAT; }
-DSTR_HD int ntensor(int in0) { return in0 == NFEAT ? NTENSOR : NTENSOR + 1; }
 DSTR_HD int x0_pitch(int in0) { return (in0 + 3) & ~3; }      // floats per layer-0 input row: 4 or 132 (whole float4s, zero padded)
 DSTR_HD int layer_in(int l, int in0) { return l == 0 ? in0 : HID; }
 DSTR_HD int64_t kernel_off(int l, int in0)        // floats from a direction's start to layer l's kernel
@@ -41,43 +45,6 @@ DSTR_HD int64_t w2_off(int in0) { return w1_off(in0) + (int64_t)FC * FC; }
 DSTR_HD int64_t emb_off(int in0) { return w2_off(in0) + (int64_t)FC * NCLASS; }
 DSTR_HD int64_t param_floats(int in0) { return emb_off(in0) + (in0 == NFEAT ? 0 : (int64_t)VOCAB * EMB); }
 
-inline int64_t tensor_off(int idx, int in0)
-{
-    if (idx < 12) return (idx / 6) * dir_floats(in0) + ((idx & 1) ? bias_off((idx % 6) / 2, in0) : kernel_off((idx % 6) / 2, in0));
-    return idx == 12 ? w1_off(in0) : idx == 13 ? w2_off(in0) : emb_off(in0);
-}
-inline int64_t tensor_floats(int idx, int in0)
-{
-    if (idx < 12) return (idx & 1) ? GATES : (int64_t)(layer_in((idx % 6) / 2, in0) + HID) * GATES;
-    return idx == 12 ? (int64_t)FC * FC : idx == 13 ? (int64_t)FC * NCLASS : (int64_t)VOCAB * EMB;
-}
-// TF variable name -> index, -1 when it is none of the 15
-inline int tensor_index(const char* name)
-{
-    if (!name) return -1;
-    if (!strcmp(name, "dense/kernel")) return 12;
-    if (!strcmp(name, "dense_1/kernel")) return 13;
-    if (!strcmp(name, "modelembedding")) return TENSOR_EMB;
-    const char* dirs[2] = {"fw", "bw"};
-    const char* leaf[2] = {"kernel", "bias"};
-    for (int d = 0; d < 2; ++d)
-        for (int l = 0; l < NLAYER; ++l)
-            for (int k = 0; k < 2; ++k) {
-                char nm[160];
-                snprintf(nm, sizeof nm, "modelem/%s/multi_rnn_cell/cell_%d/lstm_cell/%s", dirs[d], l, leaf[k]);
-                if (!strcmp(name, nm)) return d * 6 + l * 2 + k;
-            }
-    return -1;
-}
-inline std::string tensor_name(int idx)
-{
-    if (idx == 12) return "dense/kernel";
-    if (idx == 13) return "dense_1/kernel";
-    if (idx == TENSOR_EMB) return "modelembedding";
-    char nm[160];
-    snprintf(nm, sizeof nm, "modelem/%s/multi_rnn_cell/cell_%d/lstm_cell/%s", idx / 6 ? "bw" : "fw", (idx % 6) / 2, (idx & 1) ? "bias" : "kernel");
-    return nm;
-}
 // a k-mer code as the forward reads it (include/deepsignal_hip.h, "CODES"): below 0 acts as 0, above VOCAB - 1 as VOCAB - 1
 DSTR_HD int clamp_code(int32_t c) { return c < 0 ? 0 : c > VOCAB - 1 ? VOCAB - 1 : c; }
 
@@ -112,16 +79,16 @@ DSTR_HD bool kept(uint64_t rkey, int t, int unit, uint32_t thr)
     return (uint32_t)(mix(rkey + (((uint64_t)t << 16) | (uint64_t)unit)) >> 40) < thr;
 }
 
-// host checker: the 0/1 bytes of one stream for rows 0 .. n - 1
-inline void mask_reference(uint64_t seed, int64_t step, int stream, int n, int T, float keep_prob, uint8_t* out)
+// host checker: the 0/1 bytes [n][steps][width] of one stream for rows 0 .. n - 1 (a cell's stream: steps = T, width = 256; "fc1" and
+// "fc2": steps = 1, width = the joint width and 2). A unit's mask does not depend on the row's width.
+inline void mask_reference(uint64_t seed, int64_t step, int stream, int n, int steps, int width, float keep_prob, uint8_t* out)
 {
     const uint32_t thr = keep_threshold(keep_prob);
     const uint64_t sk = stream_key(seed, step, stream);
-    const int W = stream_width(stream), steps = stream < 6 ? T : 1;
     for (int r = 0; r < n; ++r) {
         const uint64_t rk = row_key(sk, r);
         for (int t = 0; t < steps; ++t)
-            for (int u = 0; u < W; ++u) out[((size_t)r * steps + t) * W + u] = kept(rk, t, u, thr) ? 1 : 0;
+            for (int u = 0; u < width; ++u) out[((size_t)r * steps + t) * width + u] = kept(rk, t, u, thr) ? 1 : 0;
     }
 }
 
@@ -142,12 +109,35 @@ struct GemmArgs {
     int nb1, nb2;
     long long sA1, sA2, sB1, sB2, sC1, sC2, sBias2;
 };
-// ds_train.hip's kernels as the signal trainer launches them (ds_train_signal.hip): the kernels themselves are one copy
+// ds_train.hip's kernels as every variant launches them: the kernels themselves are one copy
 hipError_t launch_gemm(hipStream_t s, const GemmArgs& g);
 GemmArgs make_gemm(const float* A, int lda, int transA, const float* Bm, int ldb, int transB, float* C, int ldc, int M, int N, int K, int acc);
 hipError_t launch_reduce_slabs(hipStream_t s, const float* slab, float* out, long long count, int ns, long long stride);      // out[e] = slab[0][e] + slab[1][e] + ...
 hipError_t launch_adam(hipStream_t s, float* P, const float* G, float* M, float* V, long long count, float lr_t, float b1, float b2, float eps);
 hipError_t launch_mask(hipStream_t s, uint8_t* out, int n, int steps, int W, int stream_id, uint32_t thr, uint64_t seed, long long step);
+// the joint layers' second half at width J (train_head_kernel, one workgroup per row) and what follows it (train_head_reduce_kernel):
+// the loss, and dW2 unless it is nullptr
+struct HeadArgs {
+    const float *fc1, *W2;
+    float *drop1, *dfc1, *logits, *dfc2, *rowloss;
+    const int32_t* labels;
+    int32_t* pred;
+    int n, J;
+    float inv_keep, pos_weight, grad_scale;     // grad_scale = 1 / (number of loss terms)
+    uint32_t thr;
+    uint64_t seed;
+    long long step;
+};
+hipError_t launch_head(hipStream_t s, const HeadArgs& a);
+hipError_t launch_head_reduce(hipStream_t s, const float* rowloss, const float* drop1, const float* dfc2, float* loss, float* dW2, int n, int J, float scale);
+
+// a failed HIP call as a return code and a message; TCK returns it from a function that has `std::string* err`
+int hip_fail(std::string* err, const char* what, hipError_t e);
+#define TCK(expr)                                                         \
+    do {                                                                  \
+        hipError_t e_ = (expr);                                           \
+        if (e_ != hipSuccess) return dstr::hip_fail(err, #expr, e_);      \
+    } while (0)
 
 // ---- one run on a handle ---------------------------------------------------------------------------------------------------------
 struct Config {
@@ -156,16 +146,74 @@ struct Config {
 };
 constexpr int NPHASE = 5;      // forward sweep, backward sweep, weight gradients, head (forward + loss + backward), Adam
 
-struct Trainer {
-    int device = 0, T = 0, B = 0;
-    int in0 = NFEAT;                 // layer-0 input width of the run: NFEAT, or EMB + NFEAT with the embedding trained too
+struct TensorRef { int block; int64_t off, count; };      // block 0: the parameter block (and G, M, V), 1: the statistics block
+typedef std::map<std::string, std::vector<float>> TensorMap;
+// the host pointers of one batch; a variant reads the ones its model takes
+struct Inputs {
+    const int32_t* kmer;
+    const float *means, *stds, *lens, *signals;
+    const int32_t* labels;
+};
+
+// The part of a run that is not the model. A variant derives from it, keeps its layout and activation buffers, fills `tensors`, and
+// in step() does its forward up to fc1, calls head(), returns through finish() on an evaluation, else does its backward and weight
+// gradients between the events ev[2] .. ev[4] and ends in finish().
+struct Run {
+    int device = 0, B = 0, J = 0;    // J: width of fc1
     Config cfg;
-    int64_t step_count = 0;          // steps taken since begin(); the masks of step s use the counter s (first step: 0)
+    int64_t step_count = 0;          // steps taken since restart(); the masks of step s use the counter s (first step: 0)
     int last_n = 0;                  // rows of the last step (0: none yet)
     hipStream_t stream = nullptr;
     hipEvent_t ev[NPHASE + 1] = {};       // phase boundaries of the last step
-    // parameter-shaped blocks [param_floats(in0)]
-    float *P = nullptr, *G = nullptr, *M = nullptr, *V = nullptr;
+    int64_t steps_timed = 0;
+    double ms[NPHASE] = {};
+    int64_t PF = 0, MSF = 0;         // floats of a parameter-shaped block and of the statistics block (0: none)
+    float *P = nullptr, *G = nullptr, *M = nullptr, *V = nullptr, *MS = nullptr;      // P == nullptr: not open
+    std::map<std::string, TensorRef> tensors;
+    float *fc1 = nullptr, *drop1 = nullptr, *dfc1 = nullptr;                      // [B][J]
+    float *logits = nullptr, *dfc2 = nullptr, *rowloss = nullptr;                 // [B][2], [B][2], [B]
+    int32_t *d_lab = nullptr, *d_pred = nullptr;     // [B]
+    float* d_loss = nullptr;
+    uint8_t* d_mask = nullptr;       // ds_train_get_mask staging
+    float* pin = nullptr;            // pinned staging: [inputs, pin_in floats | labels [B] | loss, pred [B] | logits [B][2]]
+    size_t pin_in = 0;
+    std::vector<void*> allocs;       // every device block of the run, the variant's too
+
+    virtual ~Run() { release(); }
+    // one step (eval = false), or the forward alone with every mask kept, which changes nothing but scratch (eval = true; lr unused)
+    virtual int step(bool eval, int n, const Inputs& in, float lr, float* loss, int32_t* pred, float* logits_out, std::string* err) = 0;
+
+    template <class T> hipError_t alloc(T** p, size_t count)
+    {
+        const hipError_t e = hipMalloc((void**)p, std::max<size_t>(count * sizeof(T), 256));
+        if (e == hipSuccess) allocs.push_back((void*)*p);
+        return e;
+    }
+    // everything here but `tensors`, which the variant fills: blocks of PF (and MSF) floats, the head's buffers at width J,
+    // `mask_bytes` of mask staging, a pinned block with `pin_in` floats of inputs, the stream and the events
+    int open(int device, int B, int64_t PF, int64_t MSF, int J, size_t mask_bytes, size_t pin_in, std::string* err);
+    void release();
+    // start (over) from `weights`, which must hold every tensor of the table: parameters and statistics up, G, M, V and the counters 0
+    int restart(const Config& cfg, const TensorMap& weights, std::string* err);
+    float keep_prob(bool eval) const { return eval ? 1.f : cfg.keep_prob; }      // evaluation: every element kept whatever the step's masks are
+    int32_t* pin_labels() const { return reinterpret_cast<int32_t*>(pin + pin_in); }
+    int stage_labels(int n, const int32_t* labels, std::string* err);
+    // fc1 -> dropout, fc2, dropout, loss and prediction, dfc1 and (a step) dW2
+    int head(bool eval, int n, const float* fc1, const float* W2, float* dW2, std::string* err);
+    // an evaluation: loss, prediction and logits out, nothing else written or timed. A step: Adam over the block, the same out
+    // (no logits), the phase times and the counters.
+    int finish(bool eval, int n, float lr, float* loss, int32_t* pred, float* logits_out, std::string* err);
+    int64_t get(const char* name, bool grad, float* out, int64_t cap, std::string* err);
+    int read_all(TensorMap* out, std::string* err);      // every tensor of the table, statistics included
+    int64_t get_mask(int stream, int steps, int W, uint8_t* out, int64_t cap, std::string* err);      // of the last step
+};
+
+// the BiLSTM variants' table: 14 names, and modelembedding with in0 != NFEAT
+std::map<std::string, TensorRef> bilstm_tensors(int in0);
+
+struct Trainer : Run {
+    int T = 0;
+    int in0 = NFEAT;                 // layer-0 input width of the run: NFEAT, or EMB + NFEAT with the embedding trained too
     // per (direction, layer) activations, time-major: index ((d * NLAYER + l) * T + t) * B + row
     float* X0 = nullptr;             // [2][T][B][x0_pitch] layer-0 inputs ([embedding row |] mean, std, length, 0) in processing order
     float* H = nullptr;              // [2][3][T][B][256] h_t
@@ -176,8 +224,7 @@ struct Trainer {
     float* DH = nullptr;             // [2][B][256] recurrent gradient dz_{t+1} Kh^T
     float* DC = nullptr;             // [2][B][256] cell-state gradient carried down the steps
     float* slab = nullptr;           // [2][T][256][1024] per-step partial weight gradients of one layer (both directions), then [2][T][1024] for its bias
-    float *fc1 = nullptr, *drop1 = nullptr, *dfc1 = nullptr, *djoint = nullptr;   // [B][512]
-    float *logits = nullptr, *dfc2 = nullptr, *rowloss = nullptr;                 // [B][2], [B][2], [B]
+    float* djoint = nullptr;         // [B][512]
     float* d_in = nullptr;           // [3][B][T] means | stds | lengths
     // is_base 1 only: the codes, the gradient of the embedded layer-0 inputs and the workspace of the embedding-gradient reduction
     int32_t* d_kmer = nullptr;       // [B][T]
@@ -187,24 +234,10 @@ struct Trainer {
     int32_t* eg_entry = nullptr;     // [B * T] entries e = row * T + p sorted by code, ascending in e within a code
     int32_t* eg_chunk_code = nullptr;   // [chunks] the code a chunk belongs to
     float* eg_partial = nullptr;     // [chunks][128] a chunk's sum
-    int32_t* d_lab = nullptr;        // [B]
-    int32_t* d_pred = nullptr;       // [B]
-    float* d_loss = nullptr;
-    uint8_t* d_mask = nullptr;       // ds_train_get_mask staging [B][T][512]
-    float* pin = nullptr;            // pinned staging: inputs in, [loss | pred] out, then codes in and logits out
-    int64_t steps_timed = 0;
-    double ms[NPHASE] = {};
 
-    ~Trainer();
-    int begin(int device, int T, int B, int in0, const Config& cfg, const float* params, std::string* err);   // params: host block [param_floats(in0)]
-    // one step (eval = false), or the forward alone with every mask kept, which changes nothing but scratch (eval = true; lr unused)
-    int run(bool eval, int n, const int32_t* kmer, const float* means, const float* stds, const float* lens, const int32_t* labels, float lr,
-            float* loss, int32_t* pred, float* logits_out, std::string* err);
+    int begin(int device, int T, int B, int in0, const Config& cfg, const TensorMap& weights, std::string* err);
+    int step(bool eval, int n, const Inputs& in, float lr, float* loss, int32_t* pred, float* logits_out, std::string* err) override;
     int max_chunks() const { return (B * T + 63) / 64 + (B * T < VOCAB ? B * T : VOCAB); }      // chunks of 64 entries, one partly filled per code
-    int read_params(float* out, std::string* err);                 // the whole block, to the host
-    int64_t get(const float* block, int idx, float* out, int64_t cap, std::string* err);
-    int64_t get_mask(int stream, uint8_t* out, int64_t cap, std::string* err);
-    void release();
 };
 
 }  // namespace dstr

@@ -4,7 +4,9 @@
 // and reduce_slabs_kernel adds them in a fixed order, so a step is a pure function of (weights, batch, seed, step).
 // With is_base 1 (train; model.py:61-69) layer 0 reads [embedding row of the base's code | mean, std, length] and the embedding is a
 // 15th trained tensor: gather_x0_base_kernel in front, and after layer 0's backward sweep DX0 = dz_0 K0[0:128]^T summed per code in
-// an order the codes alone decide (emb_count_kernel .. emb_reduce_kernel). run(eval = true) is the forward alone with every mask kept.
+// an order the codes alone decide (emb_count_kernel .. emb_reduce_kernel). step(eval = true) is the forward alone with every mask kept.
+// The file also holds dstr::Run (ds_train.h), the part of a run that every variant shares, and the kernels they share: the matrix
+// product, the joint layers' second half at a run-time width (train_head_kernel), the slab reduction, Adam and the mask writer.
 //
 // Layout. Activations are time-major per (direction d, layer l): element ((d * 3 + l) * T + t) * B + row, B = max_batch, t = the step
 // in the order the stack processes the sequence (bw: t = 0 is the last base). A step of one cell is then a dense [n][width] matrix
@@ -273,18 +275,6 @@ __global__ void cell_backward_kernel(CellBackArgs a)
     a.DC[od] = dc * sf;
 }
 
-struct HeadArgs {
-    const float *fc1, *W2;
-    float *drop1, *dfc1, *logits, *dfc2, *rowloss;
-    const int32_t* labels;
-    int32_t* pred;
-    int n;
-    float inv_keep, pos_weight, grad_scale;     // grad_scale = 1 / (number of loss terms)
-    uint32_t thr;
-    uint64_t seed;
-    long long step;
-};
-
 // stable weighted cross entropy on one logit (tf.nn.weighted_cross_entropy_with_logits) and its derivative
 __device__ inline float wce(float x, float zt, float pw, float* dx)
 {
@@ -294,23 +284,21 @@ __device__ inline float wce(float x, float zt, float pw, float* dx)
     return (1.f - zt) * x + q * sp;
 }
 
-// one workgroup per row: dropout of fc1, fc2 = drop1 W2, dropout of the logits (layers.py:257-264), the row's loss terms and
-// prediction (model.py:100-116), and the gradient back to fc1. The 512-term sums are a fixed tree over the workgroup.
+// one workgroup per row, the joint layers' second half at width J (HeadArgs, ds_train.h): dropout of fc1,
+// fc2 = drop1 W2, dropout of the logits (layers.py:257-264), the row's loss terms and prediction (model.py:100-116), and the gradient
+// back to fc1. A thread adds its units k = tid, tid + 256, ... in ascending order, then a fixed tree over the workgroup.
 __global__ __launch_bounds__(256) void train_head_kernel(HeadArgs a)
 {
     __shared__ float red[2][256];
     __shared__ float dl[2];
     const int row = blockIdx.x, tid = threadIdx.x;
     const uint64_t rk1 = row_key(stream_key(a.seed, a.step, STREAM_FC1), row);
-    float dv[2], p0 = 0.f, p1 = 0.f;
-    bool k1[2];
-    for (int s = 0; s < 2; ++s) {
-        const int k = tid + 256 * s;
-        k1[s] = kept(rk1, 0, k, a.thr);
-        dv[s] = k1[s] ? a.fc1[(size_t)row * FC + k] * a.inv_keep : 0.f;
-        a.drop1[(size_t)row * FC + k] = dv[s];
-        p0 = fmaf(dv[s], a.W2[k * 2], p0);
-        p1 = fmaf(dv[s], a.W2[k * 2 + 1], p1);
+    float p0 = 0.f, p1 = 0.f;
+    for (int k = tid; k < a.J; k += 256) {
+        const float dv = kept(rk1, 0, k, a.thr) ? a.fc1[(size_t)row * a.J + k] * a.inv_keep : 0.f;
+        a.drop1[(size_t)row * a.J + k] = dv;
+        p0 = fmaf(dv, a.W2[k * 2], p0);
+        p1 = fmaf(dv, a.W2[k * 2 + 1], p1);
     }
     red[0][tid] = p0; red[1][tid] = p1;
     __syncthreads();
@@ -339,25 +327,25 @@ __global__ __launch_bounds__(256) void train_head_kernel(HeadArgs a)
         dl[0] = d0; dl[1] = d1;
     }
     __syncthreads();
-    for (int s = 0; s < 2; ++s) {
-        const int k = tid + 256 * s;
-        const float dd = dl[0] * a.W2[k * 2] + dl[1] * a.W2[k * 2 + 1];
-        a.dfc1[(size_t)row * FC + k] = k1[s] ? dd * a.inv_keep : 0.f;
+    for (int k = tid; k < a.J; k += 256) {
+        // one product rounded, the other fused into the sum: the form the fixed-width kernel of the BiLSTM step was compiled to
+        const float dd = fmaf(dl[0], a.W2[k * 2], __fmul_rn(dl[1], a.W2[k * 2 + 1]));
+        a.dfc1[(size_t)row * a.J + k] = kept(rk1, 0, k, a.thr) ? dd * a.inv_keep : 0.f;
     }
 }
 
 // loss = sum of the rows' terms in row order, times `scale`; dW2[k][c] = sum over rows of drop1[row][k] dfc2[row][c] in row order
-// (dW2 = nullptr: the loss alone, for ds_train_eval)
-__global__ void train_head_reduce_kernel(const float* rowloss, const float* drop1, const float* dfc2, float* loss, float* dW2, int n, float scale)
+// (dW2 = nullptr: the loss alone, for an evaluation)
+__global__ void train_head_reduce_kernel(const float* rowloss, const float* drop1, const float* dfc2, float* loss, float* dW2, int n, int J, float scale)
 {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx < FC * NCLASS) {
+    if (idx < J * NCLASS) {
         if (!dW2) return;
         const int k = idx >> 1, c = idx & 1;
         float s = 0.f;
-        for (int r = 0; r < n; ++r) s = fmaf(drop1[(size_t)r * FC + k], dfc2[r * 2 + c], s);
+        for (int r = 0; r < n; ++r) s = fmaf(drop1[(size_t)r * J + k], dfc2[r * 2 + c], s);
         dW2[idx] = s;
-    } else if (idx == FC * NCLASS) {
+    } else if (idx == J * NCLASS) {
         float s = 0.f;
         for (int r = 0; r < n; ++r) s += rowloss[r];
         *loss = s * scale;
@@ -406,18 +394,6 @@ __global__ void mask_kernel(uint8_t* out, int n, int steps, int W, int stream, u
     out[idx] = kept(row_key(stream_key(seed, step, stream), row), t, u, thr) ? 1 : 0;
 }
 
-int hip_fail(std::string* err, const char* what, hipError_t e)
-{
-    (void)hipGetLastError();
-    if (err) *err = std::string(what) + ": " + hipGetErrorString(e);
-    return e == hipErrorOutOfMemory ? DS_ERR_NOMEM : DS_ERR_HIP;
-}
-#define TCK(expr)                                                   \
-    do {                                                            \
-        hipError_t e_ = (expr);                                     \
-        if (e_ != hipSuccess) return hip_fail(err, #expr, e_);      \
-    } while (0)
-
 hipError_t gemm(hipStream_t s, const GemmArgs& g)
 {
     dim3 grid((g.N + TN - 1) / TN, (g.M + TM - 1) / TM, g.nb1 * g.nb2);
@@ -435,7 +411,7 @@ GemmArgs gemm_args(const float* A, int lda, int transA, const float* Bm, int ldb
 
 }  // namespace
 
-// ---- the kernels the signal trainer (ds_train_signal.hip) shares, launched as they are --------------------------------------------
+// ---- the kernels every variant shares, launched as they are ----------------------------------------------------------------------
 hipError_t launch_gemm(hipStream_t s, const GemmArgs& g) { return gemm(s, g); }
 GemmArgs make_gemm(const float* A, int lda, int transA, const float* Bm, int ldb, int transB, float* C, int ldc, int M, int N, int K, int acc)
 {
@@ -457,104 +433,234 @@ hipError_t launch_mask(hipStream_t s, uint8_t* out, int n, int steps, int W, int
     hipLaunchKernelGGL(mask_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, out, n, steps, W, stream_id, thr, seed, step);
     return hipGetLastError();
 }
+hipError_t launch_head(hipStream_t s, const HeadArgs& a)
+{
+    hipLaunchKernelGGL(train_head_kernel, dim3(a.n), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_head_reduce(hipStream_t s, const float* rowloss, const float* drop1, const float* dfc2, float* loss, float* dW2, int n, int J, float scale)
+{
+    hipLaunchKernelGGL(train_head_reduce_kernel, dim3((J * NCLASS + 1 + 255) / 256), dim3(256), 0, s, rowloss, drop1, dfc2, loss, dW2, n, J, scale);
+    return hipGetLastError();
+}
 
-void Trainer::release()
+int hip_fail(std::string* err, const char* what, hipError_t e)
+{
+    (void)hipGetLastError();
+    if (err) *err = std::string(what) + ": " + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? DS_ERR_NOMEM : DS_ERR_HIP;
+}
+
+// ---- dstr::Run: the part of a run that is not the model ---------------------------------------------------------------------------
+int Run::open(int dev, int B_, int64_t PF_, int64_t MSF_, int J_, size_t mask_bytes, size_t pin_in_, std::string* err)
+{
+    release();
+    device = dev; B = B_; PF = PF_; MSF = MSF_; J = J_; pin_in = pin_in_;
+    TCK(hipSetDevice(dev));
+    const size_t Bz = (size_t)B;
+    TCK(alloc(&P, (size_t)PF)); TCK(alloc(&G, (size_t)PF)); TCK(alloc(&M, (size_t)PF)); TCK(alloc(&V, (size_t)PF));
+    if (MSF) TCK(alloc(&MS, (size_t)MSF));
+    TCK(alloc(&fc1, Bz * J)); TCK(alloc(&drop1, Bz * J)); TCK(alloc(&dfc1, Bz * J));
+    TCK(alloc(&logits, Bz * 2)); TCK(alloc(&dfc2, Bz * 2)); TCK(alloc(&rowloss, Bz));
+    TCK(alloc(&d_lab, Bz)); TCK(alloc(&d_pred, Bz)); TCK(alloc(&d_loss, 1)); TCK(alloc(&d_mask, mask_bytes));
+    TCK(hipHostMalloc((void**)&pin, (pin_in + 4 * Bz + 4) * sizeof(float), hipHostMallocDefault));
+    TCK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : ev) TCK(hipEventCreate(&e));
+    return DS_OK;
+}
+
+void Run::release()
 {
     if (device >= 0) hipSetDevice(device);
     if (stream) hipStreamSynchronize(stream);
-    for (void* p : {(void*)P, (void*)G, (void*)M, (void*)V, (void*)X0, (void*)H, (void*)Y, (void*)Cs, (void*)Z, (void*)DX, (void*)DH, (void*)DC,
-                    (void*)slab, (void*)fc1, (void*)drop1, (void*)dfc1, (void*)djoint, (void*)logits, (void*)dfc2, (void*)rowloss, (void*)d_in,
-                    (void*)d_lab, (void*)d_pred, (void*)d_loss, (void*)d_mask, (void*)d_kmer, (void*)DX0, (void*)eg_count, (void*)eg_run, (void*)eg_entry,
-                    (void*)eg_chunk_code, (void*)eg_partial})
-        if (p) hipFree(p);
-    P = G = M = V = X0 = H = Y = Cs = Z = DX = DH = DC = slab = fc1 = drop1 = dfc1 = djoint = logits = dfc2 = rowloss = d_in = d_loss = nullptr;
-    DX0 = eg_partial = nullptr;
-    d_lab = d_pred = d_kmer = eg_count = eg_run = eg_entry = eg_chunk_code = nullptr;
-    d_mask = nullptr;
+    for (void* p : allocs) hipFree(p);
+    allocs.clear();
+    P = MS = nullptr;
     if (pin) hipHostFree(pin);
     pin = nullptr;
     for (hipEvent_t& e : ev) { if (e) hipEventDestroy(e); e = nullptr; }
     if (stream) hipStreamDestroy(stream);
     stream = nullptr;
     (void)hipGetLastError();
-    T = B = 0;
+    B = 0;
 }
 
-Trainer::~Trainer() { release(); }
-
-int Trainer::begin(int dev, int T_, int B_, int in0_, const Config& c, const float* params, std::string* err)
+int Run::restart(const Config& c, const TensorMap& weights, std::string* err)
 {
-    TCK(hipSetDevice(dev));
-    const size_t PF = (size_t)param_floats(in0_);
-    if (T_ != T || B_ != B || in0_ != in0 || dev != device || !P) {
-        release();
-        device = dev;
-        in0 = in0_;
-        TCK(hipSetDevice(dev));
-        const size_t cells = (size_t)NDIR * NLAYER * T_ * B_;
-        auto alloc = [&](auto** p, size_t count) { return hipMalloc((void**)p, std::max<size_t>(count * sizeof(**p), 256)); };
-        TCK(alloc(&P, PF)); TCK(alloc(&G, PF)); TCK(alloc(&M, PF)); TCK(alloc(&V, PF));
-        TCK(alloc(&X0, (size_t)NDIR * T_ * B_ * x0_pitch(in0)));
-        TCK(alloc(&H, cells * HID)); TCK(alloc(&Y, cells * HID)); TCK(alloc(&Cs, cells * HID)); TCK(alloc(&Z, cells * GATES));
-        TCK(alloc(&DX, (size_t)NDIR * T_ * B_ * HID)); TCK(alloc(&DH, (size_t)NDIR * B_ * HID)); TCK(alloc(&DC, (size_t)NDIR * B_ * HID));
-        TCK(alloc(&slab, (size_t)NDIR * T_ * HID * GATES));
-        TCK(alloc(&fc1, (size_t)B_ * FC)); TCK(alloc(&drop1, (size_t)B_ * FC)); TCK(alloc(&dfc1, (size_t)B_ * FC)); TCK(alloc(&djoint, (size_t)B_ * FC));
-        TCK(alloc(&logits, (size_t)B_ * 2)); TCK(alloc(&dfc2, (size_t)B_ * 2)); TCK(alloc(&rowloss, (size_t)B_));
-        TCK(alloc(&d_in, (size_t)3 * B_ * T_)); TCK(alloc(&d_lab, (size_t)B_)); TCK(alloc(&d_pred, (size_t)B_)); TCK(alloc(&d_loss, 1));
-        TCK(alloc(&d_mask, (size_t)B_ * T_ * FC));
-        TCK(hipHostMalloc((void**)&pin, ((size_t)4 * B_ * T_ + 4 * (size_t)B_ + 4) * 4, hipHostMallocDefault));
-        TCK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        for (hipEvent_t& e : ev) TCK(hipEventCreate(&e));
-        T = T_; B = B_;
-        if (in0 != NFEAT) {
-            TCK(alloc(&d_kmer, (size_t)B * T)); TCK(alloc(&DX0, (size_t)NDIR * T * B * EMB));
-            TCK(alloc(&eg_count, (size_t)((B * T + EG_BLOCK - 1) / EG_BLOCK) * VOCAB)); TCK(alloc(&eg_run, (size_t)2 * (VOCAB + 1)));
-            TCK(alloc(&eg_entry, (size_t)B * T)); TCK(alloc(&eg_chunk_code, (size_t)max_chunks())); TCK(alloc(&eg_partial, (size_t)max_chunks() * EMB));
-        }
-    }
+    TCK(hipSetDevice(device));
     TCK(hipStreamSynchronize(stream));
     cfg = c;
-    TCK(hipMemcpy(P, params, PF * sizeof(float), hipMemcpyHostToDevice));
-    TCK(hipMemset(G, 0, PF * sizeof(float)));
-    TCK(hipMemset(M, 0, PF * sizeof(float)));
-    TCK(hipMemset(V, 0, PF * sizeof(float)));
+    std::vector<float> hp((size_t)PF), hs((size_t)MSF, 0.f);
+    for (const auto& kv : tensors) {
+        auto it = weights.find(kv.first);
+        if (it == weights.end() || (int64_t)it->second.size() != kv.second.count) { if (err) *err = "missing/bad tensor " + kv.first; return DS_ERR_INVALID; }
+        std::copy(it->second.begin(), it->second.end(), (kv.second.block ? hs.begin() : hp.begin()) + kv.second.off);
+    }
+    TCK(hipMemcpy(P, hp.data(), (size_t)PF * sizeof(float), hipMemcpyHostToDevice));
+    if (MSF) TCK(hipMemcpy(MS, hs.data(), (size_t)MSF * sizeof(float), hipMemcpyHostToDevice));
+    TCK(hipMemset(G, 0, (size_t)PF * sizeof(float)));
+    TCK(hipMemset(M, 0, (size_t)PF * sizeof(float)));
+    TCK(hipMemset(V, 0, (size_t)PF * sizeof(float)));
     step_count = 0;
     last_n = 0;
     return DS_OK;
 }
 
-int Trainer::run(bool eval, int n, const int32_t* kmer, const float* means, const float* stds, const float* lens, const int32_t* labels, float lr,
-                 float* loss, int32_t* pred, float* logits_out, std::string* err)
+int Run::stage_labels(int n, const int32_t* labels, std::string* err)
+{
+    memcpy(pin_labels(), labels, (size_t)n * sizeof(int32_t));
+    TCK(hipMemcpyAsync(d_lab, pin_labels(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    return DS_OK;
+}
+
+int Run::head(bool eval, int n, const float* fc1_, const float* W2, float* dW2, std::string* err)
+{
+    const float kp = keep_prob(eval);
+    const float scale = 1.f / (float)(cfg.pos_weight == 1.f ? 2 * n : n);      // both columns carry a loss term, or column 1 alone
+    HeadArgs ha{};
+    ha.fc1 = fc1_; ha.W2 = W2; ha.drop1 = drop1; ha.dfc1 = dfc1; ha.logits = logits; ha.dfc2 = dfc2; ha.rowloss = rowloss; ha.labels = d_lab;
+    ha.pred = d_pred; ha.n = n; ha.J = J; ha.inv_keep = 1.f / kp; ha.pos_weight = cfg.pos_weight; ha.grad_scale = scale; ha.thr = keep_threshold(kp);
+    ha.seed = cfg.seed; ha.step = step_count;
+    TCK(launch_head(stream, ha));
+    TCK(launch_head_reduce(stream, rowloss, drop1, dfc2, d_loss, eval ? nullptr : dW2, n, J, scale));
+    return DS_OK;
+}
+
+int Run::finish(bool eval, int n, float lr, float* loss, int32_t* pred, float* logits_out, std::string* err)
+{
+    hipStream_t s = stream;
+    if (!eval) {      // Adam on every tensor of the block
+        const float lr_t = adam_step_size(lr, cfg.beta1, cfg.beta2, step_count + 1);
+        TCK(launch_adam(s, P, G, M, V, (long long)PF, lr_t, cfg.beta1, cfg.beta2, cfg.epsilon));
+        TCK(hipEventRecord(ev[5], s));
+    }
+    float* pout = pin + pin_in + B;      // [loss | pred [B] | logits [B][2]]
+    TCK(hipMemcpyAsync(pout, d_loss, sizeof(float), hipMemcpyDeviceToHost, s));
+    TCK(hipMemcpyAsync(pout + 1, d_pred, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (eval) TCK(hipMemcpyAsync(pout + 1 + B, logits, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, s));
+    TCK(hipStreamSynchronize(s));
+    if (loss) *loss = pout[0];
+    if (pred) memcpy(pred, pout + 1, (size_t)n * sizeof(int32_t));
+    if (eval) {      // the forward, its loss and prediction alone: no gradient, moment, parameter or counter is written
+        if (logits_out) memcpy(logits_out, pout + 1 + B, (size_t)n * 2 * sizeof(float));
+        return DS_OK;
+    }
+    // phases in the order ds_get_train_times reports them: forward, backward, weight gradients, head, Adam
+    const int from[NPHASE] = {0, 2, 3, 1, 4};
+    for (int k = 0; k < NPHASE; ++k) {
+        float t_ms = 0.f;
+        TCK(hipEventElapsedTime(&t_ms, ev[from[k]], ev[from[k] + 1]));
+        ms[k] += t_ms;
+    }
+    steps_timed += 1;
+    step_count += 1;
+    last_n = n;
+    return DS_OK;
+}
+
+int64_t Run::get(const char* name, bool grad, float* out, int64_t cap, std::string* err)
+{
+    auto it = tensors.find(name ? name : "");
+    if (it == tensors.end() || !out) { if (err) *err = std::string("unknown tensor ") + (name ? name : "(null)"); return DS_ERR_INVALID; }
+    const TensorRef& t = it->second;
+    if (grad && t.block) { if (err) *err = std::string("a moving statistic is not trained and has no gradient: ") + name; return DS_ERR_INVALID; }
+    if (cap < t.count) { if (err) *err = std::string("buffer too small for ") + name; return DS_ERR_INVALID; }
+    TCK(hipSetDevice(device));
+    TCK(hipMemcpy(out, (t.block ? MS : grad ? G : P) + t.off, (size_t)t.count * sizeof(float), hipMemcpyDeviceToHost));
+    return t.count;
+}
+
+int Run::read_all(TensorMap* out, std::string* err)
+{
+    TCK(hipSetDevice(device));
+    std::vector<float> hp((size_t)PF), hs((size_t)MSF);
+    TCK(hipMemcpy(hp.data(), P, (size_t)PF * sizeof(float), hipMemcpyDeviceToHost));
+    if (MSF) TCK(hipMemcpy(hs.data(), MS, (size_t)MSF * sizeof(float), hipMemcpyDeviceToHost));
+    for (const auto& kv : tensors) {
+        const float* src = (kv.second.block ? hs.data() : hp.data()) + kv.second.off;
+        (*out)[kv.first].assign(src, src + kv.second.count);
+    }
+    return DS_OK;
+}
+
+int64_t Run::get_mask(int stream_id, int steps, int W, uint8_t* out, int64_t cap, std::string* err)
+{
+    const int64_t count = (int64_t)last_n * steps * W;
+    if (cap < count) { if (err) *err = "mask buffer too small"; return DS_ERR_INVALID; }
+    TCK(hipSetDevice(device));
+    TCK(launch_mask(stream, d_mask, last_n, steps, W, stream_id, keep_threshold(cfg.keep_prob), cfg.seed, (long long)(step_count - 1)));
+    TCK(hipMemcpyAsync(out, d_mask, count, hipMemcpyDeviceToHost, stream));
+    TCK(hipStreamSynchronize(stream));
+    return count;
+}
+
+// ---- dstr::Trainer: the BiLSTM variants ---------------------------------------------------------------------------------------------
+std::map<std::string, TensorRef> bilstm_tensors(int in0)
+{
+    std::map<std::string, TensorRef> t;
+    for (int d = 0; d < NDIR; ++d)
+        for (int l = 0; l < NLAYER; ++l) {
+            char nm[160];
+            snprintf(nm, sizeof nm, "modelem/%s/multi_rnn_cell/cell_%d/lstm_cell/", d ? "bw" : "fw", l);
+            t[std::string(nm) + "kernel"] = {0, d * dir_floats(in0) + kernel_off(l, in0), (int64_t)(layer_in(l, in0) + HID) * GATES};
+            t[std::string(nm) + "bias"] = {0, d * dir_floats(in0) + bias_off(l, in0), GATES};
+        }
+    t["dense/kernel"] = {0, w1_off(in0), (int64_t)FC * FC};
+    t["dense_1/kernel"] = {0, w2_off(in0), (int64_t)FC * NCLASS};
+    if (in0 != NFEAT) t["modelembedding"] = {0, emb_off(in0), (int64_t)VOCAB * EMB};
+    return t;
+}
+
+int Trainer::begin(int dev, int T_, int B_, int in0_, const Config& c, const TensorMap& weights, std::string* err)
+{
+    if (T_ != T || B_ != B || in0_ != in0 || dev != device || !P) {
+        const size_t BT = (size_t)B_ * T_, cells = (size_t)NDIR * NLAYER * BT;
+        const bool base = in0_ != NFEAT;
+        // mask staging: a cell's stream [B][T][256] or fc1 [B][512]; pinned inputs: means | stds | lengths [3][B][T], then the codes [B][T]
+        if (int rc = open(dev, B_, param_floats(in0_), 0, FC, std::max(BT * HID, (size_t)B_ * FC), (base ? 4 : 3) * BT, err)) return rc;
+        T = T_; in0 = in0_;
+        tensors = bilstm_tensors(in0);
+        TCK(alloc(&X0, NDIR * BT * x0_pitch(in0)));
+        TCK(alloc(&H, cells * HID)); TCK(alloc(&Y, cells * HID)); TCK(alloc(&Cs, cells * HID)); TCK(alloc(&Z, cells * GATES));
+        TCK(alloc(&DX, NDIR * BT * HID)); TCK(alloc(&DH, (size_t)NDIR * B * HID)); TCK(alloc(&DC, (size_t)NDIR * B * HID));
+        TCK(alloc(&slab, (size_t)NDIR * T * HID * GATES));
+        TCK(alloc(&djoint, (size_t)B * FC));
+        TCK(alloc(&d_in, 3 * BT));
+        if (base) {
+            TCK(alloc(&d_kmer, BT)); TCK(alloc(&DX0, NDIR * BT * EMB));
+            TCK(alloc(&eg_count, (size_t)((B * T + EG_BLOCK - 1) / EG_BLOCK) * VOCAB)); TCK(alloc(&eg_run, (size_t)2 * (VOCAB + 1)));
+            TCK(alloc(&eg_entry, BT)); TCK(alloc(&eg_chunk_code, (size_t)max_chunks())); TCK(alloc(&eg_partial, (size_t)max_chunks() * EMB));
+        }
+    }
+    return restart(c, weights, err);
+}
+
+int Trainer::step(bool eval, int n, const Inputs& inp, float lr, float* loss, int32_t* pred, float* logits_out, std::string* err)
 {
     TCK(hipSetDevice(device));
     hipStream_t s = stream;
     const bool base = in0 != NFEAT;
     const int ldx = x0_pitch(in0);
-    const long long DF = dir_floats(in0), PF = param_floats(in0);
+    const long long DF = dir_floats(in0);
     const long long sAct = (long long)B * HID, sZt = (long long)B * GATES;               // floats per step
     const long long sActD = (long long)NLAYER * T * sAct, sZD = (long long)NLAYER * T * sZt;   // floats per direction
     auto act = [&](float* base, int l, int t) { return base + ((size_t)l * T + t) * sAct; };      // direction 0
     auto zat = [&](int l, int t) { return Z + ((size_t)l * T + t) * sZt; };
-    // eval: keep_prob 1, under which inv_keep is 1 and the threshold 2^24 keeps every element whatever the step's masks are
-    const float keep_prob = eval ? 1.f : cfg.keep_prob;
-    const float inv_keep = 1.f / keep_prob;
-    const uint32_t thr = keep_threshold(keep_prob);
+    const float inv_keep = 1.f / keep_prob(eval);
+    const uint32_t thr = keep_threshold(keep_prob(eval));
     const long long mstep = step_count;
     const dim3 cell_grid((n * HID + 255) / 256, 2);
 
-    // inputs: [means | stds | lengths] pitched for B rows, then the labels
-    float* pf = pin;
-    const float* srcs[3] = {means, stds, lens};
-    for (int k = 0; k < 3; ++k) memcpy(pf + (size_t)k * B * T, srcs[k], (size_t)n * T * sizeof(float));
-    int32_t* plab = reinterpret_cast<int32_t*>(pf + (size_t)3 * B * T);
-    memcpy(plab, labels, (size_t)n * sizeof(int32_t));
-    TCK(hipMemcpyAsync(d_in, pf, (size_t)3 * B * T * sizeof(float), hipMemcpyHostToDevice, s));
-    TCK(hipMemcpyAsync(d_lab, plab, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    float* ptail = pf + (size_t)3 * B * T + 2 * (size_t)B + 4;      // past [loss | pred]: the codes [B * T] in, the logits [B][2] out
+    // inputs: [means | stds | lengths] pitched for B rows, then the codes
+    const float* srcs[3] = {inp.means, inp.stds, inp.lens};
+    for (int k = 0; k < 3; ++k) memcpy(pin + (size_t)k * B * T, srcs[k], (size_t)n * T * sizeof(float));
+    TCK(hipMemcpyAsync(d_in, pin, (size_t)3 * B * T * sizeof(float), hipMemcpyHostToDevice, s));
     if (base) {
-        memcpy(ptail, kmer, (size_t)n * T * sizeof(int32_t));
-        TCK(hipMemcpyAsync(d_kmer, ptail, (size_t)n * T * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        float* pk = pin + (size_t)3 * B * T;
+        memcpy(pk, inp.kmer, (size_t)n * T * sizeof(int32_t));
+        TCK(hipMemcpyAsync(d_kmer, pk, (size_t)n * T * sizeof(int32_t), hipMemcpyHostToDevice, s));
     }
+    if (int rc = stage_labels(n, inp.labels, err)) return rc;
 
     // ---- forward sweep
     if (!eval) TCK(hipEventRecord(ev[0], s));
@@ -594,28 +700,8 @@ int Trainer::run(bool eval, int n, const int32_t* kmer, const float* means, cons
     float* W2 = P + w2_off(in0);
     for (int d = 0; d < 2; ++d)
         TCK(gemm(s, gemm_args(act(Y, NLAYER - 1, T - 1) + d * sActD, HID, 0, W1 + (size_t)d * HID * FC, FC, 0, fc1, FC, n, FC, HID, d)));
-    const bool two_col = cfg.pos_weight == 1.f;
-    const float scale = 1.f / (float)(two_col ? 2 * n : n);
-    HeadArgs ha{};
-    ha.fc1 = fc1; ha.W2 = W2; ha.drop1 = drop1; ha.dfc1 = dfc1; ha.logits = logits; ha.dfc2 = dfc2; ha.rowloss = rowloss; ha.labels = d_lab;
-    ha.pred = d_pred; ha.n = n; ha.inv_keep = inv_keep; ha.pos_weight = cfg.pos_weight; ha.grad_scale = scale; ha.thr = thr; ha.seed = cfg.seed;
-    ha.step = mstep;
-    hipLaunchKernelGGL(train_head_kernel, dim3(n), dim3(256), 0, s, ha);
-    TCK(hipGetLastError());
-    hipLaunchKernelGGL(train_head_reduce_kernel, dim3((FC * NCLASS + 1 + 255) / 256), dim3(256), 0, s, rowloss, drop1, dfc2, d_loss,
-                       eval ? nullptr : G + w2_off(in0), n, scale);
-    TCK(hipGetLastError());
-    float* pout = pin + (size_t)3 * B * T + B;
-    if (eval) {      // the forward, its loss and prediction alone: no gradient, moment, parameter or counter is written
-        TCK(hipMemcpyAsync(pout, d_loss, sizeof(float), hipMemcpyDeviceToHost, s));
-        TCK(hipMemcpyAsync(pout + 1, d_pred, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        TCK(hipMemcpyAsync(ptail + (size_t)B * T, logits, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, s));
-        TCK(hipStreamSynchronize(s));
-        if (loss) *loss = pout[0];
-        if (pred) memcpy(pred, pout + 1, (size_t)n * sizeof(int32_t));
-        if (logits_out) memcpy(logits_out, ptail + (size_t)B * T, (size_t)n * 2 * sizeof(float));
-        return DS_OK;
-    }
+    if (int rc = head(eval, n, fc1, W2, G + w2_off(in0), err)) return rc;
+    if (eval) return finish(true, n, lr, loss, pred, logits_out, err);
     {   // dW1 = joint^T dfc1 (rows 0 .. 255 from y_fw, 256 .. 511 from y_bw); djoint = dfc1 W1^T
         GemmArgs g = gemm_args(act(Y, NLAYER - 1, T - 1), HID, 1, dfc1, FC, 0, G + w1_off(in0), FC, HID, FC, n, 0);
         g.nb2 = 2; g.sA2 = sActD; g.sC2 = (long long)HID * FC;
@@ -711,59 +797,7 @@ int Trainer::run(bool eval, int n, const int32_t* kmer, const float* means, cons
     }
     TCK(hipEventRecord(ev[4], s));
 
-    // ---- Adam on every tensor of the block
-    const float lr_t = adam_step_size(lr, cfg.beta1, cfg.beta2, step_count + 1);
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((PF + 255) / 256)), dim3(256), 0, s, P, G, M, V, (long long)PF, lr_t, cfg.beta1,
-                       cfg.beta2, cfg.epsilon);
-    TCK(hipGetLastError());
-    TCK(hipEventRecord(ev[5], s));
-
-    TCK(hipMemcpyAsync(pout, d_loss, sizeof(float), hipMemcpyDeviceToHost, s));
-    TCK(hipMemcpyAsync(pout + 1, d_pred, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    TCK(hipStreamSynchronize(s));
-    if (loss) *loss = pout[0];
-    if (pred) memcpy(pred, pout + 1, (size_t)n * sizeof(int32_t));
-    // phases in the order ds_get_train_times reports them: forward sweep, backward sweep, weight gradients, head, Adam
-    const int from[NPHASE] = {0, 2, 3, 1, 4};
-    for (int k = 0; k < NPHASE; ++k) {
-        float t_ms = 0.f;
-        TCK(hipEventElapsedTime(&t_ms, ev[from[k]], ev[from[k] + 1]));
-        ms[k] += t_ms;
-    }
-    steps_timed += 1;
-    step_count += 1;
-    last_n = n;
-    return DS_OK;
-}
-
-int Trainer::read_params(float* out, std::string* err)
-{
-    TCK(hipSetDevice(device));
-    TCK(hipMemcpy(out, P, param_floats(in0) * sizeof(float), hipMemcpyDeviceToHost));
-    return DS_OK;
-}
-
-int64_t Trainer::get(const float* block, int idx, float* out, int64_t cap, std::string* err)
-{
-    const int64_t count = tensor_floats(idx, in0);
-    if (cap < count) { if (err) *err = "buffer too small for " + tensor_name(idx); return DS_ERR_INVALID; }
-    TCK(hipSetDevice(device));
-    TCK(hipMemcpy(out, block + tensor_off(idx, in0), count * sizeof(float), hipMemcpyDeviceToHost));
-    return count;
-}
-
-int64_t Trainer::get_mask(int stream_id, uint8_t* out, int64_t cap, std::string* err)
-{
-    const int W = stream_width(stream_id), steps = stream_id < 6 ? T : 1;
-    const int64_t count = (int64_t)last_n * steps * W;
-    if (cap < count) { if (err) *err = "mask buffer too small"; return DS_ERR_INVALID; }
-    TCK(hipSetDevice(device));
-    hipLaunchKernelGGL(mask_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, d_mask, last_n, steps, W, stream_id,
-                       keep_threshold(cfg.keep_prob), cfg.seed, (long long)(step_count - 1));
-    TCK(hipGetLastError());
-    TCK(hipMemcpyAsync(out, d_mask, count, hipMemcpyDeviceToHost, stream));
-    TCK(hipStreamSynchronize(stream));
-    return count;
+    return finish(false, n, lr, loss, pred, logits_out, err);
 }
 
 }  // namespace dstr

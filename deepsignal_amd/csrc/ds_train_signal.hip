@@ -296,106 +296,6 @@ __global__ void avgpool_kernel(const float* in, float* out, int n, int W, int C,
     out[idx] = s;
 }
 
-struct HeadArgs {
-    const float *fc1, *W2;
-    float *drop1, *dfc1, *logits, *dfc2, *rowloss;
-    const int32_t* labels;
-    int32_t* pred;
-    int n, J;
-    float inv_keep, pos_weight, grad_scale;
-    uint32_t thr;
-    uint64_t seed;
-    long long step;
-};
-
-__device__ inline float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
-// stable weighted cross entropy on one logit (tf.nn.weighted_cross_entropy_with_logits) and its derivative, as ds_train.hip's
-__device__ inline float wce(float x, float zt, float pw, float* dx)
-{
-    const float q = 1.f + (pw - 1.f) * zt;
-    const float sp = log1pf(expf(-fabsf(x))) + fmaxf(-x, 0.f);
-    *dx = (1.f - zt) - q * sigmoidf_(-x);
-    return (1.f - zt) * x + q * sp;
-}
-
-// one workgroup per row, the joint layers' second half at width J: dropout of fc1, fc2 = drop1 W2, dropout of the
-// logits, the row's loss terms and prediction, and the gradient back to fc1. A thread adds its units in ascending order, then a fixed tree.
-__global__ __launch_bounds__(256) void signal_head_kernel(HeadArgs a)
-{
-    __shared__ float red[2][256];
-    __shared__ float dl[2];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    const uint64_t rk1 = dstr::row_key(dstr::stream_key(a.seed, a.step, STREAM_FC1), row);
-    float p0 = 0.f, p1 = 0.f;
-    for (int k = tid; k < a.J; k += 256) {
-        const float dv = dstr::kept(rk1, 0, k, a.thr) ? a.fc1[(size_t)row * a.J + k] * a.inv_keep : 0.f;
-        a.drop1[(size_t)row * a.J + k] = dv;
-        p0 = fmaf(dv, a.W2[k * 2], p0);
-        p1 = fmaf(dv, a.W2[k * 2 + 1], p1);
-    }
-    red[0][tid] = p0; red[1][tid] = p1;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) { red[0][tid] += red[0][tid + w]; red[1][tid] += red[1][tid + w]; }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const uint64_t rk2 = dstr::row_key(dstr::stream_key(a.seed, a.step, STREAM_FC2), row);
-        const bool m0 = dstr::kept(rk2, 0, 0, a.thr), m1 = dstr::kept(rk2, 0, 1, a.thr);
-        const float l0 = m0 ? red[0][0] * a.inv_keep : 0.f, l1 = m1 ? red[1][0] * a.inv_keep : 0.f;
-        a.logits[row * 2] = l0; a.logits[row * 2 + 1] = l1;
-        const int lab = a.labels[row];
-        float d0 = 0.f, d1 = 0.f, loss;
-        if (a.pos_weight == 1.f) {
-            loss = wce(l0, lab == 0 ? 1.f : 0.f, 1.f, &d0) + wce(l1, lab == 1 ? 1.f : 0.f, 1.f, &d1);
-            a.pred[row] = l1 > l0 ? 1 : 0;
-        } else {
-            loss = wce(l1, (float)lab, a.pos_weight, &d1);
-            a.pred[row] = l1 > 0.f ? 1 : 0;
-        }
-        a.rowloss[row] = loss;
-        d0 = m0 ? d0 * a.grad_scale * a.inv_keep : 0.f;
-        d1 = m1 ? d1 * a.grad_scale * a.inv_keep : 0.f;
-        a.dfc2[row * 2] = d0; a.dfc2[row * 2 + 1] = d1;
-        dl[0] = d0; dl[1] = d1;
-    }
-    __syncthreads();
-    for (int k = tid; k < a.J; k += 256) {
-        const float dd = dl[0] * a.W2[k * 2] + dl[1] * a.W2[k * 2 + 1];
-        a.dfc1[(size_t)row * a.J + k] = dstr::kept(rk1, 0, k, a.thr) ? dd * a.inv_keep : 0.f;
-    }
-}
-
-// loss = the rows' terms in row order, times `scale`; dW2[k][c] = sum over rows of drop1[row][k] dfc2[row][c] in row order (nullptr: none)
-__global__ void signal_head_reduce_kernel(const float* rowloss, const float* drop1, const float* dfc2, float* loss, float* dW2, int n, int J, float scale)
-{
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx < J * NCLASS) {
-        if (!dW2) return;
-        const int k = idx >> 1, c = idx & 1;
-        float s = 0.f;
-        for (int r = 0; r < n; ++r) s = fmaf(drop1[(size_t)r * J + k], dfc2[r * 2 + c], s);
-        dW2[idx] = s;
-    } else if (idx == J * NCLASS) {
-        float s = 0.f;
-        for (int r = 0; r < n; ++r) s += rowloss[r];
-        *loss = s * scale;
-    }
-}
-
-int hip_fail(std::string* err, const char* what, hipError_t e)
-{
-    (void)hipGetLastError();
-    if (err) *err = std::string(what) + ": " + hipGetErrorString(e);
-    return e == hipErrorOutOfMemory ? DS_ERR_NOMEM : DS_ERR_HIP;
-}
-#define TCK(expr)                                                   \
-    do {                                                            \
-        hipError_t e_ = (expr);                                     \
-        if (e_ != hipSuccess) return hip_fail(err, #expr, e_);      \
-    } while (0)
-
 inline unsigned blocks(long long count) { return (unsigned)((count + 255) / 256); }
 
 // rows per slab and slabs of a reduction over R rows: at most NSLAB slabs, a function of R alone
@@ -456,45 +356,19 @@ void Trainer::layout(int S_)
         tensors[c.scope + "/" + c.bn + "/moving_mean"] = {1, c.ms_off, c.cout};
         tensors[c.scope + "/" + c.bn + "/moving_variance"] = {1, c.ms_off + c.cout, c.cout};
     }
-    w1_off = p; w2_off = p + (int64_t)J * J; PF = w2_off + (int64_t)J * NCLASS; MSF = s; STF = st;
+    w1_off = p; w2_off = p + (int64_t)J * J; PF = w2_off + (int64_t)J * NCLASS; MSF = s; STF = st;      // open() is given these back
     tensors["dense/kernel"] = {0, w1_off, (int64_t)J * J};
     tensors["dense_1/kernel"] = {0, w2_off, (int64_t)J * NCLASS};
 }
 
-void Trainer::release()
+int Trainer::begin(int dev, int S_, int B_, const dstr::Config& c, const dstr::TensorMap& weights, std::string* err)
 {
-    if (device >= 0) hipSetDevice(device);
-    if (stream) hipStreamSynchronize(stream);
-    for (void* p : allocs) hipFree(p);
-    allocs.clear();
-    P = nullptr;
-    if (pin) hipHostFree(pin);
-    pin = nullptr;
-    for (hipEvent_t& e : ev) { if (e) hipEventDestroy(e); e = nullptr; }
-    if (stream) hipStreamDestroy(stream);
-    stream = nullptr;
-    (void)hipGetLastError();
-    S = B = 0;
-}
-
-Trainer::~Trainer() { release(); }
-
-int Trainer::begin(int dev, int S_, int B_, const dstr::Config& c, const std::map<std::string, std::vector<float>>& weights, std::string* err)
-{
-    TCK(hipSetDevice(dev));
     if (S_ != S || B_ != B || dev != device || !P) {
-        release();
-        device = dev;
         layout(S_);
-        B = B_;
-        auto alloc = [&](auto** p, size_t count) {
-            hipError_t e = hipMalloc((void**)p, std::max<size_t>(count * sizeof(**p), 256));
-            if (e == hipSuccess) allocs.push_back((void*)*p);
-            return e;
-        };
+        // mask staging: fc1 [B][J]; pinned inputs: the signals [B][S]
+        if (int rc = open(dev, B_, PF, MSF, J, (size_t)B_ * J, (size_t)B_ * S, err)) return rc;
         const size_t Bz = (size_t)B;
-        TCK(alloc(&P, (size_t)PF)); TCK(alloc(&G, (size_t)PF)); TCK(alloc(&M, (size_t)PF)); TCK(alloc(&V, (size_t)PF));
-        TCK(alloc(&MS, (size_t)MSF)); TCK(alloc(&ST, (size_t)STF));
+        TCK(alloc(&ST, (size_t)STF));
         TCK(alloc(&d_sig, Bz * S));
         TCK(alloc(&pool1, Bz * Wa * 64));
         for (int m = 0; m < NMOD; ++m) {
@@ -537,38 +411,18 @@ int Trainer::begin(int dev, int S_, int B_, const dstr::Config& c, const std::ma
             taps[tp] = {out + 192, cv[0].Wout, 48, INC_OUT};
         }
         for (Conv& cv : convs) taps[cv.tap] = {cv.y, cv.Wout, cv.cout, cv.ldy};
-        TCK(alloc(&feat, Bz * J)); TCK(alloc(&fc1, Bz * J)); TCK(alloc(&drop1, Bz * J)); TCK(alloc(&dfc1, Bz * J)); TCK(alloc(&dfeat, Bz * J));
-        TCK(alloc(&logits, Bz * 2)); TCK(alloc(&dfc2, Bz * 2)); TCK(alloc(&rowloss, Bz));
+        TCK(alloc(&feat, Bz * J)); TCK(alloc(&dfeat, Bz * J));
         taps["feat"] = {feat, 1, J, J};
         taps["logits"] = {logits, 1, 2, 2};
         const size_t gmax = std::max(Bz * Wa * 256, Bz * W1 * 64);
         TCK(alloc(&gA, gmax)); TCK(alloc(&gB, gmax)); TCK(alloc(&gPool, Bz * Wa * 256)); TCK(alloc(&gMid, Bz * Wa * 64)); TCK(alloc(&gMid32, Bz * Wa * 32));
         TCK(alloc(&part, (size_t)NSLAB * 2 * 256)); TCK(alloc(&slab, (size_t)NSLAB * wmax));
-        TCK(alloc(&d_lab, Bz)); TCK(alloc(&d_pred, Bz)); TCK(alloc(&d_loss, 1)); TCK(alloc(&d_mask, Bz * J));
-        TCK(hipHostMalloc((void**)&pin, (Bz * S + 4 * Bz + 4) * 4, hipHostMallocDefault));
-        TCK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        for (hipEvent_t& e : ev) TCK(hipEventCreate(&e));
     }
-    TCK(hipStreamSynchronize(stream));
-    cfg = c;
-    std::vector<float> hp((size_t)PF), hs((size_t)MSF, 0.f);
-    for (const auto& kv : tensors) {
-        auto it = weights.find(kv.first);
-        if (it == weights.end() || (int64_t)it->second.size() != kv.second.count) { if (err) *err = "missing/bad tensor " + kv.first; return DS_ERR_INVALID; }
-        std::copy(it->second.begin(), it->second.end(), (kv.second.kind ? hs.begin() : hp.begin()) + kv.second.off);
-    }
-    TCK(hipMemcpy(P, hp.data(), (size_t)PF * sizeof(float), hipMemcpyHostToDevice));
-    TCK(hipMemcpy(MS, hs.data(), (size_t)MSF * sizeof(float), hipMemcpyHostToDevice));
-    TCK(hipMemset(G, 0, (size_t)PF * sizeof(float)));
-    TCK(hipMemset(M, 0, (size_t)PF * sizeof(float)));
-    TCK(hipMemset(V, 0, (size_t)PF * sizeof(float)));
-    step_count = 0;
-    last_n = 0;
     taps_valid = failed = false;
-    return DS_OK;
+    return restart(c, weights, err);
 }
 
-int Trainer::run(bool eval, int n, const float* signals, const int32_t* labels, float lr, float* loss, int32_t* pred, float* logits_out, std::string* err)
+int Trainer::step(bool eval, int n, const dstr::Inputs& in, float lr, float* loss, int32_t* pred, float* logits_out, std::string* err)
 {
     // a step that stopped part-way has advanced some layers' moving statistics and not the step counter: nothing may build on that
     if (failed) { if (err) *err = "an earlier step of this run failed part-way; its state is unusable: ds_train_begin_signal again"; return DS_ERR_INVALID; }
@@ -576,16 +430,11 @@ int Trainer::run(bool eval, int n, const float* signals, const int32_t* labels, 
     hipStream_t s = stream;
     taps_valid = false;      // from here on the stored layer outputs are being overwritten
     if (!eval) failed = true;      // until the step has run to its end
-    const float keep_prob = eval ? 1.f : cfg.keep_prob;
-    const float inv_keep = 1.f / keep_prob;
-    const uint32_t thr = dstr::keep_threshold(keep_prob);
     const float debias = moving_debias(step_count + 1);
 
-    memcpy(pin, signals, (size_t)n * S * sizeof(float));
-    int32_t* plab = reinterpret_cast<int32_t*>(pin + (size_t)B * S);
-    memcpy(plab, labels, (size_t)n * sizeof(int32_t));
+    memcpy(pin, in.signals, (size_t)n * S * sizeof(float));
     TCK(hipMemcpyAsync(d_sig, pin, (size_t)n * S * sizeof(float), hipMemcpyHostToDevice, s));
-    TCK(hipMemcpyAsync(d_lab, plab, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (int rc = stage_labels(n, in.labels, err)) return rc;
 
     auto conv_launch = [&](const Conv& c, int mode, float* out, int ldo) {
         ConvArgs a{};
@@ -683,27 +532,8 @@ int Trainer::run(bool eval, int n, const float* signals, const int32_t* labels, 
     float* Wd1 = P + w1_off;
     float* Wd2 = P + w2_off;
     TCK(dstr::launch_gemm(s, dstr::make_gemm(feat, J, 0, Wd1, J, 0, fc1, J, n, J, J, 0)));
-    const bool two_col = cfg.pos_weight == 1.f;
-    const float scale = 1.f / (float)(two_col ? 2 * n : n);
-    HeadArgs ha{};
-    ha.fc1 = fc1; ha.W2 = Wd2; ha.drop1 = drop1; ha.dfc1 = dfc1; ha.logits = logits; ha.dfc2 = dfc2; ha.rowloss = rowloss; ha.labels = d_lab;
-    ha.pred = d_pred; ha.n = n; ha.J = J; ha.inv_keep = inv_keep; ha.pos_weight = cfg.pos_weight; ha.grad_scale = scale; ha.thr = thr;
-    ha.seed = cfg.seed; ha.step = step_count;
-    hipLaunchKernelGGL(signal_head_kernel, dim3(n), dim3(256), 0, s, ha);
-    TCK(hipGetLastError());
-    hipLaunchKernelGGL(signal_head_reduce_kernel, dim3(blocks(J * NCLASS + 1)), dim3(256), 0, s, rowloss, drop1, dfc2, d_loss, eval ? nullptr : G + w2_off, n, J, scale);
-    TCK(hipGetLastError());
-    float* pout = pin + (size_t)B * S + B;      // [loss | pred [B] | logits [B][2]]
-    if (eval) {      // the forward, its loss and prediction alone: no gradient, moment, parameter, statistic or counter is written
-        TCK(hipMemcpyAsync(pout, d_loss, sizeof(float), hipMemcpyDeviceToHost, s));
-        TCK(hipMemcpyAsync(pout + 1, d_pred, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        TCK(hipMemcpyAsync(pout + 1 + B, logits, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, s));
-        TCK(hipStreamSynchronize(s));
-        if (loss) *loss = pout[0];
-        if (pred) memcpy(pred, pout + 1, (size_t)n * sizeof(int32_t));
-        if (logits_out) memcpy(logits_out, pout + 1 + B, (size_t)n * 2 * sizeof(float));
-        return DS_OK;
-    }
+    RUN(head(eval, n, fc1, Wd2, G + w2_off, err));
+    if (eval) return finish(true, n, lr, loss, pred, logits_out, err);      // no gradient, moment, parameter, statistic or counter is written
     TCK(dstr::launch_gemm(s, dstr::make_gemm(feat, J, 1, dfc1, J, 0, G + w1_off, J, J, J, n, 0)));      // dW1 = feat^T dfc1
     TCK(dstr::launch_gemm(s, dstr::make_gemm(dfc1, J, 0, Wd1, J, 1, dfeat, J, n, J, J, 0)));            // dfeat = dfc1 W1^T
     TCK(hipEventRecord(ev[2], s));
@@ -772,42 +602,11 @@ int Trainer::run(bool eval, int n, const float* signals, const int32_t* labels, 
     }
     TCK(hipEventRecord(ev[4], s));
 
-    // ---- Adam on the 341 trained tensors, one block
-    const float lr_t = dstr::adam_step_size(lr, cfg.beta1, cfg.beta2, step_count + 1);
-    TCK(dstr::launch_adam(s, P, G, M, V, (long long)PF, lr_t, cfg.beta1, cfg.beta2, cfg.epsilon));
-    TCK(hipEventRecord(ev[5], s));
+    RUN(finish(false, n, lr, loss, pred, logits_out, err));      // Adam on the 341 trained tensors, one block
 #undef RUN
-
-    TCK(hipMemcpyAsync(pout, d_loss, sizeof(float), hipMemcpyDeviceToHost, s));
-    TCK(hipMemcpyAsync(pout + 1, d_pred, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    TCK(hipStreamSynchronize(s));
-    if (loss) *loss = pout[0];
-    if (pred) memcpy(pred, pout + 1, (size_t)n * sizeof(int32_t));
-    // phases as ds_get_train_times reports them: forward (signal model), backward (data and BN gradients), weight gradients, joint layers, Adam
-    const int from[dstr::NPHASE] = {0, 2, 3, 1, 4};
-    for (int k = 0; k < dstr::NPHASE; ++k) {
-        float t_ms = 0.f;
-        TCK(hipEventElapsedTime(&t_ms, ev[from[k]], ev[from[k] + 1]));
-        ms[k] += t_ms;
-    }
-    steps_timed += 1;
-    step_count += 1;
-    last_n = n;
     taps_valid = true;
     failed = false;
     return DS_OK;
-}
-
-int64_t Trainer::get(const char* name, bool grad, float* out, int64_t cap, std::string* err)
-{
-    auto it = tensors.find(name ? name : "");
-    if (it == tensors.end() || !out) { if (err) *err = std::string("unknown tensor ") + (name ? name : "(null)"); return DS_ERR_INVALID; }
-    const TensorRef& t = it->second;
-    if (grad && t.kind) { if (err) *err = std::string("a moving statistic is not trained and has no gradient: ") + name; return DS_ERR_INVALID; }
-    if (cap < t.count) { if (err) *err = std::string("buffer too small for ") + name; return DS_ERR_INVALID; }
-    TCK(hipSetDevice(device));
-    TCK(hipMemcpy(out, (t.kind ? MS : grad ? G : P) + t.off, (size_t)t.count * sizeof(float), hipMemcpyDeviceToHost));
-    return t.count;
 }
 
 int64_t Trainer::get_tap(const char* name, float* out, int64_t cap, std::string* err)
@@ -823,31 +622,6 @@ int64_t Trainer::get_tap(const char* name, float* out, int64_t cap, std::string*
     TCK(hipStreamSynchronize(stream));
     TCK(hipMemcpy2D(out, (size_t)t.C * sizeof(float), t.p, (size_t)t.ld * sizeof(float), (size_t)t.C * sizeof(float), (size_t)rows, hipMemcpyDeviceToHost));
     return count;
-}
-
-int64_t Trainer::get_mask(int stream_id, uint8_t* out, int64_t cap, std::string* err)
-{
-    const int W = stream_id == STREAM_FC1 ? J : NCLASS;
-    const int64_t count = (int64_t)last_n * W;
-    if (cap < count) { if (err) *err = "mask buffer too small"; return DS_ERR_INVALID; }
-    TCK(hipSetDevice(device));
-    TCK(dstr::launch_mask(stream, d_mask, last_n, 1, W, stream_id, dstr::keep_threshold(cfg.keep_prob), cfg.seed, (long long)(step_count - 1)));
-    TCK(hipMemcpyAsync(out, d_mask, count, hipMemcpyDeviceToHost, stream));
-    TCK(hipStreamSynchronize(stream));
-    return count;
-}
-
-int Trainer::read_all(std::map<std::string, std::vector<float>>* out, std::string* err)
-{
-    TCK(hipSetDevice(device));
-    std::vector<float> hp((size_t)PF), hs((size_t)MSF);
-    TCK(hipMemcpy(hp.data(), P, (size_t)PF * sizeof(float), hipMemcpyDeviceToHost));
-    TCK(hipMemcpy(hs.data(), MS, (size_t)MSF * sizeof(float), hipMemcpyDeviceToHost));
-    for (const auto& kv : tensors) {
-        const float* src = (kv.second.kind ? hs.data() : hp.data()) + kv.second.off;
-        (*out)[kv.first].assign(src, src + kv.second.count);
-    }
-    return DS_OK;
 }
 
 }  // namespace dsts

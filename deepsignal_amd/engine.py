@@ -985,33 +985,34 @@ class Engine:
                 raise ValueError("training arrays have inconsistent shapes")
         return n, means, stds, sanums, labels, kmer
 
+    def _train_call(self, what: str, n: int, *args, lr: Optional[float] = None):
+        """One step (`lr` given) or evaluation entry `what` on n rows: makes the loss, prediction and, for an evaluation, logits
+        buffers, calls it with the inputs `args` in front and checks the return code."""
+        loss = ctypes.c_float()
+        pred = np.empty((n,), np.int32)
+        fn = getattr(self._lib, what)
+        if lr is not None:
+            self._check(fn(self._h, n, *args, lr, ctypes.byref(loss), pred.ctypes.data), what)
+            return float(loss.value), pred
+        logits = np.empty((n, 2), np.float32)
+        self._check(fn(self._h, n, *args, ctypes.byref(loss), pred.ctypes.data, logits.ctypes.data), what)
+        return float(loss.value), pred, logits
+
     def train_step(self, means, stds, sanums, labels, lr: float, kmer=None) -> Tuple[float, np.ndarray]:
         """One step on these rows: (cost, prediction int32[n]). `kmer` int32[n, kmer_len]: the codes, which a run that trains
         the embedding needs (without them it is refused); given, the step goes through ds_train_step_base."""
         n, means, stds, sanums, labels, kmer = self._train_arrays(means, stds, sanums, labels, kmer)
-        loss = ctypes.c_float()
-        pred = np.empty((n,), np.int32)
+        rows = (means.ctypes.data, stds.ctypes.data, sanums.ctypes.data, labels.ctypes.data)
         if kmer is not None:
-            rc = self._lib.ds_train_step_base(self._h, n, kmer.ctypes.data, means.ctypes.data, stds.ctypes.data,
-                                              sanums.ctypes.data, labels.ctypes.data, lr, ctypes.byref(loss), pred.ctypes.data)
-            self._check(rc, "ds_train_step_base")
-        else:
-            rc = self._lib.ds_train_step(self._h, n, means.ctypes.data, stds.ctypes.data, sanums.ctypes.data, labels.ctypes.data,
-                                         lr, ctypes.byref(loss), pred.ctypes.data)
-            self._check(rc, "ds_train_step")
-        return float(loss.value), pred
+            return self._train_call("ds_train_step_base", n, kmer.ctypes.data, *rows, lr=lr)
+        return self._train_call("ds_train_step", n, *rows, lr=lr)
 
     def train_eval(self, means, stds, sanums, labels, kmer=None) -> Tuple[float, np.ndarray, np.ndarray]:
         """The training forward on the current parameters with keep_prob 1 and nothing changed: (cost, prediction int32[n],
         logits float32[n, 2])."""
         n, means, stds, sanums, labels, kmer = self._train_arrays(means, stds, sanums, labels, kmer)
-        loss = ctypes.c_float()
-        pred = np.empty((n,), np.int32)
-        logits = np.empty((n, 2), np.float32)
-        rc = self._lib.ds_train_eval(self._h, n, None if kmer is None else kmer.ctypes.data, means.ctypes.data, stds.ctypes.data,
-                                     sanums.ctypes.data, labels.ctypes.data, ctypes.byref(loss), pred.ctypes.data, logits.ctypes.data)
-        self._check(rc, "ds_train_eval")
-        return float(loss.value), pred, logits
+        return self._train_call("ds_train_eval", n, None if kmer is None else kmer.ctypes.data, means.ctypes.data, stds.ctypes.data,
+                                sanums.ctypes.data, labels.ctypes.data)
 
     # -- ... of the signal-only model (train_model.py with --is_cnn yes --is_rnn no) --------------
     def _signal_arrays(self, signals, labels):
@@ -1025,23 +1026,13 @@ class Engine:
     def train_step_signal(self, signals, labels, lr: float) -> Tuple[float, np.ndarray]:
         """One step of a signal run on signals float32[n, signal_len]: (cost, prediction int32[n])."""
         n, signals, labels = self._signal_arrays(signals, labels)
-        loss = ctypes.c_float()
-        pred = np.empty((n,), np.int32)
-        rc = self._lib.ds_train_step_signal(self._h, n, signals.ctypes.data, labels.ctypes.data, lr, ctypes.byref(loss), pred.ctypes.data)
-        self._check(rc, "ds_train_step_signal")
-        return float(loss.value), pred
+        return self._train_call("ds_train_step_signal", n, signals.ctypes.data, labels.ctypes.data, lr=lr)
 
     def train_eval_signal(self, signals, labels) -> Tuple[float, np.ndarray, np.ndarray]:
         """training = False, keep_prob = 1: the forward on the current parameters with the moving statistics, nothing changed:
         (cost, prediction int32[n], logits float32[n, 2])."""
         n, signals, labels = self._signal_arrays(signals, labels)
-        loss = ctypes.c_float()
-        pred = np.empty((n,), np.int32)
-        logits = np.empty((n, 2), np.float32)
-        rc = self._lib.ds_train_eval_signal(self._h, n, signals.ctypes.data, labels.ctypes.data, ctypes.byref(loss), pred.ctypes.data,
-                                            logits.ctypes.data)
-        self._check(rc, "ds_train_eval_signal")
-        return float(loss.value), pred, logits
+        return self._train_call("ds_train_eval_signal", n, signals.ctypes.data, labels.ctypes.data)
 
     def train_tap(self, name: str, n: int) -> np.ndarray:
         """A layer output of the last step of a signal run (`signal_tap_names`), float32 [n, W, C] ([n, C] for feat and logits)."""

@@ -38,6 +38,16 @@ def test_a_rows_mask_does_not_depend_on_n(ref):
             assert (ref(21, 2, s, n, 5, 0.5) == big[:n]).all()
 
 
+def test_wide_reference_is_the_same_function(ref):
+    """ds_train_mask_reference and ds_train_mask_reference_wide are one function: the joint-layer streams agree byte for byte at
+    the BiLSTM widths, and a unit's mask does not depend on the width of its row."""
+    from deepsignal_amd.engine import train_mask_reference_wide as wide
+    seed, step, n, T, kp = 21, 2, 5, 5, 0.5
+    assert ref(seed, step, "fc1", n, T, kp).tobytes() == wide(seed, step, "fc1", n, 512, kp).tobytes()
+    assert ref(seed, step, "fc2", n, T, kp).tobytes() == wide(seed, step, "fc2", n, 2, kp).tobytes()
+    assert np.ascontiguousarray(wide(seed, step, "fc1", n, 720, kp)[:, :240]).tobytes() == wide(seed, step, "fc1", n, 240, kp).tobytes()
+
+
 @pytest.mark.parametrize("keep_prob", [0.5, 0.8, 0.1])
 def test_kept_share_is_keep_prob(ref, keep_prob):
     m = ref(1234, 7, "bw_l1", 64, 17, keep_prob)

@@ -6,13 +6,24 @@ cores. Writes profiles/train_throughput.json.
     python tools/train_throughput.py [--steps 30] [--warmup 5] [--cpu_steps 2] [--is_base no] [--out profiles/train_throughput.json]
     python tools/train_throughput.py --parity [--out profiles/train_parity.json]
     python tools/train_throughput.py --variant signal [--signal_len 360] [--cpu_steps 1] [--out profiles/train_throughput_signal.json]
+    python tools/train_throughput.py --digest [--against other_side.json] [--out profiles/train_runs_digest.json]
 
 --parity writes the distances tests/test_gpu_train_grad.py asserts on (GPU and float32 statement against the float64 statement,
 per case and tensor) instead. --is_base yes times the step with the embedding trained (ds_train_step_base, codes uniform over
 A, C, G, T); the default no is the step denoise runs, through ds_train_step. --variant signal times the signal-only model's step
 (ds_train_step_signal: stem, eleven inception modules, joint layers at J = w_c x 240) on normal signals; its CPU baseline is
-tests/train_statement_signal.py in float32, one step without a warm-up (a step takes far longer than any start-up cost)."""
+tests/train_statement_signal.py in float32, one step without a warm-up (a step takes far longer than any start-up cost).
+--cpu_steps 0 skips the CPU baseline, which is what a comparison of two builds wants.
+
+--digest is a refactor's proof that no bit moved: small runs of the three variants (RNN-only, is_base, signal at signal_len 40;
+max_batch 8, n 6, kmer_len 5, keep_prob 0.5, pos_weight 1 and 3), three steps and one evaluation each, and a sha256 per quantity:
+the loss of every step, the evaluation's loss, prediction and logits, every tensor (a signal run's moving statistics among them),
+gradient and mask stream after the third step, and a signal run's taps. It uses public Engine methods only, so the same file runs
+in a checkout of another commit. Alone it writes the sha256 per quantity. --against names the file another commit wrote that way:
+what is written then is both sides by group of quantities (one combined sha256 per side, how many of the group's quantities differ)
+and the first quantity that differs, and the exit status is 1 if any does."""
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -132,6 +143,87 @@ def throughput_signal(a):
     return out
 
 
+def digest(a):
+    from deepsignal_amd import engine, weights
+    n, B, T, S, keep_prob = 6, 8, 5, 40, 0.5
+    rng = np.random.default_rng(11)
+    rows = {"means": rng.normal(0.0, 1.0, (n, T)).astype(np.float32), "stds": rng.uniform(0.05, 1.0, (n, T)).astype(np.float32),
+            "sanums": rng.integers(1, 60, (n, T)).astype(np.float32)}
+    kmer = rng.integers(0, 1024, (n, T)).astype(np.int32)
+    signals = rng.normal(0.0, 1.0, (n, S)).astype(np.float32)
+    labels = np.array([0, 1, 1, 0, 1, 0], np.int32)
+    out = {}
+
+    def put(key, value):
+        out[key] = hashlib.sha256(np.ascontiguousarray(value).tobytes()).hexdigest()
+
+    for variant in ("rnn", "base", "signal"):
+        for pos_weight in (1.0, 3.0):
+            tag = "%s/pos_weight_%g/" % (variant, pos_weight)
+            if variant == "signal":
+                w = weights.random_weights(seed=7, signal_len=S, is_cnn=True, is_rnn=False, randomize_bn=True)
+                eng = engine.Engine(signal_len=S, max_batch=B, is_cnn=True, is_rnn=False, device=a.device)
+                step = lambda: eng.train_step_signal(signals, labels, 1e-3)
+                evaluate = lambda: eng.train_eval_signal(signals, labels)
+                streams = engine.SIGNAL_MASK_STREAMS
+            else:
+                base = variant == "base"
+                w = weights.random_weights(seed=7, is_cnn=False, is_base=base, kmer_len=T)
+                eng = engine.Engine(kmer_len=T, max_batch=B, is_cnn=False, is_base=base, device=a.device)
+                step = lambda: eng.train_step(rows["means"], rows["stds"], rows["sanums"], labels, 1e-3, kmer=kmer if base else None)
+                evaluate = lambda: eng.train_eval(rows["means"], rows["stds"], rows["sanums"], labels, kmer=kmer if base else None)
+                streams = engine.MASK_STREAMS
+            eng.load_weights(w)
+            eng.train_begin(keep_prob=keep_prob, pos_weight=pos_weight, seed=3, base=variant == "base")
+            for k in range(3):
+                loss, pred = step()
+                put(tag + "step%d/loss" % k, np.float32(loss))
+                put(tag + "step%d/prediction" % k, pred)
+            for name, v in eng.train_tensors().items():
+                put(tag + "tensor/" + name, v)
+            for name, v in eng.train_grads().items():
+                put(tag + "gradient/" + name, v)
+            for name in streams:
+                put(tag + "mask/" + name, eng.train_mask(name, n))
+            if variant == "signal":
+                for name in engine.signal_tap_names():
+                    put(tag + "tap/" + name, eng.train_tap(name, n))
+            loss, pred, logits = evaluate()
+            put(tag + "eval/loss", np.float32(loss))
+            put(tag + "eval/prediction", pred)
+            put(tag + "eval/logits", logits)
+            eng.close()
+    if not a.against:
+        return out
+    with open(a.against) as f:
+        other = json.load(f)
+    return compare_digests(other, out, {"max_batch": B, "n": n, "kmer_len": T, "signal_len": S, "keep_prob": keep_prob, "steps": 3, "lr": 1e-3})
+
+
+def compare_digests(parent, change, shape):
+    """Both sides in one record that stays readable: the quantities go by group (variant / pos_weight / kind: the steps' and the
+    evaluation's outputs, tensor, gradient, mask, tap), and a group carries one sha256 per side over its `key=sha256` lines in key
+    order, its number of quantities and how many of them differ."""
+    def group(key):
+        part = key.split("/")
+        return "/".join(part[:2] + [part[2] if part[2] in ("tensor", "gradient", "mask", "tap") else "outputs"])
+
+    def combined(side, keys):
+        return hashlib.sha256("".join("%s=%s\n" % (k, side.get(k)) for k in keys).encode()).hexdigest()
+
+    keys = sorted(set(parent) | set(change))
+    differ = [k for k in keys if parent.get(k) != change.get(k)]
+    groups = {}
+    for name in sorted(set(map(group, keys))):
+        mine = [k for k in keys if group(k) == name]
+        groups[name] = {"quantities": len(mine), "differ": sum(parent.get(k) != change.get(k) for k in mine),
+                        "parent": combined(parent, mine), "change": combined(change, mine)}
+    # the first differing quantity in the order the run produced them (the change's insertion order: steps, tensors, ..., evaluation)
+    first = next((k for k in change if parent.get(k) != change[k]), differ[0] if differ else None)
+    return {"shape": shape, "quantities": len(keys), "differ": len(differ), "first_differing": first,
+            "differing_outputs": [k for k in differ if group(k).endswith("/outputs")], "groups": groups}
+
+
 def parity(a):
     import torch
     import test_gpu_train_grad as cases
@@ -168,16 +260,22 @@ def main():
     ap.add_argument("--variant", default="rnn", choices=["rnn", "signal"], help="signal: the signal-only model's step (ds_train_step_signal)")
     ap.add_argument("--signal_len", type=int, default=360)
     ap.add_argument("--parity", action="store_true")
+    ap.add_argument("--digest", action="store_true", help="sha256 of every quantity of small runs of the three variants")
+    ap.add_argument("--against", default=None, help="with --digest: the digest another commit wrote, to be recorded and compared with")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.variant == "signal" and a.parity:
         ap.error("--parity covers the BiLSTM step; the signal step's distances are printed by tests/test_gpu_train_signal_grad.py")
-    result = parity(a) if a.parity else throughput_signal(a) if a.variant == "signal" else throughput(a)
-    default = "train_parity.json" if a.parity else "train_throughput_signal.json" if a.variant == "signal" else "train_throughput.json"
+    result = digest(a) if a.digest else parity(a) if a.parity else throughput_signal(a) if a.variant == "signal" else throughput(a)
+    default = "train_runs_digest.json" if a.digest else "train_parity.json" if a.parity else "train_throughput_signal.json" if a.variant == "signal" else "train_throughput.json"
     path = a.out or os.path.join(ROOT, "profiles", default)
     with open(path, "w") as f:
         json.dump(result, f, indent=1, sort_keys=True)
         f.write("\n")
+    if a.digest:
+        differ = result["differ"] if a.against else 0
+        print(json.dumps({"quantities": result["quantities"] if a.against else len(result), "differ": differ, "written": path}, sort_keys=True))
+        return 1 if differ else 0
     print(json.dumps(result if not a.parity else {"cases": len(result["cases"]), "written": path}, sort_keys=True))
     return 0
 
