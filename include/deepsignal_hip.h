@@ -163,7 +163,15 @@ int ds_finalize_weights(ds_handle *h);
  *     site whose act is NaN is unspecified.
  *  3. CODES. kmer values 0 .. 1023 select the embedding row; a value below 0 acts as 0 and one above 1023 as 1023 (no read
  *     outside the table). With is_base = 0 the codes are not read for their value at all.
- * tests/test_gpu_hostile_inputs.py holds the engine to this; DESIGN.md section 2 lists the cases. */
+ * tests/test_gpu_hostile_inputs.py holds the engine to this; DESIGN.md section 2 lists the cases.
+ *
+ * EXTENT, for every entry of this header and every buffer a caller owns, host or device: an entry writes the stated elements of a
+ * caller's buffer and no other byte of it, also when it refuses. act is n x class_num floats and pred n ints whatever max_batch is;
+ * an entry that takes a capacity (cap, capacity_rows, name_cap, info_cap, cap_words ...) writes nothing beyond it, and one that
+ * returns DS_ERR_INVALID or -(bytes needed) for a short capacity leaves that buffer untouched unless its own text says otherwise.
+ * Buffers are expected at their natural alignment. tests/test_gpu_output_extents.py and tests/test_output_extents_host.py hold
+ * every output between guard bands; tests/guard_bands.py lists them, and a new entry fails tests/test_output_extents_table.py
+ * until it is listed there. */
 int ds_forward(ds_handle *h, int32_t n, const int32_t *kmer, const float *means, const float *stds,
                const float *sanums, const float *signals, float *act, int32_t *pred);
 
@@ -427,7 +435,10 @@ int ds_recheck_select(ds_handle *h, int32_t n, const float *act, float margin, i
  * DS_TEXT_ROW_HOST are parsed here by the host parser: a malformed one fails the call with DS_ERR_IO and ds_last_error names its
  * index within the ticket ("row I of the ticket"); well-formed ones are forwarded once on the now idle slot by the steps of a
  * ds_forward pass (an attached recheck applies to them too) and merged in, so the results equal the host route's for every row.
- * A text ticket is waited with ds_wait_text only; a failed wait consumes the ticket. Same ticket order rules as ds_submit. */
+ * A text ticket is waited with ds_wait_text only; a failed wait consumes the ticket. Same ticket order rules as ds_submit.
+ * A short info_cap is such a failure (DS_ERR_INVALID, ds_last_error gives the bytes needed): nothing is written to info, while act,
+ * pred, kmer, labels and all n + 1 entries of info_off are (info_off[n] = the bytes needed), and the ticket is consumed. The six
+ * leading columns are never longer than the rows' own text, so the bytes of the submitted rows are always enough. */
 #define DS_TEXT_BYTES_PER_ROW 6144
 #define DS_TEXT_ROW_OK 0
 #define DS_TEXT_ROW_HOST 1

@@ -3,7 +3,8 @@ GPU): the directed table of values for the number rule, and the host extractor's
 import numpy as np
 
 from deepsignal_amd import extract_features as ef
-from deepsignal_amd.engine import ReadBatch, pack_info
+from deepsignal_amd import synth
+from deepsignal_amd.engine import ReadBatch, base_codes, pack_info
 
 LABEL = 1
 
@@ -54,3 +55,24 @@ def split_rows(text, row_off):
     rows = [text[a:b] for a, b in zip(row_off[:-1], row_off[1:])]
     assert all(r.endswith(b"\n") and r.count(b"\n") == 1 for r in rows)
     return [r[:-1].decode() for r in rows]
+
+
+def two_read_batch(T, norm, nsites=70):
+    """(ReadBatch, info blob, info offsets): `nsites` CG sites of two synthetic reads, half from each, at k-mer length T, and the
+    six leading columns of their rows. Shared by the output-extent tests (CPU and GPU)."""
+    reads = []
+    for i in range(2):
+        raw, starts, lengths, bases, scaling, offset = synth.synthetic_read(700 + 90 * i, 40 + i, long_bases=i)
+        reads.append((raw, starts, lengths, base_codes(bases), scaling, offset, 500 + i))
+    sr, sl = [], []
+    for i, r in enumerate(reads):
+        codes = r[3]
+        for loc in range(T // 2, len(codes) - T // 2):
+            if codes[loc] == 1 and codes[loc + 1] == 2:
+                sr.append(i)
+                sl.append(loc)
+    half = nsites // 2
+    assert sr.count(0) >= half and sr.count(1) >= nsites - half
+    sr, sl = np.array(sr[:half] + sr[half - nsites:], np.int32), np.array(sl[:half] + sl[half - nsites:], np.int32)
+    rows = [("chr%d\t%d\t+\t%d\tread%d\tt" % (r, loc, 5 * loc, r)).encode() for r, loc in zip(sr.tolist(), sl.tolist())]
+    return (ReadBatch(reads, sr, sl, norm=norm, seed=3),) + pack_info(rows)
