@@ -119,8 +119,12 @@ struct Plan {
     std::vector<LstmLaunch> lstm_launches;   // fp32 BiLSTM diagonals (lstm_cell_*kernel): passed by value at launch
     std::vector<Op> ops;                  // merged issue order
     int fc1_parts = 1;                    // partial products the split dense leaves in fc1o (launch_head adds them up)
-    hipGraphExec_t graph = nullptr;
-    int64_t uses = 0, last_use = 0;       // ragged tails produce many one-off sizes: graphs are captured for sizes that
+    // the captured forward (ensure_graphs): the event ops and the signal ops as one linear graph each, replayed on the slot's s1
+    // and s0 (replay_forward); a branch the model does not have leaves its graph null
+    hipGraphExec_t graph_ev = nullptr, graph_sig = nullptr;
+    bool captured = false;
+    bool ev_on_s1 = false;                // the split the graphs were captured with (graphs_split at that time)
+    int64_t uses = 0, last_use = 0;      // ragged tails produce many one-off sizes: graphs are captured for sizes that
                                           // recur, and the per-slot plan cache is bounded (get_plan)
 };
 
@@ -146,7 +150,8 @@ struct Block { char* p = nullptr; size_t cap = 0; };   // pinned host or device 
 }  // namespace
 
 // One pipeline slot: private workspace, stream pair, fork/join events and captured graphs, and the staging blocks of every route
-// through it. All work of a slot is enqueued on s0 (the forward forks to s1 and joins back), so a drained s0 is an idle slot.
+// through it. Every forward's work on s1 (the event model, and ds_forward_device's copy of its inputs) is joined back into s0 in
+// front of the joint model (fork_event_stream / join_event_stream), and everything else is enqueued on s0, so a drained s0 is an idle slot.
 struct Slot {
     hipStream_t s0 = nullptr, s1 = nullptr;
     bool owns_s1 = true;                 // false: DS_TUNE_SHARED_EVENT_STREAM -- s1 is slot 0's event-model stream
@@ -1362,12 +1367,47 @@ int issue_op(ds_handle* h, Plan& plan, const Op& op, hipStream_t s)
     return DS_OK;
 }
 
-// Enqueue the whole forward on (s0, s1): fork after the inputs are in place, join before fc1.
-// timed: bracket every launch with its own HIP event pair on the stream it is launched on.
-int enqueue_forward(ds_handle* h, Plan& plan, int timed)
+// The two cross-stream edges of a forward, plain stream calls in front of and behind whatever runs on s1 (never graph nodes).
+//
+// fork_event_stream: s1 waits for everything enqueued on s0 so far. That is (a) the event model's inputs where a route stages
+// them on s0 (the host copies, the text parser, the extraction kernels), and (b) the SLOT-REUSE edge: the slot's previous
+// forward is on s0 up to its last launch, and s0 had joined that forward's s1 work before its joint model. ds_forward_device
+// forks BEFORE it enqueues anything of the new forward on s0, so its event branch waits for (b) alone and depends on nothing of
+// this forward that sits in s0's hardware queue behind other slots' work. What (b) orders, buffer by buffer (writer of the new
+// forward on s1 <- reader / writer of the previous one):
+//   d_in [kmer | means | stds | sanums]  gather (s1, ds_forward_device)  <- the cells on s1 (same stream); recheck_select_kernel,
+//                                        inputs_to_host and the text ticket's k-mer D2H on s0 behind that forward: edge (b)
+//                                        (a model without an event branch: ds_forward_device leaves these four arrays out, so after
+//                                        it they hold an EARLIER forward's or no values; nothing of such a model reads them, and a
+//                                        read-back of the inputs -- inputs_to_host -- belongs to the routes that stage all five)
+//   d_in [signals]                       written and read on s0 only
+//   H, Cst, xproj                        written and read by the event ops only: s1 order (serial handles: s0 order)
+//   hlast                                the last cells (s1)  <- dense / dense_split / head_folded of the previous forward (s0): edge (b)
+//   joint (bf16 modes)                   pack_event_feat (s1) <- dense / head_folded of the previous forward (s0): edge (b); its
+//                                        signal columns are written by avgpool7 on s0, disjoint bytes
+//   sigfeat, fc1o, logits, act, pred,    s0 only (pred / act leave through scatter_outputs_kernel, the D2H copies and the
+//   jsplit, d_rc, pin_*, d_text, d_tres  recheck on s0)
+// join_event_stream: s0 waits for everything enqueued on s1 so far; the joint model, and with it every later launch and copy of
+// the slot, runs behind it.
+int fork_event_stream(ds_handle* h)
 {
     HIPCHK(h, hipEventRecord(h->cur->ev_fork, h->cur->s0));
     HIPCHK(h, hipStreamWaitEvent(h->cur->s1, h->cur->ev_fork, 0));
+    return DS_OK;
+}
+
+int join_event_stream(ds_handle* h)
+{
+    HIPCHK(h, hipEventRecord(h->cur->ev_join, h->cur->s1));
+    HIPCHK(h, hipStreamWaitEvent(h->cur->s0, h->cur->ev_join, 0));
+    return DS_OK;
+}
+
+// Enqueue the whole forward eagerly on (s0, s1): fork (unless the caller already has: `forked`), join before the joint model.
+// timed: bracket every launch with its own HIP event pair on the stream it is launched on.
+int enqueue_forward(ds_handle* h, Plan& plan, int timed, bool forked)
+{
+    if (!forked) { int rc = fork_event_stream(h); if (rc) return rc; }
     bool joined = false;
     const bool serial = h->serial || timed == 3;   // diagnostic: one stream, no overlap
     if (timed == 3) timed = 1;
@@ -1386,8 +1426,7 @@ int enqueue_forward(ds_handle* h, Plan& plan, int timed)
         if (op.after_join && !joined) {
             int rc = close_run(0); if (rc) return rc;
             rc = close_run(1); if (rc) return rc;
-            HIPCHK(h, hipEventRecord(h->cur->ev_join, h->cur->s1));
-            HIPCHK(h, hipStreamWaitEvent(h->cur->s0, h->cur->ev_join, 0));
+            rc = join_event_stream(h); if (rc) return rc;
             joined = true;
         }
         if (timed && !op.ev0) {
@@ -1415,10 +1454,7 @@ int enqueue_forward(ds_handle* h, Plan& plan, int timed)
         }
     }
     { int rc = close_run(0); if (rc) return rc; rc = close_run(1); if (rc) return rc; }
-    if (!joined) {
-        HIPCHK(h, hipEventRecord(h->cur->ev_join, h->cur->s1));
-        HIPCHK(h, hipStreamWaitEvent(h->cur->s0, h->cur->ev_join, 0));
-    }
+    if (!joined) return join_event_stream(h);
     return DS_OK;
 }
 
@@ -1439,16 +1475,24 @@ int collect_stage_times(ds_handle* h)
     return DS_OK;
 }
 
+void destroy_graphs(Plan& p)
+{
+    if (p.graph_ev) hipGraphExecDestroy(p.graph_ev);
+    if (p.graph_sig) hipGraphExecDestroy(p.graph_sig);
+    p.graph_ev = p.graph_sig = nullptr;
+    p.captured = false;
+}
+
 void destroy_plan(ds_handle* h, Plan& p)
 {
-    if (p.graph) hipGraphExecDestroy(p.graph);
+    destroy_graphs(p);
     for (Op& op : p.ops) { if (op.ev0) hipEventDestroy(op.ev0); if (op.ev1) hipEventDestroy(op.ev1); }
     if (p.d_launches) {
         hipFree(p.d_launches);
         auto it = std::find(h->allocs.begin(), h->allocs.end(), (void*)p.d_launches);
         if (it != h->allocs.end()) h->allocs.erase(it);
     }
-    p.graph = nullptr; p.d_launches = nullptr; p.ops.clear();
+    p.d_launches = nullptr; p.ops.clear();
 }
 
 constexpr size_t MAX_PLANS_PER_SLOT = 24;
@@ -1483,23 +1527,68 @@ int get_plan(ds_handle* h, int n, Plan** out)
     return DS_OK;
 }
 
-int ensure_graph(ds_handle* h, Plan& plan)
+// Which stream the event ops of a forward run on. Two questions with two answers:
+// graphs_split: do the CAPTURED graphs put them on s1? Fixed when the handle is created (the model has an event branch and the
+// handle is not DS_TUNE_SERIAL); it must not follow anything that can change afterwards, a graph is captured once and kept.
+// event_ops_on_s1: does THIS forward? The same, except that profiling mode 3 issues every launch eagerly on s0; a profiled
+// forward never replays a graph (run_resident), so the two agree wherever a graph is replayed.
+bool graphs_split(const ds_handle* h) { return h->is_rnn && !h->serial; }
+bool event_ops_on_s1(const ds_handle* h) { return graphs_split(h) && h->profiling != 3; }
+
+// One linear graph of the plan's ops in front of the join that go to stream `si` (the event ops to s1, the signal ops -- on a serial
+// handle: all of them -- to s0), captured on that stream; null where there is none. No cross-stream call is captured.
+int capture_branch(ds_handle* h, Plan& plan, int si, hipGraphExec_t* out)
 {
-    if (plan.graph) return DS_OK;
+    const bool split = plan.ev_on_s1;
+    auto mine = [&](const Op& op) { return !op.after_join && ((op.stream == 1 && split) ? 1 : 0) == si; };
+    if (std::none_of(plan.ops.begin(), plan.ops.end(), mine)) return DS_OK;
+    hipStream_t s = si == 0 ? h->cur->s0 : h->cur->s1;
     hipGraph_t g = nullptr;
-    HIPCHK(h, hipStreamBeginCapture(h->cur->s0, hipStreamCaptureModeThreadLocal));
-    int rc = enqueue_forward(h, plan, 0);
-    hipError_t e = hipStreamEndCapture(h->cur->s0, &g);
+    HIPCHK(h, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    int rc = DS_OK;
+    for (const Op& op : plan.ops)
+        if (mine(op) && (rc = issue_op(h, plan, op, s))) break;
+    hipError_t e = hipStreamEndCapture(s, &g);
     if (rc) { if (g) hipGraphDestroy(g); return rc; }
     if (e != hipSuccess) return fail(h, DS_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-    e = hipGraphInstantiate(&plan.graph, g, nullptr, nullptr, 0);
+    e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
     hipGraphDestroy(g);
     if (e != hipSuccess) return fail(h, DS_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
     return DS_OK;
 }
 
-// inputs must already be in the handle's device input buffers
-int run_resident(ds_handle* h, int n)
+int ensure_graphs(ds_handle* h, Plan& plan)
+{
+    if (plan.captured) return DS_OK;
+    plan.ev_on_s1 = graphs_split(h);
+    int rc = capture_branch(h, plan, 1, &plan.graph_ev);
+    if (!rc) rc = capture_branch(h, plan, 0, &plan.graph_sig);
+    if (rc) { destroy_graphs(plan); return rc; }
+    plan.captured = true;
+    return DS_OK;
+}
+
+// The captured forward: the event graph on s1 and the signal graph on s0, neither waiting for the other, then the join and the
+// joint model's one or two launches eagerly on s0. `forked`: as enqueue_forward.
+int replay_forward(ds_handle* h, Plan& plan, bool forked)
+{
+    // a caller that has put the event model's inputs on s1 needs the event ops there too, and the graphs say where they are
+    if (forked && !(plan.ev_on_s1 && plan.graph_ev))
+        return fail(h, DS_ERR_INVALID, "internal error: the forward was forked to the event stream, its captured graphs were not");
+    if (plan.graph_ev) {
+        if (!forked) { int rc = fork_event_stream(h); if (rc) return rc; }
+        HIPCHK(h, hipGraphLaunch(plan.graph_ev, h->cur->s1));
+    }
+    if (plan.graph_sig) HIPCHK(h, hipGraphLaunch(plan.graph_sig, h->cur->s0));
+    if (plan.graph_ev || forked) { int rc = join_event_stream(h); if (rc) return rc; }
+    for (const Op& op : plan.ops)
+        if (op.after_join) { int rc = issue_op(h, plan, op, h->cur->s0); if (rc) return rc; }
+    return DS_OK;
+}
+
+// The inputs must already be on their way into the slot's device input block: on s0, or, with `forked` (the caller has called
+// fork_event_stream for this forward), the event model's four arrays on s1 behind the fork.
+int run_resident(ds_handle* h, int n, bool forked = false)
 {
     Plan* plan = nullptr;
     int rc = get_plan(h, n, &plan);
@@ -1509,19 +1598,18 @@ int run_resident(ds_handle* h, int n)
     if (h->profiling) {
         rc = collect_stage_times(h);      // events of a previous profiled forward are reused below
         if (rc) return rc;
-        rc = enqueue_forward(h, *plan, h->profiling);
+        rc = enqueue_forward(h, *plan, h->profiling, forked);
         if (rc) return rc;
         for (Stage& S : h->stages) S.calls += 1;
         return DS_OK;
     }
     // a graph is worth its capture (~ms) only for sizes that come back: the full batch, or any size seen twice
-    if (h->use_graph && (plan->graph || n == h->B || plan->uses >= 2)) {
-        rc = ensure_graph(h, *plan);
+    if (h->use_graph && (plan->captured || n == h->B || plan->uses >= 2)) {
+        rc = ensure_graphs(h, *plan);
         if (rc) return rc;
-        HIPCHK(h, hipGraphLaunch(plan->graph, h->cur->s0));
-        return DS_OK;
+        return replay_forward(h, *plan, forked);
     }
-    return enqueue_forward(h, *plan, 0);
+    return enqueue_forward(h, *plan, 0, forked);
 }
 
 // Every slot's plan and captured graph for the full batch, built when the weights are finalized: the first max_batch-sized
@@ -1541,7 +1629,7 @@ void prepare_slots(ds_handle* h)
         h->cur = &sl;
         Plan* plan = nullptr;
         int rc = get_plan(h, h->B, &plan);
-        if (!rc) { plan->uses = 0; rc = ensure_graph(h, *plan); }
+        if (!rc) { plan->uses = 0; rc = ensure_graphs(h, *plan); }
         if (rc) {
             fprintf(stderr, "deepsignal_amd: preparing a slot's full-batch plan failed (%s); plans will be built at the first forward\n",
                     h->err.c_str());
@@ -1691,8 +1779,14 @@ static int ds_create_impl(const ds_config* cfg, ds_handle** out)
     CK(configure_fused_kernels());
     CK(configure_split_kernels());
     // reserved[1] = forwards in flight (pipeline slots); 0 -> default
-    // (the bf16 modes: a 512-site forward is ~0.2 ms, four in flight measured 2.60 M sites/s against 2.51 M with eight)
-    int nslots = cfg->reserved[1] > 0 ? cfg->reserved[1] : (h->B <= 1024 && !h->bf16 ? 8 : 4);
+    // (the bf16 modes: a 512-site forward is ~0.2 ms, four in flight measured 2.60 M sites/s against 2.51 M with eight. fp32 three-step,
+    // each branch of a forward on its own stream: four slots put two streams on each of the four hardware queues and measured 460.6 k
+    // against 454.9 k sites/s with eight at 512 sites, four runs a side. That is the ONLY configuration measured that way, so only it
+    // moves to four: the folded fp32 engine has one run a side, 584.7 k with four and 582.9 k with eight, and keeps eight (where
+    // it is 1.8 % BELOW the one-graph form it had, four runs a side: an open loss of the new order, profiles/README.md); so do the
+    // split-operand modes, bf16x3 649 k with four, 665 k with eight -- profiles/run_ahead_ab.json)
+    const bool eight = h->B <= 1024 && !h->bf16 && (h->split || h->fold_fc);
+    int nslots = cfg->reserved[1] > 0 ? cfg->reserved[1] : (eight ? 8 : 4);
     nslots = std::max(1, std::min(nslots, 16));
     h->slots.resize(nslots);
     int rc = DS_OK;
@@ -1731,7 +1825,7 @@ void ds_destroy(ds_handle* h)
     }
     for (Slot& sl : h->slots) {
         for (auto& kv : sl.plans) {
-            if (kv.second.graph) hipGraphExecDestroy(kv.second.graph);
+            destroy_graphs(kv.second);
             for (Op& op : kv.second.ops) { if (op.ev0) hipEventDestroy(op.ev0); if (op.ev1) hipEventDestroy(op.ev1); }
         }
         for (void* p : {(void*)sl.pin_in, (void*)sl.pin_act /* pin_pred points into it */, (void*)sl.pin_rowoff, (void*)sl.pin_rc,
@@ -1839,9 +1933,20 @@ static int ds_forward_device_impl(ds_handle* h, int32_t n, const int32_t* d_kmer
     HIPCHK(h, hipSetDevice(h->cfg.device));
     // next pipeline slot (profiling runs stay on slot 0 so the event statistics are coherent)
     h->cur = &h->slots[h->profiling ? 0 : (h->next_slot++ % h->slots.size())];
-    // one gather launch in, one scatter launch out (seven copy dispatches per forward before)
-    HIPCHK(h, launch_gather_inputs(d_kmer, d_means, d_stds, d_sanums, d_signals, h->cur->d_in, n, h->T, h->S, h->B, h->cur->s0));
-    int rc = run_resident(h, n);
+    // The caller's arrays into the slot's input block, each branch's part on the stream that branch runs on: the event model's four
+    // arrays on s1 behind a fork that has nothing of this forward in front of it (fork_event_stream), the signals on s0. A branch
+    // the model lacks has its part left out. One scatter launch out.
+    const bool forked = event_ops_on_s1(h);
+    const int ev_end = 4 * h->T, row_end = 4 * h->T + h->S;       // array boundaries, elements per site: [kmer | means | stds | sanums) [signals)
+    int rc = DS_OK;
+    if (forked) {
+        if ((rc = fork_event_stream(h))) return rc;
+        HIPCHK(h, launch_gather_inputs(d_kmer, d_means, d_stds, d_sanums, d_signals, h->cur->d_in, n, h->T, h->S, h->B, 0, ev_end, h->cur->s1));
+    }
+    const int s0_from = (forked || !h->is_rnn) ? ev_end : 0, s0_to = h->is_cnn ? row_end : ev_end;
+    if (s0_from < s0_to)
+        HIPCHK(h, launch_gather_inputs(d_kmer, d_means, d_stds, d_sanums, d_signals, h->cur->d_in, n, h->T, h->S, h->B, s0_from, s0_to, h->cur->s0));
+    rc = run_resident(h, n, forked);
     if (rc) return rc;
     HIPCHK(h, launch_scatter_outputs(h->cur->act, h->cur->pred, d_act, d_pred, n, h->C, h->cur->s0));
     return DS_OK;

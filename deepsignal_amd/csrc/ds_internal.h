@@ -308,9 +308,10 @@ struct HeadFoldedArgs {
 };
 hipError_t launch_head_folded(const HeadFoldedArgs& a, hipStream_t s);
 // the caller's device arrays -> the slot's contiguous input block [kmer | means | stds | lens | signals] (regions sized for
-// max_batch B), and the slot's act / pred -> the caller's buffers
+// max_batch B), and the slot's act / pred -> the caller's buffers. The gather copies whole arrays: those between the
+// per-site offsets col_lo and col_hi (each one of 0, T, 2 T, 3 T, 4 T, 4 T + S): [0, 4 T) the event model's four, [4 T, 4 T + S) the signals
 hipError_t launch_gather_inputs(const int* kmer, const float* means, const float* stds, const float* lens, const float* signals,
-                                float* block, int n, int T, int S, int B, hipStream_t s);
+                                float* block, int n, int T, int S, int B, int col_lo, int col_hi, hipStream_t s);
 hipError_t launch_scatter_outputs(const float* act, const int* pred, float* act_out, int* pred_out, int n, int C, hipStream_t s);
 // Cascaded precision (ds_recheck.hip, ds_set_recheck): the sites of a finished forward whose act falls within `margin` of the
 // threshold, in ascending site order: count[0] = how many, index[k] = the k-th one, and its five input rows copied to row k of

@@ -2819,16 +2819,17 @@ hipError_t launch_head_folded(const HeadFoldedArgs& a, hipStream_t s)
 }
 
 // ds_forward_device: the caller's five device arrays into the slot's contiguous input block and the slot's outputs
-// back to the caller -- ONE small launch each way instead of five + two copy dispatches per forward (the captured graph
-// reads and writes the slot's own buffers).
+// back to the caller -- small launches instead of five + two copy dispatches per forward (the captured graphs read and write the
+// slot's own buffers). The gather copies the elements [lo, hi) of the five arrays laid end to end ([kmer | means | stds | lens] =
+// 4 n T elements, the event model's inputs, then n S signals), so that each branch's inputs can be copied on that branch's stream.
 __global__ __launch_bounds__(256) void gather_inputs_kernel(const int* __restrict__ kmer, const float* __restrict__ means,
                                                             const float* __restrict__ stds, const float* __restrict__ lens,
                                                             const float* __restrict__ signals, float* __restrict__ block,
-                                                            int n, int T, int S, int B)
+                                                            int n, int T, int S, int B, long lo, long hi)
 {
-    const long nt = (long)n * T, ns = (long)n * S, total = 4 * nt + ns;
+    const long nt = (long)n * T;
     const long bt = (long)B * T;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    for (long i = lo + (long)blockIdx.x * 256 + threadIdx.x; i < hi; i += (long)gridDim.x * 256) {
         if (i < nt) reinterpret_cast<int*>(block)[i] = kmer[i];
         else if (i < 2 * nt) block[bt + (i - nt)] = means[i - nt];
         else if (i < 3 * nt) block[2 * bt + (i - 2 * nt)] = stds[i - 2 * nt];
@@ -2848,12 +2849,13 @@ __global__ __launch_bounds__(256) void scatter_outputs_kernel(const float* __res
 }
 
 hipError_t launch_gather_inputs(const int* kmer, const float* means, const float* stds, const float* lens, const float* signals,
-                                float* block, int n, int T, int S, int B, hipStream_t s)
+                                float* block, int n, int T, int S, int B, int col_lo, int col_hi, hipStream_t s)
 {
-    if (n <= 0) return hipSuccess;
-    const long total = (long)n * (4 * T + S);
-    const int grid = (int)std::min<long>((total + 1023) / 1024, 1024);
-    hipLaunchKernelGGL(gather_inputs_kernel, dim3(grid), dim3(256), 0, s, kmer, means, stds, lens, signals, block, n, T, S, B);
+    // [col_lo, col_hi): array boundaries as per-site offsets (0, T, 2 T, 3 T, 4 T, 4 T + S); 4 T lies between the two branches' inputs
+    if (n <= 0 || col_lo < 0 || col_hi > 4 * T + S || col_lo >= col_hi) return hipSuccess;
+    const long lo = (long)n * col_lo, hi = (long)n * col_hi;
+    const int grid = (int)std::min<long>((hi - lo + 1023) / 1024, 1024);
+    hipLaunchKernelGGL(gather_inputs_kernel, dim3(grid), dim3(256), 0, s, kmer, means, stds, lens, signals, block, n, T, S, B, lo, hi);
     return hipGetLastError();
 }
 

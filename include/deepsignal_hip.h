@@ -78,7 +78,8 @@ typedef struct ds_config {
     int32_t reserved[7];  /* reserved[0] != 0: debug mode — keep every module output for ds_get_intermediate;
                              reserved[1]: forwards in flight for ds_forward_device / ds_submit (pipeline slots, each
                              with its own workspace, stream pair and captured graphs; default 8 for
-                             max_batch <= 1024, else 4; max 16);
+                             max_batch <= 1024, except 4 for the bf16 modes and for fp32 with the three-step joint
+                             model (DS_TUNE_NO_FOLD_FC, debug mode); else 4; max 16; ds_num_slots tells);
                              reserved[2]: DS_TUNE_* flag bits (diagnostics, below);
                              reserved[3]: DS_LSTM_TILING_* override of the planner's BiLSTM tile choice;
                              reserved[4]: fused inception module, most sites per tile (0 = default 8);
@@ -177,8 +178,8 @@ int ds_forward(ds_handle *h, int32_t n, const int32_t *kmer, const float *means,
 
 /* Same contract with every pointer in DEVICE memory of h's GPU (n <= max_batch). Asynchronous and
  * PIPELINED: consecutive calls rotate over independent slots (own workspace, HIP streams and captured
- * graph), so several forwards are in flight at once; inputs are staged and outputs written on the slot's
- * stream, so keep both buffers untouched until ds_sync() returns. Used when features are already
+ * graphs), so several forwards are in flight at once; inputs are staged and outputs written on the slot's
+ * streams, so keep both buffers untouched until ds_sync() returns. Used when features are already
  * resident in HBM. */
 int ds_forward_device(ds_handle *h, int32_t n, const int32_t *d_kmer, const float *d_means,
                       const float *d_stds, const float *d_sanums, const float *d_signals,
@@ -188,7 +189,7 @@ int ds_sync(ds_handle *h);
 /* Asynchronous form of ds_forward for host buffers (n <= max_batch): ds_submit stages the batch in pinned memory of
  * the next pipeline slot and enqueues H2D + forward + D2H there; ds_wait blocks on that one forward and copies its
  * act[n, class_num] / pred[n] out. Tickets must be waited in submission order at the latest when all slots
- * (ds_config.reserved[1], default 8) are in flight. Replaces the blocking tf_sess.run (call_modifications.py:177-178)
+ * (ds_config.reserved[1]; ds_num_slots) are in flight. Replaces the blocking tf_sess.run (call_modifications.py:177-178)
  * where the caller has other work to overlap (parsing the next queue item, formatting the previous rows). */
 int ds_submit(ds_handle *h, int32_t n, const int32_t *kmer, const float *means, const float *stds,
               const float *sanums, const float *signals, int32_t *ticket);
