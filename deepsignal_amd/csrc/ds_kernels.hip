@@ -2548,17 +2548,42 @@ hipError_t launch_inception_fused_bf16(int tm, const FusedChain& c, hipStream_t 
 // One block per site; the window sits in LDS with a zero halo (SAME padding, no bounds checks in the
 // tap loop); lane = output channel, so the 64-float output rows are written as whole 256-B lines.
 constexpr int STEM_HALO = 8;
+// DS_SMALL_PRIO / DS_SMALL_PRIO_POST: issue priority (s_setprio) of the step's short non-matrix kernels, from entry to the end of
+// the kernel. Like the BiLSTM cells (DS_CELL_PRIO) they are guests beside fused-module and dense waves that live hundreds of
+// microseconds, are older, and win every oldest-first arbitration among equals, and each of them sits on a forward's critical chain.
+// DS_SMALL_PRIO: the kernels inside the branches (stem1_kernel<false>, avgpool7_kernel, gather_inputs_kernel);
+// DS_SMALL_PRIO_POST: the kernels behind the join (head_kernel, head_folded_kernel, scatter_outputs_kernel).
+// Measured on the pipelined 512-site step against the parent, libraries alternating, four runs a side, k sites/s
+// (profiles/small_kernels_ab.json; parent 459.9, its spread 0.14 %). On the parent's bodies: both at 1: 462.9 (+0.65 %), both at
+// 2: 462.9, branches only: 462.2 (+0.50 %), behind the join only: 459.0 (-0.20 %). On the lean bodies below (no priority: 462.3,
+// +0.51 %): both at 1 / both at 2: 465.2 / 465.1, branches only at 1 / at 2: 464.9 / 465.9. So the branch kernels ask, at the
+// cells' level (2 is not above 1 by the project's bar), and the kernels behind the join do not: nothing is gained there, and
+// alone it loses. Results are bit-identical (tests/test_gpu_small_kernel_bits.py).
+#ifndef DS_SMALL_PRIO
+#define DS_SMALL_PRIO 1
+#endif
+#ifndef DS_SMALL_PRIO_POST
+#define DS_SMALL_PRIO_POST 0
+#endif
+// base + a 32-bit BYTE offset: with a wave-uniform base this is a scalar base and a 32-bit lane offset in the instruction (an element
+// index would be widened to 64 bits before it is scaled, and the lane would carry the whole address)
+template <typename T> __device__ __forceinline__ T* at_bytes(T* base, unsigned bytes)
+{
+    return (T*)((const char*)base + bytes);
+}
+constexpr int STEM1_WAVES = 4;
 template <bool OUT_BF>
 __global__ __launch_bounds__(256) void stem1_kernel(const float* __restrict__ signals, const float* __restrict__ w,
                                                      const float* __restrict__ bias, float* __restrict__ out,
                                                      int signal_len, int w1, int pad_l_conv, int wa, int pad_l_pool)
 {
     extern __shared__ __attribute__((aligned(16))) float sig[];   // [STEM_HALO + signal_len + STEM_HALO + 8]
-    const int site = blockIdx.x;
+    if constexpr (!OUT_BF && DS_SMALL_PRIO != 0) __builtin_amdgcn_s_setprio(DS_SMALL_PRIO);
     const int total = signal_len + 2 * STEM_HALO + 8;
+    const float* src = signals + (size_t)blockIdx.x * signal_len;          // scalar base, 32-bit lane offsets
     for (int i = threadIdx.x; i < total; i += blockDim.x) {
         const int k = i - STEM_HALO;
-        sig[i] = (k >= 0 && k < signal_len) ? signals[(size_t)site * signal_len + k] : 0.0f;
+        sig[i] = (k >= 0 && k < signal_len) ? *at_bytes(src, 4u * (unsigned)k) : 0.0f;
     }
     __syncthreads();
     const int c = threadIdx.x & 63;
@@ -2566,28 +2591,50 @@ __global__ __launch_bounds__(256) void stem1_kernel(const float* __restrict__ si
 #pragma unroll
     for (int t = 0; t < 7; ++t) wk[t] = w[t * 64 + c];
     const float b = bias[c];
-    for (int p = threadIdx.x >> 6; p < wa; p += blockDim.x >> 6) {
-        // conv positions wc = 2p - pad_l_pool + {0,1,2}; each reads sig[2*wc - pad_l_conv + 0..6]
-        const int wc0 = 2 * p - pad_l_pool;
-        const float* s0 = sig + STEM_HALO + 2 * wc0 - pad_l_conv;
+    // A wave walks consecutive pooled positions. Pooled position p takes the conv positions wc = 2p - pad_l_pool + {0,1,2}, each
+    // reading sig[2*wc - pad_l_conv + 0..6]: the third of p is the first of p + 1, so it stays in a register (`carry`) with the
+    // seven window samples behind it, and a step computes two conv positions from four new samples where it was three from eleven.
+    // Every conv position is still the fma chain t = 0..6 from 0.f, and the maximum takes them in the same order.
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int chunk = (wa + STEM1_WAVES - 1) / STEM1_WAVES;
+    const int p_lo = wave * chunk, p_hi = p_lo + chunk < wa ? p_lo + chunk : wa;
+    if (p_lo < p_hi) {
+        const float* s0 = sig + STEM_HALO + 2 * (2 * p_lo - pad_l_pool) - pad_l_conv;
+        float* orow = out + (size_t)blockIdx.x * wa * (OUT_BF ? 32 : 64);     // a bf16 row is 128 bytes
         float v[11];
 #pragma unroll
-        for (int i = 0; i < 11; ++i) v[i] = s0[i];
-        float best = -INFINITY;
+        for (int i = 0; i < 7; ++i) v[i] = s0[i];
+        float carry = 0.0f;
 #pragma unroll
-        for (int pt = 0; pt < 3; ++pt) {
-            float a = 0.0f;
+        for (int t = 0; t < 7; ++t) carry = fmaf(v[t], wk[t], carry);
+        for (int p = p_lo; p < p_hi; ++p, s0 += 4) {
 #pragma unroll
-            for (int t = 0; t < 7; ++t) a = fmaf(v[2 * pt + t], wk[t], a);
-            const int wc = wc0 + pt;
-            // padded pool taps are ignored; a NaN tap wins and stays (fmaxf would drop it: a window that is NaN throughout
-            // came out as relu(-inf + b) = 0). These are pre-ReLU values of either sign: no relu_max here, the IEEE maximum.
-            best = (wc >= 0 && wc < w1) ? __builtin_elementwise_maximum(best, a) : best;
+            for (int i = 7; i < 11; ++i) v[i] = s0[i];
+            const int wc0 = 2 * p - pad_l_pool;
+            float best = -INFINITY;
+#pragma unroll
+            for (int pt = 0; pt < 3; ++pt) {
+                float a = carry;
+                if (pt > 0) {
+                    a = 0.0f;
+#pragma unroll
+                    for (int t = 0; t < 7; ++t) a = fmaf(v[2 * pt + t], wk[t], a);
+                }
+                const int wc = wc0 + pt;
+                // padded pool taps are ignored; a NaN tap wins and stays (fmaxf would drop it: a window that is NaN throughout
+                // came out as relu(-inf + b) = 0). These are pre-ReLU values of either sign: no relu_max here, the IEEE maximum.
+                best = (wc >= 0 && wc < w1) ? __builtin_elementwise_maximum(best, a) : best;
+                if (pt == 2) carry = a;
+            }
+            const float y = relu_f(best + b);
+            const unsigned o = (unsigned)p * 64u + (unsigned)c;
+            if (OUT_BF) *at_bytes(reinterpret_cast<unsigned short*>(orow), 2u * o) = f2bf(y);
+            else *at_bytes(orow, 4u * o) = y;
+#pragma unroll
+            for (int i = 0; i < 7; ++i) v[i] = v[i + 4];
         }
-        const float y = relu_f(best + b);
-        if (OUT_BF) reinterpret_cast<unsigned short*>(out)[((size_t)site * wa + p) * 64 + c] = f2bf(y);
-        else out[((size_t)site * wa + p) * 64 + c] = y;
     }
+    if constexpr (!OUT_BF && DS_SMALL_PRIO != 0) __builtin_amdgcn_s_setprio(0);
 }
 
 hipError_t launch_stem1(const float* signals, const float* w7x64, const float* bias64, float* out, int n,
@@ -2597,10 +2644,10 @@ hipError_t launch_stem1(const float* signals, const float* w7x64, const float* b
     const size_t lds = (signal_len + 2 * STEM_HALO + 8) * sizeof(float);
     if (lds > 64 * 1024) return hipErrorInvalidValue;      // no opt-in to more: ds_create refuses signal_len > DS_MAX_SIGNAL_LEN
     if (out_bf16)
-        hipLaunchKernelGGL(stem1_kernel<true>, dim3(n), dim3(256), lds, s, signals, w7x64, bias64, out,
+        hipLaunchKernelGGL(stem1_kernel<true>, dim3(n), dim3(64 * STEM1_WAVES), lds, s, signals, w7x64, bias64, out,
                            signal_len, w1, pad_l_conv, wa, pad_l_pool);
     else
-        hipLaunchKernelGGL(stem1_kernel<false>, dim3(n), dim3(256), lds, s, signals, w7x64, bias64, out,
+        hipLaunchKernelGGL(stem1_kernel<false>, dim3(n), dim3(64 * STEM1_WAVES), lds, s, signals, w7x64, bias64, out,
                            signal_len, w1, pad_l_conv, wa, pad_l_pool);
     return hipGetLastError();
 }
@@ -2633,34 +2680,36 @@ hipError_t launch_maxpool_s2(const float* in, float* out, int n, int win, int wo
     return hipGetLastError();
 }
 
-__global__ __launch_bounds__(256) void avgpool7_kernel(const float4* __restrict__ in, float4* __restrict__ out, long total,
-                                                        int w, int ch4)
+// 7-wide average over the width axis, clipped at both ends (count = taps in bounds). One workgroup per site: a wave takes whole
+// output rows, so the clipping is scalar, and a lane takes float4 columns: the site in a scalar base, (row, column) in a 32-bit
+// lane offset, no division but the average's own. The sum is from 0.f over the taps in ascending order, then the IEEE division.
+__global__ __launch_bounds__(256) void avgpool7_kernel(const float4* __restrict__ in, float4* __restrict__ out, int w, int ch4)
 {
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int c = (int)(i % ch4);
-        const long r = i / ch4;
-        const int wo = (int)(r % w);
-        const long site = r / w;
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-        int cnt = 0;
-        for (int t = -3; t <= 3; ++t) {
-            const int wi = wo + t;
-            if (wi < 0 || wi >= w) continue;
-            const float4 v = in[(site * w + wi) * ch4 + c];
-            a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-            ++cnt;
+    if constexpr (DS_SMALL_PRIO != 0) __builtin_amdgcn_s_setprio(DS_SMALL_PRIO);
+    const size_t base = (size_t)blockIdx.x * (size_t)w * (size_t)ch4;
+    const float4* src = in + base;
+    float4* dst = out + base;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int wo = wave; wo < w; wo += 4) {
+        const int lo = wo - 3 > 0 ? wo - 3 : 0, hi = wo + 3 < w - 1 ? wo + 3 : w - 1;
+        const float d = (float)(hi - lo + 1);
+        for (int c = lane; c < ch4; c += 64) {
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int wi = lo; wi <= hi; ++wi) {
+                const float4 v = *at_bytes(src, 16u * (unsigned)(wi * ch4 + c));
+                a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+            }
+            *at_bytes(dst, 16u * (unsigned)(wo * ch4 + c)) = make_float4(a.x / d, a.y / d, a.z / d, a.w / d);
         }
-        const float d = (float)cnt;
-        out[i] = make_float4(a.x / d, a.y / d, a.z / d, a.w / d);
     }
+    if constexpr (DS_SMALL_PRIO != 0) __builtin_amdgcn_s_setprio(0);
 }
 
 hipError_t launch_avgpool7(const float* in, float* out, int n, int w, int ch, hipStream_t s)
 {
-    const long total = (long)n * w * (ch / 4);
-    if (total <= 0) return hipSuccess;
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(avgpool7_kernel, dim3(blocks), dim3(256), 0, s, (const float4*)in, (float4*)out, total, w, ch / 4);
+    if (n <= 0 || w <= 0 || ch < 4) return hipSuccess;
+    if ((long)w * (ch / 4) >= (1L << 27)) return hipErrorInvalidValue;      // a site's bytes in a 32-bit lane offset
+    hipLaunchKernelGGL(avgpool7_kernel, dim3(n), dim3(256), 0, s, (const float4*)in, (float4*)out, w, ch / 4);
     return hipGetLastError();
 }
 
@@ -2670,20 +2719,25 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ fc1
                                                     int* __restrict__ pred, int n, int J, int C, int nparts, size_t part_stride)
 {
     __shared__ float part[4][16];
+    if constexpr (DS_SMALL_PRIO_POST != 0) __builtin_amdgcn_s_setprio(DS_SMALL_PRIO_POST);
     const int site = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float4* x4 = reinterpret_cast<const float4*>(fc1 + (size_t)site * J);
+    // the site's row (and the same row of every partial product) in a scalar base, the lane's float4 in a 32-bit byte offset
+    const char* xrow = reinterpret_cast<const char*>(fc1 + (size_t)site * J);
+    const char* wrow = reinterpret_cast<const char*>(w2);
+    const size_t part_bytes = part_stride * sizeof(float);
     float accv[16];
 #pragma unroll
     for (int c = 0; c < 16; ++c) accv[c] = 0.0f;
     const int J4 = J >> 2;
     for (int k4 = tid; k4 < J4; k4 += 256) {
-        float4 x = x4[k4];
+        const unsigned xo = (unsigned)k4 * 16u;
+        float4 x = *reinterpret_cast<const float4*>(at_bytes(xrow, xo));
         for (int p = 1; p < nparts; ++p) {            // fc1 in partial products over ranges of K (the split dense at small forwards): summed in order
-            const float4 y = *reinterpret_cast<const float4*>(fc1 + p * part_stride + (size_t)site * J + 4 * (size_t)k4);
+            const float4 y = *reinterpret_cast<const float4*>(at_bytes(xrow + p * part_bytes, xo));
             x.x += y.x; x.y += y.y; x.z += y.z; x.w += y.w;
         }
-        const float* w = w2 + (size_t)k4 * 4 * C;
+        const float* w = reinterpret_cast<const float*>(wrow + xo * (unsigned)C);
         if (C == 2) {
             const float4 wa = *reinterpret_cast<const float4*>(w);
             const float4 wb = *reinterpret_cast<const float4*>(w + 4);
@@ -2696,9 +2750,10 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ fc1
         }
     }
     for (int k = (J4 << 2) + tid; k < J; k += 256) {    // J not a multiple of 4
-        float xk = fc1[(size_t)site * J + k];
-        for (int p = 1; p < nparts; ++p) xk += fc1[p * part_stride + (size_t)site * J + k];
-        for (int c = 0; c < C; ++c) accv[c] += xk * w2[(size_t)k * C + c];
+        const unsigned ko = (unsigned)k * 4u;
+        float xk = *reinterpret_cast<const float*>(xrow + ko);
+        for (int p = 1; p < nparts; ++p) xk += *reinterpret_cast<const float*>(xrow + p * part_bytes + ko);
+        for (int c = 0; c < C; ++c) accv[c] += xk * *reinterpret_cast<const float*>(wrow + (ko * (unsigned)C + 4u * (unsigned)c));
     }
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
@@ -2715,12 +2770,13 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ fc1
         for (int c = 0; c < C; ++c) {
             const float a = (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]);
             const float sg = sigmoidf_(a);
-            logits[(size_t)site * C + c] = a;
+            logits[(size_t)site * C + c] = a;      // one lane, wave-uniform: scalar address arithmetic
             act[(size_t)site * C + c] = sg;
             if (c == 0 || sg > best) { best = sg; bi = c; }
         }
         pred[site] = bi;
     }
+    if constexpr (DS_SMALL_PRIO_POST != 0) __builtin_amdgcn_s_setprio(0);
 }
 
 hipError_t launch_head(const float* fc1, const float* w2, float* logits, float* act, int* pred, int n, int J,
@@ -2735,6 +2791,7 @@ hipError_t launch_head(const float* fc1, const float* w2, float* logits, float* 
 __global__ __launch_bounds__(256) void head_folded_kernel(const HeadFoldedArgs a)
 {
     __shared__ float part[4][16];
+    if constexpr (DS_SMALL_PRIO_POST != 0) __builtin_amdgcn_s_setprio(DS_SMALL_PRIO_POST);
     const int site = blockIdx.x, C = a.C;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float accv[16];
@@ -2743,11 +2800,12 @@ __global__ __launch_bounds__(256) void head_folded_kernel(const HeadFoldedArgs a
     int koff = 0;
     if (a.bf16) {                                         // bf16 modes: bf16 rows, 8 values per 16 bytes
         for (int sg = 0; sg < a.nseg; ++sg) {             // uniform
-        const float4* x8 = reinterpret_cast<const float4*>(reinterpret_cast<const unsigned short*>(a.seg[sg]) + (size_t)site * a.pitch[sg]);
+        const char* x8 = reinterpret_cast<const char*>(reinterpret_cast<const unsigned short*>(a.seg[sg]) + (size_t)site * a.pitch[sg]);
+        const char* wseg = reinterpret_cast<const char*>(a.w + (size_t)koff * C);      // scalar bases, 32-bit lane byte offsets
         for (int k8 = tid; k8 < (a.len[sg] >> 3); k8 += 256) {
-            const float4 raw = x8[k8];
+            const float4 raw = *reinterpret_cast<const float4*>(x8 + (unsigned)k8 * 16u);
             const unsigned u[4] = {__float_as_uint(raw.x), __float_as_uint(raw.y), __float_as_uint(raw.z), __float_as_uint(raw.w)};
-            const float* w = a.w + (size_t)(koff + k8 * 8) * C;
+            const float* w = reinterpret_cast<const float*>(wseg + (unsigned)k8 * 32u * (unsigned)C);
             if (C == 2) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -2771,10 +2829,12 @@ __global__ __launch_bounds__(256) void head_folded_kernel(const HeadFoldedArgs a
     } else
     for (int sg = 0; sg < a.nseg; ++sg) {                 // uniform
         const int len = a.len[sg];
-        const float4* x4 = reinterpret_cast<const float4*>(a.seg[sg] + (size_t)site * len);
+        const char* x4 = reinterpret_cast<const char*>(a.seg[sg] + (size_t)site * len);
+        const char* wseg = reinterpret_cast<const char*>(a.w + (size_t)koff * C);
         for (int k4 = tid; k4 < (len >> 2); k4 += 256) {
-            const float4 x = x4[k4];
-            const float* w = a.w + (size_t)(koff + k4 * 4) * C;
+            const unsigned xo = (unsigned)k4 * 16u;
+            const float4 x = *reinterpret_cast<const float4*>(x4 + xo);
+            const float* w = reinterpret_cast<const float*>(wseg + xo * (unsigned)C);
             if (C == 2) {
                 const float4 wa = *reinterpret_cast<const float4*>(w);
                 const float4 wb = *reinterpret_cast<const float4*>(w + 4);
@@ -2809,6 +2869,7 @@ __global__ __launch_bounds__(256) void head_folded_kernel(const HeadFoldedArgs a
         }
         a.pred[site] = bi;
     }
+    if constexpr (DS_SMALL_PRIO_POST != 0) __builtin_amdgcn_s_setprio(0);
 }
 
 hipError_t launch_head_folded(const HeadFoldedArgs& a, hipStream_t s)
@@ -2822,30 +2883,55 @@ hipError_t launch_head_folded(const HeadFoldedArgs& a, hipStream_t s)
 // back to the caller -- small launches instead of five + two copy dispatches per forward (the captured graphs read and write the
 // slot's own buffers). The gather copies the elements [lo, hi) of the five arrays laid end to end ([kmer | means | stds | lens] =
 // 4 n T elements, the event model's inputs, then n S signals), so that each branch's inputs can be copied on that branch's stream.
-__global__ __launch_bounds__(256) void gather_inputs_kernel(const int* __restrict__ kmer, const float* __restrict__ means,
-                                                            const float* __restrict__ stds, const float* __restrict__ lens,
-                                                            const float* __restrict__ signals, float* __restrict__ block,
-                                                            int n, int T, int S, int B, long lo, long hi)
+// Both copy whole ranges of 32-bit words. copy_words is one such range over the x dimension of the grid: source and destination
+// are wave-uniform, so each pass is a scalar base plus the lane's constant offset, 16 bytes per lane where both ends are 16-byte
+// aligned (the caller's arrays need not be) and 4 bytes otherwise; the words past the last whole 16 bytes go one per lane.
+__device__ __forceinline__ void copy_words(const unsigned* __restrict__ src, unsigned* __restrict__ dst, long cnt)
 {
-    const long nt = (long)n * T;
-    const long bt = (long)B * T;
-    for (long i = lo + (long)blockIdx.x * 256 + threadIdx.x; i < hi; i += (long)gridDim.x * 256) {
-        if (i < nt) reinterpret_cast<int*>(block)[i] = kmer[i];
-        else if (i < 2 * nt) block[bt + (i - nt)] = means[i - nt];
-        else if (i < 3 * nt) block[2 * bt + (i - 2 * nt)] = stds[i - 2 * nt];
-        else if (i < 4 * nt) block[3 * bt + (i - 3 * nt)] = lens[i - 3 * nt];
-        else block[4 * bt + (i - 4 * nt)] = signals[i - 4 * nt];
+    const unsigned tid = threadIdx.x;
+    const long step = (long)gridDim.x * 256;
+    if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
+        const long cnt4 = cnt >> 2;
+        for (long i0 = (long)blockIdx.x * 256; i0 < cnt4; i0 += step) {
+            const unsigned left = (unsigned)(cnt4 - i0 < 256 ? cnt4 - i0 : 256);
+            if (tid < left) (reinterpret_cast<uint4*>(dst) + i0)[tid] = (reinterpret_cast<const uint4*>(src) + i0)[tid];
+        }
+        if (blockIdx.x == 0 && tid < (unsigned)(cnt & 3)) (dst + 4 * cnt4)[tid] = (src + 4 * cnt4)[tid];
+    } else {
+        for (long i0 = (long)blockIdx.x * 256; i0 < cnt; i0 += step) {
+            const unsigned left = (unsigned)(cnt - i0 < 256 ? cnt - i0 : 256);
+            if (tid < left) (dst + i0)[tid] = (src + i0)[tid];
+        }
     }
 }
 
+// blockIdx.y + seg0 names the array: 0 .. 3 = kmer, means, stds, lens (n T words each, B T apart in the block), 4 = signals (n S)
+__global__ __launch_bounds__(256) void gather_inputs_kernel(const int* __restrict__ kmer, const float* __restrict__ means,
+                                                            const float* __restrict__ stds, const float* __restrict__ lens,
+                                                            const float* __restrict__ signals, float* __restrict__ block,
+                                                            int n, int T, int S, int B, long lo, long hi, int seg0)
+{
+    if constexpr (DS_SMALL_PRIO != 0) __builtin_amdgcn_s_setprio(DS_SMALL_PRIO);
+    const long nt = (long)n * T;
+    const long bt = (long)B * T;
+    const int seg = seg0 + (int)blockIdx.y;
+    const void* arr = seg == 0 ? (const void*)kmer : seg == 1 ? (const void*)means : seg == 2 ? (const void*)stds
+                    : seg == 3 ? (const void*)lens : (const void*)signals;
+    const long first = seg * nt, last = seg < 4 ? first + nt : first + (long)n * S;      // the array's place in [0, 4 n T + n S)
+    const long from = lo > first ? lo : first, to = hi < last ? hi : last;
+    if (from < to)
+        copy_words(static_cast<const unsigned*>(arr) + (from - first), reinterpret_cast<unsigned*>(block) + seg * bt + (from - first), to - from);
+    if constexpr (DS_SMALL_PRIO != 0) __builtin_amdgcn_s_setprio(0);
+}
+
+// blockIdx.y: 0 = act (n C words), 1 = pred (n)
 __global__ __launch_bounds__(256) void scatter_outputs_kernel(const float* __restrict__ act, const int* __restrict__ pred,
                                                               float* __restrict__ act_out, int* __restrict__ pred_out, int n, int C)
 {
-    const int total = n * C + n;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-        if (i < n * C) act_out[i] = act[i];
-        else pred_out[i - n * C] = pred[i - n * C];
-    }
+    if constexpr (DS_SMALL_PRIO_POST != 0) __builtin_amdgcn_s_setprio(DS_SMALL_PRIO_POST);
+    if (blockIdx.y == 0) copy_words(reinterpret_cast<const unsigned*>(act), reinterpret_cast<unsigned*>(act_out), (long)n * C);
+    else copy_words(reinterpret_cast<const unsigned*>(pred), reinterpret_cast<unsigned*>(pred_out), n);
+    if constexpr (DS_SMALL_PRIO_POST != 0) __builtin_amdgcn_s_setprio(0);
 }
 
 hipError_t launch_gather_inputs(const int* kmer, const float* means, const float* stds, const float* lens, const float* signals,
@@ -2854,15 +2940,19 @@ hipError_t launch_gather_inputs(const int* kmer, const float* means, const float
     // [col_lo, col_hi): array boundaries as per-site offsets (0, T, 2 T, 3 T, 4 T, 4 T + S); 4 T lies between the two branches' inputs
     if (n <= 0 || col_lo < 0 || col_hi > 4 * T + S || col_lo >= col_hi) return hipSuccess;
     const long lo = (long)n * col_lo, hi = (long)n * col_hi;
-    const int grid = (int)std::min<long>((hi - lo + 1023) / 1024, 1024);
-    hipLaunchKernelGGL(gather_inputs_kernel, dim3(grid), dim3(256), 0, s, kmer, means, stds, lens, signals, block, n, T, S, B, lo, hi);
+    const int seg0 = std::min(col_lo / T, 4), seg1 = std::min((col_hi - 1) / T, 4);      // first and last array the range touches
+    const long widest = (long)n * (seg1 == 4 ? std::max(S, seg0 < 4 ? T : 0) : T);
+    const int grid = (int)std::min<long>((widest + 1023) / 1024, 1024);
+    hipLaunchKernelGGL(gather_inputs_kernel, dim3(grid, seg1 - seg0 + 1), dim3(256), 0, s, kmer, means, stds, lens, signals, block, n, T, S,
+                       B, lo, hi, seg0);
     return hipGetLastError();
 }
 
 hipError_t launch_scatter_outputs(const float* act, const int* pred, float* act_out, int* pred_out, int n, int C, hipStream_t s)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(scatter_outputs_kernel, dim3((n * (C + 1) + 255) / 256), dim3(256), 0, s, act, pred, act_out, pred_out, n, C);
+    hipLaunchKernelGGL(scatter_outputs_kernel, dim3((int)std::min<long>(((long)n * C + 1023) / 1024, 1024), 2), dim3(256), 0, s, act, pred,
+                       act_out, pred_out, n, C);
     return hipGetLastError();
 }
 
