@@ -223,6 +223,54 @@ def test_split_operand_statement_is_exact_in_its_terms_and_fp32_class():
     assert (p3[decided] == p64[decided]).all()
 
 
+# The ends of --kmer_len and --class_num. At kmer_len 1 no cell has a recurrent operand and the last step of both directions
+# is t = 0; at 3 (= the number of LSTM layers) the wavefront of the engine's BiLSTM has exactly one full diagonal; class_num 1
+# makes the prediction constant and 16 is the widest head the engine's kernels keep registers for. tests/test_gpu_kmer_ends.py
+# and tests/test_gpu_class_ends.py hold the HIP engine to the C oracle at these shapes, so the oracle is pinned to both
+# independent statements here first.
+END_GEOMETRIES = [dict(kmer_len=1, signal_len=40), dict(kmer_len=3, signal_len=40),
+                  dict(kmer_len=5, signal_len=40, class_num=1), dict(kmer_len=5, signal_len=40, class_num=16),
+                  dict(kmer_len=1, signal_len=40, class_num=16)]
+
+
+def end_features(n, seed, kmer_len, signal_len):
+    """synthetic_features cuts a short window somewhere in [kmer_len, signal_len): drawn at a window that is always
+    longer than the k-mer and sliced, so the same call serves kmer_len 255 at signal_len 40."""
+    feats = synth.synthetic_features(n, seed=seed, kmer_len=kmer_len, signal_len=max(signal_len, 2 * kmer_len + 64))
+    feats["signals"] = np.ascontiguousarray(feats["signals"][:, :signal_len])
+    return feats
+
+
+@pytest.mark.parametrize("geom", END_GEOMETRIES, ids=lambda g: "-".join("%s%d" % kv for kv in g.items()))
+def test_statements_agree_at_the_ends_of_kmer_len_and_class_num(geom):
+    """The three forward statements (float64) on every tap, with the bars of test_independent_torch_statement_agrees /
+    test_third_statement_in_nn_modules_agrees, and nn_statement's fp32 library kernels against the fp32 C oracle."""
+    from oracle import nn_statement
+    n, T, S, C = 9, geom["kmer_len"], geom["signal_len"], geom.get("class_num", 2)
+    w = weights.random_weights(seed=33, lstm_bias_std=0.1, **geom)
+    feats = end_features(n, 8, T, S)
+    o_act, o_pred, o_taps = oracle.forward(w, feats, "f64", taps=True, **geom)
+    assert o_act.shape == (n, C) and o_taps["logits"].shape == (n, C) and o_taps["lstm_fw_l0"].shape == (n, T, spec.HIDDEN)
+    assert np.array_equal(o_pred, np.argmax(o_act, axis=1)) and (C > 1 or not o_pred.any())
+    if T == 1:      # one step: each direction's last output is its only one, and the two directions have their own weights
+        assert np.array_equal(o_taps["joint"][:, :256], o_taps["lstm_fw_l2"][:, 0])
+        assert np.array_equal(o_taps["joint"][:, 256:512], o_taps["lstm_bw_l2"][:, 0])
+        assert np.abs(o_taps["lstm_fw_l0"] - o_taps["lstm_bw_l0"]).max() > 1e-3
+    t_act, t_pred, t_taps = torch_statement.forward(w, feats, torch.float64, True)
+    assert set(o_taps) == set(t_taps)
+    assert np.abs(o_act - t_act).max() < 1e-7 and np.array_equal(o_pred, t_pred)
+    for k, v in o_taps.items():
+        assert np.abs(v - t_taps[k]).max() <= 1e-6 * max(1.0, np.abs(v).max()), k
+    n_act, n_pred, n_taps = nn_statement.forward(w, feats, torch.float64, True)
+    assert np.abs(o_act - n_act).max() < 1e-7 and np.array_equal(o_pred, n_pred)
+    assert set(n_taps) >= {"lstm_fw_l2", "lstm_bw_l2", "stem_pool", "module1", "module4", "module9", "module11", "fc1", "logits"}
+    for k, v in n_taps.items():
+        assert np.abs(v - o_taps[k]).max() <= 1e-6 * max(1.0, np.abs(o_taps[k]).max()), k
+    f_act, _ = nn_statement.forward(w, feats, torch.float32)
+    c_act, _ = oracle.forward(w, feats, "f32", **geom)
+    assert f_act.shape == (n, C) and np.abs(f_act - c_act).max() < 1e-5
+
+
 # Long windows (--cent_signals_len, deepsignal.py:260): widths on both sides of the fused kernels' 96-row limit, odd widths with
 # a left pool pad of 1 (385, 1537), even ones (800), and a joint width of 23,792 at 1537. tests/test_gpu_long_windows.py holds the
 # HIP engine to the C oracle at these shapes, so the oracle is pinned to both independent statements here first.

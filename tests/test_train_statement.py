@@ -5,7 +5,7 @@ import pytest
 import torch
 
 import train_statement as ts
-from deepsignal_amd import weights
+from deepsignal_amd import spec, weights
 
 
 @pytest.fixture(scope="module")
@@ -21,6 +21,35 @@ def case():
 
 @pytest.mark.parametrize("pos_weight", [1.0, 3.0])
 def test_autograd_matches_central_differences(case, pos_weight):
+    _central_differences(case, pos_weight)
+
+
+def _case_at(n, T):
+    w = weights.random_weights(seed=7, is_cnn=False, is_base=False, kmer_len=T, lstm_bias_std=0.1)
+    feats = ts.train_features(n, T, seed=11)
+    labels = (np.arange(n) % 2).astype(np.int32)
+    rng = np.random.default_rng(5)
+    masks = {s: (rng.random(m.shape) < 0.5).astype(np.uint8) for s, m in ts.no_masks(n, T).items()}
+    return w, feats, labels, masks
+
+
+@pytest.mark.parametrize("pos_weight", [1.0, 3.0])
+@pytest.mark.parametrize("T", [1, 3])
+def test_autograd_matches_central_differences_at_the_ends_of_kmer_len(T, pos_weight):
+    """T = 1: no cell has a recurrent operand, so the rows [in:] of every LSTM kernel have a gradient of exactly zero (and the
+    central difference is zero too: the loss does not depend on them). T = 3 = the number of layers. tests/test_gpu_train_kmer_ends.py
+    holds the GPU step to the statement at these lengths."""
+    case = _case_at(5, T)
+    grads = _central_differences(case, pos_weight)
+    for direction in ("fw", "bw"):
+        for layer in range(spec.LSTM_LAYERS):
+            g = grads[spec.lstm_tensor(direction, layer, "kernel")]
+            rec = g[g.shape[0] - spec.HIDDEN:]
+            assert np.abs(g[:g.shape[0] - spec.HIDDEN]).max() > 0
+            assert (rec == 0).all() if T == 1 else np.abs(rec).max() > 0
+
+
+def _central_differences(case, pos_weight):
     w, feats, labels, masks = case
     _, _, grads = ts.step(w, feats, labels, masks, keep_prob=0.5, pos_weight=pos_weight)
     rng = np.random.default_rng(1)
@@ -45,6 +74,7 @@ def test_autograd_matches_central_differences(case, pos_weight):
             fd = (up - dn) / (2 * eps)
             # central differences in float64: truncation ~eps^2 |f'''|, rounding ~1e-16 / eps = 1e-11
             assert abs(fd - g.flat[idx]) <= 1e-8 + 1e-6 * abs(fd), (name, idx, fd, g.flat[idx])
+    return grads
 
 
 @pytest.mark.parametrize("pos_weight", [1.0, 3.0])

@@ -23,6 +23,35 @@ def case():
 
 @pytest.mark.parametrize("pos_weight", [1.0, 3.0])
 def test_autograd_matches_central_differences(case, pos_weight):
+    _central_differences(case, pos_weight)
+
+
+@pytest.mark.parametrize("pos_weight", [1.0, 3.0])
+@pytest.mark.parametrize("n,T", [(1, 1), (4, 1), (4, 3)])
+def test_autograd_matches_central_differences_at_the_ends_of_kmer_len(n, T, pos_weight):
+    """T = 1: the rows [in:] of every LSTM kernel have a gradient of exactly zero, and at n = 1 the embedding's gradient has one
+    non-zero row, the (clamped) code's. T = 3 = the number of layers. tests/test_gpu_train_kmer_ends.py holds the GPU step to the
+    statement at these lengths."""
+    w = weights.random_weights(seed=7, is_cnn=False, is_base=True, kmer_len=T, lstm_bias_std=0.1)
+    feats = tsb.train_features(n, T, seed=11, kind="hostile")
+    labels = (np.arange(n) % 2 == 0).astype(np.int32)
+    rng = np.random.default_rng(5)
+    masks = {s: (rng.random(m.shape) < 0.5).astype(np.uint8) for s, m in tsb.no_masks(n, T).items()}
+    if n == 1:      # a random two-entry mask on the logits can drop the whole loss
+        masks = tsb.no_masks(n, T)
+    grads = _central_differences((w, feats, labels, masks), pos_weight, ends=False)
+    for direction in ("fw", "bw"):
+        for layer in range(spec.LSTM_LAYERS):
+            g = grads[spec.lstm_tensor(direction, layer, "kernel")]
+            rec = g[g.shape[0] - spec.HIDDEN:]
+            assert np.abs(g[:g.shape[0] - spec.HIDDEN]).max() > 0
+            assert (rec == 0).all() if T == 1 else np.abs(rec).max() > 0
+    if n * T == 1:
+        row = int(tsb.clamp_codes(feats["kmer"])[0, 0])
+        assert list(np.nonzero(np.abs(grads[tsb.EMBEDDING]).max(axis=1))[0]) == [row]
+
+
+def _central_differences(case, pos_weight, ends=True):
     w, feats, labels, masks = case
     _, _, grads = tsb.step(w, feats, labels, masks, keep_prob=0.5, pos_weight=pos_weight)
     rng = np.random.default_rng(1)
@@ -39,7 +68,7 @@ def test_autograd_matches_central_differences(case, pos_weight):
         flat = list(np.argsort(np.abs(g).ravel())[-2:]) + list(rng.integers(0, g.size, 2))
         if name == tsb.EMBEDDING:      # ... and one in each row the codes select, the clamped ones among them
             rows = np.unique(tsb.clamp_codes(feats["kmer"]))
-            assert 0 in rows and spec.VOCAB_SIZE - 1 in rows
+            assert not ends or (0 in rows and spec.VOCAB_SIZE - 1 in rows)
             flat += [int(r) * spec.EMBEDDING_SIZE + int(rng.integers(spec.EMBEDDING_SIZE)) for r in rows]
         for idx in flat:
             base = w64[name].flat[idx]
@@ -51,6 +80,7 @@ def test_autograd_matches_central_differences(case, pos_weight):
             fd = (up - dn) / (2 * eps)
             # central differences in float64: truncation ~eps^2 |f'''|, rounding ~1e-16 / eps = 1e-11
             assert abs(fd - g.flat[idx]) <= 1e-8 + 1e-6 * abs(fd), (name, idx, fd, g.flat[idx])
+    return grads
 
 
 def test_rows_no_code_selects_have_zero_gradient(case):
