@@ -4,6 +4,7 @@
 // and layers.py (cited per stage below); nothing here falls back to a CPU path.
 #include "../../include/deepsignal_hip.h"
 #include "ds_internal.h"
+#include "ds_abi.h"
 #include "ds_extract.h"
 #include "ds_tsv_device.h"
 #include "ds_freq.h"
@@ -1643,21 +1644,10 @@ void prepare_slots(ds_handle* h)
 }  // namespace
 
 // ---- exception firewall: nothing may unwind across the C ABI (std::bad_alloc from an oversized tensor, length_error
-// from a corrupt header, ...): every allocating entry point runs behind this guard and reports a DS_ERR_* code instead.
+// from a corrupt header, ...): every entry point that returns int or int64_t is a function-try-block that ends in this handler
+// (ds_abi.h) and reports a DS_ERR_* code instead. The text goes where fail() puts it, without fail()'s temporary string.
 namespace {
-template <class F>
-auto guarded(ds_handle* h, F&& body) -> decltype(body())      // int, or the int64_t of the entry points that return byte counts
-{
-    try {
-        return body();
-    } catch (const std::bad_alloc&) {
-        return fail(h, DS_ERR_NOMEM, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(h, DS_ERR_INVALID, std::string("internal error: ") + e.what());
-    } catch (...) {
-        return fail(h, DS_ERR_INVALID, "internal error");
-    }
-}
+int abi_error(ds_handle* h) noexcept { return ds_abi::caught(h ? &h->err : &g_create_error); }
 
 // ---- table runs: call_freq, combine_strands and evaluate --on gpu (ds_freq.hip, ds_combine.hip, ds_eval.hip) ---------------------
 // One lifecycle for the three routes (TableRuns): a begin opens the route's run, every other call goes to the open run, the route's
@@ -1713,8 +1703,7 @@ const char* ds_version(void)
 
 const char* ds_last_error(const ds_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
-static int ds_create_impl(const ds_config* cfg, ds_handle** out)
-{
+int ds_create(const ds_config* cfg, ds_handle** out) try {
     if (!cfg || !out) return fail(nullptr, DS_ERR_INVALID, "ds_create: null argument");
     *out = nullptr;
     if (!(cfg->is_cnn || cfg->is_rnn))
@@ -1812,10 +1801,9 @@ static int ds_create_impl(const ds_config* cfg, ds_handle** out)
     if (rc) { g_create_error = h->err; ds_destroy(h); return rc; }
     *out = h;
     return DS_OK;
-}
+} catch (...) { return abi_error(nullptr); }
 
-void ds_destroy(ds_handle* h)
-{
+void ds_destroy(ds_handle* h) try {
     if (!h) return;
     hipSetDevice(h->cfg.device);
     // every stream is drained before any is destroyed: with DS_TUNE_SHARED_EVENT_STREAM the slots share slot 0's s1
@@ -1847,10 +1835,9 @@ void ds_destroy(ds_handle* h)
     for (void* p : h->allocs) hipFree(p);
     (void)hipGetLastError();      // nothing a teardown call returned may surface in a later handle's first launch
     delete h;
-}
+} catch (...) {}
 
-static int ds_set_tensor_impl(ds_handle* h, const char* name, const float* data, const int64_t* shape, int32_t ndim)
-{
+int ds_set_tensor(ds_handle* h, const char* name, const float* data, const int64_t* shape, int32_t ndim) try {
     if (!h || !name || !data || !shape || ndim < 1 || ndim > 8) return fail(h, DS_ERR_INVALID, "ds_set_tensor: bad argument");
     if (h->finalized) return fail(h, DS_ERR_INVALID, "weights already finalized");
     HostTensor t;
@@ -1860,10 +1847,9 @@ static int ds_set_tensor_impl(ds_handle* h, const char* name, const float* data,
     t.data.assign(data, data + cnt);
     h->host[name] = std::move(t);
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
-static int ds_finalize_weights_impl(ds_handle* h)
-{
+int ds_finalize_weights(ds_handle* h) try {
     if (!h) return DS_ERR_INVALID;
     if (h->finalized) return fail(h, DS_ERR_INVALID, "weights already finalized");
     hipSetDevice(h->cfg.device);
@@ -1872,10 +1858,9 @@ static int ds_finalize_weights_impl(ds_handle* h)
     h->weight_allocs.assign(h->allocs.begin() + allocs_before, h->allocs.end());
     if (!rc) prepare_slots(h);
     return rc;
-}
+} catch (...) { return abi_error(h); }
 
-static int ds_load_weights_impl(ds_handle* h, const char* path)
-{
+int ds_load_weights(ds_handle* h, const char* path) try {
     if (!h || !path) return fail(h, DS_ERR_INVALID, "ds_load_weights: bad argument");
     FILE* f = fopen(path, "rb");
     if (!f) return fail(h, DS_ERR_IO, std::string("cannot open ") + path);
@@ -1917,11 +1902,10 @@ static int ds_load_weights_impl(ds_handle* h, const char* path)
     }
     fclose(f);
     return ds_finalize_weights(h);
-}
+} catch (...) { return abi_error(h); }
 
-static int ds_forward_device_impl(ds_handle* h, int32_t n, const int32_t* d_kmer, const float* d_means, const float* d_stds,
-                      const float* d_sanums, const float* d_signals, float* d_act, int32_t* d_pred)
-{
+int ds_forward_device(ds_handle* h, int32_t n, const int32_t* d_kmer, const float* d_means, const float* d_stds,
+                      const float* d_sanums, const float* d_signals, float* d_act, int32_t* d_pred) try {
     if (!h) return DS_ERR_INVALID;
     if (!h->finalized) return fail(h, DS_ERR_INVALID, "weights not loaded");
     if (n < 0 || n > h->B) return fail(h, DS_ERR_INVALID, "n exceeds max_batch");
@@ -1950,10 +1934,9 @@ static int ds_forward_device_impl(ds_handle* h, int32_t n, const int32_t* d_kmer
     if (rc) return rc;
     HIPCHK(h, launch_scatter_outputs(h->cur->act, h->cur->pred, d_act, d_pred, n, h->C, h->cur->s0));
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
-int ds_sync(ds_handle* h)
-{
+int ds_sync(ds_handle* h) try {
     if (!h) return DS_ERR_INVALID;
     for (Slot& sl : h->slots) {
         HIPCHK(h, hipStreamSynchronize(sl.s0));
@@ -1961,7 +1944,7 @@ int ds_sync(ds_handle* h)
     }
     if (h->profiling) return collect_stage_times(h);
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
 // cascaded precision (ds_set_recheck, below): the selection behind a forward, and the merge of the fine handle's results
 static int enqueue_recheck(ds_handle* h, Slot& sl, int n);
@@ -2097,9 +2080,8 @@ static int inputs_to_host(ds_handle* h, Slot& sl, const char* who, size_t n, voi
     return fail(h, DS_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
 }
 
-static int ds_forward_impl(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums,
-               const float* signals, float* act, int32_t* pred)
-{
+int ds_forward(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums,
+               const float* signals, float* act, int32_t* pred) try {
     if (!h) return DS_ERR_INVALID;
     if (!h->finalized) return fail(h, DS_ERR_INVALID, "weights not loaded");
     if (n < 0) return fail(h, DS_ERR_INVALID, "negative n");
@@ -2167,7 +2149,7 @@ static int ds_forward_impl(ds_handle* h, int32_t n, const int32_t* kmer, const f
         if (rc) return rc;
     }
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
 // ---- cascaded precision (ds_set_recheck) ----------------------------------------------------------------------------------
 // A forward of a handle with a fine handle attached is followed, on the slot's stream, by recheck_select_kernel (ds_recheck.hip):
@@ -2275,8 +2257,7 @@ static int finish_recheck(ds_handle* h, Slot& sl, int n, float* act, int32_t* pr
     return DS_OK;
 }
 
-static int ds_set_recheck_impl(ds_handle* c, ds_handle* f, float margin)
-{
+int ds_set_recheck(ds_handle* c, ds_handle* f, float margin) try {
     if (!c) return DS_ERR_INVALID;
     if (margin != margin) return fail(c, DS_ERR_INVALID, "ds_set_recheck: margin is NaN");
     if (tickets_in_flight(c)) return fail(c, DS_ERR_INVALID, "ds_set_recheck: tickets are still in flight");
@@ -2307,23 +2288,23 @@ static int ds_set_recheck_impl(ds_handle* c, ds_handle* f, float margin)
     c->rc_margin = margin;
     c->rc_sites = c->rc_rechecked = c->rc_forwards = 0;
     return DS_OK;
-}
+} catch (...) { return abi_error(c); }
 
-int ds_get_recheck_stats(ds_handle* h, int64_t* sites, int64_t* rechecked, int64_t* fine_forwards)
-{
+int ds_get_recheck_stats(ds_handle* h, int64_t* sites, int64_t* rechecked, int64_t* fine_forwards) try {
     if (!h) return DS_ERR_INVALID;
     if (sites) *sites = h->rc_sites;
     if (rechecked) *rechecked = h->rc_rechecked;
     if (fine_forwards) *fine_forwards = h->rc_forwards;
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
-int ds_get_recheck_times(ds_handle* h, int32_t reset, int64_t* launches, double* ms) { return h ? h->rc_t.get(reset, launches, ms) : DS_ERR_INVALID; }
+int ds_get_recheck_times(ds_handle* h, int32_t reset, int64_t* launches, double* ms) try {
+    return h ? h->rc_t.get(reset, launches, ms) : DS_ERR_INVALID;
+} catch (...) { return abi_error(h); }
 
 // Diagnostic: the selection of recheck_select_kernel for n rows of act given by the caller (directed values: the specials, every
 // lane / wave / workgroup pattern), on an idle slot. The rows it compacts are whatever the slot's inputs hold.
-static int ds_recheck_select_impl(ds_handle* h, int32_t n, const float* act, float margin, int32_t* count, int32_t* index)
-{
+int ds_recheck_select(ds_handle* h, int32_t n, const float* act, float margin, int32_t* count, int32_t* index) try {
     if (!h) return DS_ERR_INVALID;
     if (!act || !count || !index || n < 1 || n > h->B) return fail(h, DS_ERR_INVALID, "ds_recheck_select: bad argument");
     if (h->C != 2) return fail(h, DS_ERR_UNSUPPORTED, "ds_recheck_select: the selection rule is defined for two classes");
@@ -2342,15 +2323,14 @@ static int ds_recheck_select_impl(ds_handle* h, int32_t n, const float* act, flo
     *count = m;
     memcpy(index, sl.pin_rc + rc_layout(h).index / 4, (size_t)m * 4);
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
 // Asynchronous host-buffer boundary: ds_submit copies one batch into the next slot's pinned staging buffer and
 // enqueues H2D + forward + D2H on that slot's streams; ds_wait(ticket) blocks until that forward is done and hands
 // the results out. Up to `slots` forwards are in flight, so PCIe copies, the 19-launch LSTM chain of one batch and
 // the host's own work (parsing, formatting) overlap.
-static int ds_submit_parts_impl(ds_handle* h, int32_t nparts, const int32_t* counts, const int32_t* const* kmer, const float* const* means,
-                                const float* const* stds, const float* const* sanums, const float* const* signals, int32_t* ticket)
-{
+int ds_submit_parts(ds_handle* h, int32_t nparts, const int32_t* counts, const int32_t* const* kmer, const float* const* means,
+                    const float* const* stds, const float* const* sanums, const float* const* signals, int32_t* ticket) try {
     if (!h || !ticket) return DS_ERR_INVALID;
     if (!h->finalized) return fail(h, DS_ERR_INVALID, "weights not loaded");
     if (nparts <= 0 || !counts || !kmer || !means || !stds || !sanums || !signals) return fail(h, DS_ERR_INVALID, "null buffer");
@@ -2367,23 +2347,21 @@ static int ds_submit_parts_impl(ds_handle* h, int32_t nparts, const int32_t* cou
     int rc = idle_slot(h, "ds_submit", &sl);
     if (!rc) rc = stage_host_inputs(h, *sl, nparts, counts, kmer, means, stds, sanums, signals);
     return rc ? rc : submit_forward(h, *sl, n, ticket);
-}
+} catch (...) { return abi_error(h); }
 
-static int ds_submit_impl(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums,
-              const float* signals, int32_t* ticket)
-{
+int ds_submit(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums,
+              const float* signals, int32_t* ticket) try {
     if (h && (!kmer || !means || !stds || !sanums || !signals)) return fail(h, DS_ERR_INVALID, "null buffer");
-    return ds_submit_parts_impl(h, 1, &n, &kmer, &means, &stds, &sanums, &signals, ticket);
-}
+    return ds_submit_parts(h, 1, &n, &kmer, &means, &stds, &sanums, &signals, ticket);
+} catch (...) { return abi_error(h); }
 
-static int ds_wait_impl(ds_handle* h, int32_t ticket, float* act, int32_t* pred)
-{
+int ds_wait(ds_handle* h, int32_t ticket, float* act, int32_t* pred) try {
     if (!h || !act || !pred) return DS_ERR_INVALID;
     Slot* sl = nullptr;
     int n = 0;
     int rc = ticket_slot(h, "ds_wait", ticket, Ticket::Forward, &sl, &n);
     return rc ? rc : take_results(h, *sl, n, act, pred);
-}
+} catch (...) { return abi_error(h); }
 
 // Scope row f2 on the device: the reads of `r` are validated, packed into the slot's pinned block, copied to its device block
 // and the extraction kernels write the features into the slot's forward inputs (d_kmer .. d_signals), all on sl.s0. Captured
@@ -2412,8 +2390,7 @@ static int stage_reads(ds_handle* h, Slot& sl, const ds_reads* r, dsx::ExtractPl
     return DS_OK;
 }
 
-static int ds_extract_impl(ds_handle* h, const ds_reads* r, int32_t* kmer, float* means, float* stds, float* sanums, float* signals)
-{
+int ds_extract(ds_handle* h, const ds_reads* r, int32_t* kmer, float* means, float* stds, float* sanums, float* signals) try {
     if (!h) return DS_ERR_INVALID;
     if (!kmer || !means || !stds || !sanums || !signals) return fail(h, DS_ERR_INVALID, "null buffer");
     Slot* sl = nullptr;
@@ -2433,10 +2410,9 @@ static int ds_extract_impl(ds_handle* h, const ds_reads* r, int32_t* kmer, float
         h->kstat[K_EXTRACT_SITES].launches += 1; h->kstat[K_EXTRACT_SITES].total_ms += ms1;
     }
     return rc;
-}
+} catch (...) { return abi_error(h); }
 
-static int ds_submit_reads_impl(ds_handle* h, const ds_reads* r, int32_t* ticket)
-{
+int ds_submit_reads(ds_handle* h, const ds_reads* r, int32_t* ticket) try {
     if (!h || !ticket) return DS_ERR_INVALID;
     if (!h->finalized) return fail(h, DS_ERR_INVALID, "weights not loaded");
     if (h->profiling) return fail(h, DS_ERR_INVALID, "ds_submit_reads is not available while profiling is on");
@@ -2445,7 +2421,7 @@ static int ds_submit_reads_impl(ds_handle* h, const ds_reads* r, int32_t* ticket
     int rc = idle_slot(h, "ds_submit_reads", &sl);
     if (!rc) rc = stage_reads(h, *sl, r, &p, nullptr);
     return rc ? rc : submit_forward(h, *sl, p.nsites, ticket);
-}
+} catch (...) { return abi_error(h); }
 
 // ---- feature-TSV rows parsed on the device (ds_tsv_parse.hip tsv_parse_kernel; call_mods --parse_on gpu) ----------------------------
 // The producer beside ds_submit_reads: the rows' text is packed into the slot's pinned block (16-byte aligned starts, an offset
@@ -2550,8 +2526,7 @@ static hipError_t enqueue_text_results(const ds_handle* h, Slot& sl, int n)
     return e;
 }
 
-static int ds_submit_text_impl(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, int32_t* ticket)
-{
+int ds_submit_text(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, int32_t* ticket) try {
     if (!h || !ticket) return DS_ERR_INVALID;
     if (!h->finalized) return fail(h, DS_ERR_INVALID, "weights not loaded");
     if (h->profiling) return fail(h, DS_ERR_INVALID, "ds_submit_text is not available while profiling is on");
@@ -2568,7 +2543,7 @@ static int ds_submit_text_impl(ds_handle* h, const char* text, int32_t nrows, co
     rc = enqueue_results(h, *sl, nrows);
     if (!rc) hold(h, *sl, Ticket::Text, nrows, ticket);
     return rc;
-}
+} catch (...) { return abi_error(h); }
 
 // m host arrays through the forward on the idle slot sl, by the steps ds_forward's passes take (pinned staging, H2D, forward,
 // recheck selection, one copy back, merge of the rechecks)
@@ -2580,9 +2555,8 @@ static int forward_on_slot(ds_handle* h, Slot& sl, int m, const int32_t* kmer, c
     return rc ? rc : take_results(h, sl, m, act, pred);
 }
 
-static int ds_wait_text_impl(ds_handle* h, int32_t ticket, float* act, int32_t* pred, int32_t* kmer, int32_t* labels, char* info,
-                             int64_t info_cap, int64_t* info_off)
-{
+int ds_wait_text(ds_handle* h, int32_t ticket, float* act, int32_t* pred, int32_t* kmer, int32_t* labels, char* info,
+                 int64_t info_cap, int64_t* info_off) try {
     if (!h || !act || !pred || !kmer || !labels || !info || !info_off) return DS_ERR_INVALID;
     Slot* held = nullptr;
     int n = 0;
@@ -2637,12 +2611,11 @@ static int ds_wait_text_impl(ds_handle* h, int32_t ticket, float* act, int32_t* 
     if (tot > info_cap) return fail(h, DS_ERR_INVALID, "ds_wait_text: info buffer too small (" + std::to_string(tot) + " bytes needed)");
     for (int i = 0; i < n; ++i) memcpy(info + info_off[i], sl.text_rows[(size_t)i].first, (size_t)ilen[(size_t)i]);
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
 // Blocking diagnostic on an idle slot (not advanced, as ds_extract): the device's arrays and per-row status, no forward
-static int ds_parse_text_impl(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, int32_t* kmer,
-                              float* means, float* stds, float* lens, float* signals, int32_t* labels, int32_t* info_len, int32_t* status)
-{
+int ds_parse_text(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, int32_t* kmer,
+                  float* means, float* stds, float* lens, float* signals, int32_t* labels, int32_t* info_len, int32_t* status) try {
     if (!h) return DS_ERR_INVALID;
     if (!kmer || !means || !stds || !lens || !signals || !labels || !status) return fail(h, DS_ERR_INVALID, "null buffer");
     int rc = check_text_args(h, "ds_parse_text", text, nrows, begin, end);
@@ -2665,12 +2638,11 @@ static int ds_parse_text_impl(ds_handle* h, const char* text, int32_t nrows, con
     if (info_len) memcpy(info_len, sl.pin_tres + 2 * B, n * 4);
     memcpy(kmer, sl.pin_tres + 3 * B, n * T * 4);
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
 int ds_parse_text_reference(int32_t kmer_len, int32_t signal_len, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end,
                             int32_t* kmer, float* means, float* stds, float* lens, float* signals, int32_t* labels, int32_t* info_len,
-                            int32_t* status)
-{
+                            int32_t* status) try {
     if (nrows == 0) return DS_OK;
     if (kmer_len < 1 || signal_len < 1 || nrows < 0 || !text || !begin || !end || !kmer || !means || !stds || !lens || !signals || !labels ||
         !info_len || !status)
@@ -2679,216 +2651,184 @@ int ds_parse_text_reference(int32_t kmer_len, int32_t signal_len, const char* te
         if (begin[i] < 0 || end[i] < begin[i]) return fail(nullptr, DS_ERR_INVALID, "ds_parse_text_reference: row " + std::to_string(i) + " has a bad span");
     dst::parse_reference(kmer_len, signal_len, text, nrows, begin, end, kmer, means, stds, lens, signals, labels, info_len, status);
     return DS_OK;
-}
+} catch (...) { return abi_error(nullptr); }
 
-int ds_get_text_stats(ds_handle* h, int64_t* rows, int64_t* host_rows)
-{
+int ds_get_text_stats(ds_handle* h, int64_t* rows, int64_t* host_rows) try {
     if (!h) return DS_ERR_INVALID;
     if (rows) *rows = h->tx_rows;
     if (host_rows) *host_rows = h->tx_host_rows;
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
-int ds_get_text_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms) { return h ? h->tx_t.get(reset, batches, ms) : DS_ERR_INVALID; }
+int ds_get_text_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms) try {
+    return h ? h->tx_t.get(reset, batches, ms) : DS_ERR_INVALID;
+} catch (...) { return abi_error(h); }
 
 // ---- table runs: call_freq, combine_strands and evaluate --on gpu (ds_freq.hip, ds_combine.hip, ds_eval.hip; open_run, in_run, end_run) ----
 // per-site modification frequency (dsf::Freq)
-static int ds_freq_begin_stream_impl(ds_handle* h, int64_t initial_slots, int32_t batch_rows, double prob_cf)
-{
+int ds_freq_begin_stream(ds_handle* h, int64_t initial_slots, int32_t batch_rows, double prob_cf) try {
     return open_run(h, &ds_handle::freq, "begin_stream",
                     [&](dsf::Freq& r, std::string* err) { return r.begin_stream(h->cfg.device, initial_slots, batch_rows, prob_cf, err); });
-}
+} catch (...) { return abi_error(h); }
 
-static int ds_freq_push_impl(ds_handle* h, int32_t nrows, const int32_t* chrom, const int64_t* pos, const float* act, int32_t class_num,
-                             const int32_t* pred, int32_t* status, int32_t* opened)
-{
+int ds_freq_push(ds_handle* h, int32_t nrows, const int32_t* chrom, const int64_t* pos, const float* act, int32_t class_num,
+                 const int32_t* pred, int32_t* status, int32_t* opened) try {
     return in_run(h, &ds_handle::freq, "push",
                   [&](dsf::Freq& r, std::string* err) { return r.push(nrows, chrom, pos, act, class_num, pred, status, opened, err); }, "begin_stream");
-}
+} catch (...) { return abi_error(h); }
 
-static int ds_freq_values_impl(ds_handle* h, int64_t n, const float* act, int32_t class_num, double* p0, double* p1, int32_t* status)
-{
+int ds_freq_values(ds_handle* h, int64_t n, const float* act, int32_t class_num, double* p0, double* p1, int32_t* status) try {
     if (!h) return DS_ERR_INVALID;
     std::string err;
     const int rc = dsf::values_device(h->cfg.device, n, act, class_num, p0, p1, status, &err);
     return rc ? fail(h, rc, err) : DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
-static int ds_freq_begin_impl(ds_handle* h, int64_t total_rows, int32_t batch_rows, double prob_cf)
-{
+int ds_freq_begin(ds_handle* h, int64_t total_rows, int32_t batch_rows, double prob_cf) try {
     return open_run(h, &ds_handle::freq, "begin",
                     [&](dsf::Freq& r, std::string* err) { return r.begin(h->cfg.device, total_rows, batch_rows, prob_cf, err); });
-}
+} catch (...) { return abi_error(h); }
 
-static int ds_freq_parse_impl(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, const int32_t* chrom,
-                              const uint8_t* flags, int32_t* status)
-{
+int ds_freq_parse(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, const int32_t* chrom,
+                  const uint8_t* flags, int32_t* status) try {
     return in_run(h, &ds_handle::freq, "parse",
                   [&](dsf::Freq& r, std::string* err) { return r.parse(text, nrows, begin, end, chrom, flags, status, err); });
-}
+} catch (...) { return abi_error(h); }
 
-static int ds_freq_accumulate_impl(ds_handle* h, int32_t nover, const int32_t* row, const int32_t* chrom, const int64_t* pos, const double* p0,
-                                   const double* p1, const int32_t* met)
-{
+int ds_freq_accumulate(ds_handle* h, int32_t nover, const int32_t* row, const int32_t* chrom, const int64_t* pos, const double* p0,
+                       const double* p1, const int32_t* met) try {
     return in_run(h, &ds_handle::freq, "accumulate",
                   [&](dsf::Freq& r, std::string* err) { return r.accumulate(nover, row, chrom, pos, p0, p1, met, err); });
-}
+} catch (...) { return abi_error(h); }
 
-static int64_t ds_freq_result_impl(ds_handle* h, int64_t cap, int64_t* first_row, int32_t* chrom, int64_t* pos, double* sum0, double* sum1,
-                                   int32_t* met, int32_t* unmet, int64_t* rows, int64_t* used)
-{
+int64_t ds_freq_result(ds_handle* h, int64_t cap, int64_t* first_row, int32_t* chrom, int64_t* pos, double* sum0, double* sum1,
+                       int32_t* met, int32_t* unmet, int64_t* rows, int64_t* used) try {
     return in_run(h, &ds_handle::freq, "result",
                   [&](dsf::Freq& r, std::string* err) { return r.result(cap, first_row, chrom, pos, sum0, sum1, met, unmet, rows, used, err); });
-}
+} catch (...) { return abi_error(h); }
 
-int ds_freq_end(ds_handle* h) { return end_run(h, &ds_handle::freq); }
+int ds_freq_end(ds_handle* h) try { return end_run(h, &ds_handle::freq); } catch (...) { return abi_error(h); }
 
 int64_t ds_freq_reference(const char* text, int64_t nrows, const int64_t* begin, const int64_t* end, const int32_t* chrom, const uint8_t* flags,
                           double prob_cf, int32_t* status, int64_t* pos, double* p0, double* p1, int32_t* met, int64_t cap, int64_t* first_row,
-                          int32_t* site_chrom, int64_t* site_pos, double* sum0, double* sum1, int32_t* site_met, int32_t* site_unmet, int64_t* used)
-{
-    return guarded(nullptr, [&]() -> int64_t {
-        std::string err;
-        const int64_t rc = dsf::reference(text, nrows, begin, end, chrom, flags, prob_cf, status, pos, p0, p1, met, cap, first_row, site_chrom,
-                                          site_pos, sum0, sum1, site_met, site_unmet, used, &err);
-        return rc < 0 ? fail(nullptr, DS_ERR_INVALID, err) : rc;
-    });
-}
+                          int32_t* site_chrom, int64_t* site_pos, double* sum0, double* sum1, int32_t* site_met, int32_t* site_unmet, int64_t* used) try {
+    std::string err;
+    const int64_t rc = dsf::reference(text, nrows, begin, end, chrom, flags, prob_cf, status, pos, p0, p1, met, cap, first_row, site_chrom,
+                                      site_pos, sum0, sum1, site_met, site_unmet, used, &err);
+    return rc < 0 ? fail(nullptr, DS_ERR_INVALID, err) : rc;
+} catch (...) { return abi_error(nullptr); }
 
-int ds_freq_values_reference(int64_t n, const float* act, int32_t class_num, double* p0, double* p1, int32_t* status)
-{
+int ds_freq_values_reference(int64_t n, const float* act, int32_t class_num, double* p0, double* p1, int32_t* status) try {
     if (n < 0 || class_num < 2 || (n > 0 && (!act || !p0 || !p1 || !status))) return DS_ERR_INVALID;
-    return guarded(nullptr, [&]() -> int { dsf::values_reference(n, act, class_num, p0, p1, status); return DS_OK; });
-}
+    dsf::values_reference(n, act, class_num, p0, p1, status);
+    return DS_OK;
+} catch (...) { return abi_error(nullptr); }
 
-int ds_get_freq_stream_times(ds_handle* h, int32_t reset, int64_t* growths, double* ms)
-{
+int ds_get_freq_stream_times(ds_handle* h, int32_t reset, int64_t* growths, double* ms) try {
     return h ? h->freq.ended.stream.get(reset, growths, ms, h->freq.open ? &h->freq.open->t.stream : nullptr) : DS_ERR_INVALID;
-}
+} catch (...) { return abi_error(h); }
 
-int ds_get_freq_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms)
-{
+int ds_get_freq_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms) try {
     return h ? h->freq.ended.batch.get(reset, batches, ms, h->freq.open ? &h->freq.open->t.batch : nullptr) : DS_ERR_INVALID;
-}
+} catch (...) { return abi_error(h); }
 
 // both strands of a CpG table combined (dsc::Combine)
-static int ds_combine_begin_impl(ds_handle* h, int32_t form, int32_t nrec, const int64_t* rec_len, int64_t total_rows, int32_t batch_rows)
-{
+int ds_combine_begin(ds_handle* h, int32_t form, int32_t nrec, const int64_t* rec_len, int64_t total_rows, int32_t batch_rows) try {
     return open_run(h, &ds_handle::combine, "begin",
                     [&](dsc::Combine& r, std::string* err) { return r.begin(h->cfg.device, form, nrec, rec_len, total_rows, batch_rows, err); });
-}
+} catch (...) { return abi_error(h); }
 
-static int ds_combine_genome_impl(ds_handle* h, const char* text, int64_t nseg, const int64_t* seg_begin, const int64_t* seg_end, const int64_t* seg_bit,
-                                  const uint8_t* seg_carry)
-{
+int ds_combine_genome(ds_handle* h, const char* text, int64_t nseg, const int64_t* seg_begin, const int64_t* seg_end, const int64_t* seg_bit,
+                      const uint8_t* seg_carry) try {
     return in_run(h, &ds_handle::combine, "genome",
                   [&](dsc::Combine& r, std::string* err) { return r.genome(text, nseg, seg_begin, seg_end, seg_bit, seg_carry, err); });
-}
+} catch (...) { return abi_error(h); }
 
-static int ds_combine_bitmap_impl(ds_handle* h, int64_t cap_words, uint32_t* bitmap)
-{
+int ds_combine_bitmap(ds_handle* h, int64_t cap_words, uint32_t* bitmap) try {
     return in_run(h, &ds_handle::combine, "bitmap", [&](dsc::Combine& r, std::string* err) { return r.get_bitmap(cap_words, bitmap, err); });
-}
+} catch (...) { return abi_error(h); }
 
-static int ds_combine_parse_impl(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, const int32_t* chrom,
-                                 const uint8_t* flags, int32_t* status)
-{
+int ds_combine_parse(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, const int32_t* chrom,
+                     const uint8_t* flags, int32_t* status) try {
     return in_run(h, &ds_handle::combine, "parse",
                   [&](dsc::Combine& r, std::string* err) { return r.parse(text, nrows, begin, end, chrom, flags, status, err); });
-}
+} catch (...) { return abi_error(h); }
 
-static int ds_combine_accumulate_impl(ds_handle* h, int32_t nover, const int32_t* row, const int32_t* status, const int32_t* chrom, const int64_t* pos,
-                                      const int32_t* plus, const double* a, const double* b, const int64_t* met, const int64_t* unmet, const int64_t* cov)
-{
+int ds_combine_accumulate(ds_handle* h, int32_t nover, const int32_t* row, const int32_t* status, const int32_t* chrom, const int64_t* pos,
+                          const int32_t* plus, const double* a, const double* b, const int64_t* met, const int64_t* unmet, const int64_t* cov) try {
     return in_run(h, &ds_handle::combine, "accumulate", [&](dsc::Combine& r, std::string* err) {
         return r.accumulate(nover, row, status, chrom, pos, plus, a, b, met, unmet, cov, err);
     });
-}
+} catch (...) { return abi_error(h); }
 
-static int64_t ds_combine_result_impl(ds_handle* h, int64_t cap, int32_t* chrom, int64_t* pos, double* sum0, double* sum1, int64_t* met, int64_t* unmet,
-                                      int64_t* cov, int64_t* last_plus, int64_t* rows)
-{
+int64_t ds_combine_result(ds_handle* h, int64_t cap, int32_t* chrom, int64_t* pos, double* sum0, double* sum1, int64_t* met, int64_t* unmet,
+                          int64_t* cov, int64_t* last_plus, int64_t* rows) try {
     return in_run(h, &ds_handle::combine, "result", [&](dsc::Combine& r, std::string* err) {
         return r.result(cap, chrom, pos, sum0, sum1, met, unmet, cov, last_plus, rows, err);
     });
-}
+} catch (...) { return abi_error(h); }
 
-int ds_combine_end(ds_handle* h) { return end_run(h, &ds_handle::combine); }
+int ds_combine_end(ds_handle* h) try { return end_run(h, &ds_handle::combine); } catch (...) { return abi_error(h); }
 
 int ds_motif_reference(const char* text, int64_t nseg, const int64_t* seg_begin, const int64_t* seg_end, const int64_t* seg_bit, const uint8_t* seg_carry,
-                       int64_t nbits, uint32_t* bitmap)
-{
-    return guarded(nullptr, [&]() -> int {
-        std::string err;
-        return dsc::motif_reference(text, nseg, seg_begin, seg_end, seg_bit, seg_carry, nbits, bitmap, &err) ? DS_OK
-                                                                                                             : fail(nullptr, DS_ERR_INVALID, "ds_motif_reference: " + err);
-    });
-}
+                       int64_t nbits, uint32_t* bitmap) try {
+    std::string err;
+    return dsc::motif_reference(text, nseg, seg_begin, seg_end, seg_bit, seg_carry, nbits, bitmap, &err) ? DS_OK
+                                                                                                         : fail(nullptr, DS_ERR_INVALID, "ds_motif_reference: " + err);
+} catch (...) { return abi_error(nullptr); }
 
 int64_t ds_combine_reference(int32_t form, const char* text, int64_t nrows, const int64_t* begin, const int64_t* end, int32_t* chrom, const uint8_t* flags,
                              int32_t nrec, const int64_t* rec_len, const uint32_t* bitmap, int32_t* status, int64_t* pos, int32_t* plus, double* a,
                              double* b, int64_t* met, int64_t* unmet, int64_t* cov, int64_t cap, int32_t* site_chrom, int64_t* site_pos, double* sum0,
-                             double* sum1, int64_t* site_met, int64_t* site_unmet, int64_t* site_cov, int64_t* last_plus)
-{
-    return guarded(nullptr, [&]() -> int64_t {
-        std::string err;
-        const int64_t rc = dsc::reference(form, text, nrows, begin, end, chrom, flags, nrec, rec_len, bitmap, status, pos, plus, a, b, met, unmet, cov, cap,
-                                          site_chrom, site_pos, sum0, sum1, site_met, site_unmet, site_cov, last_plus, &err);
-        return rc < 0 ? fail(nullptr, DS_ERR_INVALID, err) : rc;
-    });
-}
+                             double* sum1, int64_t* site_met, int64_t* site_unmet, int64_t* site_cov, int64_t* last_plus) try {
+    std::string err;
+    const int64_t rc = dsc::reference(form, text, nrows, begin, end, chrom, flags, nrec, rec_len, bitmap, status, pos, plus, a, b, met, unmet, cov, cap,
+                                      site_chrom, site_pos, sum0, sum1, site_met, site_unmet, site_cov, last_plus, &err);
+    return rc < 0 ? fail(nullptr, DS_ERR_INVALID, err) : rc;
+} catch (...) { return abi_error(nullptr); }
 
-int ds_get_combine_times(ds_handle* h, int32_t reset, int64_t* chunks, int64_t* batches, double* ms)
-{
+int ds_get_combine_times(ds_handle* h, int32_t reset, int64_t* chunks, int64_t* batches, double* ms) try {
     if (!h || !chunks || !batches || !ms) return DS_ERR_INVALID;
     const dsc::Combine::Tally t = h->combine.ended.take(reset, h->combine.open ? &h->combine.open->t : nullptr);
     *batches = t.n[0];
     *chunks = t.n[1];
     std::copy(t.ms, t.ms + 5, ms);
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
 // call accuracy and AUROC of labelled call rows (dse::Eval)
-static int ds_eval_begin_impl(ds_handle* h, int64_t total_rows, int32_t batch_rows, int32_t ncf, const double* cf)
-{
+int ds_eval_begin(ds_handle* h, int64_t total_rows, int32_t batch_rows, int32_t ncf, const double* cf) try {
     return open_run(h, &ds_handle::eval, "begin",
                     [&](dse::Eval& r, std::string* err) { return r.begin(h->cfg.device, total_rows, batch_rows, ncf, cf, err); });
-}
+} catch (...) { return abi_error(h); }
 
-static int ds_eval_parse_impl(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, const uint8_t* flags, int32_t* status)
-{
+int ds_eval_parse(ds_handle* h, const char* text, int32_t nrows, const int64_t* begin, const int64_t* end, const uint8_t* flags, int32_t* status) try {
     return in_run(h, &ds_handle::eval, "parse", [&](dse::Eval& r, std::string* err) { return r.parse(text, nrows, begin, end, flags, status, err); });
-}
+} catch (...) { return abi_error(h); }
 
-static int ds_eval_accumulate_impl(ds_handle* h, const uint8_t* mask, int32_t nover, const int32_t* row, const double* p0, const double* p1,
-                                   const int32_t* called)
-{
+int ds_eval_accumulate(ds_handle* h, const uint8_t* mask, int32_t nover, const int32_t* row, const double* p0, const double* p1,
+                       const int32_t* called) try {
     return in_run(h, &ds_handle::eval, "accumulate",
                   [&](dse::Eval& r, std::string* err) { return r.accumulate(mask, nover, row, p0, p1, called, err); });
-}
+} catch (...) { return abi_error(h); }
 
-static int ds_eval_result_impl(ds_handle* h, int64_t* counts, uint64_t* u2, int64_t* pn, int64_t* nn, int64_t* rows, int64_t* distinct)
-{
+int ds_eval_result(ds_handle* h, int64_t* counts, uint64_t* u2, int64_t* pn, int64_t* nn, int64_t* rows, int64_t* distinct) try {
     return in_run(h, &ds_handle::eval, "result",
                   [&](dse::Eval& r, std::string* err) { return r.result(counts, u2, pn, nn, rows, distinct, err); });
-}
+} catch (...) { return abi_error(h); }
 
-int ds_eval_end(ds_handle* h) { return end_run(h, &ds_handle::eval); }
+int ds_eval_end(ds_handle* h) try { return end_run(h, &ds_handle::eval); } catch (...) { return abi_error(h); }
 
 int ds_eval_reference(const char* text, int64_t nrows, const int64_t* begin, const int64_t* end, const uint8_t* flags, const uint8_t* mask, int32_t ncf,
-                      const double* cf, int32_t* status, double* p0, double* p1, int32_t* called, int64_t* counts, uint64_t* u2, int64_t* pn, int64_t* nn)
-{
-    return guarded(nullptr, [&]() -> int {
-        std::string err;
-        return dse::reference(text, nrows, begin, end, flags, mask, ncf, cf, status, p0, p1, called, counts, u2, pn, nn, &err) ? DS_OK
-                                                                                                                               : fail(nullptr, DS_ERR_INVALID, err);
-    });
-}
+                      const double* cf, int32_t* status, double* p0, double* p1, int32_t* called, int64_t* counts, uint64_t* u2, int64_t* pn, int64_t* nn) try {
+    std::string err;
+    return dse::reference(text, nrows, begin, end, flags, mask, ncf, cf, status, p0, p1, called, counts, u2, pn, nn, &err) ? DS_OK
+                                                                                                                           : fail(nullptr, DS_ERR_INVALID, err);
+} catch (...) { return abi_error(nullptr); }
 
-int ds_get_eval_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms)
-{
+int ds_get_eval_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms) try {
     return h ? h->eval.ended.get(reset, batches, ms, h->eval.open ? &h->eval.open->t : nullptr) : DS_ERR_INVALID;
-}
+} catch (...) { return abi_error(h); }
 
 // ---- feature rows: float64 values and their text on the device (ds_extract.hip rows_*_kernel) ---------------------------------
 // Needs no weights: the slot's streams and the blocks below are all it uses. The rows path enqueues, on sl.s0: H2D of the packed
@@ -2958,8 +2898,7 @@ static int64_t collect_rows(ds_handle* h, Slot& sl, int n, char* out, int64_t ca
     return total;
 }
 
-static int ds_submit_rows_impl(ds_handle* h, const ds_reads* r, const char* info, const int64_t* info_off, int32_t label, int32_t* ticket)
-{
+int ds_submit_rows(ds_handle* h, const ds_reads* r, const char* info, const int64_t* info_off, int32_t label, int32_t* ticket) try {
     if (!h || !ticket) return DS_ERR_INVALID;
     Slot* sl = nullptr;
     dsx::ExtractPlan p;
@@ -2969,10 +2908,9 @@ static int ds_submit_rows_impl(ds_handle* h, const ds_reads* r, const char* info
     h->next_slot++;
     hold(h, *sl, Ticket::Rows, p.nsites, ticket);
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
-static int64_t ds_wait_rows_impl(ds_handle* h, int32_t ticket, char* out, int64_t cap, int64_t* row_off)
-{
+int64_t ds_wait_rows(ds_handle* h, int32_t ticket, char* out, int64_t cap, int64_t* row_off) try {
     if (!h || !out) return DS_ERR_INVALID;
     Slot* sl = nullptr;
     int n = 0;
@@ -2981,13 +2919,12 @@ static int64_t ds_wait_rows_impl(ds_handle* h, int32_t ticket, char* out, int64_
     const int64_t got = collect_rows(h, *sl, n, out, cap, row_off, nullptr);
     if (got >= 0) release(*sl);       // a short buffer (or a failed copy) keeps the ticket: the wait is repeated
     return got;
-}
+} catch (...) { return abi_error(h); }
 
 // Blocking form on the idle slot, which it leaves idle: a short buffer consumes nothing the caller could come back for, the
 // call is repeated. With profiling on, the kernels and the text copy are timed.
-static int64_t ds_extract_rows_impl(ds_handle* h, const ds_reads* r, const char* info, const int64_t* info_off, int32_t label,
-                                    char* out, int64_t cap, int64_t* row_off)
-{
+int64_t ds_extract_rows(ds_handle* h, const ds_reads* r, const char* info, const int64_t* info_off, int32_t label,
+                        char* out, int64_t cap, int64_t* row_off) try {
     if (!h || !out) return DS_ERR_INVALID;
     Slot* sl = nullptr;
     int rc = idle_slot(h, "ds_extract_rows", &sl);
@@ -3007,10 +2944,9 @@ static int64_t ds_extract_rows_impl(ds_handle* h, const ds_reads* r, const char*
         h->rows_t.ms[4] += ms;
     }
     return got;
-}
+} catch (...) { return abi_error(h); }
 
-static int64_t ds_format_values_impl(ds_handle* h, int64_t n, const double* values, char* out, int64_t cap)
-{
+int64_t ds_format_values(ds_handle* h, int64_t n, const double* values, char* out, int64_t cap) try {
     if (n < 0 || (n > 0 && !values) || !out) return h ? fail(h, DS_ERR_INVALID, "ds_format_values: bad argument") : DS_ERR_INVALID;
     if (n == 0) return 0;
     if (!h) {
@@ -3037,11 +2973,10 @@ static int64_t ds_format_values_impl(ds_handle* h, int64_t n, const double* valu
     hipFree(d);
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, DS_ERR_HIP, std::string("ds_format_values: ") + hipGetErrorString(e)); }
     return total <= cap ? total : -total;
-}
+} catch (...) { return abi_error(h); }
 
 int64_t ds_extract_rows_reference(const ds_reads* r, int32_t kmer_len, int32_t signal_len, const char* info, const int64_t* info_off,
-                                  int32_t label, char* out, int64_t cap, int64_t* row_off)
-{
+                                  int32_t label, char* out, int64_t cap, int64_t* row_off) try {
     std::string err, text;
     std::vector<int64_t> off;
     int rc = out ? dsx::rows_reference(r, kmer_len, signal_len, info, info_off, label, &text, &off, &err) : DS_ERR_INVALID;
@@ -3050,31 +2985,30 @@ int64_t ds_extract_rows_reference(const ds_reads* r, int32_t kmer_len, int32_t s
     memcpy(out, text.data(), text.size());
     if (row_off) memcpy(row_off, off.data(), off.size() * 8);
     return (int64_t)text.size();
-}
+} catch (...) { return abi_error(nullptr); }
 
-int ds_get_rows_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms) { return h ? h->rows_t.get(reset, batches, ms) : DS_ERR_INVALID; }
+int ds_get_rows_times(ds_handle* h, int32_t reset, int64_t* batches, double* ms) try {
+    return h ? h->rows_t.get(reset, batches, ms) : DS_ERR_INVALID;
+} catch (...) { return abi_error(h); }
 
 int ds_extract_reference(const ds_reads* r, int32_t kmer_len, int32_t signal_len, int32_t* kmer, float* means, float* stds,
-                         float* sanums, float* signals)
-{
+                         float* sanums, float* signals) try {
     std::string err;
     int rc = dsx::reference(r, kmer_len, signal_len, kmer, means, stds, sanums, signals, &err);
     if (rc) fail(nullptr, rc, err);
     return rc;
-}
+} catch (...) { return abi_error(nullptr); }
 
-int ds_num_slots(ds_handle* h) { return h ? (int)h->slots.size() : DS_ERR_INVALID; }
+int ds_num_slots(ds_handle* h) try { return h ? (int)h->slots.size() : DS_ERR_INVALID; } catch (...) { return abi_error(h); }
 
-int ds_alloc_host(size_t bytes, void** out)
-{
+int ds_alloc_host(size_t bytes, void** out) try {
     if (!out) return DS_ERR_INVALID;
     return hipHostMalloc(out, bytes, hipHostMallocDefault) == hipSuccess ? DS_OK : DS_ERR_NOMEM;
-}
+} catch (...) { return abi_error(nullptr); }
 
-int ds_free_host(void* p) { return hipHostFree(p) == hipSuccess ? DS_OK : DS_ERR_HIP; }
+int ds_free_host(void* p) try { return hipHostFree(p) == hipSuccess ? DS_OK : DS_ERR_HIP; } catch (...) { return abi_error(nullptr); }
 
-int64_t ds_get_intermediate(ds_handle* h, const char* name, float* out, int64_t capacity)
-{
+int64_t ds_get_intermediate(ds_handle* h, const char* name, float* out, int64_t capacity) try {
     if (!h || !name || !out) return DS_ERR_INVALID;
     const int n = h->cur->last_n;
     if (n <= 0) return fail(h, DS_ERR_INVALID, "no forward has run");
@@ -3295,21 +3229,19 @@ int64_t ds_get_intermediate(ds_handle* h, const char* name, float* out, int64_t 
         return count;
     }
     return fail(h, DS_ERR_INVALID, "unknown intermediate " + s);
-}
+} catch (...) { return abi_error(h); }
 
-int ds_set_profiling(ds_handle* h, int32_t enable)
-{
+int ds_set_profiling(ds_handle* h, int32_t enable) try {
     if (!h) return DS_ERR_INVALID;
     int rc = ds_sync(h);
     h->profiling = enable < 0 ? 0 : (enable > 3 ? 3 : enable);
     return rc;
-}
+} catch (...) { return abi_error(h); }
 
-int ds_num_stages(ds_handle* h) { return h ? (int)h->stages.size() : DS_ERR_INVALID; }
+int ds_num_stages(ds_handle* h) try { return h ? (int)h->stages.size() : DS_ERR_INVALID; } catch (...) { return abi_error(h); }
 
 int ds_get_stage(ds_handle* h, int32_t index, char* name, int32_t name_cap, int32_t* launches, double* total_ms,
-                 int64_t* calls, double* flops_per_site)
-{
+                 int64_t* calls, double* flops_per_site) try {
     if (!h || index < 0 || index >= (int)h->stages.size()) return DS_ERR_INVALID;
     const Stage& S = h->stages[index];
     if (name && name_cap > 0) { strncpy(name, S.name.c_str(), name_cap - 1); name[name_cap - 1] = 0; }
@@ -3318,21 +3250,19 @@ int ds_get_stage(ds_handle* h, int32_t index, char* name, int32_t name_cap, int3
     if (calls) *calls = S.calls;
     if (flops_per_site) *flops_per_site = S.flops_per_site;
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
-int ds_reset_stage_times(ds_handle* h)
-{
+int ds_reset_stage_times(ds_handle* h) try {
     if (!h) return DS_ERR_INVALID;
     for (Stage& S : h->stages) { S.total_ms = 0; S.calls = 0; }
     for (KernelStat& K : h->kstat) K = KernelStat();
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
-int ds_num_kernels(ds_handle* h) { return h ? (int)K_COUNT : DS_ERR_INVALID; }
+int ds_num_kernels(ds_handle* h) try { return h ? (int)K_COUNT : DS_ERR_INVALID; } catch (...) { return abi_error(h); }
 
 int ds_get_kernel_stat(ds_handle* h, int32_t index, char* name, int32_t name_cap, int64_t* launches, double* total_ms,
-                       double* flops)
-{
+                       double* flops) try {
     if (!h || index < 0 || index >= K_COUNT) return DS_ERR_INVALID;
     if (name && name_cap > 0) {
         // (a DS_PRECISION_FP16X2 handle runs the two-term instantiation of every split kernel: the entry carries that name)
@@ -3344,14 +3274,13 @@ int ds_get_kernel_stat(ds_handle* h, int32_t index, char* name, int32_t name_cap
     if (total_ms) *total_ms = h->kstat[index].total_ms;
     if (flops) *flops = h->kstat[index].flops;
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
-int ds_set_graph(ds_handle* h, int32_t enable)
-{
+int ds_set_graph(ds_handle* h, int32_t enable) try {
     if (!h) return DS_ERR_INVALID;
     h->use_graph = enable != 0 && !h->shared_s1;      // DS_TUNE_SHARED_EVENT_STREAM handles always issue eagerly
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
 // ---- training (ds_train.hip: the run core and the RNN-only model, model.py:70-116 with the optimiser of train.py / denoise.py;
 // ds_train_signal.hip: the signal-only model, model.py:89-95, layers.py:80-139,176-264) ---------------------------------------------
@@ -3388,7 +3317,7 @@ static int check_train_config(ds_handle* h, const std::string& me, const ds_trai
 
 // ds_train_begin (`with_base` 0), ds_train_begin_base (which takes an is_base 1 handle too; ds_train_begin keeps refusing it) and
 // ds_train_begin_signal (`signal`). The run is created once: a re-begin at the same shape keeps its allocations.
-static int ds_train_begin_impl(ds_handle* h, const char* who, const ds_train_config* cfg, bool signal, bool with_base)
+static int train_begin(ds_handle* h, const char* who, const ds_train_config* cfg, bool signal, bool with_base)
 {
     if (!h) return DS_ERR_INVALID;
     const std::string me = who;
@@ -3415,8 +3344,19 @@ static int ds_train_begin_impl(ds_handle* h, const char* who, const ds_train_con
     return DS_OK;
 }
 
-static int ds_train_set_tensor_impl(ds_handle* h, const char* name, const float* data, int64_t count)
-{
+int ds_train_begin(ds_handle* h, const ds_train_config* cfg) try {
+    return train_begin(h, "ds_train_begin", cfg, false, false);
+} catch (...) { return abi_error(h); }
+
+int ds_train_begin_base(ds_handle* h, const ds_train_config* cfg) try {
+    return train_begin(h, "ds_train_begin", cfg, false, true);
+} catch (...) { return abi_error(h); }
+
+int ds_train_begin_signal(ds_handle* h, const ds_train_config* cfg) try {
+    return train_begin(h, "ds_train_begin_signal", cfg, true, false);
+} catch (...) { return abi_error(h); }
+
+int ds_train_set_tensor(ds_handle* h, const char* name, const float* data, int64_t count) try {
     if (!h || !name || !data) return fail(h, DS_ERR_INVALID, "ds_train_set_tensor: bad argument");
     if (!h->finalized || h->kept.empty()) return fail(h, DS_ERR_INVALID, "ds_train_set_tensor: the handle holds no trainable weights (RNN-only or signal-only, loaded)");
     // the signal-only variant: any tensor it was loaded with, moving statistics included; a BiLSTM variant: the tensors it trains
@@ -3425,12 +3365,12 @@ static int ds_train_set_tensor_impl(ds_handle* h, const char* name, const float*
     if (!known || count != (int64_t)it->second.data.size()) return fail(h, DS_ERR_INVALID, std::string("ds_train_set_tensor: unknown tensor or wrong size: ") + name);
     it->second.data.assign(data, data + count);
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
 // every step and evaluation entry (`eval`; lr unused). The entry names the buffers its variant needs: `signal` takes in.signals,
 // the BiLSTM variants in.means, in.stds, in.lens and, with the embedding trained, in.kmer.
-static int ds_train_run_impl(ds_handle* h, const char* who, bool signal, bool eval, int32_t n, const dstr::Inputs& in, float lr, float* loss, int32_t* pred,
-                             float* logits)
+static int train_run(ds_handle* h, const char* who, bool signal, bool eval, int32_t n, const dstr::Inputs& in, float lr, float* loss, int32_t* pred,
+                     float* logits)
 {
     const std::string me = who;
     if (int rc = train_ready(h, who)) return rc;
@@ -3448,8 +3388,30 @@ static int ds_train_run_impl(ds_handle* h, const char* who, bool signal, bool ev
     return rc ? fail(h, rc, me + ": " + err) : DS_OK;
 }
 
-static int ds_train_sync_weights_impl(ds_handle* h)
-{
+int ds_train_step(ds_handle* h, int32_t n, const float* means, const float* stds, const float* sanums, const int32_t* labels, float lr, float* loss,
+                  int32_t* pred) try {
+    return train_run(h, "ds_train_step", false, false, n, {nullptr, means, stds, sanums, nullptr, labels}, lr, loss, pred, nullptr);
+} catch (...) { return abi_error(h); }
+
+int ds_train_step_base(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums, const int32_t* labels,
+                       float lr, float* loss, int32_t* pred) try {
+    return train_run(h, "ds_train_step_base", false, false, n, {kmer, means, stds, sanums, nullptr, labels}, lr, loss, pred, nullptr);
+} catch (...) { return abi_error(h); }
+
+int ds_train_eval(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums, const int32_t* labels,
+                  float* loss, int32_t* pred, float* logits) try {
+    return train_run(h, "ds_train_eval", false, true, n, {kmer, means, stds, sanums, nullptr, labels}, 0.f, loss, pred, logits);
+} catch (...) { return abi_error(h); }
+
+int ds_train_step_signal(ds_handle* h, int32_t n, const float* signals, const int32_t* labels, float lr, float* loss, int32_t* pred) try {
+    return train_run(h, "ds_train_step_signal", true, false, n, {nullptr, nullptr, nullptr, nullptr, signals, labels}, lr, loss, pred, nullptr);
+} catch (...) { return abi_error(h); }
+
+int ds_train_eval_signal(ds_handle* h, int32_t n, const float* signals, const int32_t* labels, float* loss, int32_t* pred, float* logits) try {
+    return train_run(h, "ds_train_eval_signal", true, true, n, {nullptr, nullptr, nullptr, nullptr, signals, labels}, 0.f, loss, pred, logits);
+} catch (...) { return abi_error(h); }
+
+int ds_train_sync_weights(ds_handle* h) try {
     if (int rc = train_ready(h, "ds_train_sync_weights")) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     dstr::TensorMap all;      // every tensor of the run by name, a signal run's moving statistics included
@@ -3479,10 +3441,10 @@ static int ds_train_sync_weights_impl(ds_handle* h)
     }
     h->finalized = false;
     h->cur = &h->slots[0];
-    const int rc = ds_finalize_weights_impl(h);
+    const int rc = ds_finalize_weights(h);
     h->kept = std::move(loaded);
     return rc;
-}
+} catch (...) { return abi_error(h); }
 
 static int64_t train_get(ds_handle* h, const char* who, const char* name, float* out, int64_t cap, bool grad)
 {
@@ -3492,8 +3454,15 @@ static int64_t train_get(ds_handle* h, const char* who, const char* name, float*
     return rc < 0 ? fail(h, (int)rc, std::string(who) + ": " + err) : rc;
 }
 
-static int64_t ds_train_get_mask_impl(ds_handle* h, const char* stream, uint8_t* out, int64_t cap)
-{
+int64_t ds_train_get_tensor(ds_handle* h, const char* name, float* out, int64_t cap) try {
+    return train_get(h, "ds_train_get_tensor", name, out, cap, false);
+} catch (...) { return abi_error(h); }
+
+int64_t ds_train_get_grad(ds_handle* h, const char* name, float* out, int64_t cap) try {
+    return train_get(h, "ds_train_get_grad", name, out, cap, true);
+} catch (...) { return abi_error(h); }
+
+int64_t ds_train_get_mask(ds_handle* h, const char* stream, uint8_t* out, int64_t cap) try {
     if (int rc = train_ready(h, "ds_train_get_mask")) return rc;
     const int sid = dstr::stream_index(stream);
     if (sid < 0 || !out) return fail(h, DS_ERR_INVALID, std::string("ds_train_get_mask: unknown stream ") + (stream ? stream : "(null)"));
@@ -3504,103 +3473,46 @@ static int64_t ds_train_get_mask_impl(ds_handle* h, const char* stream, uint8_t*
     std::string err;
     const int64_t rc = h->train->get_mask(sid, steps, W, out, cap, &err);
     return rc < 0 ? fail(h, (int)rc, "ds_train_get_mask: " + err) : rc;
-}
+} catch (...) { return abi_error(h); }
 
-int ds_train_end(ds_handle* h)
-{
+int ds_train_end(ds_handle* h) try {
     if (!h) return DS_ERR_INVALID;
     hipSetDevice(h->cfg.device);
     delete h->train;
     h->train = nullptr;
     h->training = false;
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
-static int64_t ds_train_get_tap_impl(ds_handle* h, const char* name, float* out, int64_t cap)
-{
+int64_t ds_train_get_tap(ds_handle* h, const char* name, float* out, int64_t cap) try {
     if (int rc = train_ready(h, "ds_train_get_tap")) return rc;
     if (!h->is_cnn) return fail(h, DS_ERR_INVALID, "ds_train_get_tap: only a signal run (ds_train_begin_signal) keeps taps");
     std::string err;
     const int64_t rc = static_cast<dsts::Trainer*>(h->train)->get_tap(name, out, cap, &err);
     return rc < 0 ? fail(h, (int)rc, "ds_train_get_tap: " + err) : rc;
-}
+} catch (...) { return abi_error(h); }
 
-int ds_train_mask_reference_wide(uint64_t seed, int64_t step, const char* stream, int32_t n, int32_t width, float keep_prob, uint8_t* out)
-{
+int ds_train_mask_reference_wide(uint64_t seed, int64_t step, const char* stream, int32_t n, int32_t width, float keep_prob, uint8_t* out) try {
     const int sid = dstr::stream_index(stream);
     if ((sid != dstr::STREAM_FC1 && sid != dstr::STREAM_FC2) || n < 0 || width < 1 || width > dsts::MAX_JOINT || !out || !(keep_prob > 0.f && keep_prob <= 1.f))
         return DS_ERR_INVALID;
     dstr::mask_reference(seed, step, sid, n, 1, width, keep_prob, out);
     return DS_OK;
-}
+} catch (...) { return abi_error(nullptr); }
 
-int ds_train_mask_reference(uint64_t seed, int64_t step, const char* stream, int32_t n, int32_t kmer_len, float keep_prob, uint8_t* out)
-{
+int ds_train_mask_reference(uint64_t seed, int64_t step, const char* stream, int32_t n, int32_t kmer_len, float keep_prob, uint8_t* out) try {
     const int sid = dstr::stream_index(stream);
     if (sid < 0 || n < 0 || kmer_len < 1 || !out || !(keep_prob > 0.f && keep_prob <= 1.f)) return DS_ERR_INVALID;
     dstr::mask_reference(seed, step, sid, n, sid < dstr::STREAM_FC1 ? kmer_len : 1, dstr::stream_width(sid), keep_prob, out);
     return DS_OK;
-}
+} catch (...) { return abi_error(nullptr); }
 
-int ds_get_train_times(ds_handle* h, int32_t reset, int64_t* steps, double* ms)
-{
+int ds_get_train_times(ds_handle* h, int32_t reset, int64_t* steps, double* ms) try {
     if (!h || !steps || !ms) return DS_ERR_INVALID;
     *steps = h->train ? h->train->steps_timed : 0;
     for (int i = 0; i < dstr::NPHASE; ++i) ms[i] = h->train ? h->train->ms[i] : 0.0;
     if (reset && h->train) { h->train->steps_timed = 0; for (double& v : h->train->ms) v = 0; }
     return DS_OK;
-}
+} catch (...) { return abi_error(h); }
 
-int ds_train_begin_signal(ds_handle* h, const ds_train_config* cfg) { return guarded(h, [&] { return ds_train_begin_impl(h, "ds_train_begin_signal", cfg, true, false); }); }
-int ds_train_step_signal(ds_handle* h, int32_t n, const float* signals, const int32_t* labels, float lr, float* loss, int32_t* pred) { return guarded(h, [&] { return ds_train_run_impl(h, "ds_train_step_signal", true, false, n, {nullptr, nullptr, nullptr, nullptr, signals, labels}, lr, loss, pred, nullptr); }); }
-int ds_train_eval_signal(ds_handle* h, int32_t n, const float* signals, const int32_t* labels, float* loss, int32_t* pred, float* logits) { return guarded(h, [&] { return ds_train_run_impl(h, "ds_train_eval_signal", true, true, n, {nullptr, nullptr, nullptr, nullptr, signals, labels}, 0.f, loss, pred, logits); }); }
-int64_t ds_train_get_tap(ds_handle* h, const char* name, float* out, int64_t cap) { return guarded(h, [&] { return ds_train_get_tap_impl(h, name, out, cap); }); }
-int ds_train_begin(ds_handle* h, const ds_train_config* cfg) { return guarded(h, [&] { return ds_train_begin_impl(h, "ds_train_begin", cfg, false, false); }); }
-int ds_train_begin_base(ds_handle* h, const ds_train_config* cfg) { return guarded(h, [&] { return ds_train_begin_impl(h, "ds_train_begin", cfg, false, true); }); }
-int ds_train_step_base(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums, const int32_t* labels, float lr, float* loss, int32_t* pred) { return guarded(h, [&] { return ds_train_run_impl(h, "ds_train_step_base", false, false, n, {kmer, means, stds, sanums, nullptr, labels}, lr, loss, pred, nullptr); }); }
-int ds_train_eval(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums, const int32_t* labels, float* loss, int32_t* pred, float* logits) { return guarded(h, [&] { return ds_train_run_impl(h, "ds_train_eval", false, true, n, {kmer, means, stds, sanums, nullptr, labels}, 0.f, loss, pred, logits); }); }
-int ds_train_set_tensor(ds_handle* h, const char* name, const float* data, int64_t count) { return guarded(h, [&] { return ds_train_set_tensor_impl(h, name, data, count); }); }
-int ds_train_step(ds_handle* h, int32_t n, const float* means, const float* stds, const float* sanums, const int32_t* labels, float lr, float* loss, int32_t* pred) { return guarded(h, [&] { return ds_train_run_impl(h, "ds_train_step", false, false, n, {nullptr, means, stds, sanums, nullptr, labels}, lr, loss, pred, nullptr); }); }
-int ds_train_sync_weights(ds_handle* h) { return guarded(h, [&] { return ds_train_sync_weights_impl(h); }); }
-int64_t ds_train_get_tensor(ds_handle* h, const char* name, float* out, int64_t cap) { return guarded(h, [&] { return train_get(h, "ds_train_get_tensor", name, out, cap, false); }); }
-int64_t ds_train_get_grad(ds_handle* h, const char* name, float* out, int64_t cap) { return guarded(h, [&] { return train_get(h, "ds_train_get_grad", name, out, cap, true); }); }
-int64_t ds_train_get_mask(ds_handle* h, const char* stream, uint8_t* out, int64_t cap) { return guarded(h, [&] { return ds_train_get_mask_impl(h, stream, out, cap); }); }
-
-int ds_create(const ds_config* cfg, ds_handle** out) { return guarded(nullptr, [&] { return ds_create_impl(cfg, out); }); }
-int ds_set_tensor(ds_handle* h, const char* name, const float* data, const int64_t* shape, int32_t ndim) { return guarded(h, [&] { return ds_set_tensor_impl(h, name, data, shape, ndim); }); }
-int ds_finalize_weights(ds_handle* h) { return guarded(h, [&] { return ds_finalize_weights_impl(h); }); }
-int ds_load_weights(ds_handle* h, const char* path) { return guarded(h, [&] { return ds_load_weights_impl(h, path); }); }
-int ds_forward_device(ds_handle* h, int32_t n, const int32_t* d_kmer, const float* d_means, const float* d_stds, const float* d_sanums, const float* d_signals, float* d_act, int32_t* d_pred) { return guarded(h, [&] { return ds_forward_device_impl(h, n, d_kmer, d_means, d_stds, d_sanums, d_signals, d_act, d_pred); }); }
-int ds_forward(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums, const float* signals, float* act, int32_t* pred) { return guarded(h, [&] { return ds_forward_impl(h, n, kmer, means, stds, sanums, signals, act, pred); }); }
-int ds_submit(ds_handle* h, int32_t n, const int32_t* kmer, const float* means, const float* stds, const float* sanums, const float* signals, int32_t* ticket) { return guarded(h, [&] { return ds_submit_impl(h, n, kmer, means, stds, sanums, signals, ticket); }); }
-int ds_submit_parts(ds_handle* h, int32_t nparts, const int32_t* counts, const int32_t* const* kmer, const float* const* means, const float* const* stds, const float* const* sanums, const float* const* signals, int32_t* ticket) { return guarded(h, [&] { return ds_submit_parts_impl(h, nparts, counts, kmer, means, stds, sanums, signals, ticket); }); }
-int ds_wait(ds_handle* h, int32_t ticket, float* act, int32_t* pred) { return guarded(h, [&] { return ds_wait_impl(h, ticket, act, pred); }); }
-int ds_extract(ds_handle* h, const ds_reads* reads, int32_t* kmer, float* means, float* stds, float* sanums, float* signals) { return guarded(h, [&] { return ds_extract_impl(h, reads, kmer, means, stds, sanums, signals); }); }
-int ds_submit_reads(ds_handle* h, const ds_reads* reads, int32_t* ticket) { return guarded(h, [&] { return ds_submit_reads_impl(h, reads, ticket); }); }
-int ds_submit_rows(ds_handle* h, const ds_reads* reads, const char* info, const int64_t* info_off, int32_t label, int32_t* ticket) { return guarded(h, [&] { return ds_submit_rows_impl(h, reads, info, info_off, label, ticket); }); }
-int64_t ds_wait_rows(ds_handle* h, int32_t ticket, char* out, int64_t cap, int64_t* row_off) { return guarded(h, [&] { return ds_wait_rows_impl(h, ticket, out, cap, row_off); }); }
-int64_t ds_extract_rows(ds_handle* h, const ds_reads* reads, const char* info, const int64_t* info_off, int32_t label, char* out, int64_t cap, int64_t* row_off) { return guarded(h, [&] { return ds_extract_rows_impl(h, reads, info, info_off, label, out, cap, row_off); }); }
-int ds_set_recheck(ds_handle* coarse, ds_handle* fine, float margin) { return guarded(coarse, [&] { return ds_set_recheck_impl(coarse, fine, margin); }); }
-int ds_recheck_select(ds_handle* h, int32_t n, const float* act, float margin, int32_t* count, int32_t* index) { return guarded(h, [&] { return ds_recheck_select_impl(h, n, act, margin, count, index); }); }
-int64_t ds_format_values(ds_handle* h, int64_t n, const double* values, char* out, int64_t cap) { return guarded(h, [&] { return ds_format_values_impl(h, n, values, out, cap); }); }
-int ds_freq_begin_stream(ds_handle* h, int64_t initial_slots, int32_t batch_rows, double prob_cf) { return guarded(h, [&] { return ds_freq_begin_stream_impl(h, initial_slots, batch_rows, prob_cf); }); }
-int ds_freq_push(ds_handle* h, int32_t nrows, const int32_t* chrom, const int64_t* pos, const float* act, int32_t class_num, const int32_t* pred, int32_t* status, int32_t* opened) { return guarded(h, [&] { return ds_freq_push_impl(h, nrows, chrom, pos, act, class_num, pred, status, opened); }); }
-int ds_freq_values(ds_handle* h, int64_t n, const float* act, int32_t class_num, double* p0, double* p1, int32_t* status) { return guarded(h, [&] { return ds_freq_values_impl(h, n, act, class_num, p0, p1, status); }); }
-int ds_freq_begin(ds_handle* h, int64_t total_rows, int32_t batch_rows, double prob_cf) { return guarded(h, [&] { return ds_freq_begin_impl(h, total_rows, batch_rows, prob_cf); }); }
-int ds_freq_parse(ds_handle* h, const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, const int32_t* chrom, const uint8_t* flags, int32_t* status) { return guarded(h, [&] { return ds_freq_parse_impl(h, text, nrows, row_begin, row_end, chrom, flags, status); }); }
-int ds_freq_accumulate(ds_handle* h, int32_t nover, const int32_t* row, const int32_t* chrom, const int64_t* pos, const double* p0, const double* p1, const int32_t* met) { return guarded(h, [&] { return ds_freq_accumulate_impl(h, nover, row, chrom, pos, p0, p1, met); }); }
-int64_t ds_freq_result(ds_handle* h, int64_t cap, int64_t* first_row, int32_t* chrom, int64_t* pos, double* sum0, double* sum1, int32_t* met, int32_t* unmet, int64_t* rows, int64_t* used) { return guarded(h, [&] { return ds_freq_result_impl(h, cap, first_row, chrom, pos, sum0, sum1, met, unmet, rows, used); }); }
-int ds_eval_begin(ds_handle* h, int64_t total_rows, int32_t batch_rows, int32_t ncf, const double* cf) { return guarded(h, [&] { return ds_eval_begin_impl(h, total_rows, batch_rows, ncf, cf); }); }
-int ds_eval_parse(ds_handle* h, const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, const uint8_t* flags, int32_t* status) { return guarded(h, [&] { return ds_eval_parse_impl(h, text, nrows, row_begin, row_end, flags, status); }); }
-int ds_eval_accumulate(ds_handle* h, const uint8_t* mask, int32_t nover, const int32_t* row, const double* p0, const double* p1, const int32_t* called) { return guarded(h, [&] { return ds_eval_accumulate_impl(h, mask, nover, row, p0, p1, called); }); }
-int ds_eval_result(ds_handle* h, int64_t* counts, uint64_t* u2, int64_t* pn, int64_t* nn, int64_t* rows, int64_t* distinct) { return guarded(h, [&] { return ds_eval_result_impl(h, counts, u2, pn, nn, rows, distinct); }); }
-int ds_combine_begin(ds_handle* h, int32_t form, int32_t nrec, const int64_t* rec_len, int64_t total_rows, int32_t batch_rows) { return guarded(h, [&] { return ds_combine_begin_impl(h, form, nrec, rec_len, total_rows, batch_rows); }); }
-int ds_combine_genome(ds_handle* h, const char* text, int64_t nseg, const int64_t* seg_begin, const int64_t* seg_end, const int64_t* seg_bit, const uint8_t* seg_carry) { return guarded(h, [&] { return ds_combine_genome_impl(h, text, nseg, seg_begin, seg_end, seg_bit, seg_carry); }); }
-int ds_combine_bitmap(ds_handle* h, int64_t cap_words, uint32_t* bitmap) { return guarded(h, [&] { return ds_combine_bitmap_impl(h, cap_words, bitmap); }); }
-int ds_combine_parse(ds_handle* h, const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, const int32_t* chrom, const uint8_t* flags, int32_t* status) { return guarded(h, [&] { return ds_combine_parse_impl(h, text, nrows, row_begin, row_end, chrom, flags, status); }); }
-int ds_combine_accumulate(ds_handle* h, int32_t nover, const int32_t* row, const int32_t* status, const int32_t* chrom, const int64_t* pos, const int32_t* plus, const double* a, const double* b, const int64_t* met, const int64_t* unmet, const int64_t* cov) { return guarded(h, [&] { return ds_combine_accumulate_impl(h, nover, row, status, chrom, pos, plus, a, b, met, unmet, cov); }); }
-int64_t ds_combine_result(ds_handle* h, int64_t cap, int32_t* chrom, int64_t* pos, double* sum0, double* sum1, int64_t* met, int64_t* unmet, int64_t* cov, int64_t* last_plus, int64_t* rows) { return guarded(h, [&] { return ds_combine_result_impl(h, cap, chrom, pos, sum0, sum1, met, unmet, cov, last_plus, rows); }); }
-int ds_submit_text(ds_handle* h, const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, int32_t* ticket) { return guarded(h, [&] { return ds_submit_text_impl(h, text, nrows, row_begin, row_end, ticket); }); }
-int ds_wait_text(ds_handle* h, int32_t ticket, float* act, int32_t* pred, int32_t* kmer, int32_t* labels, char* info, int64_t info_cap, int64_t* info_off) { return guarded(h, [&] { return ds_wait_text_impl(h, ticket, act, pred, kmer, labels, info, info_cap, info_off); }); }
-int ds_parse_text(ds_handle* h, const char* text, int32_t nrows, const int64_t* row_begin, const int64_t* row_end, int32_t* kmer, float* means, float* stds, float* lens, float* signals, int32_t* labels, int32_t* info_len, int32_t* status) { return guarded(h, [&] { return ds_parse_text_impl(h, text, nrows, row_begin, row_end, kmer, means, stds, lens, signals, labels, info_len, status); }); }
 }  // extern "C"

@@ -10,6 +10,7 @@
 //     shortest round-trip text numpy's str(np.float32) prints.
 // Host-only code (no HIP); compiled into libdeepsignal_hip.so.
 #include "../../include/deepsignal_hip.h"
+#include "ds_abi.h"
 #include "ds_dec_token.h"
 
 #include <algorithm>
@@ -21,6 +22,7 @@
 #include <cstdlib>
 #include <condition_variable>
 #include <cstring>
+#include <exception>
 #include <functional>
 #include <mutex>
 #include <string>
@@ -45,29 +47,36 @@ struct ds_team {
     uint64_t gen = 0;
     int want = 0, running = 0;       // helpers asked to run this generation / still running it
     bool stop = false;
+    std::exception_ptr error;        // the first exception this generation's job threw, on a helper or on the caller
     explicit ds_team(int helpers)
     {
-        for (int i = 0; i < helpers; ++i)
-            th.emplace_back([this, i] {
-                uint64_t seen = 0;
-                for (;;) {
-                    const std::function<void()>* j;
-                    {
-                        std::unique_lock<std::mutex> lk(m);
-                        cv_go.wait(lk, [&] { return stop || (gen != seen && i < want); });
-                        if (stop) return;
-                        seen = gen;
-                        j = job;
+        try {
+            for (int i = 0; i < helpers; ++i)
+                th.emplace_back([this, i] {
+                    uint64_t seen = 0;
+                    for (;;) {
+                        const std::function<void()>* j;
+                        {
+                            std::unique_lock<std::mutex> lk(m);
+                            cv_go.wait(lk, [&] { return stop || (gen != seen && i < want); });
+                            if (stop) return;
+                            seen = gen;
+                            j = job;
+                        }
+                        attempt(*j);
+                        {
+                            std::lock_guard<std::mutex> lk(m);
+                            if (--running == 0) cv_done.notify_one();
+                        }
                     }
-                    (*j)();
-                    {
-                        std::lock_guard<std::mutex> lk(m);
-                        if (--running == 0) cv_done.notify_one();
-                    }
-                }
-            });
+                });
+        } catch (...) {          // a thread that did not start: the ones that did are joinable and must not be destroyed so
+            shut_down();
+            throw;
+        }
     }
-    // run `f` on the caller and on up to `helpers` team threads; returns when all of them are done
+    // Run `f` on the caller and on up to `helpers` team threads; returns when all of them are done. What `f` throws, on
+    // whichever thread, leaves here on the caller, and only then: `f` and what it refers to live until the last helper is back.
     void run(int helpers, const std::function<void()>& f)
     {
         helpers = std::min<int>(helpers, (int)th.size());
@@ -76,14 +85,29 @@ struct ds_team {
             job = &f; want = helpers; running = helpers; ++gen;
         }
         if (helpers > 0) cv_go.notify_all();
-        f();
-        if (helpers > 0) {
+        attempt(f);
+        std::exception_ptr e;
+        {
             std::unique_lock<std::mutex> lk(m);
             cv_done.wait(lk, [&] { return running == 0; });
             want = 0;
+            std::swap(e, error);
+        }
+        if (e) std::rethrow_exception(e);
+    }
+    ~ds_team() { shut_down(); }
+
+private:
+    void attempt(const std::function<void()>& f) noexcept
+    {
+        try {
+            f();
+        } catch (...) {          // (a std::mutex::lock that throws here would terminate: accepted, as for every other lock of the team)
+            std::lock_guard<std::mutex> lk(m);
+            if (!error) error = std::current_exception();
         }
     }
-    ~ds_team()
+    void shut_down() noexcept
     {
         {
             std::lock_guard<std::mutex> lk(m);
@@ -409,10 +433,12 @@ bool parse_row_host(int kmer_len, int signal_len, const char* b, const char* e, 
 }
 }  // namespace ds_io
 
+// the handler every int / int64_t entry point below ends in (ds_abi.h); the entries without a reader have no error text
+static int abi_error(ds_tsv* t) noexcept { return ds_abi::caught(t ? &t->err : nullptr); }
+
 extern "C" {
 
-int ds_tsv_open(const char* path, int32_t kmer_len, int32_t signal_len, int32_t nthreads, ds_tsv** out)
-{
+int ds_tsv_open(const char* path, int32_t kmer_len, int32_t signal_len, int32_t nthreads, ds_tsv** out) try {
     if (!path || !out || kmer_len < 1 || signal_len < 1) return DS_ERR_INVALID;
     *out = nullptr;
     ds_tsv* t = new ds_tsv();
@@ -432,24 +458,22 @@ int ds_tsv_open(const char* path, int32_t kmer_len, int32_t signal_len, int32_t 
     t->limit = t->size;
     *out = t;
     return DS_OK;
-}
+} catch (...) { return abi_error(nullptr); }
 
-void ds_tsv_close(ds_tsv* t)
-{
+void ds_tsv_close(ds_tsv* t) try {
     if (!t) return;
     delete t->team;
     if (t->data) munmap((void*)t->data, t->size);
     if (t->fd >= 0) close(t->fd);
     delete t;
-}
+} catch (...) {}
 
 const char* ds_tsv_error(const ds_tsv* t) { return t ? t->err.c_str() : "null reader"; }
 
 // Locate (not parse) the rows of the next queue item: all rows of the next `max_reads` reads (a read = maximal run of
 // consecutive rows with the same column 5). Returns their number (0 at end of file, negative on a row with fewer than five
 // columns); ds_tsv_parse_into() parses them.
-int64_t ds_tsv_locate(ds_tsv* t, int32_t max_reads)
-{
+int64_t ds_tsv_locate(ds_tsv* t, int32_t max_reads) try {
     if (!t || max_reads < 1) return DS_ERR_INVALID;
     if (!t->lines.empty()) {      // exactly one ds_tsv_parse_into() per successful ds_tsv_locate(): a second locate would drop the item
         t->err = "ds_tsv_locate: the rows of the previous ds_tsv_locate() have not been parsed (ds_tsv_parse_into), or their parse failed";
@@ -488,14 +512,13 @@ int64_t ds_tsv_locate(ds_tsv* t, int32_t max_reads)
     t->pos = t->pend_head < t->pend.size() ? (size_t)(t->pend[t->pend_head].first - t->data) : t->scanned;
     if (t->pos > item_begin) t->scan_bytes = std::max<size_t>(1u << 20, (t->pos - item_begin) + (t->pos - item_begin) / 4);
     return (int64_t)t->lines.size();
-}
+} catch (...) { return abi_error(t); }
 
 // Parse the rows ds_tsv_locate() found into the CALLER's arrays (kmer int32[n,kmer_len], means / stds / lens
 // float[n,kmer_len], signals float[n,signal_len], labels int32[n]) on the team; the six sampleinfo columns go to the
 // reader's own buffer (ds_tsv_info / ds_tsv_info_offsets). Returns n, or a negative code on a malformed row.
 int64_t ds_tsv_parse_into(ds_tsv* t, int64_t capacity_rows, int32_t* kmer, float* means, float* stds, float* lens, float* signals,
-                          int32_t* labels)
-{
+                          int32_t* labels) try {
     if (!t) return DS_ERR_INVALID;
     const size_t n = t->lines.size();
     if (n == 0) return 0;
@@ -543,26 +566,24 @@ int64_t ds_tsv_parse_into(ds_tsv* t, int64_t capacity_rows, int32_t* kmer, float
     t->line_no += (int64_t)n;
     t->lines.clear();
     return (int64_t)n;
-}
+} catch (...) { return abi_error(t); }
 
 // Next queue item: all rows of the next `max_reads` reads (a read = maximal run of consecutive rows with the
 // same column 5), parsed into the reader's own arrays (the ds_tsv_kmer ... accessors). Returns the number of sites, 0 at
 // end of file, negative on a malformed row.
-int64_t ds_tsv_next(ds_tsv* t, int32_t max_reads)
-{
+int64_t ds_tsv_next(ds_tsv* t, int32_t max_reads) try {
     const int64_t n = ds_tsv_locate(t, max_reads);
     if (n <= 0) return n;
     const size_t K = (size_t)t->kmer_len, S = (size_t)t->signal_len, m = (size_t)n;
     t->kmer.resize(m * K); t->means.resize(m * K); t->stds.resize(m * K); t->lens.resize(m * K);
     t->signals.resize(m * S); t->labels.resize(m);
     return ds_tsv_parse_into(t, n, t->kmer.data(), t->means.data(), t->stds.data(), t->lens.data(), t->signals.data(), t->labels.data());
-}
+} catch (...) { return abi_error(t); }
 
 // The other consumer of a located item (call_mods --parse_on gpu): hand the rows out as byte spans of the mapped file
 // (ds_tsv_data) instead of parsing them. Like ds_tsv_parse_into it is the one consumer of its ds_tsv_locate() and advances the
 // row count that error messages name.
-int64_t ds_tsv_take_lines(ds_tsv* t, int64_t capacity_rows, int64_t* begin, int64_t* end)
-{
+int64_t ds_tsv_take_lines(ds_tsv* t, int64_t capacity_rows, int64_t* begin, int64_t* end) try {
     if (!t) return DS_ERR_INVALID;
     const size_t n = t->lines.size();
     if (n == 0) return 0;
@@ -578,18 +599,17 @@ int64_t ds_tsv_take_lines(ds_tsv* t, int64_t capacity_rows, int64_t* begin, int6
     t->line_no += (int64_t)n;
     t->lines.clear();
     return (int64_t)n;
-}
+} catch (...) { return abi_error(t); }
 
 const char* ds_tsv_data(const ds_tsv* t) { return t ? t->data : nullptr; }
 
-int64_t ds_tsv_size(const ds_tsv* t) { return t ? (int64_t)t->size : DS_ERR_INVALID; }
+int64_t ds_tsv_size(const ds_tsv* t) try { return t ? (int64_t)t->size : DS_ERR_INVALID; } catch (...) { return abi_error(nullptr); }
 
 // First read boundary at or after byte `pos`: the start of the first line that begins at or after `pos` and whose
 // read id (column 5) differs from the line before it -- so [align(a), align(b)) always holds whole reads, and the
 // ranges of consecutive nominal offsets tile the file exactly. 0 stays 0; returns the file size when no boundary
 // follows. A function of the file alone: every rank computes the same cut points without talking to the others.
-int64_t ds_tsv_align(const ds_tsv* t, int64_t pos)
-{
+int64_t ds_tsv_align(const ds_tsv* t, int64_t pos) try {
     if (!t || pos < 0) return DS_ERR_INVALID;
     if (pos == 0) return 0;
     if ((size_t)pos >= t->size) return (int64_t)t->size;
@@ -622,11 +642,10 @@ int64_t ds_tsv_align(const ds_tsv* t, int64_t pos)
         p = nl ? nl + 1 : end;
     }
     return (int64_t)t->size;
-}
+} catch (...) { return abi_error(nullptr); }
 
 // Restrict the reader to the byte range [begin, end) (both from ds_tsv_align) and rewind to its start.
-int ds_tsv_set_range(ds_tsv* t, int64_t begin, int64_t end)
-{
+int ds_tsv_set_range(ds_tsv* t, int64_t begin, int64_t end) try {
     if (!t || begin < 0 || end < begin || (size_t)end > t->size) return DS_ERR_INVALID;
     t->pos = (size_t)begin;
     t->limit = (size_t)end;
@@ -636,7 +655,7 @@ int ds_tsv_set_range(ds_tsv* t, int64_t begin, int64_t end)
     t->line_no = 0;
     t->err.clear();
     return DS_OK;
-}
+} catch (...) { return abi_error(t); }
 
 const int32_t* ds_tsv_kmer(const ds_tsv* t) { return t->kmer.data(); }
 const float* ds_tsv_means(const ds_tsv* t) { return t->means.data(); }
@@ -650,8 +669,7 @@ const int64_t* ds_tsv_info_offsets(const ds_tsv* t) { return t->info_off.data();
 // Result rows of one batch (call_modifications.py:183-190). Returns bytes written (each row ends with '\n'),
 // or -(needed bytes) when `cap` is too small.
 int64_t ds_format_rows(int64_t n, const char* info, const int64_t* info_off, const float* act, int32_t class_num,
-                       const int32_t* pred, const int32_t* kmer, int32_t kmer_len, char* out, int64_t cap)
-{
+                       const int32_t* pred, const int32_t* kmer, int32_t kmer_len, char* out, int64_t cap) try {
     if (n < 0 || !info || !info_off || !act || !pred || !kmer || !out || class_num < 2) return DS_ERR_INVALID;
     const int64_t need = info_off[n] + n * (int64_t)(2 * 20 + 16 + kmer_len + 8);
     if (need > cap) return -need;
@@ -671,7 +689,7 @@ int64_t ds_format_rows(int64_t n, const char* info, const int64_t* info_off, con
         *p++ = '\n';
     }
     return (int64_t)(p - out);
-}
+} catch (...) { return abi_error(nullptr); }
 
 
 // CRC-32C, slicing-by-8 (tables built on first use). TF checkpoint tensors / table blocks carry it masked.
@@ -712,8 +730,7 @@ uint32_t ds_crc32c(const void* data, size_t n, uint32_t crc)
 // from its raw bytes -- blank, first or last byte whitespace (str.strip's ASCII set), any byte >= 0x80, any '\r' (universal
 // newlines end a line there) -- gets flag 1 and chromosome -1: the Python parser takes it, and its column 0 names no chromosome here.
 int64_t ds_freq_locate(const char* text, int64_t nbytes, int64_t cap_rows, int64_t* row_begin, int64_t* row_end, int32_t* chrom,
-                       uint8_t* flags, char* names, int64_t names_cap, int64_t* names_bytes, int32_t* n_names)
-{
+                       uint8_t* flags, char* names, int64_t names_cap, int64_t* names_bytes, int32_t* n_names) try {
     if (nbytes < 0 || (nbytes > 0 && !text) || cap_rows < 0 || names_cap < 0 || !names_bytes || !n_names ||
         (cap_rows > 0 && (!row_begin || !row_end || !chrom || !flags)) || (names_cap > 0 && !names))
         return DS_ERR_INVALID;
@@ -769,7 +786,7 @@ int64_t ds_freq_locate(const char* text, int64_t nbytes, int64_t cap_rows, int64
     *names_bytes = nb;
     *n_names = (int32_t)table.size();
     return nrows;
-}
+} catch (...) { return abi_error(nullptr); }
 
 // The keys of call_mods --freq_file: the rows are not text yet, each is its sampleinfo [info_off[i], info_off[i + 1]) -- chrom \t pos \t
 // strand \t pos_in_strand \t readname \t read_strand -- and the row call_mods prints starts with those bytes. Column 0 goes through the
@@ -778,8 +795,7 @@ int64_t ds_freq_locate(const char* text, int64_t nbytes, int64_t cap_rows, int64
 // differently (empty, first or last byte whitespace, a byte >= 0x80, a '\r' or '\n'), for any number of columns but six, and for a position
 // that is not 1 .. 13 digits below 2^40.
 int64_t ds_freq_keys(int64_t n, const char* info, const int64_t* info_off, int32_t* chrom, int64_t* pos, uint8_t* flags, char* names,
-                     int64_t names_cap, int64_t* names_bytes, int32_t* n_names)
-{
+                     int64_t names_cap, int64_t* names_bytes, int32_t* n_names) try {
     if (n < 0 || names_cap < 0 || !names_bytes || !n_names || (n > 0 && (!info || !info_off || !chrom || !pos || !flags)) ||
         (names_cap > 0 && !names))
         return DS_ERR_INVALID;
@@ -843,7 +859,7 @@ int64_t ds_freq_keys(int64_t n, const char* info, const int64_t* info_off, int32
     *names_bytes = nb;
     *n_names = (int32_t)table.size();
     return n;
-}
+} catch (...) { return abi_error(nullptr); }
 
 // The host half of combine_strands --on gpu (ds_combine.hip): one pass over a FASTA buffer as Python's text layer reads it. A line
 // is what lies between two '\n' (a last line needs none; the '\r' of a "\r\n" goes with what strip() removes). A line whose first raw
@@ -854,8 +870,7 @@ int64_t ds_freq_keys(int64_t n, const char* info, const int64_t* info_off, int32
 // their capacities and *n_recs is the number of records (>= 1): call again with room when short.
 int64_t ds_fasta_locate(const char* text, int64_t nbytes, int64_t cap_lines, int64_t* line_begin, int64_t* line_end, int32_t* line_rec,
                         int64_t* line_off, int64_t cap_recs, int64_t* name_begin, int64_t* name_end, int64_t* rec_len, int64_t* n_recs,
-                        int32_t* flags)
-{
+                        int32_t* flags) try {
     if (nbytes < 0 || (nbytes > 0 && !text) || cap_lines < 0 || cap_recs < 0 || !n_recs || !flags ||
         (cap_lines > 0 && (!line_begin || !line_end || !line_rec || !line_off)) || (cap_recs > 0 && (!name_begin || !name_end || !rec_len)))
         return DS_ERR_INVALID;
@@ -904,15 +919,14 @@ int64_t ds_fasta_locate(const char* text, int64_t nbytes, int64_t cap_lines, int
     *n_recs = nrec;
     *flags = fl;
     return nlines;
-}
+} catch (...) { return abi_error(nullptr); }
 
 // The host half of evaluate --on gpu (ds_eval.hip): the rows of a call_mods result buffer -- what lies between two '\n'; a last row
 // needs none -- for a reader that cuts a row with line.rstrip().split(). Flag 1: Python would tokenise or decode the row differently
 // from "fields separated by runs of space or tab" -- a byte >= 0x80, one of the other bytes str.split() takes for whitespace ('\r',
 // 0x0b, 0x0c, 0x1c .. 0x1f), or a blank row. Blanks in front and behind are plain. *file_flags bit 0: the buffer holds a '\r' that
 // neither a '\n' nor the end of the buffer follows -- a line end of its own in Python's text mode, which these rows do not show.
-int64_t ds_eval_locate(const char* text, int64_t nbytes, int64_t cap_rows, int64_t* row_begin, int64_t* row_end, uint8_t* flags, int32_t* file_flags)
-{
+int64_t ds_eval_locate(const char* text, int64_t nbytes, int64_t cap_rows, int64_t* row_begin, int64_t* row_end, uint8_t* flags, int32_t* file_flags) try {
     if (nbytes < 0 || (nbytes > 0 && !text) || cap_rows < 0 || !file_flags || (cap_rows > 0 && (!row_begin || !row_end || !flags))) return DS_ERR_INVALID;
     int64_t nrows = 0;
     int32_t ff = 0;
@@ -939,6 +953,6 @@ int64_t ds_eval_locate(const char* text, int64_t nbytes, int64_t cap_rows, int64
     }
     *file_flags = ff;
     return nrows;
-}
+} catch (...) { return abi_error(nullptr); }
 
 }  // extern "C"

@@ -658,6 +658,7 @@ def load_library() -> ctypes.CDLL:
     lib.ds_submit.argtypes = [vp, i32, vp, vp, vp, vp, vp, ctypes.POINTER(i32)]
     lib.ds_submit_parts.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, ctypes.POINTER(i32)]
     lib.ds_wait.argtypes = [vp, i32, vp, vp]
+    lib.ds_num_slots.argtypes = [vp]
     lib.ds_alloc_host.argtypes = [ctypes.c_size_t, ctypes.POINTER(vp)]
     lib.ds_free_host.argtypes = [vp]
     lib.ds_get_intermediate.argtypes = [vp, ctypes.c_char_p, vp, i64]
@@ -865,7 +866,6 @@ class Engine:
             self._h = ctypes.c_void_p()
             raise RuntimeError("ds_create failed (%d): %s" % (rc, msg))
         self.kmer_len, self.signal_len, self.class_num = kmer_len, signal_len, class_num
-        self._lib.ds_num_slots.argtypes = [ctypes.c_void_p]
         self._slots = int(self._lib.ds_num_slots(self._h))
         self.device, self.max_batch = device, max_batch
         self.is_base = bool(is_base)

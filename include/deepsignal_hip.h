@@ -10,6 +10,12 @@
  * sizes only; no torch / TensorFlow types. All functions return 0 on success or a negative
  * DS_ERR_* code; ds_last_error() gives the message. A handle is driven by one host thread at a
  * time; different handles (one per GPU) may be driven concurrently.
+ *
+ * No entry point throws. Every function that returns int or int64_t catches whatever its body raises and reports it as a
+ * code: DS_ERR_NOMEM "out of host memory" for std::bad_alloc, DS_ERR_INVALID "internal error[: what()]" for anything else
+ * (the text is the handle's or reader's last error; the entries without one return the code alone). The void functions
+ * swallow, the pointer-returning ones allocate nothing. After DS_ERR_NOMEM, or an "internal error", the object (ds_handle,
+ * ds_tsv) may be destroyed / closed and nothing else is promised for it.
  */
 #ifndef DEEPSIGNAL_HIP_H
 #define DEEPSIGNAL_HIP_H

@@ -1,12 +1,12 @@
 """Which build a profile belongs to, recorded AT COLLECTION TIME on the GPU box (which has no .git): the commit the snapshot was
 taken from -- written into build/COMMIT by tools/stamp_commit.sh before the gpurun call -- and a hash of the kernel / engine
 sources as they lie in the snapshot, which anyone can recompute from the repository at that commit
-(sha256 over ds_kernels.hip, ds_split.hip, ds_engine.cpp, ds_io.cpp, ds_internal.h, ds_device.h in this order, first 16 hex digits)."""
+(sha256 over ds_kernels.hip, ds_split.hip, ds_engine.cpp, ds_io.cpp, ds_internal.h, ds_device.h, ds_abi.h in this order, first 16 hex digits)."""
 import hashlib
 import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ("ds_kernels.hip", "ds_split.hip", "ds_engine.cpp", "ds_io.cpp", "ds_internal.h", "ds_device.h")
+SOURCES = ("ds_kernels.hip", "ds_split.hip", "ds_engine.cpp", "ds_io.cpp", "ds_internal.h", "ds_device.h", "ds_abi.h")
 
 
 def sources_sha16():
